@@ -78,14 +78,14 @@ $(OBJDIR)/%.o: $(CSRC)/%.cpp $(HIP_HDR)
 
 # The wave-cooperative ragged multiply keeps loads outside the compiler's books (inline-assembly loads into a reserved
 # v127, hand-counted waits): the generated code is checked wherever the library is compiled, and a finding fails the build.
-$(OBJDIR)/csgn_mul.s: $(CSRC)/csgn_mul.hip $(HIP_HDR)
+$(OBJDIR)/csgn_mul.device.s: $(CSRC)/csgn_mul.hip $(HIP_HDR)
 	mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIP_FLAGS) -S --cuda-device-only -o $@ $< 2>/dev/null
-$(OBJDIR)/coop_isa.ok: $(OBJDIR)/csgn_mul.s tools/check_coop_isa.py
+$(OBJDIR)/coop_isa.checked: $(OBJDIR)/csgn_mul.device.s tools/check_coop_isa.py
 	python3 tools/check_coop_isa.py $<
 	echo ok > $@
 
-$(LIBDIR)/libcsgn_hip.so: $(HIP_OBJ) $(OBJDIR)/coop_isa.ok
+$(LIBDIR)/libcsgn_hip.so: $(HIP_OBJ) $(OBJDIR)/coop_isa.checked
 	$(HIPCC) --offload-arch=gfx950 -shared -fPIC -o $@ $(HIP_OBJ)
 
 $(LIBDIR)/libcertFHE.so: $(CLS_SRC) $(CLS_HDR) $(LIBDIR)/libcsgn_hip.so

@@ -91,7 +91,16 @@ def parse_args():
                     help="DEVELOPMENT ONLY: every rank uses GPU 0 and the process group runs on gloo, so that the "
                          "world > 1 logic (shards, offsets, verification, max-over-ranks) can be rehearsed on a "
                          "one-GPU box; RCCL refuses two ranks on one device, so no RCCL number comes out of it")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float64, "
+                         "at most 64 MB in all): a fixed, seeded sample of the output arena's words, a digest of "
+                         "every arena slot, and the gathered term counts where there is an exchange")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.native_ranks:
+        ap.error("--dump-outputs is not available with --native-ranks")
+    return args
 
 
 def spawn_ranks(args) -> int:
@@ -640,6 +649,61 @@ def secondary_suite(hip, budget_s: float = 25.0):
     return rows
 
 
+DUMP_BYTES = 64 << 20            # --dump-outputs: every file of every rank together
+DUMP_SAMPLE_WORDS = 1 << 21      # arena words sampled per job: 16 B of value + 8 B of index each
+DUMP_COUNTS = 1 << 20            # gathered term counts written at most (the first ones)
+
+
+def _u64_halves(words):
+    """uint64 words -> float64 (k, 2) of [high 32 bits, low 32 bits]: exact, unlike a float64 of the word."""
+    import numpy as np
+    w = np.ascontiguousarray(words, dtype=np.uint64)
+    return np.stack([(w >> np.uint64(32)).astype(np.float64), (w & np.uint64(0xFFFFFFFF)).astype(np.float64)], axis=1)
+
+
+def dump_outputs(out_dir, hip, arena, slots, words_per_product, slot_pairs, gathered, rank, world):
+    """What the timed path left its caller after the last step, as DIR/<name>.npy:
+      products_sample        (k, 2)      sampled words of the output arena, [high 32, low 32] of each u64 word
+      products_sample_index  (k,)        their flat word index in the arena (slot * words_per_product + word)
+      products_slot_digest   (slots, 2)  csgn_digest of every slot's whole product, [high 32, low 32]
+      products_slot_pair     (slots,)    the global pair index whose product each slot holds
+      term_counts            (m,)        the all-gathered result term counts, the first DUMP_COUNTS at most
+                                         (rank 0, and only where the step has the exchange)
+    The sample is a fixed function of the arena size and the seed, so runs with the same arguments dump the same
+    words.  With world > 1 every rank writes its own shard's products, prefixed rank<r>_."""
+    import numpy as np
+    import torch
+    from csgn_amd.capi import check
+    os.makedirs(out_dir, exist_ok=True)
+    prefix = f"rank{rank}_" if world > 1 else ""
+    total = slots * words_per_product
+    want = min(DUMP_SAMPLE_WORDS, (DUMP_BYTES - 8 * DUMP_COUNTS) // 24 - world * slots) // world
+    if total <= want:
+        idx = np.arange(total, dtype=np.int64)
+    else:
+        idx = np.unique(np.random.default_rng(SEED ^ 0xD0).integers(0, total, size=want, dtype=np.int64))
+    sample = hip.download(arena[torch.from_numpy(idx).to(arena.device)])
+    digests = torch.zeros(slots, dtype=torch.int64, device=arena.device)
+    for slot in range(slots):
+        check(hip.lib.csgn_digest(arena[slot * words_per_product:].data_ptr(), words_per_product, 0,
+                                  digests[slot:].data_ptr(), hip.stream))
+    arrays = {
+        "products_sample": _u64_halves(sample),
+        "products_sample_index": idx.astype(np.float64),
+        "products_slot_digest": _u64_halves(hip.download(digests)),
+        "products_slot_pair": np.asarray(slot_pairs, dtype=np.float64),
+    }
+    counts = {}
+    if gathered is not None and rank == 0:
+        counts["term_counts"] = gathered[:DUMP_COUNTS].cpu().numpy().astype(np.float64)
+    assert (sum(a.nbytes for a in arrays.values()) * world + sum(a.nbytes for a in counts.values())) <= DUMP_BYTES
+    arrays = {prefix + n: a for n, a in arrays.items()}
+    arrays.update(counts)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    print(f"# rank {rank}: wrote {', '.join(n + '.npy' for n in arrays)} to {out_dir}", file=sys.stderr)
+
+
 def main():
     if len(sys.argv) == 4 and sys.argv[1] == "--cpu-worker":      # child of cpu_baseline_all_cores
         _cpu_worker((int(sys.argv[2]), int(sys.argv[3])))
@@ -879,6 +943,13 @@ def main():
     if use_dist:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     elapsed = float(tmax.item())
+
+    if args.dump_outputs:
+        # off the clock: the arena holds the last step's final `slots` products (pair p -> slot p % slots)
+        last = (launches_per_step - 1) * slots
+        slot_pairs = [lo + (last + sl if last + sl < batch else last - slots + sl) for sl in range(slots)]
+        dump_outputs(args.dump_outputs, hip, arena, slots, words_per_product, slot_pairs, gathered, rank, world)
+        torch.cuda.synchronize()
 
     # kernel time from HIP events on the launch stream: each bracket holds launches_per_step
     # back-to-back launches of the all-pairs kernel

@@ -69,9 +69,11 @@ def build_hip(force: bool = False, verbose: bool = False) -> str:
             if verbose:
                 print(" ".join(cmd))
             jobs.append((cmd, subprocess.Popen(cmd)))
-    mul_asm = os.path.join(OBJDIR, "csgn_mul.s")
+    # not csgn_mul.s / coop_isa.ok: old copies of those are kept in git, and the build neither reads nor writes
+    # them, so a fresh checkout always regenerates the assembly and runs the check
+    mul_asm = os.path.join(OBJDIR, "csgn_mul.device.s")
     mul_src = os.path.join(CSRC, "csgn_mul.hip")
-    checked = os.path.join(OBJDIR, "coop_isa.ok")
+    checked = os.path.join(OBJDIR, "coop_isa.checked")
     asm_job = None
     if force or _stale(mul_asm, [mul_src] + hdrs):
         cmd = [_hipcc()] + flags + ["-S", "--cuda-device-only", "-o", mul_asm, mul_src]

@@ -36,9 +36,54 @@ def test_parent_of_a_multi_rank_run_makes_no_gpu_call():
     assert "torch.distributed.run" in spawn and "subprocess.call" in spawn
 
 
+def test_steps_and_dump_arguments_are_checked_before_any_gpu_call():
+    p = run(["--steps", "0"])
+    assert p.returncode == 2 and "--steps must be at least 1" in p.stderr and p.stdout.strip() == ""
+    p = run(["--native-ranks", "--dump-outputs", "out", "--steps", "1"])
+    assert p.returncode == 2 and "--dump-outputs is not available with --native-ranks" in p.stderr
+    assert p.stdout.strip() == ""
+
+
 import json
 
+import numpy as np
 import pytest
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_are_the_last_steps_products(tmp_path):
+    """--dump-outputs: after 3 timed steps the arena's sampled words, every slot's digest and the pair each slot
+    holds are written as float64 .npy files (64 MB at most); the words are the oracle's products of those pairs."""
+    from oracle.binding import Oracle
+    out = tmp_path / "dump"
+    p = run(["--batch", "200", "--slots", "32", "--terms", "64", "--steps", "3", "--warmup", "1", "--no-secondary",
+             "--no-cpu-baseline", "--dump-outputs", str(out)])
+    assert p.returncode == 0, p.stderr[-2000:]
+    d = json.loads([l for l in p.stdout.splitlines() if l.strip()][-1])
+    assert d["steps"] == 3 and d["config"]["step_ms_rank0"]["n"] == 3 and d["ms_per_step"] > 0
+    assert d["config"]["verified_vs_oracle"] is True
+    names = sorted(f.name for f in out.iterdir())
+    assert names == ["products_sample.npy", "products_sample_index.npy", "products_slot_digest.npy",
+                     "products_slot_pair.npy"]
+    assert sum(f.stat().st_size for f in out.iterdir()) <= 64 << 20
+    arr = {n[:-4]: np.load(out / n) for n in names}
+    assert all(a.dtype == np.float64 for a in arr.values())
+    orc = Oracle()
+    n_bits, seed, t, slots = 1247, 0x43534743, 64, 32
+    dl = orc.default_len(n_bits)
+    wpp = t * t * dl
+    # 200 pairs through 32 slots: the last launch wrote pairs 192..199 into slots 0..7, the one before it the rest
+    assert arr["products_slot_pair"].tolist() == [192 + s if s < 8 else 160 + s for s in range(slots)]
+    idx = arr["products_sample_index"].astype(np.int64)
+    assert idx.size > 1 << 20 and np.all(np.diff(idx) > 0) and idx[-1] < slots * wpp
+    words = (arr["products_sample"][:, 0].astype(np.uint64) << np.uint64(32)) | arr["products_sample"][:, 1].astype(np.uint64)
+    digests = (arr["products_slot_digest"][:, 0].astype(np.uint64) << np.uint64(32)) | arr["products_slot_digest"][:, 1].astype(np.uint64)
+    for slot in range(slots):
+        q = int(arr["products_slot_pair"][slot])
+        want, _ = orc.mul(n_bits, orc.synth(seed + 1, n_bits, q * t * dl, t * dl), orc.synth(seed + 2, n_bits, q * t * dl, t * dl))
+        assert int(digests[slot]) == orc.digest(want), slot
+        sel = (idx // wpp) == slot
+        assert np.array_equal(words[sel], want[idx[sel] % wpp]), slot
 
 
 @pytest.mark.gpu
