@@ -156,6 +156,26 @@ class HipPath:
                                         self.stream))
         return out[: batch * (t1 + t2) * dl]
 
+    # -- gates ----------------------------------------------------------------------
+    def gate_uniform(self, n_bits: int, gate: int, batch: int, a: torch.Tensor, t_a: int,
+                     b: Optional[torch.Tensor] = None, t_b: int = 0, sel: Optional[torch.Tensor] = None,
+                     t_sel: int = 0, plain: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """csgn_gate_uniform: one of capi.CSGN_GATE_* over a uniform batch (plain: uint8 tensor, one bit per element)."""
+        dl = self.default_len(n_bits)
+        terms = int(self.lib.csgn_gate_terms(gate, t_sel, t_a, t_b))
+        assert terms, "bad gate or shape"
+        out = self.empty_words(max(batch * terms * dl, 1))
+        check(self.lib.csgn_gate_uniform(n_bits, gate, batch, t_sel, t_a, t_b, _ptr(sel), _ptr(a), _ptr(b),
+                                         _ptr(plain), _ptr(out), self.stream))
+        return out[: batch * terms * dl]
+
+    def const_fill(self, n_bits: int, batch: int, plain: Optional[torch.Tensor] = None, bit: int = 1) -> torch.Tensor:
+        """csgn_const_fill: `batch` 1-term constants, ONE where plain & 1 (or `bit` when plain is None), else ZERO."""
+        dl = self.default_len(n_bits)
+        out = self.empty_words(max(batch * dl, 1))
+        check(self.lib.csgn_const_fill(n_bits, batch, _ptr(plain), int(bit), _ptr(out), self.stream))
+        return out[: batch * dl]
+
     def add_ragged(self, n_bits: int, left: torch.Tensor, off_left: torch.Tensor,
                    right: torch.Tensor, off_right: torch.Tensor,
                    total_terms_out: Optional[int] = None, max_t1: int = 0, max_t2: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:

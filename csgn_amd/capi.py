@@ -19,6 +19,10 @@ CSGN_ERR_UNSUPPORTED = -2
 CSGN_ERR_NO_DEVICE = -3
 CSGN_ERR_HIP = -4
 
+# gates (include/csgn_hip.h, csgn_gate_uniform)
+CSGN_GATE_NOT, CSGN_GATE_XNOR, CSGN_GATE_NAND, CSGN_GATE_OR, CSGN_GATE_NOR, CSGN_GATE_MUX, \
+    CSGN_GATE_ADD_PLAIN, CSGN_GATE_MUL_PLAIN = range(1, 9)
+
 u64 = C.c_uint64
 vp = C.c_void_p
 
@@ -115,6 +119,10 @@ SIGNATURES = {
     "csgn_circuit_bits": (vp, [vp, C.c_uint32]),
     "csgn_circuit_run": (C.c_int, [vp, vp]),
     "csgn_mul_uniform_kernel": (C.c_char_p, [u64, u64, u64, u64]),
+    "csgn_gate_terms": (u64, [C.c_int, u64, u64, u64]),
+    "csgn_gate_uniform_kernel": (C.c_char_p, [u64, C.c_int, u64, u64, u64, u64]),
+    "csgn_gate_uniform": (C.c_int, [u64, C.c_int, u64, u64, u64, u64, vp, vp, vp, vp, vp, vp]),
+    "csgn_const_fill": (C.c_int, [u64, u64, vp, C.c_int, vp, vp]),
     "csgn_set_tuning": (C.c_int, [C.c_char_p, C.c_int]),
     "csgn_get_tuning": (C.c_int, [C.c_char_p, C.POINTER(C.c_int)]),
     "csgn_reset_tuning": (None, []),

@@ -343,7 +343,7 @@ Ciphertext CiphertextBatch::at(uint64_t i) const
 // ------------------------------------------------------------------ BatchCircuit
 
 BatchCircuit::BatchCircuit(const Context &context, uint64_t count)
-    : handle(nullptr), ctx(context), count_(count), next_first(0)
+    : handle(nullptr), ctx(context), count_(count), next_first(0), one_id(~0u)
 {
     detail::ensureDevice();
     detail::check(csgn_circuit_create(ctx.getN(), count, &handle), "csgn_circuit_create");
@@ -512,7 +512,12 @@ void BatchCircuit::keep(unsigned value) { detail::check(csgn_circuit_output(hand
 
 uint64_t BatchCircuit::blockBytes() const { return csgn_circuit_block_bytes(handle); }
 
-void BatchCircuit::build() { detail::check(csgn_circuit_build(handle), "csgn_circuit_build"); }
+void BatchCircuit::build()
+{
+    detail::check(csgn_circuit_build(handle), "csgn_circuit_build");
+    for (size_t i = 0; i < consts.size(); ++i)
+        fillConstant(consts[i]);
+}
 
 void BatchCircuit::set(unsigned input, const CiphertextBatch &batch)
 {

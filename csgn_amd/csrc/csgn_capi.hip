@@ -967,6 +967,81 @@ const char *csgn_mul_uniform_kernel(uint64_t n_bits, uint64_t pairs, uint64_t t1
     return csgn::mul_uniform_kernel_name(n_bits, pairs, t1, t2);
 }
 
+/* ------------------------------------------------------------------- gates ---- */
+
+namespace {
+// the gate entry points say NO_DEVICE before anything else when there is no GPU (a launch would report it less plainly)
+int require_device(const char *who)
+{
+    int n = 0;
+    const hipError_t e = hipGetDeviceCount(&n);
+    if (e != hipSuccess || n == 0)
+        return fail(CSGN_ERR_NO_DEVICE, "%s: no HIP device visible (%s); this library has no CPU fallback", who,
+                    e == hipSuccess ? "count is 0" : hipGetErrorString(e));
+    return CSGN_OK;
+}
+} // namespace
+
+uint64_t csgn_gate_terms(int gate, uint64_t t_sel, uint64_t t_a, uint64_t t_b)
+{
+    return csgn::gate_terms(gate, t_sel, t_a, t_b);
+}
+
+const char *csgn_gate_uniform_kernel(uint64_t n_bits, int gate, uint64_t batch, uint64_t t_sel, uint64_t t_a,
+                                     uint64_t t_b)
+{
+    return csgn::gate_kernel_name(n_bits, gate, batch, t_sel, t_a, t_b);
+}
+
+int csgn_gate_uniform(uint64_t n_bits, int gate, uint64_t batch, uint64_t t_sel, uint64_t t_a, uint64_t t_b,
+                      const uint64_t *d_sel, const uint64_t *d_a, const uint64_t *d_b, const uint8_t *d_plain,
+                      uint64_t *d_out, void *stream)
+{
+    if (int rc = check_n(n_bits))
+        return rc;
+    REQUIRE(gate >= CSGN_GATE_NOT && gate <= CSGN_GATE_MUL_PLAIN, "unknown gate %d", gate);
+    const bool uses_sel = gate == CSGN_GATE_MUX;
+    const bool uses_b = gate != CSGN_GATE_NOT && gate != CSGN_GATE_ADD_PLAIN && gate != CSGN_GATE_MUL_PLAIN;
+    const bool uses_plain = gate == CSGN_GATE_ADD_PLAIN || gate == CSGN_GATE_MUL_PLAIN;
+    if (!uses_sel)
+        t_sel = 0;
+    if (!uses_b)
+        t_b = 0;
+    const uint64_t terms = csgn::gate_terms(gate, t_sel, t_a, t_b);
+    REQUIRE(terms != 0, "gate %d: an operand it reads has no terms, or the term count overflows", gate);
+    const uint64_t dl = csgn_default_len(n_bits);
+    if (!product_below(terms, dl, 1, 1ull << 31))
+        return fail(CSGN_ERR_UNSUPPORTED, "gate %d: %llu terms per element exceed 2^31 words", gate,
+                    (unsigned long long)terms);
+    if (!product_below(batch, terms, dl, 1ull << 60))
+        return fail(CSGN_ERR_UNSUPPORTED, "batch of %llu elements: size overflows", (unsigned long long)batch);
+    if (int rc = require_device("csgn_gate_uniform"))
+        return rc;
+    if (batch == 0)
+        return CSGN_OK;
+    REQUIRE(d_out && d_a && (d_sel || !uses_sel) && (d_b || !uses_b) && (d_plain || !uses_plain),
+            "null device pointer");
+    HIP_TRY(csgn::gate_uniform(n_bits, gate, batch, t_sel, t_a, t_b, (const u64 *)(uses_sel ? d_sel : nullptr),
+                               (const u64 *)d_a, (const u64 *)(uses_b ? d_b : nullptr), uses_plain ? d_plain : nullptr,
+                               (u64 *)d_out, S(stream)));
+    return CSGN_OK;
+}
+
+int csgn_const_fill(uint64_t n_bits, uint64_t batch, const uint8_t *d_plain, int bit, uint64_t *d_out, void *stream)
+{
+    if (int rc = check_n(n_bits))
+        return rc;
+    if (!product_below(batch, csgn_default_len(n_bits), 1, 1ull << 60))
+        return fail(CSGN_ERR_UNSUPPORTED, "batch of %llu constants: size overflows", (unsigned long long)batch);
+    if (int rc = require_device("csgn_const_fill"))
+        return rc;
+    if (batch == 0)
+        return CSGN_OK;
+    REQUIRE(d_out, "null device pointer");
+    HIP_TRY(csgn::const_fill(n_bits, batch, d_plain, bit, (u64 *)d_out, 0, S(stream)));
+    return CSGN_OK;
+}
+
 /* ------------------------------------------------------------------ tuning ---- */
 
 int csgn_set_tuning(const char *key, int value)

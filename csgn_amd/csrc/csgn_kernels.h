@@ -119,6 +119,14 @@ hipError_t circuit_zero_words(u64 *p, u64 n, hipStream_t s);   // zero-fill by a
 hipError_t synth_fill(u64 seed, u64 n_bits, u64 first_word, u64 n_words, u64 *out, hipStream_t s);
 hipError_t digest(const u64 *w, u64 n_words, u64 first_index, u64 *d_digest, hipStream_t s);
 
+// gates over uniform batches and the constant term (csgn_gates.hip); gate = CSGN_GATE_* of include/csgn_hip.h
+u64 gate_terms(int gate, u64 ts, u64 ta, u64 tb);                  // 0: bad gate, zero term count or overflow
+const char *gate_kernel_name(u64 n_bits, int gate, u64 batch, u64 ts, u64 ta, u64 tb);
+// pitch_words: words from one element's constant to the next (0 = dL, a dense batch of 1-term ciphertexts)
+hipError_t const_fill(u64 n_bits, u64 batch, const uint8_t *plain, int bit, u64 *out, u64 pitch_words, hipStream_t s);
+hipError_t gate_uniform(u64 n_bits, int gate, u64 batch, u64 ts, u64 ta, u64 tb, const u64 *S, const u64 *A,
+                        const u64 *B, const uint8_t *plain, u64 *out, hipStream_t s);
+
 hipError_t small_ops(u64 n_bits, u64 count, const ::csgn_small_op *ops, hipStream_t s);
 size_t decrypt_scratch_bytes(u64 batch, u64 total_terms);
 // out[i] = a[i] & b[i] (is_product) or a[i] ^ b[i]: Dec(a*b) = Dec(a) & Dec(b), Dec(a+b) = Dec(a) ^ Dec(b)

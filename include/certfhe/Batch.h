@@ -25,9 +25,13 @@ struct csgn_circuit;   // include/csgn_hip.h (opaque)
 namespace certFHE {
 
 class BatchCircuit;
+namespace detail {
+struct GateAccess;   // Gates.cpp
+}
 
 class CiphertextBatch {
     friend class BatchCircuit;
+    friend struct detail::GateAccess;
     std::shared_ptr<detail::DevicePayload> payload;   // total terms * dL words, element after element
     uint64_t count_;
     uint64_t terms_;                                   // per element when uniform; 0 when ragged
@@ -105,6 +109,16 @@ class BatchCircuit {
     std::vector<std::pair<unsigned, std::shared_ptr<detail::DevicePayload> > > plains;   // encrypt inputs: value id -> plaintext bytes
     std::vector<std::pair<unsigned, std::shared_ptr<detail::DevicePayload> > > pair_plains;   // fused products: value id -> both operands' plaintext bytes
     uint64_t next_first;                                           // stream range handed to the next encrypt input
+    // constant and plain inputs (Gates.h): value id -> plaintext bytes on the device (null: every element `bit`),
+    // filled into the value's buffer at build() and setPlainBits()
+    struct ConstInput {
+        unsigned id;
+        unsigned char bit;
+        std::shared_ptr<detail::DevicePayload> plain;
+    };
+    std::vector<ConstInput> consts;
+    unsigned one_id;                                               // the ONE the gate helpers share (~0u: none yet)
+    void fillConstant(const ConstInput &c);
     BatchCircuit(const BatchCircuit &);
     BatchCircuit &operator=(const BatchCircuit &);
 
@@ -125,6 +139,20 @@ class BatchCircuit {
     void setPlainPair(unsigned product, const std::vector<unsigned char> &a, const std::vector<unsigned char> &b);
     unsigned add(unsigned a, unsigned b);
     unsigned mul(unsigned a, unsigned b);
+    // EXTENSION (Gates.h): a constant input -- ONE (bit & 1) or ZERO in every element -- and a plain input whose
+    // per-element bit setPlainBits() gives (ZERO until then).  Both are ordinary 1-term inputs filled on the device at
+    // build() / setPlainBits(); the circuit never reuses an input's buffer, so they survive every run().  TRIVIAL
+    // encryptions: their plaintext is public.
+    unsigned constant(unsigned char bit);
+    unsigned plainInput();
+    void setPlainBits(unsigned plain_input, const std::vector<unsigned char> &bits);
+    // the gates of Gates.h lowered to add / mul with the circuit's ONE
+    unsigned logicNot(unsigned a);
+    unsigned logicNand(unsigned a, unsigned b);
+    unsigned logicOr(unsigned a, unsigned b);
+    unsigned logicNor(unsigned a, unsigned b);
+    unsigned logicXnor(unsigned a, unsigned b);
+    unsigned logicMux(unsigned sel, unsigned a, unsigned b);
     // EXTENSION (see CiphertextBatch::compact): every element reduced to its distinct terms of odd multiplicity.
     // The result and everything computed from it have data-dependent sizes: value() returns them as a ragged
     // batch; permute() does not accept them.

@@ -11,5 +11,6 @@
 #include "SecretKey.h"
 #include "Timer.h"
 #include "Batch.h"   // extension: device-resident uniform batches
+#include "Gates.h"   // extension: plaintext constants and the boolean gates
 
 #endif

@@ -551,6 +551,58 @@ int csgn_circuit_run(csgn_circuit *circuit, void *stream);
  * with the kernel that really runs. */
 const char *csgn_mul_uniform_kernel(uint64_t n_bits, uint64_t pairs, uint64_t t1, uint64_t t2);
 
+/* ------------------------------------------------------------- gates ---- */
+
+/* Plaintext constants and the boolean gates they make possible (uniform batches).  `+` (XOR) and `*` (AND) both map
+ * 0 to 0, so without a constant every computable function maps the all-zero input to 0, and whoever evaluates holds no
+ * key to encrypt a 1.  But a term decrypts to the AND of the key's d positions in it (src/SecretKey.cpp:82-147): the
+ * ALL-ONES term (every word ~0, the last word masked to its top N%64 bits as in every canonical term) decrypts to 1 under
+ * every key, the all-zero term to 0.  These are TRIVIAL encryptions: their plaintext is public, and an output that is
+ * only a constant hides nothing.
+ *
+ * Every gate is a composition of the reference's operator+ / operator* (src/Ciphertext.cpp:107-179) in this order,
+ * so its words are those of that composition (ONE / ZERO: one all-ones / all-zero term):
+ *     NOT a        a + ONE                              ta + 1 terms            reads a
+ *     XNOR(a,b)    (a + b) + ONE                        ta + tb + 1             reads a, b
+ *     NAND(a,b)    (a * b) + ONE                        ta*tb + 1               reads a, b
+ *     OR(a,b)      (a + b) + (a * b)                    ta + tb + ta*tb         reads a, b
+ *     NOR(a,b)     ((a + b) + (a * b)) + ONE            ta + tb + ta*tb + 1     reads a, b
+ *     MUX(s,a,b)   (s * (a + b)) + b     (s ? a : b)    ts*(ta + tb) + tb       reads sel, a, b
+ *     ADD_PLAIN    a + (p ? ONE : ZERO)                 ta + 1                  reads a, plain
+ *     MUL_PLAIN    a * (p ? ONE : ZERO)                 ta                      reads a, plain
+ * p = d_plain[e] & 1, one public bit per element (ZERO keeps the batch uniform when p = 0). */
+enum {
+    CSGN_GATE_NOT = 1,
+    CSGN_GATE_XNOR,
+    CSGN_GATE_NAND,
+    CSGN_GATE_OR,
+    CSGN_GATE_NOR,
+    CSGN_GATE_MUX,
+    CSGN_GATE_ADD_PLAIN,
+    CSGN_GATE_MUL_PLAIN
+};
+/* Terms per output element (host only).  0: unknown gate, a term count of 0 in an operand the gate reads, or overflow. */
+uint64_t csgn_gate_terms(int gate, uint64_t t_sel, uint64_t t_a, uint64_t t_b);
+/* Which form a csgn_gate_uniform call of this shape takes (host only, a static string): "k_gate_fused" (one kernel:
+ * operands read once, every segment of the output written in one pass) or "pitched" (small products fused, larger ones
+ * through the tuned csgn_mul_uniform / csgn_add_uniform launchers writing into the output's slices, plus the constant
+ * fill; no intermediate buffer).  Knob "gate_fused" (-1 per shape, 0 / 1 forced) decides; the words are the same.
+ * MUL_PLAIN, and MUX with t_sel > 1, are always fused.  "" for an invalid gate or shape. */
+const char *csgn_gate_uniform_kernel(uint64_t n_bits, int gate, uint64_t batch,
+                                     uint64_t t_sel, uint64_t t_a, uint64_t t_b);
+/* One gate over `batch` elements: d_out = batch * csgn_gate_terms(...) * dL words, element after element.  Pointers
+ * the gate does not read (table above) may be NULL and their term counts are ignored.  d_a and d_b (and d_sel) may
+ * alias one another; d_out overlaps no input.  Limits: csgn_gate_terms(...) * dL < 2^31 words per element
+ * (CSGN_ERR_UNSUPPORTED), batch * that < 2^60.  On the caller's stream, asynchronous.  No GPU: CSGN_ERR_NO_DEVICE,
+ * no CPU fallback. */
+int csgn_gate_uniform(uint64_t n_bits, int gate, uint64_t batch, uint64_t t_sel, uint64_t t_a, uint64_t t_b,
+                      const uint64_t *d_sel, const uint64_t *d_a, const uint64_t *d_b, const uint8_t *d_plain,
+                      uint64_t *d_out, void *stream);
+/* A batch of `batch` 1-term constants into d_out (batch * dL words): element e is ONE if d_plain[e] & 1, else ZERO;
+ * d_plain NULL: every element is ONE if bit != 0, else ZERO.  Written by a kernel (graph-safe).  No GPU:
+ * CSGN_ERR_NO_DEVICE. */
+int csgn_const_fill(uint64_t n_bits, uint64_t batch, const uint8_t *d_plain, int bit, uint64_t *d_out, void *stream);
+
 /* ------------------------------------------------------------------- tuning ---- */
 
 /* Kernel-choice and sweep knobs ("mul_flat", "mul_touch", "ragged_c", "perm_ballot", ...;
