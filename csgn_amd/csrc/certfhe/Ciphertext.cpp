@@ -132,14 +132,12 @@ void Ciphertext::publish(const std::shared_ptr<DevicePayload> &p, uint64_t words
     len = words;
 }
 
-// A ciphertext made by a queued operation (detail::deferSmallOp) has no payload yet: the first look at its words
-// evaluates the queue.
-void Ciphertext::resolve() const
+// A ciphertext made by a queued operation (detail::deferSmallOp) has no payload yet: a look at its words evaluates the
+// queue.  The node keeps the result, so `lazy` stays: const members write neither `payload` nor `lazy`, and threads that
+// share one const ciphertext do not race on them.
+std::shared_ptr<DevicePayload> Ciphertext::current() const
 {
-    if (lazy) {
-        payload = detail::valueOf(lazy);
-        lazy.reset();
-    }
+    return lazy ? detail::valueOf(lazy) : payload;
 }
 
 Ciphertext &Ciphertext::operator=(const Ciphertext &c)
@@ -200,10 +198,10 @@ Context Ciphertext::getContext() const { return requireContext(certFHEcontext); 
 
 uint64_t *Ciphertext::getValues() const
 {
-    resolve();
-    if (!host_v && len && payload) {
+    const std::shared_ptr<DevicePayload> p = current();
+    if (!host_v && len && p) {
         host_v = allocMirror(len);                                 // pinned when large: the copy is one DMA
-        detail::downloadBytes(host_v, payload->ptr, (size_t)len * 8);
+        detail::downloadBytes(host_v, p->ptr, (size_t)len * 8);
     }
     return host_v;
 }
@@ -227,8 +225,8 @@ uint64_t Ciphertext::getTerms() const
 
 const uint64_t *Ciphertext::deviceValues() const
 {
-    resolve();
-    return payload ? payload->data() : nullptr;
+    const std::shared_ptr<DevicePayload> p = current();
+    return p ? p->data() : nullptr;                // (lazy or payload keeps the block)
 }
 
 bool Ciphertext::hasCanonicalBitlen() const { return !custom_bitlen; }
@@ -394,7 +392,7 @@ uint64_t getU64(std::istream &in)
 void Ciphertext::serialize(std::ostream &out) const
 {
     const Context &ctx = requireContext(certFHEcontext);
-    resolve();
+    const std::shared_ptr<DevicePayload> p = current();
     out.write(kWireMagic, 4);
     const unsigned char ver_flags[4] = {1, 0, (unsigned char)(custom_bitlen ? 1 : 0), 0};
     out.write(reinterpret_cast<const char *>(ver_flags), 4);
@@ -405,7 +403,7 @@ void Ciphertext::serialize(std::ostream &out) const
     // piece of HBM goes out as it is -- through the two pinned staging buffers, the DMA of one piece
     // behind the stream write of the previous one.  A ciphertext whose host mirror already exists
     // (getValues() was called) is written from it.
-    if (host_v || !payload || !kHostIsLittleEndian) {
+    if (host_v || !p || !kHostIsLittleEndian) {
         const uint64_t *v = getValues();
         if (kHostIsLittleEndian)
             out.write(reinterpret_cast<const char *>(v), (std::streamsize)(len * 8));
@@ -420,7 +418,7 @@ void Ciphertext::serialize(std::ostream &out) const
                 static_cast<Sink *>(ctx)->out->write(static_cast<const char *>(piece), (std::streamsize)n);
             }
         } sink = {&out};
-        detail::downloadStaged(payload->ptr, (size_t)len * 8, &Sink::take, &sink);
+        detail::downloadStaged(p->ptr, (size_t)len * 8, &Sink::take, &sink);
     }
     if (custom_bitlen)
         for (uint64_t i = 0; i < len; ++i)
@@ -432,7 +430,7 @@ void Ciphertext::serialize(std::ostream &out) const
 uint64_t Ciphertext::serializedSize() const
 {
     requireContext(certFHEcontext);
-    resolve();
+    (void)current();                               // (evaluates a queued operation, as serialize() would)
     return 32u + len * 8u * (custom_bitlen ? 2u : 1u);
 }
 
@@ -465,7 +463,8 @@ uint64_t Ciphertext::serializeTo(void *buffer, uint64_t capacity) const
     storeU64(b + 16, ctx.getD());
     storeU64(b + 24, len);
     unsigned char *w = b + 32;
-    if (host_v || !payload || !kHostIsLittleEndian) {
+    const std::shared_ptr<DevicePayload> p = current();
+    if (host_v || !p || !kHostIsLittleEndian) {
         const uint64_t *v = getValues();
         if (kHostIsLittleEndian)
             memcpy(w, v, (size_t)len * 8);
@@ -474,7 +473,7 @@ uint64_t Ciphertext::serializeTo(void *buffer, uint64_t capacity) const
                 storeU64(w + 8 * i, v[i]);
     } else if (len) {
         // straight from HBM into the caller's memory (a page-locked buffer: the DMA engine writes it)
-        detail::downloadBytes(w, payload->ptr, (size_t)len * 8);    // (returns when the bytes are there, as for getValues())
+        detail::downloadBytes(w, p->ptr, (size_t)len * 8);    // (returns when the bytes are there, as for getValues())
     }
     if (custom_bitlen)
         for (uint64_t i = 0; i < len; ++i)

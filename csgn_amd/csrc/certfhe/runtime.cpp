@@ -5,6 +5,8 @@
 #include <atomic>
 #include <cstdlib>
 #include <mutex>
+#include <string>
+#include <utility>
 #include <vector>
 
 namespace certFHE {
@@ -66,8 +68,10 @@ struct BlockCache {
     {
         static const bool disabled = getenv("CSGN_NO_BLOCK_CACHE") != nullptr;   // A/B switch
         size_t same = 0;
-        const int c = size_class(capacity, &same);   // capacities are class sizes: same == capacity
-        if (!disabled && c < kClasses && capacity <= kMaxCachedBlock && cached_bytes + capacity <= kMaxCachedTotal) {
+        const int c = size_class(capacity, &same);   // a block not of a class size (a flush of another thread's queue,
+                                                     // an allocation at thread exit) would be handed out too small
+        if (!disabled && same == capacity && c < kClasses && capacity <= kMaxCachedBlock &&
+            cached_bytes + capacity <= kMaxCachedTotal) {
             free_list[c].push_back(p);
             cached_bytes += capacity;
         } else {
@@ -392,7 +396,8 @@ std::atomic<bool> g_defer_on(getenv("CSGN_NO_DEFER") == nullptr);
 
 struct DeferQueue {
     std::mutex lock;
-    std::vector<std::shared_ptr<LazyNode> > pending;
+    std::vector<std::shared_ptr<LazyNode> > pending;   // exactly the nodes in state kPending
+    std::string error;                                 // set when the flush at the thread's end failed
     int device = -1;
     uint64_t n_bits = 0;
     // the records of a flush live in pinned, device-addressable memory: the kernel reads them over the link, no copy
@@ -414,6 +419,7 @@ struct DeferQueue {
     }
 
     // evaluate everything that is pending.  Called with `lock` held, on ANY thread: the work goes to the queue's device.
+    // If it throws, no node has changed.
     void flushLocked()
     {
         if (pending.empty())
@@ -422,8 +428,9 @@ struct DeferQueue {
         const bool foreign = caller_device != device;
         if (foreign)
             check(csgn_init(device), "csgn_init (flush of another thread's queue)");
+        std::vector<std::shared_ptr<DevicePayload> > values(pending.size());
         try {
-            evaluate(foreign);
+            evaluate(foreign, values);
         } catch (...) {
             if (foreign && caller_device >= 0)
                 (void)csgn_init(caller_device);
@@ -431,9 +438,31 @@ struct DeferQueue {
         }
         if (foreign && caller_device >= 0)
             check(csgn_init(caller_device), "csgn_init");
+        for (size_t i = 0; i < pending.size(); ++i) {
+            LazyNode &nd = *pending[i];
+            nd.value = std::move(values[i]);
+            nd.pa.reset();
+            nd.pb.reset();
+            nd.state.store(LazyNode::kDone, std::memory_order_release);
+        }
+        for (size_t i = 0; i < pending.size(); ++i) {   // (after every node has its value: a node may be another's operand)
+            pending[i]->la.reset();
+            pending[i]->lb.reset();
+        }
+        pending.clear();
     }
 
-    void evaluate(bool foreign)
+    // the thread's end could not evaluate what is pending: valueOf() throws `what` for those nodes.  `lock` held.
+    void failLocked(const char *what)
+    {
+        error = std::string("certFHE: a deferred operation failed when its thread ended: ") + what;
+        for (size_t i = 0; i < pending.size(); ++i)
+            pending[i]->state.store(LazyNode::kFailed, std::memory_order_release);
+        pending.clear();
+    }
+
+    // the results of `pending`, in its order, into `values`; touches no node but its scratch fields
+    void evaluate(bool foreign, std::vector<std::shared_ptr<DevicePayload> > &values)
     {
         const size_t n = pending.size();
         // One or two operations (a short sum in front of a large product: `big * (a + b)`): the ordinary kernels, one
@@ -442,23 +471,16 @@ struct DeferQueue {
         if (n <= 2 && !foreign) {
             for (size_t i = 0; i < n; ++i) {
                 LazyNode &nd = *pending[i];
-                const uint64_t *A = nd.la ? nd.la->value->data() : nd.pa->data();
-                const uint64_t *B = nd.lb ? nd.lb->value->data() : nd.pb->data();
+                nd.index = (int)i;
+                const uint64_t *A = nd.la ? values[(size_t)nd.la->index]->data() : nd.pa->data();
+                const uint64_t *B = nd.lb ? values[(size_t)nd.lb->index]->data() : nd.pb->data();
                 std::shared_ptr<DevicePayload> v = allocWords((nd.product ? (uint64_t)nd.t1 * nd.t2 : (uint64_t)nd.t1 + nd.t2) * nd.dl);
                 if (nd.product)
                     check(csgn_mul_uniform(nd.n_bits, 1, nd.t1, nd.t2, A, B, v->data(), 0, stream()), "csgn_mul_uniform");
                 else
                     check(csgn_add_uniform(nd.n_bits, 1, nd.t1, nd.t2, A, B, v->data(), stream()), "csgn_add_uniform");
-                nd.value = v;
-                nd.queue = nullptr;
+                values[i] = std::move(v);
             }
-            for (size_t i = 0; i < n; ++i) {
-                pending[i]->pa.reset();
-                pending[i]->pb.reset();
-                pending[i]->la.reset();
-                pending[i]->lb.reset();
-            }
-            pending.clear();
             return;
         }
         if (!h_ops) {
@@ -528,54 +550,56 @@ struct DeferQueue {
         check(csgn_event_record(slot_event[cur], stream()), "csgn_event_record");
         slot_used[cur] = true;
         for (size_t i = 0; i < n; ++i) {
-            LazyNode &nd = *pending[i];
+            const LazyNode &nd = *pending[i];
             std::shared_ptr<DevicePayload> v = std::make_shared<DevicePayload>();
             v->ptr = base + at[i];
             v->words = (nd.product ? (uint64_t)nd.t1 * nd.t2 : (uint64_t)nd.t1 + nd.t2) * nd.dl;
             v->capacity = (size_t)v->words * 8;
             v->device = device;
             v->parent = block;
-            nd.value = v;
-            nd.pa.reset();
-            nd.pb.reset();
-            nd.queue = nullptr;
+            values[i] = std::move(v);
         }
-        for (size_t i = 0; i < n; ++i) {              // (after every node has its value: a node may be another's operand)
-            pending[i]->la.reset();
-            pending[i]->lb.reset();
-        }
-        pending.clear();
     }
 };
 
 namespace {
-thread_local DeferQueue *g_queue_ptr = nullptr;
-struct QueueGuard {
+// The calling thread's queue, made on first use.  When the thread ends, what is pending is evaluated (results somebody
+// still points at must exist) or, failing that, marked failed, and the thread lets go of the queue: nodes that other
+// threads still hold keep it alive.  Nothing is deferred on the thread from then on.
+struct ThreadQueue {
+    std::shared_ptr<DeferQueue> q;
     bool dead = false;
-    ~QueueGuard()
+    ~ThreadQueue()
     {
-        if (g_queue_ptr) {
-            try {
-                std::lock_guard<std::mutex> hold(g_queue_ptr->lock);
-                g_queue_ptr->flushLocked();          // results somebody still points at must exist
-            } catch (...) {
-            }
-            delete g_queue_ptr;
-            g_queue_ptr = nullptr;
-        }
         dead = true;
+        if (!q)
+            return;
+        {
+            std::lock_guard<std::mutex> hold(q->lock);
+            try {
+                q->flushLocked();
+            } catch (const std::exception &e) {
+                q->failLocked(e.what());
+            } catch (...) {
+                q->failLocked("unknown error");
+            }
+        }
+        q.reset();
     }
 };
-thread_local QueueGuard g_queue_guard;
+thread_local ThreadQueue g_thread_queue;
 
-DeferQueue *queue()
+const std::shared_ptr<DeferQueue> &threadQueue()
 {
-    if (!g_queue_ptr && !g_queue_guard.dead) {
-        ensureDevice();
-        g_queue_ptr = new DeferQueue();
-        g_queue_ptr->device = g_device;
+    // the device first: the HIP runtime's own thread_local state is then made before g_thread_queue, so it is destroyed
+    // after it, and the flush at the thread's end still has a runtime to call
+    ensureDevice();
+    ThreadQueue &t = g_thread_queue;
+    if (!t.q && !t.dead) {
+        t.q = std::make_shared<DeferQueue>();
+        t.q->device = g_device;
     }
-    return g_queue_ptr;
+    return t.q;
 }
 } // namespace
 
@@ -589,26 +613,27 @@ bool deferralOn() { return g_defer_on.load(); }
 
 void flushDeferred()
 {
-    if (!g_queue_ptr)
+    const std::shared_ptr<DeferQueue> &q = g_thread_queue.q;
+    if (!q)
         return;
-    std::lock_guard<std::mutex> hold(g_queue_ptr->lock);
-    g_queue_ptr->flushLocked();
+    std::lock_guard<std::mutex> hold(q->lock);
+    q->flushLocked();
 }
 
 std::shared_ptr<DevicePayload> valueOf(const std::shared_ptr<LazyNode> &node)
 {
     if (!node)
         return std::shared_ptr<DevicePayload>();
-    for (;;) {
-        DeferQueue *q = node->queue;                 // (read without the lock: nullptr only ever replaces a queue)
-        if (!q)
-            return node->value;
-        std::lock_guard<std::mutex> hold(q->lock);
-        if (node->queue == q) {                      // still pending there
-            q->flushLocked();
-            return node->value;
-        }
+    int state = node->state.load(std::memory_order_acquire);
+    if (state == LazyNode::kPending) {
+        std::lock_guard<std::mutex> hold(node->owner->lock);
+        if (node->state.load(std::memory_order_relaxed) == LazyNode::kPending)
+            node->owner->flushLocked();              // returns with every node of the queue kDone, or throws
+        state = node->state.load(std::memory_order_relaxed);
     }
+    if (state == LazyNode::kFailed)
+        throw std::runtime_error(node->owner->error);
+    return node->value;
 }
 
 std::shared_ptr<LazyNode> deferSmallOp(bool product, uint64_t n_bits, uint64_t dl, uint64_t t1, uint64_t t2,
@@ -617,18 +642,18 @@ std::shared_ptr<LazyNode> deferSmallOp(bool product, uint64_t n_bits, uint64_t d
 {
     if (!g_defer_on.load() || t1 == 0 || t2 == 0 || t1 > kDeferMaxTerms || t2 > kDeferMaxTerms || dl == 0)
         return std::shared_ptr<LazyNode>();
-    DeferQueue *q = queue();
+    const std::shared_ptr<DeferQueue> &q = threadQueue();
     if (!q || q->device != g_device)                 // thread shutting down, or it moved to another GPU meanwhile
         return std::shared_ptr<LazyNode>();
-    // operands pending in ANOTHER thread's queue (or already evaluated) are taken as finished payloads, so that a
-    // queue only ever refers to its own nodes
+    // operands of ANOTHER thread's queue are taken as finished payloads, evaluated before this queue is locked (rule 3),
+    // so that a queue only ever refers to its own nodes
     std::shared_ptr<DevicePayload> fa = pa, fb = pb;
     std::shared_ptr<LazyNode> na = la, nb = lb;
-    if (na && na->queue != q) {
+    if (na && na->owner != q) {
         fa = valueOf(na);
         na.reset();
     }
-    if (nb && nb->queue != q) {
+    if (nb && nb->owner != q) {
         fb = valueOf(nb);
         nb.reset();
     }
@@ -639,16 +664,18 @@ std::shared_ptr<LazyNode> deferSmallOp(bool product, uint64_t n_bits, uint64_t d
     std::lock_guard<std::mutex> hold(q->lock);
     if (!q->pending.empty() && q->n_bits != n_bits)
         q->flushLocked();                            // one launch serves one term size
-    if (na && !na->queue) {                          // (evaluated by the flush just above)
+    // operands of this queue evaluated already (by the flush above, or another thread's valueOf): kDone, since this
+    // queue can only fail when its thread has ended
+    if (na && na->state.load(std::memory_order_relaxed) != LazyNode::kPending) {
         fa = na->value;
         na.reset();
     }
-    if (nb && !nb->queue) {
+    if (nb && nb->state.load(std::memory_order_relaxed) != LazyNode::kPending) {
         fb = nb->value;
         nb.reset();
     }
     q->n_bits = n_bits;
-    std::shared_ptr<LazyNode> nd = std::make_shared<LazyNode>();
+    std::shared_ptr<LazyNode> nd = std::make_shared<LazyNode>(q);
     nd->pa = fa;
     nd->pb = fb;
     nd->la = na;
@@ -658,8 +685,6 @@ std::shared_ptr<LazyNode> deferSmallOp(bool product, uint64_t n_bits, uint64_t d
     nd->t1 = (uint32_t)t1;
     nd->t2 = (uint32_t)t2;
     nd->product = product;
-    nd->queue = q;
-    nd->index = nd->level = 0;
     q->pending.push_back(nd);
     if (q->pending.size() >= kDeferBatch)
         q->flushLocked();

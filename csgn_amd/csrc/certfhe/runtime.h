@@ -4,6 +4,7 @@
 
 #include <stdint.h>
 
+#include <atomic>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -69,32 +70,43 @@ void releasePinnedPool();
 // Returns every cached HBM block of the calling thread to the driver.
 void releaseBlockCache();
 
-// ---- deferred small operations (round 5).  A kernel launch is 2-3 us of host time; a 1 x 1 product is
-// 480 bytes.  operator* / operator+ on ciphertexts of at most kDeferMaxTerms terms a side therefore do not launch:
-// they append a LazyNode to the calling thread's queue and return a ciphertext that points at it.  The queue is
-// evaluated -- ONE csgn_small_ops launch per dependency level, results side by side in one HBM block -- when a value
-// is needed (getValues, decrypt, serialize, an operation that is not deferred), when kDeferBatch operations have
-// piled up, or when the thread ends.  A node keeps its operands alive (payloads are immutable), so the caller's
-// objects may die or be reassigned in between; results are the words of the immediate path.
+// ---- deferred small operations.  A kernel launch is 2-3 us of host time; a 1 x 1 product is 480 bytes.  operator* /
+// operator+ on ciphertexts of at most kDeferMaxTerms terms a side therefore do not launch: they append a LazyNode to the
+// calling thread's queue and return a ciphertext that points at it.  The queue is evaluated -- ONE csgn_small_ops launch
+// per dependency level, results side by side in one HBM block -- when a value is needed (getValues, decrypt, serialize,
+// an operation that is not deferred), when kDeferBatch operations have piled up, or when the thread ends.  A node keeps
+// its operands alive (payloads are immutable), so the caller's objects may die or be reassigned in between; results are
+// the words of the immediate path.  Ownership and ordering:
+//   1. `owner` is set when the node is made and never changes.  While the node is pending, owner->pending holds it: the
+//      cycle is intended, and a flush, or the failure at the thread's end, breaks it by clearing `pending`.
+//   2. `state` leaves kPending only under owner->lock, after `value` (kDone) or owner->error (kFailed) is written, by a
+//      release store; neither is written again.  Every other field is touched only under owner->lock.  A reader without
+//      the lock loads `state` with acquire and reads `value` or owner->error only after it has seen kDone or kFailed.
+//   3. No thread holds two queue locks: an operand pending in another thread's queue is evaluated through valueOf()
+//      before the caller's own queue is locked.
 const uint32_t kDeferMaxTerms = 8;
 const size_t kDeferBatch = 256;
 struct DeferQueue;
 struct LazyNode {
-    std::shared_ptr<DevicePayload> value;          // set once evaluated (under the queue's lock)
+    enum State { kPending, kDone, kFailed };
+    explicit LazyNode(const std::shared_ptr<DeferQueue> &q) : owner(q) {}
+    const std::shared_ptr<DeferQueue> owner;
+    std::atomic<int> state{kPending};
+    std::shared_ptr<DevicePayload> value;          // the result (kDone)
     std::shared_ptr<DevicePayload> pa, pb;         // finished operands ...
-    std::shared_ptr<LazyNode> la, lb;              // ... or operands still pending in the same queue
-    uint64_t n_bits, dl;
-    uint32_t t1, t2;
-    bool product;
-    DeferQueue *queue;                             // the queue that holds the node; nullptr once evaluated
-    int index, level;                              // scratch of the flush
+    std::shared_ptr<LazyNode> la, lb;              // ... or operands pending in the same queue
+    uint64_t n_bits = 0, dl = 0;
+    uint32_t t1 = 0, t2 = 0;
+    bool product = false;
+    int index = 0, level = 0;                      // scratch of the flush
 };
 // An operand: a finished payload or a pending node (exactly one of the two).  Returns nullptr when the operation is
 // not to be deferred (too large, deferral off, thread shutting down): the caller then computes at once.
 std::shared_ptr<LazyNode> deferSmallOp(bool product, uint64_t n_bits, uint64_t dl, uint64_t t1, uint64_t t2,
                                        const std::shared_ptr<DevicePayload> &pa, const std::shared_ptr<LazyNode> &la,
                                        const std::shared_ptr<DevicePayload> &pb, const std::shared_ptr<LazyNode> &lb);
-std::shared_ptr<DevicePayload> valueOf(const std::shared_ptr<LazyNode> &node);   // evaluates the node's queue if it has to
+std::shared_ptr<DevicePayload> valueOf(const std::shared_ptr<LazyNode> &node);   // evaluates the node's queue if it has to;
+                                                                                 // throws if that queue failed
 void flushDeferred();                  // the calling thread's queue
 void setDeferral(bool on);             // process-wide switch (Library::deferSmallOperations; CSGN_NO_DEFER=1 starts off)
 bool deferralOn();

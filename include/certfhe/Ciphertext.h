@@ -35,9 +35,9 @@ class SecretKey;
 class CiphertextBatch;
 
 class Ciphertext {
-    mutable std::shared_ptr<detail::DevicePayload> payload; // immutable once published
-    mutable std::shared_ptr<detail::LazyNode> lazy; // set instead of payload while the producing operation is queued
-    void resolve() const;                           // queue evaluated, payload set
+    std::shared_ptr<detail::DevicePayload> payload; // immutable once published
+    std::shared_ptr<detail::LazyNode> lazy;         // set instead of payload while the producing operation is queued
+    std::shared_ptr<detail::DevicePayload> current() const;   // payload, or the queued operation's result
     uint64_t len;                                   // words (T * dL)
     Context *certFHEcontext;                        // owned copy, may be null (default ctor)
 

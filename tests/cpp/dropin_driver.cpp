@@ -9,6 +9,7 @@
 //   dropin_driver circuit N D seed        deterministic add/mul chain, prints every stage
 //   dropin_driver bitlen                  non-canonical Bitlen propagation (left-operand rule)
 //   dropin_driver api                     copy/assign/in-place operator semantics, printing
+#include <atomic>
 #include <cassert>
 #include <chrono>
 #include <cstdio>
@@ -1011,6 +1012,89 @@ static int cmd_deferred_threads(int rounds)
     return 0;
 }
 
+static int cmd_deferred_exit(int rounds)
+{
+    // The deferred queue's hand-over between threads, against the same operations done one launch at a time:
+    //  - a worker queues 3-20 small operations (the record path, not the one-or-two-operation one), hands the results to
+    //    the main thread and ends; its queue is evaluated at its exit and the main thread reads and decrypts the results;
+    //  - one const ciphertext whose operations are still queued is read by 4 threads at once (a start barrier), each
+    //    through SecretKey::decrypt and serializedSize().
+    Library::initializeLibrary();
+    Context ctx(1247, 16);
+    SecretKey sk(ctx);
+    uint32_t rng = 777u;
+    auto next = [&]() { rng = rng * 1664525u + 1013904223u; return rng >> 8; };
+    auto words = [](const Ciphertext &c) {
+        const uint64_t *v = c.getValues();
+        return std::vector<uint64_t>(v, v + c.getLen());
+    };
+    for (int r = 0; r < rounds; ++r) {
+        std::vector<Ciphertext> fresh;
+        std::vector<int> bits;
+        for (int i = 0; i < 4; ++i) {
+            bits.push_back((int)(next() & 1u));
+            Plaintext pt(bits.back());
+            fresh.push_back(sk.encrypt(pt));
+        }
+        const int nops = 3 + (int)(next() % 18u);
+        const uint32_t seed = rng;
+        // operands of at most 8 terms a side (kDeferMaxTerms): every operation of the worker is queued
+        auto program = [&](std::vector<Ciphertext> &pool, std::vector<int> &pbits) {
+            rng = seed;
+            for (int k = 0; k < nops; ++k) {
+                size_t ia, ib;
+                do {
+                    ia = next() % pool.size();
+                    ib = next() % pool.size();
+                } while (pool[ia].getTerms() > 8 || pool[ib].getTerms() > 8);
+                const bool mul = (next() & 1u) != 0u;
+                pool.push_back(mul ? pool[ia] * pool[ib] : pool[ia] + pool[ib]);
+                pbits.push_back(mul ? (pbits[ia] & pbits[ib]) : (pbits[ia] ^ pbits[ib]));
+            }
+        };
+        std::vector<Ciphertext> want(fresh), got(fresh);
+        std::vector<int> want_bits(bits), got_bits(bits);
+        Library::deferSmallOperations(false);
+        program(want, want_bits);
+        Library::deferSmallOperations(true);
+        std::thread worker([&] { program(got, got_bits); });
+        worker.join();
+        EXPECT(got.size() == want.size() && got_bits == want_bits);
+        for (size_t i = 0; i < got.size(); ++i) {
+            EXPECT(words(got[i]) == words(want[i]));
+            EXPECT(sk.decrypt(got[i]).getValue() == (unsigned)want_bits[i]);
+        }
+
+        // four readers of one shared const ciphertext (sk's key mask is made above, so decrypt only reads sk)
+        const Ciphertext &a = fresh[0], &b = fresh[1], &c = fresh[2];
+        Library::deferSmallOperations(false);
+        const Ciphertext x_want = ((a * b) + c) * (a + c);
+        Library::deferSmallOperations(true);
+        const Ciphertext x = ((a * b) + c) * (a + c);          // queued in the main thread's queue
+        const unsigned x_bit = (unsigned)(((bits[0] & bits[1]) ^ bits[2]) & (bits[0] ^ bits[2]));
+        std::atomic<int> ready(0);
+        unsigned seen_bit[4];
+        uint64_t seen_size[4];
+        std::vector<std::thread> readers;
+        for (int t = 0; t < 4; ++t)
+            readers.emplace_back([&, t] {
+                ready.fetch_add(1);
+                while (ready.load() < 4)
+                    std::this_thread::yield();
+                // (decrypt takes the reference API's non-const reference; it only reads the ciphertext)
+                seen_bit[t] = sk.decrypt(const_cast<Ciphertext &>(x)).getValue();
+                seen_size[t] = x.serializedSize();
+            });
+        for (std::thread &t : readers)
+            t.join();
+        for (int t = 0; t < 4; ++t)
+            EXPECT(seen_bit[t] == x_bit && seen_size[t] == x_want.serializedSize());
+        EXPECT(words(x) == words(x_want));
+    }
+    printf("deferred exit ok rounds=%d\n", rounds);
+    return 0;
+}
+
 static int cmd_latency(int iters)
 {
     // steady-state cost of single operations through the value-semantic class API
@@ -1094,6 +1178,8 @@ int main(int argc, char **argv)
             return cmd_deferred(argc > 2 ? atoi(argv[2]) : 20);
         if (cmd == "deferred_threads")
             return cmd_deferred_threads(argc > 2 ? atoi(argv[2]) : 50);
+        if (cmd == "deferred_exit")
+            return cmd_deferred_exit(argc > 2 ? atoi(argv[2]) : 20);
         return 64;
     } catch (const std::exception &e) {
         fprintf(stderr, "certFHE error: %s\n", e.what());

@@ -70,6 +70,10 @@ def test_deferred_queue_equals_one_launch_per_operation(driver):
     # ... and a ciphertext whose operation is still queued in one host thread used as an operand in another
     p = run(driver, "deferred_threads", 50)
     assert "deferred threads ok rounds=50" in p.stdout
+    # ... a worker's queue evaluated when the worker ends, its results read by the main thread; and one queued const
+    # ciphertext decrypted and sized by 4 threads at once
+    p = run(driver, "deferred_exit", 20)
+    assert "deferred exit ok rounds=20" in p.stdout
 
 
 @pytest.mark.gpu
