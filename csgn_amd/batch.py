@@ -176,6 +176,24 @@ class HipPath:
         check(self.lib.csgn_const_fill(n_bits, batch, _ptr(plain), int(bit), _ptr(out), self.stream))
         return out[: batch * dl]
 
+    # -- bit-sliced integers ----------------------------------------------------------
+    def uint_step(self, n_bits: int, step: int, batch: int, a: torch.Tensor, t_a: int, b: torch.Tensor, t_b: int,
+                  x: Optional[torch.Tensor] = None, t_x: int = 0, carry: bool = True):
+        """csgn_uint_step: one of capi.CSGN_UINT_* over a uniform batch.  Returns the output tensor, or (sum, carry) for
+        the ADD steps when `carry` (carry=False passes a null carry pointer: the carry is not computed)."""
+        dl = self.default_len(n_bits)
+        has_carry = carry and step in (capi.CSGN_UINT_ADD_HALF, capi.CSGN_UINT_ADD_FULL)
+        terms0 = int(self.lib.csgn_uint_step_terms(step, 0, t_x, t_a, t_b))
+        terms1 = int(self.lib.csgn_uint_step_terms(step, 1, t_x, t_a, t_b)) if has_carry else 0
+        assert terms0 and (terms1 or not has_carry), "bad step or shape"
+        out0 = self.empty_words(max(batch * terms0 * dl, 1))
+        out1 = self.empty_words(max(batch * terms1 * dl, 1)) if has_carry else None
+        check(self.lib.csgn_uint_step(n_bits, step, batch, _ptr(x), t_x, _ptr(a), t_a, _ptr(b), t_b, _ptr(out0),
+                                      _ptr(out1), self.stream))
+        if has_carry:
+            return out0[: batch * terms0 * dl], out1[: batch * terms1 * dl]
+        return out0[: batch * terms0 * dl]
+
     def add_ragged(self, n_bits: int, left: torch.Tensor, off_left: torch.Tensor,
                    right: torch.Tensor, off_right: torch.Tensor,
                    total_terms_out: Optional[int] = None, max_t1: int = 0, max_t2: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -23,6 +23,9 @@ CSGN_ERR_HIP = -4
 CSGN_GATE_NOT, CSGN_GATE_XNOR, CSGN_GATE_NAND, CSGN_GATE_OR, CSGN_GATE_NOR, CSGN_GATE_MUX, \
     CSGN_GATE_ADD_PLAIN, CSGN_GATE_MUL_PLAIN = range(1, 9)
 
+# bit-sliced integers (include/csgn_hip.h, csgn_uint_step)
+CSGN_UINT_ADD_HALF, CSGN_UINT_ADD_FULL, CSGN_UINT_EQ_STEP, CSGN_UINT_LT_FIRST, CSGN_UINT_LT_STEP = range(1, 6)
+
 u64 = C.c_uint64
 vp = C.c_void_p
 
@@ -123,6 +126,9 @@ SIGNATURES = {
     "csgn_gate_uniform_kernel": (C.c_char_p, [u64, C.c_int, u64, u64, u64, u64]),
     "csgn_gate_uniform": (C.c_int, [u64, C.c_int, u64, u64, u64, u64, vp, vp, vp, vp, vp, vp]),
     "csgn_const_fill": (C.c_int, [u64, u64, vp, C.c_int, vp, vp]),
+    "csgn_uint_step_terms": (u64, [C.c_int, C.c_int, u64, u64, u64]),
+    "csgn_uint_step_kernel": (C.c_char_p, [u64, C.c_int, u64, u64, u64, u64]),
+    "csgn_uint_step": (C.c_int, [u64, C.c_int, u64, vp, u64, vp, u64, vp, u64, vp, vp, vp]),
     "csgn_set_tuning": (C.c_int, [C.c_char_p, C.c_int]),
     "csgn_get_tuning": (C.c_int, [C.c_char_p, C.POINTER(C.c_int)]),
     "csgn_reset_tuning": (None, []),

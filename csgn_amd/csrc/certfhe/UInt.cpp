@@ -1,0 +1,363 @@
+// UInt.cpp -- encrypted unsigned integers as bit-planes (extension, see UInt.h) over csgn_uint_step and the gates.
+#include "UInt.h"
+
+#include "Gates.h"
+#include "runtime.h"
+
+#include <stdexcept>
+#include <string>
+
+namespace certFHE {
+
+namespace detail {
+
+struct UIntAccess {
+    static CiphertextBatch make(const Context &c, uint64_t count, uint64_t terms) { return CiphertextBatch(c, count, terms); }
+    static uint64_t *words(CiphertextBatch &b) { return b.payload->data(); }
+};
+
+} // namespace detail
+
+using detail::UIntAccess;
+
+namespace {
+
+const uint64_t kMaxWords = 1ull << 31;   // per element, as in every csgn_*_uniform entry point
+
+void requireWidth(unsigned width, const char *who)
+{
+    if (width < 1 || width > 64)
+        throw std::invalid_argument(std::string("certFHE::UIntBatch::") + who + ": width must be 1..64");
+}
+
+std::vector<unsigned char> bitPlane(const std::vector<uint64_t> &values, unsigned j)
+{
+    std::vector<unsigned char> bits(values.size());
+    for (size_t i = 0; i < values.size(); ++i)
+        bits[i] = (unsigned char)((values[i] >> j) & 1u);
+    return bits;
+}
+
+void requireFits(const std::vector<uint64_t> &values, unsigned width, const char *who)
+{
+    requireWidth(width, who);
+    for (size_t i = 0; i < values.size(); ++i)
+        if (width < 64 && values[i] >> width)
+            throw std::invalid_argument(std::string("certFHE::UIntBatch::") + who + ": a value does not fit in the width");
+}
+
+bool sameContext(const Context &x, const Context &y) { return x.getN() == y.getN() && x.getD() == y.getD(); }
+
+void requireSame(const UIntBatch &a, const UIntBatch &b, const char *who)
+{
+    if (a.width() != b.width() || a.size() != b.size() || !sameContext(a.context(), b.context()))
+        throw std::invalid_argument(std::string("certFHE::") + who + ": operands differ in width, count or context");
+}
+
+void requireSameBit(const CiphertextBatch &s, const UIntBatch &a, const char *who)
+{
+    if (s.size() != a.size() || !sameContext(s.context(), a.context()))
+        throw std::invalid_argument(std::string("certFHE::") + who + ": selector differs in count or context");
+}
+
+// ------------------------------------------------------------------ sizes, before anything is launched
+
+// terms per element of a plane (a ragged plane: its largest element, a bound for everything computed from it)
+uint64_t termsOf(const CiphertextBatch &b)
+{
+    if (b.uniform())
+        return b.terms();
+    uint64_t m = 0;
+    for (uint64_t i = 0; i < b.size(); ++i)
+        m = b.termsOf(i) > m ? b.termsOf(i) : m;
+    return m;
+}
+
+// a step's size, checked against the ABI's limit
+uint64_t checked(uint64_t terms, const Context &ctx, const char *who)
+{
+    if (terms == 0 || terms > (kMaxWords - 1) / ctx.getDefaultN())
+        throw std::invalid_argument(std::string("certFHE::") + who +
+                                    ": a step's result exceeds 2^31 words per element (the width is too large)");
+    return terms;
+}
+
+uint64_t stepTerms(int step, int output, uint64_t tx, uint64_t ta, uint64_t tb, const Context &ctx, const char *who)
+{
+    return checked(csgn_uint_step_terms(step, output, tx, ta, tb), ctx, who);
+}
+
+uint64_t gateTerms(int gate, uint64_t ts, uint64_t ta, uint64_t tb, const Context &ctx, const char *who)
+{
+    return checked(csgn_gate_terms(gate, ts, ta, tb), ctx, who);
+}
+
+// ------------------------------------------------------------------ one step
+
+CiphertextBatch ones(const CiphertextBatch &like)
+{
+    return constantBatch(like.context(), std::vector<unsigned char>(like.size(), 1));
+}
+
+bool allUniform(const CiphertextBatch *x, const CiphertextBatch &a, const CiphertextBatch &b)
+{
+    return (!x || x->uniform()) && a.uniform() && b.uniform();
+}
+
+// out[0] = the step's output 0, out[1] = the carry when `carry` (ADD steps)
+std::vector<CiphertextBatch> step(int st, const CiphertextBatch *x, const CiphertextBatch &a, const CiphertextBatch &b,
+                                  bool carry)
+{
+    std::vector<CiphertextBatch> out;
+    if (allUniform(x, a, b)) {
+        const uint64_t tx = x ? x->terms() : 0, ta = a.terms(), tb = b.terms();
+        out.push_back(UIntAccess::make(a.context(), a.size(), csgn_uint_step_terms(st, 0, tx, ta, tb)));
+        if (carry)
+            out.push_back(UIntAccess::make(a.context(), a.size(), csgn_uint_step_terms(st, 1, tx, ta, tb)));
+        if (a.size())
+            detail::check(csgn_uint_step(a.context().getN(), st, a.size(), x ? x->deviceValues() : nullptr, tx,
+                                         a.deviceValues(), ta, b.deviceValues(), tb, UIntAccess::words(out[0]),
+                                         carry ? UIntAccess::words(out[1]) : nullptr, detail::stream()),
+                          "csgn_uint_step");
+        return out;
+    }
+    // ragged: the definition itself through the batch operators
+    switch (st) {
+    case CSGN_UINT_ADD_HALF:
+        out.push_back(a + b);
+        if (carry)
+            out.push_back(a * b);
+        break;
+    case CSGN_UINT_ADD_FULL: {
+        const CiphertextBatch ab = a + b;
+        out.push_back(ab + *x);
+        if (carry)
+            out.push_back((a * b) + (ab * *x));
+        break;
+    }
+    case CSGN_UINT_EQ_STEP: out.push_back(*x * ((a + b) + ones(a))); break;
+    case CSGN_UINT_LT_FIRST: out.push_back((a + ones(a)) * b); break;
+    default: out.push_back(((a + b) * (b + *x)) + *x); break;
+    }
+    return out;
+}
+
+// ------------------------------------------------------------------ whole operations
+
+std::vector<CiphertextBatch> add(const UIntBatch &a, const UIntBatch &b)
+{
+    const Context &ctx = a.context();
+    const unsigned w = a.width();
+    uint64_t c = stepTerms(CSGN_UINT_ADD_HALF, 0, 0, termsOf(a.plane(0)), termsOf(b.plane(0)), ctx, "operator+");
+    if (w > 1)
+        c = stepTerms(CSGN_UINT_ADD_HALF, 1, 0, termsOf(a.plane(0)), termsOf(b.plane(0)), ctx, "operator+");
+    for (unsigned j = 1; j < w; ++j) {
+        const uint64_t ta = termsOf(a.plane(j)), tb = termsOf(b.plane(j));
+        stepTerms(CSGN_UINT_ADD_FULL, 0, c, ta, tb, ctx, "operator+");
+        if (j + 1 < w)
+            c = stepTerms(CSGN_UINT_ADD_FULL, 1, c, ta, tb, ctx, "operator+");
+    }
+    std::vector<CiphertextBatch> r = step(CSGN_UINT_ADD_HALF, nullptr, a.plane(0), b.plane(0), w > 1);
+    std::vector<CiphertextBatch> out(1, r[0]);
+    for (unsigned j = 1; j < w; ++j) {
+        const CiphertextBatch carry = r[1];
+        r = step(CSGN_UINT_ADD_FULL, &carry, a.plane(j), b.plane(j), j + 1 < w);
+        out.push_back(r[0]);
+    }
+    return out;
+}
+
+std::vector<CiphertextBatch> sub(const UIntBatch &a, const UIntBatch &b)
+{
+    const Context &ctx = a.context();
+    const unsigned w = a.width();
+    uint64_t c = 1;
+    for (unsigned j = 0; j < w; ++j) {
+        const uint64_t ta = termsOf(a.plane(j)), tnb = gateTerms(CSGN_GATE_NOT, 0, termsOf(b.plane(j)), 0, ctx, "operator-");
+        stepTerms(CSGN_UINT_ADD_FULL, 0, c, ta, tnb, ctx, "operator-");
+        if (j + 1 < w)
+            c = stepTerms(CSGN_UINT_ADD_FULL, 1, c, ta, tnb, ctx, "operator-");
+    }
+    CiphertextBatch carry = ones(a.plane(0));                // a + ~b + 1: the first carry in is ONE
+    std::vector<CiphertextBatch> out;
+    for (unsigned j = 0; j < w; ++j) {
+        const std::vector<CiphertextBatch> r = step(CSGN_UINT_ADD_FULL, &carry, a.plane(j), logicNot(b.plane(j)), j + 1 < w);
+        out.push_back(r[0]);
+        if (j + 1 < w)
+            carry = r[1];
+    }
+    return out;
+}
+
+// sizes of lessThan(a, b)'s steps, checked; returns the result's terms
+uint64_t lessThanTerms(const UIntBatch &a, const UIntBatch &b, const char *who)
+{
+    const Context &ctx = a.context();
+    uint64_t l = stepTerms(CSGN_UINT_LT_FIRST, 0, 0, termsOf(a.plane(0)), termsOf(b.plane(0)), ctx, who);
+    for (unsigned j = 1; j < a.width(); ++j)
+        l = stepTerms(CSGN_UINT_LT_STEP, 0, l, termsOf(a.plane(j)), termsOf(b.plane(j)), ctx, who);
+    return l;
+}
+
+CiphertextBatch lessThanUnchecked(const UIntBatch &a, const UIntBatch &b)
+{
+    CiphertextBatch l = step(CSGN_UINT_LT_FIRST, nullptr, a.plane(0), b.plane(0), false)[0];
+    for (unsigned j = 1; j < a.width(); ++j)
+        l = step(CSGN_UINT_LT_STEP, &l, a.plane(j), b.plane(j), false)[0];
+    return l;
+}
+
+uint64_t equalToTerms(const UIntBatch &a, const UIntBatch &b, const char *who)
+{
+    const Context &ctx = a.context();
+    uint64_t e = gateTerms(CSGN_GATE_XNOR, 0, termsOf(a.plane(0)), termsOf(b.plane(0)), ctx, who);
+    for (unsigned j = 1; j < a.width(); ++j)
+        e = stepTerms(CSGN_UINT_EQ_STEP, 0, e, termsOf(a.plane(j)), termsOf(b.plane(j)), ctx, who);
+    return e;
+}
+
+CiphertextBatch equalToUnchecked(const UIntBatch &a, const UIntBatch &b)
+{
+    CiphertextBatch e = logicXnor(a.plane(0), b.plane(0));
+    for (unsigned j = 1; j < a.width(); ++j)
+        e = step(CSGN_UINT_EQ_STEP, &e, a.plane(j), b.plane(j), false)[0];
+    return e;
+}
+
+} // namespace
+
+// ------------------------------------------------------------------ UIntBatch
+
+UIntBatch::UIntBatch(const std::vector<CiphertextBatch> &planes) : planes_(planes) {}
+
+UIntBatch UIntBatch::encrypt(const SecretKey &key, const std::vector<uint64_t> &values, unsigned width)
+{
+    requireFits(values, width, "encrypt");
+    std::vector<CiphertextBatch> planes;
+    for (unsigned j = 0; j < width; ++j)
+        planes.push_back(CiphertextBatch::encrypt(key, bitPlane(values, j)));
+    return UIntBatch(planes);
+}
+
+UIntBatch UIntBatch::encrypt(const SecretKey &key, const std::vector<uint64_t> &values, unsigned width, uint64_t seed)
+{
+    requireFits(values, width, "encrypt");
+    std::vector<CiphertextBatch> planes;
+    for (unsigned j = 0; j < width; ++j)
+        planes.push_back(CiphertextBatch::encrypt(key, bitPlane(values, j), seed, (uint64_t)j * values.size()));
+    return UIntBatch(planes);
+}
+
+UIntBatch UIntBatch::constant(const Context &context, const std::vector<uint64_t> &values, unsigned width)
+{
+    requireFits(values, width, "constant");
+    std::vector<CiphertextBatch> planes;
+    for (unsigned j = 0; j < width; ++j)
+        planes.push_back(constantBatch(context, bitPlane(values, j)));
+    return UIntBatch(planes);
+}
+
+UIntBatch UIntBatch::fromPlanes(const std::vector<CiphertextBatch> &planes)
+{
+    requireWidth((unsigned)(planes.size() > 64 ? 65 : planes.size()), "fromPlanes");
+    for (size_t j = 1; j < planes.size(); ++j)
+        if (planes[j].size() != planes[0].size() || !sameContext(planes[j].context(), planes[0].context()))
+            throw std::invalid_argument("certFHE::UIntBatch::fromPlanes: planes differ in count or context");
+    return UIntBatch(planes);
+}
+
+const CiphertextBatch &UIntBatch::plane(unsigned j) const
+{
+    if (j >= planes_.size())
+        throw std::out_of_range("certFHE::UIntBatch::plane");
+    return planes_[j];
+}
+
+UIntBatch UIntBatch::compact() const
+{
+    std::vector<CiphertextBatch> planes;
+    for (size_t j = 0; j < planes_.size(); ++j)
+        planes.push_back(planes_[j].compact());
+    return UIntBatch(planes);
+}
+
+std::vector<uint64_t> UIntBatch::decrypt(const SecretKey &key) const
+{
+    std::vector<uint64_t> values(size(), 0);
+    for (unsigned j = 0; j < width(); ++j) {
+        const std::vector<unsigned char> bits = planes_[j].decrypt(key);
+        for (size_t i = 0; i < values.size(); ++i)
+            values[i] |= (uint64_t)(bits[i] & 1u) << j;
+    }
+    return values;
+}
+
+UIntBatch UIntBatch::operator+(const UIntBatch &rhs) const
+{
+    requireSame(*this, rhs, "UIntBatch::operator+");
+    return UIntBatch(add(*this, rhs));
+}
+
+UIntBatch UIntBatch::operator-(const UIntBatch &rhs) const
+{
+    requireSame(*this, rhs, "UIntBatch::operator-");
+    return UIntBatch(sub(*this, rhs));
+}
+
+// ------------------------------------------------------------------ comparisons and select
+
+CiphertextBatch equalTo(const UIntBatch &a, const UIntBatch &b)
+{
+    requireSame(a, b, "equalTo");
+    equalToTerms(a, b, "equalTo");
+    return equalToUnchecked(a, b);
+}
+
+CiphertextBatch notEqualTo(const UIntBatch &a, const UIntBatch &b)
+{
+    requireSame(a, b, "notEqualTo");
+    gateTerms(CSGN_GATE_NOT, 0, equalToTerms(a, b, "notEqualTo"), 0, a.context(), "notEqualTo");
+    return logicNot(equalToUnchecked(a, b));
+}
+
+CiphertextBatch lessThan(const UIntBatch &a, const UIntBatch &b)
+{
+    requireSame(a, b, "lessThan");
+    lessThanTerms(a, b, "lessThan");
+    return lessThanUnchecked(a, b);
+}
+
+CiphertextBatch greaterThan(const UIntBatch &a, const UIntBatch &b)
+{
+    requireSame(a, b, "greaterThan");
+    lessThanTerms(b, a, "greaterThan");
+    return lessThanUnchecked(b, a);
+}
+
+CiphertextBatch lessEqual(const UIntBatch &a, const UIntBatch &b)
+{
+    requireSame(a, b, "lessEqual");
+    gateTerms(CSGN_GATE_NOT, 0, lessThanTerms(b, a, "lessEqual"), 0, a.context(), "lessEqual");
+    return logicNot(lessThanUnchecked(b, a));
+}
+
+CiphertextBatch greaterEqual(const UIntBatch &a, const UIntBatch &b)
+{
+    requireSame(a, b, "greaterEqual");
+    gateTerms(CSGN_GATE_NOT, 0, lessThanTerms(a, b, "greaterEqual"), 0, a.context(), "greaterEqual");
+    return logicNot(lessThanUnchecked(a, b));
+}
+
+UIntBatch select(const CiphertextBatch &sel, const UIntBatch &a, const UIntBatch &b)
+{
+    requireSame(a, b, "select");
+    requireSameBit(sel, a, "select");
+    for (unsigned j = 0; j < a.width(); ++j)
+        gateTerms(CSGN_GATE_MUX, termsOf(sel), termsOf(a.plane(j)), termsOf(b.plane(j)), a.context(), "select");
+    std::vector<CiphertextBatch> planes;
+    for (unsigned j = 0; j < a.width(); ++j)
+        planes.push_back(logicMux(sel, a.plane(j), b.plane(j)));
+    return UIntBatch::fromPlanes(planes);
+}
+
+} // namespace certFHE

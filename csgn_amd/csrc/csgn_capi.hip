@@ -1042,6 +1042,49 @@ int csgn_const_fill(uint64_t n_bits, uint64_t batch, const uint8_t *d_plain, int
     return CSGN_OK;
 }
 
+/* ---------------------------------------------------------------- integers ---- */
+
+uint64_t csgn_uint_step_terms(int step, int output, uint64_t t_x, uint64_t t_a, uint64_t t_b)
+{
+    return csgn::uint_step_terms(step, output, t_x, t_a, t_b);
+}
+
+const char *csgn_uint_step_kernel(uint64_t n_bits, int step, uint64_t batch, uint64_t t_x, uint64_t t_a, uint64_t t_b)
+{
+    return csgn::uint_step_kernel_name(n_bits, step, batch, t_x, t_a, t_b);
+}
+
+int csgn_uint_step(uint64_t n_bits, int step, uint64_t batch, const uint64_t *d_x, uint64_t t_x, const uint64_t *d_a,
+                   uint64_t t_a, const uint64_t *d_b, uint64_t t_b, uint64_t *d_out0, uint64_t *d_out1, void *stream)
+{
+    if (int rc = check_n(n_bits))
+        return rc;
+    REQUIRE(step >= CSGN_UINT_ADD_HALF && step <= CSGN_UINT_LT_STEP, "unknown integer step %d", step);
+    const bool uses_x = step != CSGN_UINT_ADD_HALF && step != CSGN_UINT_LT_FIRST;
+    const bool carry = (step == CSGN_UINT_ADD_HALF || step == CSGN_UINT_ADD_FULL) && d_out1;
+    if (!uses_x)
+        t_x = 0;
+    const uint64_t terms0 = csgn::uint_step_terms(step, 0, t_x, t_a, t_b);
+    const uint64_t terms1 = carry ? csgn::uint_step_terms(step, 1, t_x, t_a, t_b) : 0;
+    REQUIRE(terms0 != 0 && (terms1 != 0 || !carry),
+            "integer step %d: an operand it reads has no terms, or the term count overflows", step);
+    const uint64_t dl = csgn_default_len(n_bits);
+    const uint64_t terms = terms0 > terms1 ? terms0 : terms1;
+    if (!product_below(terms, dl, 1, 1ull << 31))
+        return fail(CSGN_ERR_UNSUPPORTED, "integer step %d: %llu terms per element exceed 2^31 words", step,
+                    (unsigned long long)terms);
+    if (!product_below(batch, terms0 + terms1, dl, 1ull << 60))
+        return fail(CSGN_ERR_UNSUPPORTED, "batch of %llu elements: size overflows", (unsigned long long)batch);
+    if (int rc = require_device("csgn_uint_step"))
+        return rc;
+    if (batch == 0)
+        return CSGN_OK;
+    REQUIRE(d_out0 && d_a && d_b && (d_x || !uses_x), "null device pointer");
+    HIP_TRY(csgn::uint_step(n_bits, step, batch, uses_x ? (const u64 *)d_x : nullptr, t_x, (const u64 *)d_a, t_a,
+                            (const u64 *)d_b, t_b, (u64 *)d_out0, carry ? (u64 *)d_out1 : nullptr, S(stream)));
+    return CSGN_OK;
+}
+
 /* ------------------------------------------------------------------ tuning ---- */
 
 int csgn_set_tuning(const char *key, int value)

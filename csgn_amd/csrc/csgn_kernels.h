@@ -127,6 +127,12 @@ hipError_t const_fill(u64 n_bits, u64 batch, const uint8_t *plain, int bit, u64 
 hipError_t gate_uniform(u64 n_bits, int gate, u64 batch, u64 ts, u64 ta, u64 tb, const u64 *S, const u64 *A,
                         const u64 *B, const uint8_t *plain, u64 *out, hipStream_t s);
 
+// one per-bit step of the bit-sliced integers over uniform batches (csgn_uint.hip); step = CSGN_UINT_* of include/csgn_hip.h
+u64 uint_step_terms(int step, int output, u64 tx, u64 ta, u64 tb);   // 0: bad step / output, zero term count or overflow
+const char *uint_step_kernel_name(u64 n_bits, int step, u64 batch, u64 tx, u64 ta, u64 tb);
+hipError_t uint_step(u64 n_bits, int step, u64 batch, const u64 *X, u64 tx, const u64 *A, u64 ta, const u64 *B, u64 tb,
+                     u64 *out0, u64 *out1, hipStream_t s);
+
 hipError_t small_ops(u64 n_bits, u64 count, const ::csgn_small_op *ops, hipStream_t s);
 size_t decrypt_scratch_bytes(u64 batch, u64 total_terms);
 // out[i] = a[i] & b[i] (is_product) or a[i] ^ b[i]: Dec(a*b) = Dec(a) & Dec(b), Dec(a+b) = Dec(a) ^ Dec(b)

@@ -49,6 +49,7 @@ enum TuneKey {
     TUNE_COMPACT_STAGGER_US, // compaction: microseconds by which every second workgroup of the main kernel starts late (phases of the two workgroups of a CU interleave), 0 = together
     TUNE_ZERO_MEMSET,    // dev: 1 = zero fills on capturable paths are hipMemsetAsync (memset NODES in a circuit's graph) instead of the k_zero_words kernel (csgn_device.h, zero_words; tools/graph_memset_probe.hip)
     TUNE_GATE_FUSED,     // uniform gates (csgn_gates.hip): -1 = per shape, 0 = pitched form (the tuned launchers into the output's slices), 1 = fused kernel
+    TUNE_UINT_FUSED,     // integer steps (csgn_uint.hip): -1 = per shape, 0 = pitched form where the step has one, 1 = fused kernel
     TUNE_COUNT
 };
 

@@ -27,11 +27,13 @@ namespace certFHE {
 class BatchCircuit;
 namespace detail {
 struct GateAccess;   // Gates.cpp
+struct UIntAccess;   // UInt.cpp
 }
 
 class CiphertextBatch {
     friend class BatchCircuit;
     friend struct detail::GateAccess;
+    friend struct detail::UIntAccess;
     std::shared_ptr<detail::DevicePayload> payload;   // total terms * dL words, element after element
     uint64_t count_;
     uint64_t terms_;                                   // per element when uniform; 0 when ragged

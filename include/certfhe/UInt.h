@@ -1,0 +1,76 @@
+// certfhe/UInt.h -- EXTENSION (not in the reference): encrypted unsigned integers as bit-planes over CiphertextBatch.
+//
+// A w-bit value is w planes: plane j is bit j, least significant first, and each plane is a CiphertextBatch of
+// `size()` elements.  Every operation is a composition of the reference's operator+ / operator* with the ONE term of
+// Gates.h, in exactly this order, so its words are pinned the same way the gates are (include/csgn_hip.h, the table
+// of csgn_uint_step):
+//     a + b              ADD_HALF on plane 0, ADD_FULL on planes 1..w-1 (the last computes no carry)   mod 2^w
+//     a - b              nb_j = logicNot(b_j), carry ONE, ADD_FULL on every plane: a + ~b + 1          mod 2^w
+//     equalTo(a, b)      e = logicXnor(a_0, b_0), then EQ_STEP on planes 1..w-1
+//     lessThan(a, b)     LT_FIRST on plane 0, then LT_STEP: l = logicMux(a_j + b_j, b_j, l)
+//     notEqualTo         logicNot(equalTo(a, b))
+//     greaterThan        lessThan(b, a)
+//     lessEqual          logicNot(lessThan(b, a))
+//     greaterEqual       logicNot(lessThan(a, b))
+//     select(s, a, b)    logicMux(s, a_j, b_j) on every plane                                          s ? a : b
+//
+// SIZES GROW WITH WIDTH -- the scheme's own nature: with fresh 1-term planes the top plane of a sum has 2^(w-1) + 1
+// terms, an equality 3^w and a less-than 3^w - 1 (at N=1247, 160 bytes a term: an 8-bit equality is about 1 MB per
+// element).  compact() shrinks planes by their duplicate terms.  Every operation computes every step's size before it
+// launches anything; a step above 2^31 words per element throws std::invalid_argument, and nothing is allocated.
+//
+// Uniform planes run one csgn_uint_step (or csgn_gate_uniform) call per bit; ragged ones (what compact() may return)
+// are composed from the CiphertextBatch operators and Gates.h, with the same words.  Only the running carry or
+// accumulator is kept alive between bits.
+#ifndef CERTFHE_UINT_H
+#define CERTFHE_UINT_H
+
+#include <stdint.h>
+
+#include <vector>
+
+#include "Batch.h"
+#include "Context.h"
+#include "SecretKey.h"
+
+namespace certFHE {
+
+class UIntBatch {
+    std::vector<CiphertextBatch> planes_;
+    explicit UIntBatch(const std::vector<CiphertextBatch> &planes);
+
+  public:
+    // values[i] < 2^width, width in 1..64 (std::invalid_argument otherwise).  Plane j encrypts bit j of every value.
+    static UIntBatch encrypt(const SecretKey &key, const std::vector<uint64_t> &values, unsigned width);
+    // REPRODUCIBLE form (tests, benchmarks): plane j is CiphertextBatch::encrypt(key, bits_j, seed, j * values.size())
+    static UIntBatch encrypt(const SecretKey &key, const std::vector<uint64_t> &values, unsigned width, uint64_t seed);
+    // trivial encryptions (Gates.h constantBatch per plane): their values are public
+    static UIntBatch constant(const Context &context, const std::vector<uint64_t> &values, unsigned width);
+    // planes[j] is bit j; 1..64 planes of one context and element count
+    static UIntBatch fromPlanes(const std::vector<CiphertextBatch> &planes);
+
+    const CiphertextBatch &plane(unsigned j) const;   // std::out_of_range past width()
+    unsigned width() const { return (unsigned)planes_.size(); }
+    uint64_t size() const { return planes_[0].size(); }
+    const Context &context() const { return planes_[0].context(); }
+    UIntBatch compact() const;                          // CiphertextBatch::compact on every plane
+    std::vector<uint64_t> decrypt(const SecretKey &key) const;
+
+    // modulo 2^width; both operands of one width, context and element count
+    UIntBatch operator+(const UIntBatch &rhs) const;
+    UIntBatch operator-(const UIntBatch &rhs) const;
+};
+
+// one encrypted bit per element
+CiphertextBatch equalTo(const UIntBatch &a, const UIntBatch &b);
+CiphertextBatch notEqualTo(const UIntBatch &a, const UIntBatch &b);
+CiphertextBatch lessThan(const UIntBatch &a, const UIntBatch &b);
+CiphertextBatch lessEqual(const UIntBatch &a, const UIntBatch &b);
+CiphertextBatch greaterThan(const UIntBatch &a, const UIntBatch &b);
+CiphertextBatch greaterEqual(const UIntBatch &a, const UIntBatch &b);
+// element i: sel[i] ? a[i] : b[i]
+UIntBatch select(const CiphertextBatch &sel, const UIntBatch &a, const UIntBatch &b);
+
+} // namespace certFHE
+
+#endif

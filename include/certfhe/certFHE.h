@@ -12,5 +12,6 @@
 #include "Timer.h"
 #include "Batch.h"   // extension: device-resident uniform batches
 #include "Gates.h"   // extension: plaintext constants and the boolean gates
+#include "UInt.h"    // extension: bit-sliced encrypted unsigned integers
 
 #endif

@@ -603,6 +603,39 @@ int csgn_gate_uniform(uint64_t n_bits, int gate, uint64_t batch, uint64_t t_sel,
  * CSGN_ERR_NO_DEVICE. */
 int csgn_const_fill(uint64_t n_bits, uint64_t batch, const uint8_t *d_plain, int bit, uint64_t *d_out, void *stream);
 
+/* ----------------------------------------------------------- integers ---- */
+
+/* Bit-sliced encrypted unsigned integers: a w-bit value is w planes, plane j = bit j (least significant first), each a
+ * uniform batch.  Whole operations (certfhe/UInt.h) are chains of the per-bit STEPS below, each a composition of the
+ * reference's operator+ / operator* with ONE (the gates above), in this order; x is the running value (carry,
+ * equality or less-than so far):
+ *     ADD_HALF(a, b)       out0 s = a + b                        ta + tb
+ *                          out1 c = a * b                        ta*tb
+ *     ADD_FULL(x=c, a, b)  out0 s = (a + b) + c                  ta + tb + tx
+ *                          out1 c' = (a * b) + ((a + b) * c)     ta*tb + (ta + tb)*tx
+ *     EQ_STEP(x=e, a, b)   out0 e' = e * ((a + b) + ONE)         tx*(ta + tb + 1)
+ *     LT_FIRST(a, b)       out0 l = (a + ONE) * b                (ta + 1)*tb
+ *     LT_STEP(x=l, a, b)   out0 l' = ((a + b) * (b + l)) + l     (ta + tb)*(tb + tx) + tx
+ * ADD_HALF and LT_FIRST do not read x (t_x and d_x are ignored). */
+enum { CSGN_UINT_ADD_HALF = 1, CSGN_UINT_ADD_FULL, CSGN_UINT_EQ_STEP, CSGN_UINT_LT_FIRST, CSGN_UINT_LT_STEP };
+/* Terms per element of one output of a step (host only).  0: unknown step or output (only the ADD steps have output 1),
+ * a term count of 0 in an operand the step reads, or overflow. */
+uint64_t csgn_uint_step_terms(int step, int output, uint64_t t_x, uint64_t t_a, uint64_t t_b);
+/* Which form a csgn_uint_step call of this shape takes (host only, a static string): "k_uint_step" (one kernel: every
+ * segment of both outputs in one pass, operands read once, ONE made in registers) or "pitched" (the tuned
+ * csgn_mul_uniform / csgn_add_uniform launchers writing into the outputs' slices; no
+ * intermediate buffer).  Knob "uint_fused" (-1 per shape, 0 / 1 forced) decides; the words are the same.  A step whose
+ * product rows interleave -- a concatenated right operand under a left operand of more than one term (EQ_STEP with
+ * t_x > 1, LT_STEP with t_a or t_b > 1) -- is always fused.  "" for an invalid step or shape. */
+const char *csgn_uint_step_kernel(uint64_t n_bits, int step, uint64_t batch, uint64_t t_x, uint64_t t_a, uint64_t t_b);
+/* One step over `batch` elements: d_out0 = batch * csgn_uint_step_terms(step, 0, ...) * dL words, d_out1 (the carry of
+ * the ADD steps) likewise for output 1, element after element.  d_out1 may be NULL: the carry is then neither computed
+ * nor read; the other steps ignore it.  d_a and d_b may alias each other; no output overlaps an input.  Limits: each
+ * output below 2^31 words per element (CSGN_ERR_UNSUPPORTED), batch * that < 2^60.  On the caller's stream,
+ * asynchronous.  No GPU: CSGN_ERR_NO_DEVICE, no CPU fallback. */
+int csgn_uint_step(uint64_t n_bits, int step, uint64_t batch, const uint64_t *d_x, uint64_t t_x, const uint64_t *d_a,
+                   uint64_t t_a, const uint64_t *d_b, uint64_t t_b, uint64_t *d_out0, uint64_t *d_out1, void *stream);
+
 /* ------------------------------------------------------------------- tuning ---- */
 
 /* Kernel-choice and sweep knobs ("mul_flat", "mul_touch", "ragged_c", "perm_ballot", ...;
