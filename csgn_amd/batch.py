@@ -194,6 +194,20 @@ class HipPath:
             return out0[: batch * terms0 * dl], out1[: batch * terms1 * dl]
         return out0[: batch * terms0 * dl]
 
+    def uint_plain(self, n_bits: int, cmp: int, batch: int, planes, terms, k: int) -> torch.Tensor:
+        """csgn_uint_plain: one of capi.CSGN_UINT_PLAIN_* of the w-bit integer `planes` (bit 0 first; plane j a uniform
+        batch of terms[j] terms per element) against the public constant k.  Returns the output tensor."""
+        w = len(planes)
+        assert w == len(terms)
+        h_terms = (C.c_uint64 * max(w, 1))(*[int(t) for t in terms])
+        h_planes = (C.c_void_p * max(w, 1))(*[_ptr(p) for p in planes])
+        total = int(self.lib.csgn_uint_plain_terms(cmp, w, k, h_terms))
+        assert total, "bad comparison or shape"
+        dl = self.default_len(n_bits)
+        out = self.empty_words(max(batch * total * dl, 1))
+        check(self.lib.csgn_uint_plain(n_bits, cmp, batch, w, k, h_planes, h_terms, _ptr(out), self.stream))
+        return out[: batch * total * dl]
+
     def add_ragged(self, n_bits: int, left: torch.Tensor, off_left: torch.Tensor,
                    right: torch.Tensor, off_right: torch.Tensor,
                    total_terms_out: Optional[int] = None, max_t1: int = 0, max_t2: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:

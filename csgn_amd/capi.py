@@ -25,6 +25,9 @@ CSGN_GATE_NOT, CSGN_GATE_XNOR, CSGN_GATE_NAND, CSGN_GATE_OR, CSGN_GATE_NOR, CSGN
 
 # bit-sliced integers (include/csgn_hip.h, csgn_uint_step)
 CSGN_UINT_ADD_HALF, CSGN_UINT_ADD_FULL, CSGN_UINT_EQ_STEP, CSGN_UINT_LT_FIRST, CSGN_UINT_LT_STEP = range(1, 6)
+# comparisons against a public constant (include/csgn_hip.h, csgn_uint_plain)
+CSGN_UINT_PLAIN_EQ, CSGN_UINT_PLAIN_NE, CSGN_UINT_PLAIN_LT, CSGN_UINT_PLAIN_LE, CSGN_UINT_PLAIN_GT, \
+    CSGN_UINT_PLAIN_GE = range(1, 7)
 
 u64 = C.c_uint64
 vp = C.c_void_p
@@ -129,6 +132,9 @@ SIGNATURES = {
     "csgn_uint_step_terms": (u64, [C.c_int, C.c_int, u64, u64, u64]),
     "csgn_uint_step_kernel": (C.c_char_p, [u64, C.c_int, u64, u64, u64, u64]),
     "csgn_uint_step": (C.c_int, [u64, C.c_int, u64, vp, u64, vp, u64, vp, u64, vp, vp, vp]),
+    "csgn_uint_plain_terms": (u64, [C.c_int, u64, u64, C.POINTER(u64)]),
+    "csgn_uint_plain_kernel": (C.c_char_p, [u64, C.c_int, u64, u64, u64, C.POINTER(u64)]),
+    "csgn_uint_plain": (C.c_int, [u64, C.c_int, u64, u64, u64, C.POINTER(vp), C.POINTER(u64), vp, vp]),
     "csgn_set_tuning": (C.c_int, [C.c_char_p, C.c_int]),
     "csgn_get_tuning": (C.c_int, [C.c_char_p, C.POINTER(C.c_int)]),
     "csgn_reset_tuning": (None, []),

@@ -224,6 +224,60 @@ CiphertextBatch equalToUnchecked(const UIntBatch &a, const UIntBatch &b)
     return e;
 }
 
+// ------------------------------------------------------------------ comparisons with a public constant
+
+CiphertextBatch comparePlain(int cmp, const UIntBatch &a, uint64_t k, const char *who)
+{
+    const unsigned w = a.width();
+    if (w < 64 && (k >> w) != 0)
+        throw std::invalid_argument(std::string("certFHE::") + who + ": the constant does not fit in the width");
+    const Context &ctx = a.context();
+    std::vector<uint64_t> terms(w);
+    bool uniform = true;
+    for (unsigned j = 0; j < w; ++j) {
+        terms[j] = termsOf(a.plane(j));                  // a ragged plane: its largest element, a bound
+        uniform = uniform && a.plane(j).uniform();
+    }
+    const uint64_t total = checked(csgn_uint_plain_terms(cmp, w, k, terms.data()), ctx, who);
+    if (uniform) {
+        CiphertextBatch out = UIntAccess::make(ctx, a.size(), total);
+        if (a.size()) {
+            std::vector<const uint64_t *> planes(w);
+            for (unsigned j = 0; j < w; ++j)
+                planes[j] = a.plane(j).deviceValues();
+            detail::check(csgn_uint_plain(ctx.getN(), cmp, a.size(), w, k, planes.data(), terms.data(),
+                                          UIntAccess::words(out), detail::stream()),
+                          "csgn_uint_plain");
+        }
+        return out;
+    }
+    // ragged: the definition itself through the batch operators (every intermediate is no larger than the result)
+    const int base = cmp == CSGN_UINT_PLAIN_NE ? CSGN_UINT_PLAIN_EQ : cmp == CSGN_UINT_PLAIN_LE ? CSGN_UINT_PLAIN_GT
+                   : cmp == CSGN_UINT_PLAIN_GE ? CSGN_UINT_PLAIN_LT : cmp;
+    auto bit = [&](unsigned j) { return (k >> j) & 1u; };
+    auto n = [&](unsigned j) { return logicNot(a.plane(j)); };
+    const uint64_t all = w == 64 ? ~0ull : (1ull << w) - 1;
+    CiphertextBatch r = a.plane(0);
+    if ((base == CSGN_UINT_PLAIN_LT && k == 0) || (base == CSGN_UINT_PLAIN_GT && k == all)) {
+        r = constantBatch(ctx, std::vector<unsigned char>(a.size(), 0));
+    } else if (base == CSGN_UINT_PLAIN_EQ) {
+        r = bit(0) ? a.plane(0) : n(0);
+        for (unsigned j = 1; j < w; ++j)
+            r = r * (bit(j) ? a.plane(j) : n(j));
+    } else if (base == CSGN_UINT_PLAIN_LT) {
+        const unsigned m = (unsigned)__builtin_ctzll(k);
+        r = n(m);
+        for (unsigned j = m + 1; j < w; ++j)
+            r = bit(j) ? (r * a.plane(j)) + n(j) : r * n(j);
+    } else {
+        const unsigned m = (unsigned)__builtin_ctzll(~k);
+        r = a.plane(m);
+        for (unsigned j = m + 1; j < w; ++j)
+            r = bit(j) ? r * a.plane(j) : (r * n(j)) + a.plane(j);
+    }
+    return base != cmp ? logicNot(r) : r;
+}
+
 } // namespace
 
 // ------------------------------------------------------------------ UIntBatch
@@ -346,6 +400,16 @@ CiphertextBatch greaterEqual(const UIntBatch &a, const UIntBatch &b)
     requireSame(a, b, "greaterEqual");
     gateTerms(CSGN_GATE_NOT, 0, lessThanTerms(a, b, "greaterEqual"), 0, a.context(), "greaterEqual");
     return logicNot(lessThanUnchecked(a, b));
+}
+
+CiphertextBatch equalTo(const UIntBatch &a, uint64_t k) { return comparePlain(CSGN_UINT_PLAIN_EQ, a, k, "equalTo"); }
+CiphertextBatch notEqualTo(const UIntBatch &a, uint64_t k) { return comparePlain(CSGN_UINT_PLAIN_NE, a, k, "notEqualTo"); }
+CiphertextBatch lessThan(const UIntBatch &a, uint64_t k) { return comparePlain(CSGN_UINT_PLAIN_LT, a, k, "lessThan"); }
+CiphertextBatch lessEqual(const UIntBatch &a, uint64_t k) { return comparePlain(CSGN_UINT_PLAIN_LE, a, k, "lessEqual"); }
+CiphertextBatch greaterThan(const UIntBatch &a, uint64_t k) { return comparePlain(CSGN_UINT_PLAIN_GT, a, k, "greaterThan"); }
+CiphertextBatch greaterEqual(const UIntBatch &a, uint64_t k)
+{
+    return comparePlain(CSGN_UINT_PLAIN_GE, a, k, "greaterEqual");
 }
 
 UIntBatch select(const CiphertextBatch &sel, const UIntBatch &a, const UIntBatch &b)

@@ -1085,6 +1085,47 @@ int csgn_uint_step(uint64_t n_bits, int step, uint64_t batch, const uint64_t *d_
     return CSGN_OK;
 }
 
+uint64_t csgn_uint_plain_terms(int cmp, uint64_t width, uint64_t k, const uint64_t *h_terms)
+{
+    return csgn::uint_plain_terms(cmp, width, k, (const u64 *)h_terms);
+}
+
+const char *csgn_uint_plain_kernel(uint64_t n_bits, int cmp, uint64_t batch, uint64_t width, uint64_t k,
+                                   const uint64_t *h_terms)
+{
+    return csgn::uint_plain_kernel_name(n_bits, cmp, batch, width, k, (const u64 *)h_terms);
+}
+
+int csgn_uint_plain(uint64_t n_bits, int cmp, uint64_t batch, uint64_t width, uint64_t k,
+                    const uint64_t *const *h_planes, const uint64_t *h_terms, uint64_t *d_out, void *stream)
+{
+    if (int rc = check_n(n_bits))
+        return rc;
+    REQUIRE(cmp >= CSGN_UINT_PLAIN_EQ && cmp <= CSGN_UINT_PLAIN_GE, "unknown comparison %d", cmp);
+    REQUIRE(width >= 1 && width <= 64, "width %llu outside 1..64", (unsigned long long)width);
+    REQUIRE(width == 64 || (k >> width) == 0, "constant %llu does not fit in %llu bits", (unsigned long long)k,
+            (unsigned long long)width);
+    REQUIRE(h_planes && h_terms, "null host pointer");
+    const uint64_t terms = csgn::uint_plain_terms(cmp, width, k, (const u64 *)h_terms);
+    REQUIRE(terms != 0, "comparison %d: a plane has no terms, or the term count overflows", cmp);
+    const uint64_t dl = csgn_default_len(n_bits);
+    if (!product_below(terms, dl, 1, 1ull << 31))
+        return fail(CSGN_ERR_UNSUPPORTED, "comparison %d: %llu terms per element exceed 2^31 words", cmp,
+                    (unsigned long long)terms);
+    if (!product_below(batch, terms, dl, 1ull << 60))
+        return fail(CSGN_ERR_UNSUPPORTED, "batch of %llu elements: size overflows", (unsigned long long)batch);
+    if (int rc = require_device("csgn_uint_plain"))
+        return rc;
+    if (batch == 0)
+        return CSGN_OK;
+    REQUIRE(d_out, "null device pointer");
+    for (uint64_t j = 0; j < width; ++j)
+        REQUIRE(h_planes[j], "null device pointer (plane %llu)", (unsigned long long)j);
+    HIP_TRY(csgn::uint_plain(n_bits, cmp, batch, width, k, (const u64 *const *)h_planes, (const u64 *)h_terms,
+                             (u64 *)d_out, S(stream)));
+    return CSGN_OK;
+}
+
 /* ------------------------------------------------------------------ tuning ---- */
 
 int csgn_set_tuning(const char *key, int value)

@@ -274,6 +274,13 @@ inline hipError_t zero_words(u64 *p, u64 n, hipStream_t s)
 }
 
 // ------------------------------------------------------------------------- launch helpers
+// the used bits of a term's last word (MSB first; the unused low bits stay zero): ONE's last word
+inline u64 last_word_mask(u64 n_bits)
+{
+    const u32 r = (u32)(n_bits % 64);
+    return r ? ~0ull << (64 - r) : ~0ull;
+}
+
 template <typename T>
 inline bool aligned16(const T *p)
 {

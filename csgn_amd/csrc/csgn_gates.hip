@@ -135,12 +135,6 @@ __global__ void __launch_bounds__(256) k_gate_fused(GateArgs a)
     unit_store<Unit, true>(reinterpret_cast<Unit *>(a.out) + g, v);
 }
 
-u64 last_word_mask(u64 n_bits)
-{
-    const u32 r = (u32)(n_bits % 64);
-    return r ? ~0ull << (64 - r) : ~0ull;
-}
-
 struct GateShape {
     u32 nseg;
     u32 kind[4], x[4], y[4];

@@ -133,6 +133,13 @@ const char *uint_step_kernel_name(u64 n_bits, int step, u64 batch, u64 tx, u64 t
 hipError_t uint_step(u64 n_bits, int step, u64 batch, const u64 *X, u64 tx, const u64 *A, u64 ta, const u64 *B, u64 tb,
                      u64 *out0, u64 *out1, hipStream_t s);
 
+// a w-bit comparison of bit-sliced integers against a public constant over uniform planes (csgn_uint_plain.hip);
+// cmp = CSGN_UINT_PLAIN_* of include/csgn_hip.h, planes[j] / terms[j]: plane j and its terms per element
+u64 uint_plain_terms(int cmp, u64 width, u64 k, const u64 *terms);   // 0: invalid argument or overflow
+const char *uint_plain_kernel_name(u64 n_bits, int cmp, u64 batch, u64 width, u64 k, const u64 *terms);
+hipError_t uint_plain(u64 n_bits, int cmp, u64 batch, u64 width, u64 k, const u64 *const *planes, const u64 *terms,
+                      u64 *out, hipStream_t s);
+
 hipError_t small_ops(u64 n_bits, u64 count, const ::csgn_small_op *ops, hipStream_t s);
 size_t decrypt_scratch_bytes(u64 batch, u64 total_terms);
 // out[i] = a[i] & b[i] (is_product) or a[i] ^ b[i]: Dec(a*b) = Dec(a) & Dec(b), Dec(a+b) = Dec(a) ^ Dec(b)

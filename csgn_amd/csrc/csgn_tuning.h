@@ -50,6 +50,7 @@ enum TuneKey {
     TUNE_ZERO_MEMSET,    // dev: 1 = zero fills on capturable paths are hipMemsetAsync (memset NODES in a circuit's graph) instead of the k_zero_words kernel (csgn_device.h, zero_words; tools/graph_memset_probe.hip)
     TUNE_GATE_FUSED,     // uniform gates (csgn_gates.hip): -1 = per shape, 0 = pitched form (the tuned launchers into the output's slices), 1 = fused kernel
     TUNE_UINT_FUSED,     // integer steps (csgn_uint.hip): -1 = per shape, 0 = pitched form where the step has one, 1 = fused kernel
+    TUNE_UINT_PLAIN_FUSED, // comparisons with a public constant (csgn_uint_plain.hip): -1 = per shape, 0 = composed form (the tuned launchers level by level), 1 = fused kernel
     TUNE_COUNT
 };
 

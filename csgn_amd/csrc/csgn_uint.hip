@@ -154,12 +154,6 @@ __global__ void __launch_bounds__(256) k_uint_step(UintArgs a)
     unit_store<Unit, true>(o, va & vb);
 }
 
-u64 last_word_mask(u64 n_bits)
-{
-    const u32 r = (u32)(n_bits % 64);
-    return r ? ~0ull << (64 - r) : ~0ull;
-}
-
 struct USeg {
     u32 kind, out, left, np, part[3];
     u64 terms;                // terms per element

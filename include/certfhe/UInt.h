@@ -19,6 +19,17 @@
 // element).  compact() shrinks planes by their duplicate terms.  Every operation computes every step's size before it
 // launches anything; a step above 2^31 words per element throws std::invalid_argument, and nothing is allocated.
 //
+// COMPARISONS WITH A PUBLIC CONSTANT (k < 2^width, the same for every element; std::invalid_argument otherwise) take k
+// as plaintext instead of as a trivially encrypted UIntBatch::constant, so no term is spent on k: with fresh planes an
+// equality has 2^(zeros of k) terms instead of 3^w, a less-than at most 2^w instead of about 3^w.  Their words are the
+// table of csgn_uint_plain (include/csgn_hip.h), with n_j = logicNot(a_j):
+//     equalTo(a, k)       g_j = k_j ? a_j : n_j;  e = g_0 * g_1 * ... * g_{w-1}  (left to right)
+//     lessThan(a, k)      k == 0: ZERO; else l = n_m (m: lowest set bit), then k_j ? (l * a_j) + n_j : l * n_j
+//     greaterThan(a, k)   k == 2^w-1: ZERO; else l = a_m (m: lowest clear bit), then k_j ? l * a_j : (l * n_j) + a_j
+//     notEqualTo, lessEqual, greaterEqual   logicNot of equalTo, greaterThan, lessThan
+// Uniform planes take one csgn_uint_plain call (one kernel for the whole comparison); ragged ones are composed from the
+// CiphertextBatch operators and Gates.h.  The result's size is checked before anything is allocated or launched.
+//
 // Uniform planes run one csgn_uint_step (or csgn_gate_uniform) call per bit; ragged ones (what compact() may return)
 // are composed from the CiphertextBatch operators and Gates.h, with the same words.  Only the running carry or
 // accumulator is kept alive between bits.
@@ -68,6 +79,13 @@ CiphertextBatch lessThan(const UIntBatch &a, const UIntBatch &b);
 CiphertextBatch lessEqual(const UIntBatch &a, const UIntBatch &b);
 CiphertextBatch greaterThan(const UIntBatch &a, const UIntBatch &b);
 CiphertextBatch greaterEqual(const UIntBatch &a, const UIntBatch &b);
+// against the public constant k (one encrypted bit per element)
+CiphertextBatch equalTo(const UIntBatch &a, uint64_t k);
+CiphertextBatch notEqualTo(const UIntBatch &a, uint64_t k);
+CiphertextBatch lessThan(const UIntBatch &a, uint64_t k);
+CiphertextBatch lessEqual(const UIntBatch &a, uint64_t k);
+CiphertextBatch greaterThan(const UIntBatch &a, uint64_t k);
+CiphertextBatch greaterEqual(const UIntBatch &a, uint64_t k);
 // element i: sel[i] ? a[i] : b[i]
 UIntBatch select(const CiphertextBatch &sel, const UIntBatch &a, const UIntBatch &b);
 

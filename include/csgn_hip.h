@@ -636,6 +636,37 @@ const char *csgn_uint_step_kernel(uint64_t n_bits, int step, uint64_t batch, uin
 int csgn_uint_step(uint64_t n_bits, int step, uint64_t batch, const uint64_t *d_x, uint64_t t_x, const uint64_t *d_a,
                    uint64_t t_a, const uint64_t *d_b, uint64_t t_b, uint64_t *d_out0, uint64_t *d_out1, void *stream);
 
+/* Comparison of a w-bit integer (planes a_0..a_{w-1}, least significant first) against one PUBLIC constant k < 2^w for
+ * the whole batch; one encrypted bit per element.  A fixed composition of the reference's operator+ / operator* with
+ * ONE and ZERO (csgn_const_fill), in this order; n_j = a_j + ONE (logicNot); the running value is always the LEFT
+ * operand of a product:
+ *     EQ   g_j = k_j ? a_j : n_j;  e = g_0;  e = e * g_j  for j = 1..w-1
+ *     LT   k == 0: ZERO.  m = lowest set bit of k;  l = n_m;  for j = m+1..w-1:
+ *              k_j = 1: l = (l * a_j) + n_j        k_j = 0: l = l * n_j
+ *     GT   k == 2^w-1: ZERO.  m = lowest clear bit of k;  l = a_m;  for j = m+1..w-1:
+ *              k_j = 1: l = l * a_j                k_j = 0: l = (l * n_j) + a_j
+ *     NE = EQ + ONE,  LE = GT + ONE,  GE = LT + ONE
+ * Fresh 1-term planes: EQ has 2^(zeros of k) terms, LT at most 2^w, GT at most 2^w - 1. */
+enum { CSGN_UINT_PLAIN_EQ = 1, CSGN_UINT_PLAIN_NE, CSGN_UINT_PLAIN_LT, CSGN_UINT_PLAIN_LE, CSGN_UINT_PLAIN_GT,
+       CSGN_UINT_PLAIN_GE };
+/* Terms per element of the result (host only); h_terms[j] = terms per element of plane j.  0: unknown cmp, width
+ * outside 1..64, k >= 2^width, a plane of 0 terms, or a count of 2^62 or more. */
+uint64_t csgn_uint_plain_terms(int cmp, uint64_t width, uint64_t k, const uint64_t *h_terms);
+/* Which form a csgn_uint_plain call of this shape takes (host only, a static string): "k_uint_plain" (one kernel writes
+ * the whole comparison, planes read in place, ONE and ZERO made in registers) or "composed" (the tuned
+ * csgn_mul_uniform / csgn_add_uniform / csgn_const_fill launchers level by level, the running value in a stream-ordered
+ * temporary block: hipMallocAsync).  Knob "uint_plain_fused" (-1 per shape, 0 / 1 forced) decides; the words are the
+ * same.  Per shape: composed for width 1 and the ZERO results, fused otherwise.  "" for an invalid shape. */
+const char *csgn_uint_plain_kernel(uint64_t n_bits, int cmp, uint64_t batch, uint64_t width, uint64_t k,
+                                   const uint64_t *h_terms);
+/* One comparison over `batch` elements: h_planes is a HOST array of `width` device pointers (plane j: batch *
+ * h_terms[j] * dL words, element after element), d_out = batch * csgn_uint_plain_terms(...) * dL words.  Planes may
+ * alias one another; d_out overlaps no plane.  Limits: the result below 2^31 words per element (CSGN_ERR_UNSUPPORTED),
+ * batch * that < 2^60.  On the caller's stream, asynchronous; the fused form is graph-capturable.  No GPU:
+ * CSGN_ERR_NO_DEVICE, no CPU fallback. */
+int csgn_uint_plain(uint64_t n_bits, int cmp, uint64_t batch, uint64_t width, uint64_t k,
+                    const uint64_t *const *h_planes, const uint64_t *h_terms, uint64_t *d_out, void *stream);
+
 /* ------------------------------------------------------------------- tuning ---- */
 
 /* Kernel-choice and sweep knobs ("mul_flat", "mul_touch", "ragged_c", "perm_ballot", ...;

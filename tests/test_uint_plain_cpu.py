@@ -1,0 +1,255 @@
+"""Comparisons of bit-sliced integers against a PUBLIC constant (csgn_uint_plain_*) on a box without a GPU: the term
+counts, the dispatch names and knob, the loud failure without a device, the DEFINITION of all six comparisons -- a
+composition of the reference's operator+ / operator* with ONE and ZERO -- pinned against the compiled reference and the
+oracle, and decryptions under random keys, which equal clear comparisons and today's route through constant(k).  The
+device side is tests/test_uint_plain_gpu.py."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from oracle.binding import glibc_draws
+from tests.test_gates_cpu import const_term, np_add, np_mul, oracle_ops, rand_terms, ref_ops
+from tests.test_uint_cpu import np_uint_eq, np_uint_lt
+
+EQ, NE, LT, LE, GT, GE = range(1, 7)
+CMPS = {"eq": EQ, "ne": NE, "lt": LT, "le": LE, "gt": GT, "ge": GE}
+LIMIT = 1 << 62
+
+
+@pytest.fixture(scope="module")
+def lib():
+    from csgn_amd import build, capi
+    build.build_hip()
+    return capi.load_library()
+
+
+def u64s(xs):
+    return (C.c_uint64 * max(len(xs), 1))(*[int(x) for x in xs])
+
+
+def lowest(k, bit, w):
+    return next(j for j in range(w) if (k >> j) & 1 == bit)
+
+
+# -- the definition, over any (add, mul, one, zero) ---------------------------------------------------------------------
+def compose(cmp, planes, k, add, mul, one, zero):
+    """include/csgn_hip.h's table, in exactly its order."""
+    w = len(planes)
+    nt = lambda j: add(planes[j], one)                                       # logicNot
+    base = {NE: EQ, LE: GT, GE: LT}.get(cmp, cmp)
+    if base == EQ:
+        g = lambda j: planes[j] if (k >> j) & 1 else nt(j)
+        r = g(0)
+        for j in range(1, w):
+            r = mul(r, g(j))
+    elif base == LT:
+        if k == 0:
+            r = zero
+        else:
+            m = lowest(k, 1, w)
+            r = nt(m)
+            for j in range(m + 1, w):
+                r = add(mul(r, planes[j]), nt(j)) if (k >> j) & 1 else mul(r, nt(j))
+    else:
+        if k == (1 << w) - 1:
+            r = zero
+        else:
+            m = lowest(k, 0, w)
+            r = planes[m]
+            for j in range(m + 1, w):
+                r = mul(r, planes[j]) if (k >> j) & 1 else add(mul(r, nt(j)), planes[j])
+    return add(r, one) if cmp != base else r
+
+
+def np_plain(n, cmp, planes, k):
+    """Words of one comparison over uniform planes (words[batch, t_j, dL], bit 0 first)."""
+    batch, _, dl = planes[0].shape
+    one = np.broadcast_to(const_term(n, 1), (batch, 1, dl))
+    zero = np.broadcast_to(const_term(n, 0), (batch, 1, dl))
+    return compose(cmp, planes, k, np_add, np_mul, one, zero)
+
+
+def expected_terms(cmp, w, k, t):
+    """The same composition over term counts (Python integers: no overflow); 0 past 2^62."""
+    counts = compose(cmp, list(t), k, lambda x, y: x + y, lambda x, y: x * y, 1, 1)
+    return counts if counts < LIMIT else 0
+
+
+def edge_ks(w, rng):
+    top = (1 << w) - 1
+    ks = {0, 1, top, 1 << (w - 1), top ^ 1, 0x5555555555555555 & top, 0xAAAAAAAAAAAAAAAA & top}
+    ks.update(int(rng.integers(0, 1 << min(w, 63))) for _ in range(3))
+    return sorted(x for x in ks if x <= top)
+
+
+# -- the C ABI, host side ---------------------------------------------------------------------------------------------
+def test_plain_terms_formulas(lib):
+    rng = np.random.default_rng(5)
+    for w in range(1, 65):
+        for ts in ([1] * w, [int(x) for x in rng.integers(1, 4, w)], [2] * w):
+            for k in edge_ks(w, rng):
+                for cmp in CMPS.values():
+                    want = expected_terms(cmp, w, k, ts)
+                    assert lib.csgn_uint_plain_terms(cmp, w, k, u64s(ts)) == want, (cmp, w, k, ts)
+
+
+def test_plain_terms_fresh_planes():
+    """The sizes of the issue for fresh 1-term planes."""
+    for w in range(1, 11):
+        for k in range(1 << w):
+            zeros = w - bin(k).count("1")
+            assert expected_terms(EQ, w, k, [1] * w) == 2 ** zeros
+            assert expected_terms(NE, w, k, [1] * w) == 2 ** zeros + 1
+            assert expected_terms(LT, w, k, [1] * w) <= 2 ** w
+            assert expected_terms(GT, w, k, [1] * w) <= 2 ** w - 1
+    assert expected_terms(LT, 8, 1, [1] * 8) == 256 and expected_terms(LT, 8, 255, [1] * 8) == 16 and expected_terms(EQ, 16, 0, [1] * 16) == 65536
+
+
+def test_plain_terms_invalid(lib):
+    one = u64s([1] * 64)
+    for bad in (0, 7, -1, 100):
+        assert lib.csgn_uint_plain_terms(bad, 4, 3, one) == 0
+    assert lib.csgn_uint_plain_terms(EQ, 0, 0, one) == 0                  # width outside 1..64
+    assert lib.csgn_uint_plain_terms(EQ, 65, 0, one) == 0
+    assert lib.csgn_uint_plain_terms(EQ, 4, 16, one) == 0                 # k >= 2^w
+    assert lib.csgn_uint_plain_terms(LT, 8, 1 << 40, one) == 0
+    assert lib.csgn_uint_plain_terms(EQ, 64, (1 << 64) - 1, one) == 1     # every k fits 64 bits
+    assert lib.csgn_uint_plain_terms(EQ, 3, 0, u64s([1, 0, 1])) == 0       # a plane of no terms
+    assert lib.csgn_uint_plain_terms(EQ, 2, 0, None) == 0
+    # overflow: 2^62 or more terms
+    assert lib.csgn_uint_plain_terms(EQ, 62, 0, one) == 0
+    assert lib.csgn_uint_plain_terms(EQ, 61, 0, one) == 1 << 61
+    assert lib.csgn_uint_plain_terms(LT, 64, 1, one) == 0 and lib.csgn_uint_plain_terms(LT, 64, (1 << 64) - 1, one) == 128
+    assert lib.csgn_uint_plain_terms(GT, 2, 0, u64s([1 << 40, 1 << 40])) == 0
+    assert lib.csgn_uint_plain_terms(EQ, 1, 1, u64s([(1 << 64) - 1])) == 0
+
+
+def test_plain_dispatch_names(lib, knobs):
+    knobs.unset("uint_plain_fused")
+
+    def name(cmp, w, k, ts=None):
+        return lib.csgn_uint_plain_kernel(1247, cmp, 1 << 16, w, k, u64s(ts or [1] * w)).decode()
+
+    for cmp in CMPS.values():
+        assert name(cmp, 8, 77) == "k_uint_plain", cmp
+        assert name(cmp, 16, 4711) == "k_uint_plain", cmp
+        assert name(cmp, 1, 1) == "composed", cmp                          # one copy and a constant
+    assert name(LT, 8, 0) == "composed" and name(GE, 8, 0) == "composed"  # ZERO (then ONE)
+    assert name(GT, 8, 255) == "composed" and name(LE, 8, 255) == "composed"
+    assert name(EQ, 4, 16) == "" and name(9, 4, 1) == ""
+    knobs.set("uint_plain_fused", 1)
+    assert name(EQ, 1, 1) == "k_uint_plain" and name(LT, 8, 0) == "k_uint_plain"
+    knobs.set("uint_plain_fused", 0)
+    assert name(EQ, 8, 77) == "composed" and name(GT, 16, 4711, [2] * 16) == "composed"
+
+
+def test_plain_fails_without_gpu(lib):
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("a GPU is present: tests/test_uint_plain_gpu.py covers the device")
+    buf = np.zeros(4096, dtype=np.uint64)
+    p = buf.ctypes.data
+    planes = (C.c_void_p * 64)(*([p] * 64))
+    one = u64s([1] * 64)
+    rc = lib.csgn_uint_plain(1247, EQ, 4, 8, 77, planes, one, p, None)
+    assert rc == -3, lib.csgn_last_error()
+    assert b"no CPU fallback" in lib.csgn_last_error()
+    assert lib.csgn_uint_plain(1247, LT, 4, 8, 0, planes, one, p, None) == -3
+    # argument errors are reported before the device is looked for
+    assert lib.csgn_uint_plain(1247, 0, 4, 8, 77, planes, one, p, None) == -1
+    assert lib.csgn_uint_plain(0, EQ, 4, 8, 77, planes, one, p, None) == -1
+    assert lib.csgn_uint_plain(1247, EQ, 4, 8, 256, planes, one, p, None) == -1
+    assert lib.csgn_uint_plain(1247, EQ, 4, 65, 0, planes, one, p, None) == -1
+    assert lib.csgn_uint_plain(1247, EQ, 4, 3, 0, planes, u64s([1, 0, 1]), p, None) == -1
+    assert lib.csgn_uint_plain(1247, EQ, 4, 3, 0, None, one, p, None) == -1
+    # too large: 2^27 terms * 20 words per element exceed 2^31 words
+    assert lib.csgn_uint_plain(1247, EQ, 4, 27, 0, planes, one, p, None) == -2
+    assert lib.csgn_uint_plain(1247, EQ, 4, 26, 0, planes, one, p, None) == -3
+    assert lib.csgn_uint_plain(1247, EQ, 1 << 56, 8, 0, planes, one, p, None) == -2     # batch
+
+
+# -- the definition against the genuine reference and the oracle -----------------------------------------------------
+@pytest.mark.parametrize("n,d", [(63, 4), (65, 4), (129, 8), (1247, 16)])
+@pytest.mark.parametrize("cmp", sorted(CMPS.values()))
+@pytest.mark.parametrize("w,k,ts", [(1, 0, [1]), (1, 1, [2]), (3, 5, [1, 2, 1]), (4, 0, [1, 1, 2, 1]),
+                                    (4, 15, [2, 1, 1, 1]), (4, 6, [1, 1, 1, 1]), (5, 18, [1, 2, 1, 1, 2])])
+def test_plain_definition_matches_reference(oracle, ref, n, d, cmp, w, k, ts):
+    planes = [rand_terms(n, 1, t, 40 + j)[0].ravel() for j, t in enumerate(ts)]
+    add, mul = ref_ops(ref, n, d)
+    want = compose(cmp, planes, k, add, mul, const_term(n, 1), const_term(n, 0))
+    add, mul = oracle_ops(oracle, n)
+    got = compose(cmp, planes, k, add, mul, const_term(n, 1), const_term(n, 0))
+    words = np_plain(n, cmp, [p.reshape(1, t, -1) for p, t in zip(planes, ts)], k)
+    dl = (n + 63) // 64
+    assert np.array_equal(got, want)
+    assert got.size == expected_terms(cmp, w, k, ts) * dl
+    assert np.array_equal(words.ravel(), got)
+
+
+@pytest.mark.parametrize("n", [64, 4096, 63, 1247])
+@pytest.mark.parametrize("cmp", sorted(CMPS.values()))
+def test_plain_definition_matches_oracle(oracle, n, cmp):
+    ts, batch = [2, 1, 3, 1, 2, 1], 3
+    planes = [rand_terms(n, batch, t, 60 + j) for j, t in enumerate(ts)]
+    add, mul = oracle_ops(oracle, n)
+    for k in (0, 1, 37, 63, 32, 21):
+        words = np_plain(n, cmp, planes, k)
+        for e in range(batch):
+            want = compose(cmp, [p[e].ravel() for p in planes], k, add, mul, const_term(n, 1), const_term(n, 0))
+            assert np.array_equal(words[e].ravel(), want), (k, e)
+
+
+# -- decryptions: clear comparisons, and today's route through constant(k) ------------------------------------------------
+CLEAR = {EQ: np.equal, NE: np.not_equal, LT: np.less, LE: np.less_equal, GT: np.greater, GE: np.greater_equal}
+
+
+def encrypt_planes(oracle, n, key, values, w, seed):
+    dl = (n + 63) // 64
+    count = len(values)
+    out = []
+    for j in range(w):
+        bits = ((np.asarray(values, dtype=np.uint64) >> np.uint64(j)) & np.uint64(1)).astype(np.uint8)
+        out.append(oracle.encrypt_seq(n, key, bits, glibc_draws(seed * 100 + j, count * (n + 2)))[0].reshape(count, 1, dl))
+    return out
+
+
+def decrypt_bits(oracle, n, key, words):
+    return np.array([oracle.decrypt_canonical(n, key, words[e].ravel()) for e in range(words.shape[0])], dtype=bool)
+
+
+@pytest.mark.parametrize("w", [1, 2, 3, 4])
+def test_plain_truth_tables(oracle, w):
+    n, d = 127, 8
+    key, _ = oracle.keygen(n, d, glibc_draws(70 + w, 64 * d + 64))
+    values = np.arange(1 << w, dtype=np.uint64)
+    planes = encrypt_planes(oracle, n, key, values, w, 80 + w)
+    for k in range(1 << w):
+        const = [np.broadcast_to(const_term(n, (k >> j) & 1), (len(values), 1, planes[0].shape[2])) for j in range(w)]
+        eq_today = decrypt_bits(oracle, n, key, np_uint_eq(n, planes, const))
+        lt_today = decrypt_bits(oracle, n, key, np_uint_lt(n, planes, const))
+        gt_today = decrypt_bits(oracle, n, key, np_uint_lt(n, const, planes))
+        for cmp, f in CLEAR.items():
+            got = decrypt_bits(oracle, n, key, np_plain(n, cmp, planes, k))
+            assert np.array_equal(got, f(values, np.uint64(k))), (cmp, k)
+        # the same bits as today's route (whose words differ: 3^w terms against at most 2^w)
+        assert np.array_equal(decrypt_bits(oracle, n, key, np_plain(n, EQ, planes, k)), eq_today)
+        assert np.array_equal(decrypt_bits(oracle, n, key, np_plain(n, LT, planes, k)), lt_today)
+        assert np.array_equal(decrypt_bits(oracle, n, key, np_plain(n, GT, planes, k)), gt_today)
+        assert np_plain(n, EQ, planes, k).shape[1] < 3 ** w or w == 1
+
+
+@pytest.mark.parametrize("w,count", [(8, 40), (16, 3)])
+def test_plain_random_pairs(oracle, w, count):
+    n, d = 127, 8
+    rng = np.random.default_rng(w)
+    key, _ = oracle.keygen(n, d, glibc_draws(90 + w, 64 * d + 64))
+    values = rng.integers(0, 1 << w, count).astype(np.uint64)
+    planes = encrypt_planes(oracle, n, key, values, w, 95 + w)
+    ks = [int(rng.integers(0, 1 << w)), int(values[0]), (1 << w) - 1 - 0x10, 1 << (w - 1)]
+    for k in ks:
+        for cmp, f in CLEAR.items():
+            if w == 16 and cmp in (EQ, NE) and bin(k).count("1") < 6:
+                continue                                              # 2^(zeros of k) terms: kept to 2^10 here
+            got = decrypt_bits(oracle, n, key, np_plain(n, cmp, planes, k))
+            assert np.array_equal(got, f(values, np.uint64(k))), (cmp, k)
