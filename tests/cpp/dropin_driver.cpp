@@ -906,13 +906,14 @@ static int cmd_graph(int count)
     return 0;
 }
 
-static int cmd_deferred(int rounds)
+static int cmd_deferred(int rounds, uint64_t n, uint64_t d)
 {
     // The deferred queue against the immediate path, word for word: random expression DAGs over fresh ciphertexts
     // (products and sums of operands that are themselves queued results, copies, reassigned and destroyed operands, more
-    // than one queue-full of operations), evaluated twice -- queued and one launch per operation.
+    // than one queue-full of operations), evaluated twice -- queued and one launch per operation.  Context(n, d): odd and
+    // even word counts put both unit widths of the queue's kernel on the path.
     Library::initializeLibrary();
-    Context ctx(1247, 16);
+    Context ctx(n, d);
     SecretKey sk(ctx);
     uint32_t rng = 12345u;
     auto next = [&]() { rng = rng * 1664525u + 1013904223u; return rng >> 8; };
@@ -965,7 +966,7 @@ static int cmd_deferred(int rounds)
         EXPECT(clear[0] == clear[1]);
     }
     Library::deferSmallOperations(true);
-    printf("deferred ok rounds=%d\n", rounds);
+    printf("deferred ok rounds=%d n=%llu d=%llu\n", rounds, (unsigned long long)n, (unsigned long long)d);
     return 0;
 }
 
@@ -1175,7 +1176,8 @@ int main(int argc, char **argv)
         if (cmd == "latency")
             return cmd_latency(argc > 2 ? atoi(argv[2]) : 2000);
         if (cmd == "deferred")
-            return cmd_deferred(argc > 2 ? atoi(argv[2]) : 20);
+            return cmd_deferred(argc > 2 ? atoi(argv[2]) : 20, argc > 4 ? strtoull(argv[3], nullptr, 10) : 1247,
+                                argc > 4 ? strtoull(argv[4], nullptr, 10) : 16);
         if (cmd == "deferred_threads")
             return cmd_deferred_threads(argc > 2 ? atoi(argv[2]) : 50);
         if (cmd == "deferred_exit")

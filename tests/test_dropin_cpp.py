@@ -66,7 +66,11 @@ def test_deferred_queue_equals_one_launch_per_operation(driver):
     DAGs -- results feeding results, reassigned and destroyed operands, copies, more than a queue-full of operations --
     give the words and plaintexts of the same program with one launch per operation."""
     p = run(driver, "deferred", 20)
-    assert "deferred ok rounds=20" in p.stdout
+    assert "deferred ok rounds=20 n=1247 d=16" in p.stdout
+    # ... at odd word counts (the queue's kernel on 8-byte units throughout) and other even ones
+    for n, d in ((63, 4), (129, 3), (1300, 4), (4096, 32)):
+        p = run(driver, "deferred", 8, n, d)
+        assert f"deferred ok rounds=8 n={n} d={d}" in p.stdout
     # ... and a ciphertext whose operation is still queued in one host thread used as an operand in another
     p = run(driver, "deferred_threads", 50)
     assert "deferred threads ok rounds=50" in p.stdout

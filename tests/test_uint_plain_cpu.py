@@ -83,6 +83,20 @@ def edge_ks(w, rng):
     return sorted(x for x in ks if x <= top)
 
 
+def full_width_cases(w):
+    """(cmp, k) pairs at widths up to 64 whose result over fresh 1-term planes stays at most 4096 terms: EQ / NE with few
+    zero bits in k, LT / GE at the top (2w terms) and at 2^(w-1), GT / LE just below the top, and the ZERO constants (LT
+    at 0, GT at the top).  Picked by expected_terms: GT at small k is the expensive end (2^w terms at k = 0)."""
+    top = (1 << w) - 1
+    ks = {0, 1, top, top - 1, 1 << (w - 1), top ^ (1 << (w - 1)), top ^ 0x2D5, top ^ 0x3FF, top ^ (0b1011 << (w - 5)),
+          top ^ ((1 << (w - 1)) | 1), (1 << (w - 1)) | 1}
+    cases = sorted((c, k) for k in ks for c in CMPS.values() if 0 < expected_terms(c, w, k, [1] * w) <= 4096)
+    for must in ((EQ, top), (NE, top ^ 0x3FF), (LT, top), (GE, top), (LT, 1 << (w - 1)), (GE, 1 << (w - 1)), (LT, 0),
+                 (GT, top - 1), (LE, top - 1), (GT, top), (GT, top ^ 0x2D5)):
+        assert must in cases, must
+    return cases
+
+
 # -- the C ABI, host side ---------------------------------------------------------------------------------------------
 def test_plain_terms_formulas(lib):
     rng = np.random.default_rng(5)
@@ -253,3 +267,29 @@ def test_plain_random_pairs(oracle, w, count):
                 continue                                              # 2^(zeros of k) terms: kept to 2^10 here
             got = decrypt_bits(oracle, n, key, np_plain(n, cmp, planes, k))
             assert np.array_equal(got, f(values, np.uint64(k))), (cmp, k)
+
+
+@pytest.mark.parametrize("n", [65, 1247])
+def test_plain_definition_at_64_bits(lib, oracle, n):
+    """np_plain at w = 64 (k and values at and above 2^63 are Python / uint64 integers throughout): as many terms as
+    csgn_uint_plain_terms says, the words of the composition through the oracle's operators, and decryptions equal to
+    clear uint64 comparisons."""
+    w, batch = 64, 2
+    planes = [rand_terms(n, batch, 1, 900 + j) for j in range(w)]
+    add, mul = oracle_ops(oracle, n)
+    for cmp, k in full_width_cases(w):
+        words = np_plain(n, cmp, planes, k)
+        assert words.shape[1] == lib.csgn_uint_plain_terms(cmp, w, k, u64s([1] * w)) == expected_terms(cmp, w, k, [1] * w)
+        if words.shape[1] <= 256:
+            want = compose(cmp, [p[1].ravel() for p in planes], k, add, mul, const_term(n, 1), const_term(n, 0))
+            assert np.array_equal(words[1].ravel(), want), (cmp, k)
+    d = 8
+    key, _ = oracle.keygen(n, d, glibc_draws(64, 64 * d + 64))
+    values = np.array([0, 1, 1 << 63, (1 << 64) - 1, (1 << 64) - 2, (1 << 63) - 1, (1 << 63) + 1, 0x0123456789ABCDEF],
+                      dtype=np.uint64)
+    planes = encrypt_planes(oracle, n, key, values, w, 640)
+    for k in (0, 1, 1 << 63, (1 << 63) - 1, (1 << 64) - 1, (1 << 64) - 2):
+        for cmp, f in CLEAR.items():
+            if 0 < expected_terms(cmp, w, k, [1] * w) <= 4096:
+                got = decrypt_bits(oracle, n, key, np_plain(n, cmp, planes, k))
+                assert np.array_equal(got, f(values, np.uint64(k))), (cmp, k)

@@ -9,7 +9,7 @@ import pytest
 from oracle.binding import glibc_draws
 from tests.test_gates_cpu import rand_terms
 from tests.test_uint_plain_cpu import (CLEAR, CMPS, EQ, GE, GT, LE, LT, NE, decrypt_bits, encrypt_planes,
-                                       expected_terms, np_plain, u64s)
+                                       expected_terms, full_width_cases, np_plain, u64s)
 
 pytestmark = pytest.mark.gpu
 
@@ -64,6 +64,36 @@ def test_plain_words_wide(hip, knobs, w):
         for cmp in (EQ, NE, LT, LE, GT, GE):
             if expected_terms(cmp, w, k, [1] * w) <= 4096:
                 check_forms(hip, knobs, n, cmp, planes, k)
+
+
+@pytest.mark.parametrize("n", [65, 1247])
+@pytest.mark.parametrize("w", [17, 31, 32, 33, 63, 64])
+def test_plain_words_full_width(hip, knobs, n, w):
+    """Levels at and above bit 16, 32 and 63: the kernel's 64-bit level masks and 64-entry tables, every (cmp, k) of at
+    most 4096 terms over fresh planes."""
+    batch = 3
+    planes = [rand_terms(n, batch, 1, 4000 + 67 * w + j) for j in range(w)]
+    for cmp, k in full_width_cases(w):
+        check_forms(hip, knobs, n, cmp, planes, k)
+
+
+def test_plain_64bit_by_decryption(hip, knobs, oracle):
+    """w = 64 against clear uint64 comparisons, values and constants at and around 0, 2^63 and 2^64 - 1."""
+    n, d, w = 1247, 16, 64
+    key, _ = oracle.keygen(n, d, glibc_draws(164, 64 * d + 64))
+    rng = np.random.default_rng(64)
+    values = np.concatenate([np.array([0, 1, 1 << 63, (1 << 63) - 1, (1 << 63) + 1, (1 << 64) - 1, (1 << 64) - 2],
+                                      dtype=np.uint64), rng.integers(0, 2**64 - 1, 9, dtype=np.uint64, endpoint=True)])
+    planes = encrypt_planes(oracle, n, key, values, w, 190)
+    knobs.unset("uint_plain_fused")
+    ks = [0, 1, 1 << 63, (1 << 63) - 1, (1 << 63) + 1, (1 << 64) - 1, (1 << 64) - 2, int(values[-1]) | 0xFFFFFFFFFFFF0000]
+    for k in ks:
+        for cmp, f in CLEAR.items():
+            if not 0 < expected_terms(cmp, w, k, [1] * w) <= 4096:
+                continue
+            got = run(hip, n, cmp, planes, k).reshape(len(values), -1, (n + 63) // 64)
+            assert np.array_equal(got.reshape(-1), np_plain(n, cmp, planes, k).ravel()), (cmp, k)
+            assert np.array_equal(decrypt_bits(oracle, n, key, got), f(values, np.uint64(k))), (cmp, k)
 
 
 @pytest.mark.parametrize("batch", [1, 2, 255, 257, 4099, (1 << 16) + 3])
