@@ -208,6 +208,43 @@ class HipPath:
         check(self.lib.csgn_uint_plain(n_bits, cmp, batch, w, k, h_planes, h_terms, _ptr(out), self.stream))
         return out[: batch * total * dl]
 
+    def uint_lut_create(self, table, in_width: int, out_width: int, terms) -> int:
+        """csgn_uint_lut_create: the public table (2^in_width entries < 2^out_width) compiled for planes of terms[i] terms
+        per element.  Returns the handle; release it with self.lib.csgn_uint_lut_destroy."""
+        h_table = (C.c_uint64 * len(table))(*[int(v) for v in table])
+        h_terms = (C.c_uint64 * max(len(terms), 1))(*[int(t) for t in terms])
+        handle = C.c_void_p()
+        check(self.lib.csgn_uint_lut_create(in_width, out_width, h_table, h_terms, C.byref(handle)))
+        return handle.value
+
+    def uint_lut_apply(self, handle: int, n_bits: int, batch: int, planes, out_terms, outs=None):
+        """csgn_uint_lut_apply of a compiled table: planes bit 0 first, out_terms[j] = T_j.  Returns the output tensors
+        (fresh ones unless `outs` is given)."""
+        dl = self.default_len(n_bits)
+        if outs is None:
+            outs = [self.empty_words(max(batch * int(t) * dl, 1)) for t in out_terms]
+        h_planes = (C.c_void_p * max(len(planes), 1))(*[_ptr(p) for p in planes])
+        h_out = (C.c_void_p * len(outs))(*[_ptr(o) for o in outs])
+        check(self.lib.csgn_uint_lut_apply(handle, n_bits, batch, h_planes, h_out, self.stream))
+        return [o[: batch * int(t) * dl] for o, t in zip(outs, out_terms)]
+
+    def uint_lut(self, n_bits: int, batch: int, planes, terms, table, out_width: int):
+        """The public lookup table `table` applied to the w-bit integer `planes` (bit 0 first; plane i a uniform batch of
+        terms[i] terms per element): one tensor per output bit, T_j terms per element (csgn_uint_lut_terms)."""
+        w = len(planes)
+        assert w == len(terms) and len(table) == 1 << w
+        h_table = (C.c_uint64 * len(table))(*[int(v) for v in table])
+        h_terms = (C.c_uint64 * w)(*[int(t) for t in terms])
+        out_terms = (C.c_uint64 * out_width)()
+        check(self.lib.csgn_uint_lut_terms(w, out_width, h_table, h_terms, out_terms))
+        handle = self.uint_lut_create(table, w, out_width, terms)
+        try:
+            outs = self.uint_lut_apply(handle, n_bits, batch, planes, list(out_terms))
+            torch.cuda.current_stream(self.device).synchronize()
+        finally:
+            self.lib.csgn_uint_lut_destroy(handle)
+        return outs
+
     def add_ragged(self, n_bits: int, left: torch.Tensor, off_left: torch.Tensor,
                    right: torch.Tensor, off_right: torch.Tensor,
                    total_terms_out: Optional[int] = None, max_t1: int = 0, max_t2: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -135,6 +135,12 @@ SIGNATURES = {
     "csgn_uint_plain_terms": (u64, [C.c_int, u64, u64, C.POINTER(u64)]),
     "csgn_uint_plain_kernel": (C.c_char_p, [u64, C.c_int, u64, u64, u64, C.POINTER(u64)]),
     "csgn_uint_plain": (C.c_int, [u64, C.c_int, u64, u64, u64, C.POINTER(vp), C.POINTER(u64), vp, vp]),
+    "csgn_uint_lut_anf": (C.c_int, [u64, u64, C.POINTER(u64), C.POINTER(u64)]),
+    "csgn_uint_lut_terms": (C.c_int, [u64, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
+    "csgn_uint_lut_create": (C.c_int, [u64, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(vp)]),
+    "csgn_uint_lut_destroy": (None, [vp]),
+    "csgn_uint_lut_kernel": (C.c_char_p, [u64, vp, u64]),
+    "csgn_uint_lut_apply": (C.c_int, [vp, u64, u64, C.POINTER(vp), C.POINTER(vp), vp]),
     "csgn_set_tuning": (C.c_int, [C.c_char_p, C.c_int]),
     "csgn_get_tuning": (C.c_int, [C.c_char_p, C.POINTER(C.c_int)]),
     "csgn_reset_tuning": (None, []),

@@ -4,6 +4,8 @@
 #include "Gates.h"
 #include "runtime.h"
 
+#include <map>
+#include <mutex>
 #include <stdexcept>
 #include <string>
 
@@ -422,6 +424,137 @@ UIntBatch select(const CiphertextBatch &sel, const UIntBatch &a, const UIntBatch
     for (unsigned j = 0; j < a.width(); ++j)
         planes.push_back(logicMux(sel, a.plane(j), b.plane(j)));
     return UIntBatch::fromPlanes(planes);
+}
+
+} // namespace certFHE
+
+namespace certFHE {
+
+// ------------------------------------------------------------------ public lookup tables
+
+struct LookupTable::Impl {
+    unsigned w = 0, m = 0;
+    std::vector<uint64_t> table, anf;
+    std::mutex mutex;
+    std::map<std::vector<uint64_t>, csgn_uint_lut *> plans;     // device plans per vector of plane term counts
+
+    ~Impl()
+    {
+        for (auto &p : plans)
+            csgn_uint_lut_destroy(p.second);
+    }
+
+    const csgn_uint_lut *plan(const std::vector<uint64_t> &terms)
+    {
+        std::lock_guard<std::mutex> lock(mutex);
+        auto it = plans.find(terms);
+        if (it != plans.end())
+            return it->second;
+        csgn_uint_lut *p = nullptr;
+        detail::check(csgn_uint_lut_create(w, m, table.data(), terms.data(), &p), "csgn_uint_lut_create");
+        plans[terms] = p;
+        return p;
+    }
+};
+
+LookupTable::LookupTable(const std::vector<uint64_t> &table, unsigned in_width, unsigned out_width)
+    : impl_(std::make_shared<Impl>())
+{
+    if (in_width < 1 || in_width > 16 || out_width < 1 || out_width > 64)
+        throw std::invalid_argument("certFHE::LookupTable: in_width must be 1..16 and out_width 1..64");
+    if (table.size() != (size_t(1) << in_width))
+        throw std::invalid_argument("certFHE::LookupTable: the table must have 2^in_width entries");
+    impl_->w = in_width;
+    impl_->m = out_width;
+    impl_->table = table;
+    impl_->anf.resize(table.size());
+    if (csgn_uint_lut_anf(in_width, out_width, table.data(), impl_->anf.data()) != CSGN_OK)
+        throw std::invalid_argument("certFHE::LookupTable: an entry does not fit in out_width bits");
+}
+
+unsigned LookupTable::inWidth() const { return impl_->w; }
+unsigned LookupTable::outWidth() const { return impl_->m; }
+const std::vector<uint64_t> &LookupTable::table() const { return impl_->table; }
+const std::vector<uint64_t> &LookupTable::anf() const { return impl_->anf; }
+
+namespace {
+
+// M_S = ((a_{i1} * a_{i2}) * ...) over i in S ascending; ONE for the empty set
+CiphertextBatch monomial(const UIntBatch &a, uint64_t S)
+{
+    if (S == 0)
+        return ones(a.plane(0));
+    CiphertextBatch r = a.plane((unsigned)__builtin_ctzll(S));
+    for (S &= S - 1; S; S &= S - 1)
+        r = r * a.plane((unsigned)__builtin_ctzll(S));
+    return r;
+}
+
+} // namespace
+
+UIntBatch lookup(const UIntBatch &a, const LookupTable &f)
+{
+    LookupTable::Impl &L = *f.impl();
+    if (a.width() != L.w)
+        throw std::invalid_argument("certFHE::lookup: the operand's width differs from the table's in_width");
+    const Context &ctx = a.context();
+    std::vector<uint64_t> terms(L.w), T(L.m);
+    bool uniform = true;
+    for (unsigned i = 0; i < L.w; ++i) {
+        terms[i] = termsOf(a.plane(i));                   // a ragged plane: its largest element, a bound
+        uniform = uniform && a.plane(i).uniform();
+    }
+    if (csgn_uint_lut_terms(L.w, L.m, L.table.data(), terms.data(), T.data()) != CSGN_OK)
+        throw std::invalid_argument("certFHE::lookup: an output's result exceeds 2^31 words per element");
+    for (unsigned j = 0; j < L.m; ++j)
+        checked(T[j], ctx, "lookup");
+    std::vector<CiphertextBatch> out;
+    if (uniform) {
+        const csgn_uint_lut *plan = L.plan(terms);
+        out.reserve(L.m);
+        for (unsigned j = 0; j < L.m; ++j)
+            out.push_back(UIntAccess::make(ctx, a.size(), T[j]));
+        if (a.size()) {
+            std::vector<const uint64_t *> planes(L.w);
+            std::vector<uint64_t *> outs(L.m);
+            for (unsigned i = 0; i < L.w; ++i)
+                planes[i] = a.plane(i).deviceValues();
+            for (unsigned j = 0; j < L.m; ++j)
+                outs[j] = UIntAccess::words(out[j]);
+            detail::check(csgn_uint_lut_apply(plan, ctx.getN(), a.size(), planes.data(), outs.data(), detail::stream()),
+                          "csgn_uint_lut_apply");
+        }
+        return UIntBatch::fromPlanes(out);
+    }
+    // ragged: the definition itself through the batch operators
+    for (unsigned j = 0; j < L.m; ++j) {
+        std::vector<CiphertextBatch> acc;                 // empty until the first monomial
+        for (uint64_t S = 0; S < L.anf.size(); ++S) {
+            if (!((L.anf[S] >> j) & 1u))
+                continue;
+            const CiphertextBatch mono = monomial(a, S);
+            if (acc.empty())
+                acc.push_back(mono);
+            else
+                acc[0] = acc[0] + mono;
+        }
+        out.push_back(acc.empty() ? constantBatch(ctx, std::vector<unsigned char>(a.size(), 0)) : acc[0]);
+    }
+    return UIntBatch::fromPlanes(out);
+}
+
+UIntBatch lookup(const UIntBatch &a, const UIntBatch &b, const LookupTable &f)
+{
+    if (a.size() != b.size() || !sameContext(a.context(), b.context()))
+        throw std::invalid_argument("certFHE::lookup: operands differ in count or context");
+    if (a.width() + b.width() != f.inWidth())
+        throw std::invalid_argument("certFHE::lookup: the operands' widths do not add up to the table's in_width");
+    std::vector<CiphertextBatch> planes;
+    for (unsigned i = 0; i < a.width(); ++i)
+        planes.push_back(a.plane(i));
+    for (unsigned i = 0; i < b.width(); ++i)
+        planes.push_back(b.plane(i));
+    return lookup(UIntBatch::fromPlanes(planes), f);
 }
 
 } // namespace certFHE

@@ -1126,6 +1126,96 @@ int csgn_uint_plain(uint64_t n_bits, int cmp, uint64_t batch, uint64_t width, ui
     return CSGN_OK;
 }
 
+int csgn_uint_lut_anf(uint64_t in_width, uint64_t out_width, const uint64_t *h_table, uint64_t *h_anf)
+{
+    if (int rc = csgn::uint_lut_anf(in_width, out_width, (const u64 *)h_table, (u64 *)h_anf))
+        return fail(rc, "lookup table: in_width %llu (1..16), out_width %llu (1..64), a null pointer or an entry past "
+                        "out_width", (unsigned long long)in_width, (unsigned long long)out_width);
+    return CSGN_OK;
+}
+
+int csgn_uint_lut_terms(uint64_t in_width, uint64_t out_width, const uint64_t *h_table, const uint64_t *h_terms,
+                        uint64_t *h_out_terms)
+{
+    if (int rc = csgn::uint_lut_terms(in_width, out_width, (const u64 *)h_table, (const u64 *)h_terms,
+                                      (u64 *)h_out_terms))
+        return fail(rc, "lookup table: bad widths, a null pointer, an entry past out_width, a plane of 0 terms or a "
+                        "term count of 2^62 or more");
+    return CSGN_OK;
+}
+
+struct csgn_uint_lut {
+    csgn::LutPlan plan;
+};
+
+int csgn_uint_lut_create(uint64_t in_width, uint64_t out_width, const uint64_t *h_table, const uint64_t *h_terms,
+                         csgn_uint_lut **lut)
+{
+    REQUIRE(lut, "lut is null");
+    *lut = nullptr;
+    uint64_t T[csgn::kLutMaxOut];
+    if (int rc = csgn_uint_lut_terms(in_width, out_width, h_table, h_terms, T))
+        return rc;
+    for (uint64_t j = 0; j < out_width; ++j)
+        if (T[j] >= (1ull << 31))
+            return fail(CSGN_ERR_UNSUPPORTED, "lookup table: output %llu has %llu terms per element (2^31 or more)",
+                        (unsigned long long)j, (unsigned long long)T[j]);
+    if (int rc = require_device("csgn_uint_lut_create"))
+        return rc;
+    csgn_uint_lut *l = new csgn_uint_lut();
+    hipError_t e = hipSuccess;
+    const int rc = csgn::uint_lut_plan_create(in_width, out_width, (const u64 *)h_table, (const u64 *)h_terms, l->plan, e);
+    if (rc != CSGN_OK) {
+        delete l;
+        return rc == CSGN_ERR_HIP ? hip_fail(e, "csgn_uint_lut_create") : fail(rc, "lookup table: invalid");
+    }
+    *lut = l;
+    return CSGN_OK;
+}
+
+void csgn_uint_lut_destroy(csgn_uint_lut *lut)
+{
+    if (!lut)
+        return;
+    csgn::uint_lut_plan_free(lut->plan);
+    delete lut;
+}
+
+const char *csgn_uint_lut_kernel(uint64_t n_bits, const csgn_uint_lut *lut, uint64_t batch)
+{
+    if (!lut || n_bits == 0)
+        return "";
+    return csgn::uint_lut_kernel_name(lut->plan, n_bits, batch);
+}
+
+int csgn_uint_lut_apply(const csgn_uint_lut *lut, uint64_t n_bits, uint64_t batch, const uint64_t *const *h_planes,
+                        uint64_t *const *h_out, void *stream)
+{
+    if (int rc = check_n(n_bits))
+        return rc;
+    REQUIRE(lut, "lut is null");
+    REQUIRE(h_planes && h_out, "null host pointer");
+    const csgn::LutPlan &p = lut->plan;
+    const uint64_t dl = csgn_default_len(n_bits);
+    for (u32 j = 0; j < p.m; ++j) {
+        if (!product_below(p.T[j], dl, 1, 1ull << 31))
+            return fail(CSGN_ERR_UNSUPPORTED, "lookup table: output %u has %llu terms per element, past 2^31 words", j,
+                        (unsigned long long)p.T[j]);
+        if (!product_below(batch, p.T[j], dl, 1ull << 60))
+            return fail(CSGN_ERR_UNSUPPORTED, "batch of %llu elements: size overflows", (unsigned long long)batch);
+    }
+    if (int rc = require_device("csgn_uint_lut_apply"))
+        return rc;
+    if (batch == 0)
+        return CSGN_OK;
+    for (u32 i = 0; i < p.w; ++i)
+        REQUIRE(h_planes[i], "null device pointer (plane %u)", i);
+    for (u32 j = 0; j < p.m; ++j)
+        REQUIRE(h_out[j], "null device pointer (output %u)", j);
+    HIP_TRY(csgn::uint_lut(p, n_bits, batch, (const u64 *const *)h_planes, (u64 *const *)h_out, S(stream)));
+    return CSGN_OK;
+}
+
 /* ------------------------------------------------------------------ tuning ---- */
 
 int csgn_set_tuning(const char *key, int value)

@@ -4,6 +4,8 @@
 
 #include "csgn_common.h"
 
+#include <vector>
+
 struct csgn_small_op;   // include/csgn_hip.h
 
 namespace csgn {
@@ -139,6 +141,30 @@ u64 uint_plain_terms(int cmp, u64 width, u64 k, const u64 *terms);   // 0: inval
 const char *uint_plain_kernel_name(u64 n_bits, int cmp, u64 batch, u64 width, u64 k, const u64 *terms);
 hipError_t uint_plain(u64 n_bits, int cmp, u64 batch, u64 width, u64 k, const u64 *const *planes, const u64 *terms,
                       u64 *out, hipStream_t s);
+
+// a public lookup table applied to a w-bit integer of uniform planes (csgn_uint_lut.hip), include/csgn_hip.h's
+// definition: output j is the sum, ascending in S, of the monomials M_S of the table's Mobius transform with bit j set.
+// A plan compiles one table for one vector of plane term counts; it lives in a csgn_uint_lut object of the caller's.
+constexpr u32 kLutMaxIn = 16, kLutMaxOut = 64;
+struct LutPlan {
+    u32 w = 0, m = 0;                 // in_width, out_width
+    u64 t[kLutMaxIn] = {};            // terms per element of plane i
+    u64 T[kLutMaxOut] = {};           // terms per element of output j
+    u32 mbase[kLutMaxOut + 1] = {};   // output j's monomials: entries [mbase[j], mbase[j + 1]) of the lists
+    bool fresh = false;               // every t_i = 1: monomial index = term index
+    u32 *d_mono = nullptr;            // the monomial masks, ascending within each output
+    u32 *d_moff = nullptr;            // each monomial's first term inside its output (the multi-term decode)
+    std::vector<u32> mono;            // host copy of the masks (the composed form)
+};
+// 0 = CSGN_OK, or a negative csgn_status; the ANF of the table (2^w words)
+int uint_lut_anf(u64 w, u64 m, const u64 *table, u64 *anf);
+// T_j of every output (m words); CSGN_ERR_INVALID for a bad argument or a count of 2^62 or more
+int uint_lut_terms(u64 w, u64 m, const u64 *table, const u64 *t, u64 *T);
+// compiles and uploads (synchronous); CSGN_ERR_UNSUPPORTED when an output reaches 2^31 terms
+int uint_lut_plan_create(u64 w, u64 m, const u64 *table, const u64 *t, LutPlan &p, hipError_t &herr);
+void uint_lut_plan_free(LutPlan &p);
+const char *uint_lut_kernel_name(const LutPlan &p, u64 n_bits, u64 batch);
+hipError_t uint_lut(const LutPlan &p, u64 n_bits, u64 batch, const u64 *const *planes, u64 *const *out, hipStream_t s);
 
 hipError_t small_ops(u64 n_bits, u64 count, const ::csgn_small_op *ops, hipStream_t s);
 size_t decrypt_scratch_bytes(u64 batch, u64 total_terms);

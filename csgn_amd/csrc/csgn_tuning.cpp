@@ -32,6 +32,7 @@ const Knob kKnobs[TUNE_COUNT] = {
     {"gate_fused", -1},
     {"uint_fused", -1},
     {"uint_plain_fused", -1},
+    {"uint_lut_fused", -1},
 };
 
 // Knob values are PER HOST THREAD: a thread that sets a knob changes the dispatch of its own later

@@ -51,6 +51,7 @@ enum TuneKey {
     TUNE_GATE_FUSED,     // uniform gates (csgn_gates.hip): -1 = per shape, 0 = pitched form (the tuned launchers into the output's slices), 1 = fused kernel
     TUNE_UINT_FUSED,     // integer steps (csgn_uint.hip): -1 = per shape, 0 = pitched form where the step has one, 1 = fused kernel
     TUNE_UINT_PLAIN_FUSED, // comparisons with a public constant (csgn_uint_plain.hip): -1 = per shape, 0 = composed form (the tuned launchers level by level), 1 = fused kernel
+    TUNE_UINT_LUT_FUSED, // public lookup tables (csgn_uint_lut.hip): -1 = per shape, 0 = composed form (the tuned launchers monomial by monomial), 1 = fused kernel
     TUNE_COUNT
 };
 

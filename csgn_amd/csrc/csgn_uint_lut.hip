@@ -1,0 +1,500 @@
+// csgn_uint_lut.hip -- a PUBLIC lookup table applied to a bit-sliced encrypted integer, every output plane in one
+// launch.  Hand-written CDNA4 (gfx950) HIP; shared helpers in csgn_device.h, design notes in DESIGN.md §4.15.
+//
+// The definition (include/csgn_hip.h, csgn_uint_lut_apply) is the table's algebraic normal form over the planes: output
+// j is the left-nested sum, ascending in S, of the monomials M_S = a_{i1} * a_{i2} * ... (ascending i, ONE for S = {})
+// with bit j of anf[S] set, ZERO when there is none.  A term of a product is the AND of one term per factor, the last
+// factor fastest, so term idx of output j is found by
+//     the monomial m whose term range [moff[m], moff[m] + prod t_i) holds idx   (fresh planes: m = idx)
+//     r = idx - moff[m];  for i in S, highest first:  d_i = r % t_i,  r /= t_i;  AND a_i[d_i]
+//
+// Fresh planes (every t_i = 1), the case this kernel is built for, read each plane once per workgroup: the workgroup
+// builds, for its elements and its slice of units, subset tables in LDS -- table k holds the AND of every subset of its
+// planes [hb[k], hb[k+1]) -- and every written unit is T_0[S_0] & T_1[S_1] & T_2[S_2]: one to three LDS reads, whatever
+// |S| is.  Lanes walk one output's contiguous term stream, so one store instruction writes 64 consecutive units of one
+// plane.  Multi-term planes take the decode above straight from the planes (correct, not fast).
+#include "csgn_device.h"
+#include "csgn_hip.h"
+
+#include <algorithm>
+#include <vector>
+
+namespace csgn {
+
+namespace {
+
+constexpr u32 kMaxTables = 3;
+constexpr u64 kLdsBudget = 32768;       // bytes of subset tables per workgroup: four workgroups per CU
+constexpr u64 kPartUnits = 8192;        // units a workgroup writes at least, where the shape has them
+
+__device__ inline unit16 lut_one(unit16, u32 k, u32 U, u64 last_mask)
+{
+    unit16 v = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
+    if (k == U - 1u) {
+        v.z = (u32)last_mask;
+        v.w = (u32)(last_mask >> 32);
+    }
+    return v;
+}
+__device__ inline unit8 lut_one(unit8, u32 k, u32 U, u64 last_mask) { return k == U - 1u ? last_mask : ~0ull; }
+__device__ inline unit16 lut_zero(unit16) { return unit16{0u, 0u, 0u, 0u}; }
+__device__ inline unit8 lut_zero(unit8) { return 0ull; }
+
+// By value in the kernel arguments (uniform, scalar loads).  A workgroup is (element group, unit chunk, part): it owns
+// elements [group * G, + G), units [chunk * KC, + KC) of every term, and part `part` of the stream of its units laid
+// out output by output -- output j's G * T_j * KC units from seg[j] on, element, then term, then unit.
+struct LutArgs {
+    const void *plane[kLutMaxIn];
+    void *out[kLutMaxOut];
+    u64 seg[kLutMaxOut + 1];
+    u32 T[kLutMaxOut];
+    u32 mbase[kLutMaxOut + 1];
+    u32 tk_d[kLutMaxOut], tk_magic[kLutMaxOut], tk_shift[kLutMaxOut];    // T_j * KC as a FastDiv
+    u32 t[kLutMaxIn];
+    const u32 *mono, *moff;
+    u64 zero;                 // bit j: output j has an empty ANF (ZERO)
+    u64 last_mask;
+    u64 batch;                // elements of this launch
+    u32 w, m;
+    u32 U, KC, G, chunks, parts, nblocks, xcd;
+    u32 ntab, hb[kMaxTables + 1], tbase[kMaxTables];   // table k: planes [hb[k], hb[k+1]), at unit tbase[k] of the LDS
+    FastDiv dKC;
+};
+
+template <typename Unit, bool Fresh>
+__global__ void __launch_bounds__(256) k_uint_lut(LutArgs a)
+{
+    extern __shared__ __align__(16) unsigned char smem_raw[];
+    Unit *tab = reinterpret_cast<Unit *>(smem_raw);
+    const u32 bid = a.xcd ? xcd_contiguous_block(blockIdx.x, a.nblocks) : blockIdx.x;
+    const u32 gc = bid / a.parts, part = bid - gc * a.parts;
+    const u32 group = gc / a.chunks, chunk = gc - group * a.chunks;
+    const u64 e0 = (u64)group * a.G;
+    const u32 ne = (u32)min((u64)a.G, a.batch - e0);
+    const u32 k0 = chunk * a.KC, kc = min(a.KC, a.U - k0);
+
+    if (Fresh) {
+        // entry 0 of every table is ONE; level b fills entries [2^b, 2^(b+1)) from [0, 2^b) and plane hb[k] + b
+        for (u32 tb = 0; tb < a.ntab; ++tb) {
+            const u32 h = a.hb[tb + 1] - a.hb[tb];
+            for (u32 x = threadIdx.x; x < a.G * a.KC; x += 256u) {
+                const u32 el = csgn_fastdiv(x, a.dKC), kk = x - el * a.KC;
+                tab[a.tbase[tb] + ((el << h) * a.KC) + kk] = lut_one(Unit(), k0 + kk, a.U, a.last_mask);
+            }
+        }
+        for (u32 b = 0; b < a.hb[1]; ++b) {              // table 0 is the widest
+            __syncthreads();
+            for (u32 tb = 0; tb < a.ntab; ++tb) {
+                const u32 h = a.hb[tb + 1] - a.hb[tb];
+                if (b >= h)
+                    continue;
+                const Unit *p = reinterpret_cast<const Unit *>(a.plane[a.hb[tb] + b]);
+                const u32 n = (a.G * a.KC) << b;
+                for (u32 x = threadIdx.x; x < n; x += 256u) {
+                    const u32 row = csgn_fastdiv(x, a.dKC), kk = x - row * a.KC;
+                    const u32 el = row >> b, s = (1u << b) | (row & ((1u << b) - 1u));
+                    if (el >= ne || kk >= kc)
+                        continue;
+                    const u32 at = a.tbase[tb] + ((el << h) | s) * a.KC + kk;
+                    tab[at] = tab[at - (1u << b) * a.KC] & p[(e0 + el) * a.U + k0 + kk];
+                }
+            }
+        }
+        __syncthreads();
+    }
+
+    const u64 W = a.seg[a.m];
+    const u64 lo = W * part / a.parts, hi = W * (part + 1u) / a.parts;
+    for (u32 j = 0; j < a.m; ++j) {
+        const u64 s0 = max(lo, a.seg[j]), s1 = min(hi, a.seg[j + 1]);
+        if (s0 >= s1)
+            continue;
+        const FastDiv dtk = {a.tk_d[j], a.tk_magic[j], a.tk_shift[j]};
+        const u32 Tj = a.T[j], mb = a.mbase[j];
+        const bool zero = (a.zero >> j) & 1u;
+        Unit *o = reinterpret_cast<Unit *>(a.out[j]);
+        const u32 l1 = (u32)(s1 - a.seg[j]);
+        for (u32 l = (u32)(s0 - a.seg[j]) + threadIdx.x; l < l1; l += 256u) {
+            const u32 el = csgn_fastdiv(l, dtk), r = l - el * dtk.d;
+            const u32 q = csgn_fastdiv(r, a.dKC), kk = r - q * a.KC;
+            if (el >= ne || kk >= kc)
+                continue;
+            const u32 k = k0 + kk;
+            const u64 e = e0 + el;
+            Unit v;
+            if (zero) {
+                v = lut_zero(Unit());
+            } else if (Fresh) {
+                const u32 S = a.mono[mb + q];
+                v = tab[a.tbase[0] + ((el << a.hb[1]) | (S & ((1u << a.hb[1]) - 1u))) * a.KC + kk];
+                for (u32 tb = 1; tb < a.ntab; ++tb) {
+                    const u32 h = a.hb[tb + 1] - a.hb[tb];
+                    v &= tab[a.tbase[tb] + ((el << h) | ((S >> a.hb[tb]) & ((1u << h) - 1u))) * a.KC + kk];
+                }
+            } else {
+                // the monomial holding term q: the last one of output j starting at or before it
+                u32 lo_m = mb, hi_m = a.mbase[j + 1];
+                while (hi_m - lo_m > 1u) {
+                    const u32 mid = (lo_m + hi_m) >> 1;
+                    if (a.moff[mid] <= q)
+                        lo_m = mid;
+                    else
+                        hi_m = mid;
+                }
+                const u32 S = a.mono[lo_m];
+                u32 rr = q - a.moff[lo_m];
+                v = lut_one(Unit(), k, a.U, a.last_mask);
+                for (u32 i = a.w; i-- > 0u;) {
+                    if (!((S >> i) & 1u))
+                        continue;
+                    const u32 ti = a.t[i], d = rr % ti;
+                    rr /= ti;
+                    v &= reinterpret_cast<const Unit *>(a.plane[i])[(e * ti + d) * a.U + k];
+                }
+            }
+            unit_store<Unit, true>(o + (e * Tj + q) * a.U + k, v);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------ the plan on the host
+
+constexpr u64 kTermLimit = 1ull << 62;
+
+int lut_check(u64 w, u64 m, const u64 *table)
+{
+    if (w < 1 || w > kLutMaxIn || m < 1 || m > kLutMaxOut || !table)
+        return CSGN_ERR_INVALID;
+    for (u64 x = 0; x < (1ull << w); ++x)
+        if (m < 64 && (table[x] >> m) != 0)
+            return CSGN_ERR_INVALID;
+    return CSGN_OK;
+}
+
+void lut_mobius(u64 w, const u64 *table, u64 *anf)
+{
+    const u64 n = 1ull << w;
+    std::copy(table, table + n, anf);
+    for (u64 i = 0; i < w; ++i)
+        for (u64 x = 0; x < n; ++x)
+            if ((x >> i) & 1u)
+                anf[x] ^= anf[x ^ (1ull << i)];
+}
+
+// terms of M_S: the product of t_i over S (1 for the empty set); 0 at 2^62 or more
+u64 mono_terms(u64 S, const u64 *t)
+{
+    u64 p = 1;
+    for (u32 i = 0; S >> i; ++i) {
+        if (!((S >> i) & 1u))
+            continue;
+        unsigned long long q;
+        if (__builtin_mul_overflow((unsigned long long)p, (unsigned long long)t[i], &q) || q >= kTermLimit)
+            return 0;
+        p = q;
+    }
+    return p;
+}
+
+bool lut_use_fused()
+{
+    const int forced = tune(TUNE_UINT_LUT_FUSED);
+    if (forced == 0 || forced == 1)
+        return forced == 1;
+    return true;              // one launch for every output: no shape measured where the composed form is faster
+}
+
+// The workgroup shape of one apply: tables, elements per workgroup, unit chunks, parts.
+template <typename Unit>
+hipError_t lut_fused(const LutPlan &p, u64 n_bits, u64 batch, const u64 *const *planes, u64 *const *out, u32 U,
+                     hipStream_t s)
+{
+    LutArgs a = {};
+    a.w = p.w;
+    a.m = p.m;
+    a.U = U;
+    a.last_mask = last_word_mask(n_bits);
+    a.mono = p.d_mono;
+    a.moff = p.d_moff;
+    for (u32 i = 0; i < p.w; ++i)
+        a.t[i] = (u32)p.t[i];
+    u64 sumT = 0, maxT = 0;
+    for (u32 j = 0; j < p.m; ++j) {
+        a.T[j] = (u32)p.T[j];
+        if (p.mbase[j + 1] == p.mbase[j])
+            a.zero |= 1ull << j;
+        sumT += p.T[j];
+        maxT = std::max(maxT, p.T[j]);
+    }
+    for (u32 j = 0; j <= p.m; ++j)
+        a.mbase[j] = p.mbase[j];
+    // subset tables: one up to 5 planes, two up to 10, three above; the low tables take the odd planes
+    u64 entries = 0;      // table units per element and unit of a term
+    if (p.fresh) {
+        a.ntab = p.w <= 5 ? 1 : p.w <= 10 ? 2 : 3;
+        a.hb[0] = 0;
+        for (u32 k = 0; k < a.ntab; ++k) {
+            const u32 h = (p.w - a.hb[k] + (a.ntab - k) - 1) / (a.ntab - k);
+            a.hb[k + 1] = a.hb[k] + h;
+            entries += 1ull << h;
+        }
+    }
+    // unit chunks: only when one element's tables at whole terms pass the budget
+    const u64 per_unit = entries * sizeof(Unit);
+    u32 chunks = 1;
+    if (p.fresh && per_unit * U > kLdsBudget)
+        chunks = (u32)((per_unit * U + kLdsBudget - 1) / kLdsBudget);
+    a.chunks = chunks;
+    a.KC = (U + chunks - 1) / chunks;
+    a.chunks = (U + a.KC - 1) / a.KC;
+    // elements per workgroup: enough to give it kPartUnits to write, as many as the tables allow
+    const u64 elem_units = sumT * a.KC;
+    u64 G = std::max<u64>(1, kPartUnits / std::max<u64>(elem_units, 1));
+    if (p.fresh)
+        G = std::min<u64>(G, std::max<u64>(1, kLdsBudget / (per_unit * a.KC)));
+    G = std::min<u64>({G, batch, 64, 0xFFFFFFFFull / (maxT * a.KC)});
+    a.G = (u32)std::max<u64>(G, 1);
+    a.dKC = csgn_fastdiv_make(a.KC);
+    u64 seg = 0;
+    for (u32 j = 0; j < p.m; ++j) {
+        a.seg[j] = seg;
+        const u64 tk = p.T[j] * a.KC;
+        const FastDiv d = csgn_fastdiv_make((u32)tk);
+        a.tk_d[j] = d.d;
+        a.tk_magic[j] = d.magic;
+        a.tk_shift[j] = d.shift;
+        seg += a.G * tk;
+    }
+    a.seg[p.m] = seg;
+    // parts: a workgroup's stream split so each part writes kPartUnits, or four times its table build
+    const u64 build = a.G * entries * a.KC;
+    const u64 target = std::max<u64>(kPartUnits, 4 * build);
+    a.parts = (u32)std::min<u64>(std::max<u64>(1, seg / target), 1u << 16);
+    u32 lds = 0;
+    if (p.fresh) {
+        u32 at = 0;
+        for (u32 k = 0; k < a.ntab; ++k) {
+            a.tbase[k] = at;
+            at += (u32)((a.G << (a.hb[k + 1] - a.hb[k])) * a.KC);
+        }
+        lds = at * (u32)sizeof(Unit);
+    }
+    const u64 per_group = (u64)a.chunks * a.parts;
+    const u64 max_groups = std::max<u64>(1, kMaxBlocks256 / per_group);
+    const u64 groups = (batch + a.G - 1) / a.G;
+    a.xcd = stream_xcd(batch * sumT * U);
+    for (u64 g0 = 0; g0 < groups; g0 += max_groups) {
+        const u64 ng = std::min(max_groups, groups - g0), e0 = g0 * a.G;
+        a.batch = std::min<u64>(batch - e0, ng * a.G);
+        for (u32 i = 0; i < p.w; ++i)
+            a.plane[i] = reinterpret_cast<const Unit *>(planes[i]) + e0 * p.t[i] * U;
+        for (u32 j = 0; j < p.m; ++j)
+            a.out[j] = reinterpret_cast<Unit *>(out[j]) + e0 * p.T[j] * U;
+        a.nblocks = (u32)(ng * per_group);
+        if (p.fresh)
+            k_uint_lut<Unit, true><<<dim3(a.nblocks), 256, lds, s>>>(a);
+        else
+            k_uint_lut<Unit, false><<<dim3(a.nblocks), 256, 0, s>>>(a);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess)
+            return e;
+    }
+    return hipSuccess;
+}
+
+// The composed form: every monomial through the tuned launchers, written into its slice of the output (pitch T_j):
+// ONE by csgn_const_fill, one plane by the strided copy, a product left to right, the last factor written in place.
+// The partial products ping-pong through one stream-ordered block (hipMallocAsync).
+hipError_t lut_composed(const LutPlan &p, u64 n_bits, u64 batch, const u64 *const *planes, u64 *const *out,
+                        hipStream_t s)
+{
+    const u64 dL = (n_bits + 63) / 64;
+    const std::vector<u32> &mono = p.mono;
+    u64 maxP = 0;             // the largest partial product: 2 .. |S| - 1 factors of a monomial
+    for (u32 S : mono) {
+        u64 prod = 1;
+        u32 f = 0;
+        const u32 nf = (u32)__builtin_popcount(S);
+        for (u32 i = 0; i < p.w; ++i)
+            if ((S >> i) & 1u) {
+                prod *= p.t[i];
+                if (++f >= 2 && f < nf)
+                    maxP = std::max(maxP, prod);
+            }
+    }
+    u64 *block = nullptr;
+    if (maxP) {
+        const hipError_t e = hipMallocAsync(reinterpret_cast<void **>(&block), 2 * batch * maxP * dL * 8, s);
+        if (e != hipSuccess)
+            return e;
+    }
+    hipError_t e = hipSuccess;
+    for (u32 j = 0; j < p.m && e == hipSuccess; ++j) {
+        const u64 pitch = p.T[j] * dL;
+        if (p.mbase[j + 1] == p.mbase[j]) {
+            e = const_fill(n_bits, batch, nullptr, 0, out[j], pitch, s);
+            continue;
+        }
+        u64 off = 0;
+        for (u32 x = p.mbase[j]; x < p.mbase[j + 1] && e == hipSuccess; ++x) {
+            const u32 S = mono[x];
+            u64 *dst = out[j] + off * dL;
+            off += mono_terms(S, p.t);
+            if (S == 0) {
+                e = const_fill(n_bits, batch, nullptr, 1, dst, pitch, s);
+                continue;
+            }
+            u32 left = (u32)__builtin_ctz(S);
+            const u64 *cur = planes[left];
+            u64 tc = p.t[left];
+            const u32 rest = S & (S - 1u);
+            if (rest == 0) {
+                e = add_uniform(n_bits, batch, tc, 0, cur, nullptr, dst, s, pitch);
+                continue;
+            }
+            int flip = 0;
+            for (u32 r = rest; r && e == hipSuccess; r &= r - 1u) {
+                const u32 i = (u32)__builtin_ctz(r);
+                const bool last = (r & (r - 1u)) == 0;
+                u64 *to = last ? dst : block + (u64)flip * batch * maxP * dL;
+                e = mul_uniform(n_bits, batch, tc, p.t[i], cur, planes[i], to, 0, s, last ? pitch : 0);
+                cur = to;
+                tc *= p.t[i];
+                flip ^= 1;
+            }
+        }
+    }
+    if (block) {
+        const hipError_t f = hipFreeAsync(block, s);
+        if (e == hipSuccess)
+            e = f;
+    }
+    return e;
+}
+
+} // namespace
+
+// ------------------------------------------------------------------------------ public
+
+int uint_lut_anf(u64 w, u64 m, const u64 *table, u64 *anf)
+{
+    if (int rc = lut_check(w, m, table))
+        return rc;
+    if (!anf)
+        return CSGN_ERR_INVALID;
+    lut_mobius(w, table, anf);
+    return CSGN_OK;
+}
+
+int uint_lut_terms(u64 w, u64 m, const u64 *table, const u64 *t, u64 *T)
+{
+    if (int rc = lut_check(w, m, table))
+        return rc;
+    if (!t || !T)
+        return CSGN_ERR_INVALID;
+    for (u64 i = 0; i < w; ++i)
+        if (t[i] == 0 || t[i] >= kTermLimit)
+            return CSGN_ERR_INVALID;
+    std::vector<u64> anf(1ull << w);
+    lut_mobius(w, table, anf.data());
+    std::vector<u64> out(m, 0);
+    std::vector<bool> any(m, false);
+    for (u64 S = 0; S < anf.size(); ++S) {
+        if (!anf[S])
+            continue;
+        const u64 c = mono_terms(S, t);
+        if (!c)
+            return CSGN_ERR_INVALID;
+        for (u64 j = 0; j < m; ++j)
+            if ((anf[S] >> j) & 1u) {
+                out[j] += c;
+                any[j] = true;
+                if (out[j] >= kTermLimit)
+                    return CSGN_ERR_INVALID;
+            }
+    }
+    for (u64 j = 0; j < m; ++j)
+        T[j] = any[j] ? out[j] : 1;
+    return CSGN_OK;
+}
+
+int uint_lut_plan_create(u64 w, u64 m, const u64 *table, const u64 *t, LutPlan &p, hipError_t &herr)
+{
+    herr = hipSuccess;
+    p = LutPlan();
+    u64 T[kLutMaxOut];
+    if (int rc = uint_lut_terms(w, m, table, t, T))
+        return rc;
+    for (u64 j = 0; j < m; ++j)
+        if (T[j] >= (1ull << 31))
+            return CSGN_ERR_UNSUPPORTED;
+    p.w = (u32)w;
+    p.m = (u32)m;
+    p.fresh = true;
+    for (u64 i = 0; i < w; ++i) {
+        p.t[i] = t[i];
+        p.fresh = p.fresh && t[i] == 1;
+    }
+    std::vector<u64> anf(1ull << w);
+    lut_mobius(w, table, anf.data());
+    std::vector<u32> mono, moff;
+    for (u64 j = 0; j < m; ++j) {
+        p.T[j] = T[j];
+        p.mbase[j] = (u32)mono.size();
+        u64 off = 0;
+        for (u64 S = 0; S < anf.size(); ++S)
+            if ((anf[S] >> j) & 1u) {
+                mono.push_back((u32)S);
+                moff.push_back((u32)off);
+                off += mono_terms(S, t);
+            }
+    }
+    p.mbase[m] = (u32)mono.size();
+    const size_t bytes = std::max<size_t>(mono.size(), 1) * sizeof(u32);
+    if ((herr = hipMalloc(reinterpret_cast<void **>(&p.d_mono), bytes)) != hipSuccess ||
+        (herr = hipMalloc(reinterpret_cast<void **>(&p.d_moff), bytes)) != hipSuccess ||
+        (!mono.empty() && (herr = hipMemcpy(p.d_mono, mono.data(), mono.size() * sizeof(u32), hipMemcpyHostToDevice)) != hipSuccess) ||
+        (!moff.empty() && (herr = hipMemcpy(p.d_moff, moff.data(), moff.size() * sizeof(u32), hipMemcpyHostToDevice)) != hipSuccess)) {
+        uint_lut_plan_free(p);
+        return CSGN_ERR_HIP;
+    }
+    p.mono = std::move(mono);
+    return CSGN_OK;
+}
+
+void uint_lut_plan_free(LutPlan &p)
+{
+    if (p.d_mono)
+        (void)hipFree(p.d_mono);
+    if (p.d_moff)
+        (void)hipFree(p.d_moff);
+    p.d_mono = p.d_moff = nullptr;
+}
+
+const char *uint_lut_kernel_name(const LutPlan &p, u64 n_bits, u64 batch)
+{
+    (void)n_bits;
+    (void)batch;
+    if (p.w == 0)
+        return "";
+    return lut_use_fused() ? "k_uint_lut" : "composed";
+}
+
+hipError_t uint_lut(const LutPlan &p, u64 n_bits, u64 batch, const u64 *const *planes, u64 *const *out, hipStream_t s)
+{
+    if (batch == 0)
+        return hipSuccess;
+    if (!lut_use_fused())
+        return lut_composed(p, n_bits, batch, planes, out, s);
+    const u64 dL = (n_bits + 63) / 64;
+    bool wide = dL % 2 == 0;
+    for (u32 i = 0; i < p.w && wide; ++i)
+        wide = aligned16(planes[i]);
+    for (u32 j = 0; j < p.m && wide; ++j)
+        wide = aligned16(out[j]);
+    const u32 U = (u32)(wide ? dL / 2 : dL);
+    return wide ? lut_fused<unit16>(p, n_bits, batch, planes, out, U, s)
+                : lut_fused<unit8>(p, n_bits, batch, planes, out, U, s);
+}
+
+} // namespace csgn

@@ -30,6 +30,16 @@
 // Uniform planes take one csgn_uint_plain call (one kernel for the whole comparison); ragged ones are composed from the
 // CiphertextBatch operators and Gates.h.  The result's size is checked before anything is allocated or launched.
 //
+// PUBLIC LOOKUP TABLES: LookupTable compiles a table f of 2^inWidth entries (each < 2^outWidth; inWidth 1..16, outWidth
+// 1..64) to its algebraic normal form, the Mobius transform of the table, kept on the host.  lookup(a, f) returns f(a)
+// with output bit j = the sum, ascending in S, of the monomials a_{i1} * a_{i2} * ... (ascending i; ONE for the empty S)
+// with bit j of anf[S] set, ZERO when there is none: csgn_uint_lut_apply's words (include/csgn_hip.h).  With fresh
+// planes output j has |ANF(f_j)| <= 2^w terms.  lookup(a, b, f) indexes f by a + (b << a.width()): encrypted x
+// encrypted functions of small widths (4x4-bit multiply, min, max).  Uniform planes take one csgn_uint_lut_apply (one
+// launch for every output bit), its device plan cached in the LookupTable per vector of plane term counts; ragged
+// planes are composed from the CiphertextBatch operators with the same words.  Every output's size is checked before
+// anything is allocated; past 2^31 words per element std::invalid_argument is thrown.
+//
 // Uniform planes run one csgn_uint_step (or csgn_gate_uniform) call per bit; ragged ones (what compact() may return)
 // are composed from the CiphertextBatch operators and Gates.h, with the same words.  Only the running carry or
 // accumulator is kept alive between bits.
@@ -38,6 +48,7 @@
 
 #include <stdint.h>
 
+#include <memory>
 #include <vector>
 
 #include "Batch.h"
@@ -88,6 +99,27 @@ CiphertextBatch greaterThan(const UIntBatch &a, uint64_t k);
 CiphertextBatch greaterEqual(const UIntBatch &a, uint64_t k);
 // element i: sel[i] ? a[i] : b[i]
 UIntBatch select(const CiphertextBatch &sel, const UIntBatch &a, const UIntBatch &b);
+
+// A public table compiled once; copies share the compiled form.  Safe to use from several threads at once.
+class LookupTable {
+  public:
+    struct Impl;
+    // table.size() == 2^in_width, every entry < 2^out_width (std::invalid_argument otherwise)
+    LookupTable(const std::vector<uint64_t> &table, unsigned in_width, unsigned out_width);
+    unsigned inWidth() const;
+    unsigned outWidth() const;
+    const std::vector<uint64_t> &table() const;
+    const std::vector<uint64_t> &anf() const;      // bit j of anf()[S]: monomial S of output j
+    const std::shared_ptr<Impl> &impl() const { return impl_; }
+
+  private:
+    std::shared_ptr<Impl> impl_;
+};
+
+// f(a), a.width() == f.inWidth(); f.outWidth() planes
+UIntBatch lookup(const UIntBatch &a, const LookupTable &f);
+// f(a + (b << a.width())), a.width() + b.width() == f.inWidth(); one context and element count
+UIntBatch lookup(const UIntBatch &a, const UIntBatch &b, const LookupTable &f);
 
 } // namespace certFHE
 

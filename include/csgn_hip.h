@@ -667,6 +667,44 @@ const char *csgn_uint_plain_kernel(uint64_t n_bits, int cmp, uint64_t batch, uin
 int csgn_uint_plain(uint64_t n_bits, int cmp, uint64_t batch, uint64_t width, uint64_t k,
                     const uint64_t *const *h_planes, const uint64_t *h_terms, uint64_t *d_out, void *stream);
 
+/* A PUBLIC lookup table f applied to a w-bit integer (planes a_0..a_{w-1}, least significant first, plane i uniform with
+ * t_i terms per element): out_width output planes, output j encrypting bit j of f(x).  in_width 1..16, out_width 1..64,
+ * h_table: 2^in_width entries, each < 2^out_width.  The words are the table's algebraic normal form over the planes, a
+ * fixed composition of the reference's operator* / operator+ with ONE and ZERO (csgn_const_fill):
+ *     anf = the Mobius transform of the table, bitwise on the whole word: for each i, for each x with bit i set,
+ *           anf[x] ^= anf[x ^ (1 << i)];  bit j of anf[S] is the coefficient of the monomial S in output j
+ *     M_S = ((a_{i1} * a_{i2}) * ...) over i in S ascending;  M_{} = ONE
+ *     out_j = ((M_{S1} + M_{S2}) + ...) over the S with bit j of anf[S] set, ascending;  none: ZERO (one term)
+ * Terms of output j: T_j = sum over those S of prod_{i in S} t_i (the empty S counts 1); 1 when the ANF is empty.
+ * Fresh 1-term planes: T_j = |ANF(f_j)| <= 2^w. */
+typedef struct csgn_uint_lut csgn_uint_lut;
+/* Host only: the Mobius transform of the table into h_anf (2^in_width words).  CSGN_ERR_INVALID: a width outside its
+ * range, a null pointer or an entry >= 2^out_width. */
+int csgn_uint_lut_anf(uint64_t in_width, uint64_t out_width, const uint64_t *h_table, uint64_t *h_anf);
+/* Host only: T_j of every output into h_out_terms (out_width words), for planes of h_terms[i] terms per element.
+ * CSGN_ERR_INVALID for a bad argument, an entry >= 2^out_width, a plane of 0 terms or a count of 2^62 or more. */
+int csgn_uint_lut_terms(uint64_t in_width, uint64_t out_width, const uint64_t *h_table, const uint64_t *h_terms,
+                        uint64_t *h_out_terms);
+/* Compiles the table for planes of h_terms[i] terms: the ANF, every output's monomial masks and their term offsets,
+ * uploaded once (synchronous).  CSGN_ERR_UNSUPPORTED when an output reaches 2^31 terms; no GPU: CSGN_ERR_NO_DEVICE.
+ * A compiled table is read-only: one may be applied from several host threads at once. */
+int csgn_uint_lut_create(uint64_t in_width, uint64_t out_width, const uint64_t *h_table, const uint64_t *h_terms,
+                         csgn_uint_lut **lut);
+void csgn_uint_lut_destroy(csgn_uint_lut *lut);
+/* Which form a csgn_uint_lut_apply call takes (host only, a static string): "k_uint_lut" (one kernel writes every
+ * output plane, planes read in place, ONE and ZERO made in registers) or "composed" (csgn_mul_uniform /
+ * csgn_add_uniform / csgn_const_fill monomial by monomial into the outputs' slices, partial products in a
+ * stream-ordered block: hipMallocAsync).  Knob "uint_lut_fused" (-1 per shape, 0 / 1 forced) decides; the words are the
+ * same.  Per shape: fused.  "" for a null table or n_bits of 0. */
+const char *csgn_uint_lut_kernel(uint64_t n_bits, const csgn_uint_lut *lut, uint64_t batch);
+/* Applies the table over `batch` elements: h_planes is a HOST array of in_width device pointers (plane i: batch * t_i
+ * * dL words), h_out a HOST array of out_width device pointers (output j: batch * T_j * dL words).  Planes may alias one
+ * another; no output overlaps a plane or another output.  Limits: every T_j * dL below 2^31 words per element
+ * (CSGN_ERR_UNSUPPORTED), batch * that < 2^60.  On the caller's stream, asynchronous; the fused form is one launch and
+ * graph-capturable.  No GPU: CSGN_ERR_NO_DEVICE, no CPU fallback. */
+int csgn_uint_lut_apply(const csgn_uint_lut *lut, uint64_t n_bits, uint64_t batch, const uint64_t *const *h_planes,
+                        uint64_t *const *h_out, void *stream);
+
 /* ------------------------------------------------------------------- tuning ---- */
 
 /* Kernel-choice and sweep knobs ("mul_flat", "mul_touch", "ragged_c", "perm_ballot", ...;
