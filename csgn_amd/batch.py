@@ -245,6 +245,56 @@ class HipPath:
             self.lib.csgn_uint_lut_destroy(handle)
         return outs
 
+    def gather_plan(self, count_in: int, count_out: int, index: Optional[torch.Tensor] = None,
+                    src_off: Optional[torch.Tensor] = None, out_off: Optional[torch.Tensor] = None):
+        """csgn_gather_plan (synchronous).  Returns (rc, total output terms, bad indices, out_off): rc is CSGN_OK or
+        CSGN_ERR_INVALID when an index is >= count_in (then out_off is not written); it does not raise for that case.
+        A ragged source (src_off given) gets fresh output offsets unless `out_off` is given."""
+        if src_off is not None and out_off is None:
+            out_off = self.empty_words(count_out + 1)
+        res = (C.c_uint64 * 2)()
+        rc = self.lib.csgn_gather_plan(count_in, _ptr(src_off), count_out, _ptr(index), _ptr(out_off), res, self.stream)
+        if rc not in (capi.CSGN_OK, capi.CSGN_ERR_INVALID) or (rc != capi.CSGN_OK and res[1] == 0):
+            check(rc)
+        return rc, int(res[0]), int(res[1]), out_off
+
+    def gather(self, n_bits: int, count_in: int, src: torch.Tensor, t_src: int, count_out: int,
+               index: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """csgn_gather of a uniform source (t_src terms per element): element e of the result is source element
+        index[e], or e mod count_in without an index list (tile / broadcast).  The indices must be valid (a plan's)."""
+        dl = self.default_len(n_bits)
+        if out is None:
+            out = self.empty_words(max(count_out * t_src * dl, 1))
+        check(self.lib.csgn_gather(n_bits, count_in, _ptr(src), None, t_src, count_out, _ptr(index), _ptr(out), None, 0,
+                                   self.stream))
+        return out[: count_out * t_src * dl]
+
+    def gather_ragged(self, n_bits: int, count_in: int, src: torch.Tensor, src_off: torch.Tensor, count_out: int,
+                      index: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Plan + gather of a ragged (CSR) source; returns (words, output offsets).  Raises on a bad index."""
+        rc, total, bad, out_off = self.gather_plan(count_in, count_out, index, src_off)
+        check(rc)
+        dl = self.default_len(n_bits)
+        out = self.empty_words(max(total * dl, 1))
+        check(self.lib.csgn_gather(n_bits, count_in, _ptr(src), _ptr(src_off), 0, count_out, _ptr(index), _ptr(out),
+                                   _ptr(out_off), total, self.stream))
+        return out[: total * dl], out_off
+
+    def gather_planes(self, n_bits: int, planes, terms, count_in: int, count_out: int,
+                      index: Optional[torch.Tensor] = None, outs=None):
+        """csgn_gather_planes: every uniform plane (plane j: terms[j] terms per element) gathered by one index list (or
+        the tile form) in one launch.  Returns the output tensors."""
+        dl = self.default_len(n_bits)
+        if outs is None:
+            outs = [self.empty_words(max(count_out * int(t) * dl, 1)) for t in terms]
+        n = len(planes)
+        h_src = (C.c_void_p * n)(*[_ptr(p) for p in planes])
+        h_dst = (C.c_void_p * n)(*[_ptr(o) for o in outs])
+        h_terms = (C.c_uint64 * n)(*[int(t) for t in terms])
+        check(self.lib.csgn_gather_planes(n_bits, n, h_src, h_terms, count_in, count_out, _ptr(index), h_dst,
+                                          self.stream))
+        return [o[: count_out * int(t) * dl] for o, t in zip(outs, terms)]
+
     def add_ragged(self, n_bits: int, left: torch.Tensor, off_left: torch.Tensor,
                    right: torch.Tensor, off_right: torch.Tensor,
                    total_terms_out: Optional[int] = None, max_t1: int = 0, max_t2: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:

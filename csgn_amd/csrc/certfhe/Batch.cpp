@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <string>
 
 namespace certFHE {
 
@@ -164,6 +165,139 @@ CiphertextBatch CiphertextBatch::pack(const std::vector<Ciphertext> &items)
         detail::check(csgn_memcpy_d2d(out.payload->data() + i * terms * dl, items[i].deviceValues(),
                                       (size_t)terms * dl * 8, detail::stream()),
                       "csgn_memcpy_d2d");
+    }
+    return out;
+}
+
+// ---------------------------------------------------------------------------------- data movement (csgn_gather*)
+
+CiphertextBatch CiphertextBatch::gather(const std::vector<uint64_t> &indices) const
+{
+    for (size_t e = 0; e < indices.size(); ++e)
+        if (indices[e] >= count_)
+            throw std::out_of_range("certFHE::CiphertextBatch::gather: index " + std::to_string(indices[e]) +
+                                    " past a batch of " + std::to_string(count_));
+    const uint64_t n = indices.size(), dl = ctx.getDefaultN();
+    if (uniform()) {
+        CiphertextBatch out(ctx, n, terms_);
+        if (n == 0 || terms_ == 0)
+            return out;
+        std::shared_ptr<DevicePayload> d_idx = detail::uploadWords(indices.data(), n);
+        detail::check(csgn_gather(ctx.getN(), count_, deviceValues(), nullptr, terms_, n, d_idx->data(),
+                                  out.payload->data(), nullptr, 0, detail::stream()),
+                      "csgn_gather");
+        return out;
+    }
+    CiphertextBatch out(ctx, n, 0);
+    out.offsets_.assign(n + 1, 0);
+    for (uint64_t e = 0; e < n; ++e)
+        out.offsets_[e + 1] = out.offsets_[e] + termsOf(indices[e]);
+    if (n == 0)
+        return out;
+    std::shared_ptr<DevicePayload> d_idx = detail::uploadWords(indices.data(), n);
+    std::shared_ptr<DevicePayload> off_out = detail::allocWords(n + 1);
+    uint64_t plan[2] = {0, 0};
+    detail::check(csgn_gather_plan(count_, deviceOffsets(), n, d_idx->data(), off_out->data(), plan, detail::stream()),
+                  "csgn_gather_plan");
+    if (plan[0] != out.offsets_.back())
+        throw std::logic_error("certFHE::CiphertextBatch::gather: device and host offsets disagree");
+    out.payload = detail::allocWords(plan[0] * dl);
+    out.d_offsets_ = off_out;
+    if (plan[0])
+        detail::check(csgn_gather(ctx.getN(), count_, deviceValues(), deviceOffsets(), 0, n, d_idx->data(),
+                                  out.payload->data(), off_out->data(), plan[0], detail::stream()),
+                      "csgn_gather");
+    return out;
+}
+
+CiphertextBatch CiphertextBatch::slice(uint64_t begin, uint64_t end) const
+{
+    if (begin > end || end > count_)
+        throw std::out_of_range("certFHE::CiphertextBatch::slice: [" + std::to_string(begin) + ", " + std::to_string(end) +
+                                ") of a batch of " + std::to_string(count_));
+    const uint64_t n = end - begin, dl = ctx.getDefaultN();
+    const uint64_t t0 = uniform() ? begin * terms_ : offsets_[begin], t1 = uniform() ? end * terms_ : offsets_[end];
+    CiphertextBatch out(ctx, n, uniform() ? terms_ : 0);
+    if (!uniform()) {
+        out.offsets_.resize(n + 1);
+        for (uint64_t i = 0; i <= n; ++i)
+            out.offsets_[i] = offsets_[begin + i] - t0;
+        out.payload = detail::allocWords((t1 - t0) * dl);
+    }
+    if (t1 > t0)
+        detail::check(csgn_memcpy_d2d(out.payload->data(), deviceValues() + t0 * dl, (size_t)(t1 - t0) * dl * 8,
+                                      detail::stream()),
+                      "csgn_memcpy_d2d");
+    return out;
+}
+
+CiphertextBatch CiphertextBatch::broadcast(uint64_t count) const
+{
+    if (count_ != 1)
+        throw std::invalid_argument("certFHE::CiphertextBatch::broadcast: the batch holds " + std::to_string(count_) +
+                                    " elements, not 1");
+    if (count >= (1ull << 32))
+        throw std::invalid_argument("certFHE::CiphertextBatch::broadcast: 2^32 elements or more");
+    const uint64_t t = uniform() ? terms_ : offsets_[1];
+    if (!uniform()) {                                              // a ragged batch of one element stays ragged
+        CiphertextBatch out(ctx, count, 0);
+        out.offsets_.resize(count + 1);
+        for (uint64_t i = 0; i <= count; ++i)
+            out.offsets_[i] = i * t;
+        if (count == 0)
+            return out;
+        std::shared_ptr<DevicePayload> off_out = detail::allocWords(count + 1);
+        uint64_t plan[2] = {0, 0};
+        detail::check(csgn_gather_plan(1, deviceOffsets(), count, nullptr, off_out->data(), plan, detail::stream()),
+                      "csgn_gather_plan");
+        out.payload = detail::allocWords(plan[0] * ctx.getDefaultN());
+        out.d_offsets_ = off_out;
+        if (plan[0])
+            detail::check(csgn_gather(ctx.getN(), 1, deviceValues(), deviceOffsets(), 0, count, nullptr,
+                                      out.payload->data(), off_out->data(), plan[0], detail::stream()),
+                          "csgn_gather");
+        return out;
+    }
+    CiphertextBatch out(ctx, count, t);
+    if (count && t)
+        detail::check(csgn_gather(ctx.getN(), 1, deviceValues(), nullptr, t, count, nullptr, out.payload->data(),
+                                  nullptr, 0, detail::stream()),
+                      "csgn_gather");
+    return out;
+}
+
+CiphertextBatch CiphertextBatch::concat(const std::vector<CiphertextBatch> &parts)
+{
+    if (parts.empty())
+        throw std::invalid_argument("certFHE::CiphertextBatch::concat: no parts");
+    const Context &c = parts[0].ctx;
+    bool same_terms = true;
+    uint64_t count = 0, total = 0;
+    for (size_t k = 0; k < parts.size(); ++k) {
+        if (parts[k].ctx.getN() != c.getN() || parts[k].ctx.getD() != c.getD())
+            throw std::invalid_argument("certFHE::CiphertextBatch::concat: parts differ in context");
+        same_terms = same_terms && parts[k].uniform() && parts[k].terms_ == parts[0].terms_;
+        count += parts[k].count_;
+        total += parts[k].totalTerms();
+    }
+    const uint64_t dl = c.getDefaultN();
+    CiphertextBatch out(c, count, same_terms ? parts[0].terms_ : 0);
+    if (!same_terms) {
+        out.offsets_.reserve(count + 1);
+        out.offsets_.push_back(0);
+        for (size_t k = 0; k < parts.size(); ++k)
+            for (uint64_t i = 0; i < parts[k].count_; ++i)
+                out.offsets_.push_back(out.offsets_.back() + parts[k].termsOf(i));
+        out.payload = detail::allocWords(total * dl);
+    }
+    uint64_t at = 0;
+    for (size_t k = 0; k < parts.size(); ++k) {
+        const uint64_t words = parts[k].totalTerms() * dl;
+        if (words)
+            detail::check(csgn_memcpy_d2d(out.payload->data() + at, parts[k].deviceValues(), (size_t)words * 8,
+                                          detail::stream()),
+                          "csgn_memcpy_d2d");
+        at += words;
     }
     return out;
 }

@@ -337,6 +337,101 @@ UIntBatch UIntBatch::compact() const
     return UIntBatch(planes);
 }
 
+namespace {
+// every plane uniform: one csgn_gather_planes launch (d_idx nullptr: the tile form) into fresh uniform planes
+std::vector<CiphertextBatch> gatherUniformPlanes(const std::vector<CiphertextBatch> &planes, uint64_t count_out,
+                                                 const uint64_t *d_idx)
+{
+    const Context &ctx = planes[0].context();
+    std::vector<CiphertextBatch> out;
+    std::vector<const uint64_t *> src;
+    std::vector<uint64_t *> dst;
+    std::vector<uint64_t> terms;
+    for (size_t j = 0; j < planes.size(); ++j) {
+        out.push_back(UIntAccess::make(ctx, count_out, planes[j].terms()));
+        src.push_back(planes[j].deviceValues());
+        terms.push_back(planes[j].terms());
+    }
+    for (size_t j = 0; j < out.size(); ++j)
+        dst.push_back(UIntAccess::words(out[j]));
+    if (count_out)
+        detail::check(csgn_gather_planes(ctx.getN(), planes.size(), src.data(), terms.data(), planes[0].size(), count_out,
+                                         d_idx, dst.data(), detail::stream()),
+                      "csgn_gather_planes");
+    return out;
+}
+
+bool allUniform(const std::vector<CiphertextBatch> &planes)
+{
+    for (size_t j = 0; j < planes.size(); ++j)
+        if (!planes[j].uniform())
+            return false;
+    return true;
+}
+} // namespace
+
+UIntBatch UIntBatch::gather(const std::vector<uint64_t> &indices) const
+{
+    for (size_t e = 0; e < indices.size(); ++e)
+        if (indices[e] >= size())
+            throw std::out_of_range("certFHE::UIntBatch::gather: index " + std::to_string(indices[e]) +
+                                    " past a batch of " + std::to_string(size()));
+    if (!allUniform(planes_)) {
+        std::vector<CiphertextBatch> planes;
+        for (size_t j = 0; j < planes_.size(); ++j)
+            planes.push_back(planes_[j].gather(indices));
+        return UIntBatch(planes);
+    }
+    if (indices.empty())
+        return UIntBatch(gatherUniformPlanes(planes_, 0, nullptr));
+    std::shared_ptr<detail::DevicePayload> d_idx = detail::uploadWords(indices.data(), indices.size());
+    return UIntBatch(gatherUniformPlanes(planes_, indices.size(), d_idx->data()));
+}
+
+UIntBatch UIntBatch::slice(uint64_t begin, uint64_t end) const
+{
+    if (begin > end || end > size())
+        throw std::out_of_range("certFHE::UIntBatch::slice: [" + std::to_string(begin) + ", " + std::to_string(end) +
+                                ") of a batch of " + std::to_string(size()));
+    std::vector<CiphertextBatch> planes;
+    for (size_t j = 0; j < planes_.size(); ++j)
+        planes.push_back(planes_[j].slice(begin, end));
+    return UIntBatch(planes);
+}
+
+UIntBatch UIntBatch::broadcast(uint64_t count) const
+{
+    if (size() != 1)
+        throw std::invalid_argument("certFHE::UIntBatch::broadcast: the batch holds " + std::to_string(size()) +
+                                    " integers, not 1");
+    if (count >= (1ull << 32))
+        throw std::invalid_argument("certFHE::UIntBatch::broadcast: 2^32 integers or more");
+    if (!allUniform(planes_)) {
+        std::vector<CiphertextBatch> planes;
+        for (size_t j = 0; j < planes_.size(); ++j)
+            planes.push_back(planes_[j].broadcast(count));
+        return UIntBatch(planes);
+    }
+    return UIntBatch(gatherUniformPlanes(planes_, count, nullptr));
+}
+
+UIntBatch UIntBatch::concat(const std::vector<UIntBatch> &parts)
+{
+    if (parts.empty())
+        throw std::invalid_argument("certFHE::UIntBatch::concat: no parts");
+    for (size_t k = 1; k < parts.size(); ++k)
+        if (parts[k].width() != parts[0].width() || !sameContext(parts[k].context(), parts[0].context()))
+            throw std::invalid_argument("certFHE::UIntBatch::concat: parts differ in width or context");
+    std::vector<CiphertextBatch> planes;
+    for (unsigned j = 0; j < parts[0].width(); ++j) {
+        std::vector<CiphertextBatch> pieces;
+        for (size_t k = 0; k < parts.size(); ++k)
+            pieces.push_back(parts[k].planes_[j]);
+        planes.push_back(CiphertextBatch::concat(pieces));
+    }
+    return UIntBatch(planes);
+}
+
 std::vector<uint64_t> UIntBatch::decrypt(const SecretKey &key) const
 {
     std::vector<uint64_t> values(size(), 0);

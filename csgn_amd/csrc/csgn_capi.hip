@@ -1216,6 +1216,117 @@ int csgn_uint_lut_apply(const csgn_uint_lut *lut, uint64_t n_bits, uint64_t batc
     return CSGN_OK;
 }
 
+/* ------------------------------------------------------ gather / tile / broadcast ---- */
+
+namespace {
+// the counts every gather entry point shares; CSGN_OK or the failure (arguments are checked before the device)
+int check_gather_counts(uint64_t count_in, uint64_t count_out)
+{
+    REQUIRE(count_in < (1ull << 32) && count_out < (1ull << 32), "gather: counts %llu -> %llu (both below 2^32)",
+            (unsigned long long)count_in, (unsigned long long)count_out);
+    REQUIRE(count_in > 0 || count_out == 0, "gather: %llu output elements from an empty source",
+            (unsigned long long)count_out);
+    return CSGN_OK;
+}
+} // namespace
+
+const char *csgn_gather_kernel(uint64_t n_bits, uint64_t count_out, int ragged, uint64_t n_planes)
+{
+    return csgn::gather_kernel_name(n_bits, count_out, ragged != 0, n_planes);
+}
+
+int csgn_gather_plan(uint64_t count_in, const uint64_t *d_src_off, uint64_t count_out, const uint64_t *d_index,
+                     uint64_t *d_out_off, uint64_t *h_result, void *stream)
+{
+    REQUIRE(h_result, "h_result is null");
+    h_result[0] = h_result[1] = 0;
+    if (count_in == 0 && count_out > 0 && d_index && count_out < (1ull << 32)) {
+        h_result[1] = count_out;                                   // every index is past an empty source
+        return fail(CSGN_ERR_INVALID, "gather plan: %llu indices into an empty source", (unsigned long long)count_out);
+    }
+    if (int rc = check_gather_counts(count_in, count_out))
+        return rc;
+    REQUIRE(!d_src_off || d_out_off, "gather plan: a ragged source needs d_out_off");
+    if (int rc = require_device("csgn_gather_plan"))
+        return rc;
+    u64 result[2] = {0, 0};
+    hipError_t e = hipSuccess;
+    if (csgn::gather_plan(count_in, (const u64 *)d_src_off, count_out, (const u64 *)d_index, (u64 *)d_out_off, result, e,
+                          S(stream)))
+        return hip_fail(e, "csgn_gather_plan");
+    h_result[0] = result[0];
+    h_result[1] = result[1];
+    if (result[1])
+        return fail(CSGN_ERR_INVALID, "gather plan: %llu of %llu indices are >= count_in = %llu",
+                    (unsigned long long)result[1], (unsigned long long)count_out, (unsigned long long)count_in);
+    return CSGN_OK;
+}
+
+int csgn_gather(uint64_t n_bits, uint64_t count_in, const uint64_t *d_src, const uint64_t *d_src_off, uint64_t t_src,
+                uint64_t count_out, const uint64_t *d_index, uint64_t *d_dst, const uint64_t *d_dst_off,
+                uint64_t total_terms_out, void *stream)
+{
+    if (int rc = check_n(n_bits))
+        return rc;
+    if (int rc = check_gather_counts(count_in, count_out))
+        return rc;
+    const uint64_t dl = csgn_default_len(n_bits);
+    if (!d_src_off) {
+        REQUIRE(!d_dst_off, "gather: a uniform source gives a uniform output (d_dst_off must be NULL)");
+        if (!product_below(t_src, dl, 1, 1ull << 31))
+            return fail(CSGN_ERR_UNSUPPORTED, "gather: %llu terms per element exceed 2^31 words", (unsigned long long)t_src);
+        if (!product_below(count_out, t_src, dl, 1ull << 60))
+            return fail(CSGN_ERR_UNSUPPORTED, "gather of %llu elements: size overflows", (unsigned long long)count_out);
+        REQUIRE(count_out == 0 || t_src == 0 || (d_src && d_dst), "null device pointer");
+        if (int rc = require_device("csgn_gather"))
+            return rc;
+        const u64 *src = (const u64 *)d_src;
+        u64 *dst = (u64 *)d_dst;
+        HIP_TRY(csgn::gather_planes(n_bits, 1, &src, (const u64 *)&t_src, count_in, count_out, (const u64 *)d_index,
+                                    &dst, S(stream)));
+        return CSGN_OK;
+    }
+    REQUIRE(d_dst_off, "gather: a ragged source needs the output offsets of its plan");
+    if (!product_below(total_terms_out, dl, 1, 1ull << 60))
+        return fail(CSGN_ERR_UNSUPPORTED, "gather of %llu terms: size overflows", (unsigned long long)total_terms_out);
+    REQUIRE(count_out == 0 || total_terms_out == 0 || (d_src && d_dst), "null device pointer");
+    if (int rc = require_device("csgn_gather"))
+        return rc;
+    HIP_TRY(csgn::gather_ragged(n_bits, count_in, (const u64 *)d_src, (const u64 *)d_src_off, count_out,
+                                (const u64 *)d_index, (u64 *)d_dst, (const u64 *)d_dst_off, total_terms_out, S(stream)));
+    return CSGN_OK;
+}
+
+int csgn_gather_planes(uint64_t n_bits, uint64_t n_planes, const uint64_t *const *h_src, const uint64_t *h_terms,
+                       uint64_t count_in, uint64_t count_out, const uint64_t *d_index, uint64_t *const *h_dst,
+                       void *stream)
+{
+    if (int rc = check_n(n_bits))
+        return rc;
+    REQUIRE(n_planes >= 1 && n_planes <= csgn::kGatherMaxPlanes, "gather: %llu planes (1..64)",
+            (unsigned long long)n_planes);
+    REQUIRE(h_src && h_terms && h_dst, "null host pointer");
+    if (int rc = check_gather_counts(count_in, count_out))
+        return rc;
+    const uint64_t dl = csgn_default_len(n_bits);
+    uint64_t words = 0;
+    for (uint64_t j = 0; j < n_planes; ++j) {
+        if (!product_below(h_terms[j], dl, 1, 1ull << 31))
+            return fail(CSGN_ERR_UNSUPPORTED, "gather: plane %llu has %llu terms per element, past 2^31 words",
+                        (unsigned long long)j, (unsigned long long)h_terms[j]);
+        if (!product_below(count_out, h_terms[j], dl, (1ull << 60) - words))
+            return fail(CSGN_ERR_UNSUPPORTED, "gather of %llu elements: size overflows", (unsigned long long)count_out);
+        words += count_out * h_terms[j] * dl;
+        REQUIRE(count_out == 0 || h_terms[j] == 0 || (h_src[j] && h_dst[j]), "null device pointer (plane %llu)",
+                (unsigned long long)j);
+    }
+    if (int rc = require_device("csgn_gather_planes"))
+        return rc;
+    HIP_TRY(csgn::gather_planes(n_bits, n_planes, (const u64 *const *)h_src, (const u64 *)h_terms, count_in, count_out,
+                                (const u64 *)d_index, (u64 *const *)h_dst, S(stream)));
+    return CSGN_OK;
+}
+
 /* ------------------------------------------------------------------ tuning ---- */
 
 int csgn_set_tuning(const char *key, int value)

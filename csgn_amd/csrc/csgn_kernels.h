@@ -166,6 +166,20 @@ void uint_lut_plan_free(LutPlan &p);
 const char *uint_lut_kernel_name(const LutPlan &p, u64 n_bits, u64 batch);
 hipError_t uint_lut(const LutPlan &p, u64 n_bits, u64 batch, const u64 *const *planes, u64 *const *out, hipStream_t s);
 
+// gather / tile / broadcast (csgn_gather.hip), include/csgn_hip.h's definition: output element e = source element
+// idx[e], or e mod count_in when idx is nullptr.  Counts below 2^32, count_in > 0 when count_out > 0.
+constexpr u64 kGatherMaxPlanes = 64;
+const char *gather_kernel_name(u64 n_bits, u64 count_out, bool ragged, u64 n_planes);
+// synchronous; result[0] = output terms (ragged source), result[1] = bad indices (out_off untouched when nonzero).
+// Returns 0, or 1 with herr set.
+int gather_plan(u64 count_in, const u64 *src_off, u64 count_out, const u64 *idx, u64 *out_off, u64 result[2],
+                hipError_t &herr, hipStream_t s);
+// uniform planes, plane j of terms[j] terms per element, every plane in one launch
+hipError_t gather_planes(u64 n_bits, u64 n_planes, const u64 *const *src, const u64 *terms, u64 count_in,
+                         u64 count_out, const u64 *idx, u64 *const *dst, hipStream_t s);
+hipError_t gather_ragged(u64 n_bits, u64 count_in, const u64 *src, const u64 *src_off, u64 count_out, const u64 *idx,
+                         u64 *dst, const u64 *out_off, u64 total_terms_out, hipStream_t s);
+
 hipError_t small_ops(u64 n_bits, u64 count, const ::csgn_small_op *ops, hipStream_t s);
 size_t decrypt_scratch_bytes(u64 batch, u64 total_terms);
 // out[i] = a[i] & b[i] (is_product) or a[i] ^ b[i]: Dec(a*b) = Dec(a) & Dec(b), Dec(a+b) = Dec(a) ^ Dec(b)

@@ -80,6 +80,21 @@ class CiphertextBatch {
     std::vector<unsigned char> decryptProduct(const CiphertextBatch &rhs, const SecretKey &key) const;
     std::vector<unsigned char> decryptSum(const CiphertextBatch &rhs, const SecretKey &key) const;
 
+    // EXTENSION: data movement (csgn_gather* of include/csgn_hip.h).  Element e of the result is a bit-for-bit copy of a
+    // source element: the same terms in the same order.  A uniform batch gives a uniform result of the same terms per
+    // element, a ragged batch a ragged one (an element of 0 terms stays at 0 terms).
+    // gather: element e = this[indices[e]]; any order, repeats allowed, any length (0 included).  Every index is
+    // checked on the host first: std::out_of_range before anything is allocated or launched.  One kernel launch.
+    CiphertextBatch gather(const std::vector<uint64_t> &indices) const;
+    // slice: elements [begin, end) as a new batch (a copy); std::out_of_range unless begin <= end <= size().
+    CiphertextBatch slice(uint64_t begin, uint64_t end) const;
+    // broadcast: `count` copies of the only element; std::invalid_argument unless size() == 1.  One kernel launch,
+    // e.g. one encrypted query against a table of `count` rows: equalTo(db, q.broadcast(db.size())) (UInt.h).
+    CiphertextBatch broadcast(uint64_t count) const;
+    // concat: the parts' elements one after the other.  std::invalid_argument for no parts or parts of different
+    // contexts.  Parts that are all uniform with one term count give a uniform batch, anything else a ragged one.
+    static CiphertextBatch concat(const std::vector<CiphertextBatch> &parts);
+
     Ciphertext at(uint64_t i) const;          // copy of element i as an ordinary Ciphertext
     uint64_t size() const { return count_; }
     uint64_t terms() const { return terms_; }  // per element; 0 for a ragged batch (see termsOf)

@@ -79,6 +79,16 @@ class UIntBatch {
     std::vector<uint64_t> decrypt(const SecretKey &key) const;
 
     // modulo 2^width; both operands of one width, context and element count
+    // The data movement of CiphertextBatch (Batch.h) on every plane: element e of the result is a bit-for-bit copy of a
+    // source integer.  gather and broadcast move every uniform plane in ONE launch (csgn_gather_planes); ragged planes
+    // go through CiphertextBatch::gather / broadcast.  gather: std::out_of_range before anything is allocated;
+    // slice: std::out_of_range unless begin <= end <= size(); broadcast: std::invalid_argument unless size() == 1;
+    // concat: std::invalid_argument for no parts, or parts of different widths or contexts.
+    UIntBatch gather(const std::vector<uint64_t> &indices) const;
+    UIntBatch slice(uint64_t begin, uint64_t end) const;
+    UIntBatch broadcast(uint64_t count) const;
+    static UIntBatch concat(const std::vector<UIntBatch> &parts);
+
     UIntBatch operator+(const UIntBatch &rhs) const;
     UIntBatch operator-(const UIntBatch &rhs) const;
 };

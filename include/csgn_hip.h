@@ -705,6 +705,44 @@ const char *csgn_uint_lut_kernel(uint64_t n_bits, const csgn_uint_lut *lut, uint
 int csgn_uint_lut_apply(const csgn_uint_lut *lut, uint64_t n_bits, uint64_t batch, const uint64_t *const *h_planes,
                         uint64_t *const *h_out, void *stream);
 
+/* ------------------------------------------------------ gather / tile / broadcast ---- */
+
+/* Data movement between batches: output element e is a bit-for-bit copy of source element idx[e] -- the same terms in
+ * the same order, so the same words.  Indices are uint64 device words in any order and may repeat; count_out may be 0,
+ * smaller than count_in or larger.  Both counts stay below 2^32.  d_index == NULL selects the TILE form,
+ * idx[e] = e mod count_in; with count_in == 1 that is a BROADCAST.  Shapes: a uniform source of t terms per element
+ * gives a uniform output of t terms per element; a ragged (CSR) source gives a ragged output whose offsets are the
+ * exclusive prefix sums of the gathered elements' term counts (an element of 0 terms stays at 0 terms).  An index
+ * >= count_in is an error: csgn_gather_plan reports it, and no kernel reads outside the source or its offsets because
+ * of one.  A nonempty output needs count_in >= 1 (CSGN_ERR_INVALID otherwise).  No GPU: CSGN_ERR_NO_DEVICE, no CPU
+ * fallback. */
+/* Validates the index list and, for a ragged source (d_src_off != NULL, count_in + 1 words), writes the output offsets
+ * to d_out_off (count_out + 1 words) and sets h_result[0] to the output's total terms.  Uniform source
+ * (d_src_off == NULL): validation only, h_result[0] = 0.  h_result[1] = the number of indices >= count_in; when it is
+ * nonzero the call returns CSGN_ERR_INVALID and d_out_off is not written.  Runs on the device (the prefix sum never
+ * leaves it) and is SYNCHRONOUS: it hands sizes to the host.  d_index == NULL: the tile form (nothing to validate). */
+int csgn_gather_plan(uint64_t count_in, const uint64_t *d_src_off, uint64_t count_out, const uint64_t *d_index,
+                     uint64_t *d_out_off, uint64_t *h_result, void *stream);
+/* The gather itself, one launch per 2^32 workgroups' worth of output (in practice one), asynchronous on the caller's
+ * stream and graph-capturable.  Uniform source: d_src_off and d_dst_off NULL, t_src terms per element (t_src * dL
+ * below 2^31 words), d_dst: count_out * t_src * dL words.  Ragged source: d_src_off (count_in + 1 words), d_dst_off
+ * from csgn_gather_plan of the same index list, total_terms_out = its h_result[0], d_dst: total_terms_out * dL words;
+ * t_src is ignored.  The index list must have passed a plan: the kernel still compares every index with count_in
+ * before it follows it and leaves an element whose index fails unwritten.  Outputs below 2^60 words. */
+int csgn_gather(uint64_t n_bits, uint64_t count_in, const uint64_t *d_src, const uint64_t *d_src_off, uint64_t t_src,
+                uint64_t count_out, const uint64_t *d_index, uint64_t *d_dst, const uint64_t *d_dst_off,
+                uint64_t total_terms_out, void *stream);
+/* The UIntBatch form: n_planes (1..64) UNIFORM planes of count_in elements, plane j of h_terms[j] terms per element
+ * (0: an empty plane, nothing written), gathered by ONE index list (or the tile form) into h_dst[j]
+ * (count_out * h_terms[j] * dL words) in ONE launch.  h_src / h_dst / h_terms are HOST arrays of n_planes entries. */
+int csgn_gather_planes(uint64_t n_bits, uint64_t n_planes, const uint64_t *const *h_src, const uint64_t *h_terms,
+                       uint64_t count_in, uint64_t count_out, const uint64_t *d_index, uint64_t *const *h_dst,
+                       void *stream);
+/* Host only, a static string: the kernel a csgn_gather / csgn_gather_planes call launches -- "k_gather" (uniform
+ * planes, indexed or tile), "k_gather_ragged" (a ragged source; n_planes must be 1), "none" (count_out == 0), ""
+ * (n_bits == 0, n_planes outside 1..64, or a ragged plane table). */
+const char *csgn_gather_kernel(uint64_t n_bits, uint64_t count_out, int ragged, uint64_t n_planes);
+
 /* ------------------------------------------------------------------- tuning ---- */
 
 /* Kernel-choice and sweep knobs ("mul_flat", "mul_touch", "ragged_c", "perm_ballot", ...;
