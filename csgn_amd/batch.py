@@ -295,6 +295,26 @@ class HipPath:
                                           self.stream))
         return [o[: count_out * int(t) * dl] for o, t in zip(outs, terms)]
 
+    def uint_read(self, n_bits: int, batch: int, index, index_terms, rows: int, table, table_terms, outs=None):
+        """csgn_uint_read: the encrypted table `table` (planes of `rows` elements, plane j uniform with table_terms[j]
+        terms) read at the encrypted index `index` (bit 0 first; plane k a uniform batch of index_terms[k] terms).  One
+        tensor per table plane, table_terms[j] * E terms per element (E = csgn_uint_read_terms); fresh ones unless
+        `outs` is given."""
+        v, w = len(index), len(table)
+        assert v == len(index_terms) and w == len(table_terms)
+        h_s = (C.c_uint64 * max(v, 1))(*[int(t) for t in index_terms])
+        h_t = (C.c_uint64 * max(w, 1))(*[int(t) for t in table_terms])
+        E = int(self.lib.csgn_uint_read_terms(v, h_s, rows))
+        assert E, "bad index width, rows or term count"
+        dl = self.default_len(n_bits)
+        if outs is None:
+            outs = [self.empty_words(max(batch * int(t) * E * dl, 1)) for t in table_terms]
+        h_x = (C.c_void_p * max(v, 1))(*[_ptr(p) for p in index])
+        h_d = (C.c_void_p * max(w, 1))(*[_ptr(p) for p in table])
+        h_out = (C.c_void_p * max(w, 1))(*[_ptr(o) for o in outs])
+        check(self.lib.csgn_uint_read(n_bits, batch, v, h_x, h_s, rows, w, h_d, h_t, h_out, self.stream))
+        return [o[: batch * int(t) * E * dl] for o, t in zip(outs, table_terms)]
+
     def add_ragged(self, n_bits: int, left: torch.Tensor, off_left: torch.Tensor,
                    right: torch.Tensor, off_right: torch.Tensor,
                    total_terms_out: Optional[int] = None, max_t1: int = 0, max_t2: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:

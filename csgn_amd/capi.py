@@ -145,6 +145,10 @@ SIGNATURES = {
     "csgn_gather": (C.c_int, [u64, u64, vp, vp, u64, u64, vp, vp, vp, u64, vp]),
     "csgn_gather_planes": (C.c_int, [u64, u64, C.POINTER(vp), C.POINTER(u64), u64, u64, vp, C.POINTER(vp), vp]),
     "csgn_gather_kernel": (C.c_char_p, [u64, u64, C.c_int, u64]),
+    "csgn_uint_read_terms": (u64, [u64, C.POINTER(u64), u64]),
+    "csgn_uint_read_kernel": (C.c_char_p, [u64, u64, u64, C.POINTER(u64), u64, u64, C.POINTER(u64)]),
+    "csgn_uint_read": (C.c_int, [u64, u64, u64, C.POINTER(vp), C.POINTER(u64), u64, u64, C.POINTER(vp), C.POINTER(u64),
+                                 C.POINTER(vp), vp]),
     "csgn_set_tuning": (C.c_int, [C.c_char_p, C.c_int]),
     "csgn_get_tuning": (C.c_int, [C.c_char_p, C.POINTER(C.c_int)]),
     "csgn_reset_tuning": (None, []),

@@ -653,3 +653,87 @@ UIntBatch lookup(const UIntBatch &a, const UIntBatch &b, const LookupTable &f)
 }
 
 } // namespace certFHE
+
+namespace certFHE {
+
+// ------------------------------------------------------------------ encrypted tables at encrypted indices
+
+namespace {
+
+// every table plane read at the index: out_j = sum over r < rows of equalTo(index, r) * row r of plane j
+std::vector<CiphertextBatch> readPlanes(const std::vector<CiphertextBatch> &table, const UIntBatch &index)
+{
+    const Context &ctx = index.context();
+    const uint64_t v = index.width(), rows = table[0].size(), m = index.size();
+    for (size_t j = 0; j < table.size(); ++j)
+        if (!sameContext(table[j].context(), ctx) || table[j].size() != rows)
+            throw std::invalid_argument("certFHE::readAt: the table and the index differ in context, or the table planes in rows");
+    if (v > 16)
+        throw std::invalid_argument("certFHE::readAt: the index is wider than 16 bits");
+    if (rows == 0 || rows > (1ull << v))
+        throw std::invalid_argument("certFHE::readAt: the table has " + std::to_string(rows) + " rows, not 1..2^" +
+                                    std::to_string(v));
+    std::vector<uint64_t> s(v), t(table.size()), T(table.size());
+    bool uniform = true;
+    for (unsigned k = 0; k < v; ++k) {
+        s[k] = termsOf(index.plane(k));                   // a ragged plane: its largest element, a bound
+        uniform = uniform && index.plane(k).uniform();
+    }
+    const uint64_t E = csgn_uint_read_terms(v, s.data(), rows);
+    for (size_t j = 0; j < table.size(); ++j) {
+        t[j] = termsOf(table[j]);
+        uniform = uniform && table[j].uniform();
+        if (E == 0 || t[j] == 0 || t[j] > kMaxWords / E)
+            throw std::invalid_argument("certFHE::readAt: an output plane exceeds 2^31 words per element (the index "
+                                        "is too wide or has too many terms)");
+        T[j] = checked(t[j] * E, ctx, "readAt");
+    }
+    std::vector<CiphertextBatch> out;
+    if (uniform || m == 0) {
+        for (size_t j = 0; j < table.size(); ++j)
+            out.push_back(UIntAccess::make(ctx, m, T[j]));
+        if (m) {
+            std::vector<const uint64_t *> x(v), d(table.size());
+            std::vector<uint64_t *> o(table.size());
+            for (unsigned k = 0; k < v; ++k)
+                x[k] = index.plane(k).deviceValues();
+            for (size_t j = 0; j < table.size(); ++j) {
+                d[j] = table[j].deviceValues();
+                o[j] = UIntAccess::words(out[j]);
+            }
+            detail::check(csgn_uint_read(ctx.getN(), m, v, x.data(), s.data(), rows, table.size(), d.data(), t.data(),
+                                         o.data(), detail::stream()),
+                          "csgn_uint_read");
+        }
+        return out;
+    }
+    // ragged: the definition itself through the batch operators
+    for (uint64_t r = 0; r < rows; ++r) {
+        const CiphertextBatch eq = equalTo(index, r);
+        for (size_t j = 0; j < table.size(); ++j) {
+            const CiphertextBatch p = eq * table[j].slice(r, r + 1).broadcast(m);
+            if (r == 0)
+                out.push_back(p);
+            else
+                out[j] = out[j] + p;
+        }
+    }
+    return out;
+}
+
+} // namespace
+
+UIntBatch readAt(const UIntBatch &table, const UIntBatch &index)
+{
+    std::vector<CiphertextBatch> planes;
+    for (unsigned j = 0; j < table.width(); ++j)
+        planes.push_back(table.plane(j));
+    return UIntBatch::fromPlanes(readPlanes(planes, index));
+}
+
+CiphertextBatch readAt(const CiphertextBatch &table, const UIntBatch &index)
+{
+    return readPlanes(std::vector<CiphertextBatch>(1, table), index)[0];
+}
+
+} // namespace certFHE

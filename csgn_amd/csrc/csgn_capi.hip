@@ -1327,6 +1327,58 @@ int csgn_gather_planes(uint64_t n_bits, uint64_t n_planes, const uint64_t *const
     return CSGN_OK;
 }
 
+/* ------------------------------------------- encrypted tables at encrypted indices ---- */
+
+uint64_t csgn_uint_read_terms(uint64_t index_width, const uint64_t *h_index_terms, uint64_t rows)
+{
+    return csgn::uint_read_terms(index_width, (const u64 *)h_index_terms, rows);
+}
+
+const char *csgn_uint_read_kernel(uint64_t n_bits, uint64_t batch, uint64_t index_width, const uint64_t *h_index_terms,
+                                  uint64_t rows, uint64_t width, const uint64_t *h_table_terms)
+{
+    return csgn::uint_read_kernel_name(n_bits, batch, index_width, (const u64 *)h_index_terms, rows, width,
+                                       (const u64 *)h_table_terms);
+}
+
+int csgn_uint_read(uint64_t n_bits, uint64_t batch, uint64_t index_width, const uint64_t *const *h_index,
+                   const uint64_t *h_index_terms, uint64_t rows, uint64_t width, const uint64_t *const *h_table,
+                   const uint64_t *h_table_terms, uint64_t *const *h_out, void *stream)
+{
+    if (int rc = check_n(n_bits))
+        return rc;
+    REQUIRE(index_width >= 1 && index_width <= csgn::kReadMaxIndex, "read: index width %llu outside 1..16",
+            (unsigned long long)index_width);
+    REQUIRE(width >= 1 && width <= csgn::kReadMaxPlanes, "read: table width %llu outside 1..64",
+            (unsigned long long)width);
+    REQUIRE(rows >= 1 && rows <= (1ull << index_width), "read: %llu rows outside 1..2^%llu", (unsigned long long)rows,
+            (unsigned long long)index_width);
+    REQUIRE(h_index && h_index_terms && h_table && h_table_terms && h_out, "null host pointer");
+    const uint64_t E = csgn::uint_read_terms(index_width, (const u64 *)h_index_terms, rows);
+    REQUIRE(E != 0, "read: an index plane has no terms, or the term count overflows");
+    const uint64_t dl = csgn_default_len(n_bits);
+    for (uint64_t j = 0; j < width; ++j) {
+        REQUIRE(h_table_terms[j] != 0, "read: table plane %llu has no terms", (unsigned long long)j);
+        if (!product_below(h_table_terms[j], E, dl, 1ull << 31))
+            return fail(CSGN_ERR_UNSUPPORTED, "read: output %llu has %llu x %llu terms per element, past 2^31 words",
+                        (unsigned long long)j, (unsigned long long)h_table_terms[j], (unsigned long long)E);
+        if (!product_below(batch, h_table_terms[j] * E, dl, 1ull << 60))
+            return fail(CSGN_ERR_UNSUPPORTED, "batch of %llu elements: size overflows", (unsigned long long)batch);
+    }
+    if (int rc = require_device("csgn_uint_read"))
+        return rc;
+    if (batch == 0)
+        return CSGN_OK;
+    for (uint64_t k = 0; k < index_width; ++k)
+        REQUIRE(h_index[k], "null device pointer (index plane %llu)", (unsigned long long)k);
+    for (uint64_t j = 0; j < width; ++j)
+        REQUIRE(h_table[j] && h_out[j], "null device pointer (table plane or output %llu)", (unsigned long long)j);
+    HIP_TRY(csgn::uint_read(n_bits, batch, index_width, (const u64 *const *)h_index, (const u64 *)h_index_terms, rows,
+                            width, (const u64 *const *)h_table, (const u64 *)h_table_terms, (u64 *const *)h_out,
+                            S(stream)));
+    return CSGN_OK;
+}
+
 /* ------------------------------------------------------------------ tuning ---- */
 
 int csgn_set_tuning(const char *key, int value)

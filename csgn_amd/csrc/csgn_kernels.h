@@ -180,6 +180,15 @@ hipError_t gather_planes(u64 n_bits, u64 n_planes, const u64 *const *src, const 
 hipError_t gather_ragged(u64 n_bits, u64 count_in, const u64 *src, const u64 *src_off, u64 count_out, const u64 *idx,
                          u64 *dst, const u64 *out_off, u64 total_terms_out, hipStream_t s);
 
+// an encrypted table read at an encrypted index (csgn_uint_read.hip), include/csgn_hip.h's definition: output j is the
+// sum, ascending in r < rows, of EQ(x, r) * d_{r,j}.  index planes: v = 1..16, terms s[k]; table planes: w = 1..64,
+// terms t[j].
+constexpr u32 kReadMaxIndex = 16, kReadMaxPlanes = 64;
+u64 uint_read_terms(u64 v, const u64 *s, u64 rows);   // E; 0: invalid argument or a count of 2^62 or more
+const char *uint_read_kernel_name(u64 n_bits, u64 batch, u64 v, const u64 *s, u64 rows, u64 w, const u64 *t);
+hipError_t uint_read(u64 n_bits, u64 batch, u64 v, const u64 *const *index, const u64 *s, u64 rows, u64 w,
+                     const u64 *const *table, const u64 *t, u64 *const *out, hipStream_t stream);
+
 hipError_t small_ops(u64 n_bits, u64 count, const ::csgn_small_op *ops, hipStream_t s);
 size_t decrypt_scratch_bytes(u64 batch, u64 total_terms);
 // out[i] = a[i] & b[i] (is_product) or a[i] ^ b[i]: Dec(a*b) = Dec(a) & Dec(b), Dec(a+b) = Dec(a) ^ Dec(b)

@@ -52,6 +52,7 @@ enum TuneKey {
     TUNE_UINT_FUSED,     // integer steps (csgn_uint.hip): -1 = per shape, 0 = pitched form where the step has one, 1 = fused kernel
     TUNE_UINT_PLAIN_FUSED, // comparisons with a public constant (csgn_uint_plain.hip): -1 = per shape, 0 = composed form (the tuned launchers level by level), 1 = fused kernel
     TUNE_UINT_LUT_FUSED, // public lookup tables (csgn_uint_lut.hip): -1 = per shape, 0 = composed form (the tuned launchers monomial by monomial), 1 = fused kernel
+    TUNE_UINT_READ_FUSED, // encrypted tables read at encrypted indices (csgn_uint_read.hip): -1 = per shape, 0 = composed form (the tuned launchers row by row), 1 = fused kernel
     TUNE_COUNT
 };
 

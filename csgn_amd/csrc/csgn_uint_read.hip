@@ -1,0 +1,429 @@
+// csgn_uint_read.hip -- an ENCRYPTED table read at an ENCRYPTED index, every output plane in one launch.
+// Hand-written CDNA4 (gfx950) HIP; shared helpers in csgn_device.h, design notes in DESIGN.md §4.17.
+//
+// The definition (include/csgn_hip.h, csgn_uint_read) is out_j = sum over r < rows, ascending, of EQ(x, r) * d_{r,j}:
+// csgn_uint_plain's EQ row with k = r as the left operand, plane j of table element r as the right.  Term q * t_j + c of
+// output j is (term q of the E stream) & (term c of d_{r,j}), where the E stream is the concatenation, ascending in r,
+// of the EQ rows.  Nothing of it is tabulated: q is decoded by
+//     the walk    from the top index bit down: below a fixed prefix of high bits a whole subtree holds
+//                 prod (2 s_k + 1) terms over its free bits, times the R_k of the bits already fixed, so each step
+//                 either skips the bit-0 subtree (bit 1) or enters it; while the prefix equals that of rows - 1 and
+//                 that bit is 0 there is only the bit-0 subtree
+//     the digits  inside row r's block: mixed radix over R_k = r_k ? s_k : s_k + 1 with k = 0 slowest; digit s_k (a
+//                 zero bit only) selects ONE, any other digit that term of x_k
+//
+// Fresh index planes (every s_k = 1), the case this kernel is built for: a term of the E stream is P[S], the AND of x_k
+// over S = ones(r) + the zero bits whose digit is 0.  A workgroup owns G elements, a slice of KC units of every term,
+// and one range of the E stream, for EVERY output plane: it builds the subset tables of §4.15 (one to three, the AND of
+// every subset of their planes) for its elements in LDS, decodes its range once into an LDS list of (S, r), and every
+// written unit is then 1-3 LDS reads ANDed with one unit of the table row -- a row every element reads, so it hits in
+// L2.  The table build and the decode are spent on all `w` outputs.  Lanes walk one output's stream with the unit
+// fastest, then the table term, the E index and the element, so one store instruction writes 64 consecutive units of
+// one plane.  Multi-term index planes take the walk and the digits per unit straight from the planes (correct, not
+// fast).
+#include "csgn_device.h"
+#include "csgn_hip.h"
+
+#include <algorithm>
+
+namespace csgn {
+
+namespace {
+
+constexpr u32 kMaxTables = 3;
+constexpr u64 kLdsBudget = 32768;       // bytes of subset tables per workgroup
+constexpr u32 kMaxRange = 2048;         // E-stream entries one workgroup decodes (8 KB of LDS)
+constexpr u64 kPartUnits = 8192;        // units a workgroup writes at least, where the shape has them
+constexpr u64 kTermLimit = 1ull << 62;
+
+__device__ inline unit16 read_one(unit16, u32 k, u32 U, u64 last_mask)
+{
+    unit16 v = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
+    if (k == U - 1u) {
+        v.z = (u32)last_mask;
+        v.w = (u32)(last_mask >> 32);
+    }
+    return v;
+}
+__device__ inline unit8 read_one(unit8, u32 k, u32 U, u64 last_mask) { return k == U - 1u ? last_mask : ~0ull; }
+
+// By value in the kernel arguments (uniform, scalar loads).  A workgroup is (element group, unit chunk, part): it owns
+// elements [group * G, + G), units [chunk * KC, + KC) of every term and entries [part * QP, + QP) of the E stream.
+struct ReadArgs {
+    const void *index[kReadMaxIndex];
+    const void *table[kReadMaxPlanes];
+    void *out[kReadMaxPlanes];
+    u32 t[kReadMaxPlanes];                                              // terms of table plane j
+    u32 tk_d[kReadMaxPlanes], tk_magic[kReadMaxPlanes], tk_shift[kReadMaxPlanes];   // t_j * KC as a FastDiv
+    u64 F[kReadMaxIndex];       // prod over i < k of (2 s_i + 1): a whole subtree below bit k (saturated; read only
+                                // where the subtree lies below rows, so at most E)
+    u32 s[kReadMaxIndex];
+    u64 last_mask;
+    u64 batch;                  // elements of this launch
+    u32 E, last_row, v, w;
+    u32 U, KC, G, QP, chunks, parts, nblocks, xcd;
+    u32 ntab, hb[kMaxTables + 1], tbase[kMaxTables];   // table k: planes [hb[k], hb[k+1]), at unit tbase[k] of the LDS
+    u32 lbase;                                         // byte offset of the decoded range in the LDS
+    FastDiv dKC, dQP;
+};
+
+// q < E: the row r holding entry q of the E stream, and q's index inside r's block (the walk)
+__device__ inline u32 read_walk(const ReadArgs &a, u64 q, u64 &in)
+{
+    u32 r = 0;
+    u64 H = 1;                  // prod of R_k over the bits fixed so far
+    bool tight = true;          // the prefix equals that of rows - 1
+    for (u32 k = a.v; k-- > 0u;) {
+        const u64 s = a.s[k];
+        if (tight && !((a.last_row >> k) & 1u)) {
+            H *= s + 1u;
+            continue;
+        }
+        const u64 c0 = H * (s + 1u) * a.F[k];
+        if (q < c0) {
+            H *= s + 1u;
+            tight = false;
+        } else {
+            q -= c0;
+            r |= 1u << k;
+            H *= s;
+        }
+    }
+    in = q;
+    return r;
+}
+
+template <typename Unit, bool Fresh>
+__global__ void __launch_bounds__(256) k_uint_read(ReadArgs a)
+{
+    extern __shared__ __align__(16) unsigned char smem_raw[];
+    Unit *tab = reinterpret_cast<Unit *>(smem_raw);
+    u32 *code = reinterpret_cast<u32 *>(smem_raw + a.lbase);
+    const u32 bid = a.xcd ? xcd_contiguous_block(blockIdx.x, a.nblocks) : blockIdx.x;
+    const u32 gc = bid / a.parts, part = bid - gc * a.parts;
+    const u32 group = gc / a.chunks, chunk = gc - group * a.chunks;
+    const u64 e0 = (u64)group * a.G;
+    const u32 ne = (u32)min((u64)a.G, a.batch - e0);
+    const u32 k0 = chunk * a.KC, kc = min(a.KC, a.U - k0);
+    const u32 q0 = part * a.QP, nq = min(a.QP, a.E - q0);
+
+    if (Fresh) {
+        // entry 0 of every table is ONE; level b fills entries [2^b, 2^(b+1)) from [0, 2^b) and plane hb[k] + b
+        for (u32 tb = 0; tb < a.ntab; ++tb) {
+            const u32 h = a.hb[tb + 1] - a.hb[tb];
+            for (u32 x = threadIdx.x; x < a.G * a.KC; x += 256u) {
+                const u32 el = csgn_fastdiv(x, a.dKC), kk = x - el * a.KC;
+                tab[a.tbase[tb] + ((el << h) * a.KC) + kk] = read_one(Unit(), k0 + kk, a.U, a.last_mask);
+            }
+        }
+        // the range of the E stream: S in the low 16 bits, r in the high 16
+        for (u32 i = threadIdx.x; i < nq; i += 256u) {
+            u64 in;
+            const u32 r = read_walk(a, q0 + i, in);
+            u32 S = r;
+            for (u32 k = a.v; k-- > 0u;) {      // zero bits, the highest the fastest binary digit; digit 0 = x_k
+                if ((r >> k) & 1u)
+                    continue;
+                if (!(in & 1u))
+                    S |= 1u << k;
+                in >>= 1;
+            }
+            code[i] = S | (r << 16);
+        }
+        for (u32 b = 0; b < a.hb[1]; ++b) {     // table 0 is the widest
+            __syncthreads();
+            for (u32 tb = 0; tb < a.ntab; ++tb) {
+                const u32 h = a.hb[tb + 1] - a.hb[tb];
+                if (b >= h)
+                    continue;
+                const Unit *p = reinterpret_cast<const Unit *>(a.index[a.hb[tb] + b]);
+                const u32 n = (a.G * a.KC) << b;
+                for (u32 x = threadIdx.x; x < n; x += 256u) {
+                    const u32 row = csgn_fastdiv(x, a.dKC), kk = x - row * a.KC;
+                    const u32 el = row >> b, s = (1u << b) | (row & ((1u << b) - 1u));
+                    if (el >= ne || kk >= kc)
+                        continue;
+                    const u32 at = a.tbase[tb] + ((el << h) | s) * a.KC + kk;
+                    tab[at] = tab[at - (1u << b) * a.KC] & p[(e0 + el) * a.U + k0 + kk];
+                }
+            }
+        }
+        __syncthreads();
+    }
+
+    for (u32 j = 0; j < a.w; ++j) {
+        const FastDiv dtk = {a.tk_d[j], a.tk_magic[j], a.tk_shift[j]};
+        const u32 tj = a.t[j];
+        const u64 Tj = (u64)tj * a.E;
+        const Unit *d = reinterpret_cast<const Unit *>(a.table[j]);
+        Unit *o = reinterpret_cast<Unit *>(a.out[j]);
+        const u32 len = ne * a.QP * dtk.d;      // (element, E entry, table term, unit), below 2^32 by the plan
+        for (u32 l = threadIdx.x; l < len; l += 256u) {
+            const u32 eq = csgn_fastdiv(l, dtk), rem = l - eq * dtk.d;
+            const u32 c = csgn_fastdiv(rem, a.dKC), kk = rem - c * a.KC;
+            const u32 el = csgn_fastdiv(eq, a.dQP), qi = eq - el * a.QP;
+            if (qi >= nq || kk >= kc)
+                continue;
+            const u32 k = k0 + kk;
+            const u64 e = e0 + el, q = (u64)q0 + qi;
+            Unit v;
+            u32 r;
+            if (Fresh) {
+                const u32 cd = code[qi], S = cd & 0xFFFFu;
+                r = cd >> 16;
+                v = tab[a.tbase[0] + ((el << a.hb[1]) | (S & ((1u << a.hb[1]) - 1u))) * a.KC + kk];
+                for (u32 tb = 1; tb < a.ntab; ++tb) {
+                    const u32 h = a.hb[tb + 1] - a.hb[tb];
+                    v &= tab[a.tbase[tb] + ((el << h) | ((S >> a.hb[tb]) & ((1u << h) - 1u))) * a.KC + kk];
+                }
+            } else {
+                u64 in;
+                r = read_walk(a, q, in);
+                v = read_one(Unit(), k, a.U, a.last_mask);
+                for (u32 kb = a.v; kb-- > 0u;) {
+                    const u64 s = a.s[kb], R = ((r >> kb) & 1u) ? s : s + 1u;
+                    const u64 dg = in % R;
+                    in /= R;
+                    if (dg < s)
+                        v &= reinterpret_cast<const Unit *>(a.index[kb])[(e * s + dg) * a.U + k];
+                }
+            }
+            v &= d[((u64)r * tj + c) * a.U + k];
+            unit_store<Unit, true>(o + ((e * Tj) + q * tj + c) * a.U + k, v);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------ host side
+
+u64 sat_mul(u64 x, u64 y)
+{
+    unsigned long long p;
+    return __builtin_mul_overflow((unsigned long long)x, (unsigned long long)y, &p) || p >= kTermLimit ? kTermLimit
+                                                                                                       : (u64)p;
+}
+
+bool read_shape_ok(u64 v, const u64 *s, u64 rows, u64 w, const u64 *t)
+{
+    if (w < 1 || w > kReadMaxPlanes || !t || uint_read_terms(v, s, rows) == 0)
+        return false;
+    for (u64 j = 0; j < w; ++j)
+        if (t[j] == 0 || t[j] >= kTermLimit)
+            return false;
+    return true;
+}
+
+bool read_use_fused()
+{
+    const int forced = tune(TUNE_UINT_READ_FUSED);
+    if (forced == 0 || forced == 1)
+        return forced == 1;
+    return true;              // one launch for every output: no shape measured where the composed form is faster
+}
+
+template <typename Unit>
+hipError_t read_fused(u64 n_bits, u64 batch, u64 v, const u64 *const *index, const u64 *s, u64 rows, u64 w,
+                      const u64 *const *table, const u64 *t, u64 *const *out, u64 E, u32 U, hipStream_t st)
+{
+    ReadArgs a = {};
+    a.v = (u32)v;
+    a.w = (u32)w;
+    a.U = U;
+    a.E = (u32)E;
+    a.last_row = (u32)(rows - 1);
+    a.last_mask = last_word_mask(n_bits);
+    bool fresh = true;
+    u64 f = 1;
+    for (u32 k = 0; k < v; ++k) {
+        a.s[k] = (u32)s[k];
+        a.F[k] = f;
+        f = sat_mul(f, 2 * s[k] + 1);
+        fresh = fresh && s[k] == 1;
+    }
+    u64 sumt = 0, maxt = 0;
+    for (u32 j = 0; j < w; ++j) {
+        a.t[j] = (u32)t[j];
+        sumt += t[j];
+        maxt = std::max(maxt, t[j]);
+    }
+    // subset tables: one up to 5 planes, two up to 10, three above; the low tables take the odd planes
+    u64 entries = 0;          // table units per element and unit of a term
+    if (fresh) {
+        a.ntab = v <= 5 ? 1 : v <= 10 ? 2 : 3;
+        a.hb[0] = 0;
+        for (u32 k = 0; k < a.ntab; ++k) {
+            const u32 h = ((u32)v - a.hb[k] + (a.ntab - k) - 1) / (a.ntab - k);
+            a.hb[k + 1] = a.hb[k] + h;
+            entries += 1ull << h;
+        }
+    }
+    // unit chunks: only when one element's tables at whole terms pass the budget
+    const u64 per_unit = entries * sizeof(Unit);
+    u32 chunks = 1;
+    if (fresh && per_unit * U > kLdsBudget)
+        chunks = (u32)((per_unit * U + kLdsBudget - 1) / kLdsBudget);
+    a.KC = (U + chunks - 1) / chunks;
+    a.chunks = (U + a.KC - 1) / a.KC;
+    // elements per workgroup: enough to give it kPartUnits to write, as many as the tables allow
+    const u64 elem_units = E * sumt * a.KC;
+    u64 G = std::max<u64>(1, kPartUnits / elem_units);
+    if (fresh)
+        G = std::min<u64>(G, std::max<u64>(1, kLdsBudget / (per_unit * a.KC)));
+    G = std::min<u64>({G, batch, 64});
+    G = std::max<u64>(G, 1);
+    // parts of the E stream: each writes kPartUnits or four times its table build, and decodes at most kMaxRange
+    const u64 build = G * entries * a.KC;
+    const u64 target = std::max<u64>(kPartUnits, 4 * build);
+    u64 parts = std::max<u64>(1, G * elem_units / target);
+    parts = std::max<u64>(parts, (E + kMaxRange - 1) / kMaxRange);
+    parts = std::min<u64>(parts, E);
+    const u64 QP = (E + parts - 1) / parts;
+    a.QP = (u32)QP;
+    a.parts = (u32)((E + QP - 1) / QP);
+    // one output's stream of a workgroup, G * QP * t_j * KC, stays below 2^32 (QP * t_j * KC <= T_j * U < 2^31)
+    G = std::min<u64>(G, 0xFFFFFFFFull / (QP * maxt * a.KC));
+    a.G = (u32)std::max<u64>(G, 1);
+    a.dKC = csgn_fastdiv_make(a.KC);
+    a.dQP = csgn_fastdiv_make(a.QP);
+    for (u32 j = 0; j < w; ++j) {
+        const FastDiv d = csgn_fastdiv_make((u32)(t[j] * a.KC));
+        a.tk_d[j] = d.d;
+        a.tk_magic[j] = d.magic;
+        a.tk_shift[j] = d.shift;
+    }
+    u32 lds = 0;
+    if (fresh) {
+        u32 at = 0;
+        for (u32 k = 0; k < a.ntab; ++k) {
+            a.tbase[k] = at;
+            at += (u32)((a.G << (a.hb[k + 1] - a.hb[k])) * a.KC);
+        }
+        a.lbase = (at * (u32)sizeof(Unit) + 15u) & ~15u;
+        lds = a.lbase + a.QP * 4u;
+    }
+    const u64 per_group = (u64)a.chunks * a.parts;
+    const u64 max_groups = std::max<u64>(1, kMaxBlocks256 / per_group);
+    const u64 groups = (batch + a.G - 1) / a.G;
+    a.xcd = stream_xcd(batch * E * sumt * U);
+    for (u64 g0 = 0; g0 < groups; g0 += max_groups) {
+        const u64 ng = std::min(max_groups, groups - g0), e0 = g0 * a.G;
+        a.batch = std::min<u64>(batch - e0, ng * a.G);
+        for (u32 k = 0; k < v; ++k)
+            a.index[k] = reinterpret_cast<const Unit *>(index[k]) + e0 * s[k] * U;
+        for (u32 j = 0; j < w; ++j) {
+            a.table[j] = table[j];
+            a.out[j] = reinterpret_cast<Unit *>(out[j]) + e0 * t[j] * E * U;
+        }
+        a.nblocks = (u32)(ng * per_group);
+        if (fresh)
+            k_uint_read<Unit, true><<<dim3(a.nblocks), 256, lds, st>>>(a);
+        else
+            k_uint_read<Unit, false><<<dim3(a.nblocks), 256, 0, st>>>(a);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess)
+            return e;
+    }
+    return hipSuccess;
+}
+
+// The composed form, row by row through the tuned launchers: EQ(x, r) by csgn_uint_plain into a temporary, row r of
+// every table plane broadcast to the batch by one csgn_gather_planes (tile form), then csgn_mul_uniform of the two into
+// r's slice of every output (pitch T_j).  The temporaries live in one stream-ordered block (hipMallocAsync).
+hipError_t read_composed(u64 n_bits, u64 batch, u64 v, const u64 *const *index, const u64 *s, u64 rows, u64 w,
+                         const u64 *const *table, const u64 *t, u64 *const *out, u64 E, hipStream_t st)
+{
+    const u64 dL = (n_bits + 63) / 64;
+    u64 max_eq = 1, sumt = 0;           // row 0 has the most EQ terms: every R_k = s_k + 1
+    for (u64 k = 0; k < v; ++k)
+        max_eq *= s[k] + 1;
+    for (u64 j = 0; j < w; ++j)
+        sumt += t[j];
+    u64 *block = nullptr;
+    hipError_t e = hipMallocAsync(reinterpret_cast<void **>(&block), batch * (max_eq + sumt) * dL * 8, st);
+    if (e != hipSuccess)
+        return e;
+    u64 *eq = block;
+    const u64 *src[kReadMaxPlanes];
+    u64 *row[kReadMaxPlanes];
+    u64 at = batch * max_eq * dL;
+    for (u64 j = 0; j < w; ++j) {
+        row[j] = block + at;
+        at += batch * t[j] * dL;
+    }
+    u64 off = 0;                        // r's first entry of the E stream
+    for (u64 r = 0; r < rows && e == hipSuccess; ++r) {
+        const u64 er = uint_plain_terms(CSGN_UINT_PLAIN_EQ, v, r, s);
+        e = uint_plain(n_bits, CSGN_UINT_PLAIN_EQ, batch, v, r, index, s, eq, st);
+        for (u64 j = 0; j < w; ++j)
+            src[j] = table[j] + r * t[j] * dL;
+        if (e == hipSuccess)
+            e = gather_planes(n_bits, w, src, t, 1, batch, nullptr, row, st);
+        for (u64 j = 0; j < w && e == hipSuccess; ++j)
+            e = mul_uniform(n_bits, batch, er, t[j], eq, row[j], out[j] + off * t[j] * dL, 0, st, t[j] * E * dL);
+        off += er;
+    }
+    const hipError_t f = hipFreeAsync(block, st);
+    return e == hipSuccess ? f : e;
+}
+
+} // namespace
+
+// ------------------------------------------------------------------------------ public
+
+u64 uint_read_terms(u64 v, const u64 *s, u64 rows)
+{
+    if (v < 1 || v > kReadMaxIndex || !s || rows < 1 || rows > (1ull << v))
+        return 0;
+    for (u64 k = 0; k < v; ++k)
+        if (s[k] == 0 || s[k] >= kTermLimit)
+            return 0;
+    // the walk along rows - 1: every bit-0 subtree left of the path is whole, then the row rows - 1 itself
+    const u64 last = rows - 1;
+    u64 F[kReadMaxIndex], f = 1;
+    for (u64 k = 0; k < v; ++k) {
+        F[k] = f;
+        f = sat_mul(f, 2 * s[k] + 1);
+    }
+    u64 E = 0, H = 1;
+    for (u64 k = v; k-- > 0;) {
+        if ((last >> k) & 1u) {
+            E += sat_mul(sat_mul(H, s[k] + 1), F[k]);
+            H = sat_mul(H, s[k]);
+        } else {
+            H = sat_mul(H, s[k] + 1);
+        }
+        if (E >= kTermLimit)
+            return 0;
+    }
+    E += H;
+    return E >= kTermLimit ? 0 : E;
+}
+
+const char *uint_read_kernel_name(u64 n_bits, u64 batch, u64 v, const u64 *s, u64 rows, u64 w, const u64 *t)
+{
+    (void)batch;
+    if (n_bits == 0 || !read_shape_ok(v, s, rows, w, t))
+        return "";
+    return read_use_fused() ? "k_uint_read" : "composed";
+}
+
+hipError_t uint_read(u64 n_bits, u64 batch, u64 v, const u64 *const *index, const u64 *s, u64 rows, u64 w,
+                     const u64 *const *table, const u64 *t, u64 *const *out, hipStream_t stream)
+{
+    if (batch == 0)
+        return hipSuccess;
+    const u64 E = uint_read_terms(v, s, rows);
+    if (!read_use_fused())
+        return read_composed(n_bits, batch, v, index, s, rows, w, table, t, out, E, stream);
+    const u64 dL = (n_bits + 63) / 64;
+    bool wide = dL % 2 == 0;
+    for (u64 k = 0; k < v && wide; ++k)
+        wide = aligned16(index[k]);
+    for (u64 j = 0; j < w && wide; ++j)
+        wide = aligned16(table[j]) && aligned16(out[j]);
+    const u32 U = (u32)(wide ? dL / 2 : dL);
+    return wide ? read_fused<unit16>(n_bits, batch, v, index, s, rows, w, table, t, out, E, U, stream)
+                : read_fused<unit8>(n_bits, batch, v, index, s, rows, w, table, t, out, E, U, stream);
+}
+
+} // namespace csgn

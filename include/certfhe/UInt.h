@@ -40,6 +40,17 @@
 // planes are composed from the CiphertextBatch operators with the same words.  Every output's size is checked before
 // anything is allocated; past 2^31 words per element std::invalid_argument is thrown.
 //
+// ENCRYPTED TABLES AT ENCRYPTED INDICES: readAt(table, index) reads a table of n = table.size() encrypted rows
+// (1 <= n <= 2^v, v = index.width() <= 16) at every element's encrypted index.  Output plane j is the left-nested sum,
+// ascending in r < n, of equalTo(index, r) * (plane j of row r, broadcast): the EQ row of csgn_uint_plain with k = r as
+// the LEFT operand, csgn_uint_read's words (include/csgn_hip.h).  It decrypts to table[x] where x < n and to 0 in every
+// plane where x >= n.  Plane j of the result has t_j * E terms, E = sum over r < n of prod_k (r_k ? s_k : s_k + 1) for
+// index planes of s_k terms: 3^v with fresh planes and a full table -- 6561 at v = 8, about 1 MB per output plane and
+// element at N=1247 -- the same growth as an equality.  Uniform planes take one csgn_uint_read (one launch for every
+// output plane); ragged planes are composed from the CiphertextBatch operators, equalTo(index, r) and broadcast, with
+// the same words.  Every size is checked before anything is allocated: std::invalid_argument for a mismatched context,
+// a table of 0 or more than 2^v rows, or an output plane past 2^31 words per element.
+//
 // Uniform planes run one csgn_uint_step (or csgn_gate_uniform) call per bit; ragged ones (what compact() may return)
 // are composed from the CiphertextBatch operators and Gates.h, with the same words.  Only the running carry or
 // accumulator is kept alive between bits.
@@ -130,6 +141,10 @@ class LookupTable {
 UIntBatch lookup(const UIntBatch &a, const LookupTable &f);
 // f(a + (b << a.width())), a.width() + b.width() == f.inWidth(); one context and element count
 UIntBatch lookup(const UIntBatch &a, const UIntBatch &b, const LookupTable &f);
+
+// element e: table[index[e]] where index[e] < table.size(), else 0; one output plane per table plane
+UIntBatch readAt(const UIntBatch &table, const UIntBatch &index);
+CiphertextBatch readAt(const CiphertextBatch &table, const UIntBatch &index);
 
 } // namespace certFHE
 

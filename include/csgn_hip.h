@@ -743,6 +743,43 @@ int csgn_gather_planes(uint64_t n_bits, uint64_t n_planes, const uint64_t *const
  * (n_bits == 0, n_planes outside 1..64, or a ragged plane table). */
 const char *csgn_gather_kernel(uint64_t n_bits, uint64_t count_out, int ragged, uint64_t n_planes);
 
+/* ------------------------------------------- encrypted tables at encrypted indices ---- */
+
+/* An ENCRYPTED table read at an ENCRYPTED index.  Index: index_width = v planes x_0..x_{v-1} (bit 0 first, v in 1..16)
+ * of `batch` elements, plane k uniform with s_k terms per element.  Table: `width` planes d_0..d_{width-1} (1..64) of
+ * `rows` elements (1 <= rows <= 2^v), plane j uniform with t_j terms per element.  Output: `width` planes of `batch`
+ * elements.  A fixed composition of the reference's operator+ / operator* with ONE:
+ *     out_j = ((EQ(x, 0) * d_{0,j}) + (EQ(x, 1) * d_{1,j})) + ... + (EQ(x, rows-1) * d_{rows-1,j})   (left-nested)
+ *     EQ(x, r)   the EQ row of csgn_uint_plain with k = r over element e's planes:  g_k = r_k ? x_k : (x_k + ONE),
+ *                EQ = ((g_0 * g_1) * ...) * g_{v-1}
+ *     d_{r,j}    plane j of table element r, the same for every e;  EQ is the LEFT operand of every product
+ * Decrypts to table[x] when x < rows, and to 0 in every plane when x >= rows.
+ * Terms of output j: T_j = t_j * E,  E = sum over r < rows of prod_k R_k(r),  R_k(r) = r_k ? s_k : s_k + 1;
+ * rows = 2^v: E = prod_k (2 s_k + 1).  Fresh 1-term index planes: E = 3^v (6561 at v = 8: about 1 MB per output plane
+ * and element at N=1247) -- the scheme's own growth, as for csgn_uint_step's comparisons.
+ * Term order (decoding needs no table): row r's terms form a block of t_j * prod_k R_k(r) terms, blocks ascending in r;
+ * inside a block term (q, c) is at q * t_j + c, c the table term (fastest), and q's mixed-radix digits d_k < R_k run
+ * with k = 0 slowest; d_k selects term d_k of x_k, and d_k = s_k (only for r_k = 0) selects ONE. */
+/* E (host only); 0 for index_width outside 1..16, rows outside 1..2^index_width, a null pointer, an index plane of 0
+ * terms or a count of 2^62 or more. */
+uint64_t csgn_uint_read_terms(uint64_t index_width, const uint64_t *h_index_terms, uint64_t rows);
+/* Which form a csgn_uint_read call of this shape takes (host only, a static string): "k_uint_read" (one kernel writes
+ * every output plane, planes read in place, ONE made in registers) or "composed" (per row r: csgn_uint_plain's EQ into
+ * a stream-ordered temporary, the broadcast of row r by csgn_gather_planes' tile form, csgn_mul_uniform into r's slice
+ * of every output).  Knob "uint_read_fused" (-1 per shape, 0 / 1 forced) decides; the words are the same.  Per shape:
+ * fused.  "" for an invalid shape (n_bits 0, a bad width, rows or term count). */
+const char *csgn_uint_read_kernel(uint64_t n_bits, uint64_t batch, uint64_t index_width, const uint64_t *h_index_terms,
+                                  uint64_t rows, uint64_t width, const uint64_t *h_table_terms);
+/* The read over `batch` elements.  h_index: a HOST array of index_width device pointers (plane k: batch * s_k * dL
+ * words), h_table: a HOST array of `width` device pointers (plane j: rows * t_j * dL words), h_out: a HOST array of
+ * `width` device pointers (output j: batch * T_j * dL words).  Planes may alias one another; no output overlaps an input
+ * or another output.  Limits: every T_j * dL below 2^31 words per element (CSGN_ERR_UNSUPPORTED), batch * that < 2^60.
+ * On the caller's stream, asynchronous; the fused form is one launch and graph-capturable.  No GPU:
+ * CSGN_ERR_NO_DEVICE, no CPU fallback. */
+int csgn_uint_read(uint64_t n_bits, uint64_t batch, uint64_t index_width, const uint64_t *const *h_index,
+                   const uint64_t *h_index_terms, uint64_t rows, uint64_t width, const uint64_t *const *h_table,
+                   const uint64_t *h_table_terms, uint64_t *const *h_out, void *stream);
+
 /* ------------------------------------------------------------------- tuning ---- */
 
 /* Kernel-choice and sweep knobs ("mul_flat", "mul_touch", "ragged_c", "perm_ballot", ...;
