@@ -1,7 +1,10 @@
-// csgn_device.h -- helpers shared by the kernel translation units (csgn_mul.hip, csgn_add.hip,
-// csgn_decrypt.hip, csgn_encrypt.hip, csgn_permute.hip, csgn_compact.hip, csgn_harness.hip):
-// 16-/8-byte unit access, the XCD-contiguous block order, CSR pair search, launch limits and the
-// knob-dependent launch choices (csgn_tuning.h).  Everything has internal linkage (one copy per translation unit).
+// csgn_device.h -- helpers shared by the kernel translation units (csgn_mul.hip, csgn_add.hip, csgn_decrypt.hip,
+// csgn_encrypt.hip, csgn_permute.hip, csgn_compact.hip, csgn_harness.hip, and the uniform-batch families
+// csgn_gates.hip, csgn_uint.hip, csgn_uint_plain.hip, csgn_uint_lut.hip, csgn_uint_read.hip, csgn_gather.hip):
+// 16-/8-byte unit access and the choice between them, the ONE and ZERO terms' units, FastDiv tables in kernel
+// arguments, the XCD-contiguous block order, CSR pair search, the LDS subset tables of DESIGN §4.15, launch limits,
+// the term-count limit and the knob-dependent launch choices (csgn_tuning.h).  Everything has internal linkage (one
+// copy per translation unit).
 //
 // Common shape of the data path: lanes own consecutive 16-byte units so every wave-level
 // load/store is one global_{load,store}_dwordx4 covering 1 KiB of contiguous, 128-B-aligned
@@ -12,6 +15,8 @@
 
 #include "csgn_kernels.h"
 #include "csgn_tuning.h"
+
+#include <algorithm>
 
 namespace csgn {
 
@@ -35,6 +40,37 @@ __device__ inline bool unit_covers(unit16 x, unit16 m)
     return (d.x | d.y | d.z | d.w) == 0u;
 }
 __device__ inline bool unit_covers(unit8 x, unit8 m) { return (x & m) == m; }
+
+// the ONE term's unit k of U: every bit set except the unused low bits of the term's last word (last_mask:
+// last_word_mask), which stay zero as in every canonical term.  It decrypts to 1 under every key, ZERO to 0.
+__device__ inline unit16 one_unit(unit16, u32 k, u32 U, u64 last_mask)
+{
+    unit16 v = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
+    if (k == U - 1u) {
+        v.z = (u32)last_mask;
+        v.w = (u32)(last_mask >> 32);
+    }
+    return v;
+}
+__device__ inline unit8 one_unit(unit8, u32 k, u32 U, u64 last_mask) { return k == U - 1u ? last_mask : ~0ull; }
+__device__ inline unit16 zero_unit(unit16) { return unit16{0u, 0u, 0u, 0u}; }
+__device__ inline unit8 zero_unit(unit8) { return 0ull; }
+
+// N divisors of a kernel's arguments as three parallel u32 arrays (d, magic, shift), the layout the scalar loads of a
+// uniform index read: set on the host, at() on the device.
+template <u32 N>
+struct FastDivTable {
+    u32 d[N], magic[N], shift[N];
+
+    void set(u32 i, u32 divisor)
+    {
+        const FastDiv f = csgn_fastdiv_make(divisor);
+        d[i] = f.d;
+        magic[i] = f.magic;
+        shift[i] = f.shift;
+    }
+    __device__ FastDiv at(u32 i) const { return FastDiv{d[i], magic[i], shift[i]}; }
+};
 
 inline u32 ceil_div_u64(u64 a, u64 b) { return (u32)((a + b - 1) / b); }
 
@@ -287,15 +323,61 @@ inline bool aligned16(const T *p)
     return (reinterpret_cast<uintptr_t>(p) & 15u) == 0;
 }
 
+// the n pointers of an array, as one argument of wide_units
+template <typename T>
+struct PtrArray {
+    T *const *p;
+    u64 n;
+};
+template <typename T>
+inline PtrArray<T> ptr_array(T *const *p, u64 n) { return PtrArray<T>{p, n}; }
+template <typename T>
+inline bool aligned16(PtrArray<T> a) { return std::all_of(a.p, a.p + a.n, [](T *q) { return aligned16(q); }); }
+
+// The unit of the uniform launchers: 16 bytes when dL is even and every pointer (one by one, or ptr_array) is 16-byte
+// aligned -- a null pointer counts as aligned --, else 8 bytes.
+template <typename... P>
+inline bool wide_units(u64 dL, P... p)
+{
+    return dL % 2 == 0 && (aligned16(p) && ...);
+}
+
+// Term counts per element stay below 2^62, every count the C ABI computes or accepts.
+constexpr u64 kTermLimit = 1ull << 62;
+
+// p = x * y; false when the product reaches kTermLimit
+inline bool term_mul(u64 x, u64 y, u64 &p)
+{
+    unsigned long long q;
+    if (__builtin_mul_overflow((unsigned long long)x, (unsigned long long)y, &q) || q >= kTermLimit)
+        return false;
+    p = q;
+    return true;
+}
+
 // Block order of the one-unit-per-lane stream kernels (1x1 multiply, uniform add): XCD-contiguous
 // once a launch is large (measured +3-5 % from 32 M units = 512 MB per stream up, -1-2 % at
 // 10 M units).  Knob stream_xcd = 0 / 1 forces it.
 inline u32 stream_xcd(u64 units)
 {
-    const int forced = tune(TUNE_STREAM_XCD);
-    if (forced == 0 || forced == 1)
-        return (u32)forced;
-    return units >= (1ull << 25) ? 1u : 0u;
+    return tune_choose(TUNE_STREAM_XCD, units >= (1ull << 25)) ? 1u : 0u;
+}
+
+// The launches of a grid of per_group workgroups for every group of G elements, as many groups per launch as
+// kMaxBlocks256 allows: launch(e0, elements, workgroups) issues the one from element e0 on.
+template <typename Launch>
+inline hipError_t launch_groups(u64 batch, u32 G, u64 per_group, Launch launch)
+{
+    const u64 max_groups = std::max<u64>(1, kMaxBlocks256 / per_group);
+    const u64 groups = (batch + G - 1) / G;
+    for (u64 g0 = 0; g0 < groups; g0 += max_groups) {
+        const u64 ng = std::min(max_groups, groups - g0), e0 = g0 * G;
+        launch(e0, std::min<u64>(batch - e0, ng * G), (u32)(ng * per_group));
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess)
+            return e;
+    }
+    return hipSuccess;
 }
 
 // 4 KiB chunks per workgroup of the flat ragged kernels: as many as 8 (the workgroup's first search
@@ -310,6 +392,106 @@ inline int ragged_chunks(u64 total_units)
     while (c < 8 && total_units / (256u * 2u * (u64)c) >= 8192u)
         c *= 2;
     return c;
+}
+
+// ------------------------------------------------------------------------- subset tables
+// For a workgroup's elements and its slice of KC units of every term, table k holds the AND of every subset of the
+// fresh (one-term) planes [hb[k], hb[k+1]), entry S of element el at units tbase[k] + ((el << h_k) | S) * KC on; the
+// AND of any subset of all the planes is then one to three LDS reads (csgn_uint_lut.hip, csgn_uint_read.hip).
+constexpr u32 kMaxSubsetTables = 3;
+
+// by value in the kernel arguments
+struct SubsetTables {
+    u32 ntab, hb[kMaxSubsetTables + 1], tbase[kMaxSubsetTables];   // table k: planes [hb[k], hb[k+1]), at unit tbase[k]
+};
+
+// The build by a 256-thread workgroup for its elements [e0, e0 + ne) of G and units [k0, k0 + kc) of a KC-unit slice
+// (dKC: KC), plane i of the elements from plane[i] on; every table is complete at the closing barrier.
+template <typename Unit>
+__device__ inline void subset_build(Unit *tab, const SubsetTables &t, const void *const *plane, u32 G, u32 KC,
+                                    const FastDiv &dKC, u32 U, u64 last_mask, u64 e0, u32 ne, u32 k0, u32 kc)
+{
+    // entry 0 of every table is ONE; level b fills entries [2^b, 2^(b+1)) from [0, 2^b) and plane hb[k] + b
+    for (u32 tb = 0; tb < t.ntab; ++tb) {
+        const u32 h = t.hb[tb + 1] - t.hb[tb];
+        for (u32 x = threadIdx.x; x < G * KC; x += 256u) {
+            const u32 el = csgn_fastdiv(x, dKC), kk = x - el * KC;
+            tab[t.tbase[tb] + ((el << h) * KC) + kk] = one_unit(Unit(), k0 + kk, U, last_mask);
+        }
+    }
+    for (u32 b = 0; b < t.hb[1]; ++b) {              // table 0 is the widest
+        __syncthreads();
+        for (u32 tb = 0; tb < t.ntab; ++tb) {
+            const u32 h = t.hb[tb + 1] - t.hb[tb];
+            if (b >= h)
+                continue;
+            const Unit *p = reinterpret_cast<const Unit *>(plane[t.hb[tb] + b]);
+            const u32 n = (G * KC) << b;
+            for (u32 x = threadIdx.x; x < n; x += 256u) {
+                const u32 row = csgn_fastdiv(x, dKC), kk = x - row * KC;
+                const u32 el = row >> b, s = (1u << b) | (row & ((1u << b) - 1u));
+                if (el >= ne || kk >= kc)
+                    continue;
+                const u32 at = t.tbase[tb] + ((el << h) | s) * KC + kk;
+                tab[at] = tab[at - (1u << b) * KC] & p[(e0 + el) * U + k0 + kk];
+            }
+        }
+    }
+    __syncthreads();
+}
+
+// the AND of the planes of subset S for element el, unit kk of the slice
+template <typename Unit>
+__device__ inline Unit subset_and(const Unit *tab, const SubsetTables &t, u32 el, u32 S, u32 KC, u32 kk)
+{
+    Unit v = tab[t.tbase[0] + ((el << t.hb[1]) | (S & ((1u << t.hb[1]) - 1u))) * KC + kk];
+    for (u32 tb = 1; tb < t.ntab; ++tb) {
+        const u32 h = t.hb[tb + 1] - t.hb[tb];
+        v &= tab[t.tbase[tb] + ((el << h) | ((S >> t.hb[tb]) & ((1u << h) - 1u))) * KC + kk];
+    }
+    return v;
+}
+
+// The host plan: the table split and the unit slices of `planes` fresh planes (0: no tables) at U units of unit_bytes
+// per term within `budget` bytes of LDS per workgroup; layout(G) places the tables of G elements.
+struct SubsetPlan {
+    SubsetTables t;
+    u64 entries;              // table units per element and unit of a term
+    u32 unit_bytes;
+    u32 KC, chunks;           // units of a slice, slices of a term
+    u64 max_G;                // elements whose tables fit the budget (no limit without tables)
+
+    u32 layout(u32 G)         // tbase[]; returns the LDS bytes
+    {
+        u32 at = 0;
+        for (u32 k = 0; k < t.ntab; ++k) {
+            t.tbase[k] = at;
+            at += (u32)((G << (t.hb[k + 1] - t.hb[k])) * KC);
+        }
+        return at * unit_bytes;
+    }
+};
+
+inline SubsetPlan subset_plan(u32 planes, u32 U, u32 unit_bytes, u64 budget)
+{
+    SubsetPlan p = {};
+    p.unit_bytes = unit_bytes;
+    // one table up to 5 planes, two up to 10, three above; the low tables take the odd planes
+    if (planes) {
+        p.t.ntab = planes <= 5 ? 1 : planes <= 10 ? 2 : 3;
+        for (u32 k = 0; k < p.t.ntab; ++k) {
+            const u32 h = (planes - p.t.hb[k] + (p.t.ntab - k) - 1) / (p.t.ntab - k);
+            p.t.hb[k + 1] = p.t.hb[k] + h;
+            p.entries += 1ull << h;
+        }
+    }
+    // unit chunks: only when one element's tables at whole terms pass the budget
+    const u64 per_unit = p.entries * unit_bytes;
+    const u32 chunks = per_unit * U > budget ? (u32)((per_unit * U + budget - 1) / budget) : 1u;
+    p.KC = (U + chunks - 1) / chunks;
+    p.chunks = (U + p.KC - 1) / p.KC;
+    p.max_G = per_unit ? std::max<u64>(1, budget / (per_unit * p.KC)) : ~0ull;
+    return p;
 }
 
 } // namespace

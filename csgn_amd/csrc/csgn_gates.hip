@@ -18,25 +18,6 @@ namespace csgn {
 
 namespace {
 
-// the constant term's unit k of U: every bit set but the unused low bits of the term's last word
-__device__ inline unit16 const_unit(unit16, u32 k, u32 U, u64 last_mask, bool one)
-{
-    const u32 m = one ? 0xFFFFFFFFu : 0u;
-    unit16 v = {m, m, m, m};
-    if (k == U - 1u) {
-        v.z &= (u32)last_mask;
-        v.w &= (u32)(last_mask >> 32);
-    }
-    return v;
-}
-__device__ inline unit8 const_unit(unit8, u32 k, u32 U, u64 last_mask, bool one)
-{
-    const u64 m = one ? ~0ull : 0ull;
-    return k == U - 1u ? (m & last_mask) : m;
-}
-__device__ inline unit16 unit_fill(unit16, u32 m) { return unit16{m, m, m, m}; }
-__device__ inline unit8 unit_fill(unit8, u32 m) { return m ? ~0ull : 0ull; }
-
 // One constant term per element: ONE where plain[e] & 1 (or `bit` when plain is null), ZERO elsewhere, written at
 // out + e * pitch (units).  Written by the kernel: no compute path calls hipMemsetAsync (csgn_device.h, zero_words).
 template <typename Unit>
@@ -48,7 +29,7 @@ __global__ void __launch_bounds__(256) k_const_fill(const uint8_t *__restrict__ 
         return;
     const u32 e = csgn_fastdiv(g, dU), k = g - e * U;
     const bool one = (plain ? plain[e] & 1u : bit) != 0u;
-    unit_store<Unit, true>(out + (u64)e * pitch + k, const_unit(Unit(), k, U, last_mask, one));
+    unit_store<Unit, true>(out + (u64)e * pitch + k, one ? one_unit(Unit(), k, U, last_mask) : zero_unit(Unit()));
 }
 
 // ---------------------------------------------------------------------------------------
@@ -130,8 +111,8 @@ __global__ void __launch_bounds__(256) k_gate_fused(GateArgs a)
         else
             keep = keep && p;
     }
-    const Unit v = (va & vb & unit_fill(Unit(), keep ? 0xFFFFFFFFu : 0u)) |
-                   (kind == SEG_CONST ? const_unit(Unit(), rr, U, a.last_mask, one) : unit_fill(Unit(), 0u));
+    const Unit v = (keep ? va & vb : zero_unit(Unit())) |
+                   (one ? one_unit(Unit(), rr, U, a.last_mask) : zero_unit(Unit()));
     unit_store<Unit, true>(reinterpret_cast<Unit *>(a.out) + g, v);
 }
 
@@ -180,16 +161,13 @@ constexpr u64 kFusedMaxProductTerms = 64;
 // the form a call takes: true = fused
 bool gate_use_fused(int gate, u64 ts, u64 ta, u64 tb)
 {
-    const int forced = tune(TUNE_GATE_FUSED);
     // mulPlain has no composed form (a per-element select), MUX over a multi-term selector has none without an
     // intermediate buffer (its product rows interleave s_i & a with s_i & b)
     if (gate == CSGN_GATE_MUL_PLAIN || (gate == CSGN_GATE_MUX && ts != 1))
         return true;
-    if (forced == 0 || forced == 1)
-        return forced == 1;
     GateShape g;
     gate_shape(gate, ts, ta, tb, g);
-    return g.prod < 0 || g.terms[g.prod] <= kFusedMaxProductTerms;
+    return tune_choose(TUNE_GATE_FUSED, g.prod < 0 || g.terms[g.prod] <= kFusedMaxProductTerms);
 }
 
 template <typename Unit>
@@ -253,23 +231,16 @@ u64 gate_terms(int gate, u64 ts, u64 ta, u64 tb)
                         gate == CSGN_GATE_NOR || gate == CSGN_GATE_MUX;
     if (ta == 0 || (uses_s && ts == 0) || (uses_b && tb == 0))
         return 0;
-    const u64 lim = 1ull << 62;
-    if (ta >= lim || tb >= lim || ts >= lim)
+    if (ta >= kTermLimit || tb >= kTermLimit || ts >= kTermLimit)
         return 0;
-    u64 total = 0;
-    if (uses_s) {                                                       // ts * (ta + tb) + tb
-        unsigned long long p;
-        if (__builtin_mul_overflow((unsigned long long)ts, (unsigned long long)(ta + tb), &p) || p >= lim)
-            return 0;
-        return p + tb < lim ? p + tb : 0;
-    }
-    unsigned long long p = 0;
-    if (uses_b && gate != CSGN_GATE_XNOR &&
-        (__builtin_mul_overflow((unsigned long long)ta, (unsigned long long)tb, &p) || p >= lim))
+    u64 p = 0, total = 0;
+    if (uses_s)                                                         // ts * (ta + tb) + tb
+        return term_mul(ts, ta + tb, p) && p + tb < kTermLimit ? p + tb : 0;
+    if (uses_b && gate != CSGN_GATE_XNOR && !term_mul(ta, tb, p))
         return 0;
     for (u32 i = 0; i < g.nseg; ++i)
         total += g.terms[i];
-    return total < lim ? total : 0;
+    return total < kTermLimit ? total : 0;
 }
 
 const char *gate_kernel_name(u64 n_bits, int gate, u64 batch, u64 ts, u64 ta, u64 tb)
@@ -289,7 +260,7 @@ hipError_t const_fill(u64 n_bits, u64 batch, const uint8_t *plain, int bit, u64 
         return hipSuccess;
     if (pitch_words == 0)
         pitch_words = dL;
-    const bool wide = dL % 2 == 0 && pitch_words % 2 == 0 && aligned16(out);
+    const bool wide = pitch_words % 2 == 0 && wide_units(dL, out);
     const u32 U = (u32)(wide ? dL / 2 : dL);
     const u64 pitch = wide ? pitch_words / 2 : pitch_words;
     const FastDiv dU = csgn_fastdiv_make(U);
@@ -323,7 +294,7 @@ hipError_t gate_uniform(u64 n_bits, int gate, u64 batch, u64 ts, u64 ta, u64 tb,
     const u64 t[3] = {ts, ta, tb};
     const u64 *ops[3] = {S, A, B};
     if (gate_use_fused(gate, ts, ta, tb)) {
-        const bool wide = dL % 2 == 0 && aligned16(S) && aligned16(A) && aligned16(B) && aligned16(out);
+        const bool wide = wide_units(dL, S, A, B, out);
         const u32 U = (u32)(wide ? dL / 2 : dL);
         const u32 pm = gate == CSGN_GATE_ADD_PLAIN ? 1u : (gate == CSGN_GATE_MUL_PLAIN ? 2u : 0u);
         return wide ? gate_fused<unit16>(sh, n_bits, batch, t, ops, plain, pm, out, U, s)

@@ -24,8 +24,7 @@ struct GatherArgs {
     const void *src[kGatherMaxPlanes];
     void *dst[kGatherMaxPlanes];
     u64 first[kGatherMaxPlanes + 1];                  // virtual workgroup where plane j starts; first[n_planes]: the end
-    u32 eu[kGatherMaxPlanes];                         // units per element of plane j (t_j * U)
-    u32 eu_magic[kGatherMaxPlanes], eu_shift[kGatherMaxPlanes];   // FastDiv by eu[j]
+    FastDivTable<kGatherMaxPlanes> eu;                // units per element of plane j (t_j * U)
     const u64 *idx;                                   // nullptr: tile, idx[e] = e mod count_in
     u64 block_base;                                   // virtual workgroup of this launch's workgroup 0
     u32 count_in, count_out;
@@ -49,11 +48,8 @@ __global__ void __launch_bounds__(256) k_gather(GatherArgs a)
             hi = mid;
     }
     const u32 j = lo;
-    const u32 eu = a.eu[j];
-    FastDiv deu;
-    deu.d = eu;
-    deu.magic = a.eu_magic[j];
-    deu.shift = a.eu_shift[j];
+    const FastDiv deu = a.eu.at(j);
+    const u32 eu = deu.d;
     const Unit *__restrict__ src = reinterpret_cast<const Unit *>(a.src[j]);
     Unit *__restrict__ dst = reinterpret_cast<Unit *>(a.dst[j]);
     const u64 units = (u64)a.count_out * eu;
@@ -345,9 +341,7 @@ hipError_t gather_planes(u64 n_bits, u64 n_planes, const u64 *const *src, const 
     const u64 dL = (n_bits + 63) / 64;
     if (count_out == 0 || n_planes == 0 || n_planes > kGatherMaxPlanes)
         return n_planes > kGatherMaxPlanes ? hipErrorInvalidValue : hipSuccess;
-    bool wide = dL % 2 == 0;
-    for (u64 j = 0; j < n_planes; ++j)
-        wide = wide && aligned16(src[j]) && aligned16(dst[j]);
+    const bool wide = wide_units(dL, ptr_array(src, n_planes), ptr_array(dst, n_planes));
     const u32 U = (u32)(wide ? dL / 2 : dL);
     GatherArgs a;
     u32 n = 0;
@@ -356,12 +350,9 @@ hipError_t gather_planes(u64 n_bits, u64 n_planes, const u64 *const *src, const 
         if (terms[j] == 0)
             continue;                                              // an empty plane: nothing to write
         const u32 eu = (u32)(terms[j] * U);
-        const FastDiv f = csgn_fastdiv_make(eu);
         a.src[n] = src[j];
         a.dst[n] = dst[j];
-        a.eu[n] = eu;
-        a.eu_magic[n] = f.magic;
-        a.eu_shift[n] = f.shift;
+        a.eu.set(n, eu);
         a.first[n] = blocks;
         blocks += (count_out * eu + kGatherBlockUnits - 1) / kGatherBlockUnits;
         units += count_out * eu;
@@ -396,7 +387,7 @@ hipError_t gather_ragged(u64 n_bits, u64 count_in, const u64 *src, const u64 *sr
     const u64 dL = (n_bits + 63) / 64;
     if (count_out == 0 || total_terms_out == 0)
         return hipSuccess;
-    const bool wide = dL % 2 == 0 && aligned16(src) && aligned16(dst);
+    const bool wide = wide_units(dL, src, dst);
     const u32 U = (u32)(wide ? dL / 2 : dL);
     const u64 total_units = total_terms_out * U;
     const FastDiv dU = csgn_fastdiv_make(U), d_in = csgn_fastdiv_make(count_in ? (u32)count_in : 1u);

@@ -86,6 +86,14 @@ int find(const char *name)
 
 int tune(TuneKey k) { return values()[k]; }
 
+bool tune_choose(TuneKey k, bool by_shape)
+{
+    const int forced = tune(k);
+    if (forced == 0 || forced == 1)
+        return forced == 1;
+    return by_shape;
+}
+
 const char *tune_name(int k) { return (k >= 0 && k < TUNE_COUNT) ? kKnobs[k].name : nullptr; }
 
 bool tune_set(const char *name, int value)

@@ -57,6 +57,7 @@ enum TuneKey {
 };
 
 int tune(TuneKey k);                      // the calling thread's value
+bool tune_choose(TuneKey k, bool by_shape); // a "-1 = by shape, 0 / 1 forced" knob: forced 0 / 1 wins, else by_shape
 const char *tune_name(int k);             // "mul_m", ... (nullptr past the end)
 bool tune_set(const char *name, int value);
 bool tune_get(const char *name, int *value);

@@ -2,7 +2,7 @@
 // batches.  Hand-written CDNA4 (gfx950) HIP; shared helpers in csgn_device.h, design notes in DESIGN.md ("Integers").
 //
 // Every step is a composition of the reference's operator+ (concatenation) and operator* (all-pairs AND, left term
-// slowest) with the all-ones term ONE (csgn_gates.hip), in the order of the table in include/csgn_hip.h.  One output
+// slowest) with the all-ones term ONE (csgn_device.h), in the order of the table in include/csgn_hip.h.  One output
 // element is a sequence of SEGMENTS:
 //     copy of one operand | all-pairs product of one operand (or ONE) with a VIRTUAL concatenation of up to three
 //     operands / ONE
@@ -52,18 +52,6 @@ __host__ __device__ constexpr u32 step_segment(int step, u32 s)
     }
 }
 
-// the ONE term's unit k of U (the unused low bits of the term's last word zero)
-__device__ inline unit16 one_unit(unit16, u32 k, u32 U, u64 last_mask)
-{
-    unit16 v = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
-    if (k == U - 1u) {
-        v.z = (u32)last_mask;
-        v.w = (u32)(last_mask >> 32);
-    }
-    return v;
-}
-__device__ inline unit8 one_unit(unit8, u32 k, u32 U, u64 last_mask) { return k == U - 1u ? last_mask : ~0ull; }
-
 // Segment s (step_segment) of an element covers its units [begin[s], end[s]) of the two outputs laid end to end
 // (out0's segments first; r >= EU0 is out1); a product's right operand has its part ends pend0 / pend1 (units into a
 // row) and its row length (row_*).
@@ -73,7 +61,7 @@ struct UintArgs {
     u32 t[4];                 // terms per element of x, a, b; t[3] = 1 (ONE)
     u32 begin[kMaxSeg], end[kMaxSeg - 1];
     u32 pend0[kMaxSeg], pend1[kMaxSeg];
-    u32 row_d[kMaxSeg], row_magic[kMaxSeg], row_shift[kMaxSeg];   // FastDiv of each product's row (units)
+    FastDivTable<kMaxSeg> row;                                    // FastDiv of each product's row (units)
     u32 U, EU0, EU1, EU;      // units per term, per element of out0 / out1 / both
     u32 total_units;          // this launch
     u32 xcd;
@@ -130,7 +118,7 @@ __global__ void __launch_bounds__(256) k_uint_step(UintArgs a)
     const u32 left = (desc >> 2) & 3u;
     const u32 tl = left == OP_X ? a.t[0] : (left == OP_A ? a.t[1] : (left == OP_B ? a.t[2] : 1u));
     // product coordinates (harmless for a copy: only selected below)
-    const FastDiv dRow = {pick<N>(a.row_d, s), pick<N>(a.row_magic, s), pick<N>(a.row_shift, s)};
+    const FastDiv dRow = {pick<N>(a.row.d, s), pick<N>(a.row.magic, s), pick<N>(a.row.shift, s)};
     const u32 i = csgn_fastdiv(rr, dRow), c = rr - i * dRow.d;
     const u32 k = c - csgn_fastdiv(c, a.dU) * U;
     const u32 pe0 = pick<N>(a.pend0, s), pe1 = pick<N>(a.pend1, s);
@@ -207,10 +195,8 @@ bool uint_use_fused(int step, u64 tx, u64 ta, u64 tb)
                 return true;
             prod_terms += sh.seg[i].terms;
         }
-    const int forced = tune(TUNE_UINT_FUSED);
-    if (forced == 0 || forced == 1)
-        return forced == 1;
-    return prod_terms <= (step == CSGN_UINT_LT_STEP ? kLtFusedMaxProductTerms : kUintFusedMaxProductTerms);
+    return tune_choose(TUNE_UINT_FUSED,
+                       prod_terms <= (step == CSGN_UINT_LT_STEP ? kLtFusedMaxProductTerms : kUintFusedMaxProductTerms));
 }
 
 template <typename Unit>
@@ -225,7 +211,7 @@ hipError_t uint_fused(int step, const UintShape &sh, u64 n_bits, u64 batch, cons
     a.t[3] = 1;
     u64 run = 0;
     for (u32 i = 0; i < kMaxSeg; ++i) {
-        FastDiv row_div = csgn_fastdiv_make(1);
+        u32 row_div = 1;
         if (i < sh.nseg) {
             const USeg &g = sh.seg[i];
             a.begin[i] = (u32)run;
@@ -235,12 +221,10 @@ hipError_t uint_fused(int step, const UintShape &sh, u64 n_bits, u64 batch, cons
                 const u64 row = e1 + (g.np > 2 ? a.t[g.part[2]] * (u64)U : 0);
                 a.pend0[i] = (u32)(g.np > 1 ? e0 : row);
                 a.pend1[i] = (u32)(g.np > 2 ? e1 : row);
-                row_div = csgn_fastdiv_make((u32)row);
+                row_div = (u32)row;
             }
         }
-        a.row_d[i] = row_div.d;
-        a.row_magic[i] = row_div.magic;
-        a.row_shift[i] = row_div.shift;
+        a.row.set(i, row_div);
         if (i + 1 < kMaxSeg)
             a.end[i] = (u32)run;                               // completed below for the segments past nseg
     }
@@ -288,12 +272,11 @@ u64 uint_step_terms(int step, int output, u64 tx, u64 ta, u64 tb)
         tx = 1;                                                          // not read: any count
     if (tx == 0 || ta == 0 || tb == 0)
         return 0;
-    const u64 lim = 1ull << 62;
-    if (tx >= lim || ta >= lim || tb >= lim)
+    if (tx >= kTermLimit || ta >= kTermLimit || tb >= kTermLimit)
         return 0;
     UintShape sh;
     uint_shape(step, true, tx, ta, tb, sh);
-    // every product (the segments' term counts) below lim, and their sum
+    // every product (the segments' term counts) below kTermLimit, and their sum
     u64 total = 0;
     for (u32 i = 0; i < sh.nseg; ++i) {
         const USeg &g = sh.seg[i];
@@ -303,14 +286,14 @@ u64 uint_step_terms(int step, int output, u64 tx, u64 ta, u64 tb)
             const u64 tl = g.left == OP_X ? tx : (g.left == OP_A ? ta : (g.left == OP_B ? tb : 1));
             const u64 tr[4] = {tx, ta, tb, 1};
             const u64 right = tr[g.part[0]] + (g.np > 1 ? tr[g.part[1]] : 0) + (g.np > 2 ? tr[g.part[2]] : 0);
-            unsigned long long p;
-            if (right >= lim || __builtin_mul_overflow((unsigned long long)tl, (unsigned long long)right, &p) || p >= lim)
+            u64 p;
+            if (!term_mul(tl, right, p))
                 return 0;
             total += p;
         } else {
             total += g.terms;
         }
-        if (total >= lim)
+        if (total >= kTermLimit)
             return 0;
     }
     return total;
@@ -346,8 +329,7 @@ hipError_t uint_step(u64 n_bits, int step, u64 batch, const u64 *X, u64 tx, cons
     const u64 *ops[3] = {X, A, B};
     u64 *const outs[2] = {out0, out1};
     if (uint_use_fused(step, tx, ta, tb)) {
-        const bool wide = dL % 2 == 0 && aligned16(X) && aligned16(A) && aligned16(B) && aligned16(out0) &&
-                          aligned16(out1);
+        const bool wide = wide_units(dL, X, A, B, out0, out1);
         const u32 U = (u32)(wide ? dL / 2 : dL);
         return wide ? uint_fused<unit16>(step, sh, n_bits, batch, t, ops, outs, U, s)
                     : uint_fused<unit8>(step, sh, n_bits, batch, t, ops, outs, U, s);

@@ -9,10 +9,11 @@
 //     r = idx - moff[m];  for i in S, highest first:  d_i = r % t_i,  r /= t_i;  AND a_i[d_i]
 //
 // Fresh planes (every t_i = 1), the case this kernel is built for, read each plane once per workgroup: the workgroup
-// builds, for its elements and its slice of units, subset tables in LDS -- table k holds the AND of every subset of its
-// planes [hb[k], hb[k+1]) -- and every written unit is T_0[S_0] & T_1[S_1] & T_2[S_2]: one to three LDS reads, whatever
-// |S| is.  Lanes walk one output's contiguous term stream, so one store instruction writes 64 consecutive units of one
-// plane.  Multi-term planes take the decode above straight from the planes (correct, not fast).
+// builds, for its elements and its slice of units, subset tables in LDS (csgn_device.h) -- table k holds the AND of
+// every subset of its planes [hb[k], hb[k+1]) -- and every written unit is T_0[S_0] & T_1[S_1] & T_2[S_2]: one to three
+// LDS reads, whatever |S| is.  Lanes walk one output's contiguous term stream, so one store instruction writes 64
+// consecutive units of one plane.  Multi-term planes take the decode above straight from the planes (correct, not
+// fast).
 #include "csgn_device.h"
 #include "csgn_hip.h"
 
@@ -23,22 +24,8 @@ namespace csgn {
 
 namespace {
 
-constexpr u32 kMaxTables = 3;
 constexpr u64 kLdsBudget = 32768;       // bytes of subset tables per workgroup: four workgroups per CU
 constexpr u64 kPartUnits = 8192;        // units a workgroup writes at least, where the shape has them
-
-__device__ inline unit16 lut_one(unit16, u32 k, u32 U, u64 last_mask)
-{
-    unit16 v = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
-    if (k == U - 1u) {
-        v.z = (u32)last_mask;
-        v.w = (u32)(last_mask >> 32);
-    }
-    return v;
-}
-__device__ inline unit8 lut_one(unit8, u32 k, u32 U, u64 last_mask) { return k == U - 1u ? last_mask : ~0ull; }
-__device__ inline unit16 lut_zero(unit16) { return unit16{0u, 0u, 0u, 0u}; }
-__device__ inline unit8 lut_zero(unit8) { return 0ull; }
 
 // By value in the kernel arguments (uniform, scalar loads).  A workgroup is (element group, unit chunk, part): it owns
 // elements [group * G, + G), units [chunk * KC, + KC) of every term, and part `part` of the stream of its units laid
@@ -49,7 +36,7 @@ struct LutArgs {
     u64 seg[kLutMaxOut + 1];
     u32 T[kLutMaxOut];
     u32 mbase[kLutMaxOut + 1];
-    u32 tk_d[kLutMaxOut], tk_magic[kLutMaxOut], tk_shift[kLutMaxOut];    // T_j * KC as a FastDiv
+    FastDivTable<kLutMaxOut> tk;                                         // T_j * KC
     u32 t[kLutMaxIn];
     const u32 *mono, *moff;
     u64 zero;                 // bit j: output j has an empty ANF (ZERO)
@@ -57,7 +44,7 @@ struct LutArgs {
     u64 batch;                // elements of this launch
     u32 w, m;
     u32 U, KC, G, chunks, parts, nblocks, xcd;
-    u32 ntab, hb[kMaxTables + 1], tbase[kMaxTables];   // table k: planes [hb[k], hb[k+1]), at unit tbase[k] of the LDS
+    SubsetTables tabs;
     FastDiv dKC;
 };
 
@@ -73,35 +60,8 @@ __global__ void __launch_bounds__(256) k_uint_lut(LutArgs a)
     const u32 ne = (u32)min((u64)a.G, a.batch - e0);
     const u32 k0 = chunk * a.KC, kc = min(a.KC, a.U - k0);
 
-    if (Fresh) {
-        // entry 0 of every table is ONE; level b fills entries [2^b, 2^(b+1)) from [0, 2^b) and plane hb[k] + b
-        for (u32 tb = 0; tb < a.ntab; ++tb) {
-            const u32 h = a.hb[tb + 1] - a.hb[tb];
-            for (u32 x = threadIdx.x; x < a.G * a.KC; x += 256u) {
-                const u32 el = csgn_fastdiv(x, a.dKC), kk = x - el * a.KC;
-                tab[a.tbase[tb] + ((el << h) * a.KC) + kk] = lut_one(Unit(), k0 + kk, a.U, a.last_mask);
-            }
-        }
-        for (u32 b = 0; b < a.hb[1]; ++b) {              // table 0 is the widest
-            __syncthreads();
-            for (u32 tb = 0; tb < a.ntab; ++tb) {
-                const u32 h = a.hb[tb + 1] - a.hb[tb];
-                if (b >= h)
-                    continue;
-                const Unit *p = reinterpret_cast<const Unit *>(a.plane[a.hb[tb] + b]);
-                const u32 n = (a.G * a.KC) << b;
-                for (u32 x = threadIdx.x; x < n; x += 256u) {
-                    const u32 row = csgn_fastdiv(x, a.dKC), kk = x - row * a.KC;
-                    const u32 el = row >> b, s = (1u << b) | (row & ((1u << b) - 1u));
-                    if (el >= ne || kk >= kc)
-                        continue;
-                    const u32 at = a.tbase[tb] + ((el << h) | s) * a.KC + kk;
-                    tab[at] = tab[at - (1u << b) * a.KC] & p[(e0 + el) * a.U + k0 + kk];
-                }
-            }
-        }
-        __syncthreads();
-    }
+    if (Fresh)
+        subset_build(tab, a.tabs, a.plane, a.G, a.KC, a.dKC, a.U, a.last_mask, e0, ne, k0, kc);
 
     const u64 W = a.seg[a.m];
     const u64 lo = W * part / a.parts, hi = W * (part + 1u) / a.parts;
@@ -109,7 +69,7 @@ __global__ void __launch_bounds__(256) k_uint_lut(LutArgs a)
         const u64 s0 = max(lo, a.seg[j]), s1 = min(hi, a.seg[j + 1]);
         if (s0 >= s1)
             continue;
-        const FastDiv dtk = {a.tk_d[j], a.tk_magic[j], a.tk_shift[j]};
+        const FastDiv dtk = a.tk.at(j);
         const u32 Tj = a.T[j], mb = a.mbase[j];
         const bool zero = (a.zero >> j) & 1u;
         Unit *o = reinterpret_cast<Unit *>(a.out[j]);
@@ -123,14 +83,9 @@ __global__ void __launch_bounds__(256) k_uint_lut(LutArgs a)
             const u64 e = e0 + el;
             Unit v;
             if (zero) {
-                v = lut_zero(Unit());
+                v = zero_unit(Unit());
             } else if (Fresh) {
-                const u32 S = a.mono[mb + q];
-                v = tab[a.tbase[0] + ((el << a.hb[1]) | (S & ((1u << a.hb[1]) - 1u))) * a.KC + kk];
-                for (u32 tb = 1; tb < a.ntab; ++tb) {
-                    const u32 h = a.hb[tb + 1] - a.hb[tb];
-                    v &= tab[a.tbase[tb] + ((el << h) | ((S >> a.hb[tb]) & ((1u << h) - 1u))) * a.KC + kk];
-                }
+                v = subset_and(tab, a.tabs, el, a.mono[mb + q], a.KC, kk);
             } else {
                 // the monomial holding term q: the last one of output j starting at or before it
                 u32 lo_m = mb, hi_m = a.mbase[j + 1];
@@ -143,7 +98,7 @@ __global__ void __launch_bounds__(256) k_uint_lut(LutArgs a)
                 }
                 const u32 S = a.mono[lo_m];
                 u32 rr = q - a.moff[lo_m];
-                v = lut_one(Unit(), k, a.U, a.last_mask);
+                v = one_unit(Unit(), k, a.U, a.last_mask);
                 for (u32 i = a.w; i-- > 0u;) {
                     if (!((S >> i) & 1u))
                         continue;
@@ -158,8 +113,6 @@ __global__ void __launch_bounds__(256) k_uint_lut(LutArgs a)
 }
 
 // ------------------------------------------------------------------------------ the plan on the host
-
-constexpr u64 kTermLimit = 1ull << 62;
 
 int lut_check(u64 w, u64 m, const u64 *table)
 {
@@ -188,20 +141,16 @@ u64 mono_terms(u64 S, const u64 *t)
     for (u32 i = 0; S >> i; ++i) {
         if (!((S >> i) & 1u))
             continue;
-        unsigned long long q;
-        if (__builtin_mul_overflow((unsigned long long)p, (unsigned long long)t[i], &q) || q >= kTermLimit)
+        if (!term_mul(p, t[i], p))
             return 0;
-        p = q;
     }
     return p;
 }
 
 bool lut_use_fused()
 {
-    const int forced = tune(TUNE_UINT_LUT_FUSED);
-    if (forced == 0 || forced == 1)
-        return forced == 1;
-    return true;              // one launch for every output: no shape measured where the composed form is faster
+    // by shape: one launch for every output, no shape measured where the composed form is faster
+    return tune_choose(TUNE_UINT_LUT_FUSED, true);
 }
 
 // The workgroup shape of one apply: tables, elements per workgroup, unit chunks, parts.
@@ -228,78 +177,42 @@ hipError_t lut_fused(const LutPlan &p, u64 n_bits, u64 batch, const u64 *const *
     }
     for (u32 j = 0; j <= p.m; ++j)
         a.mbase[j] = p.mbase[j];
-    // subset tables: one up to 5 planes, two up to 10, three above; the low tables take the odd planes
-    u64 entries = 0;      // table units per element and unit of a term
-    if (p.fresh) {
-        a.ntab = p.w <= 5 ? 1 : p.w <= 10 ? 2 : 3;
-        a.hb[0] = 0;
-        for (u32 k = 0; k < a.ntab; ++k) {
-            const u32 h = (p.w - a.hb[k] + (a.ntab - k) - 1) / (a.ntab - k);
-            a.hb[k + 1] = a.hb[k] + h;
-            entries += 1ull << h;
-        }
-    }
-    // unit chunks: only when one element's tables at whole terms pass the budget
-    const u64 per_unit = entries * sizeof(Unit);
-    u32 chunks = 1;
-    if (p.fresh && per_unit * U > kLdsBudget)
-        chunks = (u32)((per_unit * U + kLdsBudget - 1) / kLdsBudget);
-    a.chunks = chunks;
-    a.KC = (U + chunks - 1) / chunks;
-    a.chunks = (U + a.KC - 1) / a.KC;
+    SubsetPlan sp = subset_plan(p.fresh ? p.w : 0, U, (u32)sizeof(Unit), kLdsBudget);
+    a.KC = sp.KC;
+    a.chunks = sp.chunks;
     // elements per workgroup: enough to give it kPartUnits to write, as many as the tables allow
     const u64 elem_units = sumT * a.KC;
     u64 G = std::max<u64>(1, kPartUnits / std::max<u64>(elem_units, 1));
-    if (p.fresh)
-        G = std::min<u64>(G, std::max<u64>(1, kLdsBudget / (per_unit * a.KC)));
-    G = std::min<u64>({G, batch, 64, 0xFFFFFFFFull / (maxT * a.KC)});
+    G = std::min<u64>({G, sp.max_G, batch, 64, 0xFFFFFFFFull / (maxT * a.KC)});
     a.G = (u32)std::max<u64>(G, 1);
     a.dKC = csgn_fastdiv_make(a.KC);
     u64 seg = 0;
     for (u32 j = 0; j < p.m; ++j) {
         a.seg[j] = seg;
         const u64 tk = p.T[j] * a.KC;
-        const FastDiv d = csgn_fastdiv_make((u32)tk);
-        a.tk_d[j] = d.d;
-        a.tk_magic[j] = d.magic;
-        a.tk_shift[j] = d.shift;
+        a.tk.set(j, (u32)tk);
         seg += a.G * tk;
     }
     a.seg[p.m] = seg;
     // parts: a workgroup's stream split so each part writes kPartUnits, or four times its table build
-    const u64 build = a.G * entries * a.KC;
+    const u64 build = a.G * sp.entries * a.KC;
     const u64 target = std::max<u64>(kPartUnits, 4 * build);
     a.parts = (u32)std::min<u64>(std::max<u64>(1, seg / target), 1u << 16);
-    u32 lds = 0;
-    if (p.fresh) {
-        u32 at = 0;
-        for (u32 k = 0; k < a.ntab; ++k) {
-            a.tbase[k] = at;
-            at += (u32)((a.G << (a.hb[k + 1] - a.hb[k])) * a.KC);
-        }
-        lds = at * (u32)sizeof(Unit);
-    }
-    const u64 per_group = (u64)a.chunks * a.parts;
-    const u64 max_groups = std::max<u64>(1, kMaxBlocks256 / per_group);
-    const u64 groups = (batch + a.G - 1) / a.G;
+    const u32 lds = sp.layout(a.G);
+    a.tabs = sp.t;
     a.xcd = stream_xcd(batch * sumT * U);
-    for (u64 g0 = 0; g0 < groups; g0 += max_groups) {
-        const u64 ng = std::min(max_groups, groups - g0), e0 = g0 * a.G;
-        a.batch = std::min<u64>(batch - e0, ng * a.G);
+    return launch_groups(batch, a.G, (u64)a.chunks * a.parts, [&](u64 e0, u64 ne, u32 nblocks) {
+        a.batch = ne;
         for (u32 i = 0; i < p.w; ++i)
             a.plane[i] = reinterpret_cast<const Unit *>(planes[i]) + e0 * p.t[i] * U;
         for (u32 j = 0; j < p.m; ++j)
             a.out[j] = reinterpret_cast<Unit *>(out[j]) + e0 * p.T[j] * U;
-        a.nblocks = (u32)(ng * per_group);
+        a.nblocks = nblocks;
         if (p.fresh)
             k_uint_lut<Unit, true><<<dim3(a.nblocks), 256, lds, s>>>(a);
         else
             k_uint_lut<Unit, false><<<dim3(a.nblocks), 256, 0, s>>>(a);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess)
-            return e;
-    }
-    return hipSuccess;
+    });
 }
 
 // The composed form: every monomial through the tuned launchers, written into its slice of the output (pitch T_j):
@@ -487,11 +400,7 @@ hipError_t uint_lut(const LutPlan &p, u64 n_bits, u64 batch, const u64 *const *p
     if (!lut_use_fused())
         return lut_composed(p, n_bits, batch, planes, out, s);
     const u64 dL = (n_bits + 63) / 64;
-    bool wide = dL % 2 == 0;
-    for (u32 i = 0; i < p.w && wide; ++i)
-        wide = aligned16(planes[i]);
-    for (u32 j = 0; j < p.m && wide; ++j)
-        wide = aligned16(out[j]);
+    const bool wide = wide_units(dL, ptr_array(planes, p.w), ptr_array(out, p.m));
     const u32 U = (u32)(wide ? dL / 2 : dL);
     return wide ? lut_fused<unit16>(p, n_bits, batch, planes, out, U, s)
                 : lut_fused<unit8>(p, n_bits, batch, planes, out, U, s);

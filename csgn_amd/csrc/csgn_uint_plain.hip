@@ -27,19 +27,6 @@ namespace {
 constexpr u32 kMaxLevels = 64;
 constexpr u32 kRun = 16;              // terms per lane
 
-__device__ inline unit16 plain_one(unit16, u32 k, u32 U, u64 last_mask)
-{
-    unit16 v = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
-    if (k == U - 1u) {
-        v.z = (u32)last_mask;
-        v.w = (u32)(last_mask >> 32);
-    }
-    return v;
-}
-__device__ inline unit8 plain_one(unit8, u32 k, u32 U, u64 last_mask) { return k == U - 1u ? last_mask : ~0ull; }
-__device__ inline unit16 plain_zero(unit16) { return unit16{0u, 0u, 0u, 0u}; }
-__device__ inline unit8 plain_zero(unit8) { return 0ull; }
-
 // The level table, by value in the kernel arguments (uniform, scalar loads).  Level j in [base, top]:
 //     plane[j]  a_j of this launch's first element, t[j] terms per element
 //     radix[j]  |f_j| as a FastDiv (t_j, or t_j + 1 when the factor is n_j); unused at the base
@@ -50,7 +37,7 @@ struct PlainArgs {
     const void *plane[kMaxLevels];
     u32 t[kMaxLevels];
     u32 pend[kMaxLevels];
-    u32 rad_d[kMaxLevels], rad_magic[kMaxLevels], rad_shift[kMaxLevels];
+    FastDivTable<kMaxLevels> rad;
     u64 unit;
     void *out;
     u32 base, top, cut;       // levels [cut, top] are walked per term, [base, cut) once per run (cut > top: none)
@@ -88,7 +75,7 @@ __device__ inline bool plain_walk(const PlainArgs &a, u32 hi, u32 lo, u64 eu, u3
             v &= plain_term<Unit>(a, j, eu, idx - pe, k, one);
             return true;
         }
-        const FastDiv dr = {a.rad_d[j], a.rad_magic[j], a.rad_shift[j]};
+        const FastDiv dr = a.rad.at(j);
         const u32 q = csgn_fastdiv(idx, dr), d = idx - q * dr.d;
         idx = q;
         v &= plain_term<Unit>(a, j, eu, d, k, one);
@@ -107,7 +94,7 @@ __global__ void __launch_bounds__(256) k_uint_plain(PlainArgs a)
     const u32 run = csgn_fastdiv(rem, a.dU), k = rem - run * a.U;
     const u32 t0 = run * a.R, nt = min(a.R, a.T - t0);
     const u64 eu = (u64)e * a.U;                          // element e's first unit of a 1-term-per-element list
-    const Unit one = plain_one(Unit(), k, a.U, a.last_mask);
+    const Unit one = one_unit(Unit(), k, a.U, a.last_mask);
     Unit *o = reinterpret_cast<Unit *>(a.out) + ((u64)e * a.T + t0) * a.U + k;
     // the radix-1 factors of the fast levels: every term that passes the cut carries all of them
     Unit fast_unit = one;
@@ -122,7 +109,7 @@ __global__ void __launch_bounds__(256) k_uint_plain(PlainArgs a)
         if (a.neg && idx0 == a.T - 1u) {
             // the appended ONE
         } else if (a.zero) {
-            v = plain_zero(Unit());
+            v = zero_unit(Unit());
         } else {
             // the fast levels, loading only where the digit moves (|f_j| > 1) or a tail ends the walk
             u32 idx = idx0, stop = 0xFFFFFFFFu;
@@ -135,7 +122,7 @@ __global__ void __launch_bounds__(256) k_uint_plain(PlainArgs a)
                 }
                 if ((a.unit >> j) & 1u)
                     continue;                             // d = 0, idx unchanged: f_j[0] is in fast_unit
-                const FastDiv dr = {a.rad_d[j], a.rad_magic[j], a.rad_shift[j]};
+                const FastDiv dr = a.rad.at(j);
                 const u32 q = csgn_fastdiv(idx, dr), d = idx - q * dr.d;
                 idx = q;
                 v &= plain_term<Unit>(a, j, eu, d, k, one);
@@ -171,8 +158,6 @@ struct PlainShape {
     u64 L[kMaxLevels] = {};                // terms of the running value after level j (j >= base)
     u64 T = 0;                             // terms of the result
 };
-
-constexpr u64 kTermLimit = 1ull << 62;
 
 // false: invalid argument or a term count past kTermLimit
 bool plain_shape(int cmp, u64 w, u64 k, const u64 *t, PlainShape &sh)
@@ -227,10 +212,8 @@ bool plain_shape(int cmp, u64 w, u64 k, const u64 *t, PlainShape &sh)
     u64 l = radix(sh.base);
     sh.L[sh.base] = l;
     for (u64 j = sh.base + 1; j < w; ++j) {
-        unsigned long long p;
-        if (__builtin_mul_overflow((unsigned long long)l, (unsigned long long)radix(j), &p) || p >= kTermLimit)
+        if (!term_mul(l, radix(j), l))
             return false;
-        l = p;
         if ((sh.sum >> j) & 1u)
             l += t[j] + ((sh.tail_n >> j) & 1u);
         if (l >= kTermLimit)
@@ -244,10 +227,7 @@ bool plain_shape(int cmp, u64 w, u64 k, const u64 *t, PlainShape &sh)
 // Fused unless forced, and for w = 1 (one copy and at most one constant: the composed form is those tuned launchers).
 bool plain_use_fused(const PlainShape &sh)
 {
-    const int forced = tune(TUNE_UINT_PLAIN_FUSED);
-    if (forced == 0 || forced == 1)
-        return forced == 1;
-    return sh.w > 1 && !sh.zero;
+    return tune_choose(TUNE_UINT_PLAIN_FUSED, sh.w > 1 && !sh.zero);
 }
 
 template <typename Unit>
@@ -277,22 +257,20 @@ hipError_t plain_fused(const PlainShape &sh, u64 n_bits, u64 batch, const u64 *c
         }
     }
     for (u32 j = 0; j < kMaxLevels; ++j) {
-        FastDiv d = csgn_fastdiv_make(1);
+        u32 d = 1;
         a.pend[j] = 0xFFFFFFFFu;
         if (!sh.zero && j < sh.w) {
             a.t[j] = (u32)t[j];
             if (j > sh.base) {
                 const u64 r = t[j] + ((sh.nfac >> j) & 1u);
-                d = csgn_fastdiv_make((u32)r);
+                d = (u32)r;
                 if (r == 1)
                     a.unit |= 1ull << j;
                 if ((sh.sum >> j) & 1u)
                     a.pend[j] = (u32)(sh.L[j - 1] * r);
             }
         }
-        a.rad_d[j] = d.d;
-        a.rad_magic[j] = d.magic;
-        a.rad_shift[j] = d.shift;
+        a.rad.set(j, d);
     }
     a.xcd = stream_xcd(batch * sh.T * U);
     const u64 per = std::max<u64>(1, 0xFFFFFF00ull / a.IPE);            // elements per launch: < 2^32 lane items
@@ -408,9 +386,7 @@ hipError_t uint_plain(u64 n_bits, int cmp, u64 batch, u64 width, u64 k, const u6
     if (!plain_use_fused(sh))
         return plain_composed(sh, n_bits, batch, planes, terms, out, s);
     const u64 dL = (n_bits + 63) / 64;
-    bool wide = dL % 2 == 0 && aligned16(out);
-    for (u32 j = 0; j < sh.w && wide && !sh.zero; ++j)
-        wide = aligned16(planes[j]);
+    const bool wide = wide_units(dL, out, ptr_array(planes, sh.zero ? 0 : sh.w));
     const u32 U = (u32)(wide ? dL / 2 : dL);
     return wide ? plain_fused<unit16>(sh, n_bits, batch, planes, terms, out, U, s)
                 : plain_fused<unit8>(sh, n_bits, batch, planes, terms, out, U, s);

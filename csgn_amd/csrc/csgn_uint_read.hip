@@ -14,13 +14,13 @@
 //
 // Fresh index planes (every s_k = 1), the case this kernel is built for: a term of the E stream is P[S], the AND of x_k
 // over S = ones(r) + the zero bits whose digit is 0.  A workgroup owns G elements, a slice of KC units of every term,
-// and one range of the E stream, for EVERY output plane: it builds the subset tables of §4.15 (one to three, the AND of
-// every subset of their planes) for its elements in LDS, decodes its range once into an LDS list of (S, r), and every
-// written unit is then 1-3 LDS reads ANDed with one unit of the table row -- a row every element reads, so it hits in
-// L2.  The table build and the decode are spent on all `w` outputs.  Lanes walk one output's stream with the unit
-// fastest, then the table term, the E index and the element, so one store instruction writes 64 consecutive units of
-// one plane.  Multi-term index planes take the walk and the digits per unit straight from the planes (correct, not
-// fast).
+// and one range of the E stream, for EVERY output plane: it builds the subset tables of §4.15 (csgn_device.h: one to
+// three, the AND of every subset of their planes) for its elements in LDS, decodes its range once into an LDS list of
+// (S, r), and every written unit is then 1-3 LDS reads ANDed with one unit of the table row -- a row every element
+// reads, so it hits in L2.  The table build and the decode are spent on all `w` outputs.  Lanes walk one output's
+// stream with the unit fastest, then the table term, the E index and the element, so one store instruction writes 64
+// consecutive units of one plane.  Multi-term index planes take the walk and the digits per unit straight from the
+// planes (correct, not fast).
 #include "csgn_device.h"
 #include "csgn_hip.h"
 
@@ -30,22 +30,9 @@ namespace csgn {
 
 namespace {
 
-constexpr u32 kMaxTables = 3;
 constexpr u64 kLdsBudget = 32768;       // bytes of subset tables per workgroup
 constexpr u32 kMaxRange = 2048;         // E-stream entries one workgroup decodes (8 KB of LDS)
 constexpr u64 kPartUnits = 8192;        // units a workgroup writes at least, where the shape has them
-constexpr u64 kTermLimit = 1ull << 62;
-
-__device__ inline unit16 read_one(unit16, u32 k, u32 U, u64 last_mask)
-{
-    unit16 v = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
-    if (k == U - 1u) {
-        v.z = (u32)last_mask;
-        v.w = (u32)(last_mask >> 32);
-    }
-    return v;
-}
-__device__ inline unit8 read_one(unit8, u32 k, u32 U, u64 last_mask) { return k == U - 1u ? last_mask : ~0ull; }
 
 // By value in the kernel arguments (uniform, scalar loads).  A workgroup is (element group, unit chunk, part): it owns
 // elements [group * G, + G), units [chunk * KC, + KC) of every term and entries [part * QP, + QP) of the E stream.
@@ -54,7 +41,7 @@ struct ReadArgs {
     const void *table[kReadMaxPlanes];
     void *out[kReadMaxPlanes];
     u32 t[kReadMaxPlanes];                                              // terms of table plane j
-    u32 tk_d[kReadMaxPlanes], tk_magic[kReadMaxPlanes], tk_shift[kReadMaxPlanes];   // t_j * KC as a FastDiv
+    FastDivTable<kReadMaxPlanes> tk;                                    // t_j * KC
     u64 F[kReadMaxIndex];       // prod over i < k of (2 s_i + 1): a whole subtree below bit k (saturated; read only
                                 // where the subtree lies below rows, so at most E)
     u32 s[kReadMaxIndex];
@@ -62,8 +49,8 @@ struct ReadArgs {
     u64 batch;                  // elements of this launch
     u32 E, last_row, v, w;
     u32 U, KC, G, QP, chunks, parts, nblocks, xcd;
-    u32 ntab, hb[kMaxTables + 1], tbase[kMaxTables];   // table k: planes [hb[k], hb[k+1]), at unit tbase[k] of the LDS
-    u32 lbase;                                         // byte offset of the decoded range in the LDS
+    SubsetTables tabs;
+    u32 lbase;                  // byte offset of the decoded range in the LDS
     FastDiv dKC, dQP;
 };
 
@@ -108,15 +95,7 @@ __global__ void __launch_bounds__(256) k_uint_read(ReadArgs a)
     const u32 q0 = part * a.QP, nq = min(a.QP, a.E - q0);
 
     if (Fresh) {
-        // entry 0 of every table is ONE; level b fills entries [2^b, 2^(b+1)) from [0, 2^b) and plane hb[k] + b
-        for (u32 tb = 0; tb < a.ntab; ++tb) {
-            const u32 h = a.hb[tb + 1] - a.hb[tb];
-            for (u32 x = threadIdx.x; x < a.G * a.KC; x += 256u) {
-                const u32 el = csgn_fastdiv(x, a.dKC), kk = x - el * a.KC;
-                tab[a.tbase[tb] + ((el << h) * a.KC) + kk] = read_one(Unit(), k0 + kk, a.U, a.last_mask);
-            }
-        }
-        // the range of the E stream: S in the low 16 bits, r in the high 16
+        // the range of the E stream: S in the low 16 bits, r in the high 16 (published by the tables' closing barrier)
         for (u32 i = threadIdx.x; i < nq; i += 256u) {
             u64 in;
             const u32 r = read_walk(a, q0 + i, in);
@@ -130,29 +109,11 @@ __global__ void __launch_bounds__(256) k_uint_read(ReadArgs a)
             }
             code[i] = S | (r << 16);
         }
-        for (u32 b = 0; b < a.hb[1]; ++b) {     // table 0 is the widest
-            __syncthreads();
-            for (u32 tb = 0; tb < a.ntab; ++tb) {
-                const u32 h = a.hb[tb + 1] - a.hb[tb];
-                if (b >= h)
-                    continue;
-                const Unit *p = reinterpret_cast<const Unit *>(a.index[a.hb[tb] + b]);
-                const u32 n = (a.G * a.KC) << b;
-                for (u32 x = threadIdx.x; x < n; x += 256u) {
-                    const u32 row = csgn_fastdiv(x, a.dKC), kk = x - row * a.KC;
-                    const u32 el = row >> b, s = (1u << b) | (row & ((1u << b) - 1u));
-                    if (el >= ne || kk >= kc)
-                        continue;
-                    const u32 at = a.tbase[tb] + ((el << h) | s) * a.KC + kk;
-                    tab[at] = tab[at - (1u << b) * a.KC] & p[(e0 + el) * a.U + k0 + kk];
-                }
-            }
-        }
-        __syncthreads();
+        subset_build(tab, a.tabs, a.index, a.G, a.KC, a.dKC, a.U, a.last_mask, e0, ne, k0, kc);
     }
 
     for (u32 j = 0; j < a.w; ++j) {
-        const FastDiv dtk = {a.tk_d[j], a.tk_magic[j], a.tk_shift[j]};
+        const FastDiv dtk = a.tk.at(j);
         const u32 tj = a.t[j];
         const u64 Tj = (u64)tj * a.E;
         const Unit *d = reinterpret_cast<const Unit *>(a.table[j]);
@@ -169,17 +130,13 @@ __global__ void __launch_bounds__(256) k_uint_read(ReadArgs a)
             Unit v;
             u32 r;
             if (Fresh) {
-                const u32 cd = code[qi], S = cd & 0xFFFFu;
+                const u32 cd = code[qi];
                 r = cd >> 16;
-                v = tab[a.tbase[0] + ((el << a.hb[1]) | (S & ((1u << a.hb[1]) - 1u))) * a.KC + kk];
-                for (u32 tb = 1; tb < a.ntab; ++tb) {
-                    const u32 h = a.hb[tb + 1] - a.hb[tb];
-                    v &= tab[a.tbase[tb] + ((el << h) | ((S >> a.hb[tb]) & ((1u << h) - 1u))) * a.KC + kk];
-                }
+                v = subset_and(tab, a.tabs, el, cd & 0xFFFFu, a.KC, kk);
             } else {
                 u64 in;
                 r = read_walk(a, q, in);
-                v = read_one(Unit(), k, a.U, a.last_mask);
+                v = one_unit(Unit(), k, a.U, a.last_mask);
                 for (u32 kb = a.v; kb-- > 0u;) {
                     const u64 s = a.s[kb], R = ((r >> kb) & 1u) ? s : s + 1u;
                     const u64 dg = in % R;
@@ -196,11 +153,11 @@ __global__ void __launch_bounds__(256) k_uint_read(ReadArgs a)
 
 // ------------------------------------------------------------------------------ host side
 
+// x * y, saturated at kTermLimit
 u64 sat_mul(u64 x, u64 y)
 {
-    unsigned long long p;
-    return __builtin_mul_overflow((unsigned long long)x, (unsigned long long)y, &p) || p >= kTermLimit ? kTermLimit
-                                                                                                       : (u64)p;
+    u64 p;
+    return term_mul(x, y, p) ? p : kTermLimit;
 }
 
 bool read_shape_ok(u64 v, const u64 *s, u64 rows, u64 w, const u64 *t)
@@ -215,10 +172,8 @@ bool read_shape_ok(u64 v, const u64 *s, u64 rows, u64 w, const u64 *t)
 
 bool read_use_fused()
 {
-    const int forced = tune(TUNE_UINT_READ_FUSED);
-    if (forced == 0 || forced == 1)
-        return forced == 1;
-    return true;              // one launch for every output: no shape measured where the composed form is faster
+    // by shape: one launch for every output, no shape measured where the composed form is faster
+    return tune_choose(TUNE_UINT_READ_FUSED, true);
 }
 
 template <typename Unit>
@@ -246,33 +201,16 @@ hipError_t read_fused(u64 n_bits, u64 batch, u64 v, const u64 *const *index, con
         sumt += t[j];
         maxt = std::max(maxt, t[j]);
     }
-    // subset tables: one up to 5 planes, two up to 10, three above; the low tables take the odd planes
-    u64 entries = 0;          // table units per element and unit of a term
-    if (fresh) {
-        a.ntab = v <= 5 ? 1 : v <= 10 ? 2 : 3;
-        a.hb[0] = 0;
-        for (u32 k = 0; k < a.ntab; ++k) {
-            const u32 h = ((u32)v - a.hb[k] + (a.ntab - k) - 1) / (a.ntab - k);
-            a.hb[k + 1] = a.hb[k] + h;
-            entries += 1ull << h;
-        }
-    }
-    // unit chunks: only when one element's tables at whole terms pass the budget
-    const u64 per_unit = entries * sizeof(Unit);
-    u32 chunks = 1;
-    if (fresh && per_unit * U > kLdsBudget)
-        chunks = (u32)((per_unit * U + kLdsBudget - 1) / kLdsBudget);
-    a.KC = (U + chunks - 1) / chunks;
-    a.chunks = (U + a.KC - 1) / a.KC;
+    SubsetPlan sp = subset_plan(fresh ? (u32)v : 0, U, (u32)sizeof(Unit), kLdsBudget);
+    a.KC = sp.KC;
+    a.chunks = sp.chunks;
     // elements per workgroup: enough to give it kPartUnits to write, as many as the tables allow
     const u64 elem_units = E * sumt * a.KC;
     u64 G = std::max<u64>(1, kPartUnits / elem_units);
-    if (fresh)
-        G = std::min<u64>(G, std::max<u64>(1, kLdsBudget / (per_unit * a.KC)));
-    G = std::min<u64>({G, batch, 64});
+    G = std::min<u64>({G, sp.max_G, batch, 64});
     G = std::max<u64>(G, 1);
     // parts of the E stream: each writes kPartUnits or four times its table build, and decodes at most kMaxRange
-    const u64 build = G * entries * a.KC;
+    const u64 build = G * sp.entries * a.KC;
     const u64 target = std::max<u64>(kPartUnits, 4 * build);
     u64 parts = std::max<u64>(1, G * elem_units / target);
     parts = std::max<u64>(parts, (E + kMaxRange - 1) / kMaxRange);
@@ -285,45 +223,29 @@ hipError_t read_fused(u64 n_bits, u64 batch, u64 v, const u64 *const *index, con
     a.G = (u32)std::max<u64>(G, 1);
     a.dKC = csgn_fastdiv_make(a.KC);
     a.dQP = csgn_fastdiv_make(a.QP);
-    for (u32 j = 0; j < w; ++j) {
-        const FastDiv d = csgn_fastdiv_make((u32)(t[j] * a.KC));
-        a.tk_d[j] = d.d;
-        a.tk_magic[j] = d.magic;
-        a.tk_shift[j] = d.shift;
-    }
+    for (u32 j = 0; j < w; ++j)
+        a.tk.set(j, (u32)(t[j] * a.KC));
     u32 lds = 0;
     if (fresh) {
-        u32 at = 0;
-        for (u32 k = 0; k < a.ntab; ++k) {
-            a.tbase[k] = at;
-            at += (u32)((a.G << (a.hb[k + 1] - a.hb[k])) * a.KC);
-        }
-        a.lbase = (at * (u32)sizeof(Unit) + 15u) & ~15u;
+        a.lbase = (sp.layout(a.G) + 15u) & ~15u;
         lds = a.lbase + a.QP * 4u;
     }
-    const u64 per_group = (u64)a.chunks * a.parts;
-    const u64 max_groups = std::max<u64>(1, kMaxBlocks256 / per_group);
-    const u64 groups = (batch + a.G - 1) / a.G;
+    a.tabs = sp.t;
     a.xcd = stream_xcd(batch * E * sumt * U);
-    for (u64 g0 = 0; g0 < groups; g0 += max_groups) {
-        const u64 ng = std::min(max_groups, groups - g0), e0 = g0 * a.G;
-        a.batch = std::min<u64>(batch - e0, ng * a.G);
+    return launch_groups(batch, a.G, (u64)a.chunks * a.parts, [&](u64 e0, u64 ne, u32 nblocks) {
+        a.batch = ne;
         for (u32 k = 0; k < v; ++k)
             a.index[k] = reinterpret_cast<const Unit *>(index[k]) + e0 * s[k] * U;
         for (u32 j = 0; j < w; ++j) {
             a.table[j] = table[j];
             a.out[j] = reinterpret_cast<Unit *>(out[j]) + e0 * t[j] * E * U;
         }
-        a.nblocks = (u32)(ng * per_group);
+        a.nblocks = nblocks;
         if (fresh)
             k_uint_read<Unit, true><<<dim3(a.nblocks), 256, lds, st>>>(a);
         else
             k_uint_read<Unit, false><<<dim3(a.nblocks), 256, 0, st>>>(a);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess)
-            return e;
-    }
-    return hipSuccess;
+    });
 }
 
 // The composed form, row by row through the tuned launchers: EQ(x, r) by csgn_uint_plain into a temporary, row r of
@@ -416,11 +338,7 @@ hipError_t uint_read(u64 n_bits, u64 batch, u64 v, const u64 *const *index, cons
     if (!read_use_fused())
         return read_composed(n_bits, batch, v, index, s, rows, w, table, t, out, E, stream);
     const u64 dL = (n_bits + 63) / 64;
-    bool wide = dL % 2 == 0;
-    for (u64 k = 0; k < v && wide; ++k)
-        wide = aligned16(index[k]);
-    for (u64 j = 0; j < w && wide; ++j)
-        wide = aligned16(table[j]) && aligned16(out[j]);
+    const bool wide = wide_units(dL, ptr_array(index, v), ptr_array(table, w), ptr_array(out, w));
     const u32 U = (u32)(wide ? dL / 2 : dL);
     return wide ? read_fused<unit16>(n_bits, batch, v, index, s, rows, w, table, t, out, E, U, stream)
                 : read_fused<unit8>(n_bits, batch, v, index, s, rows, w, table, t, out, E, U, stream);
