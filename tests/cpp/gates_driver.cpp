@@ -3,30 +3,11 @@
 //   gates_driver batch     CiphertextBatch gates, uniform and ragged (compact() output)
 //   gates_driver circuit   BatchCircuit: 4-bit equality and 6-bit unsigned less-than over 1000 random pairs
 // Prints "<mode> ok" and exits 0, or names the first mismatch and exits 1.
-#include "certFHE.h"
-
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
+#include "driver.h"
 
 using namespace certFHE;
 
 namespace {
-
-int fails = 0;
-
-void expect(bool ok, const std::string &what)
-{
-    if (!ok && fails++ < 10)
-        printf("MISMATCH %s\n", what.c_str());
-}
-
-bool sameWords(const Ciphertext &x, const Ciphertext &y)
-{
-    return x.getLen() == y.getLen() && memcmp(x.getValues(), y.getValues(), x.getLen() * 8) == 0;
-}
 
 // the ONE term from its words, not through Gates.cpp
 Ciphertext oneByHand(const Context &ctx)
@@ -74,14 +55,6 @@ int single()
     return 0;
 }
 
-std::vector<unsigned char> randomBits(size_t n)
-{
-    std::vector<unsigned char> v(n);
-    for (size_t i = 0; i < n; ++i)
-        v[i] = (unsigned char)(rand() & 1);
-    return v;
-}
-
 void checkBatch(const CiphertextBatch &r, SecretKey &key, const std::vector<unsigned char> &want, const std::string &what)
 {
     const std::vector<unsigned char> got = r.decrypt(key);
@@ -89,16 +62,6 @@ void checkBatch(const CiphertextBatch &r, SecretKey &key, const std::vector<unsi
     for (size_t i = 0; ok && i < want.size(); ++i)
         ok = got[i] == want[i];
     expect(ok, what);
-}
-
-bool sameBatchWords(const CiphertextBatch &x, const CiphertextBatch &y)
-{
-    if (x.size() != y.size())
-        return false;
-    for (uint64_t i = 0; i < x.size(); ++i)
-        if (!sameWords(x.at(i), y.at(i)))
-            return false;
-    return true;
 }
 
 int batch()
@@ -216,27 +179,5 @@ int circuit()
 
 int main(int argc, char **argv)
 {
-    const std::string mode = argc > 1 ? argv[1] : "";
-    srand(12345);
-    try {
-        if (mode == "single")
-            single();
-        else if (mode == "batch")
-            batch();
-        else if (mode == "circuit")
-            circuit();
-        else {
-            fprintf(stderr, "usage: gates_driver single|batch|circuit\n");
-            return 2;
-        }
-    } catch (const std::exception &e) {
-        printf("EXCEPTION %s\n", e.what());
-        return 1;
-    }
-    if (fails) {
-        printf("%d mismatches\n", fails);
-        return 1;
-    }
-    printf("%s ok\n", mode.c_str());
-    return 0;
+    return runModes(argc, argv, 12345, "gates_driver", {{"single", single}, {"batch", batch}, {"circuit", circuit}});
 }

@@ -7,31 +7,13 @@
 //                         is built from n per-element copies through pack()
 //   gather_driver throws  bad indices, ranges and shapes throw std::out_of_range / std::invalid_argument
 // Prints "<mode> ok" and exits 0, or names the first mismatch and exits 1.
-#include "certFHE.h"
+#include "driver.h"
 
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <stdexcept>
-#include <string>
-#include <vector>
 
 using namespace certFHE;
 
 namespace {
-
-int fails = 0;
-
-void expect(bool ok, const std::string &what)
-{
-    if (!ok && fails++ < 10)
-        printf("MISMATCH %s\n", what.c_str());
-}
-
-bool sameWords(const Ciphertext &a, const Ciphertext &b)
-{
-    return a.getLen() == b.getLen() && (a.getLen() == 0 || memcmp(a.getValues(), b.getValues(), a.getLen() * 8) == 0);
-}
 
 // out[e] is a copy of src[from[e]], word for word
 void expectMoved(const CiphertextBatch &out, const CiphertextBatch &src, const std::vector<uint64_t> &from,
@@ -44,14 +26,6 @@ void expectMoved(const CiphertextBatch &out, const CiphertextBatch &src, const s
     for (uint64_t e = 0; e < from.size() && same; ++e)
         same = out.termsOf(e) == src.termsOf(from[e]) && sameWords(out.at(e), src.at(from[e]));
     expect(same, what + ": words");
-}
-
-std::vector<unsigned char> randomBits(size_t n)
-{
-    std::vector<unsigned char> b(n);
-    for (auto &x : b)
-        x = (unsigned char)(rand() & 1);
-    return b;
 }
 
 std::vector<uint64_t> randomIndices(size_t n, uint64_t below)
@@ -182,17 +156,6 @@ int query()
     return 0;
 }
 
-template <typename E, typename F>
-bool throws(F f)
-{
-    try {
-        f();
-    } catch (const E &) {
-        return true;
-    }
-    return false;
-}
-
 int throwsMode()
 {
     Context ctx(1247, 16);
@@ -226,27 +189,5 @@ int throwsMode()
 
 int main(int argc, char **argv)
 {
-    const std::string mode = argc > 1 ? argv[1] : "";
-    srand(4711);
-    try {
-        if (mode == "move")
-            move();
-        else if (mode == "query")
-            query();
-        else if (mode == "throws")
-            throwsMode();
-        else {
-            fprintf(stderr, "usage: gather_driver move|query|throws\n");
-            return 2;
-        }
-    } catch (const std::exception &e) {
-        printf("EXCEPTION %s\n", e.what());
-        return 1;
-    }
-    if (fails) {
-        printf("%d mismatches\n", fails);
-        return 1;
-    }
-    printf("%s ok\n", mode.c_str());
-    return 0;
+    return runModes(argc, argv, 4711, "gather_driver", {{"move", move}, {"query", query}, {"throws", throwsMode}});
 }

@@ -5,44 +5,14 @@
 //   uint_driver encrypt   reproducible encrypt == CiphertextBatch::encrypt plane by plane; argument checks
 //   uint_driver oversize  a width whose steps exceed 2^31 words per element throws before anything is allocated
 // Prints "<mode> ok" and exits 0, or names the first mismatch and exits 1.
-#include "certFHE.h"
+#include "driver.h"
 
 #include <chrono>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <stdexcept>
-#include <string>
-#include <vector>
 
 using namespace certFHE;
 
 namespace {
-
-int fails = 0;
-
-void expect(bool ok, const std::string &what)
-{
-    if (!ok && fails++ < 10)
-        printf("MISMATCH %s\n", what.c_str());
-}
-
-bool sameWords(const Ciphertext &x, const Ciphertext &y)
-{
-    return x.getLen() == y.getLen() && memcmp(x.getValues(), y.getValues(), x.getLen() * 8) == 0;
-}
-
-bool sameBatchWords(const CiphertextBatch &x, const CiphertextBatch &y)
-{
-    if (x.size() != y.size())
-        return false;
-    for (uint64_t i = 0; i < x.size(); ++i)
-        if (!sameWords(x.at(i), y.at(i)))
-            return false;
-    return true;
-}
-
-uint64_t rnd(unsigned w) { return (((uint64_t)rand() << 31) ^ (uint64_t)rand()) & (w == 64 ? ~0ull : (1ull << w) - 1); }
 
 // -- the definitions of UInt.h, composed by hand from the batch operators and Gates.h
 CiphertextBatch ones(const Context &ctx, uint64_t n) { return constantBatch(ctx, std::vector<unsigned char>(n, 1)); }
@@ -93,11 +63,6 @@ void checkBits(const CiphertextBatch &r, SecretKey &key, const std::vector<uint6
     expect(ok, what);
 }
 
-void checkValues(const UIntBatch &r, SecretKey &key, const std::vector<uint64_t> &want, const std::string &what)
-{
-    expect(r.decrypt(key) == want, what);
-}
-
 void checkPlanes(const UIntBatch &r, const std::vector<CiphertextBatch> &want, const std::string &what)
 {
     bool ok = r.width() == want.size();
@@ -127,15 +92,15 @@ void checkAll(const UIntBatch &a, const UIntBatch &b, const CiphertextBatch &s, 
     }
     const UIntBatch rs = a + b, rd = a - b, rsel = select(s, a, b);
     const CiphertextBatch req = equalTo(a, b), rlt = lessThan(a, b), rgt = greaterThan(a, b);
-    checkValues(rs, key, sum, "add" + tag);
-    checkValues(rd, key, diff, "sub" + tag);
+    checkValues(rs.decrypt(key), sum, "add" + tag);
+    checkValues(rd.decrypt(key), diff, "sub" + tag);
     checkBits(req, key, eq, "equalTo" + tag);
     checkBits(notEqualTo(a, b), key, ne, "notEqualTo" + tag);
     checkBits(rlt, key, lt, "lessThan" + tag);
     checkBits(lessEqual(a, b), key, le, "lessEqual" + tag);
     checkBits(rgt, key, gt, "greaterThan" + tag);
     checkBits(greaterEqual(a, b), key, ge, "greaterEqual" + tag);
-    checkValues(rsel, key, sel, "select" + tag);
+    checkValues(rsel.decrypt(key), sel, "select" + tag);
     if (!words)
         return;
     checkPlanes(rs, refAddSub(a, b, false), "add words" + tag);
@@ -221,22 +186,9 @@ int ragged()
         checkAll(a, b, CiphertextBatch::encrypt(key, low(in.vs), 30), key, in.va, in.vb, in.vs, w, true,
                  " ragged w=" + std::to_string(w));
         // compact() of a whole integer keeps its value
-        checkValues(a.compact(), key, in.va, "compact" + std::to_string(w));
+        checkValues(a.compact().decrypt(key), in.va, "compact" + std::to_string(w));
     }
     return 0;
-}
-
-template <typename F>
-bool throwsInvalid(F f)
-{
-    try {
-        f();
-    } catch (const std::invalid_argument &) {
-        return true;
-    } catch (...) {
-        return false;
-    }
-    return false;
 }
 
 int encrypt()
@@ -254,25 +206,28 @@ int encrypt()
         expect(sameBatchWords(a.plane(j), CiphertextBatch::encrypt(key, bits, 99, (uint64_t)j * count)),
                "plane " + std::to_string(j));
     }
-    checkValues(a, key, in.va, "decrypt");
-    checkValues(UIntBatch::encrypt(key, in.va, 13), key, in.va, "OS-keyed encrypt");
-    checkValues(UIntBatch::constant(ctx, in.va, 13), key, in.va, "constant");
+    checkValues(a.decrypt(key), in.va, "decrypt");
+    checkValues(UIntBatch::encrypt(key, in.va, 13).decrypt(key), in.va, "OS-keyed encrypt");
+    checkValues(UIntBatch::constant(ctx, in.va, 13).decrypt(key), in.va, "constant");
     std::vector<uint64_t> big(3, ~0ull);
-    checkValues(UIntBatch::encrypt(key, big, 64, 3), key, big, "64-bit values");
+    checkValues(UIntBatch::encrypt(key, big, 64, 3).decrypt(key), big, "64-bit values");
     // argument checks
-    expect(throwsInvalid([&] { UIntBatch::encrypt(key, in.va, 0); }), "width 0");
-    expect(throwsInvalid([&] { UIntBatch::encrypt(key, in.va, 65, 1); }), "width 65");
-    expect(throwsInvalid([&] { UIntBatch::encrypt(key, std::vector<uint64_t>(1, 8), 3, 1); }), "value >= 2^width");
-    expect(throwsInvalid([&] { UIntBatch::constant(ctx, std::vector<uint64_t>(1, 2), 1); }), "constant >= 2^width");
-    expect(throwsInvalid([&] { UIntBatch::fromPlanes(std::vector<CiphertextBatch>()); }), "no planes");
+    expect(throws<std::invalid_argument>([&] { UIntBatch::encrypt(key, in.va, 0); }), "width 0");
+    expect(throws<std::invalid_argument>([&] { UIntBatch::encrypt(key, in.va, 65, 1); }), "width 65");
+    expect(throws<std::invalid_argument>([&] { UIntBatch::encrypt(key, std::vector<uint64_t>(1, 8), 3, 1); }),
+           "value >= 2^width");
+    expect(throws<std::invalid_argument>([&] { UIntBatch::constant(ctx, std::vector<uint64_t>(1, 2), 1); }),
+           "constant >= 2^width");
+    expect(throws<std::invalid_argument>([&] { UIntBatch::fromPlanes(std::vector<CiphertextBatch>()); }), "no planes");
     const UIntBatch b12 = UIntBatch::encrypt(key, std::vector<uint64_t>(count, 1), 12, 1);
     const UIntBatch c13 = UIntBatch::encrypt(key, std::vector<uint64_t>(count - 1, 1), 13, 1);
     const UIntBatch d13 = UIntBatch::encrypt(key2, std::vector<uint64_t>(count, 1), 13, 1);
-    expect(throwsInvalid([&] { a + b12; }), "width mismatch");
-    expect(throwsInvalid([&] { a - c13; }), "count mismatch");
-    expect(throwsInvalid([&] { equalTo(a, d13); }), "context mismatch");
-    expect(throwsInvalid([&] { select(c13.plane(0), a, a); }), "selector count mismatch");
-    expect(throwsInvalid([&] { UIntBatch::fromPlanes(std::vector<CiphertextBatch>(1, c13.plane(0))) + a; }),
+    expect(throws<std::invalid_argument>([&] { a + b12; }), "width mismatch");
+    expect(throws<std::invalid_argument>([&] { a - c13; }), "count mismatch");
+    expect(throws<std::invalid_argument>([&] { equalTo(a, d13); }), "context mismatch");
+    expect(throws<std::invalid_argument>([&] { select(c13.plane(0), a, a); }), "selector count mismatch");
+    expect(throws<std::invalid_argument>(
+               [&] { UIntBatch::fromPlanes(std::vector<CiphertextBatch>(1, c13.plane(0))) + a; }),
            "fromPlanes width mismatch");
     bool caught = false;
     try {
@@ -297,11 +252,11 @@ int oversize()
         v[i] = rnd(24);
     const UIntBatch a = UIntBatch::encrypt(key, v, 24, 1), b = UIntBatch::encrypt(key, v, 24, 2);
     const auto t0 = std::chrono::steady_clock::now();
-    expect(throwsInvalid([&] { equalTo(a, b); }), "equalTo");
-    expect(throwsInvalid([&] { notEqualTo(a, b); }), "notEqualTo");
-    expect(throwsInvalid([&] { lessThan(a, b); }), "lessThan");
-    expect(throwsInvalid([&] { greaterEqual(a, b); }), "greaterEqual");
-    expect(throwsInvalid([&] { a - b; }), "operator-");
+    expect(throws<std::invalid_argument>([&] { equalTo(a, b); }), "equalTo");
+    expect(throws<std::invalid_argument>([&] { notEqualTo(a, b); }), "notEqualTo");
+    expect(throws<std::invalid_argument>([&] { lessThan(a, b); }), "lessThan");
+    expect(throws<std::invalid_argument>([&] { greaterEqual(a, b); }), "greaterEqual");
+    expect(throws<std::invalid_argument>([&] { a - b; }), "operator-");
     const double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     expect(s < 1.0, "the size checks ran before any launch (" + std::to_string(s) + " s)");
     return 0;
@@ -311,29 +266,6 @@ int oversize()
 
 int main(int argc, char **argv)
 {
-    const std::string mode = argc > 1 ? argv[1] : "";
-    srand(4242);
-    try {
-        if (mode == "ops")
-            ops();
-        else if (mode == "ragged")
-            ragged();
-        else if (mode == "encrypt")
-            encrypt();
-        else if (mode == "oversize")
-            oversize();
-        else {
-            fprintf(stderr, "usage: uint_driver ops|ragged|encrypt|oversize\n");
-            return 2;
-        }
-    } catch (const std::exception &e) {
-        printf("EXCEPTION %s\n", e.what());
-        return 1;
-    }
-    if (fails) {
-        printf("%d mismatches\n", fails);
-        return 1;
-    }
-    printf("%s ok\n", mode.c_str());
-    return 0;
+    return runModes(argc, argv, 4242, "uint_driver",
+                    {{"ops", ops}, {"ragged", ragged}, {"encrypt", encrypt}, {"oversize", oversize}});
 }

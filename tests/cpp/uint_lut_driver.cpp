@@ -7,41 +7,14 @@
 //                             same words; every word == the definition; decryptions == the table
 //   uint_lut_driver oversize  a lookup past 2^31 words per element throws before anything is allocated; bad tables throw
 // Prints "<mode> ok" and exits 0, or names the first mismatch and exits 1.
-#include "certFHE.h"
+#include "driver.h"
 
 #include <chrono>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <stdexcept>
-#include <string>
-#include <vector>
 
 using namespace certFHE;
 
 namespace {
-
-int fails = 0;
-
-void expect(bool ok, const std::string &what)
-{
-    if (!ok && fails++ < 10)
-        printf("MISMATCH %s\n", what.c_str());
-}
-
-bool sameBatchWords(const CiphertextBatch &x, const CiphertextBatch &y)
-{
-    if (x.size() != y.size())
-        return false;
-    for (uint64_t i = 0; i < x.size(); ++i) {
-        const Ciphertext a = x.at(i), b = y.at(i);
-        if (a.getLen() != b.getLen() || memcmp(a.getValues(), b.getValues(), a.getLen() * 8) != 0)
-            return false;
-    }
-    return true;
-}
-
-uint64_t rnd(unsigned w) { return (((uint64_t)rand() << 31) ^ (uint64_t)rand()) & ((1ull << w) - 1); }
 
 std::vector<uint64_t> aesSbox()
 {
@@ -95,26 +68,6 @@ UIntBatch definition(const UIntBatch &a, const LookupTable &f)
         out.push_back(acc.empty() ? constantBatch(a.context(), std::vector<unsigned char>(a.size(), 0)) : acc[0]);
     }
     return UIntBatch::fromPlanes(out);
-}
-
-bool sameWords(const UIntBatch &x, const UIntBatch &y)
-{
-    if (x.width() != y.width())
-        return false;
-    for (unsigned j = 0; j < x.width(); ++j)
-        if (!sameBatchWords(x.plane(j), y.plane(j)))
-            return false;
-    return true;
-}
-
-void checkValues(const std::vector<uint64_t> &got, const std::vector<uint64_t> &want, const std::string &tag)
-{
-    for (size_t i = 0; i < want.size(); ++i)
-        if (got[i] != want[i]) {
-            expect(false, tag + " element " + std::to_string(i) + ": " + std::to_string(got[i]) + " != " +
-                              std::to_string(want[i]));
-            return;
-        }
 }
 
 int sbox()
@@ -286,29 +239,6 @@ int oversize()
 
 int main(int argc, char **argv)
 {
-    const std::string mode = argc > 1 ? argv[1] : "";
-    srand(4711);
-    try {
-        if (mode == "sbox")
-            sbox();
-        else if (mode == "two")
-            two();
-        else if (mode == "ragged")
-            ragged();
-        else if (mode == "oversize")
-            oversize();
-        else {
-            fprintf(stderr, "usage: uint_lut_driver sbox|two|ragged|oversize\n");
-            return 2;
-        }
-    } catch (const std::exception &e) {
-        printf("EXCEPTION %s\n", e.what());
-        return 1;
-    }
-    if (fails) {
-        printf("%d mismatches\n", fails);
-        return 1;
-    }
-    printf("%s ok\n", mode.c_str());
-    return 0;
+    return runModes(argc, argv, 4711, "uint_lut_driver",
+                    {{"sbox", sbox}, {"two", two}, {"ragged", ragged}, {"oversize", oversize}});
 }

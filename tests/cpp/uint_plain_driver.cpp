@@ -6,41 +6,14 @@
 //                               the same words; every word == the definition; decryptions == clear comparisons
 //   uint_plain_driver oversize  a comparison past 2^31 words per element throws before anything is allocated
 // Prints "<mode> ok" and exits 0, or names the first mismatch and exits 1.
-#include "certFHE.h"
+#include "driver.h"
 
 #include <chrono>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <stdexcept>
-#include <string>
-#include <vector>
 
 using namespace certFHE;
 
 namespace {
-
-int fails = 0;
-
-void expect(bool ok, const std::string &what)
-{
-    if (!ok && fails++ < 10)
-        printf("MISMATCH %s\n", what.c_str());
-}
-
-bool sameBatchWords(const CiphertextBatch &x, const CiphertextBatch &y)
-{
-    if (x.size() != y.size())
-        return false;
-    for (uint64_t i = 0; i < x.size(); ++i) {
-        const Ciphertext a = x.at(i), b = y.at(i);
-        if (a.getLen() != b.getLen() || memcmp(a.getValues(), b.getValues(), a.getLen() * 8) != 0)
-            return false;
-    }
-    return true;
-}
-
-uint64_t rnd(unsigned w) { return (((uint64_t)rand() << 31) ^ (uint64_t)rand()) & ((1ull << w) - 1); }
 
 enum Cmp { EQ, NE, LT, LE, GT, GE };
 const char *kNames[] = {"equalTo", "notEqualTo", "lessThan", "lessEqual", "greaterThan", "greaterEqual"};
@@ -229,27 +202,5 @@ int oversize()
 
 int main(int argc, char **argv)
 {
-    const std::string mode = argc > 1 ? argv[1] : "";
-    srand(4711);
-    try {
-        if (mode == "ops")
-            ops();
-        else if (mode == "ragged")
-            ragged();
-        else if (mode == "oversize")
-            oversize();
-        else {
-            fprintf(stderr, "usage: uint_plain_driver ops|ragged|oversize\n");
-            return 2;
-        }
-    } catch (const std::exception &e) {
-        printf("EXCEPTION %s\n", e.what());
-        return 1;
-    }
-    if (fails) {
-        printf("%d mismatches\n", fails);
-        return 1;
-    }
-    printf("%s ok\n", mode.c_str());
-    return 0;
+    return runModes(argc, argv, 4711, "uint_plain_driver", {{"ops", ops}, {"ragged", ragged}, {"oversize", oversize}});
 }

@@ -8,52 +8,15 @@
 //   uint_read_driver oversize  a read past 2^31 words per element throws before anything is allocated; bad row counts
 //                              and mismatched contexts throw
 // Prints "<mode> ok" and exits 0, or names the first mismatch and exits 1.
-#include "certFHE.h"
+#include "driver.h"
 
 #include <algorithm>
 #include <chrono>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <stdexcept>
-#include <string>
-#include <vector>
 
 using namespace certFHE;
 
 namespace {
-
-int fails = 0;
-
-void expect(bool ok, const std::string &what)
-{
-    if (!ok && fails++ < 10)
-        printf("MISMATCH %s\n", what.c_str());
-}
-
-bool sameBatchWords(const CiphertextBatch &x, const CiphertextBatch &y)
-{
-    if (x.size() != y.size())
-        return false;
-    for (uint64_t i = 0; i < x.size(); ++i) {
-        const Ciphertext a = x.at(i), b = y.at(i);
-        if (a.getLen() != b.getLen() || memcmp(a.getValues(), b.getValues(), a.getLen() * 8) != 0)
-            return false;
-    }
-    return true;
-}
-
-bool sameWords(const UIntBatch &x, const UIntBatch &y)
-{
-    if (x.width() != y.width())
-        return false;
-    for (unsigned j = 0; j < x.width(); ++j)
-        if (!sameBatchWords(x.plane(j), y.plane(j)))
-            return false;
-    return true;
-}
-
-uint64_t rnd(unsigned w) { return (((uint64_t)rand() << 31) ^ (uint64_t)rand()) & ((1ull << w) - 1); }
 
 // the definition of UInt.h, by hand from the batch operators
 CiphertextBatch definition(const CiphertextBatch &table, const UIntBatch &index)
@@ -75,16 +38,6 @@ UIntBatch definition(const UIntBatch &table, const UIntBatch &index)
     for (unsigned j = 0; j < table.width(); ++j)
         out.push_back(definition(table.plane(j), index));
     return UIntBatch::fromPlanes(out);
-}
-
-void checkValues(const std::vector<uint64_t> &got, const std::vector<uint64_t> &want, const std::string &tag)
-{
-    for (size_t i = 0; i < want.size(); ++i)
-        if (got[i] != want[i]) {
-            expect(false, tag + " element " + std::to_string(i) + ": " + std::to_string(got[i]) + " != " +
-                              std::to_string(want[i]));
-            return;
-        }
 }
 
 int words()
@@ -238,27 +191,6 @@ int oversize()
 
 int main(int argc, char **argv)
 {
-    const std::string mode = argc > 1 ? argv[1] : "";
-    srand(4713);
-    try {
-        if (mode == "words")
-            words();
-        else if (mode == "ragged")
-            ragged();
-        else if (mode == "oversize")
-            oversize();
-        else {
-            fprintf(stderr, "usage: uint_read_driver words|ragged|oversize\n");
-            return 2;
-        }
-    } catch (const std::exception &e) {
-        printf("EXCEPTION %s\n", e.what());
-        return 1;
-    }
-    if (fails) {
-        printf("%d mismatches\n", fails);
-        return 1;
-    }
-    printf("%s ok\n", mode.c_str());
-    return 0;
+    return runModes(argc, argv, 4713, "uint_read_driver",
+                    {{"words", words}, {"ragged", ragged}, {"oversize", oversize}});
 }

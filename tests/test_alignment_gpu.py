@@ -14,22 +14,15 @@ import pytest
 import torch
 
 from oracle.binding import glibc_draws
-from tests.test_gates_cpu import GATES, expected_terms as gate_terms, np_add, np_gate, np_mul, rand_terms
-from tests.test_gpu_parity import csr, explicit_randomness, make_key, planted
-from tests.test_uint_cpu import ADD_FULL, ADD_HALF, STEPS, np_step
-from tests.test_uint_plain_cpu import EQ, GE, GT, LE, LT, NE, np_plain, u64s
+from tests.model import (ADD_FULL, ADD_HALF, EQ, GATES, GE, GT, LE, LT, NE, STEPS, const_term, csr, explicit_randomness,
+                         gate_terms, hip, make_key, np_add, np_gate, np_mul, np_plain, np_step, planted, rand_terms,
+                         u64s)
 
 pytestmark = pytest.mark.gpu
 
 NS = [1247, 4096, 128, 1300]                # even dL (20, 64, 2) and one odd (21)
 KEY_D = {1247: 16, 4096: 32, 128: 8, 1300: 4}
 GUARD = 0x5A5A5A5A5A5A5A5A
-
-
-@pytest.fixture(scope="module")
-def hip():
-    from csgn_amd.batch import HipPath
-    return HipPath(0)
 
 
 def patterns(names):
@@ -471,7 +464,6 @@ def test_compact_ragged(hip, oracle, n, kind):
 
 @pytest.mark.parametrize("n", NS)
 def test_const_fill(hip, n):
-    from tests.test_gates_cpu import const_term
     batch = 333
     plain = np.random.default_rng(n).integers(0, 256, batch).astype(np.uint8)
     want = np.stack([const_term(n, p & 1) for p in plain]).ravel()

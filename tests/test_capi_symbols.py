@@ -8,14 +8,9 @@ import re
 import numpy as np
 import pytest
 
+from tests.model import lib
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from csgn_amd import build, capi
-    build.build_hip()
-    return capi.load_library()
 
 
 def declared_symbols():

@@ -8,79 +8,17 @@ any GPU is involved.  The GPU tests (tests/test_gpu_parity.py::test_circuit_comp
 real kernels.  Reference semantics: src/Ciphertext.cpp:107-122 (add = concatenation), :146-163 (all-pairs AND),
 src/SecretKey.cpp:104-147 (decrypt = XOR over terms of AND over key positions)."""
 import ctypes as C
-import json
 
 import numpy as np
 import pytest
 
 from csgn_amd import capi
 from csgn_amd.capi import check
+from tests.model import Described, config5, lib, random_circuit
 
 REUSE, PLACE, FUSE, PUSHDOWN, HOIST = 1, 2, 4, 8, 16
 CORE, ALL = 7, 23
 FOREVER = 2 ** 31 - 1
-FAKE_PTR = 0x1000                                   # a device pointer the host passes never read
-
-
-@pytest.fixture(scope="module")
-def lib():
-    return capi.load_library()
-
-
-class Described:
-    """A circuit described through the C ABI and, beside it, the same description as Python tuples."""
-
-    def __init__(self, lib, n, batch, mask_ptr=FAKE_PTR):
-        self.lib, self.n, self.batch, self.mask_ptr = lib, n, batch, mask_ptr
-        self.dl = int(lib.csgn_default_len(n))
-        self.c = C.c_void_p()
-        check(lib.csgn_circuit_create(n, batch, C.byref(self.c)))
-        self.terms = []                             # per value
-        self.nodes = []                             # ("in",) / ("add", a, b) / ("mul", a, b) per value
-        self.decrypts = []                          # value ids, in bits_id order
-        self.outputs = set()
-
-    def close(self):
-        self.lib.csgn_circuit_destroy(self.c)
-
-    def _new(self, fn, *args):
-        v = C.c_uint32()
-        check(fn(self.c, *args, C.byref(v)))
-        return v.value
-
-    def input(self, terms=1):
-        v = self._new(self.lib.csgn_circuit_input, terms)
-        self.terms.append(terms)
-        self.nodes.append(("in",))
-        return v
-
-    def add(self, a, b):
-        v = self._new(self.lib.csgn_circuit_add, a, b)
-        self.terms.append(self.terms[a] + self.terms[b])
-        self.nodes.append(("add", a, b))
-        return v
-
-    def mul(self, a, b):
-        v = self._new(self.lib.csgn_circuit_mul, a, b)
-        self.terms.append(self.terms[a] * self.terms[b])
-        self.nodes.append(("mul", a, b))
-        return v
-
-    def decrypt(self, a):
-        bid = self._new(self.lib.csgn_circuit_decrypt, a, self.mask_ptr)
-        assert bid == len(self.decrypts)
-        self.decrypts.append(a)
-        return bid
-
-    def output(self, v):
-        check(self.lib.csgn_circuit_output(self.c, v))
-        self.outputs.add(v)
-
-    def plan(self, flags):
-        check(self.lib.csgn_circuit_optimize(self.c, flags))
-        buf = C.create_string_buffer(1 << 22)
-        check(self.lib.csgn_circuit_plan_json(self.c, buf, len(buf)))
-        return json.loads(buf.value.decode())
 
 
 def evaluate(d, inputs):
@@ -97,7 +35,7 @@ def evaluate(d, inputs):
     return vals
 
 
-def decrypt_bits(vals, mask):
+def decrypt_masked(vals, mask):
     hits = np.all((vals & mask) == mask, axis=2)               # [batch, terms]
     return (hits.sum(axis=1) & 1).astype(np.uint8)
 
@@ -169,11 +107,11 @@ def execute(d, plan, inputs, mask):
             def ev(ei):
                 e = plan["exprs"][ei]
                 if e["kind"] < 0:
-                    return decrypt_bits(read(e["value"]), mask)
+                    return decrypt_masked(read(e["value"]), mask)
                 l, r = ev(e["l"]), ev(e["r"])
                 return (l & r) if e["kind"] == 1 else (l ^ r)
             bid = sum(1 for o in plan["ops"][:i] if o["kind"] == 2)
-            bits[bid] = ev(op["expr"]) if op["expr"] >= 0 else decrypt_bits(read(op["a"]), mask)
+            bits[bid] = ev(op["expr"]) if op["expr"] >= 0 else decrypt_masked(read(op["a"]), mask)
     return block, bits, read
 
 
@@ -185,30 +123,6 @@ def check_regions(plan):
         for b in regs[i + 1:]:
             if a["from"] <= b["to"] and b["from"] <= a["to"]:
                 assert a["at"] + a["bytes"] <= b["at"] or b["at"] + b["bytes"] <= a["at"], (a, b)
-
-
-def random_circuit(lib, seed, n, batch, mask_ptr=FAKE_PTR, max_terms=400):
-    rng = np.random.default_rng(seed)
-    d = Described(lib, n, batch, mask_ptr)
-    for _ in range(int(rng.integers(2, 6))):
-        d.input(int(rng.integers(1, 4)))
-    for _ in range(int(rng.integers(3, 14))):
-        k = len(d.terms)
-        # mostly chains (the newest value and something else), sometimes two old values: shared sub-expressions
-        a = k - 1 if rng.random() < 0.6 else int(rng.integers(0, k))
-        b = int(rng.integers(0, k))
-        if rng.random() < 0.45 and d.terms[a] * d.terms[b] <= max_terms:
-            d.mul(a, b)
-        elif d.terms[a] + d.terms[b] <= max_terms:
-            d.add(a, b)
-    k = len(d.terms)
-    for v in sorted(set(int(x) for x in rng.integers(0, k, size=int(rng.integers(1, 4))))):
-        d.decrypt(v)
-    if rng.random() < 0.5:
-        d.decrypt(k - 1)
-    for v in sorted(set(int(x) for x in rng.integers(0, k, size=int(rng.integers(0, 3))))):
-        d.output(v)
-    return d
 
 
 @pytest.mark.parametrize("flags", [ALL, CORE, REUSE, PLACE, FUSE, HOIST, REUSE | HOIST, PLACE | FUSE, ALL | PUSHDOWN, REUSE | PUSHDOWN])
@@ -230,7 +144,7 @@ def test_compiled_plans_of_random_circuits_compute_what_the_tape_computes(lib, f
             want = evaluate(d, inputs)
             block, bits, read = execute(d, plan, inputs, mask)
             for bid, v in enumerate(d.decrypts):
-                assert np.array_equal(bits[bid], decrypt_bits(want[v], mask)), (seed, bid)
+                assert np.array_equal(bits[bid], decrypt_masked(want[v], mask)), (seed, bid)
             for v in d.outputs | {i for i, nd in enumerate(d.nodes) if nd[0] == "in"}:
                 assert plan["values"][v]["addressable"], (seed, v)
                 assert np.array_equal(read(v), want[v]), (seed, v)
@@ -270,19 +184,6 @@ def test_tape_mode_keeps_every_value_in_a_region_of_its_own(lib):
         assert all(r["to"] == FOREVER or r["from"] == r["to"] for r in plan["regions"])
     finally:
         d.close()
-
-
-def config5(lib, n, batch, levels=16, mask_ptr=FAKE_PTR):
-    d = Described(lib, n, batch, mask_ptr)
-    ins = [d.input(1) for _ in range(1 + levels // 2 + 2 * (levels // 2))]
-    x, k = ins[0], 1
-    for level in range(1, levels + 1):
-        if level % 2:
-            x = d.add(x, ins[k]); k += 1
-        else:
-            x = d.mul(x, d.add(ins[k], ins[k + 1])); k += 2
-    d.decrypt(x)
-    return d, x
 
 
 def test_config5_plan_elides_the_last_product_and_every_copy_of_a_product(lib):

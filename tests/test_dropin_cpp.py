@@ -14,33 +14,11 @@ import numpy as np
 import pytest
 
 from oracle.binding import glibc_draws
+from tests.cpp_driver import LIBDIR, ROOT, fixture, run
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DRIVER_SRC = os.path.join(ROOT, "tests", "cpp", "dropin_driver.cpp")
-DRIVER = os.path.join(ROOT, "tests", "cpp", "dropin_driver")
-LIBDIR = os.path.join(ROOT, "csgn_amd", "lib")
 KAT_PATH = os.path.join(ROOT, "tests", "golden", "csgn_kat.json")
 
-
-@pytest.fixture(scope="module")
-def driver():
-    from csgn_amd import build
-    build.build_all()
-    deps = [DRIVER_SRC, os.path.join(LIBDIR, "libcertFHE.so")]
-    if (not os.path.exists(DRIVER)
-            or os.path.getmtime(DRIVER) < max(os.path.getmtime(d) for d in deps)):
-        subprocess.check_call(
-            ["g++", "-std=c++11", "-O1", "-Wall", "-I" + os.path.join(ROOT, "include", "certfhe"),
-             "-I" + os.path.join(ROOT, "include"), "-o", DRIVER, DRIVER_SRC,
-             "-L" + LIBDIR, "-lcertFHE", "-lcsgn_hip", "-lpthread", "-Wl,-rpath," + LIBDIR])
-    return DRIVER
-
-
-def run(driver, *args, check=True):
-    p = subprocess.run([driver, *map(str, args)], capture_output=True, text=True, timeout=600)
-    if check:
-        assert p.returncode == 0, f"{args}: rc={p.returncode}\n{p.stdout[-2000:]}\n{p.stderr[-2000:]}"
-    return p
+driver = fixture("tests/cpp/dropin_driver.cpp")
 
 
 def test_driver_builds_against_dropin_headers(driver):

@@ -13,26 +13,17 @@ import subprocess
 import pytest
 
 from oracle.binding import Ref
+from tests.cpp_driver import ROOT, build
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIBDIR = os.path.join(ROOT, "csgn_amd", "lib")
 DRIVER_SO = os.path.join(ROOT, "tests", "cpp", "libdropin_refdriver.so")
 
 
 @pytest.fixture(scope="module")
 def ref():
     """Overrides conftest's `ref`: the same extern-C driver, linked against the drop-in."""
-    from csgn_amd import build
-    build.build_all()
-    src = os.path.join(ROOT, "oracle", "ref_driver.cpp")
-    deps = [src, os.path.join(LIBDIR, "libcertFHE.so")]
-    if not os.path.exists(DRIVER_SO) or os.path.getmtime(DRIVER_SO) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call(
-            ["g++", "-std=c++11", "-O1", "-fPIC", "-shared", "-I" + os.path.join(ROOT, "include", "certfhe"),
-             "-I" + os.path.join(ROOT, "include"), "-o", DRIVER_SO, src, "-L" + LIBDIR, "-lcertFHE", "-lcsgn_hip",
-             "-Wl,-rpath," + LIBDIR])
+    build("oracle/ref_driver.cpp", "tests/cpp/libdropin_refdriver.so", shared=True)
     r = Ref(DRIVER_SO)
     maps = open("/proc/self/maps").read()
     assert "libcertFHE.so" in maps and "libcsgn_hip.so" in maps, "the drop-in library is not the one loaded"

@@ -1,36 +1,12 @@
 """The class-level gates (include/certfhe/Gates.h) through tests/cpp/gates_driver.cpp: user-style C++ against the
 drop-in headers.  The driver builds everywhere; its flows run on an MI355X (`pytest -m gpu`)."""
 import os
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DRIVER_SRC = os.path.join(ROOT, "tests", "cpp", "gates_driver.cpp")
-DRIVER = os.path.join(ROOT, "tests", "cpp", "gates_driver")
-LIBDIR = os.path.join(ROOT, "csgn_amd", "lib")
+from tests.cpp_driver import fixture, run_mode
 
-
-@pytest.fixture(scope="module")
-def driver():
-    from csgn_amd import build
-    build.build_all()
-    deps = [DRIVER_SRC, os.path.join(LIBDIR, "libcertFHE.so")] + [
-        os.path.join(ROOT, "include", "certfhe", f) for f in ("Gates.h", "Batch.h")]
-    if (not os.path.exists(DRIVER)
-            or os.path.getmtime(DRIVER) < max(os.path.getmtime(d) for d in deps)):
-        subprocess.check_call(
-            ["g++", "-std=c++11", "-O1", "-Wall", "-I" + os.path.join(ROOT, "include", "certfhe"),
-             "-I" + os.path.join(ROOT, "include"), "-o", DRIVER, DRIVER_SRC,
-             "-L" + LIBDIR, "-lcertFHE", "-lcsgn_hip", "-lpthread", "-Wl,-rpath," + LIBDIR])
-    return DRIVER
-
-
-def run(driver, mode):
-    p = subprocess.run([driver, mode], capture_output=True, text=True, timeout=900)
-    assert p.returncode == 0, f"{mode}: rc={p.returncode}\n{p.stdout[-3000:]}\n{p.stderr[-2000:]}"
-    assert f"{mode} ok" in p.stdout
-    return p
+driver = fixture("tests/cpp/gates_driver.cpp")
 
 
 def test_gates_driver_builds(driver):
@@ -39,14 +15,14 @@ def test_gates_driver_builds(driver):
 
 @pytest.mark.gpu
 def test_single_ciphertext_gates(driver):
-    run(driver, "single")
+    run_mode(driver, "single")
 
 
 @pytest.mark.gpu
 def test_batch_gates_uniform_and_ragged(driver):
-    run(driver, "batch")
+    run_mode(driver, "batch")
 
 
 @pytest.mark.gpu
 def test_circuit_equality_and_less_than(driver):
-    run(driver, "circuit")
+    run_mode(driver, "circuit")

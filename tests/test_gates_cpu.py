@@ -6,124 +6,16 @@ reference and the oracle.  The device side is tests/test_gates_gpu.py."""
 import numpy as np
 import pytest
 
-from oracle.binding import canonical_bitlen, glibc_draws
-
-NOT, XNOR, NAND, OR, NOR, MUX, ADD_PLAIN, MUL_PLAIN = range(1, 9)
-GATES = {"not": NOT, "xnor": XNOR, "nand": NAND, "or": OR, "nor": NOR, "mux": MUX, "add_plain": ADD_PLAIN,
-         "mul_plain": MUL_PLAIN}
-MASK64 = (1 << 64) - 1
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from csgn_amd import build, capi
-    build.build_hip()
-    return capi.load_library()
-
-
-# -- the definition, in numpy, on uniform batches: words[batch, terms, dL] -------------------------------------------
-def const_term(n, bit):
-    dl = (n + 63) // 64
-    t = np.full(dl, MASK64 if bit else 0, dtype=np.uint64)
-    if n % 64 and bit:
-        t[-1] = np.uint64((MASK64 << (64 - n % 64)) & MASK64)
-    return t
-
-
-def np_add(x, y):
-    return np.concatenate([x, y], axis=1)
-
-
-def np_mul(x, y):
-    b, t1, dl = x.shape
-    return (x[:, :, None, :] & y[:, None, :, :]).reshape(b, t1 * y.shape[1], dl)
-
-
-def np_gate(n, gate, a=None, b=None, sel=None, plain=None):
-    """Words of one gate over a uniform batch, by the table of include/csgn_hip.h."""
-    batch = a.shape[0]
-    one = np.broadcast_to(const_term(n, 1), (batch, 1, a.shape[2]))
-    if plain is not None:
-        pc = np.where((np.asarray(plain) & 1).astype(bool)[:, None, None], one, np.uint64(0))
-    if gate == NOT:
-        return np_add(a, one)
-    if gate == XNOR:
-        return np_add(np_add(a, b), one)
-    if gate == NAND:
-        return np_add(np_mul(a, b), one)
-    if gate == OR:
-        return np_add(np_add(a, b), np_mul(a, b))
-    if gate == NOR:
-        return np_add(np_add(np_add(a, b), np_mul(a, b)), one)
-    if gate == MUX:
-        return np_add(np_mul(sel, np_add(a, b)), b)
-    if gate == ADD_PLAIN:
-        return np_add(a, pc)
-    if gate == MUL_PLAIN:
-        return np_mul(a, pc)
-    raise ValueError(gate)
-
-
-def gate_clear(gate, a, b=0, s=0, p=0):
-    return {NOT: 1 - a, XNOR: 1 - (a ^ b), NAND: 1 - (a & b), OR: a | b, NOR: 1 - (a | b),
-            MUX: a if s else b, ADD_PLAIN: a ^ p, MUL_PLAIN: a & p}[gate]
-
-
-def rand_terms(n, batch, terms, seed):
-    """Random canonical terms (the unused low bits of the last word zero)."""
-    dl = (n + 63) // 64
-    w = np.random.default_rng(seed).integers(0, 2**64, size=(batch, terms, dl), dtype=np.uint64)
-    w[:, :, -1] &= const_term(n, 1)[-1]
-    return w
-
-
-def compose(ops, n, gate, a, b=None, sel=None, p=0):
-    """The same definition for ONE element through `ops` = (add, mul) on flat word arrays: the compiled reference's
-    operators or the oracle's.  Order of the operands exactly as in the table."""
-    add, mul = ops
-    one, pc = const_term(n, 1), const_term(n, p)
-    if gate == NOT:
-        return add(a, one)
-    if gate == XNOR:
-        return add(add(a, b), one)
-    if gate == NAND:
-        return add(mul(a, b), one)
-    if gate == OR:
-        return add(add(a, b), mul(a, b))
-    if gate == NOR:
-        return add(add(add(a, b), mul(a, b)), one)
-    if gate == MUX:
-        return add(mul(sel, add(a, b)), b)
-    if gate == ADD_PLAIN:
-        return add(a, pc)
-    if gate == MUL_PLAIN:
-        return mul(a, pc)
-    raise ValueError(gate)
-
-
-def oracle_ops(oracle, n):
-    return (lambda x, y: oracle.add(x, y)[0], lambda x, y: oracle.mul(n, x, y)[0])
-
-
-def ref_ops(ref, n, d):
-    dl = (n + 63) // 64
-
-    def bl(x):
-        return canonical_bitlen(n, len(x) // dl)
-
-    return (lambda x, y: ref.add(n, d, x, bl(x), y, bl(y))[0], lambda x, y: ref.mul(n, d, x, bl(x), y, bl(y))[0])
-
-
-def expected_terms(gate, ts, ta, tb):
-    return {NOT: ta + 1, XNOR: ta + tb + 1, NAND: ta * tb + 1, OR: ta + tb + ta * tb, NOR: ta + tb + ta * tb + 1,
-            MUX: ts * (ta + tb) + tb, ADD_PLAIN: ta + 1, MUL_PLAIN: ta}[gate]
+from oracle.binding import glibc_draws
+from tests.model import (ADD_PLAIN, GATES, MASK64, MUL_PLAIN, MUX, NAND, NOR, NOT, OR, compose_gate, const_term,
+                         gate_clear, gate_terms, lib, np_gate, oracle_ops, rand_terms, ref_ops)
 
 
 # -- the C ABI, host side ---------------------------------------------------------------------------------------------
 def test_gate_terms_table(lib):
     for gate in GATES.values():
         for ts, ta, tb in [(1, 1, 1), (1, 2, 3), (3, 5, 2), (64, 64, 64), (7, 1, 9)]:
-            assert lib.csgn_gate_terms(gate, ts, ta, tb) == expected_terms(gate, ts, ta, tb), (gate, ts, ta, tb)
+            assert lib.csgn_gate_terms(gate, ts, ta, tb) == gate_terms(gate, ts, ta, tb), (gate, ts, ta, tb)
     for bad in (0, 9, -1, 100):
         assert lib.csgn_gate_terms(bad, 1, 1, 1) == 0
     assert lib.csgn_gate_terms(NOT, 0, 0, 0) == 0                  # an operand the gate reads has no terms
@@ -182,10 +74,10 @@ def test_gate_entry_points_fail_without_gpu(lib):
 def test_gate_definition_matches_reference(oracle, ref, n, d, gate, ts, ta, tb):
     a, b, s = (rand_terms(n, 1, t, seed)[0].ravel() for t, seed in ((ta, 1), (tb, 2), (ts, 3)))
     for p in (0, 1):
-        want = compose(ref_ops(ref, n, d), n, gate, a, b, s, p)
-        got = compose(oracle_ops(oracle, n), n, gate, a, b, s, p)
+        want = compose_gate(ref_ops(ref, n, d), n, gate, a, b, s, p)
+        got = compose_gate(oracle_ops(oracle, n), n, gate, a, b, s, p)
         assert np.array_equal(got, want), (gate, p)
-        assert got.size == expected_terms(gate, ts, ta, tb) * ((n + 63) // 64)
+        assert got.size == gate_terms(gate, ts, ta, tb) * ((n + 63) // 64)
         words = np_gate(n, gate, a[None].reshape(1, ta, -1), b[None].reshape(1, tb, -1), s[None].reshape(1, ts, -1),
                         plain=[p])
         assert np.array_equal(words.ravel(), got)
@@ -199,7 +91,7 @@ def test_gate_definition_matches_oracle(oracle, n, gate):
     plain = np.array([1, 0, 1, 1, 0], dtype=np.uint8)
     words = np_gate(n, gate, a, b, s, plain)
     for e in range(batch):
-        want = compose(oracle_ops(oracle, n), n, gate, a[e].ravel(), b[e].ravel(), s[e].ravel(), int(plain[e]))
+        want = compose_gate(oracle_ops(oracle, n), n, gate, a[e].ravel(), b[e].ravel(), s[e].ravel(), int(plain[e]))
         assert np.array_equal(words[e].ravel(), want), e
 
 
@@ -221,6 +113,6 @@ def test_constants_and_truth_tables_decrypt(oracle, n, d):
                 for x in (0, 1):
                     for y in (0, 1):
                         for p in (0, 1):
-                            w = compose(ops, n, gate, ct[x], ct[2 + y], ct[4 + s], p)
+                            w = compose_gate(ops, n, gate, ct[x], ct[2 + y], ct[4 + s], p)
                             assert oracle.decrypt_canonical(n, key, w) == gate_clear(gate, x, y, s, p), \
                                 (gate, s, x, y, p)

@@ -5,8 +5,8 @@ import numpy as np
 import pytest
 
 from oracle.binding import glibc_draws
-from tests.test_gates_cpu import (ADD_PLAIN, GATES, MUL_PLAIN, MUX, NOT, compose, const_term, expected_terms,
-                                  gate_clear, np_gate, oracle_ops, rand_terms)
+from tests.model import (ADD_PLAIN, GATES, MUL_PLAIN, MUX, NOT, compose_gate, const_term, gate_clear, gate_terms, hip,
+                         np_gate, oracle_ops, rand_terms)
 
 pytestmark = pytest.mark.gpu
 
@@ -14,12 +14,6 @@ NS = [63, 64, 65, 129, 1247, 4096]
 # (t_sel, t_a, t_b, batch): fresh operands up to past the fused / pitched cut (64 product terms per element)
 SHAPES = [(1, 1, 1, 1), (1, 1, 1, 1000), (2, 1, 3, 3), (1, 4, 4, 1000), (1, 5, 4, 3), (3, 8, 8, 3), (1, 9, 8, 3),
           (1, 64, 64, 3)]
-
-
-@pytest.fixture(scope="module")
-def hip():
-    from csgn_amd.batch import HipPath
-    return HipPath(0)
 
 
 def run_gate(hip, n, gate, a, b, s, plain):
@@ -45,12 +39,12 @@ def test_gate_words(hip, oracle, knobs, n, gate, shape):
         batch = 1
     a, b, s, plain = operands(n, ts, ta, tb, batch, 1000 * gate + ta)
     want = np_gate(n, gate, a, b, s, plain).ravel()
-    assert want.size == batch * expected_terms(gate, ts, ta, tb) * ((n + 63) // 64)
+    assert want.size == batch * gate_terms(gate, ts, ta, tb) * ((n + 63) // 64)
     # the first and last element also straight through the oracle's operators
     ops = oracle_ops(oracle, n)
     per = want.size // batch
     for e in {0, batch - 1}:
-        o = compose(ops, n, gate, a[e].ravel(), b[e].ravel(), s[e].ravel(), int(plain[e]))
+        o = compose_gate(ops, n, gate, a[e].ravel(), b[e].ravel(), s[e].ravel(), int(plain[e]))
         assert np.array_equal(want[e * per:(e + 1) * per], o)
     for fused in (-1, 0, 1):
         knobs.set("gate_fused", fused)
@@ -96,7 +90,7 @@ def test_gate_truth_tables_decrypt(hip, oracle, n, d):
         for gate in GATES.values():
             out = hip.gate_uniform(n, gate, batch, hip.upload(a_ct), 1, hip.upload(b_ct), 1, hip.upload(s_ct), 1,
                                    hip.upload(bits[:, 3].copy()))
-            terms = expected_terms(gate, 1, 1, 1)
+            terms = gate_terms(gate, 1, 1, 1)
             dec = hip.download(hip.decrypt_uniform(n, batch, terms, out, mask))
             host = hip.download(out).reshape(batch, terms * dl)
             for e, (s, x, y, p) in enumerate(combos):

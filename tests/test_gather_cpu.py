@@ -6,18 +6,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
-OK, INVALID, UNSUPPORTED, NO_DEVICE = 0, -1, -2, -3
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from csgn_amd import build, capi
-    build.build_hip()
-    return capi.load_library()
-
-
-def u64s(xs):
-    return (C.c_uint64 * max(len(xs), 1))(*[int(x) for x in xs])
+from tests.model import (INVALID, NO_DEVICE, UNSUPPORTED, lib, np_gather, np_gather_offsets, np_gather_uniform,
+                         tile_index, u64s)
 
 
 def vps(xs):
@@ -25,32 +15,6 @@ def vps(xs):
 
 
 # -- the model --------------------------------------------------------------------------------------------------------
-def tile_index(count_in, count_out):
-    return np.arange(count_out, dtype=np.uint64) % np.uint64(max(count_in, 1))
-
-
-def np_gather_offsets(src_off, idx):
-    """Output offsets: exclusive prefix sums of the gathered elements' term counts (count_out + 1 entries)."""
-    src_off = np.asarray(src_off, dtype=np.uint64)
-    idx = np.asarray(idx, dtype=np.int64)
-    sizes = (src_off[idx + 1] - src_off[idx]) if len(idx) else np.zeros(0, dtype=np.uint64)
-    return np.concatenate([[0], np.cumsum(sizes, dtype=np.uint64)]).astype(np.uint64)
-
-
-def np_gather(words, src_off, idx, dl):
-    """Words and offsets of the gather of a CSR batch (`words`: total terms * dl words)."""
-    out_off = np_gather_offsets(src_off, idx)
-    parts = [words[int(src_off[i]) * dl:int(src_off[i + 1]) * dl] for i in np.asarray(idx, dtype=np.int64)]
-    out = np.concatenate(parts).astype(np.uint64) if parts else np.zeros(0, dtype=np.uint64)
-    assert len(out) == int(out_off[-1]) * dl
-    return out, out_off
-
-
-def np_gather_uniform(words, t, idx, dl):
-    elems = np.asarray(words, dtype=np.uint64).reshape(-1, t * dl)
-    return elems[np.asarray(idx, dtype=np.int64)].ravel()
-
-
 def np_concat(parts):
     """parts: [(words, offsets)] -> (words, offsets) of their concatenation."""
     words = np.concatenate([w for w, _ in parts]).astype(np.uint64)

@@ -4,15 +4,10 @@ import numpy as np
 import pytest
 import torch
 
-from tests.test_gather_cpu import INVALID, OK, np_gather, np_gather_offsets, np_gather_uniform, tile_index
+from tests.model import INVALID, OK, hip, np_gather, np_gather_offsets, np_gather_uniform, tile_index
+
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def hip():
-    from csgn_amd.batch import HipPath
-    return HipPath(0)
 
 
 def words(seed, n):

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from oracle.binding import canonical_bitlen, glibc_draws
+from tests.model import config5, csr, explicit_randomness, hip, make_key, planted, random_circuit
 
 pytestmark = pytest.mark.gpu
 
@@ -27,26 +28,9 @@ def words(hex_list):
 
 
 @pytest.fixture(scope="module")
-def hip():
-    from csgn_amd.batch import HipPath
-    return HipPath(0)
-
-
-@pytest.fixture(scope="module")
 def kat():
     with open(KAT_PATH) as f:
         return json.load(f)
-
-
-def make_key(n, d, seed):
-    rng = np.random.default_rng(seed)
-    return rng.permutation(n)[:d].astype(np.uint64)
-
-
-def csr(counts):
-    off = np.zeros(len(counts) + 1, dtype=np.uint64)
-    off[1:] = np.cumsum(np.asarray(counts, dtype=np.uint64))
-    return off
 
 
 # ------------------------------------------------------------------------------ harness
@@ -442,17 +426,6 @@ def test_add_ragged_matches_oracle(hip, oracle, n, d):
 
 # ------------------------------------------------------------------------------ decrypt
 
-def planted(oracle, n, key, terms, hits, seed):
-    dl = oracle.default_len(n)
-    v = oracle.synth(seed, n, 0, terms * dl).reshape(terms, dl)
-    v[:hits] |= oracle.key_mask(n, key)
-    w, b = int(key[0]) // 64, 63 - int(key[0]) % 64
-    v[hits:, w] &= ~np.uint64(1 << b)
-    rng = np.random.default_rng(seed)
-    rng.shuffle(v, axis=0)
-    return np.ascontiguousarray(v.reshape(-1))
-
-
 @pytest.mark.parametrize("n,d", CONTEXTS)
 def test_decrypt_uniform_matches_oracle(hip, oracle, n, d):
     key = make_key(n, d, 3)
@@ -497,42 +470,6 @@ def test_decrypt_one_million_terms(hip, oracle):
 
 
 # ------------------------------------------------------------------------------ encrypt
-
-def explicit_randomness(n, key, bit, draws):
-    """Map the reference's rand() stream (src/SecretKey.cpp:35-80) onto the explicit
-    arguments of csgn_encrypt_explicit.  Returns (rnd words, chosen, last, draws used)."""
-    dl = (n + 63) // 64
-    keyset = set(int(k) for k in key)
-    rnd = np.zeros(dl, dtype=np.uint64)
-    pos = 0
-
-    def setbit(i, v):
-        if v:
-            rnd[i // 64] |= np.uint64(1 << (63 - i % 64))
-
-    if bit & 1:
-        for i in range(n):
-            if i not in keyset:
-                setbit(i, int(draws[pos]) % 2)
-                pos += 1
-        return rnd, 0, 0, pos
-    chosen = int(key[int(draws[pos]) % len(key)])
-    pos += 1
-    others = []
-    for i in range(n):
-        if i == chosen:
-            continue
-        v = int(draws[pos]) % 2
-        pos += 1
-        setbit(i, v)
-        if i in keyset:
-            others.append(v)
-    last = 0
-    if not (others and all(others)):
-        last = int(draws[pos]) % 2
-        pos += 1
-    return rnd, chosen, last, pos
-
 
 def test_encrypt_explicit_reproduces_reference_ciphertexts(hip, oracle, kat):
     """Golden fresh ciphertexts (from the genuine reference under srand(seed)) rebuilt on the GPU."""
@@ -2427,7 +2364,6 @@ def test_circuit_compiled_matches_tape_on_random_dags(hip, oracle, n, d, batch, 
     import ctypes as C
     import torch
     from csgn_amd.capi import check
-    from tests.test_circuit_compiler import random_circuit
     lib = hip.lib
     dl = oracle.default_len(n)
     key = make_key(n, d, 31)
@@ -2529,7 +2465,6 @@ def test_circuit_compiled_config5(hip, oracle, n, d, batch):
     import ctypes as C
     import torch
     from csgn_amd.capi import check
-    from tests.test_circuit_compiler import config5
     lib = hip.lib
     dl = oracle.default_len(n)
     key = make_key(n, d, 5)

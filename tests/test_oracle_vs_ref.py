@@ -13,16 +13,12 @@ import pytest
 
 from oracle.binding import (canonical_bitlen, glibc_draws, text_ciphertext, text_context, text_key,
                             text_permutation, text_plaintext)
+from tests.model import make_key
 
 CONTEXTS = [(1247, 16), (4096, 32), (63, 4), (64, 4), (65, 4), (128, 8), (130, 5), (100, 1)]
 
 
-def make_key(n, d, seed):
-    rng = np.random.default_rng(seed)
-    return rng.permutation(n)[:d].astype(np.uint64)
-
-
-def rand_terms(oracle, n, terms, seed):
+def synth_terms(oracle, n, terms, seed):
     return oracle.synth(seed, n, 0, terms * oracle.default_len(n))
 
 
@@ -64,8 +60,8 @@ def test_encrypt_stream_matches_reference(oracle, ref, n, d, seed):
 @pytest.mark.parametrize("n,d", [(1247, 16), (4096, 32), (65, 4), (64, 4)])
 @pytest.mark.parametrize("t1,t2", [(1, 1), (1, 2), (2, 1), (2, 2), (3, 5), (7, 1), (1, 7), (32, 32)])
 def test_mul_matches_reference(oracle, ref, n, d, t1, t2):
-    a = rand_terms(oracle, n, t1, 11)
-    b = rand_terms(oracle, n, t2, 22)
+    a = synth_terms(oracle, n, t1, 11)
+    b = synth_terms(oracle, n, t2, 22)
     # distinct bitlen patterns on each side expose the left-operand rule (Ciphertext.cpp:172)
     bl1 = (np.arange(a.size, dtype=np.uint64) % 60) + 1
     bl2 = (np.arange(b.size, dtype=np.uint64) % 50) + 5
@@ -80,8 +76,8 @@ def test_mul_matches_reference(oracle, ref, n, d, t1, t2):
 @pytest.mark.parametrize("n,d", [(1247, 16), (4096, 32), (65, 4)])
 @pytest.mark.parametrize("t1,t2", [(1, 1), (1, 3), (4, 2), (17, 9)])
 def test_add_matches_reference(oracle, ref, n, d, t1, t2):
-    a = rand_terms(oracle, n, t1, 5)
-    b = rand_terms(oracle, n, t2, 6)
+    a = synth_terms(oracle, n, t1, 5)
+    b = synth_terms(oracle, n, t2, 6)
     bl1, bl2 = canonical_bitlen(n, t1), canonical_bitlen(n, t2)
     want, want_bl = ref.add(n, d, a, bl1, b, bl2)
     got, got_bl = oracle.add(a, b, bl1, bl2)
@@ -97,7 +93,7 @@ def test_decrypt_multiterm_matches_reference(oracle, ref, n, d):
     mask = oracle.key_mask(n, key)
     dl = oracle.default_len(n)
     for terms, hits in [(1, 0), (1, 1), (2, 1), (2, 2), (5, 3), (64, 17), (257, 100)]:
-        v = rand_terms(oracle, n, terms, 100 + terms).reshape(terms, dl)
+        v = synth_terms(oracle, n, terms, 100 + terms).reshape(terms, dl)
         v[:hits] |= mask          # force `hits` terms to satisfy the key
         # make sure the others do not hit by clearing one secret position
         w, b = int(key[0]) // 64, 63 - int(key[0]) % 64
@@ -212,8 +208,8 @@ def test_large_products_digest(oracle, ref):
     """32x32 and 256x256 products: full compare (the 1024x1024 digest lives in golden/)."""
     n, d = 1247, 16
     for t in (32, 256):
-        a = rand_terms(oracle, n, t, 1000 + t)
-        b = rand_terms(oracle, n, t, 2000 + t)
+        a = synth_terms(oracle, n, t, 1000 + t)
+        b = synth_terms(oracle, n, t, 2000 + t)
         bl = canonical_bitlen(n, t)
         want, _ = ref.mul(n, d, a, bl, b, bl)
         got, _ = oracle.mul(n, a, b)

@@ -16,10 +16,8 @@ import subprocess
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIBDIR = os.path.join(ROOT, "csgn_amd", "lib")
-TOOL_SRC = os.path.join(ROOT, "tools", "shard_mul.cpp")
-TOOL = os.path.join(ROOT, "tools", "bin", "shard_mul")
+from tests import cpp_driver
+from tests.cpp_driver import LIBDIR, ROOT
 
 
 @pytest.fixture(scope="module")
@@ -31,15 +29,7 @@ def shard_lib():
 
 @pytest.fixture(scope="module")
 def tool(shard_lib):
-    os.makedirs(os.path.dirname(TOOL), exist_ok=True)
-    deps = [TOOL_SRC, os.path.join(LIBDIR, "libcsgn_shard.so"), os.path.join(LIBDIR, "libcsgn_hip.so"),
-            os.path.join(LIBDIR, "libcertFHE_shard.so"), os.path.join(LIBDIR, "libcertFHE.so")]
-    if not os.path.exists(TOOL) or os.path.getmtime(TOOL) < max(os.path.getmtime(d) for d in deps):
-        inc = os.path.join(ROOT, "include")
-        subprocess.check_call(["g++", "-std=c++11", "-O2", "-Wall", "-I" + inc, "-I" + os.path.join(inc, "certfhe"),
-                               "-o", TOOL, TOOL_SRC, "-L" + LIBDIR, "-lcertFHE_shard", "-lcertFHE", "-lcsgn_shard",
-                               "-lcsgn_hip", "-lpthread", "-Wl,-rpath," + LIBDIR, "-Wl,-rpath,/opt/rocm/lib"])
-    return TOOL
+    return cpp_driver.build("tools/shard_mul.cpp", "tools/bin/shard_mul", libs=cpp_driver.SHARDED, opt="-O2")
 
 
 def test_header_symbols_are_exported_and_bound(shard_lib):

@@ -3,13 +3,9 @@ record arrays with (tests/test_small_ops_gpu.py) is the C struct's, field for fi
 import os
 import subprocess
 
-import numpy as np
+from tests.model import SMALL_OP
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-# csgn_small_op: out = left + right (kind 0) or left * right (kind 1), t1 / t2 terms a side
-SMALL_OP = np.dtype([("left", "<u8"), ("right", "<u8"), ("out", "<u8"), ("t1", "<u4"), ("t2", "<u4"),
-                     ("kind", "<u4"), ("reserved", "<u4")])
 
 LAYOUT_SRC = r"""
 #include <cstddef>

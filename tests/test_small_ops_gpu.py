@@ -10,20 +10,14 @@ import numpy as np
 import pytest
 import torch
 
-from tests.test_gates_cpu import np_add, np_mul, rand_terms
-from tests.test_small_ops_cpu import SMALL_OP
+from tests.model import SMALL_OP, hip, np_add, np_mul, rand_terms
+
 
 pytestmark = pytest.mark.gpu
 
 NS = [63, 64, 65, 128, 129, 1247, 1300, 4096]
 GUARD = 0x5A5A5A5A5A5A5A5A
 ADD, MUL = 0, 1
-
-
-@pytest.fixture(scope="module")
-def hip():
-    from csgn_amd.batch import HipPath
-    return HipPath(0)
 
 
 class Arena:

@@ -8,107 +8,16 @@ import numpy as np
 import pytest
 
 from oracle.binding import glibc_draws
-from tests.test_gates_cpu import const_term, np_add, np_mul, oracle_ops, rand_terms, ref_ops
-
-ADD_HALF, ADD_FULL, EQ_STEP, LT_FIRST, LT_STEP = range(1, 6)
-STEPS = {"add_half": ADD_HALF, "add_full": ADD_FULL, "eq_step": EQ_STEP, "lt_first": LT_FIRST, "lt_step": LT_STEP}
-MASK64 = (1 << 64) - 1
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from csgn_amd import build, capi
-    build.build_hip()
-    return capi.load_library()
-
-
-# -- the definition -------------------------------------------------------------------------------------------------------
-def np_step(n, step, x, a, b):
-    """Outputs of one step over uniform batches (words[batch, terms, dL]): (out0,) or (sum, carry) for the ADD steps."""
-    one = np.broadcast_to(const_term(n, 1), (a.shape[0], 1, a.shape[2]))
-    if step == ADD_HALF:
-        return np_add(a, b), np_mul(a, b)
-    if step == ADD_FULL:
-        return np_add(np_add(a, b), x), np_add(np_mul(a, b), np_mul(np_add(a, b), x))
-    if step == EQ_STEP:
-        return (np_mul(x, np_add(np_add(a, b), one)),)
-    if step == LT_FIRST:
-        return (np_mul(np_add(a, one), b),)
-    if step == LT_STEP:
-        return (np_add(np_mul(np_add(a, b), np_add(b, x)), x),)
-    raise ValueError(step)
-
-
-def compose_step(ops, n, step, x, a, b):
-    """The same definition for ONE element through `ops` = (add, mul) on flat word arrays."""
-    add, mul = ops
-    one = const_term(n, 1)
-    if step == ADD_HALF:
-        return add(a, b), mul(a, b)
-    if step == ADD_FULL:
-        return add(add(a, b), x), add(mul(a, b), mul(add(a, b), x))
-    if step == EQ_STEP:
-        return (mul(x, add(add(a, b), one)),)
-    if step == LT_FIRST:
-        return (mul(add(a, one), b),)
-    if step == LT_STEP:
-        return (add(mul(add(a, b), add(b, x)), x),)
-    raise ValueError(step)
-
-
-def expected_terms(step, tx, ta, tb):
-    return {ADD_HALF: (ta + tb, ta * tb), ADD_FULL: (ta + tb + tx, ta * tb + (ta + tb) * tx),
-            EQ_STEP: (tx * (ta + tb + 1),), LT_FIRST: ((ta + 1) * tb,),
-            LT_STEP: ((ta + tb) * (tb + tx) + tx,)}[step]
-
-
-# -- whole operations, composed from the steps in numpy (planes: list of words[batch, 1, dL], bit 0 first) ----------------
-def np_not(n, x):
-    return np_add(x, np.broadcast_to(const_term(n, 1), (x.shape[0], 1, x.shape[2])))
-
-
-def np_uint_add(n, a, b):
-    w = len(a)
-    s0, c = np_step(n, ADD_HALF, None, a[0], b[0])
-    out = [s0]
-    for j in range(1, w):
-        s, c = np_step(n, ADD_FULL, c, a[j], b[j])
-        out.append(s)
-    return out
-
-
-def np_uint_sub(n, a, b):
-    c = np.broadcast_to(const_term(n, 1), (a[0].shape[0], 1, a[0].shape[2]))
-    out = []
-    for j in range(len(a)):
-        s, c = np_step(n, ADD_FULL, c, a[j], np_not(n, b[j]))
-        out.append(s)
-    return out
-
-
-def np_uint_eq(n, a, b):
-    e = np_not(n, np_add(a[0], b[0]))                               # logicXnor
-    for j in range(1, len(a)):
-        (e,) = np_step(n, EQ_STEP, e, a[j], b[j])
-    return e
-
-
-def np_uint_lt(n, a, b):
-    (lt,) = np_step(n, LT_FIRST, None, a[0], b[0])
-    for j in range(1, len(a)):
-        (lt,) = np_step(n, LT_STEP, lt, a[j], b[j])
-    return lt
-
-
-def np_uint_select(n, s, a, b):
-    return [np_add(np_mul(s, np_add(aj, bj)), bj) for aj, bj in zip(a, b)]   # logicMux
+from tests.model import (ADD_FULL, ADD_HALF, EQ_STEP, LT_FIRST, LT_STEP, MASK64, STEPS, compose_step, lib, np_mul,
+                         np_not, np_step, np_uint_add, np_uint_eq, np_uint_lt, np_uint_select, np_uint_sub, oracle_ops,
+                         rand_terms, ref_ops, step_terms)
 
 
 # -- the C ABI, host side ---------------------------------------------------------------------------------------------
 def test_uint_step_terms_table(lib):
     for step in STEPS.values():
         for tx, ta, tb in [(1, 1, 1), (3, 1, 1), (2, 3, 5), (26, 1, 1), (64, 64, 64), (7, 1, 9)]:
-            want = expected_terms(step, tx, ta, tb)
+            want = step_terms(step, tx, ta, tb)
             for output in range(2):
                 got = lib.csgn_uint_step_terms(step, output, tx, ta, tb)
                 assert got == (want[output] if output < len(want) else 0), (step, output, tx, ta, tb)
@@ -202,7 +111,7 @@ def test_step_definition_matches_reference(oracle, ref, n, d, step, tx, ta, tb):
     dl = (n + 63) // 64
     for o in range(len(want)):
         assert np.array_equal(got[o], want[o]), (step, o)
-        assert got[o].size == expected_terms(step, tx, ta, tb)[o] * dl
+        assert got[o].size == step_terms(step, tx, ta, tb)[o] * dl
         assert np.array_equal(words[o].ravel(), got[o]), (step, o)
 
 

@@ -5,9 +5,8 @@ import numpy as np
 import pytest
 
 from oracle.binding import glibc_draws
-from tests.test_gates_cpu import rand_terms
-from tests.test_uint_cpu import (ADD_FULL, ADD_HALF, EQ_STEP, LT_FIRST, LT_STEP, STEPS, expected_terms, np_step,
-                                 np_uint_add, np_uint_eq, np_uint_lt, np_uint_sub)
+from tests.model import (ADD_FULL, ADD_HALF, EQ_STEP, LT_FIRST, LT_STEP, STEPS, hip, np_step, np_uint_add, np_uint_eq,
+                         np_uint_lt, np_uint_sub, rand_terms, step_terms)
 
 pytestmark = pytest.mark.gpu
 
@@ -16,12 +15,6 @@ NS = [63, 64, 65, 129, 1247, 4096]
 # left operands (rows that interleave)
 SHAPES = [(1, 1, 1, 1), (1, 1, 1, 1000), (3, 1, 1, 7), (8, 1, 1, 3), (31, 1, 1, 3), (63, 1, 1, 3), (90, 1, 1, 2),
           (3, 2, 3, 3), (1, 9, 8, 2), (2, 1, 40, 2)]
-
-
-@pytest.fixture(scope="module")
-def hip():
-    from csgn_amd.batch import HipPath
-    return HipPath(0)
 
 
 def reads_x(step):
@@ -47,7 +40,7 @@ def test_step_words(hip, knobs, n, step, shape):
     want = [w.ravel() for w in np_step(n, step, x, a, b)]
     dl = (n + 63) // 64
     for o, w in enumerate(want):
-        assert w.size == batch * expected_terms(step, tx, ta, tb)[o] * dl
+        assert w.size == batch * step_terms(step, tx, ta, tb)[o] * dl
     for fused in (-1, 0, 1):
         knobs.set("uint_fused", fused)
         kernel = hip.lib.csgn_uint_step_kernel(n, step, batch, tx, ta, tb).decode()

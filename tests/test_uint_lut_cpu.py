@@ -9,105 +9,15 @@ import numpy as np
 import pytest
 
 from oracle.binding import glibc_draws
-from tests.test_gates_cpu import const_term, np_add, np_mul, oracle_ops, rand_terms, ref_ops
-from tests.test_uint_plain_cpu import decrypt_bits, encrypt_planes
-
-LIMIT = 1 << 62
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from csgn_amd import build, capi
-    build.build_hip()
-    return capi.load_library()
-
-
-def u64s(xs):
-    return (C.c_uint64 * max(len(xs), 1))(*[int(x) for x in xs])
-
-
-# -- tables -----------------------------------------------------------------------------------------------------------
-def aes_sbox():
-    """The AES S-box from its definition: the inverse in GF(2^8) mod x^8 + x^4 + x^3 + x + 1, then the affine map."""
-    def gmul(a, b):
-        r = 0
-        while b:
-            if b & 1:
-                r ^= a
-            a = ((a << 1) ^ 0x11B) if a & 0x80 else a << 1
-            b >>= 1
-        return r
-
-    inv = [0] * 256
-    for a in range(1, 256):
-        inv[a] = next(b for b in range(1, 256) if gmul(a, b) == 1)
-    rot = lambda x, s: ((x << s) | (x >> (8 - s))) & 0xFF
-    return [inv[x] ^ rot(inv[x], 1) ^ rot(inv[x], 2) ^ rot(inv[x], 3) ^ rot(inv[x], 4) ^ 0x63 for x in range(256)]
-
-
-def random_table(w, m, seed):
-    rng = np.random.default_rng(seed)
-    if m == 64:
-        return [int(v) for v in rng.integers(0, 2**64 - 1, 1 << w, dtype=np.uint64, endpoint=True)]
-    return [int(v) for v in rng.integers(0, 1 << m, 1 << w)]
-
-
-def mul4x4():
-    """Two-input 4x4-bit multiply: index a + (b << 4), 8-bit product."""
-    return [(x & 15) * (x >> 4) for x in range(256)]
+from tests.model import (EQ, aes_sbox, c_terms, compose_lut, const_term, decrypt_bits, decrypt_value, encrypt_planes,
+                         lib, lut_terms, np_add, np_anf, np_lut, np_plain, oracle_ops, rand_terms, random_table,
+                         ref_ops, u64s)
 
 
 # -- the definition, over any (add, mul, one, zero) ---------------------------------------------------------------------
-def np_anf(table, w):
-    anf = [int(v) for v in table]
-    for i in range(w):
-        for x in range(1 << w):
-            if (x >> i) & 1:
-                anf[x] ^= anf[x ^ (1 << i)]
-    return anf
-
-
 def monomials(table, w, j):
     anf = np_anf(table, w)
     return [S for S in range(1 << w) if (anf[S] >> j) & 1]
-
-
-def compose_lut(planes, table, w, m, add, mul, one, zero):
-    """include/csgn_hip.h's definition, in exactly its order: one value per output bit."""
-    anf = np_anf(table, w)
-    outs = []
-    for j in range(m):
-        r = None
-        for S in range(1 << w):
-            if not (anf[S] >> j) & 1:
-                continue
-            mono = one
-            first = True
-            for i in range(w):
-                if (S >> i) & 1:
-                    mono = planes[i] if first else mul(mono, planes[i])
-                    first = False
-            r = mono if r is None else add(r, mono)
-        outs.append(zero if r is None else r)
-    return outs
-
-
-def np_lut(n, planes, table, m):
-    """Words of every output over uniform planes (words[batch, t_i, dL], bit 0 first)."""
-    batch, _, dl = planes[0].shape
-    one = np.broadcast_to(const_term(n, 1), (batch, 1, dl))
-    zero = np.broadcast_to(const_term(n, 0), (batch, 1, dl))
-    return compose_lut(planes, table, len(planes), m, np_add, np_mul, one, zero)
-
-
-def expected_terms(table, w, m, t):
-    return compose_lut(list(t), table, w, m, lambda x, y: x + y, lambda x, y: x * y, 1, 1)
-
-
-def c_terms(lib, table, w, m, t):
-    out = (C.c_uint64 * m)()
-    rc = lib.csgn_uint_lut_terms(w, m, u64s(table), u64s(t), out)
-    return rc, list(out)
 
 
 # -- the C ABI, host side ---------------------------------------------------------------------------------------------
@@ -157,7 +67,7 @@ def test_terms_formulas(lib):
         for t in ([1] * w, [int(x) for x in rng.integers(1, 4, w)], [2] * w, [3] + [1] * (w - 1)):
             rc, got = c_terms(lib, table, w, m, t)
             assert rc == 0
-            assert got == expected_terms(table, w, m, t), (w, m, t)
+            assert got == lut_terms(table, w, m, t), (w, m, t)
             if t == [1] * w:
                 assert got == [max(1, len(monomials(table, w, j))) for j in range(m)]
     # fresh planes: at most 2^w; the identity is one term, the constants one term
@@ -246,7 +156,7 @@ def test_definition_matches_reference(oracle, ref, n, d, name, tmode):
     got = compose_lut(planes, table, w, m, add, mul, const_term(n, 1), const_term(n, 0))
     words = np_lut(n, [p.reshape(1, t, -1) for p, t in zip(planes, ts)], table, m)
     dl = (n + 63) // 64
-    sizes = expected_terms(table, w, m, ts)
+    sizes = lut_terms(table, w, m, ts)
     for j in range(m):
         assert np.array_equal(got[j], want[j]), j
         assert got[j].size == sizes[j] * dl
@@ -286,13 +196,6 @@ def test_definition_matches_oracle_batched(oracle, n):
 
 
 # -- decryptions -------------------------------------------------------------------------------------------------------
-def decrypt_value(oracle, n, key, outs):
-    v = np.zeros(outs[0].shape[0], dtype=np.uint64)
-    for j, o in enumerate(outs):
-        v |= decrypt_bits(oracle, n, key, o).astype(np.uint64) << np.uint64(j)
-    return v
-
-
 @pytest.mark.parametrize("w", [1, 2, 3, 4])
 def test_truth_tables_decrypt(oracle, w):
     n, d = 127, 8
@@ -308,7 +211,6 @@ def test_truth_tables_decrypt(oracle, w):
 
 def test_compacted_today_route_same_bits(oracle):
     """Today's route, sum over k with bit j of f(k) of equalTo(a, k), decrypts to the same bits, with many more terms."""
-    from tests.test_uint_plain_cpu import EQ, np_plain
     n, d, w = 127, 8, 3
     key, _ = oracle.keygen(n, d, glibc_draws(33, 64 * d + 64))
     values = np.arange(1 << w, dtype=np.uint64)

@@ -8,17 +8,10 @@ import pytest
 import torch
 
 from oracle.binding import glibc_draws
-from tests.test_gates_cpu import np_add, rand_terms
-from tests.test_uint_lut_cpu import aes_sbox, c_terms, decrypt_value, mul4x4, np_lut, random_table, u64s
-from tests.test_uint_plain_cpu import EQ, decrypt_bits, encrypt_planes, np_plain
+from tests.model import (EQ, aes_sbox, c_terms, decrypt_bits, decrypt_value, encrypt_planes, hip, mul4x4, np_add,
+                         np_lut, np_plain, rand_terms, random_table, u64s)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def hip():
-    from csgn_amd.batch import HipPath
-    return HipPath(0)
 
 
 def run(hip, n, planes, table, m):

@@ -9,71 +9,9 @@ import numpy as np
 import pytest
 
 from oracle.binding import glibc_draws
-from tests.test_gates_cpu import const_term, np_add, np_mul, oracle_ops, rand_terms, ref_ops
-from tests.test_uint_cpu import np_uint_eq, np_uint_lt
-
-EQ, NE, LT, LE, GT, GE = range(1, 7)
-CMPS = {"eq": EQ, "ne": NE, "lt": LT, "le": LE, "gt": GT, "ge": GE}
-LIMIT = 1 << 62
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from csgn_amd import build, capi
-    build.build_hip()
-    return capi.load_library()
-
-
-def u64s(xs):
-    return (C.c_uint64 * max(len(xs), 1))(*[int(x) for x in xs])
-
-
-def lowest(k, bit, w):
-    return next(j for j in range(w) if (k >> j) & 1 == bit)
-
-
-# -- the definition, over any (add, mul, one, zero) ---------------------------------------------------------------------
-def compose(cmp, planes, k, add, mul, one, zero):
-    """include/csgn_hip.h's table, in exactly its order."""
-    w = len(planes)
-    nt = lambda j: add(planes[j], one)                                       # logicNot
-    base = {NE: EQ, LE: GT, GE: LT}.get(cmp, cmp)
-    if base == EQ:
-        g = lambda j: planes[j] if (k >> j) & 1 else nt(j)
-        r = g(0)
-        for j in range(1, w):
-            r = mul(r, g(j))
-    elif base == LT:
-        if k == 0:
-            r = zero
-        else:
-            m = lowest(k, 1, w)
-            r = nt(m)
-            for j in range(m + 1, w):
-                r = add(mul(r, planes[j]), nt(j)) if (k >> j) & 1 else mul(r, nt(j))
-    else:
-        if k == (1 << w) - 1:
-            r = zero
-        else:
-            m = lowest(k, 0, w)
-            r = planes[m]
-            for j in range(m + 1, w):
-                r = mul(r, planes[j]) if (k >> j) & 1 else add(mul(r, nt(j)), planes[j])
-    return add(r, one) if cmp != base else r
-
-
-def np_plain(n, cmp, planes, k):
-    """Words of one comparison over uniform planes (words[batch, t_j, dL], bit 0 first)."""
-    batch, _, dl = planes[0].shape
-    one = np.broadcast_to(const_term(n, 1), (batch, 1, dl))
-    zero = np.broadcast_to(const_term(n, 0), (batch, 1, dl))
-    return compose(cmp, planes, k, np_add, np_mul, one, zero)
-
-
-def expected_terms(cmp, w, k, t):
-    """The same composition over term counts (Python integers: no overflow); 0 past 2^62."""
-    counts = compose(cmp, list(t), k, lambda x, y: x + y, lambda x, y: x * y, 1, 1)
-    return counts if counts < LIMIT else 0
+from tests.model import (CLEAR, CMPS, EQ, GE, GT, LE, LT, NE, compose_plain, const_term, decrypt_bits, encrypt_planes,
+                         full_width_cases, lib, np_plain, np_uint_eq, np_uint_lt, oracle_ops, plain_terms, rand_terms,
+                         ref_ops, u64s)
 
 
 def edge_ks(w, rng):
@@ -83,20 +21,6 @@ def edge_ks(w, rng):
     return sorted(x for x in ks if x <= top)
 
 
-def full_width_cases(w):
-    """(cmp, k) pairs at widths up to 64 whose result over fresh 1-term planes stays at most 4096 terms: EQ / NE with few
-    zero bits in k, LT / GE at the top (2w terms) and at 2^(w-1), GT / LE just below the top, and the ZERO constants (LT
-    at 0, GT at the top).  Picked by expected_terms: GT at small k is the expensive end (2^w terms at k = 0)."""
-    top = (1 << w) - 1
-    ks = {0, 1, top, top - 1, 1 << (w - 1), top ^ (1 << (w - 1)), top ^ 0x2D5, top ^ 0x3FF, top ^ (0b1011 << (w - 5)),
-          top ^ ((1 << (w - 1)) | 1), (1 << (w - 1)) | 1}
-    cases = sorted((c, k) for k in ks for c in CMPS.values() if 0 < expected_terms(c, w, k, [1] * w) <= 4096)
-    for must in ((EQ, top), (NE, top ^ 0x3FF), (LT, top), (GE, top), (LT, 1 << (w - 1)), (GE, 1 << (w - 1)), (LT, 0),
-                 (GT, top - 1), (LE, top - 1), (GT, top), (GT, top ^ 0x2D5)):
-        assert must in cases, must
-    return cases
-
-
 # -- the C ABI, host side ---------------------------------------------------------------------------------------------
 def test_plain_terms_formulas(lib):
     rng = np.random.default_rng(5)
@@ -104,7 +28,7 @@ def test_plain_terms_formulas(lib):
         for ts in ([1] * w, [int(x) for x in rng.integers(1, 4, w)], [2] * w):
             for k in edge_ks(w, rng):
                 for cmp in CMPS.values():
-                    want = expected_terms(cmp, w, k, ts)
+                    want = plain_terms(cmp, w, k, ts)
                     assert lib.csgn_uint_plain_terms(cmp, w, k, u64s(ts)) == want, (cmp, w, k, ts)
 
 
@@ -113,11 +37,11 @@ def test_plain_terms_fresh_planes():
     for w in range(1, 11):
         for k in range(1 << w):
             zeros = w - bin(k).count("1")
-            assert expected_terms(EQ, w, k, [1] * w) == 2 ** zeros
-            assert expected_terms(NE, w, k, [1] * w) == 2 ** zeros + 1
-            assert expected_terms(LT, w, k, [1] * w) <= 2 ** w
-            assert expected_terms(GT, w, k, [1] * w) <= 2 ** w - 1
-    assert expected_terms(LT, 8, 1, [1] * 8) == 256 and expected_terms(LT, 8, 255, [1] * 8) == 16 and expected_terms(EQ, 16, 0, [1] * 16) == 65536
+            assert plain_terms(EQ, w, k, [1] * w) == 2 ** zeros
+            assert plain_terms(NE, w, k, [1] * w) == 2 ** zeros + 1
+            assert plain_terms(LT, w, k, [1] * w) <= 2 ** w
+            assert plain_terms(GT, w, k, [1] * w) <= 2 ** w - 1
+    assert plain_terms(LT, 8, 1, [1] * 8) == 256 and plain_terms(LT, 8, 255, [1] * 8) == 16 and plain_terms(EQ, 16, 0, [1] * 16) == 65536
 
 
 def test_plain_terms_invalid(lib):
@@ -191,13 +115,13 @@ def test_plain_fails_without_gpu(lib):
 def test_plain_definition_matches_reference(oracle, ref, n, d, cmp, w, k, ts):
     planes = [rand_terms(n, 1, t, 40 + j)[0].ravel() for j, t in enumerate(ts)]
     add, mul = ref_ops(ref, n, d)
-    want = compose(cmp, planes, k, add, mul, const_term(n, 1), const_term(n, 0))
+    want = compose_plain(cmp, planes, k, add, mul, const_term(n, 1), const_term(n, 0))
     add, mul = oracle_ops(oracle, n)
-    got = compose(cmp, planes, k, add, mul, const_term(n, 1), const_term(n, 0))
+    got = compose_plain(cmp, planes, k, add, mul, const_term(n, 1), const_term(n, 0))
     words = np_plain(n, cmp, [p.reshape(1, t, -1) for p, t in zip(planes, ts)], k)
     dl = (n + 63) // 64
     assert np.array_equal(got, want)
-    assert got.size == expected_terms(cmp, w, k, ts) * dl
+    assert got.size == plain_terms(cmp, w, k, ts) * dl
     assert np.array_equal(words.ravel(), got)
 
 
@@ -210,28 +134,11 @@ def test_plain_definition_matches_oracle(oracle, n, cmp):
     for k in (0, 1, 37, 63, 32, 21):
         words = np_plain(n, cmp, planes, k)
         for e in range(batch):
-            want = compose(cmp, [p[e].ravel() for p in planes], k, add, mul, const_term(n, 1), const_term(n, 0))
+            want = compose_plain(cmp, [p[e].ravel() for p in planes], k, add, mul, const_term(n, 1), const_term(n, 0))
             assert np.array_equal(words[e].ravel(), want), (k, e)
 
 
 # -- decryptions: clear comparisons, and today's route through constant(k) ------------------------------------------------
-CLEAR = {EQ: np.equal, NE: np.not_equal, LT: np.less, LE: np.less_equal, GT: np.greater, GE: np.greater_equal}
-
-
-def encrypt_planes(oracle, n, key, values, w, seed):
-    dl = (n + 63) // 64
-    count = len(values)
-    out = []
-    for j in range(w):
-        bits = ((np.asarray(values, dtype=np.uint64) >> np.uint64(j)) & np.uint64(1)).astype(np.uint8)
-        out.append(oracle.encrypt_seq(n, key, bits, glibc_draws(seed * 100 + j, count * (n + 2)))[0].reshape(count, 1, dl))
-    return out
-
-
-def decrypt_bits(oracle, n, key, words):
-    return np.array([oracle.decrypt_canonical(n, key, words[e].ravel()) for e in range(words.shape[0])], dtype=bool)
-
-
 @pytest.mark.parametrize("w", [1, 2, 3, 4])
 def test_plain_truth_tables(oracle, w):
     n, d = 127, 8
@@ -279,9 +186,9 @@ def test_plain_definition_at_64_bits(lib, oracle, n):
     add, mul = oracle_ops(oracle, n)
     for cmp, k in full_width_cases(w):
         words = np_plain(n, cmp, planes, k)
-        assert words.shape[1] == lib.csgn_uint_plain_terms(cmp, w, k, u64s([1] * w)) == expected_terms(cmp, w, k, [1] * w)
+        assert words.shape[1] == lib.csgn_uint_plain_terms(cmp, w, k, u64s([1] * w)) == plain_terms(cmp, w, k, [1] * w)
         if words.shape[1] <= 256:
-            want = compose(cmp, [p[1].ravel() for p in planes], k, add, mul, const_term(n, 1), const_term(n, 0))
+            want = compose_plain(cmp, [p[1].ravel() for p in planes], k, add, mul, const_term(n, 1), const_term(n, 0))
             assert np.array_equal(words[1].ravel(), want), (cmp, k)
     d = 8
     key, _ = oracle.keygen(n, d, glibc_draws(64, 64 * d + 64))
@@ -290,6 +197,6 @@ def test_plain_definition_at_64_bits(lib, oracle, n):
     planes = encrypt_planes(oracle, n, key, values, w, 640)
     for k in (0, 1, 1 << 63, (1 << 63) - 1, (1 << 64) - 1, (1 << 64) - 2):
         for cmp, f in CLEAR.items():
-            if 0 < expected_terms(cmp, w, k, [1] * w) <= 4096:
+            if 0 < plain_terms(cmp, w, k, [1] * w) <= 4096:
                 got = decrypt_bits(oracle, n, key, np_plain(n, cmp, planes, k))
                 assert np.array_equal(got, f(values, np.uint64(k))), (cmp, k)

@@ -7,17 +7,10 @@ import numpy as np
 import pytest
 
 from oracle.binding import glibc_draws
-from tests.test_gates_cpu import rand_terms
-from tests.test_uint_plain_cpu import (CLEAR, CMPS, EQ, GE, GT, LE, LT, NE, decrypt_bits, encrypt_planes,
-                                       expected_terms, full_width_cases, np_plain, u64s)
+from tests.model import (CLEAR, CMPS, EQ, GE, GT, LE, LT, NE, decrypt_bits, encrypt_planes, full_width_cases, hip,
+                         np_plain, plain_terms, rand_terms, u64s)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def hip():
-    from csgn_amd.batch import HipPath
-    return HipPath(0)
 
 
 def edge_ks(w):
@@ -62,7 +55,7 @@ def test_plain_words_wide(hip, knobs, w):
     top = (1 << w) - 1
     for k in (top, top ^ 0x0F0, 0xA5A5 & top, 1 << (w - 1), 4711 & top):
         for cmp in (EQ, NE, LT, LE, GT, GE):
-            if expected_terms(cmp, w, k, [1] * w) <= 4096:
+            if plain_terms(cmp, w, k, [1] * w) <= 4096:
                 check_forms(hip, knobs, n, cmp, planes, k)
 
 
@@ -89,7 +82,7 @@ def test_plain_64bit_by_decryption(hip, knobs, oracle):
     ks = [0, 1, 1 << 63, (1 << 63) - 1, (1 << 63) + 1, (1 << 64) - 1, (1 << 64) - 2, int(values[-1]) | 0xFFFFFFFFFFFF0000]
     for k in ks:
         for cmp, f in CLEAR.items():
-            if not 0 < expected_terms(cmp, w, k, [1] * w) <= 4096:
+            if not 0 < plain_terms(cmp, w, k, [1] * w) <= 4096:
                 continue
             got = run(hip, n, cmp, planes, k).reshape(len(values), -1, (n + 63) // 64)
             assert np.array_equal(got.reshape(-1), np_plain(n, cmp, planes, k).ravel()), (cmp, k)

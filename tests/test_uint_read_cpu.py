@@ -10,64 +10,8 @@ import numpy as np
 import pytest
 
 from oracle.binding import glibc_draws
-from tests.test_gates_cpu import const_term, np_add, np_mul, oracle_ops, rand_terms, ref_ops
-from tests.test_uint_plain_cpu import EQ, compose, decrypt_bits, encrypt_planes
-
-LIMIT = 1 << 62
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from csgn_amd import build, capi
-    build.build_hip()
-    return capi.load_library()
-
-
-def u64s(xs):
-    return (C.c_uint64 * max(len(xs), 1))(*[int(x) for x in xs])
-
-
-# -- the definition, over any (add, mul, one, zero) ---------------------------------------------------------------------
-def compose_read(index, rows, add, mul, one, zero):
-    """include/csgn_hip.h's definition, in exactly its order.  index: the v index planes; rows[r][j]: plane j of table
-    row r.  One value per table plane."""
-    out = None
-    for r in range(len(rows)):
-        eq = compose(EQ, index, r, add, mul, one, zero)
-        prods = [mul(eq, d) for d in rows[r]]
-        out = prods if out is None else [add(o, p) for o, p in zip(out, prods)]
-    return out
-
-
-def np_read(n, index, table):
-    """Words of every output over uniform planes: index[k] = words[batch, s_k, dL], table[j] = words[rows, t_j, dL]."""
-    batch, _, dl = index[0].shape
-    one = np.broadcast_to(const_term(n, 1), (batch, 1, dl))
-    zero = np.broadcast_to(const_term(n, 0), (batch, 1, dl))
-    rows = [[np.broadcast_to(d[r:r + 1], (batch,) + d.shape[1:]) for d in table] for r in range(table[0].shape[0])]
-    return compose_read(index, rows, np_add, np_mul, one, zero)
-
-
-def np_read_fast(n, index, table):
-    """np_read's words with every output concatenated once (a left-nested sum of concatenations is one
-    concatenation): linear in the output, for the large shapes of the device tests."""
-    from tests.test_uint_plain_cpu import np_plain
-    outs = [[] for _ in table]
-    for r in range(table[0].shape[0]):
-        eq = np_plain(n, EQ, index, r)
-        for j, d in enumerate(table):
-            outs[j].append(np_mul(eq, np.broadcast_to(d[r:r + 1], (eq.shape[0],) + d.shape[1:])))
-    return [np.concatenate(o, axis=1) for o in outs]
-
-
-def expected_E(s, rows):
-    """E by the definition itself: the EQ terms of every row."""
-    return sum(int(np.prod([(sk if (r >> k) & 1 else sk + 1) for k, sk in enumerate(s)], dtype=object))
-               for r in range(rows))
-
-
-def c_E(lib, v, s, rows):
-    return int(lib.csgn_uint_read_terms(v, u64s(s) if s is not None else None, rows))
+from tests.model import (LIMIT, c_E, compose_read, const_term, decrypt_value, encrypt_planes, lib, np_add, np_read,
+                         np_read_fast, oracle_ops, rand_terms, read_terms, ref_ops, u64s)
 
 
 # -- the term order the kernel decodes (csgn_uint_read.hip): no table of terms, a walk from the top bit ----------------
@@ -105,7 +49,7 @@ def np_read_decoded(n, index, table):
     batch, _, dl = index[0].shape
     s = [p.shape[1] for p in index]
     rows = table[0].shape[0]
-    E = expected_E(s, rows)
+    E = read_terms(s, rows)
     one = const_term(n, 1)
     outs = []
     for d in table:
@@ -138,7 +82,7 @@ def test_terms_formula(lib):
                                 int(rng.integers(1, (1 << v) + 1))}):
                 if rows < 1 or rows > 1 << v:
                     continue
-                assert c_E(lib, v, s, rows) == expected_E(s, rows), (v, s, rows)
+                assert c_E(lib, v, s, rows) == read_terms(s, rows), (v, s, rows)
         full = int(np.prod([2 * x + 1 for x in s], dtype=object))
         assert c_E(lib, v, s, 1 << v) == full
     # one row: only x == 0 matches, every bit a zero: prod (s_k + 1)
@@ -251,7 +195,7 @@ def test_definition_matches_reference(oracle, ref, n, d, case):
     got = compose_read(index, row_words, add, mul, one, zero)
     words = np_read(n, [x.reshape(1, sk, -1) for x, sk in zip(index, s)], table)
     dl = (n + 63) // 64
-    E = expected_E(s, rows)
+    E = read_terms(s, rows)
     for j in range(len(t)):
         assert np.array_equal(got[j], want[j]), j
         assert got[j].size == t[j] * E * dl
@@ -311,13 +255,6 @@ def test_decode_fresh_subsets():
 
 
 # -- decryptions -------------------------------------------------------------------------------------------------------
-def decrypt_value(oracle, n, key, outs):
-    v = np.zeros(outs[0].shape[0], dtype=np.uint64)
-    for j, o in enumerate(outs):
-        v |= decrypt_bits(oracle, n, key, o).astype(np.uint64) << np.uint64(j)
-    return v
-
-
 @pytest.mark.parametrize("v", [1, 2, 3, 4])
 def test_truth_tables_decrypt(oracle, v):
     n, d = 127, 8
@@ -350,6 +287,6 @@ def test_multi_term_planes_decrypt(oracle):
     zt = encrypt_planes(oracle, n, key, np.zeros(rows, dtype=np.uint64), 1, 305)[0].reshape(rows, 1, -1)
     table[1] = np_add(table[1], zt)
     outs = np_read(n, index, table)
-    assert outs[1].shape[1] == 2 * expected_E([1, 2, 3], rows)
+    assert outs[1].shape[1] == 2 * read_terms([1, 2, 3], rows)
     got = decrypt_value(oracle, n, key, outs)
     assert [int(g) for g in got] == [int(values[x]) if x < rows else 0 for x in range(1 << v)]

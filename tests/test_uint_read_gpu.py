@@ -9,17 +9,9 @@ import pytest
 import torch
 
 from oracle.binding import glibc_draws
-from tests.test_gates_cpu import const_term, rand_terms
-from tests.test_uint_read_cpu import decrypt_value, expected_E, np_read_fast, u64s
-from tests.test_uint_plain_cpu import encrypt_planes
+from tests.model import const_term, decrypt_value, encrypt_planes, hip, np_read_fast, rand_terms, read_terms, u64s
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def hip():
-    from csgn_amd.batch import HipPath
-    return HipPath(0)
 
 
 def run(hip, n, index, table):
@@ -60,7 +52,7 @@ def test_read_words(hip, knobs, n, v, tmode):
     index = [rand_terms(n, batch, sk, 400 + 7 * k + sk) for k, sk in enumerate(s)]
     partial = int(rng.integers(1, (1 << v) + 1))
     for rows in sorted({1, (1 << v) - 1, 1 << v, partial} - {0}):
-        E = expected_E(s, rows)
+        E = read_terms(s, rows)
         for w in (1, 8, 64):
             t = term_counts(tmode, w, rng)
             if batch * sum(t) * E * dl * 8 > (48 << 20):
@@ -183,7 +175,7 @@ def test_read_graph_capture_and_replay(hip, knobs):
     knobs.set("uint_read_fused", 1)
     dx = [hip.upload(p.ravel()) for p in index]
     dt = [hip.upload(p.ravel()) for p in table]
-    E = expected_E([1] * v, rows)
+    E = read_terms([1] * v, rows)
     dl = (n + 63) // 64
     outs = [hip.empty_words(batch * tj * E * dl) for tj in t]
     assert hip.lib.csgn_uint_read_kernel(n, batch, v, u64s([1] * v), rows, w, u64s(t)) == b"k_uint_read"
