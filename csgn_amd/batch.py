@@ -208,6 +208,36 @@ class HipPath:
         check(self.lib.csgn_uint_plain(n_bits, cmp, batch, w, k, h_planes, h_terms, _ptr(out), self.stream))
         return out[: batch * total * dl]
 
+    def uint_addk_terms(self, terms, k: int):
+        """csgn_uint_addk_terms: the terms per element of every plane of a + k and, last, of the carry-out; None for an
+        invalid shape."""
+        w = len(terms)
+        h_terms = (C.c_uint64 * max(w, 1))(*[int(t) for t in terms])
+        out = (C.c_uint64 * (w + 1))()
+        return list(out) if self.lib.csgn_uint_addk_terms(w, k, h_terms, out) else None
+
+    def uint_addk(self, n_bits: int, batch: int, planes, terms, k: int, negate: bool = False, carry: bool = False,
+                  outs=None, carry_out: Optional[torch.Tensor] = None):
+        """csgn_uint_addk: the w-bit integer `planes` (bit 0 first; plane j a uniform batch of terms[j] terms per
+        element) plus the public constant k, ONE appended to every plane when `negate`.  Returns (output tensors,
+        carry-out tensor or None); fresh tensors unless `outs` / `carry_out` are given."""
+        w = len(planes)
+        assert w == len(terms)
+        T = self.uint_addk_terms(terms, k)
+        assert T, "bad width, constant or shape"
+        dl = self.default_len(n_bits)
+        sizes = [batch * (t + (1 if negate else 0)) * dl for t in T[:w]]
+        if outs is None:
+            outs = [self.empty_words(max(s, 1)) for s in sizes]
+        if carry and carry_out is None:
+            carry_out = self.empty_words(max(batch * T[w] * dl, 1))
+        h_terms = (C.c_uint64 * w)(*[int(t) for t in terms])
+        h_planes = (C.c_void_p * w)(*[_ptr(p) for p in planes])
+        h_outs = (C.c_void_p * w)(*[_ptr(o) for o in outs])
+        check(self.lib.csgn_uint_addk(n_bits, batch, w, k, 1 if negate else 0, h_planes, h_terms, h_outs,
+                                      _ptr(carry_out) if carry else None, self.stream))
+        return [o[:s] for o, s in zip(outs, sizes)], (carry_out[: batch * T[w] * dl] if carry else None)
+
     def uint_lut_create(self, table, in_width: int, out_width: int, terms) -> int:
         """csgn_uint_lut_create: the public table (2^in_width entries < 2^out_width) compiled for planes of terms[i] terms
         per element.  Returns the handle; release it with self.lib.csgn_uint_lut_destroy."""

@@ -135,6 +135,9 @@ SIGNATURES = {
     "csgn_uint_plain_terms": (u64, [C.c_int, u64, u64, C.POINTER(u64)]),
     "csgn_uint_plain_kernel": (C.c_char_p, [u64, C.c_int, u64, u64, u64, C.POINTER(u64)]),
     "csgn_uint_plain": (C.c_int, [u64, C.c_int, u64, u64, u64, C.POINTER(vp), C.POINTER(u64), vp, vp]),
+    "csgn_uint_addk_terms": (C.c_int, [u64, u64, C.POINTER(u64), C.POINTER(u64)]),
+    "csgn_uint_addk_kernel": (C.c_char_p, [u64, u64, u64, u64, C.POINTER(u64), C.c_int]),
+    "csgn_uint_addk": (C.c_int, [u64, u64, u64, u64, C.c_int, C.POINTER(vp), C.POINTER(u64), C.POINTER(vp), vp, vp]),
     "csgn_uint_lut_anf": (C.c_int, [u64, u64, C.POINTER(u64), C.POINTER(u64)]),
     "csgn_uint_lut_terms": (C.c_int, [u64, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
     "csgn_uint_lut_create": (C.c_int, [u64, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(vp)]),

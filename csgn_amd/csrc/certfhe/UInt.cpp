@@ -280,6 +280,89 @@ CiphertextBatch comparePlain(int cmp, const UIntBatch &a, uint64_t k, const char
     return base != cmp ? logicNot(r) : r;
 }
 
+// ------------------------------------------------------------------ arithmetic with a public constant
+
+void requireConstant(const UIntBatch &a, uint64_t k, const char *who)
+{
+    if (a.width() < 64 && (k >> a.width()) != 0)
+        throw std::invalid_argument(std::string("certFHE::") + who + ": the constant does not fit in the width");
+}
+
+uint64_t maskOf(unsigned w) { return w == 64 ? ~0ull : (1ull << w) - 1; }
+
+// the planes of a + k (csgn_uint_addk's definition), each followed by ONE when `negate`; *carry_out = the last carry
+std::vector<CiphertextBatch> addPlain(const UIntBatch &a, uint64_t k, bool negate, CiphertextBatch *carry_out,
+                                      const char *who)
+{
+    requireConstant(a, k, who);
+    const unsigned w = a.width();
+    const Context &ctx = a.context();
+    std::vector<uint64_t> terms(w), T(w + 1);
+    bool uniform = true;
+    for (unsigned j = 0; j < w; ++j) {
+        terms[j] = termsOf(a.plane(j));                  // a ragged plane: its largest element, a bound
+        uniform = uniform && a.plane(j).uniform();
+    }
+    if (!csgn_uint_addk_terms(w, k, terms.data(), T.data()))
+        checked(0, ctx, who);
+    for (unsigned j = 0; j < w; ++j)
+        checked(T[j] + (negate ? 1 : 0), ctx, who);
+    if (carry_out)
+        checked(T[w], ctx, who);
+    std::vector<CiphertextBatch> out;
+    if (uniform) {
+        for (unsigned j = 0; j < w; ++j)
+            out.push_back(UIntAccess::make(ctx, a.size(), T[j] + (negate ? 1 : 0)));
+        CiphertextBatch carry = UIntAccess::make(ctx, carry_out ? a.size() : 0, T[w]);
+        if (a.size()) {
+            std::vector<const uint64_t *> planes(w);
+            std::vector<uint64_t *> outs(w);
+            for (unsigned j = 0; j < w; ++j) {
+                planes[j] = a.plane(j).deviceValues();
+                outs[j] = UIntAccess::words(out[j]);
+            }
+            detail::check(csgn_uint_addk(ctx.getN(), a.size(), w, k, negate ? 1 : 0, planes.data(), terms.data(),
+                                         outs.data(), carry_out ? UIntAccess::words(carry) : nullptr, detail::stream()),
+                          "csgn_uint_addk");
+        }
+        if (carry_out)
+            *carry_out = carry;
+        return out;
+    }
+    // ragged: the definition itself through the batch operators
+    if (k == 0) {
+        for (unsigned j = 0; j < w; ++j)
+            out.push_back(negate ? logicNot(a.plane(j)) : a.plane(j));
+        if (carry_out)
+            *carry_out = constantBatch(ctx, std::vector<unsigned char>(a.size(), 0));
+        return out;
+    }
+    const unsigned m = (unsigned)__builtin_ctzll(k);
+    CiphertextBatch c = a.plane(m);
+    for (unsigned j = 0; j < w; ++j) {
+        const bool bit = (k >> j) & 1u;
+        CiphertextBatch o = a.plane(j);
+        if (j == m) {
+            o = logicNot(o);
+        } else if (j > m) {
+            o = o + c;
+            if (bit)
+                o = logicNot(o);
+            if (j + 1 < w || carry_out)
+                c = bit ? (c * logicNot(a.plane(j))) + a.plane(j) : c * a.plane(j);
+        }
+        out.push_back(negate ? logicNot(o) : o);
+    }
+    if (carry_out)
+        *carry_out = c;
+    return out;
+}
+
+CiphertextBatch zeros(const UIntBatch &a)
+{
+    return constantBatch(a.context(), std::vector<unsigned char>(a.size(), 0));
+}
+
 } // namespace
 
 // ------------------------------------------------------------------ UIntBatch
@@ -446,13 +529,138 @@ std::vector<uint64_t> UIntBatch::decrypt(const SecretKey &key) const
 UIntBatch UIntBatch::operator+(const UIntBatch &rhs) const
 {
     requireSame(*this, rhs, "UIntBatch::operator+");
-    return UIntBatch(add(*this, rhs));
+    return UIntBatch(certFHE::add(*this, rhs));   // the helper above, not the member
 }
 
 UIntBatch UIntBatch::operator-(const UIntBatch &rhs) const
 {
     requireSame(*this, rhs, "UIntBatch::operator-");
     return UIntBatch(sub(*this, rhs));
+}
+
+UIntBatch UIntBatch::operator+(uint64_t k) const { return UIntBatch(addPlain(*this, k, false, nullptr, "UIntBatch::operator+")); }
+
+UIntBatch UIntBatch::add(uint64_t k, CiphertextBatch *carry_out) const
+{
+    return UIntBatch(addPlain(*this, k, false, carry_out, "UIntBatch::add"));
+}
+
+UIntBatch UIntBatch::operator-(uint64_t k) const
+{
+    requireConstant(*this, k, "UIntBatch::operator-");
+    return UIntBatch(addPlain(*this, (0 - k) & maskOf(width()), false, nullptr, "UIntBatch::operator-"));
+}
+
+UIntBatch operator-(uint64_t k, const UIntBatch &a)
+{
+    requireConstant(a, k, "operator-");
+    return UIntBatch(addPlain(a, ~k & maskOf(a.width()), true, nullptr, "operator-"));
+}
+
+UIntBatch UIntBatch::operator-() const { return UIntBatch(addPlain(*this, maskOf(width()), true, nullptr, "UIntBatch::operator-")); }
+
+UIntBatch UIntBatch::operator~() const
+{
+    for (unsigned j = 0; j < width(); ++j)
+        gateTerms(CSGN_GATE_NOT, 0, termsOf(planes_[j]), 0, context(), "UIntBatch::operator~");
+    std::vector<CiphertextBatch> planes;
+    for (unsigned j = 0; j < width(); ++j)
+        planes.push_back(logicNot(planes_[j]));
+    return UIntBatch(planes);
+}
+
+UIntBatch UIntBatch::operator&(const UIntBatch &rhs) const
+{
+    requireSame(*this, rhs, "UIntBatch::operator&");
+    for (unsigned j = 0; j < width(); ++j) {
+        const uint64_t ta = termsOf(planes_[j]), tb = termsOf(rhs.planes_[j]);
+        checked(tb && ta > (kMaxWords / tb) ? 0 : ta * tb, context(), "UIntBatch::operator&");
+    }
+    std::vector<CiphertextBatch> planes;
+    for (unsigned j = 0; j < width(); ++j)
+        planes.push_back(planes_[j] * rhs.planes_[j]);
+    return UIntBatch(planes);
+}
+
+UIntBatch UIntBatch::operator|(const UIntBatch &rhs) const
+{
+    requireSame(*this, rhs, "UIntBatch::operator|");
+    for (unsigned j = 0; j < width(); ++j)
+        gateTerms(CSGN_GATE_OR, 0, termsOf(planes_[j]), termsOf(rhs.planes_[j]), context(), "UIntBatch::operator|");
+    std::vector<CiphertextBatch> planes;
+    for (unsigned j = 0; j < width(); ++j)
+        planes.push_back(logicOr(planes_[j], rhs.planes_[j]));
+    return UIntBatch(planes);
+}
+
+UIntBatch UIntBatch::operator^(const UIntBatch &rhs) const
+{
+    requireSame(*this, rhs, "UIntBatch::operator^");
+    for (unsigned j = 0; j < width(); ++j)
+        checked(termsOf(planes_[j]) + termsOf(rhs.planes_[j]), context(), "UIntBatch::operator^");
+    std::vector<CiphertextBatch> planes;
+    for (unsigned j = 0; j < width(); ++j)
+        planes.push_back(planes_[j] + rhs.planes_[j]);
+    return UIntBatch(planes);
+}
+
+UIntBatch UIntBatch::operator&(uint64_t k) const
+{
+    requireConstant(*this, k, "UIntBatch::operator&");
+    std::vector<CiphertextBatch> planes;
+    const CiphertextBatch zero = zeros(*this);            // one shared payload for every cleared plane
+    for (unsigned j = 0; j < width(); ++j)
+        planes.push_back((k >> j) & 1u ? planes_[j] : zero);
+    return UIntBatch(planes);
+}
+
+UIntBatch UIntBatch::operator|(uint64_t k) const
+{
+    requireConstant(*this, k, "UIntBatch::operator|");
+    std::vector<CiphertextBatch> planes;
+    const CiphertextBatch one = ones(planes_[0]);         // one shared payload for every set plane
+    for (unsigned j = 0; j < width(); ++j)
+        planes.push_back((k >> j) & 1u ? one : planes_[j]);
+    return UIntBatch(planes);
+}
+
+UIntBatch UIntBatch::operator^(uint64_t k) const
+{
+    requireConstant(*this, k, "UIntBatch::operator^");
+    for (unsigned j = 0; j < width(); ++j)
+        if ((k >> j) & 1u)
+            gateTerms(CSGN_GATE_NOT, 0, termsOf(planes_[j]), 0, context(), "UIntBatch::operator^");
+    std::vector<CiphertextBatch> planes;
+    for (unsigned j = 0; j < width(); ++j)
+        planes.push_back((k >> j) & 1u ? logicNot(planes_[j]) : planes_[j]);
+    return UIntBatch(planes);
+}
+
+UIntBatch UIntBatch::shiftLeft(unsigned s) const
+{
+    std::vector<CiphertextBatch> planes;
+    const CiphertextBatch zero = zeros(*this);            // one shared payload for every filled plane
+    for (unsigned j = 0; j < width(); ++j)
+        planes.push_back(j >= s ? planes_[j - s] : zero);
+    return UIntBatch(planes);
+}
+
+UIntBatch UIntBatch::shiftRight(unsigned s) const
+{
+    std::vector<CiphertextBatch> planes;
+    const CiphertextBatch zero = zeros(*this);
+    for (unsigned j = 0; j < width(); ++j)
+        planes.push_back(s < width() && j < width() - s ? planes_[j + s] : zero);
+    return UIntBatch(planes);
+}
+
+UIntBatch UIntBatch::rotateLeft(unsigned s) const
+{
+    const unsigned w = width();
+    std::vector<CiphertextBatch> planes;
+    for (unsigned j = 0; j < w; ++j)
+        planes.push_back(planes_[(j + w - s % w) % w]);
+    return UIntBatch(planes);
 }
 
 // ------------------------------------------------------------------ comparisons and select

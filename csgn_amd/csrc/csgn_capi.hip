@@ -1126,6 +1126,50 @@ int csgn_uint_plain(uint64_t n_bits, int cmp, uint64_t batch, uint64_t width, ui
     return CSGN_OK;
 }
 
+int csgn_uint_addk_terms(uint64_t width, uint64_t k, const uint64_t *h_terms, uint64_t *h_out_terms)
+{
+    return csgn::uint_addk_terms(width, k, (const u64 *)h_terms, (u64 *)h_out_terms) ? 1 : 0;
+}
+
+const char *csgn_uint_addk_kernel(uint64_t n_bits, uint64_t batch, uint64_t width, uint64_t k, const uint64_t *h_terms,
+                                  int with_carry)
+{
+    return csgn::uint_addk_kernel_name(n_bits, batch, width, k, (const u64 *)h_terms, with_carry != 0);
+}
+
+int csgn_uint_addk(uint64_t n_bits, uint64_t batch, uint64_t width, uint64_t k, int negate_out,
+                   const uint64_t *const *h_planes, const uint64_t *h_terms, uint64_t *const *h_outs, uint64_t *d_carry,
+                   void *stream)
+{
+    if (int rc = check_n(n_bits))
+        return rc;
+    REQUIRE(width >= 1 && width <= 64, "width %llu outside 1..64", (unsigned long long)width);
+    REQUIRE(width == 64 || (k >> width) == 0, "constant %llu does not fit in %llu bits", (unsigned long long)k,
+            (unsigned long long)width);
+    REQUIRE(h_planes && h_terms && h_outs, "null host pointer");
+    uint64_t T[65];
+    REQUIRE(csgn::uint_addk_terms(width, k, (const u64 *)h_terms, (u64 *)T),
+            "integer + constant: a plane has no terms, or a term count overflows");
+    const uint64_t dl = csgn_default_len(n_bits);
+    for (uint64_t j = 0; j < width + (d_carry ? 1 : 0); ++j) {
+        const uint64_t terms = T[j] + (negate_out && j < width ? 1 : 0);
+        if (!product_below(terms, dl, 1, 1ull << 31))
+            return fail(CSGN_ERR_UNSUPPORTED, "integer + constant: plane %llu has %llu terms per element, past 2^31 words",
+                        (unsigned long long)j, (unsigned long long)terms);
+        if (!product_below(batch, terms, dl, 1ull << 60))
+            return fail(CSGN_ERR_UNSUPPORTED, "batch of %llu elements: size overflows", (unsigned long long)batch);
+    }
+    if (int rc = require_device("csgn_uint_addk"))
+        return rc;
+    if (batch == 0)
+        return CSGN_OK;
+    for (uint64_t j = 0; j < width; ++j)
+        REQUIRE(h_planes[j] && h_outs[j], "null device pointer (plane %llu)", (unsigned long long)j);
+    HIP_TRY(csgn::uint_addk(n_bits, batch, width, k, negate_out != 0, (const u64 *const *)h_planes, (const u64 *)h_terms,
+                            (u64 *const *)h_outs, (u64 *)d_carry, S(stream)));
+    return CSGN_OK;
+}
+
 int csgn_uint_lut_anf(uint64_t in_width, uint64_t out_width, const uint64_t *h_table, uint64_t *h_anf)
 {
     if (int rc = csgn::uint_lut_anf(in_width, out_width, (const u64 *)h_table, (u64 *)h_anf))

@@ -1,6 +1,7 @@
 // csgn_device.h -- helpers shared by the kernel translation units (csgn_mul.hip, csgn_add.hip, csgn_decrypt.hip,
 // csgn_encrypt.hip, csgn_permute.hip, csgn_compact.hip, csgn_harness.hip, and the uniform-batch families
-// csgn_gates.hip, csgn_uint.hip, csgn_uint_plain.hip, csgn_uint_lut.hip, csgn_uint_read.hip, csgn_gather.hip):
+// csgn_gates.hip, csgn_uint.hip, csgn_uint_plain.hip, csgn_uint_addk.hip, csgn_uint_lut.hip, csgn_uint_read.hip,
+// csgn_gather.hip):
 // 16-/8-byte unit access and the choice between them, the ONE and ZERO terms' units, FastDiv tables in kernel
 // arguments, the XCD-contiguous block order, CSR pair search, the LDS subset tables of DESIGN §4.15, launch limits,
 // the term-count limit and the knob-dependent launch choices (csgn_tuning.h).  Everything has internal linkage (one
@@ -392,6 +393,43 @@ inline int ragged_chunks(u64 total_units)
     while (c < 8 && total_units / (256u * 2u * (u64)c) >= 8192u)
         c *= 2;
     return c;
+}
+
+// ------------------------------------------------------------------------- chain decode
+// The left-nested product / sum chains over the planes a_j and n_j = a_j + ONE that csgn_uint_plain.hip and
+// csgn_uint_addk.hip decode.  Args is the kernel's level table, by value in its arguments: plane[j], t[j], pend[j]
+// (the start of a sum level's tail, above every index for a product level), rad (the factor's length as a FastDiv),
+// base (the level that ends every walk) and U (units per term).
+// term i of a list that is a_j (i < t_j) or n_j (i == t_j: ONE); the load is issued unconditionally (clamped)
+template <typename Unit, typename Args>
+__device__ inline Unit chain_term(const Args &a, u32 j, u64 elem_units, u32 i, u32 k, Unit one)
+{
+    const u32 tj = a.t[j];
+    const Unit *p = reinterpret_cast<const Unit *>(a.plane[j]);
+    const Unit v = p[elem_units * tj + (u64)min(i, tj - 1u) * a.U + k];
+    return i < tj ? v : one;
+}
+
+// levels j = hi down to lo (inclusive, lo >= base) applied to idx; returns true when a tail or the base ended the walk
+template <typename Unit, typename Args>
+__device__ inline bool chain_walk(const Args &a, u32 hi, u32 lo, u64 eu, u32 k, Unit one, u32 &idx, Unit &v)
+{
+    for (u32 j = hi + 1u; j-- > lo;) {
+        if (j == a.base) {
+            v &= chain_term<Unit>(a, j, eu, idx, k, one);
+            return true;
+        }
+        const u32 pe = a.pend[j];
+        if (idx >= pe) {                                  // a sum level's tail: a_j, or n_j
+            v &= chain_term<Unit>(a, j, eu, idx - pe, k, one);
+            return true;
+        }
+        const FastDiv dr = a.rad.at(j);
+        const u32 q = csgn_fastdiv(idx, dr), d = idx - q * dr.d;
+        idx = q;
+        v &= chain_term<Unit>(a, j, eu, d, k, one);
+    }
+    return false;
 }
 
 // ------------------------------------------------------------------------- subset tables

@@ -142,6 +142,13 @@ const char *uint_plain_kernel_name(u64 n_bits, int cmp, u64 batch, u64 width, u6
 hipError_t uint_plain(u64 n_bits, int cmp, u64 batch, u64 width, u64 k, const u64 *const *planes, const u64 *terms,
                       u64 *out, hipStream_t s);
 
+// a w-bit integer of uniform planes plus a public constant (csgn_uint_addk.hip), include/csgn_hip.h's definition;
+// out_terms: width + 1 counts, the last the carry-out's; outs: width planes; carry: nullptr = not computed
+bool uint_addk_terms(u64 width, u64 k, const u64 *terms, u64 *out_terms);   // false: invalid argument or overflow
+const char *uint_addk_kernel_name(u64 n_bits, u64 batch, u64 width, u64 k, const u64 *terms, bool carry);
+hipError_t uint_addk(u64 n_bits, u64 batch, u64 width, u64 k, bool negate_out, const u64 *const *planes, const u64 *terms,
+                     u64 *const *outs, u64 *carry, hipStream_t s);
+
 // a public lookup table applied to a w-bit integer of uniform planes (csgn_uint_lut.hip), include/csgn_hip.h's
 // definition: output j is the sum, ascending in S, of the monomials M_S of the table's Mobius transform with bit j set.
 // A plan compiles one table for one vector of plane term counts; it lives in a csgn_uint_lut object of the caller's.

@@ -34,6 +34,7 @@ const Knob kKnobs[TUNE_COUNT] = {
     {"uint_plain_fused", -1},
     {"uint_lut_fused", -1},
     {"uint_read_fused", -1},
+    {"uint_addk_fused", -1},
 };
 
 // Knob values are PER HOST THREAD: a thread that sets a knob changes the dispatch of its own later

@@ -53,6 +53,7 @@ enum TuneKey {
     TUNE_UINT_PLAIN_FUSED, // comparisons with a public constant (csgn_uint_plain.hip): -1 = per shape, 0 = composed form (the tuned launchers level by level), 1 = fused kernel
     TUNE_UINT_LUT_FUSED, // public lookup tables (csgn_uint_lut.hip): -1 = per shape, 0 = composed form (the tuned launchers monomial by monomial), 1 = fused kernel
     TUNE_UINT_READ_FUSED, // encrypted tables read at encrypted indices (csgn_uint_read.hip): -1 = per shape, 0 = composed form (the tuned launchers row by row), 1 = fused kernel
+    TUNE_UINT_ADDK_FUSED, // integer + public constant (csgn_uint_addk.hip): -1 = per shape, 0 = composed form (the tuned launchers plane by plane), 1 = fused kernel
     TUNE_COUNT
 };
 

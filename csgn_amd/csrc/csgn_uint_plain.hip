@@ -51,38 +51,6 @@ struct PlainArgs {
     u64 last_mask;
 };
 
-// term i of a list that is a_j (i < t_j) or n_j (i == t_j: ONE); the load is issued unconditionally (clamped)
-template <typename Unit>
-__device__ inline Unit plain_term(const PlainArgs &a, u32 j, u64 elem_units, u32 i, u32 k, Unit one)
-{
-    const u32 tj = a.t[j];
-    const Unit *p = reinterpret_cast<const Unit *>(a.plane[j]);
-    const Unit v = p[elem_units * tj + (u64)min(i, tj - 1u) * a.U + k];
-    return i < tj ? v : one;
-}
-
-// levels j = hi down to lo (inclusive, lo >= base) applied to idx; returns true when a tail or the base ended the walk
-template <typename Unit>
-__device__ inline bool plain_walk(const PlainArgs &a, u32 hi, u32 lo, u64 eu, u32 k, Unit one, u32 &idx, Unit &v)
-{
-    for (u32 j = hi + 1u; j-- > lo;) {
-        if (j == a.base) {
-            v &= plain_term<Unit>(a, j, eu, idx, k, one);
-            return true;
-        }
-        const u32 pe = a.pend[j];
-        if (idx >= pe) {                                  // a sum level's tail: a_j, or n_j
-            v &= plain_term<Unit>(a, j, eu, idx - pe, k, one);
-            return true;
-        }
-        const FastDiv dr = a.rad.at(j);
-        const u32 q = csgn_fastdiv(idx, dr), d = idx - q * dr.d;
-        idx = q;
-        v &= plain_term<Unit>(a, j, eu, d, k, one);
-    }
-    return false;
-}
-
 template <typename Unit>
 __global__ void __launch_bounds__(256) k_uint_plain(PlainArgs a)
 {
@@ -100,7 +68,7 @@ __global__ void __launch_bounds__(256) k_uint_plain(PlainArgs a)
     Unit fast_unit = one;
     for (u32 j = a.top + 1u; !a.zero && j-- > a.cut;)
         if ((a.unit >> j) & 1u)
-            fast_unit &= plain_term<Unit>(a, j, eu, 0u, k, one);
+            fast_unit &= chain_term<Unit>(a, j, eu, 0u, k, one);
     u32 key = 0xFFFFFFFFu;                                // the index that reached the cut, and the AND below it
     Unit below = one;
     for (u32 q = 0; q < nt; ++q) {
@@ -116,7 +84,7 @@ __global__ void __launch_bounds__(256) k_uint_plain(PlainArgs a)
             for (u32 j = a.top + 1u; j-- > a.cut;) {
                 const u32 pe = a.pend[j];
                 if (idx >= pe) {                          // a sum level's tail
-                    v &= plain_term<Unit>(a, j, eu, idx - pe, k, one);
+                    v &= chain_term<Unit>(a, j, eu, idx - pe, k, one);
                     stop = j;
                     break;
                 }
@@ -125,7 +93,7 @@ __global__ void __launch_bounds__(256) k_uint_plain(PlainArgs a)
                 const FastDiv dr = a.rad.at(j);
                 const u32 q = csgn_fastdiv(idx, dr), d = idx - q * dr.d;
                 idx = q;
-                v &= plain_term<Unit>(a, j, eu, d, k, one);
+                v &= chain_term<Unit>(a, j, eu, d, k, one);
             }
             const bool done = stop != 0xFFFFFFFFu;
             if (done) {
@@ -133,13 +101,13 @@ __global__ void __launch_bounds__(256) k_uint_plain(PlainArgs a)
                 // share of any large result)
                 for (u32 j = a.top + 1u; j-- > stop + 1u;)
                     if ((a.unit >> j) & 1u)
-                        v &= plain_term<Unit>(a, j, eu, 0u, k, one);
+                        v &= chain_term<Unit>(a, j, eu, 0u, k, one);
             } else {
                 v &= fast_unit;
                 if (idx != key) {
                     key = idx;
                     below = one;
-                    plain_walk<Unit>(a, a.cut - 1u, a.base, eu, k, one, idx, below);
+                    chain_walk<Unit>(a, a.cut - 1u, a.base, eu, k, one, idx, below);
                 }
                 v &= below;
             }

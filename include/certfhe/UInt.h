@@ -51,6 +51,31 @@
 // the same words.  Every size is checked before anything is allocated: std::invalid_argument for a mismatched context,
 // a table of 0 or more than 2^v rows, or an output plane past 2^31 words per element.
 //
+// ARITHMETIC WITH A PUBLIC CONSTANT (k < 2^width, the same for every element; std::invalid_argument otherwise) spends no
+// term on k: with m the lowest set bit of k the carry into plane j > m is the chain c_m = a_m, then k_j ? (c * n_j) + a_j
+// : c * a_j (n_j = logicNot(a_j), c the LEFT operand), and the words are csgn_uint_addk's (include/csgn_hip.h):
+//     a + k              k == 0: a copy.  out_j = a_j (j < m), a_m + ONE, then k_j ? (a_j + c) + ONE : a_j + c  mod 2^w
+//     a.add(k, &carry)   the same planes, and the c left after the top plane (ZERO when k == 0)
+//     a - k              a + ((2^w - k) mod 2^w)
+//     k - a              logicNot of every plane of a + (~k mod 2^w)
+//     -a                 0 - a: logicNot of every plane of a + (2^w - 1)
+//     ~a                 logicNot(a_j) on every plane
+// With fresh planes plane j of a + 1 has 2 terms (a_j + a_0 * ... * a_{j-1}) where a + constant(1) has 2^j + 1; in
+// general the carry has at most 2^(set bits of k from m to j) - 1 terms.  Uniform planes take one csgn_uint_addk call
+// (one kernel for every plane and the carry-out); ragged ones are composed from the CiphertextBatch operators and
+// Gates.h with the same words.  Every plane's size is checked before anything is allocated.
+//
+// BITWISE OPERATORS AND SHIFTS.  Between two integers of one width, context and count, per plane:
+//     a & b              a_j * b_j            a | b     logicOr(a_j, b_j)            a ^ b     a_j + b_j
+// With a public constant (k < 2^width) and for a public distance s nothing is computed on ciphertext words beyond a
+// logicNot; a kept plane is the SAME immutable payload as the source's, not a copy:
+//     a & k              a_j where k_j = 1, ZERO (one term, constantBatch) elsewhere
+//     a | k              ONE (constantBatch) where k_j = 1, a_j elsewhere
+//     a ^ k              logicNot(a_j) where k_j = 1, a_j elsewhere
+//     a.shiftLeft(s)     plane j = a_{j-s} for j >= s, ZERO below; every plane ZERO when s >= width
+//     a.shiftRight(s)    plane j = a_{j+s} for j + s < width, ZERO above; every plane ZERO when s >= width
+//     a.rotateLeft(s)    plane j = a_{(j - s) mod width}, s taken mod width
+//
 // Uniform planes run one csgn_uint_step (or csgn_gate_uniform) call per bit; ragged ones (what compact() may return)
 // are composed from the CiphertextBatch operators and Gates.h, with the same words.  Only the running carry or
 // accumulator is kept alive between bits.
@@ -102,7 +127,29 @@ class UIntBatch {
 
     UIntBatch operator+(const UIntBatch &rhs) const;
     UIntBatch operator-(const UIntBatch &rhs) const;
+
+    // with the public constant k < 2^width (std::invalid_argument otherwise), modulo 2^width
+    UIntBatch operator+(uint64_t k) const;
+    UIntBatch operator-(uint64_t k) const;
+    friend UIntBatch operator-(uint64_t k, const UIntBatch &a);     // k - a
+    UIntBatch operator-() const;                                    // -a
+    // a + k and the bit that left (carry_out may be null: the same as operator+)
+    UIntBatch add(uint64_t k, CiphertextBatch *carry_out) const;
+
+    UIntBatch operator~() const;
+    UIntBatch operator&(const UIntBatch &rhs) const;
+    UIntBatch operator|(const UIntBatch &rhs) const;
+    UIntBatch operator^(const UIntBatch &rhs) const;
+    UIntBatch operator&(uint64_t k) const;
+    UIntBatch operator|(uint64_t k) const;
+    UIntBatch operator^(uint64_t k) const;
+    // public distance s; kept planes share the source's payload
+    UIntBatch shiftLeft(unsigned s) const;
+    UIntBatch shiftRight(unsigned s) const;
+    UIntBatch rotateLeft(unsigned s) const;
 };
+
+UIntBatch operator-(uint64_t k, const UIntBatch &a);
 
 // one encrypted bit per element
 CiphertextBatch equalTo(const UIntBatch &a, const UIntBatch &b);

@@ -667,6 +667,54 @@ const char *csgn_uint_plain_kernel(uint64_t n_bits, int cmp, uint64_t batch, uin
 int csgn_uint_plain(uint64_t n_bits, int cmp, uint64_t batch, uint64_t width, uint64_t k,
                     const uint64_t *const *h_planes, const uint64_t *h_terms, uint64_t *d_out, void *stream);
 
+/* csgn_uint_addk: a + k mod 2^w, planes a_0 ... a_{w-1} least significant first, plane j uniform with t_j terms per
+ * element, 1 <= w <= 64, k < 2^w public and the same for every element.  A fixed composition of the reference's
+ * operator+ / operator* with ONE, in this order; n_j = a_j + ONE; the running carry c is always the LEFT operand of a
+ * product:
+ *     k == 0:            out_j = a_j for every j (a copy, the same terms in the same order); carry-out = ZERO (one term)
+ *     m = lowest set bit of k
+ *     j <  m:            out_j = a_j
+ *     j == m:            out_m = a_m + ONE                       c = a_m
+ *     j >  m, k_j = 0:   out_j = a_j + c                         c = c * a_j
+ *     j >  m, k_j = 1:   out_j = (a_j + c) + ONE                 c = (c * n_j) + a_j
+ *     carry-out (optional, plane index w) = the c left after j = w-1
+ * Terms per element: T(c) after plane m is t_m; after a plane with k_j = 0 it is T(c) * t_j, with k_j = 1 it is
+ * T(c) * (t_j + 1) + t_j; out_j has t_j + T(c_j) + k_j terms for j > m, T(c_j) the count of the carry INTO plane j.
+ * With fresh planes T(c) never exceeds 2^(set bits of k from bit m up to bit j) - 1, and a + 1 has 2 terms in every
+ * plane.  (In clear bits: c * (1 ^ a) ^ a = a | c, the carry of a column whose constant bit is 1; c * a where it is 0.)
+ * Derived operations add no new words:
+ *     a - k      = a + ((2^w - k) mod 2^w)
+ *     ~a         = a_j + ONE on every plane                       (logicNot of Gates.h)
+ *     k - a      = ~(a + (~k mod 2^w))                            every plane of that sum, then + ONE
+ *     -a         = 0 - a = ~(a + (2^w - 1)) */
+/* Terms per element of every output into h_out_terms (host only): width + 1 counts, the last the carry-out's, without
+ * the ONE of negate_out.  Returns 1, or 0 for a width outside 1..64, k >= 2^width, a null pointer, a plane of 0 terms
+ * or a count of 2^62 or more (h_out_terms is then not written). */
+int csgn_uint_addk_terms(uint64_t width, uint64_t k, const uint64_t *h_terms, uint64_t *h_out_terms);
+/* Which form a csgn_uint_addk call of this shape takes (host only, a static string): "k_uint_addk" (one kernel writes
+ * every output plane and the carry-out, planes read in place, ONE and ZERO made in registers) or "composed" (the tuned
+ * csgn_add_uniform / csgn_mul_uniform / csgn_const_fill launchers plane by plane with pitched writes, the running carry
+ * in a block the library keeps per host thread and stream, up to 256 MiB, grown when a call needs more).  Knob "uint_addk_fused" (-1 per shape, 0 / 1 forced) decides;
+ * the words are the same.  Per shape, by measurement: composed for a single output plane (width 1 without
+ * the carry-out), where the chain terms walk 8 levels or more on average (a + 1 from 16 bits up), for outputs of 16 GiB
+ * or more with over 5 levels walked per term written, and where one element's planes pass a launch's 2^32 lanes; fused
+ * otherwise.  "" for an invalid shape. */
+const char *csgn_uint_addk_kernel(uint64_t n_bits, uint64_t batch, uint64_t width, uint64_t k, const uint64_t *h_terms,
+                                  int with_carry);
+/* The sum over `batch` elements: h_planes is a HOST array of `width` device pointers (plane j: batch * h_terms[j] * dL
+ * words, element after element), h_outs a HOST array of `width` device pointers (output j: batch * (T_j + (negate_out ?
+ * 1 : 0)) * dL words, T_j from csgn_uint_addk_terms), d_carry the carry-out (batch * T_width * dL words) or NULL: it is
+ * then not computed.  negate_out != 0 appends ONE to every output plane (that is k' - a for the caller who passed
+ * ~k'); the carry-out is never negated.  Inputs may alias one another; no output overlaps an input or another output.
+ * Limits: every output below 2^31 words per element (CSGN_ERR_UNSUPPORTED), batch * that < 2^60.  On the caller's
+ * stream, asynchronous; the fused form is one launch and graph-capturable.  The composed form is asynchronous once its
+ * thread's block for that stream is large enough; a call that has to allocate or grow it calls hipMalloc (refused with
+ * CSGN_ERR_HIP while the stream is capturing), and a temporary past 256 MiB is allocated for the call and freed behind
+ * it, which waits for the device.  No GPU: CSGN_ERR_NO_DEVICE, no CPU fallback. */
+int csgn_uint_addk(uint64_t n_bits, uint64_t batch, uint64_t width, uint64_t k, int negate_out,
+                   const uint64_t *const *h_planes, const uint64_t *h_terms, uint64_t *const *h_outs, uint64_t *d_carry,
+                   void *stream);
+
 /* A PUBLIC lookup table f applied to a w-bit integer (planes a_0..a_{w-1}, least significant first, plane i uniform with
  * t_i terms per element): out_width output planes, output j encrypting bit j of f(x).  in_width 1..16, out_width 1..64,
  * h_table: 2^in_width entries, each < 2^out_width.  The words are the table's algebraic normal form over the planes, a
