@@ -159,12 +159,16 @@ class HipPath:
     # -- gates ----------------------------------------------------------------------
     def gate_uniform(self, n_bits: int, gate: int, batch: int, a: torch.Tensor, t_a: int,
                      b: Optional[torch.Tensor] = None, t_b: int = 0, sel: Optional[torch.Tensor] = None,
-                     t_sel: int = 0, plain: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """csgn_gate_uniform: one of capi.CSGN_GATE_* over a uniform batch (plain: uint8 tensor, one bit per element)."""
+                     t_sel: int = 0, plain: Optional[torch.Tensor] = None,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """csgn_gate_uniform: one of capi.CSGN_GATE_* over a uniform batch (plain: uint8 tensor, one bit per element).
+        A fresh tensor unless `out` is given."""
         dl = self.default_len(n_bits)
         terms = int(self.lib.csgn_gate_terms(gate, t_sel, t_a, t_b))
         assert terms, "bad gate or shape"
-        out = self.empty_words(max(batch * terms * dl, 1))
+        if out is None:
+            out = self.empty_words(max(batch * terms * dl, 1))
+        assert out.numel() >= batch * terms * dl
         check(self.lib.csgn_gate_uniform(n_bits, gate, batch, t_sel, t_a, t_b, _ptr(sel), _ptr(a), _ptr(b),
                                          _ptr(plain), _ptr(out), self.stream))
         return out[: batch * terms * dl]
@@ -178,25 +182,33 @@ class HipPath:
 
     # -- bit-sliced integers ----------------------------------------------------------
     def uint_step(self, n_bits: int, step: int, batch: int, a: torch.Tensor, t_a: int, b: torch.Tensor, t_b: int,
-                  x: Optional[torch.Tensor] = None, t_x: int = 0, carry: bool = True):
+                  x: Optional[torch.Tensor] = None, t_x: int = 0, carry: bool = True, outs=None):
         """csgn_uint_step: one of capi.CSGN_UINT_* over a uniform batch.  Returns the output tensor, or (sum, carry) for
-        the ADD steps when `carry` (carry=False passes a null carry pointer: the carry is not computed)."""
+        the ADD steps when `carry` (carry=False passes a null carry pointer: the carry is not computed).  Fresh tensors
+        unless `outs` (one tensor, two with a carry) is given."""
         dl = self.default_len(n_bits)
         has_carry = carry and step in (capi.CSGN_UINT_ADD_HALF, capi.CSGN_UINT_ADD_FULL)
         terms0 = int(self.lib.csgn_uint_step_terms(step, 0, t_x, t_a, t_b))
         terms1 = int(self.lib.csgn_uint_step_terms(step, 1, t_x, t_a, t_b)) if has_carry else 0
         assert terms0 and (terms1 or not has_carry), "bad step or shape"
-        out0 = self.empty_words(max(batch * terms0 * dl, 1))
-        out1 = self.empty_words(max(batch * terms1 * dl, 1)) if has_carry else None
+        if outs is None:
+            outs = [self.empty_words(max(batch * terms0 * dl, 1))]
+            if has_carry:
+                outs.append(self.empty_words(max(batch * terms1 * dl, 1)))
+        assert len(outs) == (2 if has_carry else 1)
+        out0, out1 = outs[0], (outs[1] if has_carry else None)
+        assert out0.numel() >= batch * terms0 * dl and (out1 is None or out1.numel() >= batch * terms1 * dl)
         check(self.lib.csgn_uint_step(n_bits, step, batch, _ptr(x), t_x, _ptr(a), t_a, _ptr(b), t_b, _ptr(out0),
                                       _ptr(out1), self.stream))
         if has_carry:
             return out0[: batch * terms0 * dl], out1[: batch * terms1 * dl]
         return out0[: batch * terms0 * dl]
 
-    def uint_plain(self, n_bits: int, cmp: int, batch: int, planes, terms, k: int) -> torch.Tensor:
+    def uint_plain(self, n_bits: int, cmp: int, batch: int, planes, terms, k: int,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """csgn_uint_plain: one of capi.CSGN_UINT_PLAIN_* of the w-bit integer `planes` (bit 0 first; plane j a uniform
-        batch of terms[j] terms per element) against the public constant k.  Returns the output tensor."""
+        batch of terms[j] terms per element) against the public constant k.  Returns the output tensor (a fresh one
+        unless `out` is given)."""
         w = len(planes)
         assert w == len(terms)
         h_terms = (C.c_uint64 * max(w, 1))(*[int(t) for t in terms])
@@ -204,7 +216,9 @@ class HipPath:
         total = int(self.lib.csgn_uint_plain_terms(cmp, w, k, h_terms))
         assert total, "bad comparison or shape"
         dl = self.default_len(n_bits)
-        out = self.empty_words(max(batch * total * dl, 1))
+        if out is None:
+            out = self.empty_words(max(batch * total * dl, 1))
+        assert out.numel() >= batch * total * dl
         check(self.lib.csgn_uint_plain(n_bits, cmp, batch, w, k, h_planes, h_terms, _ptr(out), self.stream))
         return out[: batch * total * dl]
 
@@ -258,9 +272,10 @@ class HipPath:
         check(self.lib.csgn_uint_lut_apply(handle, n_bits, batch, h_planes, h_out, self.stream))
         return [o[: batch * int(t) * dl] for o, t in zip(outs, out_terms)]
 
-    def uint_lut(self, n_bits: int, batch: int, planes, terms, table, out_width: int):
+    def uint_lut(self, n_bits: int, batch: int, planes, terms, table, out_width: int, outs=None):
         """The public lookup table `table` applied to the w-bit integer `planes` (bit 0 first; plane i a uniform batch of
-        terms[i] terms per element): one tensor per output bit, T_j terms per element (csgn_uint_lut_terms)."""
+        terms[i] terms per element): one tensor per output bit, T_j terms per element (csgn_uint_lut_terms); fresh ones
+        unless `outs` is given."""
         w = len(planes)
         assert w == len(terms) and len(table) == 1 << w
         h_table = (C.c_uint64 * len(table))(*[int(v) for v in table])
@@ -269,7 +284,7 @@ class HipPath:
         check(self.lib.csgn_uint_lut_terms(w, out_width, h_table, h_terms, out_terms))
         handle = self.uint_lut_create(table, w, out_width, terms)
         try:
-            outs = self.uint_lut_apply(handle, n_bits, batch, planes, list(out_terms))
+            outs = self.uint_lut_apply(handle, n_bits, batch, planes, list(out_terms), outs)
             torch.cuda.current_stream(self.device).synchronize()
         finally:
             self.lib.csgn_uint_lut_destroy(handle)
@@ -300,12 +315,13 @@ class HipPath:
         return out[: count_out * t_src * dl]
 
     def gather_ragged(self, n_bits: int, count_in: int, src: torch.Tensor, src_off: torch.Tensor, count_out: int,
-                      index: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
-        """Plan + gather of a ragged (CSR) source; returns (words, output offsets).  Raises on a bad index."""
+                      index: Optional[torch.Tensor] = None, out=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Plan + gather of a ragged (CSR) source; returns (words, output offsets).  Raises on a bad index.  `out`: a
+        function of the planned word count that gives the tensor to write (default: a fresh one)."""
         rc, total, bad, out_off = self.gather_plan(count_in, count_out, index, src_off)
         check(rc)
         dl = self.default_len(n_bits)
-        out = self.empty_words(max(total * dl, 1))
+        out = self.empty_words(max(total * dl, 1)) if out is None else out(total * dl)
         check(self.lib.csgn_gather(n_bits, count_in, _ptr(src), _ptr(src_off), 0, count_out, _ptr(index), _ptr(out),
                                    _ptr(out_off), total, self.stream))
         return out[: total * dl], out_off

@@ -299,15 +299,16 @@ int gather_plan(u64 count_in, const u64 *src_off, u64 count_out, const u64 *idx,
         return 0;                                                  // a uniform tile: nothing to check or size
     const u64 nchunks = count_out / kGPlanChunk + 1;              // (the closing entry count_out belongs to a chunk)
     const u64 words = kGPlanStatus + nchunks;
-    u64 *stat = nullptr;
+    // the status words: a plain block the thread keeps (scratch_take, csgn_kernels.h); the call drains s before it
+    // returns, so the next call on s finds them free
+    bool owned = false;
+    u64 *stat = scratch_take(SCRATCH_GATHER, words * 8, s, owned, herr);
+    if (herr != hipSuccess)
+        return 1;
     auto fail = [&](hipError_t e) {
-        herr = e;
-        if (stat)
-            (void)hipFreeAsync(stat, s);
+        herr = scratch_done(stat, owned, e);
         return 1;
     };
-    if ((herr = hipMallocAsync(reinterpret_cast<void **>(&stat), words * 8, s)) != hipSuccess)
-        return 1;
     if ((herr = zero_words(stat, words, s)) != hipSuccess)
         return fail(herr);
     const FastDiv d_in = csgn_fastdiv_make(count_in ? (u32)count_in : 1u);
@@ -326,9 +327,9 @@ int gather_plan(u64 count_in, const u64 *src_off, u64 count_out, const u64 *idx,
     u64 h[2] = {0, 0};
     if ((herr = hipMemcpyAsync(h, stat, 16, hipMemcpyDeviceToHost, s)) != hipSuccess)
         return fail(herr);
-    if ((herr = hipFreeAsync(stat, s)) != hipSuccess)
-        return 1;
     if ((herr = hipStreamSynchronize(s)) != hipSuccess)
+        return fail(herr);
+    if ((herr = scratch_done(stat, owned, hipSuccess)) != hipSuccess)
         return 1;
     result[0] = h[0] ? 0 : h[1];
     result[1] = h[0];

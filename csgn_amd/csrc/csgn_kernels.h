@@ -196,6 +196,15 @@ const char *uint_read_kernel_name(u64 n_bits, u64 batch, u64 v, const u64 *s, u6
 hipError_t uint_read(u64 n_bits, u64 batch, u64 v, const u64 *const *index, const u64 *s, u64 rows, u64 w,
                      const u64 *const *table, const u64 *t, u64 *const *out, hipStream_t stream);
 
+// The temporaries of the composed forms and of the gather plan (csgn_scratch.cpp): a plain (hipMalloc) block the calling
+// thread keeps per stream and per user, never the stream-ordered pool.  Returns the block, or nullptr with e set
+// (hipErrorStreamCaptureUnsupported when the call would have to allocate while s is capturing).  owned: the block is
+// past the kept size and belongs to this call; scratch_done frees it behind the call's launches (waits for the device)
+// and passes e through.
+enum ScratchSlot { SCRATCH_UINT_PLAIN, SCRATCH_UINT_LUT, SCRATCH_UINT_READ, SCRATCH_UINT_ADDK, SCRATCH_GATHER, SCRATCH_SLOTS };
+u64 *scratch_take(ScratchSlot slot, size_t bytes, hipStream_t s, bool &owned, hipError_t &e);
+hipError_t scratch_done(u64 *block, bool owned, hipError_t e);
+
 hipError_t small_ops(u64 n_bits, u64 count, const ::csgn_small_op *ops, hipStream_t s);
 size_t decrypt_scratch_bytes(u64 batch, u64 total_terms);
 // out[i] = a[i] & b[i] (is_product) or a[i] ^ b[i]: Dec(a*b) = Dec(a) & Dec(b), Dec(a+b) = Dec(a) ^ Dec(b)

@@ -231,68 +231,8 @@ hipError_t addk_fused(const AddkShape &sh, u64 n_bits, u64 batch, bool neg, cons
     return hipSuccess;
 }
 
-// The composed form's temporary.  It does NOT come from the stream-ordered pool (hipMallocAsync): in a process that
-// also allocates and frees with hipMalloc / hipFree -- the classes' block cache does, around every operator -- kernels
-// read wrong data back from pool blocks (this form 4-21 of 30 processes, csgn_uint_plain's composed form
-// 30 of 30; a plain block, even one never synchronised or freed, 0 of 30).  Each host thread keeps one plain block per
-// stream it has used, up to kScratchKeep bytes, grown when a call needs more; re-use is ordered by that stream, so a
-// steady-state call allocates nothing and stays asynchronous.  A larger temporary is allocated for the call and freed
-// behind it, which waits for the device (owned = true).  Growing or allocating under stream capture is refused.
-constexpr size_t kScratchKeep = (size_t)256 << 20;
-constexpr size_t kScratchStreams = 8;
-
-struct ScratchBlock {
-    hipStream_t s;
-    void *p;
-    size_t bytes;
-};
-struct ScratchList {
-    std::vector<ScratchBlock> v;
-    ~ScratchList()
-    {
-        for (ScratchBlock &b : v)
-            (void)hipFree(b.p);
-    }
-};
-thread_local ScratchList g_scratch;
-
-u64 *scratch_take(size_t bytes, hipStream_t s, bool &owned, hipError_t &e)
-{
-    owned = false;
-    std::vector<ScratchBlock> &v = g_scratch.v;
-    size_t i = 0;
-    while (i < v.size() && v[i].s != s)
-        ++i;
-    if (i < v.size() && v[i].bytes >= bytes)
-        return static_cast<u64 *>(v[i].p);
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) {
-        e = hipErrorStreamCaptureUnsupported;
-        return nullptr;
-    }
-    void *p = nullptr;
-    if ((e = hipMalloc(&p, bytes)) != hipSuccess)
-        return nullptr;
-    if (bytes > kScratchKeep) {
-        owned = true;
-        return static_cast<u64 *>(p);
-    }
-    if (i < v.size()) {                                   // grown: hipFree waits for the work that reads the old block
-        (void)hipFree(v[i].p);
-        v[i].p = p;
-        v[i].bytes = bytes;
-    } else {
-        if (v.size() >= kScratchStreams) {
-            (void)hipFree(v.front().p);
-            v.erase(v.begin());
-        }
-        v.push_back(ScratchBlock{s, p, bytes});
-    }
-    return static_cast<u64 *>(p);
-}
-
 // The composed form: the same chain plane by plane through the tuned launchers with pitched writes.  The running carry
-// ping-pongs through one temporary block (scratch_take) -- c_m is a_m itself, read in place -- and n_j is the copy of
+// ping-pongs through one temporary block (scratch_take, csgn_kernels.h) -- c_m is a_m itself, read in place -- and n_j is the copy of
 // a_j followed by ONE; the last carry is written to `carry` when asked and not computed otherwise.
 hipError_t addk_composed(const AddkShape &sh, u64 n_bits, u64 batch, bool neg, const u64 *const *planes, const u64 *t,
                          u64 *const *outs, u64 *carry, hipStream_t s)
@@ -315,7 +255,7 @@ hipError_t addk_composed(const AddkShape &sh, u64 n_bits, u64 batch, bool neg, c
     const u64 words = batch * dL * (2 * maxL + maxN);
     bool owned = false;
     hipError_t e = hipSuccess;
-    u64 *block = words ? scratch_take(words * 8, s, owned, e) : nullptr;
+    u64 *block = words ? scratch_take(SCRATCH_UINT_ADDK, words * 8, s, owned, e) : nullptr;
     if (e != hipSuccess)
         return e;
     u64 *buf[2] = {block, block ? block + batch * maxL * dL : nullptr};
@@ -359,12 +299,7 @@ hipError_t addk_composed(const AddkShape &sh, u64 n_bits, u64 batch, bool neg, c
     }
     if (e == hipSuccess && sh.zero && carry)
         e = const_fill(n_bits, batch, nullptr, 0, carry, dL, s);
-    if (owned) {                                          // past what the thread keeps: released once the stream drains
-        const hipError_t f = hipFree(block);
-        if (e == hipSuccess)
-            e = f;
-    }
-    return e;
+    return scratch_done(block, owned, e);
 }
 
 } // namespace

@@ -217,7 +217,7 @@ hipError_t lut_fused(const LutPlan &p, u64 n_bits, u64 batch, const u64 *const *
 
 // The composed form: every monomial through the tuned launchers, written into its slice of the output (pitch T_j):
 // ONE by csgn_const_fill, one plane by the strided copy, a product left to right, the last factor written in place.
-// The partial products ping-pong through one stream-ordered block (hipMallocAsync).
+// The partial products ping-pong through one temporary block (scratch_take, csgn_kernels.h).
 hipError_t lut_composed(const LutPlan &p, u64 n_bits, u64 batch, const u64 *const *planes, u64 *const *out,
                         hipStream_t s)
 {
@@ -235,13 +235,11 @@ hipError_t lut_composed(const LutPlan &p, u64 n_bits, u64 batch, const u64 *cons
                     maxP = std::max(maxP, prod);
             }
     }
-    u64 *block = nullptr;
-    if (maxP) {
-        const hipError_t e = hipMallocAsync(reinterpret_cast<void **>(&block), 2 * batch * maxP * dL * 8, s);
-        if (e != hipSuccess)
-            return e;
-    }
+    bool owned = false;
     hipError_t e = hipSuccess;
+    u64 *block = maxP ? scratch_take(SCRATCH_UINT_LUT, 2 * batch * maxP * dL * 8, s, owned, e) : nullptr;
+    if (e != hipSuccess)
+        return e;
     for (u32 j = 0; j < p.m && e == hipSuccess; ++j) {
         const u64 pitch = p.T[j] * dL;
         if (p.mbase[j + 1] == p.mbase[j]) {
@@ -277,12 +275,7 @@ hipError_t lut_composed(const LutPlan &p, u64 n_bits, u64 batch, const u64 *cons
             }
         }
     }
-    if (block) {
-        const hipError_t f = hipFreeAsync(block, s);
-        if (e == hipSuccess)
-            e = f;
-    }
-    return e;
+    return scratch_done(block, owned, e);
 }
 
 } // namespace

@@ -259,7 +259,7 @@ hipError_t plain_fused(const PlainShape &sh, u64 n_bits, u64 batch, const u64 *c
 
 // The composed form: the same chain through the tuned launchers, level by level, each level's value written whole
 // before the next reads it.  n_j is the copy of a_j followed by ONE (csgn_gate_uniform NOT's words).  The running values
-// ping-pong through one stream-ordered block (hipMallocAsync); the last level writes d_out.
+// ping-pong through one temporary block (scratch_take, csgn_kernels.h); the last level writes d_out.
 hipError_t plain_composed(const PlainShape &sh, u64 n_bits, u64 batch, const u64 *const *planes, const u64 *t, u64 *out,
                           hipStream_t s)
 {
@@ -285,16 +285,14 @@ hipError_t plain_composed(const PlainShape &sh, u64 n_bits, u64 batch, const u64
     for (u32 j = sh.base + 1; j <= top; ++j)
         if ((sh.nfac >> j) & 1u)
             maxN = std::max(maxN, t[j] + 1);
-    u64 *block = nullptr;
     const u64 words = batch * dL * (2 * maxL + maxN);
-    if (words) {
-        const hipError_t e = hipMallocAsync(reinterpret_cast<void **>(&block), words * 8, s);
-        if (e != hipSuccess)
-            return e;
-    }
+    bool owned = false;
+    hipError_t e = hipSuccess;
+    u64 *block = words ? scratch_take(SCRATCH_UINT_PLAIN, words * 8, s, owned, e) : nullptr;
+    if (e != hipSuccess)
+        return e;
     u64 *buf[2] = {block, block ? block + batch * maxL * dL : nullptr};
     u64 *nbuf = block ? block + 2 * batch * maxL * dL : nullptr;
-    hipError_t e = hipSuccess;
     u64 *cur = sh.base == top ? out : buf[0];
     e = list(sh.base, (sh.nfac >> sh.base) & 1u, cur, (sh.base == top ? sh.T : sh.L[sh.base]) * dL);
     for (u32 j = sh.base + 1; j <= top && e == hipSuccess; ++j) {
@@ -315,12 +313,7 @@ hipError_t plain_composed(const PlainShape &sh, u64 n_bits, u64 batch, const u64
     }
     if (e == hipSuccess && sh.neg)
         e = const_fill(n_bits, batch, nullptr, 1, out + (sh.T - 1) * dL, pitchT, s);
-    if (block) {
-        const hipError_t f = hipFreeAsync(block, s);
-        if (e == hipSuccess)
-            e = f;
-    }
-    return e;
+    return scratch_done(block, owned, e);
 }
 
 } // namespace

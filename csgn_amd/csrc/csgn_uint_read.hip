@@ -250,7 +250,8 @@ hipError_t read_fused(u64 n_bits, u64 batch, u64 v, const u64 *const *index, con
 
 // The composed form, row by row through the tuned launchers: EQ(x, r) by csgn_uint_plain into a temporary, row r of
 // every table plane broadcast to the batch by one csgn_gather_planes (tile form), then csgn_mul_uniform of the two into
-// r's slice of every output (pitch T_j).  The temporaries live in one stream-ordered block (hipMallocAsync).
+// r's slice of every output (pitch T_j).  The temporaries live in one temporary block (scratch_take,
+// csgn_kernels.h), apart from the one csgn_uint_plain's composed form may take for EQ.
 hipError_t read_composed(u64 n_bits, u64 batch, u64 v, const u64 *const *index, const u64 *s, u64 rows, u64 w,
                          const u64 *const *table, const u64 *t, u64 *const *out, u64 E, hipStream_t st)
 {
@@ -260,8 +261,9 @@ hipError_t read_composed(u64 n_bits, u64 batch, u64 v, const u64 *const *index, 
         max_eq *= s[k] + 1;
     for (u64 j = 0; j < w; ++j)
         sumt += t[j];
-    u64 *block = nullptr;
-    hipError_t e = hipMallocAsync(reinterpret_cast<void **>(&block), batch * (max_eq + sumt) * dL * 8, st);
+    bool owned = false;
+    hipError_t e = hipSuccess;
+    u64 *block = scratch_take(SCRATCH_UINT_READ, batch * (max_eq + sumt) * dL * 8, st, owned, e);
     if (e != hipSuccess)
         return e;
     u64 *eq = block;
@@ -284,8 +286,7 @@ hipError_t read_composed(u64 n_bits, u64 batch, u64 v, const u64 *const *index, 
             e = mul_uniform(n_bits, batch, er, t[j], eq, row[j], out[j] + off * t[j] * dL, 0, st, t[j] * E * dL);
         off += er;
     }
-    const hipError_t f = hipFreeAsync(block, st);
-    return e == hipSuccess ? f : e;
+    return scratch_done(block, owned, e);
 }
 
 } // namespace

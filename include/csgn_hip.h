@@ -654,9 +654,10 @@ enum { CSGN_UINT_PLAIN_EQ = 1, CSGN_UINT_PLAIN_NE, CSGN_UINT_PLAIN_LT, CSGN_UINT
 uint64_t csgn_uint_plain_terms(int cmp, uint64_t width, uint64_t k, const uint64_t *h_terms);
 /* Which form a csgn_uint_plain call of this shape takes (host only, a static string): "k_uint_plain" (one kernel writes
  * the whole comparison, planes read in place, ONE and ZERO made in registers) or "composed" (the tuned
- * csgn_mul_uniform / csgn_add_uniform / csgn_const_fill launchers level by level, the running value in a stream-ordered
- * temporary block: hipMallocAsync).  Knob "uint_plain_fused" (-1 per shape, 0 / 1 forced) decides; the words are the
- * same.  Per shape: composed for width 1 and the ZERO results, fused otherwise.  "" for an invalid shape. */
+ * csgn_mul_uniform / csgn_add_uniform / csgn_const_fill launchers level by level, the running value in a temporary
+ * block the calling thread keeps, under csgn_uint_addk's rules for its composed form).  Knob "uint_plain_fused" (-1 per shape, 0 / 1 forced) decides; the words are the
+ * same.  Per shape (the knob at -1; a forced 0 / 1 holds for every shape): composed for width 1 and the ZERO results,
+ * fused otherwise.  "" for an invalid shape. */
 const char *csgn_uint_plain_kernel(uint64_t n_bits, int cmp, uint64_t batch, uint64_t width, uint64_t k,
                                    const uint64_t *h_terms);
 /* One comparison over `batch` elements: h_planes is a HOST array of `width` device pointers (plane j: batch *
@@ -741,8 +742,8 @@ int csgn_uint_lut_create(uint64_t in_width, uint64_t out_width, const uint64_t *
 void csgn_uint_lut_destroy(csgn_uint_lut *lut);
 /* Which form a csgn_uint_lut_apply call takes (host only, a static string): "k_uint_lut" (one kernel writes every
  * output plane, planes read in place, ONE and ZERO made in registers) or "composed" (csgn_mul_uniform /
- * csgn_add_uniform / csgn_const_fill monomial by monomial into the outputs' slices, partial products in a
- * stream-ordered block: hipMallocAsync).  Knob "uint_lut_fused" (-1 per shape, 0 / 1 forced) decides; the words are the
+ * csgn_add_uniform / csgn_const_fill monomial by monomial into the outputs' slices, partial products in a temporary
+ * block the calling thread keeps, under csgn_uint_addk's rules for its composed form).  Knob "uint_lut_fused" (-1 per shape, 0 / 1 forced) decides; the words are the
  * same.  Per shape: fused.  "" for a null table or n_bits of 0. */
 const char *csgn_uint_lut_kernel(uint64_t n_bits, const csgn_uint_lut *lut, uint64_t batch);
 /* Applies the table over `batch` elements: h_planes is a HOST array of in_width device pointers (plane i: batch * t_i
@@ -813,7 +814,7 @@ const char *csgn_gather_kernel(uint64_t n_bits, uint64_t count_out, int ragged, 
 uint64_t csgn_uint_read_terms(uint64_t index_width, const uint64_t *h_index_terms, uint64_t rows);
 /* Which form a csgn_uint_read call of this shape takes (host only, a static string): "k_uint_read" (one kernel writes
  * every output plane, planes read in place, ONE made in registers) or "composed" (per row r: csgn_uint_plain's EQ into
- * a stream-ordered temporary, the broadcast of row r by csgn_gather_planes' tile form, csgn_mul_uniform into r's slice
+ * a temporary the calling thread keeps (csgn_uint_addk's rules for its composed form), the broadcast of row r by csgn_gather_planes' tile form, csgn_mul_uniform into r's slice
  * of every output).  Knob "uint_read_fused" (-1 per shape, 0 / 1 forced) decides; the words are the same.  Per shape:
  * fused.  "" for an invalid shape (n_bits 0, a bad width, rows or term count). */
 const char *csgn_uint_read_kernel(uint64_t n_bits, uint64_t batch, uint64_t index_width, const uint64_t *h_index_terms,

@@ -2,8 +2,11 @@
 //   gates_driver single    single-Ciphertext gates: words == the operators' composition, decryptions == the gate
 //   gates_driver batch     CiphertextBatch gates, uniform and ragged (compact() output)
 //   gates_driver circuit   BatchCircuit: 4-bit equality and 6-bit unsigned less-than over 1000 random pairs
+//   gates_driver forms    "<shape> -> <form>": the form csgn_gate_uniform_kernel names under the process's knob
 // Prints "<mode> ok" and exits 0, or names the first mismatch and exits 1.
 #include "driver.h"
+
+#include "csgn_hip.h"
 
 using namespace certFHE;
 
@@ -175,9 +178,25 @@ int circuit()
     return 0;
 }
 
+// No device work: the form csgn_gate_uniform_kernel names for the shapes of batch (300 elements at N=1247, fresh
+// operands) and for products past the fused / pitched cut, under the knob the process was started with.
+int forms()
+{
+    const char *names[] = {"", "NOT", "XNOR", "NAND", "OR", "NOR", "MUX", "ADD_PLAIN", "MUL_PLAIN"};
+    const uint64_t shapes[][3] = {{1, 1, 1}, {1, 3, 3}, {1, 9, 8}, {2, 3, 3}};      // t_sel, t_a, t_b
+    for (const auto &t : shapes)
+        for (int g = CSGN_GATE_NOT; g <= CSGN_GATE_MUL_PLAIN; ++g) {
+            const char *form = csgn_gate_uniform_kernel(1247, g, 300, t[0], t[1], t[2]);
+            expect(form && *form, std::string(names[g]) + " has a form");
+            printf("%s ts=%llu ta=%llu tb=%llu -> %s\n", names[g], (unsigned long long)t[0], (unsigned long long)t[1],
+                   (unsigned long long)t[2], form ? form : "");
+        }
+    return 0;
+}
+
 } // namespace
 
 int main(int argc, char **argv)
 {
-    return runModes(argc, argv, 12345, "gates_driver", {{"single", single}, {"batch", batch}, {"circuit", circuit}});
+    return runModes(argc, argv, 12345, "gates_driver", {{"single", single}, {"batch", batch}, {"circuit", circuit}, {"forms", forms}});
 }

@@ -8,8 +8,11 @@
 //                              std::invalid_argument before anything is allocated
 //   uint_addk_driver shared    the planes a shift, a rotate or a constant mask keeps are the source's payloads
 //   uint_addk_driver nodevice  without a GPU the classes throw
+//   uint_addk_driver forms   "<shape> -> <form>": the form csgn_uint_addk_kernel names under the process's knob
 // Prints "<mode> ok" and exits 0, or names the first mismatch and exits 1.
 #include "driver.h"
+
+#include "csgn_hip.h"
 
 #include <chrono>
 #include <stdexcept>
@@ -125,6 +128,13 @@ void checkOperators(const SecretKey &key, const UIntBatch &a, const UIntBatch &b
     }
 }
 
+// the constants ops adds, shared with forms: their carries stay small over fresh planes (few set bits above the lowest)
+std::vector<uint64_t> addConstants(unsigned w)
+{
+    const uint64_t all = maskOf(w);
+    return {0, 1, 2, 1ull << (w - 1), all & ~(all >> 6), 100, (1ull << (w - 1)) | 5};
+}
+
 int ops()
 {
     Context ctx(1247, 16);
@@ -136,7 +146,7 @@ int ops()
         const std::string tag = " w=" + std::to_string(w);
         // constants whose carries stay small over fresh planes: few set bits above the lowest
         const uint64_t all = maskOf(w);
-        std::vector<uint64_t> ks = {0, 1, 2, 1ull << (w - 1), all & ~(all >> 6), 100, (1ull << (w - 1)) | 5};
+        std::vector<uint64_t> ks = addConstants(w);
         std::vector<uint64_t> sub_ks = {0, all, 1ull << (w - 1), all - 99}, rsub_ks = {all, all ^ 1, all ^ 100, all >> 1};
         if (w == 8) {
             ks.push_back(255);
@@ -302,10 +312,33 @@ int nodevice()
     return 0;
 }
 
+// No device work: the form csgn_uint_addk_kernel names for the shapes of ops (64 elements at N=1247, fresh planes, with
+// and without the carry-out) and for one shape past a launch's 2^32 lanes, under the knob the process was started with.
+int forms()
+{
+    for (unsigned w : {8u, 32u}) {
+        const std::vector<uint64_t> terms(w, 1);
+        std::vector<uint64_t> ks = addConstants(w);
+        if (w == 8)
+            ks.push_back(255);
+        for (uint64_t k : ks)
+            for (int carry = 0; carry <= 1; ++carry) {
+                const char *form = csgn_uint_addk_kernel(1247, 64, w, k, terms.data(), carry);
+                expect(form && *form, "a + " + std::to_string(k) + " has a form");
+                printf("w=%u k=%llu carry=%d -> %s\n", w, (unsigned long long)k, carry, form ? form : "");
+            }
+    }
+    // a + (2^28 - 1) over fresh planes: plane j has 2^j + 1 terms, 2^28 terms of 20 words in all, past 2^32 lanes
+    const std::vector<uint64_t> terms(28, 1);
+    const char *form = csgn_uint_addk_kernel(1247, 1, 28, (1ull << 28) - 1, terms.data(), 0);
+    printf("w=28 k=%llu carry=0 -> %s\n", (unsigned long long)((1ull << 28) - 1), form ? form : "");
+    return 0;
+}
+
 } // namespace
 
 int main(int argc, char **argv)
 {
     return runModes(argc, argv, 4718, "uint_addk_driver",
-                    {{"ops", ops}, {"ragged", ragged}, {"errors", errors}, {"shared", shared}, {"nodevice", nodevice}});
+                    {{"ops", ops}, {"ragged", ragged}, {"errors", errors}, {"shared", shared}, {"nodevice", nodevice}, {"forms", forms}});
 }

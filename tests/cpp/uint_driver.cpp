@@ -4,8 +4,11 @@
 //   uint_driver ragged    the same from compacted (ragged) planes: same decryptions, words == the composition
 //   uint_driver encrypt   reproducible encrypt == CiphertextBatch::encrypt plane by plane; argument checks
 //   uint_driver oversize  a width whose steps exceed 2^31 words per element throws before anything is allocated
+//   uint_driver forms     "<shape> -> <form>": the form csgn_uint_step_kernel names under the process's knob
 // Prints "<mode> ok" and exits 0, or names the first mismatch and exits 1.
 #include "driver.h"
+
+#include "csgn_hip.h"
 
 #include <chrono>
 #include <stdexcept>
@@ -262,10 +265,25 @@ int oversize()
     return 0;
 }
 
+// No device work: the form csgn_uint_step_kernel names for the steps of ops (1000 elements at N=127, fresh planes, the
+// running carry / accumulator of the sizes the chains reach), under the knob the process was started with.
+int forms()
+{
+    const char *names[] = {"", "ADD_HALF", "ADD_FULL", "EQ_STEP", "LT_FIRST", "LT_STEP"};
+    const uint64_t tx[] = {1, 3, 9, 27, 200};
+    for (uint64_t x : tx)
+        for (int s = CSGN_UINT_ADD_HALF; s <= CSGN_UINT_LT_STEP; ++s) {
+            const char *form = csgn_uint_step_kernel(127, s, 1000, x, 1, 1);
+            expect(form && *form, std::string(names[s]) + " has a form");
+            printf("%s tx=%llu ta=1 tb=1 -> %s\n", names[s], (unsigned long long)x, form ? form : "");
+        }
+    return 0;
+}
+
 } // namespace
 
 int main(int argc, char **argv)
 {
     return runModes(argc, argv, 4242, "uint_driver",
-                    {{"ops", ops}, {"ragged", ragged}, {"encrypt", encrypt}, {"oversize", oversize}});
+                    {{"ops", ops}, {"ragged", ragged}, {"encrypt", encrypt}, {"oversize", oversize}, {"forms", forms}});
 }

@@ -6,8 +6,11 @@
 //   uint_lut_driver ragged    compacted (ragged) planes: elements holding the same terms as the uniform planes give the
 //                             same words; every word == the definition; decryptions == the table
 //   uint_lut_driver oversize  a lookup past 2^31 words per element throws before anything is allocated; bad tables throw
+//   uint_lut_driver forms   "<shape> -> <form>": the form csgn_uint_lut_kernel names under the process's knob
 // Prints "<mode> ok" and exits 0, or names the first mismatch and exits 1.
 #include "driver.h"
+
+#include "csgn_hip.h"
 
 #include <chrono>
 #include <stdexcept>
@@ -235,10 +238,28 @@ int oversize()
     return 0;
 }
 
+// The form csgn_uint_lut_kernel names for the table and shapes of sbox (fresh planes, 1000 and 40 elements), under the
+// knob the process was started with.  A compiled table is uploaded when it is made: this mode needs the device.
+int forms()
+{
+    const std::vector<uint64_t> table = aesSbox(), terms(8, 1);
+    csgn_uint_lut *lut = nullptr;
+    expect(csgn_uint_lut_create(8, 8, table.data(), terms.data(), &lut) == CSGN_OK && lut, "the table compiles");
+    if (!lut)
+        return 0;
+    for (uint64_t count : {(uint64_t)1000, (uint64_t)40}) {
+        const char *form = csgn_uint_lut_kernel(1247, lut, count);
+        expect(form && *form, "the lookup has a form");
+        printf("sbox count=%llu -> %s\n", (unsigned long long)count, form ? form : "");
+    }
+    csgn_uint_lut_destroy(lut);
+    return 0;
+}
+
 } // namespace
 
 int main(int argc, char **argv)
 {
     return runModes(argc, argv, 4711, "uint_lut_driver",
-                    {{"sbox", sbox}, {"two", two}, {"ragged", ragged}, {"oversize", oversize}});
+                    {{"sbox", sbox}, {"two", two}, {"ragged", ragged}, {"oversize", oversize}, {"forms", forms}});
 }

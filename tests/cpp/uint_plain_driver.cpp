@@ -5,8 +5,12 @@
 //   uint_plain_driver ragged    compacted (ragged) planes: elements holding the same terms as the uniform planes give
 //                               the same words; every word == the definition; decryptions == clear comparisons
 //   uint_plain_driver oversize  a comparison past 2^31 words per element throws before anything is allocated
+//   uint_plain_driver forms     "<shape> -> <form>" for the shapes of ops (fresh planes, the edge constants): the form
+//                               csgn_uint_plain_kernel names under the knob the process was started with
 // Prints "<mode> ok" and exits 0, or names the first mismatch and exits 1.
 #include "driver.h"
+
+#include "csgn_hip.h"
 
 #include <chrono>
 #include <stdexcept>
@@ -73,10 +77,22 @@ CiphertextBatch definition(Cmp c, const UIntBatch &a, uint64_t k)
     return base != c ? logicNot(r) : r;
 }
 
-std::vector<uint64_t> constants(unsigned w, const std::vector<uint64_t> &v)
+// the shapes of ops, shared with forms: widths 1..kMaxWidth, countOf(w) elements, the edge constants (ops adds a random
+// constant and the first value)
+const unsigned kMaxWidth = 16;
+size_t countOf(unsigned w) { return w <= 8 ? 300 : 20; }
+
+std::vector<uint64_t> edgeConstants(unsigned w)
 {
     const uint64_t all = (1ull << w) - 1;
-    std::vector<uint64_t> ks = {0, 1, all, 1ull << (w - 1), all ^ 1, 0x5555 & all, rnd(w), v[0]};
+    return {0, 1, all, 1ull << (w - 1), all ^ 1, 0x5555 & all};
+}
+
+std::vector<uint64_t> constants(unsigned w, const std::vector<uint64_t> &v)
+{
+    std::vector<uint64_t> ks = edgeConstants(w);
+    ks.push_back(rnd(w));
+    ks.push_back(v[0]);
     return ks;
 }
 
@@ -100,8 +116,8 @@ int ops()
 {
     Context ctx(1247, 16);
     SecretKey key(ctx);
-    for (unsigned w = 1; w <= 16; ++w) {
-        const size_t count = w <= 8 ? 300 : 20;
+    for (unsigned w = 1; w <= kMaxWidth; ++w) {
+        const size_t count = countOf(w);
         std::vector<uint64_t> v(count);
         for (size_t i = 0; i < count; ++i)
             v[i] = rnd(w);
@@ -198,9 +214,26 @@ int oversize()
     return 0;
 }
 
+// No device work: the library's own answer to "which form does this call take".
+int forms()
+{
+    const int cmps[] = {CSGN_UINT_PLAIN_EQ, CSGN_UINT_PLAIN_NE, CSGN_UINT_PLAIN_LT,
+                        CSGN_UINT_PLAIN_LE, CSGN_UINT_PLAIN_GT, CSGN_UINT_PLAIN_GE};
+    for (unsigned w = 1; w <= kMaxWidth; ++w) {
+        const std::vector<uint64_t> terms(w, 1);
+        for (uint64_t k : edgeConstants(w))
+            for (int c = EQ; c <= GE; ++c) {
+                const char *form = csgn_uint_plain_kernel(1247, cmps[c], countOf(w), w, k, terms.data());
+                expect(form && *form, std::string(kNames[c]) + " has a form");
+                printf("w=%u %s k=%llu -> %s\n", w, kNames[c], (unsigned long long)k, form ? form : "");
+            }
+    }
+    return 0;
+}
+
 } // namespace
 
 int main(int argc, char **argv)
 {
-    return runModes(argc, argv, 4711, "uint_plain_driver", {{"ops", ops}, {"ragged", ragged}, {"oversize", oversize}});
+    return runModes(argc, argv, 4711, "uint_plain_driver", {{"ops", ops}, {"ragged", ragged}, {"oversize", oversize}, {"forms", forms}});
 }

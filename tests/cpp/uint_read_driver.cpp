@@ -7,8 +7,11 @@
 //                              uniform planes give the same words; every word == the definition; decryptions
 //   uint_read_driver oversize  a read past 2^31 words per element throws before anything is allocated; bad row counts
 //                              and mismatched contexts throw
+//   uint_read_driver forms   "<shape> -> <form>": the form csgn_uint_read_kernel names under the process's knob
 // Prints "<mode> ok" and exits 0, or names the first mismatch and exits 1.
 #include "driver.h"
+
+#include "csgn_hip.h"
 
 #include <algorithm>
 #include <chrono>
@@ -187,10 +190,27 @@ int oversize()
     return 0;
 }
 
+// No device work: the form csgn_uint_read_kernel names for the shapes of words (fresh planes), under the knob the
+// process was started with.
+int forms()
+{
+    const struct {
+        unsigned v, w;
+        size_t rows, count;
+    } cases[] = {{8, 8, 256, 300}, {8, 8, 200, 300}, {4, 3, 16, 500}, {4, 5, 9, 500}, {1, 2, 1, 20}};
+    for (const auto &c : cases) {
+        const std::vector<uint64_t> s(c.v, 1), t(c.w, 1);
+        const char *form = csgn_uint_read_kernel(1247, c.count, c.v, s.data(), c.rows, c.w, t.data());
+        expect(form && *form, "the read has a form");
+        printf("v=%u rows=%zu w=%u -> %s\n", c.v, c.rows, c.w, form ? form : "");
+    }
+    return 0;
+}
+
 } // namespace
 
 int main(int argc, char **argv)
 {
     return runModes(argc, argv, 4713, "uint_read_driver",
-                    {{"words", words}, {"ragged", ragged}, {"oversize", oversize}});
+                    {{"words", words}, {"ragged", ragged}, {"oversize", oversize}, {"forms", forms}});
 }

@@ -610,3 +610,44 @@ def config5(lib, n, batch, levels=16, mask_ptr=FAKE_PTR):
             x = d.mul(x, d.add(ins[k], ins[k + 1])); k += 2
     d.decrypt(x)
     return d, x
+
+
+# ---------------------------------------------------------------- caller outputs inside guard words (GPU tests)
+
+FILL = np.uint64(0xA5A5A5A5A5A5A5A5)        # neither ZERO nor ONE nor a word a random term is likely to hold
+GUARD_WORDS = 64                            # 512 bytes either side: the outputs keep a fresh tensor's alignment
+
+
+class GuardedOutputs:
+    """Outputs of exactly the documented sizes, each inside a larger tensor whose every word holds FILL.  `outs` are the
+    views a wrapper of csgn_amd/batch.py takes as `out` / `outs`; check(wants) then asserts, output by output, that the
+    words equal the numpy definition and that the guard words before and after still hold FILL.  A form that leaves a
+    range unwritten shows as "never written" (the wanted words there are not FILL), one that writes wrong words or past
+    its end as wrong words or a broken guard: a fresh tensor of the caching allocator tells none of these apart."""
+
+    def __init__(self, hip, sizes, shift=0):
+        self.hip = hip
+        self.sizes = [int(s) for s in sizes]
+        self.first = GUARD_WORDS + int(shift)            # shift = 1: the outputs start 8 bytes off a 16-byte boundary
+        self.whole = [hip.upload(np.full(s + 2 * GUARD_WORDS + int(shift), FILL, dtype=np.uint64)) for s in self.sizes]
+        self.outs = [t[self.first:self.first + s] for t, s in zip(self.whole, self.sizes)]
+
+    def check(self, wants, what=None):
+        assert len(wants) == len(self.sizes), (what, len(wants), len(self.sizes))
+        got = []
+        for j, (t, s, want) in enumerate(zip(self.whole, self.sizes, wants)):
+            a = self.hip.download(t)
+            want = np.asarray(want, dtype=np.uint64).ravel()
+            assert want.size == s, (what, j, "the output is not of the documented size", want.size, s)
+            g = a[self.first:self.first + s]
+            wrong = g != want
+            if wrong.any():
+                at = int(np.flatnonzero(wrong)[0])
+                never = int(np.count_nonzero(wrong & (g == FILL)))
+                raise AssertionError((what, "output %d" % j, "%d of %d words wrong" % (int(wrong.sum()), s),
+                                      "%d of them never written" % never, "first at word %d" % at,
+                                      hex(int(g[at])), hex(int(want[at]))))
+            assert (a[:self.first] == FILL).all(), (what, j, "words in front of the output were written")
+            assert (a[self.first + s:] == FILL).all(), (what, j, "words behind the output were written")
+            got.append(g)
+        return got

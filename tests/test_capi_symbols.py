@@ -279,3 +279,25 @@ def test_coop_kernel_isa_keeps_loaded_registers_untouched():
                        timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
     assert r.stdout.count(" 0 findings") == 8, r.stdout          # unit16 / unit8 x 2 / 4 blocks per group x pipelined / plain
+
+
+def test_form_knobs_are_spelt_alike_everywhere(lib):
+    """The six form knobs: the enumerators of csgn_tuning.h, the names csgn_tuning.cpp stores and reads from the
+    environment (CSGN_<NAME IN CAPITALS>), the names the class-level driver tests force (tests/cpp_driver.py) and the
+    names the Python GPU tests set through the `knobs` fixture are the same six words.  A misspelt name silently
+    leaves the default form, and a forced-form test then passes without having forced anything."""
+    from tests.cpp_driver import FORM_KNOBS, form_env
+    csrc = os.path.join(ROOT, "csgn_amd", "csrc")
+    header = open(os.path.join(csrc, "csgn_tuning.h")).read()
+    source = open(os.path.join(csrc, "csgn_tuning.cpp")).read()
+    enumerators = re.findall(r"^\s*TUNE_(\w+_FUSED),", header, re.M)
+    assert sorted(enumerators) == sorted(k.upper() for k in FORM_KNOBS.values())
+    for driver, knob in FORM_KNOBS.items():
+        assert '{"%s", -1}' % knob in source, knob                     # stored under that name, per shape by default
+        assert list(form_env(driver, 0)) == ["CSGN_" + knob.upper()]
+        v = C.c_int(7)
+        assert lib.csgn_get_tuning(knob.encode(), C.byref(v)) == 0 and v.value in (-1, 0, 1), knob
+        module = "test_gates_gpu.py" if driver == "gates" else "test_%s_gpu.py" % driver
+        text = open(os.path.join(ROOT, "tests", module)).read()
+        used = set(re.findall(r"knobs\.(?:set|unset)\(\s*\"(\w+_fused)\"", text))
+        assert knob in used and used <= set(FORM_KNOBS.values()), (module, used)   # its own knob; any other is one of the six

@@ -5,8 +5,8 @@ import numpy as np
 import pytest
 
 from oracle.binding import glibc_draws
-from tests.model import (ADD_PLAIN, GATES, MUL_PLAIN, MUX, NOT, compose_gate, const_term, gate_clear, gate_terms, hip,
-                         np_gate, oracle_ops, rand_terms)
+from tests.model import (ADD_PLAIN, GATES, GuardedOutputs, MUL_PLAIN, MUX, NOT, compose_gate, const_term, gate_clear,
+                         gate_terms, hip, np_gate, oracle_ops, rand_terms)
 
 pytestmark = pytest.mark.gpu
 
@@ -16,12 +16,15 @@ SHAPES = [(1, 1, 1, 1), (1, 1, 1, 1000), (2, 1, 3, 3), (1, 4, 4, 1000), (1, 5, 4
           (1, 64, 64, 3)]
 
 
-def run_gate(hip, n, gate, a, b, s, plain):
+def run_gate(hip, n, gate, a, b, s, plain, want=None):
+    """The output, downloaded.  With `want` (the definition's words) the output is a caller tensor of exactly that size
+    between guard words, checked word for word and for writes outside it (tests/model.py, GuardedOutputs)."""
     batch, ta, _ = a.shape
     up = hip.upload
+    guarded = GuardedOutputs(hip, [want.size]) if want is not None else None
     out = hip.gate_uniform(n, gate, batch, up(a.ravel()), ta, up(b.ravel()), b.shape[1], up(s.ravel()), s.shape[1],
-                           up(plain))
-    return hip.download(out)
+                           up(plain), out=guarded.outs[0] if guarded else None)
+    return guarded.check([want], gate)[0] if guarded else hip.download(out)
 
 
 def operands(n, ts, ta, tb, batch, seed):
@@ -48,7 +51,7 @@ def test_gate_words(hip, oracle, knobs, n, gate, shape):
         assert np.array_equal(want[e * per:(e + 1) * per], o)
     for fused in (-1, 0, 1):
         knobs.set("gate_fused", fused)
-        got = run_gate(hip, n, gate, a, b, s, plain)
+        got = run_gate(hip, n, gate, a, b, s, plain, want)
         assert np.array_equal(got, want), (fused, hip.lib.csgn_gate_uniform_kernel(n, gate, batch, ts, ta, tb))
 
 
@@ -60,7 +63,7 @@ def test_gate_words_large_batch(hip, knobs, n, gate):
     want = np_gate(n, gate, a, b, s, plain).ravel()
     for fused in (0, 1):
         knobs.set("gate_fused", fused)
-        assert np.array_equal(run_gate(hip, n, gate, a, b, s, plain), want), fused
+        assert np.array_equal(run_gate(hip, n, gate, a, b, s, plain, want), want), fused
 
 
 @pytest.mark.parametrize("n", NS)

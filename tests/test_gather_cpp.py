@@ -5,7 +5,7 @@ import os
 
 import pytest
 
-from tests.cpp_driver import fixture, run_mode
+from tests.cpp_driver import NO_BLOCK_CACHE, fixture, run_mode
 
 driver = fixture("tests/cpp/gather_driver.cpp")
 
@@ -27,3 +27,11 @@ def test_encrypted_query_broadcast(driver):
 @pytest.mark.gpu
 def test_gather_bad_arguments_throw(driver):
     run_mode(driver, "throws")
+
+
+# csgn_gather_plan's status words are a default path of every class-level gather with an index list or a ragged source:
+# the same modes with every payload freed at once (hipMalloc / hipFree around each operator)
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", ["move", "query"])
+def test_gather_driver_without_block_cache(driver, mode):
+    run_mode(driver, mode, env=NO_BLOCK_CACHE)

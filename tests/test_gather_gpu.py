@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.model import INVALID, OK, hip, np_gather, np_gather_offsets, np_gather_uniform, tile_index
+from tests.model import INVALID, OK, GuardedOutputs, hip, np_gather, np_gather_offsets, np_gather_uniform, tile_index
 
 
 pytestmark = pytest.mark.gpu
@@ -29,6 +29,14 @@ def up_index(hip, idx):
     return hip.upload(idx) if len(idx) else None
 
 
+def gather_checked(hip, n, count_in, d_src, t, count_out, d_idx, want, what):
+    """csgn_gather into a caller tensor of exactly the wanted size between guard words: the words are the model's and
+    nothing outside the output was written (tests/model.py, GuardedOutputs)."""
+    guarded = GuardedOutputs(hip, [want.size])
+    hip.gather(n, count_in, d_src, t, count_out, d_idx, guarded.outs[0])
+    return guarded.check([want], what)[0]
+
+
 @pytest.mark.parametrize("n", [63, 65, 129, 1247, 4096])
 @pytest.mark.parametrize("t", [1, 2, 3, 37])
 def test_uniform_gather_words(hip, n, t):
@@ -41,13 +49,15 @@ def test_uniform_gather_words(hip, n, t):
         d_idx = up_index(hip, idx)
         rc, total, bad, _ = hip.gather_plan(count_in, len(idx), d_idx)
         assert (rc, total, bad) == (OK, 0, 0), name
-        got = hip.download(hip.gather(n, count_in, d_src, t, len(idx), d_idx))
-        assert np.array_equal(got, np_gather_uniform(src, t, idx, dl)), name
+        want = np_gather_uniform(src, t, idx, dl)
+        got = gather_checked(hip, n, count_in, d_src, t, len(idx), d_idx, want, name)
+        assert np.array_equal(got, want), name
     for count_out in (1, 96, 97, 98, 1000):                           # tile
-        got = hip.download(hip.gather(n, count_in, d_src, t, count_out))
-        assert np.array_equal(got, np_gather_uniform(src, t, tile_index(count_in, count_out), dl)), count_out
-    got = hip.download(hip.gather(n, 1, d_src, t, 300))               # broadcast of element 0
-    assert np.array_equal(got, np.tile(src[: t * dl], 300))
+        want = np_gather_uniform(src, t, tile_index(count_in, count_out), dl)
+        got = gather_checked(hip, n, count_in, d_src, t, count_out, None, want, count_out)
+        assert np.array_equal(got, want), count_out
+    want = np.tile(src[: t * dl], 300)                               # broadcast of element 0
+    assert np.array_equal(gather_checked(hip, n, 1, d_src, t, 300, None, want, "broadcast"), want)
 
 
 @pytest.mark.parametrize("n", [63, 65, 129, 1247, 4096])
@@ -67,9 +77,16 @@ def test_ragged_gather_words_and_offsets(hip, n):
         count_out = 2 * count_in + 3 if idx is None else len(idx)
         ref_idx = tile_index(count_in, count_out) if idx is None else idx
         want, want_off = np_gather(src, src_off, ref_idx, dl)
-        got, got_off = hip.gather_ragged(n, count_in, d_src, d_off, count_out, up_index(hip, idx) if idx is not None else None)
+        guarded = []
+
+        def place(n_words):                                          # the planned size decides the output's size
+            guarded.append(GuardedOutputs(hip, [n_words]))
+            return guarded[0].outs[0]
+
+        got, got_off = hip.gather_ragged(n, count_in, d_src, d_off, count_out,
+                                         up_index(hip, idx) if idx is not None else None, out=place)
         assert np.array_equal(hip.download(got_off), want_off), name
-        assert np.array_equal(hip.download(got), want), name
+        assert np.array_equal(guarded[0].check([want], name)[0], want), name
     # broadcast of a ragged element (the large one)
     one_off = np.array([0, 700], dtype=np.uint64)
     one = src[int(src_off[5]) * dl:int(src_off[6]) * dl]
@@ -115,9 +132,11 @@ def test_planes_of_mixed_terms_one_launch(hip, n):
     assert hip.lib.csgn_gather_kernel(n, 500, 0, len(terms)) == b"k_gather"
     rng = np.random.default_rng(n)
     idx = rng.integers(0, count_in, size=500)
-    outs = hip.gather_planes(n, dev, terms, count_in, 500, up_index(hip, idx))
-    for j, t in enumerate(terms):
-        want = np_gather_uniform(planes[j], t, idx, dl) if t else np.zeros(0, dtype=np.uint64)
+    wants = [np_gather_uniform(planes[j], t, idx, dl) if t else np.zeros(0, dtype=np.uint64) for j, t in enumerate(terms)]
+    guarded = GuardedOutputs(hip, [x.size for x in wants])
+    outs = hip.gather_planes(n, dev, terms, count_in, 500, up_index(hip, idx), guarded.outs)
+    guarded.check(wants, "planes")
+    for j, want in enumerate(wants):
         assert np.array_equal(hip.download(outs[j]), want), j
     outs = hip.gather_planes(n, dev, terms, 1, 77)                  # broadcast of integer 0
     for j, t in enumerate(terms):

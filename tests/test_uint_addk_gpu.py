@@ -6,16 +6,18 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from tests.model import hip, rand_terms, u64s
+from tests.model import GuardedOutputs, hip, rand_terms, u64s
 from tests.model_addk import addk_terms, full_width_ks, np_addk, term_modes
 from tests.test_uint_plain_gpu import edge_ks
 
 pytestmark = pytest.mark.gpu
 
 
-def run(hip, n, planes, k, negate, carry, offset=0):
+def run(hip, n, planes, k, negate, carry, offset=0, want=None):
     """The outputs (and carry-out) downloaded; offset = 1 places every plane and output one word past a 16-byte
-    boundary."""
+    boundary.  With `want` (the definition's planes and, last, its carry-out) the outputs are caller tensors of exactly
+    those sizes between guard words, checked word for word and for writes outside them (tests/model.py,
+    GuardedOutputs)."""
     batch = planes[0].shape[0]
     ts = [p.shape[1] for p in planes]
 
@@ -27,14 +29,21 @@ def run(hip, n, planes, k, negate, carry, offset=0):
         return t[offset:]
 
     dev = [place(p.ravel()) for p in planes]
-    outs = carry_out = None
-    if offset:
+    outs = carry_out = guarded = None
+    if want is not None:
+        guarded = GuardedOutputs(hip, [x.size for x in (want if carry else want[:-1])], shift=offset)
+        outs, carry_out = guarded.outs[:len(ts)], (guarded.outs[-1] if carry else None)
+        assert all(o.data_ptr() % 16 == (8 if offset else 0) for o in guarded.outs + dev)
+    elif offset:
         dl = (n + 63) // 64
         T = addk_terms(len(ts), k, ts)
         outs = [hip.empty_words(batch * (t + negate) * dl + offset)[offset:] for t in T[:-1]]
         carry_out = hip.empty_words(batch * T[-1] * dl + offset)[offset:]
         assert all(o.data_ptr() % 16 == 8 for o in outs + dev + [carry_out])
     outs, c = hip.uint_addk(n, batch, dev, ts, k, negate=negate, carry=carry, outs=outs, carry_out=carry_out)
+    if guarded:
+        got = guarded.check(want if carry else want[:-1], (k, negate, carry))
+        return got[:len(ts)], (got[-1] if carry else None)
     return [hip.download(o) for o in outs], (hip.download(c) if carry else None)
 
 
@@ -46,7 +55,8 @@ def check_forms(hip, knobs, n, planes, k, offset=0, carries=(False, True)):
         for fused in (-1, 0, 1):
             knobs.set("uint_addk_fused", fused)
             for carry in carries:
-                got, got_c = run(hip, n, planes, k, negate, carry, offset)
+                got, got_c = run(hip, n, planes, k, negate, carry, offset,
+                                 want=[x.ravel() for x in want] + [want_c.ravel()])
                 tag = (fused, k, negate, carry, [p.shape[1] for p in planes])
                 for j, (g, w_) in enumerate(zip(got, want)):
                     assert np.array_equal(g, w_.ravel()), (j,) + tag

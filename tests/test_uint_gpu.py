@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 
 from oracle.binding import glibc_draws
-from tests.model import (ADD_FULL, ADD_HALF, EQ_STEP, LT_FIRST, LT_STEP, STEPS, hip, np_step, np_uint_add, np_uint_eq,
+from tests.model import (ADD_FULL, ADD_HALF, EQ_STEP, GuardedOutputs, LT_FIRST, LT_STEP, STEPS, hip, np_step, np_uint_add, np_uint_eq,
                          np_uint_lt, np_uint_sub, rand_terms, step_terms)
 
 pytestmark = pytest.mark.gpu
@@ -21,13 +21,19 @@ def reads_x(step):
     return step not in (ADD_HALF, LT_FIRST)
 
 
-def run_step(hip, n, step, x, a, b, carry=True, alias=False):
+def run_step(hip, n, step, x, a, b, carry=True, alias=False, want=None):
+    """The outputs, downloaded.  With `want` (the definition's words, one array per output) they are caller tensors of
+    exactly those sizes between guard words, checked word for word and for writes outside them (tests/model.py,
+    GuardedOutputs)."""
     up = hip.upload
     da = up(a.ravel())
     db = da if alias else up(b.ravel())
     dx = up(x.ravel()) if reads_x(step) else None
+    guarded = GuardedOutputs(hip, [w.size for w in want]) if want is not None else None
     out = hip.uint_step(n, step, a.shape[0], da, a.shape[1], db, b.shape[1], dx, x.shape[1] if reads_x(step) else 0,
-                        carry=carry)
+                        carry=carry, outs=guarded.outs if guarded else None)
+    if guarded:
+        return tuple(guarded.check(want, step))
     return tuple(hip.download(o) for o in out) if isinstance(out, tuple) else (hip.download(out),)
 
 
@@ -44,7 +50,7 @@ def test_step_words(hip, knobs, n, step, shape):
     for fused in (-1, 0, 1):
         knobs.set("uint_fused", fused)
         kernel = hip.lib.csgn_uint_step_kernel(n, step, batch, tx, ta, tb).decode()
-        got = run_step(hip, n, step, x, a, b)
+        got = run_step(hip, n, step, x, a, b, want=want)
         assert len(got) == len(want)
         for o in range(len(want)):
             assert np.array_equal(got[o], want[o]), (fused, kernel, o)
@@ -59,7 +65,7 @@ def test_step_aliased_operands_and_no_carry(hip, knobs, n, step):
     want = [w.ravel() for w in np_step(n, step, x, a, a)]
     for fused in (0, 1):
         knobs.set("uint_fused", fused)
-        got = run_step(hip, n, step, x, a, a, alias=True)
+        got = run_step(hip, n, step, x, a, a, alias=True, want=want)
         for o in range(len(want)):
             assert np.array_equal(got[o], want[o]), (fused, o)
         got = run_step(hip, n, step, x, a, rand_terms(n, batch, ta, 9), carry=False)
@@ -75,7 +81,7 @@ def test_step_words_large_batch(hip, knobs, n, step):
     want = [w.ravel() for w in np_step(n, step, x, a, b)]
     for fused in (0, 1):
         knobs.set("uint_fused", fused)
-        got = run_step(hip, n, step, x, a, b)
+        got = run_step(hip, n, step, x, a, b, want=want)
         for o in range(len(want)):
             assert np.array_equal(got[o], want[o]), (fused, o)
 

@@ -8,23 +8,28 @@ import pytest
 import torch
 
 from oracle.binding import glibc_draws
-from tests.model import (EQ, aes_sbox, c_terms, decrypt_bits, decrypt_value, encrypt_planes, hip, mul4x4, np_add,
-                         np_lut, np_plain, rand_terms, random_table, u64s)
+from tests.model import (EQ, GuardedOutputs, aes_sbox, c_terms, decrypt_bits, decrypt_value, encrypt_planes, hip, mul4x4,
+                         np_add, np_lut, np_plain, rand_terms, random_table, u64s)
 
 pytestmark = pytest.mark.gpu
 
 
-def run(hip, n, planes, table, m):
+def run(hip, n, planes, table, m, want=None):
+    """The outputs, downloaded.  With `want` (the definition's words, one array per output) they are caller tensors of
+    exactly those sizes between guard words, checked word for word and for writes outside them (tests/model.py,
+    GuardedOutputs)."""
     dev = [hip.upload(p.ravel()) for p in planes]
-    outs = hip.uint_lut(n, planes[0].shape[0], dev, [p.shape[1] for p in planes], table, m)
-    return [hip.download(o) for o in outs]
+    guarded = GuardedOutputs(hip, [x.size for x in want]) if want is not None else None
+    outs = hip.uint_lut(n, planes[0].shape[0], dev, [p.shape[1] for p in planes], table, m,
+                        outs=guarded.outs if guarded else None)
+    return guarded.check(want, m) if guarded else [hip.download(o) for o in outs]
 
 
 def check_forms(hip, knobs, n, planes, table, m, forms=(-1, 0, 1)):
     want = [x.ravel() for x in np_lut(n, planes, table, m)]
     for fused in forms:
         knobs.set("uint_lut_fused", fused)
-        got = run(hip, n, planes, table, m)
+        got = run(hip, n, planes, table, m, want)
         for j in range(m):
             assert np.array_equal(got[j], want[j]), (fused, j, [p.shape[1] for p in planes])
 

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 from oracle.binding import glibc_draws
-from tests.model import (CLEAR, CMPS, EQ, GE, GT, LE, LT, NE, decrypt_bits, encrypt_planes, full_width_cases, hip,
+from tests.model import (CLEAR, CMPS, EQ, GE, GT, LE, LT, NE, GuardedOutputs, decrypt_bits, encrypt_planes, full_width_cases, hip,
                          np_plain, plain_terms, rand_terms, u64s)
 
 pytestmark = pytest.mark.gpu
@@ -19,16 +19,22 @@ def edge_ks(w):
     return sorted(ks)
 
 
-def run(hip, n, cmp, planes, k):
+def run(hip, n, cmp, planes, k, want=None):
+    """The output, downloaded.  With `want` (the definition's words) the output is a caller tensor of exactly that size
+    between guard words, checked word for word and for writes outside it (tests/model.py, GuardedOutputs)."""
     dev = [hip.upload(p.ravel()) for p in planes]
-    return hip.download(hip.uint_plain(n, cmp, planes[0].shape[0], dev, [p.shape[1] for p in planes], k))
+    if want is None:
+        return hip.download(hip.uint_plain(n, cmp, planes[0].shape[0], dev, [p.shape[1] for p in planes], k))
+    guarded = GuardedOutputs(hip, [want.size])
+    hip.uint_plain(n, cmp, planes[0].shape[0], dev, [p.shape[1] for p in planes], k, out=guarded.outs[0])
+    return guarded.check([want], (cmp, k))[0]
 
 
 def check_forms(hip, knobs, n, cmp, planes, k):
     want = np_plain(n, cmp, planes, k).ravel()
     for fused in (-1, 0, 1):
         knobs.set("uint_plain_fused", fused)
-        got = run(hip, n, cmp, planes, k)
+        got = run(hip, n, cmp, planes, k, want)
         assert np.array_equal(got, want), (fused, cmp, k, [p.shape[1] for p in planes])
 
 
@@ -107,7 +113,7 @@ def test_plain_16bit_spans_many_workgroups(hip, knobs):
         assert want.size >= batch * ((1 << 15) - 1) * 20
         for fused in (1, 0):
             knobs.set("uint_plain_fused", fused)
-            assert np.array_equal(run(hip, n, cmp, planes, k), want), (cmp, fused)
+            assert np.array_equal(run(hip, n, cmp, planes, k, want), want), (cmp, fused)
 
 
 @pytest.mark.parametrize("w", [1, 2, 3, 4, 8])

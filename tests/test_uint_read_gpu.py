@@ -9,26 +9,30 @@ import pytest
 import torch
 
 from oracle.binding import glibc_draws
-from tests.model import const_term, decrypt_value, encrypt_planes, hip, np_read_fast, rand_terms, read_terms, u64s
+from tests.model import (GuardedOutputs, const_term, decrypt_value, encrypt_planes, hip, np_read_fast, rand_terms,
+                         read_terms, u64s)
 
 pytestmark = pytest.mark.gpu
 
 
-def run(hip, n, index, table):
-    """index[k]: words[batch, s_k, dL], table[j]: words[rows, t_j, dL] (host arrays).  The outputs, downloaded."""
+def run(hip, n, index, table, want=None):
+    """index[k]: words[batch, s_k, dL], table[j]: words[rows, t_j, dL] (host arrays).  The outputs, downloaded.  With
+    `want` (the definition's words, one array per output) they are caller tensors of exactly those sizes between guard
+    words, checked word for word and for writes outside them (tests/model.py, GuardedOutputs)."""
     dx = [hip.upload(p.ravel()) for p in index]
     dt = [hip.upload(p.ravel()) for p in table]
+    guarded = GuardedOutputs(hip, [x.size for x in want]) if want is not None else None
     outs = hip.uint_read(n, index[0].shape[0], dx, [p.shape[1] for p in index], table[0].shape[0], dt,
-                         [p.shape[1] for p in table])
+                         [p.shape[1] for p in table], outs=guarded.outs if guarded else None)
     torch.cuda.synchronize()
-    return [hip.download(o) for o in outs]
+    return guarded.check(want, table[0].shape[0]) if guarded else [hip.download(o) for o in outs]
 
 
 def check_forms(hip, knobs, n, index, table, forms=(-1, 0, 1)):
     want = [x.ravel() for x in np_read_fast(n, index, table)]
     for fused in forms:
         knobs.set("uint_read_fused", fused)
-        got = run(hip, n, index, table)
+        got = run(hip, n, index, table, want)
         for j in range(len(table)):
             assert np.array_equal(got[j], want[j]), (fused, j, [p.shape[1] for p in index], table[0].shape[0])
 
