@@ -9,17 +9,9 @@
 
 namespace certFHE {
 
-namespace detail {
-
-struct GateAccess {
-    static CiphertextBatch make(const Context &c, uint64_t count, uint64_t terms) { return CiphertextBatch(c, count, terms); }
-    static uint64_t *words(CiphertextBatch &b) { return b.payload->data(); }
-};
-
-} // namespace detail
-
+using detail::BatchAccess;
 using detail::DevicePayload;
-using detail::GateAccess;
+using detail::ones;
 
 namespace {
 
@@ -45,19 +37,14 @@ CiphertextBatch uniformGate(int gate, const CiphertextBatch *sel, const Cipherte
     const uint64_t terms = csgn_gate_terms(gate, ts, ta, tb);
     if (terms == 0)
         throw std::invalid_argument("certFHE: gate over an empty operand, or its size overflows");
-    CiphertextBatch out = GateAccess::make(a.context(), a.size(), terms);
+    CiphertextBatch out = BatchAccess::make(a.context(), a.size(), terms);
     if (a.size())
         detail::check(csgn_gate_uniform(a.context().getN(), gate, a.size(), ts, ta, tb, sel ? sel->deviceValues() : nullptr,
                                         a.deviceValues(), b ? b->deviceValues() : nullptr,
                                         plain ? reinterpret_cast<const uint8_t *>(plain->data()) : nullptr,
-                                        GateAccess::words(out), detail::stream()),
+                                        BatchAccess::words(out), detail::stream()),
                       "csgn_gate_uniform");
     return out;
-}
-
-CiphertextBatch ones(const CiphertextBatch &like)
-{
-    return constantBatch(like.context(), std::vector<unsigned char>(like.size(), 1));
 }
 
 } // namespace
@@ -67,12 +54,12 @@ CiphertextBatch ones(const CiphertextBatch &like)
 CiphertextBatch constantBatch(const Context &context, const std::vector<unsigned char> &bits)
 {
     detail::ensureDevice();
-    CiphertextBatch out = GateAccess::make(context, bits.size(), 1);
+    CiphertextBatch out = BatchAccess::make(context, bits.size(), 1);
     if (bits.empty())
         return out;
     std::shared_ptr<DevicePayload> plain = uploadBits(bits);
     detail::check(csgn_const_fill(context.getN(), bits.size(), reinterpret_cast<const uint8_t *>(plain->data()), 0,
-                                  GateAccess::words(out), detail::stream()),
+                                  BatchAccess::words(out), detail::stream()),
                   "csgn_const_fill");
     return out;
 }

@@ -11,16 +11,8 @@
 
 namespace certFHE {
 
-namespace detail {
-
-struct UIntAccess {
-    static CiphertextBatch make(const Context &c, uint64_t count, uint64_t terms) { return CiphertextBatch(c, count, terms); }
-    static uint64_t *words(CiphertextBatch &b) { return b.payload->data(); }
-};
-
-} // namespace detail
-
-using detail::UIntAccess;
+using detail::BatchAccess;
+using detail::ones;
 
 namespace {
 
@@ -94,12 +86,74 @@ uint64_t gateTerms(int gate, uint64_t ts, uint64_t ta, uint64_t tb, const Contex
     return checked(csgn_gate_terms(gate, ts, ta, tb), ctx, who);
 }
 
-// ------------------------------------------------------------------ one step
+// ------------------------------------------------------------------ plane lists
 
-CiphertextBatch ones(const CiphertextBatch &like)
+// The operand planes of one call: their terms per element (a ragged plane: its largest element, a bound for
+// everything computed from it) and whether all of them are uniform, which is when the call is one launch.
+struct Planes {
+    std::vector<const CiphertextBatch *> list;
+    std::vector<uint64_t> terms;
+    bool uniform = true;
+
+    void add(const CiphertextBatch &p)
+    {
+        list.push_back(&p);
+        terms.push_back(termsOf(p));
+        uniform = uniform && p.uniform();
+    }
+    explicit Planes(const std::vector<CiphertextBatch> &planes)
+    {
+        for (size_t j = 0; j < planes.size(); ++j)
+            add(planes[j]);
+    }
+    explicit Planes(const UIntBatch &a)
+    {
+        for (unsigned j = 0; j < a.width(); ++j)
+            add(a.plane(j));
+    }
+};
+
+std::vector<const uint64_t *> sources(const Planes &p)
 {
-    return constantBatch(like.context(), std::vector<unsigned char>(like.size(), 1));
+    std::vector<const uint64_t *> src(p.list.size());
+    for (size_t j = 0; j < src.size(); ++j)
+        src[j] = p.list[j]->deviceValues();
+    return src;
 }
+
+// one fresh uniform batch of T[j] terms per element for every j
+std::vector<CiphertextBatch> makePlanes(const Context &ctx, uint64_t count, const std::vector<uint64_t> &T)
+{
+    std::vector<CiphertextBatch> out;
+    out.reserve(T.size());
+    for (size_t j = 0; j < T.size(); ++j)
+        out.push_back(BatchAccess::make(ctx, count, T[j]));
+    return out;
+}
+
+std::vector<uint64_t *> wordsOf(std::vector<CiphertextBatch> &planes)
+{
+    std::vector<uint64_t *> dst(planes.size());
+    for (size_t j = 0; j < dst.size(); ++j)
+        dst[j] = BatchAccess::words(planes[j]);
+    return dst;
+}
+
+// make(j) for every plane j < n, after check(j) has passed for every plane: nothing is launched before all sizes fit
+template <typename Check, typename Make>
+std::vector<CiphertextBatch> mapPlanes(unsigned n, Check check, Make make)
+{
+    for (unsigned j = 0; j < n; ++j)
+        check(j);
+    std::vector<CiphertextBatch> planes;
+    for (unsigned j = 0; j < n; ++j)
+        planes.push_back(make(j));
+    return planes;
+}
+
+void noCheck(unsigned) {}
+
+// ------------------------------------------------------------------ one step
 
 bool allUniform(const CiphertextBatch *x, const CiphertextBatch &a, const CiphertextBatch &b)
 {
@@ -113,13 +167,13 @@ std::vector<CiphertextBatch> step(int st, const CiphertextBatch *x, const Cipher
     std::vector<CiphertextBatch> out;
     if (allUniform(x, a, b)) {
         const uint64_t tx = x ? x->terms() : 0, ta = a.terms(), tb = b.terms();
-        out.push_back(UIntAccess::make(a.context(), a.size(), csgn_uint_step_terms(st, 0, tx, ta, tb)));
+        out.push_back(BatchAccess::make(a.context(), a.size(), csgn_uint_step_terms(st, 0, tx, ta, tb)));
         if (carry)
-            out.push_back(UIntAccess::make(a.context(), a.size(), csgn_uint_step_terms(st, 1, tx, ta, tb)));
+            out.push_back(BatchAccess::make(a.context(), a.size(), csgn_uint_step_terms(st, 1, tx, ta, tb)));
         if (a.size())
             detail::check(csgn_uint_step(a.context().getN(), st, a.size(), x ? x->deviceValues() : nullptr, tx,
-                                         a.deviceValues(), ta, b.deviceValues(), tb, UIntAccess::words(out[0]),
-                                         carry ? UIntAccess::words(out[1]) : nullptr, detail::stream()),
+                                         a.deviceValues(), ta, b.deviceValues(), tb, BatchAccess::words(out[0]),
+                                         carry ? BatchAccess::words(out[1]) : nullptr, detail::stream()),
                           "csgn_uint_step");
         return out;
     }
@@ -234,23 +288,14 @@ CiphertextBatch comparePlain(int cmp, const UIntBatch &a, uint64_t k, const char
     if (w < 64 && (k >> w) != 0)
         throw std::invalid_argument(std::string("certFHE::") + who + ": the constant does not fit in the width");
     const Context &ctx = a.context();
-    std::vector<uint64_t> terms(w);
-    bool uniform = true;
-    for (unsigned j = 0; j < w; ++j) {
-        terms[j] = termsOf(a.plane(j));                  // a ragged plane: its largest element, a bound
-        uniform = uniform && a.plane(j).uniform();
-    }
-    const uint64_t total = checked(csgn_uint_plain_terms(cmp, w, k, terms.data()), ctx, who);
-    if (uniform) {
-        CiphertextBatch out = UIntAccess::make(ctx, a.size(), total);
-        if (a.size()) {
-            std::vector<const uint64_t *> planes(w);
-            for (unsigned j = 0; j < w; ++j)
-                planes[j] = a.plane(j).deviceValues();
-            detail::check(csgn_uint_plain(ctx.getN(), cmp, a.size(), w, k, planes.data(), terms.data(),
-                                          UIntAccess::words(out), detail::stream()),
+    const Planes in(a);
+    const uint64_t total = checked(csgn_uint_plain_terms(cmp, w, k, in.terms.data()), ctx, who);
+    if (in.uniform) {
+        CiphertextBatch out = BatchAccess::make(ctx, a.size(), total);
+        if (a.size())
+            detail::check(csgn_uint_plain(ctx.getN(), cmp, a.size(), w, k, sources(in).data(), in.terms.data(),
+                                          BatchAccess::words(out), detail::stream()),
                           "csgn_uint_plain");
-        }
         return out;
     }
     // ragged: the definition itself through the batch operators (every intermediate is no larger than the result)
@@ -297,38 +342,29 @@ std::vector<CiphertextBatch> addPlain(const UIntBatch &a, uint64_t k, bool negat
     requireConstant(a, k, who);
     const unsigned w = a.width();
     const Context &ctx = a.context();
-    std::vector<uint64_t> terms(w), T(w + 1);
-    bool uniform = true;
-    for (unsigned j = 0; j < w; ++j) {
-        terms[j] = termsOf(a.plane(j));                  // a ragged plane: its largest element, a bound
-        uniform = uniform && a.plane(j).uniform();
-    }
-    if (!csgn_uint_addk_terms(w, k, terms.data(), T.data()))
+    const Planes in(a);
+    std::vector<uint64_t> T(w + 1);
+    if (!csgn_uint_addk_terms(w, k, in.terms.data(), T.data()))
         checked(0, ctx, who);
     for (unsigned j = 0; j < w; ++j)
-        checked(T[j] + (negate ? 1 : 0), ctx, who);
+        T[j] = checked(T[j] + (negate ? 1 : 0), ctx, who);
     if (carry_out)
         checked(T[w], ctx, who);
-    std::vector<CiphertextBatch> out;
-    if (uniform) {
-        for (unsigned j = 0; j < w; ++j)
-            out.push_back(UIntAccess::make(ctx, a.size(), T[j] + (negate ? 1 : 0)));
-        CiphertextBatch carry = UIntAccess::make(ctx, carry_out ? a.size() : 0, T[w]);
-        if (a.size()) {
-            std::vector<const uint64_t *> planes(w);
-            std::vector<uint64_t *> outs(w);
-            for (unsigned j = 0; j < w; ++j) {
-                planes[j] = a.plane(j).deviceValues();
-                outs[j] = UIntAccess::words(out[j]);
-            }
-            detail::check(csgn_uint_addk(ctx.getN(), a.size(), w, k, negate ? 1 : 0, planes.data(), terms.data(),
-                                         outs.data(), carry_out ? UIntAccess::words(carry) : nullptr, detail::stream()),
+    if (in.uniform) {
+        const uint64_t carry_terms = T[w];
+        T.pop_back();
+        std::vector<CiphertextBatch> out = makePlanes(ctx, a.size(), T);
+        CiphertextBatch carry = BatchAccess::make(ctx, carry_out ? a.size() : 0, carry_terms);
+        if (a.size())
+            detail::check(csgn_uint_addk(ctx.getN(), a.size(), w, k, negate ? 1 : 0, sources(in).data(), in.terms.data(),
+                                         wordsOf(out).data(), carry_out ? BatchAccess::words(carry) : nullptr,
+                                         detail::stream()),
                           "csgn_uint_addk");
-        }
         if (carry_out)
             *carry_out = carry;
         return out;
     }
+    std::vector<CiphertextBatch> out;
     // ragged: the definition itself through the batch operators
     if (k == 0) {
         for (unsigned j = 0; j < w; ++j)
@@ -414,10 +450,7 @@ const CiphertextBatch &UIntBatch::plane(unsigned j) const
 
 UIntBatch UIntBatch::compact() const
 {
-    std::vector<CiphertextBatch> planes;
-    for (size_t j = 0; j < planes_.size(); ++j)
-        planes.push_back(planes_[j].compact());
-    return UIntBatch(planes);
+    return UIntBatch(mapPlanes(width(), noCheck, [&](unsigned j) { return planes_[j].compact(); }));
 }
 
 namespace {
@@ -426,20 +459,11 @@ std::vector<CiphertextBatch> gatherUniformPlanes(const std::vector<CiphertextBat
                                                  const uint64_t *d_idx)
 {
     const Context &ctx = planes[0].context();
-    std::vector<CiphertextBatch> out;
-    std::vector<const uint64_t *> src;
-    std::vector<uint64_t *> dst;
-    std::vector<uint64_t> terms;
-    for (size_t j = 0; j < planes.size(); ++j) {
-        out.push_back(UIntAccess::make(ctx, count_out, planes[j].terms()));
-        src.push_back(planes[j].deviceValues());
-        terms.push_back(planes[j].terms());
-    }
-    for (size_t j = 0; j < out.size(); ++j)
-        dst.push_back(UIntAccess::words(out[j]));
+    const Planes in(planes);
+    std::vector<CiphertextBatch> out = makePlanes(ctx, count_out, in.terms);
     if (count_out)
-        detail::check(csgn_gather_planes(ctx.getN(), planes.size(), src.data(), terms.data(), planes[0].size(), count_out,
-                                         d_idx, dst.data(), detail::stream()),
+        detail::check(csgn_gather_planes(ctx.getN(), planes.size(), sources(in).data(), in.terms.data(), planes[0].size(),
+                                         count_out, d_idx, wordsOf(out).data(), detail::stream()),
                       "csgn_gather_planes");
     return out;
 }
@@ -459,12 +483,8 @@ UIntBatch UIntBatch::gather(const std::vector<uint64_t> &indices) const
         if (indices[e] >= size())
             throw std::out_of_range("certFHE::UIntBatch::gather: index " + std::to_string(indices[e]) +
                                     " past a batch of " + std::to_string(size()));
-    if (!allUniform(planes_)) {
-        std::vector<CiphertextBatch> planes;
-        for (size_t j = 0; j < planes_.size(); ++j)
-            planes.push_back(planes_[j].gather(indices));
-        return UIntBatch(planes);
-    }
+    if (!allUniform(planes_))
+        return UIntBatch(mapPlanes(width(), noCheck, [&](unsigned j) { return planes_[j].gather(indices); }));
     if (indices.empty())
         return UIntBatch(gatherUniformPlanes(planes_, 0, nullptr));
     std::shared_ptr<detail::DevicePayload> d_idx = detail::uploadWords(indices.data(), indices.size());
@@ -476,10 +496,7 @@ UIntBatch UIntBatch::slice(uint64_t begin, uint64_t end) const
     if (begin > end || end > size())
         throw std::out_of_range("certFHE::UIntBatch::slice: [" + std::to_string(begin) + ", " + std::to_string(end) +
                                 ") of a batch of " + std::to_string(size()));
-    std::vector<CiphertextBatch> planes;
-    for (size_t j = 0; j < planes_.size(); ++j)
-        planes.push_back(planes_[j].slice(begin, end));
-    return UIntBatch(planes);
+    return UIntBatch(mapPlanes(width(), noCheck, [&](unsigned j) { return planes_[j].slice(begin, end); }));
 }
 
 UIntBatch UIntBatch::broadcast(uint64_t count) const
@@ -489,12 +506,8 @@ UIntBatch UIntBatch::broadcast(uint64_t count) const
                                     " integers, not 1");
     if (count >= (1ull << 32))
         throw std::invalid_argument("certFHE::UIntBatch::broadcast: 2^32 integers or more");
-    if (!allUniform(planes_)) {
-        std::vector<CiphertextBatch> planes;
-        for (size_t j = 0; j < planes_.size(); ++j)
-            planes.push_back(planes_[j].broadcast(count));
-        return UIntBatch(planes);
-    }
+    if (!allUniform(planes_))
+        return UIntBatch(mapPlanes(width(), noCheck, [&](unsigned j) { return planes_[j].broadcast(count); }));
     return UIntBatch(gatherUniformPlanes(planes_, count, nullptr));
 }
 
@@ -561,106 +574,86 @@ UIntBatch UIntBatch::operator-() const { return UIntBatch(addPlain(*this, maskOf
 
 UIntBatch UIntBatch::operator~() const
 {
-    for (unsigned j = 0; j < width(); ++j)
-        gateTerms(CSGN_GATE_NOT, 0, termsOf(planes_[j]), 0, context(), "UIntBatch::operator~");
-    std::vector<CiphertextBatch> planes;
-    for (unsigned j = 0; j < width(); ++j)
-        planes.push_back(logicNot(planes_[j]));
-    return UIntBatch(planes);
+    return UIntBatch(mapPlanes(
+        width(), [&](unsigned j) { gateTerms(CSGN_GATE_NOT, 0, termsOf(planes_[j]), 0, context(), "UIntBatch::operator~"); },
+        [&](unsigned j) { return logicNot(planes_[j]); }));
 }
 
 UIntBatch UIntBatch::operator&(const UIntBatch &rhs) const
 {
     requireSame(*this, rhs, "UIntBatch::operator&");
-    for (unsigned j = 0; j < width(); ++j) {
-        const uint64_t ta = termsOf(planes_[j]), tb = termsOf(rhs.planes_[j]);
-        checked(tb && ta > (kMaxWords / tb) ? 0 : ta * tb, context(), "UIntBatch::operator&");
-    }
-    std::vector<CiphertextBatch> planes;
-    for (unsigned j = 0; j < width(); ++j)
-        planes.push_back(planes_[j] * rhs.planes_[j]);
-    return UIntBatch(planes);
+    return UIntBatch(mapPlanes(
+        width(),
+        [&](unsigned j) {
+            const uint64_t ta = termsOf(planes_[j]), tb = termsOf(rhs.planes_[j]);
+            checked(tb && ta > (kMaxWords / tb) ? 0 : ta * tb, context(), "UIntBatch::operator&");
+        },
+        [&](unsigned j) { return planes_[j] * rhs.planes_[j]; }));
 }
 
 UIntBatch UIntBatch::operator|(const UIntBatch &rhs) const
 {
     requireSame(*this, rhs, "UIntBatch::operator|");
-    for (unsigned j = 0; j < width(); ++j)
-        gateTerms(CSGN_GATE_OR, 0, termsOf(planes_[j]), termsOf(rhs.planes_[j]), context(), "UIntBatch::operator|");
-    std::vector<CiphertextBatch> planes;
-    for (unsigned j = 0; j < width(); ++j)
-        planes.push_back(logicOr(planes_[j], rhs.planes_[j]));
-    return UIntBatch(planes);
+    return UIntBatch(mapPlanes(
+        width(),
+        [&](unsigned j) {
+            gateTerms(CSGN_GATE_OR, 0, termsOf(planes_[j]), termsOf(rhs.planes_[j]), context(), "UIntBatch::operator|");
+        },
+        [&](unsigned j) { return logicOr(planes_[j], rhs.planes_[j]); }));
 }
 
 UIntBatch UIntBatch::operator^(const UIntBatch &rhs) const
 {
     requireSame(*this, rhs, "UIntBatch::operator^");
-    for (unsigned j = 0; j < width(); ++j)
-        checked(termsOf(planes_[j]) + termsOf(rhs.planes_[j]), context(), "UIntBatch::operator^");
-    std::vector<CiphertextBatch> planes;
-    for (unsigned j = 0; j < width(); ++j)
-        planes.push_back(planes_[j] + rhs.planes_[j]);
-    return UIntBatch(planes);
+    return UIntBatch(mapPlanes(
+        width(),
+        [&](unsigned j) { checked(termsOf(planes_[j]) + termsOf(rhs.planes_[j]), context(), "UIntBatch::operator^"); },
+        [&](unsigned j) { return planes_[j] + rhs.planes_[j]; }));
 }
 
 UIntBatch UIntBatch::operator&(uint64_t k) const
 {
     requireConstant(*this, k, "UIntBatch::operator&");
-    std::vector<CiphertextBatch> planes;
     const CiphertextBatch zero = zeros(*this);            // one shared payload for every cleared plane
-    for (unsigned j = 0; j < width(); ++j)
-        planes.push_back((k >> j) & 1u ? planes_[j] : zero);
-    return UIntBatch(planes);
+    return UIntBatch(mapPlanes(width(), noCheck, [&](unsigned j) { return (k >> j) & 1u ? planes_[j] : zero; }));
 }
 
 UIntBatch UIntBatch::operator|(uint64_t k) const
 {
     requireConstant(*this, k, "UIntBatch::operator|");
-    std::vector<CiphertextBatch> planes;
     const CiphertextBatch one = ones(planes_[0]);         // one shared payload for every set plane
-    for (unsigned j = 0; j < width(); ++j)
-        planes.push_back((k >> j) & 1u ? one : planes_[j]);
-    return UIntBatch(planes);
+    return UIntBatch(mapPlanes(width(), noCheck, [&](unsigned j) { return (k >> j) & 1u ? one : planes_[j]; }));
 }
 
 UIntBatch UIntBatch::operator^(uint64_t k) const
 {
     requireConstant(*this, k, "UIntBatch::operator^");
-    for (unsigned j = 0; j < width(); ++j)
-        if ((k >> j) & 1u)
-            gateTerms(CSGN_GATE_NOT, 0, termsOf(planes_[j]), 0, context(), "UIntBatch::operator^");
-    std::vector<CiphertextBatch> planes;
-    for (unsigned j = 0; j < width(); ++j)
-        planes.push_back((k >> j) & 1u ? logicNot(planes_[j]) : planes_[j]);
-    return UIntBatch(planes);
+    return UIntBatch(mapPlanes(
+        width(),
+        [&](unsigned j) {
+            if ((k >> j) & 1u)
+                gateTerms(CSGN_GATE_NOT, 0, termsOf(planes_[j]), 0, context(), "UIntBatch::operator^");
+        },
+        [&](unsigned j) { return (k >> j) & 1u ? logicNot(planes_[j]) : planes_[j]; }));
 }
 
 UIntBatch UIntBatch::shiftLeft(unsigned s) const
 {
-    std::vector<CiphertextBatch> planes;
     const CiphertextBatch zero = zeros(*this);            // one shared payload for every filled plane
-    for (unsigned j = 0; j < width(); ++j)
-        planes.push_back(j >= s ? planes_[j - s] : zero);
-    return UIntBatch(planes);
+    return UIntBatch(mapPlanes(width(), noCheck, [&](unsigned j) { return j >= s ? planes_[j - s] : zero; }));
 }
 
 UIntBatch UIntBatch::shiftRight(unsigned s) const
 {
-    std::vector<CiphertextBatch> planes;
     const CiphertextBatch zero = zeros(*this);
-    for (unsigned j = 0; j < width(); ++j)
-        planes.push_back(s < width() && j < width() - s ? planes_[j + s] : zero);
-    return UIntBatch(planes);
+    return UIntBatch(
+        mapPlanes(width(), noCheck, [&](unsigned j) { return s < width() && j < width() - s ? planes_[j + s] : zero; }));
 }
 
 UIntBatch UIntBatch::rotateLeft(unsigned s) const
 {
     const unsigned w = width();
-    std::vector<CiphertextBatch> planes;
-    for (unsigned j = 0; j < w; ++j)
-        planes.push_back(planes_[(j + w - s % w) % w]);
-    return UIntBatch(planes);
+    return UIntBatch(mapPlanes(w, noCheck, [&](unsigned j) { return planes_[(j + w - s % w) % w]; }));
 }
 
 // ------------------------------------------------------------------ comparisons and select
@@ -721,12 +714,12 @@ UIntBatch select(const CiphertextBatch &sel, const UIntBatch &a, const UIntBatch
 {
     requireSame(a, b, "select");
     requireSameBit(sel, a, "select");
-    for (unsigned j = 0; j < a.width(); ++j)
-        gateTerms(CSGN_GATE_MUX, termsOf(sel), termsOf(a.plane(j)), termsOf(b.plane(j)), a.context(), "select");
-    std::vector<CiphertextBatch> planes;
-    for (unsigned j = 0; j < a.width(); ++j)
-        planes.push_back(logicMux(sel, a.plane(j), b.plane(j)));
-    return UIntBatch::fromPlanes(planes);
+    return UIntBatch::fromPlanes(mapPlanes(
+        a.width(),
+        [&](unsigned j) {
+            gateTerms(CSGN_GATE_MUX, termsOf(sel), termsOf(a.plane(j)), termsOf(b.plane(j)), a.context(), "select");
+        },
+        [&](unsigned j) { return logicMux(sel, a.plane(j), b.plane(j)); }));
 }
 
 } // namespace certFHE
@@ -801,34 +794,22 @@ UIntBatch lookup(const UIntBatch &a, const LookupTable &f)
     if (a.width() != L.w)
         throw std::invalid_argument("certFHE::lookup: the operand's width differs from the table's in_width");
     const Context &ctx = a.context();
-    std::vector<uint64_t> terms(L.w), T(L.m);
-    bool uniform = true;
-    for (unsigned i = 0; i < L.w; ++i) {
-        terms[i] = termsOf(a.plane(i));                   // a ragged plane: its largest element, a bound
-        uniform = uniform && a.plane(i).uniform();
-    }
-    if (csgn_uint_lut_terms(L.w, L.m, L.table.data(), terms.data(), T.data()) != CSGN_OK)
+    const Planes in(a);
+    std::vector<uint64_t> T(L.m);
+    if (csgn_uint_lut_terms(L.w, L.m, L.table.data(), in.terms.data(), T.data()) != CSGN_OK)
         throw std::invalid_argument("certFHE::lookup: an output's result exceeds 2^31 words per element");
     for (unsigned j = 0; j < L.m; ++j)
         checked(T[j], ctx, "lookup");
-    std::vector<CiphertextBatch> out;
-    if (uniform) {
-        const csgn_uint_lut *plan = L.plan(terms);
-        out.reserve(L.m);
-        for (unsigned j = 0; j < L.m; ++j)
-            out.push_back(UIntAccess::make(ctx, a.size(), T[j]));
-        if (a.size()) {
-            std::vector<const uint64_t *> planes(L.w);
-            std::vector<uint64_t *> outs(L.m);
-            for (unsigned i = 0; i < L.w; ++i)
-                planes[i] = a.plane(i).deviceValues();
-            for (unsigned j = 0; j < L.m; ++j)
-                outs[j] = UIntAccess::words(out[j]);
-            detail::check(csgn_uint_lut_apply(plan, ctx.getN(), a.size(), planes.data(), outs.data(), detail::stream()),
+    if (in.uniform) {
+        const csgn_uint_lut *plan = L.plan(in.terms);
+        std::vector<CiphertextBatch> out = makePlanes(ctx, a.size(), T);
+        if (a.size())
+            detail::check(csgn_uint_lut_apply(plan, ctx.getN(), a.size(), sources(in).data(), wordsOf(out).data(),
+                                              detail::stream()),
                           "csgn_uint_lut_apply");
-        }
         return UIntBatch::fromPlanes(out);
     }
+    std::vector<CiphertextBatch> out;
     // ragged: the definition itself through the batch operators
     for (unsigned j = 0; j < L.m; ++j) {
         std::vector<CiphertextBatch> acc;                 // empty until the first monomial
@@ -881,40 +862,25 @@ std::vector<CiphertextBatch> readPlanes(const std::vector<CiphertextBatch> &tabl
     if (rows == 0 || rows > (1ull << v))
         throw std::invalid_argument("certFHE::readAt: the table has " + std::to_string(rows) + " rows, not 1..2^" +
                                     std::to_string(v));
-    std::vector<uint64_t> s(v), t(table.size()), T(table.size());
-    bool uniform = true;
-    for (unsigned k = 0; k < v; ++k) {
-        s[k] = termsOf(index.plane(k));                   // a ragged plane: its largest element, a bound
-        uniform = uniform && index.plane(k).uniform();
-    }
-    const uint64_t E = csgn_uint_read_terms(v, s.data(), rows);
+    const Planes x(index), d(table);
+    const std::vector<uint64_t> &t = d.terms;
+    std::vector<uint64_t> T(table.size());
+    const uint64_t E = csgn_uint_read_terms(v, x.terms.data(), rows);
     for (size_t j = 0; j < table.size(); ++j) {
-        t[j] = termsOf(table[j]);
-        uniform = uniform && table[j].uniform();
         if (E == 0 || t[j] == 0 || t[j] > kMaxWords / E)
             throw std::invalid_argument("certFHE::readAt: an output plane exceeds 2^31 words per element (the index "
                                         "is too wide or has too many terms)");
         T[j] = checked(t[j] * E, ctx, "readAt");
     }
-    std::vector<CiphertextBatch> out;
-    if (uniform || m == 0) {
-        for (size_t j = 0; j < table.size(); ++j)
-            out.push_back(UIntAccess::make(ctx, m, T[j]));
-        if (m) {
-            std::vector<const uint64_t *> x(v), d(table.size());
-            std::vector<uint64_t *> o(table.size());
-            for (unsigned k = 0; k < v; ++k)
-                x[k] = index.plane(k).deviceValues();
-            for (size_t j = 0; j < table.size(); ++j) {
-                d[j] = table[j].deviceValues();
-                o[j] = UIntAccess::words(out[j]);
-            }
-            detail::check(csgn_uint_read(ctx.getN(), m, v, x.data(), s.data(), rows, table.size(), d.data(), t.data(),
-                                         o.data(), detail::stream()),
+    if ((x.uniform && d.uniform) || m == 0) {
+        std::vector<CiphertextBatch> out = makePlanes(ctx, m, T);
+        if (m)
+            detail::check(csgn_uint_read(ctx.getN(), m, v, sources(x).data(), x.terms.data(), rows, table.size(),
+                                         sources(d).data(), t.data(), wordsOf(out).data(), detail::stream()),
                           "csgn_uint_read");
-        }
         return out;
     }
+    std::vector<CiphertextBatch> out;
     // ragged: the definition itself through the batch operators
     for (uint64_t r = 0; r < rows; ++r) {
         const CiphertextBatch eq = equalTo(index, r);

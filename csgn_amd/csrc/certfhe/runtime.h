@@ -9,6 +9,7 @@
 #include <stdexcept>
 #include <string>
 
+#include "Gates.h"
 #include "csgn_hip.h"
 
 namespace certFHE {
@@ -112,6 +113,18 @@ void setDeferral(bool on);             // process-wide switch (Library::deferSma
 bool deferralOn();
 
 inline void *stream() { return nullptr; }   // the classes run on the default stream
+
+// How Gates.cpp and UInt.cpp make a result batch and reach its words (the friend of CiphertextBatch, Batch.h).
+struct BatchAccess {
+    static CiphertextBatch make(const Context &c, uint64_t count, uint64_t terms) { return CiphertextBatch(c, count, terms); }
+    static uint64_t *words(CiphertextBatch &b) { return b.payload->data(); }
+};
+
+// ONE for every element of `like`
+inline CiphertextBatch ones(const CiphertextBatch &like)
+{
+    return constantBatch(like.context(), std::vector<unsigned char>(like.size(), 1));
+}
 
 } // namespace detail
 } // namespace certFHE

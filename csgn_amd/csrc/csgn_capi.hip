@@ -1,6 +1,6 @@
 // csgn_capi.hip -- the extern "C" surface of libcsgn_hip.so (declared in include/csgn_hip.h).
-// Argument validation, error reporting and stream plumbing only; the kernels live in
-// csgn_{mul,add,decrypt,encrypt,permute,compact,harness}.hip.  There is deliberately no CPU fallback anywhere in this library.
+// Argument validation, error reporting and stream plumbing only; the kernels live in the other translation units, behind
+// the launchers of csgn_kernels.h.  There is deliberately no CPU fallback anywhere in this library.
 #include "csgn_capi_util.h"
 #include "csgn_tuning.h"
 
@@ -94,6 +94,44 @@ int check_n(uint64_t n_bits)
     if (((n_bits + 63) / 64) * 8 > 16384)
         return fail(CSGN_ERR_UNSUPPORTED, "n_bits=%llu: terms above 16384 bytes are not supported",
                     (unsigned long long)n_bits);
+    return CSGN_OK;
+}
+
+int check_size(uint64_t batch, uint64_t terms, uint64_t batch_terms, uint64_t dl, const char *label, ...)
+{
+    const bool element = product_below(terms, dl, 1, 1ull << 31);
+    if (element && product_below(batch, batch_terms, dl, 1ull << 60))
+        return CSGN_OK;
+    char who[128];
+    va_list ap;
+    va_start(ap, label);
+    vsnprintf(who, sizeof(who), label, ap);
+    va_end(ap);
+    if (!element)
+        return fail(CSGN_ERR_UNSUPPORTED, "%s: %llu terms per element exceed 2^31 words", who, (unsigned long long)terms);
+    return fail(CSGN_ERR_UNSUPPORTED, "batch of %llu elements: size overflows", (unsigned long long)batch);
+}
+
+int check_width(uint64_t width, uint64_t k)
+{
+    REQUIRE(width >= 1 && width <= 64, "width %llu outside 1..64", (unsigned long long)width);
+    REQUIRE(width == 64 || (k >> width) == 0, "constant %llu does not fit in %llu bits", (unsigned long long)k,
+            (unsigned long long)width);
+    return CSGN_OK;
+}
+
+int check_planes(const uint64_t *const *a, const uint64_t *const *b, uint64_t n, const char *label)
+{
+    for (uint64_t j = 0; j < n; ++j)
+        REQUIRE(a[j] && (!b || b[j]), "null device pointer (%s %llu)", label, (unsigned long long)j);
+    return CSGN_OK;
+}
+
+int check_pair_product(uint64_t t1, uint64_t t2, uint64_t dl)
+{
+    if (t1 >= (1ull << 31) || t2 >= (1ull << 31) || !product_below(t1, t2, dl, 1ull << 32))
+        return fail(CSGN_ERR_UNSUPPORTED, "pair product of %llu x %llu terms exceeds 2^32 words",
+                    (unsigned long long)t1, (unsigned long long)t2);
     return CSGN_OK;
 }
 
@@ -342,9 +380,8 @@ int csgn_mul_uniform(uint64_t n_bits, uint64_t batch, uint64_t t1, uint64_t t2,
         return CSGN_OK;
     REQUIRE(d_left && d_right && d_out, "null device pointer");
     const uint64_t dl = csgn_default_len(n_bits);
-    if (t1 >= (1ull << 31) || t2 >= (1ull << 31) || !product_below(t1, t2, dl, 1ull << 32))
-        return fail(CSGN_ERR_UNSUPPORTED, "pair product of %llu x %llu terms exceeds 2^32 words",
-                    (unsigned long long)t1, (unsigned long long)t2);
+    if (int rc = check_pair_product(t1, t2, dl))
+        return rc;
     if (!product_below(batch, t1 + t2, dl, 1ull << 60))
         return fail(CSGN_ERR_UNSUPPORTED, "batch of %llu pairs: operand size overflows", (unsigned long long)batch);
     HIP_TRY(csgn::mul_uniform(n_bits, batch, t1, t2, (const u64 *)d_left, (const u64 *)d_right,
@@ -512,10 +549,8 @@ int csgn_mul_planned(csgn_mul_plan *plan, uint64_t n_bits, const uint64_t *d_lef
     if (n.batch == 0 || n.max_t1 == 0 || n.max_t2 == 0 || n.total == 0)
         return CSGN_OK;
     REQUIRE(d_left && d_right && d_out, "null device pointer");
-    const uint64_t dl = csgn_default_len(n_bits);
-    if (n.max_t1 >= (1ull << 31) || n.max_t2 >= (1ull << 31) || !product_below(n.max_t1, n.max_t2, dl, 1ull << 32))
-        return fail(CSGN_ERR_UNSUPPORTED, "pair product of %llu x %llu terms exceeds 2^32 words",
-                    (unsigned long long)n.max_t1, (unsigned long long)n.max_t2);
+    if (int rc = check_pair_product(n.max_t1, n.max_t2, csgn_default_len(n_bits)))
+        return rc;
     // host copies of offsets are only used for huge pairs: that is when stale offsets would give wrong words
     if (n.n != 0 && !plan->trust)
         if (int rc = csgn_mul_plan_validate(plan, stream))
@@ -576,10 +611,8 @@ int csgn_mul_ragged(uint64_t n_bits, uint64_t batch,
     if (batch == 0 || max_t1 == 0 || max_t2 == 0 || total_out_terms == 0)
         return CSGN_OK;
     REQUIRE(d_left && d_right && d_out && d_off_left && d_off_right && d_off_out, "null device pointer");
-    const uint64_t dl = csgn_default_len(n_bits);
-    if (max_t1 >= (1ull << 31) || max_t2 >= (1ull << 31) || !product_below(max_t1, max_t2, dl, 1ull << 32))
-        return fail(CSGN_ERR_UNSUPPORTED, "pair product of %llu x %llu terms exceeds 2^32 words",
-                    (unsigned long long)max_t1, (unsigned long long)max_t2);
+    if (int rc = check_pair_product(max_t1, max_t2, csgn_default_len(n_bits)))
+        return rc;
     hipError_t e = csgn::mul_ragged(n_bits, batch, (const u64 *)d_left, (const u64 *)d_off_left,
                                     (const u64 *)d_right, (const u64 *)d_off_right, (u64 *)d_out,
                                     (const u64 *)d_off_out, max_t1, max_t2, total_out_terms, S(stream));
@@ -706,9 +739,9 @@ size_t csgn_decrypt_combined_scratch_bytes(uint64_t batch, uint64_t t1, uint64_t
     return csgn::decrypt_combined_scratch_bytes(batch, t1, t2);
 }
 
-int csgn_decrypt_product_uniform(uint64_t n_bits, uint64_t batch, uint64_t t1, uint64_t t2,
-                                 const uint64_t *d_left, const uint64_t *d_right,
-                                 const uint64_t *d_mask, uint8_t *d_bits, void *d_scratch, void *stream)
+static int decrypt_combined_uniform(bool is_product, uint64_t n_bits, uint64_t batch, uint64_t t1, uint64_t t2,
+                                    const uint64_t *d_left, const uint64_t *d_right, const uint64_t *d_mask,
+                                    uint8_t *d_bits, void *d_scratch, void *stream)
 {
     if (int rc = check_n(n_bits))
         return rc;
@@ -720,26 +753,22 @@ int csgn_decrypt_product_uniform(uint64_t n_bits, uint64_t batch, uint64_t t1, u
         !product_below(batch, t2, csgn_default_len(n_bits), 1ull << 60))
         return fail(CSGN_ERR_UNSUPPORTED, "batch of %llu ciphertexts: size overflows", (unsigned long long)batch);
     HIP_TRY(csgn::decrypt_combined(n_bits, batch, t1, t2, (const u64 *)d_left, (const u64 *)d_right,
-                                   (const u64 *)d_mask, true, d_bits, d_scratch, S(stream)));
+                                   (const u64 *)d_mask, is_product, d_bits, d_scratch, S(stream)));
     return CSGN_OK;
+}
+
+int csgn_decrypt_product_uniform(uint64_t n_bits, uint64_t batch, uint64_t t1, uint64_t t2,
+                                 const uint64_t *d_left, const uint64_t *d_right,
+                                 const uint64_t *d_mask, uint8_t *d_bits, void *d_scratch, void *stream)
+{
+    return decrypt_combined_uniform(true, n_bits, batch, t1, t2, d_left, d_right, d_mask, d_bits, d_scratch, stream);
 }
 
 int csgn_decrypt_sum_uniform(uint64_t n_bits, uint64_t batch, uint64_t t1, uint64_t t2,
                              const uint64_t *d_left, const uint64_t *d_right,
                              const uint64_t *d_mask, uint8_t *d_bits, void *d_scratch, void *stream)
 {
-    if (int rc = check_n(n_bits))
-        return rc;
-    if (batch == 0)
-        return CSGN_OK;
-    REQUIRE(d_mask && d_bits && d_scratch && (d_left || t1 == 0) && (d_right || t2 == 0),
-            "null device pointer");
-    if (!product_below(batch, t1, csgn_default_len(n_bits), 1ull << 60) ||
-        !product_below(batch, t2, csgn_default_len(n_bits), 1ull << 60))
-        return fail(CSGN_ERR_UNSUPPORTED, "batch of %llu ciphertexts: size overflows", (unsigned long long)batch);
-    HIP_TRY(csgn::decrypt_combined(n_bits, batch, t1, t2, (const u64 *)d_left, (const u64 *)d_right,
-                                   (const u64 *)d_mask, false, d_bits, d_scratch, S(stream)));
-    return CSGN_OK;
+    return decrypt_combined_uniform(false, n_bits, batch, t1, t2, d_left, d_right, d_mask, d_bits, d_scratch, stream);
 }
 
 size_t csgn_compact_scratch_bytes(uint64_t n_bits, uint64_t batch, uint64_t total_terms)
@@ -1009,12 +1038,8 @@ int csgn_gate_uniform(uint64_t n_bits, int gate, uint64_t batch, uint64_t t_sel,
         t_b = 0;
     const uint64_t terms = csgn::gate_terms(gate, t_sel, t_a, t_b);
     REQUIRE(terms != 0, "gate %d: an operand it reads has no terms, or the term count overflows", gate);
-    const uint64_t dl = csgn_default_len(n_bits);
-    if (!product_below(terms, dl, 1, 1ull << 31))
-        return fail(CSGN_ERR_UNSUPPORTED, "gate %d: %llu terms per element exceed 2^31 words", gate,
-                    (unsigned long long)terms);
-    if (!product_below(batch, terms, dl, 1ull << 60))
-        return fail(CSGN_ERR_UNSUPPORTED, "batch of %llu elements: size overflows", (unsigned long long)batch);
+    if (int rc = check_size(batch, terms, terms, csgn_default_len(n_bits), "gate %d", gate))
+        return rc;
     if (int rc = require_device("csgn_gate_uniform"))
         return rc;
     if (batch == 0)
@@ -1068,13 +1093,9 @@ int csgn_uint_step(uint64_t n_bits, int step, uint64_t batch, const uint64_t *d_
     const uint64_t terms1 = carry ? csgn::uint_step_terms(step, 1, t_x, t_a, t_b) : 0;
     REQUIRE(terms0 != 0 && (terms1 != 0 || !carry),
             "integer step %d: an operand it reads has no terms, or the term count overflows", step);
-    const uint64_t dl = csgn_default_len(n_bits);
-    const uint64_t terms = terms0 > terms1 ? terms0 : terms1;
-    if (!product_below(terms, dl, 1, 1ull << 31))
-        return fail(CSGN_ERR_UNSUPPORTED, "integer step %d: %llu terms per element exceed 2^31 words", step,
-                    (unsigned long long)terms);
-    if (!product_below(batch, terms0 + terms1, dl, 1ull << 60))
-        return fail(CSGN_ERR_UNSUPPORTED, "batch of %llu elements: size overflows", (unsigned long long)batch);
+    if (int rc = check_size(batch, terms0 > terms1 ? terms0 : terms1, terms0 + terms1, csgn_default_len(n_bits),
+                            "integer step %d", step))
+        return rc;
     if (int rc = require_device("csgn_uint_step"))
         return rc;
     if (batch == 0)
@@ -1102,25 +1123,20 @@ int csgn_uint_plain(uint64_t n_bits, int cmp, uint64_t batch, uint64_t width, ui
     if (int rc = check_n(n_bits))
         return rc;
     REQUIRE(cmp >= CSGN_UINT_PLAIN_EQ && cmp <= CSGN_UINT_PLAIN_GE, "unknown comparison %d", cmp);
-    REQUIRE(width >= 1 && width <= 64, "width %llu outside 1..64", (unsigned long long)width);
-    REQUIRE(width == 64 || (k >> width) == 0, "constant %llu does not fit in %llu bits", (unsigned long long)k,
-            (unsigned long long)width);
+    if (int rc = check_width(width, k))
+        return rc;
     REQUIRE(h_planes && h_terms, "null host pointer");
     const uint64_t terms = csgn::uint_plain_terms(cmp, width, k, (const u64 *)h_terms);
     REQUIRE(terms != 0, "comparison %d: a plane has no terms, or the term count overflows", cmp);
-    const uint64_t dl = csgn_default_len(n_bits);
-    if (!product_below(terms, dl, 1, 1ull << 31))
-        return fail(CSGN_ERR_UNSUPPORTED, "comparison %d: %llu terms per element exceed 2^31 words", cmp,
-                    (unsigned long long)terms);
-    if (!product_below(batch, terms, dl, 1ull << 60))
-        return fail(CSGN_ERR_UNSUPPORTED, "batch of %llu elements: size overflows", (unsigned long long)batch);
+    if (int rc = check_size(batch, terms, terms, csgn_default_len(n_bits), "comparison %d", cmp))
+        return rc;
     if (int rc = require_device("csgn_uint_plain"))
         return rc;
     if (batch == 0)
         return CSGN_OK;
     REQUIRE(d_out, "null device pointer");
-    for (uint64_t j = 0; j < width; ++j)
-        REQUIRE(h_planes[j], "null device pointer (plane %llu)", (unsigned long long)j);
+    if (int rc = check_planes(h_planes, nullptr, width, "plane"))
+        return rc;
     HIP_TRY(csgn::uint_plain(n_bits, cmp, batch, width, k, (const u64 *const *)h_planes, (const u64 *)h_terms,
                              (u64 *)d_out, S(stream)));
     return CSGN_OK;
@@ -1143,9 +1159,8 @@ int csgn_uint_addk(uint64_t n_bits, uint64_t batch, uint64_t width, uint64_t k, 
 {
     if (int rc = check_n(n_bits))
         return rc;
-    REQUIRE(width >= 1 && width <= 64, "width %llu outside 1..64", (unsigned long long)width);
-    REQUIRE(width == 64 || (k >> width) == 0, "constant %llu does not fit in %llu bits", (unsigned long long)k,
-            (unsigned long long)width);
+    if (int rc = check_width(width, k))
+        return rc;
     REQUIRE(h_planes && h_terms && h_outs, "null host pointer");
     uint64_t T[65];
     REQUIRE(csgn::uint_addk_terms(width, k, (const u64 *)h_terms, (u64 *)T),
@@ -1153,18 +1168,15 @@ int csgn_uint_addk(uint64_t n_bits, uint64_t batch, uint64_t width, uint64_t k, 
     const uint64_t dl = csgn_default_len(n_bits);
     for (uint64_t j = 0; j < width + (d_carry ? 1 : 0); ++j) {
         const uint64_t terms = T[j] + (negate_out && j < width ? 1 : 0);
-        if (!product_below(terms, dl, 1, 1ull << 31))
-            return fail(CSGN_ERR_UNSUPPORTED, "integer + constant: plane %llu has %llu terms per element, past 2^31 words",
-                        (unsigned long long)j, (unsigned long long)terms);
-        if (!product_below(batch, terms, dl, 1ull << 60))
-            return fail(CSGN_ERR_UNSUPPORTED, "batch of %llu elements: size overflows", (unsigned long long)batch);
+        if (int rc = check_size(batch, terms, terms, dl, "integer + constant: plane %llu", (unsigned long long)j))
+            return rc;
     }
     if (int rc = require_device("csgn_uint_addk"))
         return rc;
     if (batch == 0)
         return CSGN_OK;
-    for (uint64_t j = 0; j < width; ++j)
-        REQUIRE(h_planes[j] && h_outs[j], "null device pointer (plane %llu)", (unsigned long long)j);
+    if (int rc = check_planes(h_planes, h_outs, width, "plane"))
+        return rc;
     HIP_TRY(csgn::uint_addk(n_bits, batch, width, k, negate_out != 0, (const u64 *const *)h_planes, (const u64 *)h_terms,
                             (u64 *const *)h_outs, (u64 *)d_carry, S(stream)));
     return CSGN_OK;
@@ -1200,10 +1212,9 @@ int csgn_uint_lut_create(uint64_t in_width, uint64_t out_width, const uint64_t *
     uint64_t T[csgn::kLutMaxOut];
     if (int rc = csgn_uint_lut_terms(in_width, out_width, h_table, h_terms, T))
         return rc;
-    for (uint64_t j = 0; j < out_width; ++j)
-        if (T[j] >= (1ull << 31))
-            return fail(CSGN_ERR_UNSUPPORTED, "lookup table: output %llu has %llu terms per element (2^31 or more)",
-                        (unsigned long long)j, (unsigned long long)T[j]);
+    for (uint64_t j = 0; j < out_width; ++j)                 // at any n_bits: a term is one word or more
+        if (int rc = check_size(0, T[j], T[j], 1, "lookup table: output %llu", (unsigned long long)j))
+            return rc;
     if (int rc = require_device("csgn_uint_lut_create"))
         return rc;
     csgn_uint_lut *l = new csgn_uint_lut();
@@ -1241,21 +1252,17 @@ int csgn_uint_lut_apply(const csgn_uint_lut *lut, uint64_t n_bits, uint64_t batc
     REQUIRE(h_planes && h_out, "null host pointer");
     const csgn::LutPlan &p = lut->plan;
     const uint64_t dl = csgn_default_len(n_bits);
-    for (u32 j = 0; j < p.m; ++j) {
-        if (!product_below(p.T[j], dl, 1, 1ull << 31))
-            return fail(CSGN_ERR_UNSUPPORTED, "lookup table: output %u has %llu terms per element, past 2^31 words", j,
-                        (unsigned long long)p.T[j]);
-        if (!product_below(batch, p.T[j], dl, 1ull << 60))
-            return fail(CSGN_ERR_UNSUPPORTED, "batch of %llu elements: size overflows", (unsigned long long)batch);
-    }
+    for (u32 j = 0; j < p.m; ++j)
+        if (int rc = check_size(batch, p.T[j], p.T[j], dl, "lookup table: output %u", j))
+            return rc;
     if (int rc = require_device("csgn_uint_lut_apply"))
         return rc;
     if (batch == 0)
         return CSGN_OK;
-    for (u32 i = 0; i < p.w; ++i)
-        REQUIRE(h_planes[i], "null device pointer (plane %u)", i);
-    for (u32 j = 0; j < p.m; ++j)
-        REQUIRE(h_out[j], "null device pointer (output %u)", j);
+    if (int rc = check_planes(h_planes, nullptr, p.w, "plane"))
+        return rc;
+    if (int rc = check_planes(h_out, nullptr, p.m, "output"))
+        return rc;
     HIP_TRY(csgn::uint_lut(p, n_bits, batch, (const u64 *const *)h_planes, (u64 *const *)h_out, S(stream)));
     return CSGN_OK;
 }
@@ -1317,10 +1324,8 @@ int csgn_gather(uint64_t n_bits, uint64_t count_in, const uint64_t *d_src, const
     const uint64_t dl = csgn_default_len(n_bits);
     if (!d_src_off) {
         REQUIRE(!d_dst_off, "gather: a uniform source gives a uniform output (d_dst_off must be NULL)");
-        if (!product_below(t_src, dl, 1, 1ull << 31))
-            return fail(CSGN_ERR_UNSUPPORTED, "gather: %llu terms per element exceed 2^31 words", (unsigned long long)t_src);
-        if (!product_below(count_out, t_src, dl, 1ull << 60))
-            return fail(CSGN_ERR_UNSUPPORTED, "gather of %llu elements: size overflows", (unsigned long long)count_out);
+        if (int rc = check_size(count_out, t_src, t_src, dl, "gather"))
+            return rc;
         REQUIRE(count_out == 0 || t_src == 0 || (d_src && d_dst), "null device pointer");
         if (int rc = require_device("csgn_gather"))
             return rc;
@@ -1353,14 +1358,11 @@ int csgn_gather_planes(uint64_t n_bits, uint64_t n_planes, const uint64_t *const
     if (int rc = check_gather_counts(count_in, count_out))
         return rc;
     const uint64_t dl = csgn_default_len(n_bits);
-    uint64_t words = 0;
+    uint64_t terms = 0;                                       // of the planes so far: all of them fit 2^60 words
     for (uint64_t j = 0; j < n_planes; ++j) {
-        if (!product_below(h_terms[j], dl, 1, 1ull << 31))
-            return fail(CSGN_ERR_UNSUPPORTED, "gather: plane %llu has %llu terms per element, past 2^31 words",
-                        (unsigned long long)j, (unsigned long long)h_terms[j]);
-        if (!product_below(count_out, h_terms[j], dl, (1ull << 60) - words))
-            return fail(CSGN_ERR_UNSUPPORTED, "gather of %llu elements: size overflows", (unsigned long long)count_out);
-        words += count_out * h_terms[j] * dl;
+        terms += h_terms[j];
+        if (int rc = check_size(count_out, h_terms[j], terms, dl, "gather: plane %llu", (unsigned long long)j))
+            return rc;
         REQUIRE(count_out == 0 || h_terms[j] == 0 || (h_src[j] && h_dst[j]), "null device pointer (plane %llu)",
                 (unsigned long long)j);
     }
@@ -1403,20 +1405,20 @@ int csgn_uint_read(uint64_t n_bits, uint64_t batch, uint64_t index_width, const 
     const uint64_t dl = csgn_default_len(n_bits);
     for (uint64_t j = 0; j < width; ++j) {
         REQUIRE(h_table_terms[j] != 0, "read: table plane %llu has no terms", (unsigned long long)j);
-        if (!product_below(h_table_terms[j], E, dl, 1ull << 31))
-            return fail(CSGN_ERR_UNSUPPORTED, "read: output %llu has %llu x %llu terms per element, past 2^31 words",
-                        (unsigned long long)j, (unsigned long long)h_table_terms[j], (unsigned long long)E);
-        if (!product_below(batch, h_table_terms[j] * E, dl, 1ull << 60))
-            return fail(CSGN_ERR_UNSUPPORTED, "batch of %llu elements: size overflows", (unsigned long long)batch);
+        unsigned long long terms;                            // of output j; a product that wraps is past every limit
+        if (__builtin_mul_overflow((unsigned long long)h_table_terms[j], (unsigned long long)E, &terms))
+            terms = ~0ull;
+        if (int rc = check_size(batch, terms, terms, dl, "read: output %llu", (unsigned long long)j))
+            return rc;
     }
     if (int rc = require_device("csgn_uint_read"))
         return rc;
     if (batch == 0)
         return CSGN_OK;
-    for (uint64_t k = 0; k < index_width; ++k)
-        REQUIRE(h_index[k], "null device pointer (index plane %llu)", (unsigned long long)k);
-    for (uint64_t j = 0; j < width; ++j)
-        REQUIRE(h_table[j] && h_out[j], "null device pointer (table plane or output %llu)", (unsigned long long)j);
+    if (int rc = check_planes(h_index, nullptr, index_width, "index plane"))
+        return rc;
+    if (int rc = check_planes(h_table, h_out, width, "table plane or output"))
+        return rc;
     HIP_TRY(csgn::uint_read(n_bits, batch, index_width, (const u64 *const *)h_index, (const u64 *)h_index_terms, rows,
                             width, (const u64 *const *)h_table, (const u64 *)h_table_terms, (u64 *const *)h_out,
                             S(stream)));

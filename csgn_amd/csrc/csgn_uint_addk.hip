@@ -12,17 +12,16 @@
 // One lane writes one unit; a wave's store covers 64 consecutive units of consecutive terms of one plane.  A workgroup
 // belongs to one plane (each plane's lane range is rounded up to whole workgroups), so the plane, its sizes and its
 // pointers are scalar.
-#include "csgn_device.h"
+#include "csgn_chain.h"
 #include "csgn_hip.h"
 
 #include <algorithm>
-#include <vector>
 
 namespace csgn {
 
 namespace {
 
-constexpr u32 kMaxLevels = 64, kMaxPlanes = kMaxLevels + 1;   // the carry-out is plane `width`
+constexpr u32 kMaxLevels = kChainMaxLevels, kMaxPlanes = kMaxLevels + 1;   // the carry-out is plane `width`
 
 // By value in the kernel arguments (3.7 KB of the 4 KB limit; uniform indices, scalar loads).  The level table is
 // k_uint_plain's: level j in [base, width):
@@ -87,10 +86,9 @@ __global__ void __launch_bounds__(256) k_uint_addk(AddkArgs a)
 // ------------------------------------------------------------------------------ the definition on the host
 
 struct AddkShape {
-    u32 w = 0, base = 0;
-    bool zero = false;                     // k = 0
-    u64 k = 0;
-    u64 L[kMaxLevels] = {};                // T(c_j), j >= base
+    u32 w = 0;
+    bool zero = false;                     // k = 0: no chain
+    Chain c;                               // the carries: the GT chain of ~k, c.L[j] = T(c_j)
     u64 T[kMaxPlanes] = {};                // terms of out_j without negate_out; T[w]: the carry-out
 };
 
@@ -98,42 +96,24 @@ struct AddkShape {
 bool addk_shape(u64 w, u64 k, const u64 *t, AddkShape &sh)
 {
     sh = AddkShape();
-    if (w < 1 || w > 64 || !t)
+    if (!chain_arguments(w, k, t))
         return false;
-    if (w < 64 && (k >> w) != 0)
-        return false;
-    for (u64 j = 0; j < w; ++j)
-        if (t[j] == 0 || t[j] >= kTermLimit)
-            return false;
     sh.w = (u32)w;
-    sh.k = k;
     sh.zero = k == 0;
-    if (sh.zero) {
-        for (u64 j = 0; j < w; ++j)
-            sh.T[j] = t[j];
-        sh.T[w] = 1;
+    std::copy(t, t + w, sh.T);
+    sh.T[w] = 1;
+    if (sh.zero)
         return true;
-    }
-    sh.base = (u32)__builtin_ctzll(k);
-    for (u64 j = 0; j < sh.base; ++j)
-        sh.T[j] = t[j];
-    sh.T[sh.base] = t[sh.base] + 1;
-    u64 c = t[sh.base];
-    sh.L[sh.base] = c;
-    for (u64 j = sh.base + 1; j < w; ++j) {
-        const u64 bit = (k >> j) & 1u;
-        sh.T[j] = t[j] + c + bit;
+    sh.c = chain_greater(w, ~k & (w == 64 ? ~0ull : (1ull << w) - 1));
+    if (!chain_terms(sh.c, t))
+        return false;
+    sh.T[sh.c.base] += 1;
+    for (u64 j = sh.c.base + 1; j < w; ++j) {
+        sh.T[j] += sh.c.L[j - 1] + ((k >> j) & 1u);
         if (sh.T[j] >= kTermLimit)
             return false;
-        if (!term_mul(c, t[j] + bit, c))
-            return false;
-        if (bit)
-            c += t[j];
-        if (c >= kTermLimit)
-            return false;
-        sh.L[j] = c;
     }
-    sh.T[w] = c;
+    sh.T[w] = sh.c.L[w - 1];
     return true;
 }
 
@@ -157,9 +137,9 @@ bool addk_use_fused(const AddkShape &sh, bool carry, u64 n_bits, u64 batch)
         double walked = 0, written = 0, chained = 0;
         for (u32 p = 0; p < np; ++p) {
             written += (double)sh.T[p];
-            if (p > sh.base) {
-                chained += (double)sh.L[p - 1];
-                walked += (double)sh.L[p - 1] * (p - sh.base);
+            if (p > sh.c.base) {
+                chained += (double)sh.c.L[p - 1];
+                walked += (double)sh.c.L[p - 1] * (p - sh.c.base);
             }
         }
         const double bytes = written * (double)batch * (double)((n_bits + 63) / 64) * 8.0;
@@ -176,23 +156,11 @@ hipError_t addk_fused(const AddkShape &sh, u64 n_bits, u64 batch, bool neg, cons
     a.U = U;
     a.dU = csgn_fastdiv_make(U);
     a.last_mask = last_word_mask(n_bits);
-    a.base = sh.base;
+    a.base = sh.c.base;
     a.width = sh.w;
     a.np = sh.w + (carry ? 1u : 0u);
     a.zero = sh.zero ? 1u : 0u;
-    const u32 top = a.np - 1u;                            // levels [base, top) are walked
-    for (u32 j = 0; j < kMaxLevels; ++j) {
-        u32 d = 1;
-        a.t[j] = j < sh.w ? (u32)std::min<u64>(t[j], 0xFFFFFFFFu) : 1u;
-        a.pend[j] = 0xFFFFFFFFu;
-        if (!sh.zero && j > sh.base && j < top) {
-            const u64 bit = (sh.k >> j) & 1u;
-            d = (u32)(t[j] + bit);
-            if (bit)
-                a.pend[j] = (u32)(sh.L[j - 1] * d);
-        }
-        a.rad.set(j, d);
-    }
+    chain_fill(sh.zero ? nullptr : &sh.c, sh.w, a.np - 1u, t, a);   // levels [base, np - 1) are walked
     u64 units[kMaxPlanes], sum_units = 0;                 // per element
     for (u32 p = 0; p < kMaxPlanes; ++p) {
         units[p] = 1;
@@ -200,7 +168,7 @@ hipError_t addk_fused(const AddkShape &sh, u64 n_bits, u64 batch, bool neg, cons
             const u64 T = sh.T[p] + (neg && p < sh.w ? 1 : 0);
             units[p] = T * U;
             sum_units += units[p];
-            a.chain[p] = sh.zero ? (p == sh.w ? 1u : 0u) : p > sh.base ? (u32)sh.L[p - 1] : 0u;
+            a.chain[p] = sh.zero ? (p == sh.w ? 1u : 0u) : p > sh.c.base ? (u32)sh.c.L[p - 1] : 0u;
         }
         a.PU.set(p, (u32)units[p]);
     }
@@ -231,9 +199,9 @@ hipError_t addk_fused(const AddkShape &sh, u64 n_bits, u64 batch, bool neg, cons
     return hipSuccess;
 }
 
-// The composed form: the same chain plane by plane through the tuned launchers with pitched writes.  The running carry
-// ping-pongs through one temporary block (scratch_take, csgn_kernels.h) -- c_m is a_m itself, read in place -- and n_j is the copy of
-// a_j followed by ONE; the last carry is written to `carry` when asked and not computed otherwise.
+// The composed form: csgn_chain.h's over the carries, each output plane written with pitched copies when its carry
+// comes in.  c_m is a_m itself, read in place; the last carry is written to `carry` when asked and not computed
+// otherwise.
 hipError_t addk_composed(const AddkShape &sh, u64 n_bits, u64 batch, bool neg, const u64 *const *planes, const u64 *t,
                          u64 *const *outs, u64 *carry, hipStream_t s)
 {
@@ -242,64 +210,32 @@ hipError_t addk_composed(const AddkShape &sh, u64 n_bits, u64 batch, bool neg, c
         return add_uniform(n_bits, batch, terms, 0, src, nullptr, dst, s, pitch);
     };
     auto ones = [&](u64 *dst, u64 pitch) { return const_fill(n_bits, batch, nullptr, 1, dst, pitch, s); };
-    const u32 w = sh.w, m = sh.base;
-    const u32 last = carry ? w - 1 : w - 2;               // the last level whose carry is needed (w >= 2 below)
-    u64 maxL = 0, maxN = 0;
-    if (!sh.zero && (carry || w >= 2))
-        for (u32 j = m + 1; j <= last && j < w; ++j) {
-            if (j < w - 1 || !carry)
-                maxL = std::max(maxL, sh.L[j]);
-            if ((sh.k >> j) & 1u)
-                maxN = std::max(maxN, t[j] + 1);
-        }
-    const u64 words = batch * dL * (2 * maxL + maxN);
-    bool owned = false;
-    hipError_t e = hipSuccess;
-    u64 *block = words ? scratch_take(SCRATCH_UINT_ADDK, words * 8, s, owned, e) : nullptr;
-    if (e != hipSuccess)
-        return e;
-    u64 *buf[2] = {block, block ? block + batch * maxL * dL : nullptr};
-    u64 *nbuf = block ? block + 2 * batch * maxL * dL : nullptr;
-    const u64 *cur = nullptr;                             // c_{j-1}
-    for (u32 j = 0; j < w && e == hipSuccess; ++j) {
-        const bool in_chain = !sh.zero && j >= m, bit = in_chain && ((sh.k >> j) & 1u);
+    const u32 w = sh.w, m = sh.zero ? w : sh.c.base;
+    // out_j, with cur = c_{j-1} (j > m)
+    auto plane = [&](u32 j, const u64 *cur) {
+        if (j >= w)
+            return hipSuccess;
         const u64 pitch = (sh.T[j] + (neg ? 1 : 0)) * dL;
         u64 at = t[j];
-        e = copy(planes[j], t[j], outs[j], pitch);
-        if (e == hipSuccess && in_chain && j > m) {
-            e = copy(cur, sh.L[j - 1], outs[j] + at * dL, pitch);
-            at += sh.L[j - 1];
+        hipError_t e = copy(planes[j], t[j], outs[j], pitch);
+        if (e == hipSuccess && j > m) {
+            e = copy(cur, sh.c.L[j - 1], outs[j] + at * dL, pitch);
+            at += sh.c.L[j - 1];
         }
-        if (e == hipSuccess && bit)
+        if (e == hipSuccess && at < sh.T[j])                  // the ONE of k_j = 1
             e = ones(outs[j] + at++ * dL, pitch);
         if (e == hipSuccess && neg)
             e = ones(outs[j] + at++ * dL, pitch);
-        if (e != hipSuccess || !in_chain || (j == w - 1 && !carry))
-            continue;
-        if (j == m) {
-            cur = planes[m];
-            if (j == w - 1)
-                e = copy(planes[m], t[m], carry, t[m] * dL);
-            continue;
-        }
-        u64 *dst = j == w - 1 ? carry : buf[(j - m) & 1u];
-        const u64 Lb = sh.L[j - 1], cp = sh.L[j] * dL, r = t[j] + (bit ? 1 : 0);
-        const u64 *f = planes[j];
-        if (bit) {                                            // n_j materialised
-            e = copy(planes[j], t[j], nbuf, r * dL);
-            if (e == hipSuccess)
-                e = ones(nbuf + t[j] * dL, r * dL);
-            f = nbuf;
-        }
-        if (e == hipSuccess)
-            e = mul_uniform(n_bits, batch, Lb, r, cur, f, dst, 0, s, cp);
-        if (e == hipSuccess && bit)
-            e = copy(planes[j], t[j], dst + Lb * r * dL, cp);
-        cur = dst;
+        return e;
+    };
+    if (sh.zero) {                                            // every plane a copy, the carry-out ZERO
+        hipError_t e = hipSuccess;
+        for (u32 j = 0; j < w && e == hipSuccess; ++j)
+            e = plane(j, nullptr);
+        return e == hipSuccess && carry ? const_fill(n_bits, batch, nullptr, 0, carry, dL, s) : e;
     }
-    if (e == hipSuccess && sh.zero && carry)
-        e = const_fill(n_bits, batch, nullptr, 0, carry, dL, s);
-    return scratch_done(block, owned, e);
+    return chain_composed(sh.c, carry ? w : w - 1, SCRATCH_UINT_ADDK, n_bits, batch, planes, t, true, carry,
+                          sh.c.L[w - 1] * dL, s, plane);
 }
 
 } // namespace

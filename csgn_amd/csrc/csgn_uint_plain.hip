@@ -15,7 +15,7 @@
 // only the top (fast) levels that span a run per term, and keeps the AND of the levels below that cut in registers,
 // keyed by the index that reaches the cut; consecutive terms share it until the fast digits wrap.  A fast level of radix
 // 1 moves no digit: its factor is a per-lane constant, loaded once per lane, not per term.
-#include "csgn_device.h"
+#include "csgn_chain.h"
 #include "csgn_hip.h"
 
 #include <algorithm>
@@ -24,7 +24,7 @@ namespace csgn {
 
 namespace {
 
-constexpr u32 kMaxLevels = 64;
+constexpr u32 kMaxLevels = kChainMaxLevels;
 constexpr u32 kRun = 16;              // terms per lane
 
 // The level table, by value in the kernel arguments (uniform, scalar loads).  Level j in [base, top]:
@@ -118,12 +118,11 @@ __global__ void __launch_bounds__(256) k_uint_plain(PlainArgs a)
 
 // ------------------------------------------------------------------------------ the definitions on the host
 
-// Level table of one comparison: the chain the kernel decodes and the composed form runs.
+// One comparison: the chain (csgn_chain.h) the kernel decodes and the composed form runs, or ZERO.
 struct PlainShape {
     bool zero = false, neg = false;
-    u32 w = 0, base = 0;
-    u64 nfac = 0, sum = 0, tail_n = 0;     // bit j
-    u64 L[kMaxLevels] = {};                // terms of the running value after level j (j >= base)
+    u32 w = 0;
+    Chain c;
     u64 T = 0;                             // terms of the result
 };
 
@@ -131,13 +130,8 @@ struct PlainShape {
 bool plain_shape(int cmp, u64 w, u64 k, const u64 *t, PlainShape &sh)
 {
     sh = PlainShape();
-    if (cmp < CSGN_UINT_PLAIN_EQ || cmp > CSGN_UINT_PLAIN_GE || w < 1 || w > 64 || !t)
+    if (cmp < CSGN_UINT_PLAIN_EQ || cmp > CSGN_UINT_PLAIN_GE || !chain_arguments(w, k, t))
         return false;
-    if (w < 64 && (k >> w) != 0)
-        return false;
-    for (u64 j = 0; j < w; ++j)
-        if (t[j] == 0 || t[j] >= kTermLimit)
-            return false;
     sh.w = (u32)w;
     const u64 all = w == 64 ? ~0ull : (1ull << w) - 1;
     // NE = NOT EQ, LE = NOT GT, GE = NOT LT
@@ -150,45 +144,21 @@ bool plain_shape(int cmp, u64 w, u64 k, const u64 *t, PlainShape &sh)
         sh.T = sh.neg ? 2 : 1;
         return true;
     }
-    auto bit = [&](u64 j) { return (k >> j) & 1u; };
+    Chain &c = sh.c;
     if (base_cmp == CSGN_UINT_PLAIN_EQ) {
-        sh.base = 0;
-        for (u64 j = 0; j < w; ++j)
-            if (!bit(j))
-                sh.nfac |= 1ull << j;                            // g_j = k_j ? a_j : n_j
+        c.nfac = ~k & all;                                       // g_j = k_j ? a_j : n_j, all factors
     } else if (base_cmp == CSGN_UINT_PLAIN_LT) {
-        sh.base = (u32)__builtin_ctzll(k);                       // l = n_m
-        sh.nfac |= 1ull << sh.base;
-        for (u64 j = sh.base + 1; j < w; ++j) {
-            if (bit(j)) {                                        // l = (l * a_j) + n_j
-                sh.sum |= 1ull << j;
-                sh.tail_n |= 1ull << j;
-            } else {
-                sh.nfac |= 1ull << j;                            // l = l * n_j
-            }
-        }
+        c.base = (u32)__builtin_ctzll(k);                        // l = n_m
+        c.sum = c.tail_n = k & (all << c.base << 1);             // l = (l * a_j) + n_j where k_j = 1
+        c.nfac = ~k & all & (all << c.base << 1);                // l = l * n_j where k_j = 0
+        c.nfac |= 1ull << c.base;
     } else {
-        sh.base = (u32)__builtin_ctzll(~k);                      // l = a_m
-        for (u64 j = sh.base + 1; j < w; ++j) {
-            if (!bit(j)) {                                       // l = (l * n_j) + a_j
-                sh.sum |= 1ull << j;
-                sh.nfac |= 1ull << j;
-            }                                                    // else l = l * a_j
-        }
+        c = chain_greater(w, k);
     }
-    auto radix = [&](u64 j) { return t[j] + ((sh.nfac >> j) & 1u); };
-    u64 l = radix(sh.base);
-    sh.L[sh.base] = l;
-    for (u64 j = sh.base + 1; j < w; ++j) {
-        if (!term_mul(l, radix(j), l))
-            return false;
-        if ((sh.sum >> j) & 1u)
-            l += t[j] + ((sh.tail_n >> j) & 1u);
-        if (l >= kTermLimit)
-            return false;
-        sh.L[j] = l;
-    }
-    sh.T = l + (sh.neg ? 1 : 0);
+    c.top = sh.w - 1;
+    if (!chain_terms(c, t))
+        return false;
+    sh.T = c.L[c.top] + (sh.neg ? 1 : 0);
     return sh.T < kTermLimit;
 }
 
@@ -208,7 +178,7 @@ hipError_t plain_fused(const PlainShape &sh, u64 n_bits, u64 batch, const u64 *c
     a.zero = sh.zero ? 1u : 0u;
     a.neg = sh.neg ? 1u : 0u;
     a.T = (u32)sh.T;
-    a.base = sh.base;
+    a.base = sh.c.base;
     a.top = sh.w - 1;
     a.R = (u32)std::min<u64>(sh.T, kRun);
     a.runs = (u32)((sh.T + a.R - 1) / a.R);
@@ -219,27 +189,15 @@ hipError_t plain_fused(const PlainShape &sh, u64 n_bits, u64 batch, const u64 *c
     a.cut = sh.zero ? 1u : sh.w;
     if (!sh.zero) {
         u64 span = 1;
-        while (a.cut > sh.base + 1 && span < a.R) {
+        while (a.cut > sh.c.base + 1 && span < a.R) {
             --a.cut;
-            span *= t[a.cut] + ((sh.nfac >> a.cut) & 1u);
+            span *= t[a.cut] + ((sh.c.nfac >> a.cut) & 1u);
         }
     }
-    for (u32 j = 0; j < kMaxLevels; ++j) {
-        u32 d = 1;
-        a.pend[j] = 0xFFFFFFFFu;
-        if (!sh.zero && j < sh.w) {
-            a.t[j] = (u32)t[j];
-            if (j > sh.base) {
-                const u64 r = t[j] + ((sh.nfac >> j) & 1u);
-                d = (u32)r;
-                if (r == 1)
-                    a.unit |= 1ull << j;
-                if ((sh.sum >> j) & 1u)
-                    a.pend[j] = (u32)(sh.L[j - 1] * r);
-            }
-        }
-        a.rad.set(j, d);
-    }
+    chain_fill(sh.zero ? nullptr : &sh.c, sh.w, sh.w, t, a);
+    for (u32 j = sh.c.base + 1; !sh.zero && j < sh.w; ++j)
+        if (a.rad.d[j] == 1u)
+            a.unit |= 1ull << j;
     a.xcd = stream_xcd(batch * sh.T * U);
     const u64 per = std::max<u64>(1, 0xFFFFFF00ull / a.IPE);            // elements per launch: < 2^32 lane items
     for (u64 e0 = 0; e0 < batch; e0 += per) {
@@ -257,9 +215,7 @@ hipError_t plain_fused(const PlainShape &sh, u64 n_bits, u64 batch, const u64 *c
     return hipSuccess;
 }
 
-// The composed form: the same chain through the tuned launchers, level by level, each level's value written whole
-// before the next reads it.  n_j is the copy of a_j followed by ONE (csgn_gate_uniform NOT's words).  The running values
-// ping-pong through one temporary block (scratch_take, csgn_kernels.h); the last level writes d_out.
+// The composed form: csgn_chain.h's, the last level written to d_out; the negation's ONE follows it.
 hipError_t plain_composed(const PlainShape &sh, u64 n_bits, u64 batch, const u64 *const *planes, const u64 *t, u64 *out,
                           hipStream_t s)
 {
@@ -271,49 +227,12 @@ hipError_t plain_composed(const PlainShape &sh, u64 n_bits, u64 batch, const u64
             e = const_fill(n_bits, batch, nullptr, 1, out + dL, pitchT, s);
         return e;
     }
-    // a list a_j (+ ONE when n) written at dst with pitch
-    auto list = [&](u32 j, bool n, u64 *dst, u64 pitch) {
-        hipError_t e = add_uniform(n_bits, batch, t[j], 0, planes[j], nullptr, dst, s, pitch);
-        if (e == hipSuccess && n)
-            e = const_fill(n_bits, batch, nullptr, 1, dst + t[j] * dL, pitch, s);
-        return e;
-    };
-    const u32 top = sh.w - 1;
-    u64 maxL = 0, maxN = 0;
-    for (u32 j = sh.base; j < top; ++j)
-        maxL = std::max(maxL, sh.L[j]);
-    for (u32 j = sh.base + 1; j <= top; ++j)
-        if ((sh.nfac >> j) & 1u)
-            maxN = std::max(maxN, t[j] + 1);
-    const u64 words = batch * dL * (2 * maxL + maxN);
-    bool owned = false;
-    hipError_t e = hipSuccess;
-    u64 *block = words ? scratch_take(SCRATCH_UINT_PLAIN, words * 8, s, owned, e) : nullptr;
-    if (e != hipSuccess)
-        return e;
-    u64 *buf[2] = {block, block ? block + batch * maxL * dL : nullptr};
-    u64 *nbuf = block ? block + 2 * batch * maxL * dL : nullptr;
-    u64 *cur = sh.base == top ? out : buf[0];
-    e = list(sh.base, (sh.nfac >> sh.base) & 1u, cur, (sh.base == top ? sh.T : sh.L[sh.base]) * dL);
-    for (u32 j = sh.base + 1; j <= top && e == hipSuccess; ++j) {
-        u64 *dst = j == top ? out : buf[(j - sh.base) & 1u];
-        const u64 Lb = sh.L[j - 1], pitch = (j == top ? sh.T : sh.L[j]) * dL;
-        const bool nf = (sh.nfac >> j) & 1u, sum = (sh.sum >> j) & 1u;
-        const u64 r = t[j] + (nf ? 1 : 0);
-        const u64 *f = planes[j];
-        if (nf) {                                             // n_j materialised
-            e = list(j, true, nbuf, r * dL);
-            f = nbuf;
-        }
-        if (e == hipSuccess)
-            e = mul_uniform(n_bits, batch, Lb, r, cur, f, dst, 0, s, pitch);
-        if (e == hipSuccess && sum)
-            e = list(j, (sh.tail_n >> j) & 1u, dst + Lb * r * dL, pitch);
-        cur = dst;
-    }
-    if (e == hipSuccess && sh.neg)
-        e = const_fill(n_bits, batch, nullptr, 1, out + (sh.T - 1) * dL, pitchT, s);
-    return scratch_done(block, owned, e);
+    return chain_composed(sh.c, sh.w, SCRATCH_UINT_PLAIN, n_bits, batch, planes, t, false, out, pitchT, s,
+                          [&](u32 j, const u64 *) {
+                              if (j < sh.w || !sh.neg)
+                                  return hipSuccess;
+                              return const_fill(n_bits, batch, nullptr, 1, out + (sh.T - 1) * dL, pitchT, s);
+                          });
 }
 
 } // namespace

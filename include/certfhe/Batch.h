@@ -26,14 +26,12 @@ namespace certFHE {
 
 class BatchCircuit;
 namespace detail {
-struct GateAccess;   // Gates.cpp
-struct UIntAccess;   // UInt.cpp
+struct BatchAccess;   // csgn_amd/csrc/certfhe/runtime.h
 }
 
 class CiphertextBatch {
     friend class BatchCircuit;
-    friend struct detail::GateAccess;
-    friend struct detail::UIntAccess;
+    friend struct detail::BatchAccess;
     std::shared_ptr<detail::DevicePayload> payload;   // total terms * dL words, element after element
     uint64_t count_;
     uint64_t terms_;                                   // per element when uniform; 0 when ragged

@@ -99,6 +99,60 @@ def test_fastdiv_helper_is_exact(lib):
             assert lib.csgn_debug_fastdiv(n, d) == n // d, (n, d)
 
 
+def test_plane_entry_points_reject_in_order(lib):
+    """csgn_uint_plain and csgn_uint_addk over the sweep of tests/test_uint_plain_cpu.py: the status is that of the
+    first check that fails -- n_bits, the comparison, width and constant, host pointers, the term counts (INVALID),
+    2^31 words per element and 2^60 per batch (UNSUPPORTED) -- and only then is the device asked for (NO_DEVICE on a
+    box without one; with one, the calls that pass every check are not made: their pointers are not device memory)."""
+    import torch
+    from tests.model import CMPS, plain_terms, u64s
+    from tests.model_addk import addk_terms
+    from tests.test_uint_plain_cpu import sweep_constants, sweep_term_vectors
+    buf = np.zeros(8, dtype=np.uint64)
+    planes = (C.c_void_p * 65)(*([buf.ctypes.data] * 65))
+    gpu = torch.cuda.is_available()
+    rng = np.random.default_rng(19)
+
+    def status(n, batch, counts):
+        """counts: each output's terms per element from the model; None or a 0: an argument is refused"""
+        dl = (n + 63) // 64
+        if n == 0:
+            return -1
+        if dl * 8 > 16384:
+            return -2
+        if not counts or not all(counts):
+            return -1
+        if any(c * dl >= 1 << 31 or batch * c * dl >= 1 << 60 for c in counts):
+            return -2
+        return -3
+
+    for n, batch in ((1247, 4), (0, 4), (64, 1 << 56), (64, 0), (131073, 4), (1247, 1 << 40)):
+        for w in (0, 1, 3, 8, 27, 33, 64, 65):
+            for ts in sweep_term_vectors(w, rng):
+                for k in sweep_constants(w, rng):
+                    fits = 1 <= w <= 64 and k >> w == 0 and all(0 < t < (1 << 62) for t in ts[:w])
+                    for cmp in list(CMPS.values()) + [0, 7]:
+                        counts = [plain_terms(cmp, w, k, ts[:w])] if fits and cmp in CMPS.values() else None
+                        want = status(n, batch, counts)
+                        if want != -3 or not gpu:
+                            got = lib.csgn_uint_plain(n, cmp, batch, w, k, planes, u64s(ts), buf.ctypes.data, None)
+                            assert got == want, (n, batch, cmp, w, k, ts[:w], lib.csgn_last_error())
+                    if fits and k and ts[(k & -k).bit_length() - 1] == (1 << 62) - 1:
+                        continue                                     # see test_addk_terms_sweep
+                    counts = addk_terms(w, k, ts[:w]) if fits else None
+                    for negate, carry in ((0, None), (1, None), (0, buf.ctypes.data), (1, buf.ctypes.data)):
+                        sized = counts and [c + negate for c in counts[:w]] + ([counts[w]] if carry else [])
+                        want = status(n, batch, sized)
+                        if want != -3 or not gpu:
+                            got = lib.csgn_uint_addk(n, batch, w, k, negate, planes, u64s(ts), planes, carry, None)
+                            assert got == want, (n, batch, w, k, negate, carry, ts[:w], lib.csgn_last_error())
+    # host pointers are asked for after width and constant and before the term counts
+    one = u64s([1] * 65)
+    assert lib.csgn_uint_plain(1247, 1, 4, 3, 1, None, one, buf.ctypes.data, None) == -1
+    assert lib.csgn_uint_plain(1247, 1, 4, 3, 1, planes, None, buf.ctypes.data, None) == -1
+    assert lib.csgn_uint_addk(1247, 4, 3, 1, 0, planes, one, None, None, None) == -1
+
+
 def test_fails_loudly_without_gpu(lib):
     """No CPU fallback: on a box with no HIP device csgn_init and compute calls report
     CSGN_ERR_NO_DEVICE / HIP errors.  (On a GPU box this test just checks init succeeds.)"""

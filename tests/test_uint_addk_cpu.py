@@ -96,6 +96,22 @@ def test_addk_terms_invalid(lib):
     assert c_terms(lib, 63, (1 << 63) - 1, one) is None and c_terms(lib, 62, (1 << 62) - 1, one) is not None
 
 
+def test_addk_terms_sweep(lib):
+    """csgn_uint_addk_terms over the sweep of tests/test_uint_plain_cpu.py: the model's counts, and a refusal for
+    whatever include/csgn_hip.h calls invalid."""
+    from tests.test_uint_plain_cpu import SWEEP_WIDTHS, sweep_constants, sweep_term_vectors
+    rng = np.random.default_rng(18)
+    for w in SWEEP_WIDTHS:
+        for ts in sweep_term_vectors(w, rng):
+            for k in sweep_constants(w, rng):
+                valid = 1 <= w <= 64 and k >> w == 0 and all(0 < t < (1 << 62) for t in ts[:w])
+                if valid and k and ts[(k & -k).bit_length() - 1] == (1 << 62) - 1:
+                    continue        # out_m = t_m + 1 = 2^62 terms: refused by the model, let through by the library,
+                                    # whose limit is on the carries and the planes above m; not pinned either way
+                want = addk_terms(w, k, ts[:w]) if valid else None
+                assert c_terms(lib, min(w, 65), k, ts) == want, (w, k, ts[:w])
+
+
 def test_addk_dispatch_names(lib, knobs):
     knobs.unset("uint_addk_fused")
 

@@ -63,6 +63,44 @@ def test_plain_terms_invalid(lib):
     assert lib.csgn_uint_plain_terms(EQ, 1, 1, u64s([(1 << 64) - 1])) == 0
 
 
+def sweep_term_vectors(w, rng):
+    """Term vectors of 65 counts (the first w are read): small ones, a plane of no terms, counts at 2^62 and next to it,
+    and counts whose products cross 2^62 part of the way up the chain."""
+    j = int(rng.integers(0, max(w, 1)))
+    out = [[1] * 65, [2] * 65, [int(x) for x in rng.integers(1, 4, 65)], [1 << 31] * 65, [(1 << 64) - 1] * 65]
+    for special in (0, (1 << 62) - 1, 1 << 62, (1 << 62) + 1, 1 << 40):
+        ts = [int(x) for x in rng.integers(1, 3, 65)]
+        ts[j] = special
+        out.append(ts)
+    return out
+
+
+def sweep_constants(w, rng):
+    """Constants of the sweep, all below 2^64: the ends, mixed bits, and, below 64 bits, some that do not fit."""
+    top = (1 << min(max(w, 1), 64)) - 1
+    ks = {0, 1, top, top - 1, top >> 1, 0x5555555555555555 & top, 0xAAAAAAAAAAAAAAAA & top,
+          int(rng.integers(0, 1 << 62)) & top}
+    if w < 64:
+        ks.update({top + 1, (top + 1) | 1, 1 << 63})
+    return sorted(ks)
+
+
+SWEEP_WIDTHS = (0, 1, 2, 3, 5, 8, 16, 31, 32, 33, 62, 63, 64, 65)
+
+
+def test_plain_terms_sweep(lib):
+    """csgn_uint_plain_terms over widths 0..65, constants that fit and do not, and term vectors with a 0, counts at
+    2^62 and overflowing products: the model's count, and 0 for whatever include/csgn_hip.h calls invalid."""
+    rng = np.random.default_rng(17)
+    for w in SWEEP_WIDTHS:
+        for ts in sweep_term_vectors(w, rng):
+            for k in sweep_constants(w, rng):
+                valid = 1 <= w <= 64 and k >> w == 0 and all(0 < t < (1 << 62) for t in ts[:w])
+                for cmp in CMPS.values():
+                    want = plain_terms(cmp, w, k, ts[:w]) if valid else 0
+                    assert lib.csgn_uint_plain_terms(cmp, w, k, u64s(ts)) == want, (cmp, w, k, ts[:w])
+
+
 def test_plain_dispatch_names(lib, knobs):
     knobs.unset("uint_plain_fused")
 
