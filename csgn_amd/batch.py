@@ -361,6 +361,38 @@ class HipPath:
         check(self.lib.csgn_uint_read(n_bits, batch, v, h_x, h_s, rows, w, h_d, h_t, h_out, self.stream))
         return [o[: batch * int(t) * E * dl] for o, t in zip(outs, table_terms)]
 
+    def uint_find(self, n_bits: int, batch: int, query, query_terms, rows: int, keys, key_terms, values, value_terms,
+                  outs=None, member=False):
+        """csgn_uint_find: the encrypted table of `rows` rows -- key planes `keys` (plane k uniform with key_terms[k]
+        terms) and value planes `values` (plane j uniform with value_terms[j] terms) -- looked up by the encrypted
+        `query` (plane k a uniform batch of query_terms[k] terms).  Returns (output tensors, member tensor or None): one
+        tensor per value plane, rows * P * value_terms[j] terms per element (P = csgn_uint_find_terms), fresh ones
+        unless `outs` is given; `member`: True for a fresh tensor of rows * P terms per element, or the tensor to
+        write."""
+        v, w = len(query), len(values)
+        assert v == len(query_terms) == len(keys) == len(key_terms) and w == len(value_terms)
+        h_u = (C.c_uint64 * max(v, 1))(*[int(t) for t in key_terms])
+        h_s = (C.c_uint64 * max(v, 1))(*[int(t) for t in query_terms])
+        h_t = (C.c_uint64 * max(w, 1))(*[int(t) for t in value_terms])
+        P = int(self.lib.csgn_uint_find_terms(v, h_u, h_s))
+        assert P, "bad key width or term count"
+        dl = self.default_len(n_bits)
+        E = rows * P
+        if outs is None:
+            outs = [self.empty_words(max(batch * int(t) * E * dl, 1)) for t in value_terms]
+        if member is True:
+            member = self.empty_words(max(batch * E * dl, 1))
+        elif member is False:
+            member = None
+        h_x = (C.c_void_p * max(v, 1))(*[_ptr(p) for p in query])
+        h_y = (C.c_void_p * max(v, 1))(*[_ptr(p) for p in keys])
+        h_d = (C.c_void_p * max(w, 1))(*[_ptr(p) for p in values])
+        h_out = (C.c_void_p * max(w, 1))(*[_ptr(o) for o in outs])
+        check(self.lib.csgn_uint_find(n_bits, batch, v, h_x, h_s, rows, h_y, h_u, w, h_d, h_t, h_out, _ptr(member),
+                                      self.stream))
+        return ([o[: batch * int(t) * E * dl] for o, t in zip(outs, value_terms)],
+                None if member is None else member[: batch * E * dl])
+
     def add_ragged(self, n_bits: int, left: torch.Tensor, off_left: torch.Tensor,
                    right: torch.Tensor, off_right: torch.Tensor,
                    total_terms_out: Optional[int] = None, max_t1: int = 0, max_t2: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:

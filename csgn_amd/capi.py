@@ -152,6 +152,11 @@ SIGNATURES = {
     "csgn_uint_read_kernel": (C.c_char_p, [u64, u64, u64, C.POINTER(u64), u64, u64, C.POINTER(u64)]),
     "csgn_uint_read": (C.c_int, [u64, u64, u64, C.POINTER(vp), C.POINTER(u64), u64, u64, C.POINTER(vp), C.POINTER(u64),
                                  C.POINTER(vp), vp]),
+    "csgn_uint_find_terms": (u64, [u64, C.POINTER(u64), C.POINTER(u64)]),
+    "csgn_uint_find_kernel": (C.c_char_p, [u64, u64, u64, C.POINTER(u64), C.POINTER(u64), u64, u64, C.POINTER(u64),
+                                           C.c_int]),
+    "csgn_uint_find": (C.c_int, [u64, u64, u64, C.POINTER(vp), C.POINTER(u64), u64, C.POINTER(vp), C.POINTER(u64), u64,
+                                 C.POINTER(vp), C.POINTER(u64), C.POINTER(vp), vp, vp]),
     "csgn_set_tuning": (C.c_int, [C.c_char_p, C.c_int]),
     "csgn_get_tuning": (C.c_int, [C.c_char_p, C.POINTER(C.c_int)]),
     "csgn_reset_tuning": (None, []),

@@ -910,4 +910,102 @@ CiphertextBatch readAt(const CiphertextBatch &table, const UIntBatch &index)
     return readPlanes(std::vector<CiphertextBatch>(1, table), index)[0];
 }
 
+// ------------------------------------------------------------------ encrypted tables by encrypted key
+
+namespace {
+
+// every value plane looked up by the query: out_j = sum over r of equalTo(key row r, query) * row r of plane j, and,
+// with want_member, the sum of the equalities as the last plane of the result
+std::vector<CiphertextBatch> findPlanes(const UIntBatch &keys, const std::vector<CiphertextBatch> &values,
+                                        const UIntBatch &query, bool want_member)
+{
+    const Context &ctx = query.context();
+    const uint64_t v = keys.width(), rows = keys.size(), m = query.size();
+    if (!sameContext(keys.context(), ctx))
+        throw std::invalid_argument("certFHE::readWhere: the keys and the query differ in context");
+    if (query.width() != v)
+        throw std::invalid_argument("certFHE::readWhere: the keys and the query differ in width");
+    if (v > 16)
+        throw std::invalid_argument("certFHE::readWhere: the keys are wider than 16 bits");
+    for (size_t j = 0; j < values.size(); ++j)
+        if (!sameContext(values[j].context(), ctx) || values[j].size() != rows)
+            throw std::invalid_argument("certFHE::readWhere: the values differ from the keys in context or in rows");
+    if (rows == 0)
+        throw std::invalid_argument("certFHE::readWhere: the table has no rows");
+    const Planes y(keys), x(query), d(values);
+    const std::vector<uint64_t> &t = d.terms;
+    const uint64_t P = csgn_uint_find_terms(v, y.terms.data(), x.terms.data());
+    const char *too_large = "certFHE::readWhere: an output plane exceeds 2^31 words per element (the keys are too wide, "
+                            "have too many terms, or the table too many rows)";
+    if (P == 0 || rows > kMaxWords / P)
+        throw std::invalid_argument(too_large);
+    std::vector<uint64_t> T(values.size() + (want_member ? 1 : 0));
+    for (size_t j = 0; j < T.size(); ++j) {
+        const uint64_t tj = j < values.size() ? t[j] : 1;
+        if (tj == 0 || tj > kMaxWords / (rows * P))
+            throw std::invalid_argument(too_large);
+        T[j] = checked(tj * rows * P, ctx, "readWhere");
+    }
+    if ((y.uniform && x.uniform && d.uniform) || m == 0) {
+        std::vector<CiphertextBatch> out = makePlanes(ctx, m, T);
+        if (m) {
+            std::vector<uint64_t *> dst = wordsOf(out);
+            uint64_t *member = want_member ? dst.back() : nullptr;
+            detail::check(csgn_uint_find(ctx.getN(), m, v, sources(x).data(), x.terms.data(), rows, sources(y).data(),
+                                         y.terms.data(), values.size(), sources(d).data(), t.data(), dst.data(), member,
+                                         detail::stream()),
+                          "csgn_uint_find");
+        }
+        return out;
+    }
+    std::vector<CiphertextBatch> out;
+    // ragged: the definition itself through the batch operators
+    for (uint64_t r = 0; r < rows; ++r) {
+        const CiphertextBatch eq = equalTo(keys.slice(r, r + 1).broadcast(m), query);
+        for (size_t j = 0; j < T.size(); ++j) {
+            const CiphertextBatch p = j < values.size() ? eq * values[j].slice(r, r + 1).broadcast(m) : eq;
+            if (r == 0)
+                out.push_back(p);
+            else
+                out[j] = out[j] + p;
+        }
+    }
+    return out;
+}
+
+std::vector<CiphertextBatch> planesOf(const UIntBatch &a)
+{
+    std::vector<CiphertextBatch> planes;
+    for (unsigned j = 0; j < a.width(); ++j)
+        planes.push_back(a.plane(j));
+    return planes;
+}
+
+} // namespace
+
+UIntBatch readWhere(const UIntBatch &keys, const UIntBatch &values, const UIntBatch &query)
+{
+    return UIntBatch::fromPlanes(findPlanes(keys, planesOf(values), query, false));
+}
+
+CiphertextBatch readWhere(const UIntBatch &keys, const CiphertextBatch &values, const UIntBatch &query)
+{
+    return findPlanes(keys, std::vector<CiphertextBatch>(1, values), query, false)[0];
+}
+
+UIntBatch readWhere(const UIntBatch &keys, const UIntBatch &values, const UIntBatch &query, CiphertextBatch *member)
+{
+    std::vector<CiphertextBatch> out = findPlanes(keys, planesOf(values), query, member != nullptr);
+    if (member) {
+        *member = out.back();
+        out.pop_back();
+    }
+    return UIntBatch::fromPlanes(out);
+}
+
+CiphertextBatch matches(const UIntBatch &keys, const UIntBatch &query)
+{
+    return findPlanes(keys, std::vector<CiphertextBatch>(), query, true)[0];
+}
+
 } // namespace certFHE

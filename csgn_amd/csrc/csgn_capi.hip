@@ -1425,6 +1425,65 @@ int csgn_uint_read(uint64_t n_bits, uint64_t batch, uint64_t index_width, const 
     return CSGN_OK;
 }
 
+/* ------------------------------------------------ encrypted tables by encrypted key ---- */
+
+uint64_t csgn_uint_find_terms(uint64_t key_width, const uint64_t *h_key_terms, const uint64_t *h_query_terms)
+{
+    return csgn::uint_find_terms(key_width, (const u64 *)h_key_terms, (const u64 *)h_query_terms);
+}
+
+const char *csgn_uint_find_kernel(uint64_t n_bits, uint64_t batch, uint64_t key_width, const uint64_t *h_key_terms,
+                                  const uint64_t *h_query_terms, uint64_t rows, uint64_t width,
+                                  const uint64_t *h_value_terms, int with_member)
+{
+    return csgn::uint_find_kernel_name(n_bits, batch, key_width, (const u64 *)h_key_terms, (const u64 *)h_query_terms,
+                                       rows, width, (const u64 *)h_value_terms, with_member != 0);
+}
+
+int csgn_uint_find(uint64_t n_bits, uint64_t batch, uint64_t key_width, const uint64_t *const *h_query,
+                   const uint64_t *h_query_terms, uint64_t rows, const uint64_t *const *h_keys,
+                   const uint64_t *h_key_terms, uint64_t width, const uint64_t *const *h_values,
+                   const uint64_t *h_value_terms, uint64_t *const *h_out, uint64_t *d_member, void *stream)
+{
+    if (int rc = check_n(n_bits))
+        return rc;
+    REQUIRE(key_width >= 1 && key_width <= csgn::kFindMaxKey, "find: key width %llu outside 1..16",
+            (unsigned long long)key_width);
+    REQUIRE(width <= csgn::kFindMaxPlanes, "find: value width %llu outside 0..64", (unsigned long long)width);
+    REQUIRE(width >= 1 || d_member, "find: no value planes and no member output");
+    REQUIRE(rows >= 1, "find: a table of no rows");
+    REQUIRE(h_query && h_query_terms && h_keys && h_key_terms, "null host pointer");
+    REQUIRE(width == 0 || (h_values && h_value_terms && h_out), "null host pointer");
+    const uint64_t P = csgn::uint_find_terms(key_width, (const u64 *)h_key_terms, (const u64 *)h_query_terms);
+    REQUIRE(P != 0, "find: a key or query plane has no terms, or the term count overflows");
+    for (uint64_t j = 0; j < width; ++j)
+        REQUIRE(h_value_terms[j] != 0, "find: value plane %llu has no terms", (unsigned long long)j);
+    const uint64_t dl = csgn_default_len(n_bits);
+    unsigned long long E;                                    // rows * P; a product that wraps is past every limit
+    if (__builtin_mul_overflow((unsigned long long)rows, (unsigned long long)P, &E))
+        E = ~0ull;
+    for (uint64_t j = 0; j < width + (d_member ? 1 : 0); ++j) {
+        unsigned long long terms;                            // of output j; the last is member's
+        if (__builtin_mul_overflow(E, (unsigned long long)(j < width ? h_value_terms[j] : 1), &terms))
+            terms = ~0ull;
+        if (int rc = check_size(batch, terms, terms, dl, j < width ? "find: output %llu" : "find: member",
+                                (unsigned long long)j))
+            return rc;
+    }
+    if (int rc = require_device("csgn_uint_find"))
+        return rc;
+    if (batch == 0)
+        return CSGN_OK;
+    if (int rc = check_planes(h_query, h_keys, key_width, "query or key plane"))
+        return rc;
+    if (int rc = check_planes(h_values, h_out, width, "value plane or output"))
+        return rc;
+    HIP_TRY(csgn::uint_find(n_bits, batch, key_width, (const u64 *const *)h_query, (const u64 *)h_query_terms, rows,
+                            (const u64 *const *)h_keys, (const u64 *)h_key_terms, width, (const u64 *const *)h_values,
+                            (const u64 *)h_value_terms, (u64 *const *)h_out, (u64 *)d_member, S(stream)));
+    return CSGN_OK;
+}
+
 /* ------------------------------------------------------------------ tuning ---- */
 
 int csgn_set_tuning(const char *key, int value)

@@ -196,12 +196,23 @@ const char *uint_read_kernel_name(u64 n_bits, u64 batch, u64 v, const u64 *s, u6
 hipError_t uint_read(u64 n_bits, u64 batch, u64 v, const u64 *const *index, const u64 *s, u64 rows, u64 w,
                      const u64 *const *table, const u64 *t, u64 *const *out, hipStream_t stream);
 
+// an encrypted table looked up by encrypted key (csgn_uint_find.hip), include/csgn_hip.h's definition: output j is the
+// sum, ascending in r < rows, of EQ(y_r, x) * d_{r,j}, member that of EQ(y_r, x).  key and query planes: v = 1..16,
+// terms u[k] / s[k]; value planes: w = 0..64, terms t[j]; member: nullptr = not computed (then w >= 1).
+constexpr u32 kFindMaxKey = 16, kFindMaxPlanes = 64;
+u64 uint_find_terms(u64 v, const u64 *u, const u64 *s);   // P; 0: invalid argument or a count of 2^62 or more
+const char *uint_find_kernel_name(u64 n_bits, u64 batch, u64 v, const u64 *u, const u64 *s, u64 rows, u64 w,
+                                  const u64 *t, bool member);
+hipError_t uint_find(u64 n_bits, u64 batch, u64 v, const u64 *const *query, const u64 *s, u64 rows,
+                     const u64 *const *keys, const u64 *u, u64 w, const u64 *const *values, const u64 *t,
+                     u64 *const *out, u64 *member, hipStream_t stream);
+
 // The temporaries of the composed forms and of the gather plan (csgn_scratch.cpp): a plain (hipMalloc) block the calling
 // thread keeps per stream and per user, never the stream-ordered pool.  Returns the block, or nullptr with e set
 // (hipErrorStreamCaptureUnsupported when the call would have to allocate while s is capturing).  owned: the block is
 // past the kept size and belongs to this call; scratch_done frees it behind the call's launches (waits for the device)
 // and passes e through.
-enum ScratchSlot { SCRATCH_UINT_PLAIN, SCRATCH_UINT_LUT, SCRATCH_UINT_READ, SCRATCH_UINT_ADDK, SCRATCH_GATHER, SCRATCH_SLOTS };
+enum ScratchSlot { SCRATCH_UINT_PLAIN, SCRATCH_UINT_LUT, SCRATCH_UINT_READ, SCRATCH_UINT_ADDK, SCRATCH_UINT_FIND, SCRATCH_GATHER, SCRATCH_SLOTS };
 u64 *scratch_take(ScratchSlot slot, size_t bytes, hipStream_t s, bool &owned, hipError_t &e);
 hipError_t scratch_done(u64 *block, bool owned, hipError_t e);
 

@@ -54,6 +54,8 @@ enum TuneKey {
     TUNE_UINT_LUT_FUSED, // public lookup tables (csgn_uint_lut.hip): -1 = per shape, 0 = composed form (the tuned launchers monomial by monomial), 1 = fused kernel
     TUNE_UINT_READ_FUSED, // encrypted tables read at encrypted indices (csgn_uint_read.hip): -1 = per shape, 0 = composed form (the tuned launchers row by row), 1 = fused kernel
     TUNE_UINT_ADDK_FUSED, // integer + public constant (csgn_uint_addk.hip): -1 = per shape, 0 = composed form (the tuned launchers plane by plane), 1 = fused kernel
+    TUNE_UINT_FIND_FORM, // encrypted tables looked up by encrypted key (csgn_uint_find.hip): -1 = per shape, 0 = composed form (the tuned launchers row by row), 1 = fused kernel
+    TUNE_UINT_FIND_RPARTS, // ... row parts of one k_uint_find launch at most, 0 = what a launch's workgroups allow (every shape within memory: one launch); a test sets it low to run the host's split of the rows into several launches
     TUNE_COUNT
 };
 

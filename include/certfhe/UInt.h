@@ -51,6 +51,22 @@
 // the same words.  Every size is checked before anything is allocated: std::invalid_argument for a mismatched context,
 // a table of 0 or more than 2^v rows, or an output plane past 2^31 words per element.
 //
+// ENCRYPTED TABLES BY ENCRYPTED KEY: readWhere(keys, values, query) looks a table of n = keys.size() rows up by every
+// element's encrypted query, the keys encrypted too (v = keys.width() = query.width() <= 16; values.size() = n >= 1,
+// with no bound on n but the sizes): a private key-value lookup, a join, an associative memory.  Output plane j is the
+// left-nested sum, ascending in r < n, of equalTo(key row r broadcast, query) * (plane j of value row r, broadcast) --
+// the key as a, the query as b, the equality the LEFT operand -- and matches(keys, query), or the `member` argument,
+// the sum of the equalities alone: csgn_uint_find's words (include/csgn_hip.h).  Element e decrypts to the XOR of
+// values[r] over the rows with keys[r] == query[e]: with distinct keys the matching value, or 0 when no key matches.
+// Rows with EQUAL KEYS XOR their values, and member is the PARITY of the number of matching rows -- membership only
+// when the keys are distinct.  Plane j of the result has n * P * t_j terms, P = prod_k (u_k + s_k + 1) for key planes of
+// u_k and query planes of s_k terms: n * 3^v with fresh planes (6561 n at v = 8), the same growth as an equality per row.
+// Uniform planes take one csgn_uint_find (one launch for every output plane and member); ragged planes (a compact()
+// result on any operand) are composed from slice, broadcast, equalTo(a, b), * and + with the same words.  Every size is
+// checked before anything is allocated: std::invalid_argument for mismatched contexts, keys.width() != query.width(), a
+// width past 16, keys.size() != values.size(), no rows, or an output past 2^31 words per element.  An empty query batch
+// gives empty planes.
+//
 // ARITHMETIC WITH A PUBLIC CONSTANT (k < 2^width, the same for every element; std::invalid_argument otherwise) spends no
 // term on k: with m the lowest set bit of k the carry into plane j > m is the chain c_m = a_m, then k_j ? (c * n_j) + a_j
 // : c * a_j (n_j = logicNot(a_j), c the LEFT operand), and the words are csgn_uint_addk's (include/csgn_hip.h):
@@ -192,6 +208,14 @@ UIntBatch lookup(const UIntBatch &a, const UIntBatch &b, const LookupTable &f);
 // element e: table[index[e]] where index[e] < table.size(), else 0; one output plane per table plane
 UIntBatch readAt(const UIntBatch &table, const UIntBatch &index);
 CiphertextBatch readAt(const CiphertextBatch &table, const UIntBatch &index);
+
+// element e: XOR over rows r with keys[r] == query[e] of values[r]  (distinct keys: the matching value, else 0)
+UIntBatch readWhere(const UIntBatch &keys, const UIntBatch &values, const UIntBatch &query);
+CiphertextBatch readWhere(const UIntBatch &keys, const CiphertextBatch &values, const UIntBatch &query);
+// the same, and *member = matches(keys, query) from the same launch (member may be null)
+UIntBatch readWhere(const UIntBatch &keys, const UIntBatch &values, const UIntBatch &query, CiphertextBatch *member);
+// element e: parity of the number of rows with keys[r] == query[e]  (distinct keys: membership)
+CiphertextBatch matches(const UIntBatch &keys, const UIntBatch &query);
 
 } // namespace certFHE
 

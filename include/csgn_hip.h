@@ -829,6 +829,55 @@ int csgn_uint_read(uint64_t n_bits, uint64_t batch, uint64_t index_width, const 
                    const uint64_t *h_index_terms, uint64_t rows, uint64_t width, const uint64_t *const *h_table,
                    const uint64_t *h_table_terms, uint64_t *const *h_out, void *stream);
 
+/* ------------------------------------------------ encrypted tables by encrypted key ---- */
+
+/* An ENCRYPTED table looked up by an ENCRYPTED key: a private key-value lookup, a join, an associative memory.
+ * Keys: key_width = v planes y_0..y_{v-1} (v in 1..16) of `rows` elements, plane k uniform with u_k terms per element.
+ * Query: v planes x_0..x_{v-1} of `batch` elements, plane k uniform with s_k terms.  Values: `width` planes
+ * d_0..d_{width-1} (0..64) of `rows` elements, plane j uniform with t_j terms.  rows >= 1, with no upper bound other
+ * than the size limits below.  Output: `width` planes of `batch` elements and, optionally, the bit `member`.  A fixed
+ * composition of the reference's operator+ / operator* with ONE; y_{r,k} and d_{r,j} are row r broadcast to every
+ * query element:
+ *     EQ(y_r, x)  equalTo(key row r, query) of certfhe/UInt.h, the key as a, the query as b:
+ *                 g_k = (y_{r,k} + x_k) + ONE (logicXnor);  EQ = ((g_0 * g_1) * ...) * g_{v-1}  (the EQ_STEP chain:
+ *                 the running value is the LEFT operand)
+ *     out_j  = ((EQ(y_0, x) * d_{0,j}) + (EQ(y_1, x) * d_{1,j})) + ... + (EQ(y_{rows-1}, x) * d_{rows-1,j})   (left-nested)
+ *     member =  (EQ(y_0, x) + EQ(y_1, x)) + ... + EQ(y_{rows-1}, x)
+ * out_j decrypts to the XOR, over the rows whose key equals the query, of bit j of the row's value: with distinct keys
+ * the matching row's value, or 0 when no key matches.  member decrypts to the parity of the number of matching rows:
+ * with distinct keys, membership.
+ * Terms: every row has the same P = prod_k (u_k + s_k + 1) EQ terms;  T_j = rows * P * t_j,  T_member = rows * P.
+ * Fresh 1-term planes: P = 3^v -- the scheme's own growth, as for csgn_uint_step's comparisons.
+ * Term order (decoding needs no table): row r's terms form a block of P * t_j terms, blocks ascending in r; inside a
+ * block term (q, c) is at q * t_j + c, c the value term (fastest), and q's mixed-radix digits d_k < u_k + s_k + 1 run
+ * with k = 0 slowest; d_k < u_k selects term d_k of y_{r,k}, u_k <= d_k < u_k + s_k term d_k - u_k of x_k, and
+ * d_k = u_k + s_k selects ONE.  member is the same stream without the value factor. */
+/* P (host only); 0 for key_width outside 1..16, a null pointer, a plane of 0 terms or a count of 2^62 or more. */
+uint64_t csgn_uint_find_terms(uint64_t key_width, const uint64_t *h_key_terms, const uint64_t *h_query_terms);
+/* Which form a csgn_uint_find call of this shape takes (host only, a static string): "k_uint_find" (one kernel writes
+ * every output plane and member, planes read in place, ONE made in registers) or "composed" (per row r: the broadcast
+ * of row r of the key and value planes by csgn_gather_planes' tile form, the XNOR gate and the EQ_STEPs of
+ * csgn_gate_uniform / csgn_uint_step into a temporary the calling thread keeps (csgn_uint_addk's rules for its composed
+ * form), csgn_mul_uniform into r's slice of every output and a pitched copy into r's slice of member).  Knob
+ * "uint_find_form" (-1 per shape, 0 composed, 1 fused) decides; the words are the same.  Per shape: fused (DESIGN
+ * 4.19: no measured shape has the composed form ahead).  "" for an invalid shape (n_bits 0, a bad width, no rows, a bad
+ * term count, or width 0 without member). */
+const char *csgn_uint_find_kernel(uint64_t n_bits, uint64_t batch, uint64_t key_width, const uint64_t *h_key_terms,
+                                  const uint64_t *h_query_terms, uint64_t rows, uint64_t width,
+                                  const uint64_t *h_value_terms, int with_member);
+/* The lookup over `batch` query elements.  h_query: a HOST array of key_width device pointers (plane k: batch * s_k *
+ * dL words), h_keys: a HOST array of key_width device pointers (plane k: rows * u_k * dL words), h_values: a HOST array
+ * of `width` device pointers (plane j: rows * t_j * dL words), h_out: a HOST array of `width` device pointers (output
+ * j: batch * T_j * dL words), d_member: batch * T_member * dL words, or NULL: it is then not computed.  width == 0 is
+ * allowed only with d_member (h_values, h_value_terms and h_out are then not read); otherwise CSGN_ERR_INVALID.
+ * Inputs may alias one another; no output overlaps an input or another output.  Limits: every T_j * dL and
+ * T_member * dL below 2^31 words per element (CSGN_ERR_UNSUPPORTED), batch * that < 2^60.  On the caller's stream,
+ * asynchronous; the fused form is one launch and graph-capturable.  No GPU: CSGN_ERR_NO_DEVICE, no CPU fallback. */
+int csgn_uint_find(uint64_t n_bits, uint64_t batch, uint64_t key_width, const uint64_t *const *h_query,
+                   const uint64_t *h_query_terms, uint64_t rows, const uint64_t *const *h_keys,
+                   const uint64_t *h_key_terms, uint64_t width, const uint64_t *const *h_values,
+                   const uint64_t *h_value_terms, uint64_t *const *h_out, uint64_t *d_member, void *stream);
+
 /* ------------------------------------------------------------------- tuning ---- */
 
 /* Kernel-choice and sweep knobs ("mul_flat", "mul_touch", "ragged_c", "perm_ballot", ...;
