@@ -393,6 +393,23 @@ class HipPath:
         return ([o[: batch * int(t) * E * dl] for o, t in zip(outs, value_terms)],
                 None if member is None else member[: batch * E * dl])
 
+    def matmul(self, n_bits: int, rows: int, inner: int, cols: int, a: torch.Tensor, t_a: int, b: torch.Tensor, t_b: int,
+               transposed: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """csgn_matmul: the product over F2 of the encrypted bit matrices `a` (rows x inner, element i*inner + e, t_a
+        terms each) and `b` (inner x cols, element e*cols + k, or with `transposed` cols x inner, element k*inner + e;
+        t_b terms each).  Returns rows x cols elements of inner * t_a * t_b terms (a fresh tensor unless `out` is
+        given)."""
+        dl = self.default_len(n_bits)
+        terms = int(self.lib.csgn_matmul_terms(inner, t_a, t_b))
+        assert terms, "bad shape or term count"
+        assert a.numel() >= rows * inner * t_a * dl and b.numel() >= inner * cols * t_b * dl
+        if out is None:
+            out = self.empty_words(rows * cols * terms * dl)
+        assert out.numel() >= rows * cols * terms * dl
+        check(self.lib.csgn_matmul(n_bits, rows, inner, cols, _ptr(a), t_a, _ptr(b), t_b, 1 if transposed else 0,
+                                   _ptr(out), self.stream))
+        return out[: rows * cols * terms * dl]
+
     def add_ragged(self, n_bits: int, left: torch.Tensor, off_left: torch.Tensor,
                    right: torch.Tensor, off_right: torch.Tensor,
                    total_terms_out: Optional[int] = None, max_t1: int = 0, max_t2: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:

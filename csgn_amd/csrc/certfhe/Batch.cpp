@@ -474,6 +474,98 @@ Ciphertext CiphertextBatch::at(uint64_t i) const
     return c;
 }
 
+// ------------------------------------------------------------------ sums over elements, matrix products (csgn_matmul)
+
+CiphertextBatch CiphertextBatch::sumGroups(uint64_t group) const
+{
+    if (group == 0 || count_ % group != 0)
+        throw std::invalid_argument("certFHE::CiphertextBatch::sumGroups: groups of " + std::to_string(group) +
+                                    " in a batch of " + std::to_string(count_));
+    CiphertextBatch out(ctx, 0, 0);
+    out.payload = payload;                                         // a sum is a concatenation: the same words
+    out.count_ = count_ / group;
+    if (uniform()) {
+        out.terms_ = terms_ * group;
+        return out;
+    }
+    out.offsets_.resize(out.count_ + 1);
+    for (uint64_t q = 0; q <= out.count_; ++q)
+        out.offsets_[q] = offsets_[q * group];
+    return out;
+}
+
+namespace {
+CiphertextBatch matMulAny(const CiphertextBatch &a, const CiphertextBatch &b, uint64_t rows, uint64_t inner,
+                          uint64_t cols, bool transposed, const char *who)
+{
+    const std::string name = std::string("certFHE::") + who;
+    const Context &c = a.context();
+    if (c.getN() != b.context().getN() || c.getD() != b.context().getD())
+        throw std::invalid_argument(name + ": operands differ in context");
+    unsigned long long na, nb, nc;
+    if (rows == 0 || inner == 0 || cols == 0 || __builtin_mul_overflow((unsigned long long)rows, (unsigned long long)inner, &na) ||
+        __builtin_mul_overflow((unsigned long long)inner, (unsigned long long)cols, &nb) ||
+        __builtin_mul_overflow((unsigned long long)rows, (unsigned long long)cols, &nc) || a.size() != na || b.size() != nb)
+        throw std::invalid_argument(name + ": " + std::to_string(rows) + " x " + std::to_string(inner) + " times " +
+                                    std::to_string(inner) + " x " + std::to_string(cols) + " from batches of " +
+                                    std::to_string(a.size()) + " and " + std::to_string(b.size()));
+    const uint64_t dl = c.getDefaultN();
+    if (a.uniform() && b.uniform()) {
+        const uint64_t T = csgn_matmul_terms(inner, a.terms(), b.terms());
+        if (a.terms() == 0 || b.terms() == 0)
+            throw std::invalid_argument(name + ": an operand of no terms");
+        if (T == 0 || T > ((1ull << 31) - 1) / dl)
+            throw std::invalid_argument(name + ": an output element past 2^31 words");
+        CiphertextBatch out = detail::BatchAccess::make(c, nc, T);
+        detail::check(csgn_matmul(c.getN(), rows, inner, cols, a.deviceValues(), a.terms(), b.deviceValues(), b.terms(),
+                                  transposed ? 1 : 0, detail::BatchAccess::words(out), detail::stream()),
+                      "csgn_matmul");
+        return out;
+    }
+    // a ragged operand: the definition itself, from gather, operator* and sumGroups.  The size of every output element
+    // first, from the host's term counts.
+    if (na >= (1ull << 32) || nb >= (1ull << 32) || nc >= (1ull << 32) / inner)
+        throw std::invalid_argument(name + ": ragged operands of 2^32 elements or more");
+    for (uint64_t i = 0; i < rows; ++i)
+        for (uint64_t k = 0; k < cols; ++k) {
+            unsigned long long T = 0;
+            for (uint64_t e = 0; e < inner; ++e) {
+                unsigned long long p;
+                if (__builtin_mul_overflow((unsigned long long)a.termsOf(i * inner + e),
+                                           (unsigned long long)b.termsOf(transposed ? k * inner + e : e * cols + k), &p) ||
+                    __builtin_add_overflow(T, p, &T))
+                    T = ~0ull;
+            }
+            if (T > ((1ull << 31) - 1) / dl)
+                throw std::invalid_argument(name + ": an output element past 2^31 words");
+        }
+    std::vector<uint64_t> ia(nc * inner), ib(nc * inner);
+    for (uint64_t i = 0, p = 0; i < rows; ++i)
+        for (uint64_t k = 0; k < cols; ++k)
+            for (uint64_t e = 0; e < inner; ++e, ++p) {
+                ia[p] = i * inner + e;
+                ib[p] = transposed ? k * inner + e : e * cols + k;
+            }
+    return (a.gather(ia) * b.gather(ib)).sumGroups(inner);
+}
+} // namespace
+
+CiphertextBatch matMul(const CiphertextBatch &a, const CiphertextBatch &b, uint64_t rows, uint64_t inner, uint64_t cols)
+{
+    return matMulAny(a, b, rows, inner, cols, false, "matMul");
+}
+
+CiphertextBatch matMulTransposed(const CiphertextBatch &a, const CiphertextBatch &bt, uint64_t rows, uint64_t inner,
+                                 uint64_t cols)
+{
+    return matMulAny(a, bt, rows, inner, cols, true, "matMulTransposed");
+}
+
+CiphertextBatch dot(const CiphertextBatch &a, const CiphertextBatch &b)
+{
+    return matMulAny(a, b, 1, a.size(), 1, true, "dot");
+}
+
 // ------------------------------------------------------------------ BatchCircuit
 
 BatchCircuit::BatchCircuit(const Context &context, uint64_t count)

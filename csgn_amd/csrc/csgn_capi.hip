@@ -1484,6 +1484,44 @@ int csgn_uint_find(uint64_t n_bits, uint64_t batch, uint64_t key_width, const ui
     return CSGN_OK;
 }
 
+/* ------------------------------------------------ encrypted bit matrices over F2 ---- */
+
+uint64_t csgn_matmul_terms(uint64_t inner, uint64_t t_a, uint64_t t_b) { return csgn::matmul_terms(inner, t_a, t_b); }
+
+const char *csgn_matmul_kernel(uint64_t n_bits, uint64_t rows, uint64_t inner, uint64_t cols, uint64_t t_a, uint64_t t_b,
+                               int b_transposed)
+{
+    return csgn::matmul_kernel_name(n_bits, rows, inner, cols, t_a, t_b, b_transposed != 0);
+}
+
+int csgn_matmul(uint64_t n_bits, uint64_t rows, uint64_t inner, uint64_t cols, const uint64_t *d_a, uint64_t t_a,
+                const uint64_t *d_b, uint64_t t_b, int b_transposed, uint64_t *d_out, void *stream)
+{
+    if (int rc = check_n(n_bits))
+        return rc;
+    REQUIRE(rows && inner && cols, "matmul: %llu x %llu x %llu (every dimension at least 1)", (unsigned long long)rows,
+            (unsigned long long)inner, (unsigned long long)cols);
+    REQUIRE(t_a && t_b && t_a < (1ull << 62) && t_b < (1ull << 62), "matmul: %llu and %llu terms (1 .. 2^62 - 1)",
+            (unsigned long long)t_a, (unsigned long long)t_b);
+    const uint64_t dl = csgn_default_len(n_bits);
+    // the terms of one output element; a product that wraps, or reaches 2^62, is past every limit
+    const uint64_t T = csgn::matmul_terms(inner, t_a, t_b);
+    if (T == 0 || !product_below(T, dl, 1, 1ull << 31))
+        return fail(CSGN_ERR_UNSUPPORTED, "matmul: %llu x %llu x %llu terms per element exceed 2^31 words",
+                    (unsigned long long)inner, (unsigned long long)t_a, (unsigned long long)t_b);
+    unsigned long long elems;
+    if (__builtin_mul_overflow((unsigned long long)rows, (unsigned long long)cols, &elems) ||
+        !product_below(elems, T, dl, 1ull << 60))
+        return fail(CSGN_ERR_UNSUPPORTED, "matmul of %llu x %llu elements: size overflows", (unsigned long long)rows,
+                    (unsigned long long)cols);
+    REQUIRE(d_a && d_b && d_out, "null device pointer");
+    if (int rc = require_device("csgn_matmul"))
+        return rc;
+    HIP_TRY(csgn::matmul(n_bits, rows, inner, cols, (const u64 *)d_a, t_a, (const u64 *)d_b, t_b, b_transposed != 0,
+                         (u64 *)d_out, S(stream)));
+    return CSGN_OK;
+}
+
 /* ------------------------------------------------------------------ tuning ---- */
 
 int csgn_set_tuning(const char *key, int value)

@@ -207,12 +207,20 @@ hipError_t uint_find(u64 n_bits, u64 batch, u64 v, const u64 *const *query, cons
                      const u64 *const *keys, const u64 *u, u64 w, const u64 *const *values, const u64 *t,
                      u64 *const *out, u64 *member, hipStream_t stream);
 
+// the product of two encrypted bit matrices over F2 (csgn_matmul.hip), include/csgn_hip.h's definition: C[i,k] is the
+// sum, ascending in e < inner, of A[i,e] * B[e,k].  A: rows * inner elements of ta terms, B: inner * cols elements of
+// tb terms (transposed: element k * inner + e), C: rows * cols elements of inner * ta * tb terms.
+u64 matmul_terms(u64 inner, u64 ta, u64 tb);   // 0: a zero argument or a count of 2^62 or more
+const char *matmul_kernel_name(u64 n_bits, u64 rows, u64 inner, u64 cols, u64 ta, u64 tb, bool transposed);
+hipError_t matmul(u64 n_bits, u64 rows, u64 inner, u64 cols, const u64 *A, u64 ta, const u64 *B, u64 tb,
+                  bool transposed, u64 *C, hipStream_t stream);
+
 // The temporaries of the composed forms and of the gather plan (csgn_scratch.cpp): a plain (hipMalloc) block the calling
 // thread keeps per stream and per user, never the stream-ordered pool.  Returns the block, or nullptr with e set
 // (hipErrorStreamCaptureUnsupported when the call would have to allocate while s is capturing).  owned: the block is
 // past the kept size and belongs to this call; scratch_done frees it behind the call's launches (waits for the device)
 // and passes e through.
-enum ScratchSlot { SCRATCH_UINT_PLAIN, SCRATCH_UINT_LUT, SCRATCH_UINT_READ, SCRATCH_UINT_ADDK, SCRATCH_UINT_FIND, SCRATCH_GATHER, SCRATCH_SLOTS };
+enum ScratchSlot { SCRATCH_UINT_PLAIN, SCRATCH_UINT_LUT, SCRATCH_UINT_READ, SCRATCH_UINT_ADDK, SCRATCH_UINT_FIND, SCRATCH_GATHER, SCRATCH_MATMUL, SCRATCH_SLOTS };
 u64 *scratch_take(ScratchSlot slot, size_t bytes, hipStream_t s, bool &owned, hipError_t &e);
 hipError_t scratch_done(u64 *block, bool owned, hipError_t e);
 

@@ -37,6 +37,8 @@ const Knob kKnobs[TUNE_COUNT] = {
     {"uint_addk_fused", -1},
     {"uint_find_form", -1},
     {"uint_find_rparts", 0},
+    {"matmul_form", -1},
+    {"matmul_epart", 0},
 };
 
 // Knob values are PER HOST THREAD: a thread that sets a knob changes the dispatch of its own later

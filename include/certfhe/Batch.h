@@ -93,6 +93,13 @@ class CiphertextBatch {
     // contexts.  Parts that are all uniform with one term count give a uniform batch, anything else a ragged one.
     static CiphertextBatch concat(const std::vector<CiphertextBatch> &parts);
 
+    // EXTENSION: sums over elements of ONE batch.  Element q of the result is the left-nested sum (operator+: a
+    // concatenation) of elements q*group .. q*group + group - 1.  For a uniform batch the result SHARES the payload:
+    // size()/group elements of group * terms() terms, no launch and no copy (the same words read with another shape).
+    // For a ragged batch it keeps every group-th offset and shares the words.  std::invalid_argument unless
+    // group >= 1 and group divides size().
+    CiphertextBatch sumGroups(uint64_t group) const;
+
     Ciphertext at(uint64_t i) const;          // copy of element i as an ordinary Ciphertext
     uint64_t size() const { return count_; }
     uint64_t terms() const { return terms_; }  // per element; 0 for a ragged batch (see termsOf)
@@ -102,6 +109,27 @@ class CiphertextBatch {
     const Context &context() const { return ctx; }
     const uint64_t *deviceValues() const;
 };
+
+// EXTENSION: products of ENCRYPTED bit matrices over F2 (csgn_matmul of include/csgn_hip.h).
+// Matrices are uniform CiphertextBatches in row-major order.
+//   - A is rows x inner: element i*inner + e, t_a terms each.
+//   - B is inner x cols: element e*cols + k, t_b terms each.
+//   - In the transposed layout Bt is cols x inner: element k*inner + e.
+//   - C is rows x cols: element i*cols + k, inner * t_a * t_b terms.
+//   - C[i,k] is the left-nested sum, ascending in e, of A[i,e] * B[e,k], with the reference's operator* (left term
+//     slow, right term fast) and operator+ (concatenation).
+//   - Term q of C[i,k] decodes as e = q / (t_a*t_b), a = (q / t_b) % t_a, b = q % t_b.  Its words are
+//     A[i,e][a] & B[e,k][b].
+//   - It decrypts to the matrix product over F2.
+// Uniform operands take ONE csgn_matmul; a ragged operand (a compact() result) is composed from gather, operator* and
+// sumGroups, with the same words.  std::invalid_argument for operands of different contexts, a zero dimension,
+// a.size() != rows*inner, b.size() != inner*cols, or an output past 2^31 words per element -- before anything is
+// allocated or launched.
+CiphertextBatch matMul(const CiphertextBatch &a, const CiphertextBatch &b, uint64_t rows, uint64_t inner, uint64_t cols);
+CiphertextBatch matMulTransposed(const CiphertextBatch &a, const CiphertextBatch &bt, uint64_t rows, uint64_t inner,
+                                 uint64_t cols);
+// the inner product of two encrypted bit vectors of one length, one element: matMulTransposed(a, b, 1, a.size(), 1)
+CiphertextBatch dot(const CiphertextBatch &a, const CiphertextBatch &b);
 
 // EXTENSION: a fixed add/multiply/decrypt circuit over uniform batches, captured once into a
 // hipGraph (csgn_circuit_* in include/csgn_hip.h).  For circuits whose operations are too small to

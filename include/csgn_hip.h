@@ -878,6 +878,44 @@ int csgn_uint_find(uint64_t n_bits, uint64_t batch, uint64_t key_width, const ui
                    const uint64_t *h_key_terms, uint64_t width, const uint64_t *const *h_values,
                    const uint64_t *h_value_terms, uint64_t *const *h_out, uint64_t *d_member, void *stream);
 
+/* ------------------------------------------------ encrypted bit matrices over F2 ---- */
+
+/* The product of two ENCRYPTED bit matrices over F2: an inner product of encrypted bit vectors, a secret linear map
+ * applied to a batch of encrypted vectors, the parity of every database row with every query.
+ * Matrices are uniform CiphertextBatches in row-major order.
+ *   - A is rows x inner: element i*inner + e, t_a terms each.
+ *   - B is inner x cols: element e*cols + k, t_b terms each.
+ *   - In the transposed layout Bt is cols x inner: element k*inner + e.
+ *   - C is rows x cols: element i*cols + k, inner * t_a * t_b terms.
+ *   - C[i,k] is the left-nested sum, ascending in e, of A[i,e] * B[e,k], with the reference's operator* (left term
+ *     slow, right term fast) and operator+ (concatenation).
+ *   - Term q of C[i,k] decodes as e = q / (t_a*t_b), a = (q / t_b) % t_a, b = q % t_b.  Its words are
+ *     A[i,e][a] & B[e,k][b].
+ *   - It decrypts to the matrix product over F2.
+ * A sum is a concatenation of term lists, so the product of fresh matrices has `inner` terms per output and adds one
+ * level of depth: the growth is the scheme's own. */
+/* inner * t_a * t_b (host only); 0 for a zero argument or a count of 2^62 or more. */
+uint64_t csgn_matmul_terms(uint64_t inner, uint64_t t_a, uint64_t t_b);
+/* Which form a csgn_matmul call of this shape takes (host only, a static string): "k_matmul" (one kernel writes every
+ * term of every output element: a workgroup stages a tile's operand terms in LDS once and streams its outputs) or
+ * "composed" (both operands tiled to rows * cols * inner elements by csgn_gather's launcher into a temporary the calling
+ * thread keeps, under csgn_uint_addk's rules for its composed form, then one csgn_mul_uniform over those pairs straight
+ * into the output).  Knob "matmul_form" (-1 per shape, 0 composed, 1 fused) decides; the words are the same.  Per shape:
+ * fused.  An operand of 2^32 elements or more is past the gather launcher: such a shape is fused whatever
+ * the knob says.  "" for an invalid shape (n_bits 0, a zero dimension, a zero term count or a count of 2^62 or more). */
+const char *csgn_matmul_kernel(uint64_t n_bits, uint64_t rows, uint64_t inner, uint64_t cols, uint64_t t_a, uint64_t t_b,
+                               int b_transposed);
+/* The product.  d_a: rows * inner * t_a * dL words, d_b: inner * cols * t_b * dL words (b_transposed != 0: the layout
+ * Bt), d_out: rows * cols * inner * t_a * t_b * dL words.  The operands may alias one another; the output overlaps
+ * neither.  Checks, in this order, the first that fails giving the status: n_bits; rows, inner and cols nonzero and
+ * t_a, t_b nonzero and below 2^62 (CSGN_ERR_INVALID); inner * t_a * t_b * dL below 2^31 words per element and the
+ * output below 2^60 words (CSGN_ERR_UNSUPPORTED; computed without wrap-around); null device pointers
+ * (CSGN_ERR_INVALID); the device (CSGN_ERR_NO_DEVICE, no CPU fallback).  Nothing is allocated or launched before every
+ * check has passed.  On the caller's stream, asynchronous; the fused form is one launch for every shape within memory
+ * and graph-capturable. */
+int csgn_matmul(uint64_t n_bits, uint64_t rows, uint64_t inner, uint64_t cols, const uint64_t *d_a, uint64_t t_a,
+                const uint64_t *d_b, uint64_t t_b, int b_transposed, uint64_t *d_out, void *stream);
+
 /* ------------------------------------------------------------------- tuning ---- */
 
 /* Kernel-choice and sweep knobs ("mul_flat", "mul_touch", "ragged_c", "perm_ballot", ...;
