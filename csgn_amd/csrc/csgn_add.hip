@@ -304,7 +304,10 @@ hipError_t add_ragged(u64 n_bits, u64 batch, const u64 *L, const u64 *offL, cons
     const int chunks = ragged_chunks(total_units);
     const int turn = csgn::tune(TUNE_RAGGED_M);
     const u32 xcd_group = (u32)std::max(0, csgn::tune(TUNE_RAGGED_XCD_GROUP));
-    const u64 per_launch = kMaxBlocks256 * 256u;         // units: a multiple of every 256*C
+    // units of one launch.  No multiple of 256 * C (kMaxBlocks256 is 15 mod 16): every launch is a grid of its own, whose
+    // workgroup b starts at u0 + b * 256 * C and whose end u0 + nu bounds every chunk as total_units, so its last
+    // workgroup stops where the next launch starts (tests/test_launch_split_gpu.py runs caps of both residues)
+    const u64 per_launch = launch_blocks() * 256u;
     for (u64 u0 = 0; u0 < total_units; u0 += per_launch) {
         const u64 nu = (total_units - u0 < per_launch) ? total_units - u0 : per_launch;
         const u32 blocks = ceil_div_u64(nu, 256u * (u32)chunks);

@@ -81,6 +81,15 @@ constexpr u64 kMaxBlocks256 = ((1ull << 32) - 1) / 256;    // 256-thread workgro
 constexpr u64 kMaxBlocks512 = ((1ull << 32) - 1) / 512;    // the tiled kernel's upper block size
 constexpr u64 kMaxBlocks1024 = ((1ull << 32) - 1) / 1024;
 
+// 256-thread workgroups one launch takes where the HOST cuts a call into several launches: kMaxBlocks256, or what knob
+// launch_blocks says when that is lower, which is how the tests run the second and later launches of every split (no
+// shape that fits a test gets there by itself).  Host only; a host call reads it once.
+inline u64 launch_blocks()
+{
+    const int forced = tune(TUNE_LAUNCH_BLOCKS);
+    return forced > 0 ? std::min<u64>((u64)forced, kMaxBlocks256) : kMaxBlocks256;
+}
+
 // Workgroups are dealt round-robin over the 8 XCDs (block b runs on XCD b % 8; placement is
 // a speed matter only, never correctness).  Remapping the block id so that XCD x owns the
 // x-th contiguous eighth of the logical block range makes every XCD's L2 write back one
@@ -365,11 +374,11 @@ inline u32 stream_xcd(u64 units)
 }
 
 // The launches of a grid of per_group workgroups for every group of G elements, as many groups per launch as
-// kMaxBlocks256 allows: launch(e0, elements, workgroups) issues the one from element e0 on.
+// max_blocks (the caller's launch_blocks()) allows: launch(e0, elements, workgroups) issues the one from element e0 on.
 template <typename Launch>
-inline hipError_t launch_groups(u64 batch, u32 G, u64 per_group, Launch launch)
+inline hipError_t launch_groups(u64 max_blocks, u64 batch, u32 G, u64 per_group, Launch launch)
 {
-    const u64 max_groups = std::max<u64>(1, kMaxBlocks256 / per_group);
+    const u64 max_groups = std::max<u64>(1, max_blocks / per_group);
     const u64 groups = (batch + G - 1) / G;
     for (u64 g0 = 0; g0 < groups; g0 += max_groups) {
         const u64 ng = std::min(max_groups, groups - g0), e0 = g0 * G;

@@ -14,7 +14,7 @@ namespace {
 // (16 bytes when dL is even and every pointer is 16-byte aligned, else 8: the convention of add_uniform and
 // k_copy_list), lane l the units l, l + 256, ..., so every wave-level store is 1 KiB (or 512 B) of contiguous output.
 // A plane's units start on a workgroup boundary: plane j owns the workgroups [first[j], first[j + 1]) of a virtual
-// grid that launches slice at kMaxBlocks256.  A lane finds its element by a FastDiv of its unit inside the workgroup's
+// grid that launches slice at launch_blocks().  A lane finds its element by a FastDiv of its unit inside the workgroup's
 // first element (the workgroup's first element is one 64-bit division, paid once per workgroup), so outputs past 2^32
 // units need no special case.  The lanes of one element load the same index word: one request per wave and element.
 constexpr u32 kGatherK = 4;                           // units per lane: four loads in flight before the first store
@@ -368,9 +368,10 @@ hipError_t gather_planes(u64 n_bits, u64 n_planes, const u64 *const *src, const 
     a.count_out = (u32)count_out;
     a.d_in = csgn_fastdiv_make(count_in ? (u32)count_in : 1u);
     a.xcd = stream_xcd(units);
-    for (u64 b0 = 0; b0 < blocks; b0 += kMaxBlocks256) {
+    const u64 max_blocks = launch_blocks();
+    for (u64 b0 = 0; b0 < blocks; b0 += max_blocks) {
         a.block_base = b0;
-        const u32 nb = (u32)std::min<u64>(blocks - b0, kMaxBlocks256);
+        const u32 nb = (u32)std::min<u64>(blocks - b0, max_blocks);
         if (wide)
             k_gather<unit16><<<nb, 256, 0, s>>>(a);
         else
@@ -393,7 +394,10 @@ hipError_t gather_ragged(u64 n_bits, u64 count_in, const u64 *src, const u64 *sr
     const u64 total_units = total_terms_out * U;
     const FastDiv dU = csgn_fastdiv_make(U), d_in = csgn_fastdiv_make(count_in ? (u32)count_in : 1u);
     const int chunks = ragged_chunks(total_units);
-    const u64 per_launch = kMaxBlocks256 * 256u;                  // units: a multiple of every 256 * C
+    // units of one launch.  No multiple of 256 * C (kMaxBlocks256 is 15 mod 16): every launch is a grid of its own, whose
+    // workgroup b starts at u0 + b * 256 * C and whose end u0 + nu bounds every chunk as total_units, so its last
+    // workgroup stops where the next launch starts (tests/test_launch_split_gpu.py runs caps of both residues)
+    const u64 per_launch = launch_blocks() * 256u;
     for (u64 u0 = 0; u0 < total_units; u0 += per_launch) {
         const u64 nu = std::min(total_units - u0, per_launch);
         const u32 blocks = ceil_div_u64(nu, 256u * (u32)chunks);

@@ -194,7 +194,8 @@ hipError_t matmul_fused(u64 rows, u64 inner, u64 cols, const u64 *A, u64 ta, con
     // out over the parts; or what knob matmul_epart says, which is how the tests choose the split
     const u64 capE = std::min<u64>({inner, kMaxStream / cell,
                                     staged ? kLdsBudget / ((RT * ta + CT * tb) * KC * ub) : inner});
-    const u64 minE = (inner * a.chunks + kMaxBlocks256 - 1) / kMaxBlocks256;      // one tile's parts fit one launch
+    const u64 max_blocks = launch_blocks();
+    const u64 minE = (inner * a.chunks + max_blocks - 1) / max_blocks;            // one tile's parts fit one launch
     u64 EP;
     const int forced = tune(TUNE_MATMUL_EPART);
     if (forced > 0) {
@@ -225,13 +226,13 @@ hipError_t matmul_fused(u64 rows, u64 inner, u64 cols, const u64 *A, u64 ta, con
     a.xcd = stream_xcd(rows * cols * inner * tt * U);
     // columns of one launch: as many tiles as a launch's workgroups allow; rows by launch_groups
     const u64 per_tile = (u64)a.eparts * a.chunks;
-    const u64 launch_ctiles = std::max<u64>(1, kMaxBlocks256 / per_tile);
+    const u64 launch_ctiles = std::max<u64>(1, max_blocks / per_tile);
     for (u64 t0 = 0; t0 < ctiles; t0 += launch_ctiles) {
         const u64 nt = std::min(launch_ctiles, ctiles - t0);
         a.col0 = t0 * CT;
         a.ncols = (u32)std::min<u64>(cols - a.col0, nt * CT);
         a.ctiles = (u32)nt;
-        const hipError_t err = launch_groups(rows, a.RT, nt * per_tile, [&](u64 r0, u64 nr, u32 nblocks) {
+        const hipError_t err = launch_groups(max_blocks, rows, a.RT, nt * per_tile, [&](u64 r0, u64 nr, u32 nblocks) {
             a.row0 = r0;
             a.nrows = (u32)nr;
             a.nblocks = nblocks;

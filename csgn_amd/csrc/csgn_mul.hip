@@ -1413,8 +1413,8 @@ hipError_t mul_uniform_chunk(u32 U, u64 pairs, u64 call_pairs, u32 t1, u32 t2, c
         return hipSuccess;
     const MulTuning tune = mul_tuning();
     if (t1 == 1 && t2 == 1 && !opitch) {
-        // at most 2^31-1 workgroups of 256 units per launch
-        const u64 per_launch = kMaxBlocks256 * 256u;
+        // at most launch_blocks() workgroups of 256 units per launch (kMaxBlocks256: gridDim.x * 256 stays below 2^32)
+        const u64 per_launch = launch_blocks() * 256u;
         for (u64 u0 = 0; u0 < total; u0 += per_launch) {
             const u64 nu = (total - u0 < per_launch) ? total - u0 : per_launch;
             k_and_stream<Unit, true><<<ceil_div_u64(nu, 256u), 256, 0, s>>>(Lu + u0, Ru + u0, Ou + u0, nu,

@@ -39,6 +39,7 @@ const Knob kKnobs[TUNE_COUNT] = {
     {"uint_find_rparts", 0},
     {"matmul_form", -1},
     {"matmul_epart", 0},
+    {"launch_blocks", 0},
 };
 
 // Knob values are PER HOST THREAD: a thread that sets a knob changes the dispatch of its own later

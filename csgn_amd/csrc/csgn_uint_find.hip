@@ -223,12 +223,13 @@ hipError_t find_fused(u64 n_bits, u64 batch, u64 v, const u64 *const *query, con
     // as knob uint_find_rparts says, which is how the tests reach the launches from row rl > 0 on
     const u64 per_rpart = (u64)a.chunks * a.qparts;
     const int forced_rparts = tune(TUNE_UINT_FIND_RPARTS);
-    const u64 launch_rows = (forced_rparts > 0 ? (u64)forced_rparts : std::max<u64>(1, kMaxBlocks256 / per_rpart)) * RP;
+    const u64 max_blocks = launch_blocks();
+    const u64 launch_rows = (forced_rparts > 0 ? (u64)forced_rparts : std::max<u64>(1, max_blocks / per_rpart)) * RP;
     for (u64 rl = 0; rl < rows; rl += launch_rows) {
         const u64 nrows = std::min(launch_rows, rows - rl);
         a.rows = (u32)nrows;
         a.rparts = (u32)((nrows + RP - 1) / RP);
-        const hipError_t err = launch_groups(batch, a.G, per_rpart * a.rparts, [&](u64 e0, u64 ne, u32 nblocks) {
+        const hipError_t err = launch_groups(max_blocks, batch, a.G, per_rpart * a.rparts, [&](u64 e0, u64 ne, u32 nblocks) {
             a.batch = ne;
             for (u32 k = 0; k < v; ++k) {
                 a.query[k] = reinterpret_cast<const Unit *>(query[k]) + e0 * s[k] * U;

@@ -201,7 +201,7 @@ hipError_t lut_fused(const LutPlan &p, u64 n_bits, u64 batch, const u64 *const *
     const u32 lds = sp.layout(a.G);
     a.tabs = sp.t;
     a.xcd = stream_xcd(batch * sumT * U);
-    return launch_groups(batch, a.G, (u64)a.chunks * a.parts, [&](u64 e0, u64 ne, u32 nblocks) {
+    return launch_groups(launch_blocks(), batch, a.G, (u64)a.chunks * a.parts, [&](u64 e0, u64 ne, u32 nblocks) {
         a.batch = ne;
         for (u32 i = 0; i < p.w; ++i)
             a.plane[i] = reinterpret_cast<const Unit *>(planes[i]) + e0 * p.t[i] * U;

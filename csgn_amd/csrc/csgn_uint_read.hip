@@ -232,7 +232,7 @@ hipError_t read_fused(u64 n_bits, u64 batch, u64 v, const u64 *const *index, con
     }
     a.tabs = sp.t;
     a.xcd = stream_xcd(batch * E * sumt * U);
-    return launch_groups(batch, a.G, (u64)a.chunks * a.parts, [&](u64 e0, u64 ne, u32 nblocks) {
+    return launch_groups(launch_blocks(), batch, a.G, (u64)a.chunks * a.parts, [&](u64 e0, u64 ne, u32 nblocks) {
         a.batch = ne;
         for (u32 k = 0; k < v; ++k)
             a.index[k] = reinterpret_cast<const Unit *>(index[k]) + e0 * s[k] * U;

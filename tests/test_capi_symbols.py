@@ -245,6 +245,21 @@ def test_tuning_knobs_api(lib, knobs):
     assert lib.csgn_set_tuning(None, 1) == -1
 
 
+def test_launch_blocks_knob_is_last_and_off_by_default(lib, knobs):
+    """Knob launch_blocks (the workgroups of one launch where the host splits a call; tests/test_launch_split_gpu.py):
+    the newest knob, 0 = the HIP limit unless a test sets it, and no dispatch name depends on it."""
+    from csgn_amd import capi
+    assert capi.tuning_names()[-1] == "launch_blocks"
+    knobs.unset("launch_blocks")
+    assert capi.get_tuning("launch_blocks") == 0
+    names = lambda: (lib.csgn_mul_uniform_kernel(1247, 3001, 1, 1), lib.csgn_matmul_kernel(1247, 37, 3, 3, 1, 1, 0),  # noqa: E731
+                     lib.csgn_gather_kernel(1247, 3001, 1, 1), lib.csgn_gather_kernel(1247, 3001, 0, 2))
+    before = names()
+    knobs.set("launch_blocks", 15)
+    assert capi.get_tuning("launch_blocks") == 15 and names() == before
+    assert before == (b"k_and_stream", b"k_matmul", b"k_gather_ragged", b"k_gather")
+
+
 def test_tuning_knobs_are_per_host_thread(lib, knobs):
     """a knob set by one host thread must not change another thread's dispatch (the C ABI
     is called from one host thread per GPU).  Each thread starts from the defaults and keeps its own values."""

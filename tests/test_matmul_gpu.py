@@ -62,8 +62,9 @@ def test_matmul_words(hip, knobs, n, shape):
 
 @pytest.mark.parametrize("rows,cols", [(1, 1), (257, 1), (1, 257), (4099, 1), (1, 4099), (65539, 1), (13, 11), (37, 111)])
 def test_matmul_tiles_and_groups(hip, knobs, rows, cols):
-    """Partial last tiles in rows, in columns and in both, many tiles a launch, and the row groups launch_groups deals
-    out, in every form."""
+    """Partial last tiles in rows, in columns and in both, and many tiles a launch, in every form.  Every shape here is
+    ONE launch of the fused kernel; the launches the host cuts rows and column tiles into run in
+    tests/test_launch_split_gpu.py."""
     n, inner = 65, 3
     a = rand_terms(n, rows * inner, 1, 300 + rows)
     b = rand_terms(n, inner * cols, 1, 310 + cols)
@@ -93,6 +94,56 @@ def test_matmul_misaligned_operands_take_the_8_byte_path(hip, knobs, n):
         a = rand_terms(n, rows * inner, ta, 500 + n + rows)
         b = rand_terms(n, inner * cols, tb, 510 + n + cols)
         check_forms(hip, knobs, n, a, b, rows, inner, cols, shift=1)
+
+
+# What matmul_fused (csgn_matmul.hip) plans for each case, by its own arithmetic.  ub = bytes a unit, U = units a term.
+# Terms are sliced when 2 (ta + tb) U ub > 32768: fit = 32768 / (2 (ta + tb) ub) units; fit >= 16: chunks = ceil(U / fit)
+# slices of KC = ceil(U / chunks) units, the last of U - (chunks - 1) KC; fit < 16: whole terms.  Then the tile doubles
+# rows and columns in turn while (RT ta + CT tb) KC ub <= 32768.
+#   (n, shift, ta, tb)       U  ub   fit  slices       tile (3,2,3) / (2,3,9)
+#   (4096, 0, 17, 16)        32 16   31   16 + 16      2 x 2 / 2 x 4
+#   (4096, 0, 40, 24)        32 16   16   16 + 16      2 x 2 / 2 x 2   (fit is the smallest slice allowed; the 2 x 2 tile
+#                                                                       is 32768 bytes, the whole budget)
+#   (4096, 1, 17, 16)        64  8   62   32 + 32      2 x 2 / 2 x 4
+#   (5000, 0, 16, 14)        79  8   68   40 + 39      2 x 2 / 2 x 4   (a short last slice: kc < KC, the holes of stage())
+#   (5000, 0, 31, 29)        79  8   34   27 + 27 + 25 2 x 2 / 2 x 2
+#   (4096, 0, 40, 30)        32 16   14   whole terms  1 x 1: two rows of whole terms are 56320 bytes, so the unstaged
+#                                                      kernel runs on a shape with rows, cols > 1
+SLICED = [(4096, 0, 17, 16), (4096, 0, 40, 24), (4096, 1, 17, 16), (5000, 0, 16, 14), (5000, 0, 31, 29), (4096, 0, 40, 30)]
+
+
+@pytest.mark.parametrize("shape", [(3, 2, 3), (2, 3, 9)], ids=lambda s: "x".join(map(str, s)))
+@pytest.mark.parametrize("case", SLICED, ids=lambda c: "n%d_s%d_%dx%d" % c)
+def test_matmul_unit_slices_and_lds_fallback(hip, knobs, case, shape):
+    """Terms too long for the LDS budget: slices of units (chunk, k0, and kc < KC on a short last slice), and the
+    unstaged 1 x 1 tile once a slice would be under 16 units.  Every part of e is one element (EP = 1: the tile of one e
+    nearly fills the budget)."""
+    n, shift, ta, tb = case
+    rows, inner, cols = shape
+    a = rand_terms(n, rows * inner, ta, 800 + ta)
+    b = rand_terms(n, inner * cols, tb, 810 + tb)
+    check_forms(hip, knobs, n, a, b, rows, inner, cols, forms=(-1, 1), shift=shift)
+
+
+def test_matmul_budget_stops_an_asymmetric_tile(hip, knobs):
+    """ta = 1, tb = 20 at n = 4096 (U = 32, whole terms: 2 * 21 * 512 bytes fit): the tile grows 2 x 1, 2 x 2, 4 x 2
+    (22528 bytes) and stops there, 4 x 4 being 43008; one e a part (EP = 1).  9 rows and columns: partial last tiles both
+    ways."""
+    n, rows, inner, cols = 4096, 9, 2, 9
+    a = rand_terms(n, rows * inner, 1, 820)
+    b = rand_terms(n, inner * cols, 20, 821)
+    check_forms(hip, knobs, n, a, b, rows, inner, cols, forms=(-1, 1))
+
+
+def test_matmul_unit_slices_over_several_launches(hip, knobs):
+    """Slices and the host's launch split together: (31, 29) terms at n = 5000 are 3 slices, (2, 3, 9) is 3 parts of e
+    and 5 column tiles of 2 x 2, so a tile is per_tile = eparts * chunks = 9 workgroups; at launch_blocks = 15 (knob:
+    the workgroups of one launch) a launch takes one tile: 5 launches, col0 = 0, 2, 4, 6, 8, the last of one column."""
+    n, rows, inner, cols = 5000, 2, 3, 9
+    a = rand_terms(n, rows * inner, 31, 830)
+    b = rand_terms(n, inner * cols, 29, 831)
+    knobs.set("launch_blocks", 15)
+    check_forms(hip, knobs, n, a, b, rows, inner, cols, forms=(1,))
 
 
 def test_matmul_decrypts(hip, knobs, oracle):

@@ -96,7 +96,8 @@ def test_find_words(hip, knobs, n, v, tmode):
 
 @pytest.mark.parametrize("batch", [1, 257, 4099, (1 << 16) + 3])
 def test_find_batches(hip, knobs, batch):
-    """Partial last element groups, and the element groups launch_groups deals out, in every form.  The largest batch
+    """Partial last element groups and many groups a launch, in every form (every batch here is ONE launch of the fused
+    kernel; the launches launch_groups cuts a batch into run in tests/test_launch_split_gpu.py).  The largest batch
     writes one value plane (1.1 GB at 13 * 81 terms an element) without member; the others two planes and member."""
     n, v, rows = 65, 4, 13
     keys = [rand_terms(n, rows, 1, 700 + k) for k in range(v)]
