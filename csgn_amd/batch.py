@@ -410,6 +410,26 @@ class HipPath:
                                    _ptr(out), self.stream))
         return out[: rows * cols * terms * dl]
 
+    def count(self, n_bits: int, count: int, group: int, t: int, ins, js, outs=None):
+        """csgn_count: the bits of the number of ones among every element's `group` inputs of `t` terms each.  `ins`:
+        one tensor, the grouped layout (element q * group + i), or `group` tensors of `count` elements, the plane
+        layout.  `js`: the strictly ascending planes wanted.  Returns one tensor per plane, count elements of
+        csgn_count_terms(group, t, j) terms (fresh ones unless `outs` is given)."""
+        dl = self.default_len(n_bits)
+        terms = [int(self.lib.csgn_count_terms(group, t, int(j))) for j in js]
+        assert all(terms), "bad group, term count or plane"
+        assert len(ins) in (1, group)
+        need = (count * group if len(ins) == 1 else count) * t * dl
+        assert all(x.numel() >= need for x in ins)
+        if outs is None:
+            outs = [self.empty_words(count * T * dl) for T in terms]
+        assert all(o.numel() >= count * T * dl for o, T in zip(outs, terms))
+        h_in = (C.c_void_p * len(ins))(*[_ptr(x) for x in ins])
+        h_js = (C.c_uint64 * len(js))(*[int(j) for j in js])
+        h_out = (C.c_void_p * len(outs))(*[_ptr(o) for o in outs])
+        check(self.lib.csgn_count(n_bits, count, group, t, h_in, len(ins), len(js), h_js, h_out, self.stream))
+        return [o[: count * T * dl] for o, T in zip(outs, terms)]
+
     def add_ragged(self, n_bits: int, left: torch.Tensor, off_left: torch.Tensor,
                    right: torch.Tensor, off_right: torch.Tensor,
                    total_terms_out: Optional[int] = None, max_t1: int = 0, max_t2: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -160,6 +160,9 @@ SIGNATURES = {
     "csgn_matmul_terms": (u64, [u64, u64, u64]),
     "csgn_matmul_kernel": (C.c_char_p, [u64, u64, u64, u64, u64, u64, C.c_int]),
     "csgn_matmul": (C.c_int, [u64, u64, u64, u64, vp, u64, vp, u64, C.c_int, vp, vp]),
+    "csgn_count_terms": (u64, [u64, u64, u64]),
+    "csgn_count_kernel": (C.c_char_p, [u64, u64, u64, u64, u64, u64, vp]),
+    "csgn_count": (C.c_int, [u64, u64, u64, u64, vp, u64, u64, vp, vp, vp]),
     "csgn_set_tuning": (C.c_int, [C.c_char_p, C.c_int]),
     "csgn_get_tuning": (C.c_int, [C.c_char_p, C.POINTER(C.c_int)]),
     "csgn_reset_tuning": (None, []),

@@ -4,6 +4,7 @@
 #include "Gates.h"
 #include "runtime.h"
 
+#include <algorithm>
 #include <map>
 #include <mutex>
 #include <stdexcept>
@@ -1006,6 +1007,211 @@ UIntBatch readWhere(const UIntBatch &keys, const UIntBatch &values, const UIntBa
 CiphertextBatch matches(const UIntBatch &keys, const UIntBatch &query)
 {
     return findPlanes(keys, std::vector<CiphertextBatch>(), query, true)[0];
+}
+
+// ------------------------------------------------------------------ counting (csgn_count)
+
+namespace {
+
+// Terms per element of the planes js for inputs of t terms; 0: 2^j > group, the plane is ZERO.  Throws past 2^31 words.
+std::vector<uint64_t> countSizes(const Context &ctx, uint64_t group, uint64_t t, const std::vector<unsigned> &js,
+                                 const char *who)
+{
+    std::vector<uint64_t> T(js.size(), 0);
+    for (size_t x = 0; x < js.size(); ++x) {
+        if (js[x] > 6 || (1ull << js[x]) > group)
+            continue;
+        T[x] = csgn_count_terms(group, t, js[x]);
+        if (T[x] == 0 || T[x] > (kMaxWords - 1) / ctx.getDefaultN())
+            throw std::invalid_argument(std::string("certFHE::") + who + ": plane " + std::to_string(js[x]) +
+                                        " of groups of " + std::to_string(group) + " exceeds 2^31 words per element");
+    }
+    return T;
+}
+
+std::vector<unsigned> firstPlanes(unsigned planes)
+{
+    std::vector<unsigned> js(planes);
+    for (unsigned j = 0; j < planes; ++j)
+        js[j] = j;
+    return js;
+}
+
+// The planes js of the number of ones among every element's `group` inputs.  in: one batch, the grouped layout (input i
+// of element q is element q * group + i), or `group` batches of one element count, the plane layout.  Every size
+// first; then one csgn_count for uniform inputs of one term count, else the definition through the batch operators.
+std::vector<CiphertextBatch> countPlanes(const std::vector<CiphertextBatch> &in, uint64_t group,
+                                         const std::vector<unsigned> &js, const char *who)
+{
+    const std::string name = std::string("certFHE::") + who;
+    const Context &ctx = in[0].context();
+    const bool grouped = in.size() == 1;
+    const uint64_t count = grouped ? in[0].size() / group : in[0].size();
+    std::vector<CiphertextBatch> out;
+    if (count == 0) {
+        for (size_t x = 0; x < js.size(); ++x)
+            out.push_back(BatchAccess::make(ctx, 0, 1));
+        return out;
+    }
+    const Planes p(in);
+    uint64_t t = 0;
+    bool one_t = true;
+    for (size_t i = 0; i < p.terms.size(); ++i) {
+        one_t = one_t && p.terms[i] == p.terms[0];
+        t = p.terms[i] > t ? p.terms[i] : t;
+    }
+    // sizes, from the largest term count: a bound for every element of a ragged or mixed operand
+    const std::vector<uint64_t> T = countSizes(ctx, group, t, js, who);
+    const CiphertextBatch zero = constantBatch(ctx, std::vector<unsigned char>(count, 0));
+    out.assign(js.size(), zero);
+    if (p.uniform && one_t) {
+        std::vector<uint64_t> h_js, Ts;
+        std::vector<size_t> at;
+        for (size_t x = 0; x < js.size(); ++x) {
+            if (T[x] == 0)
+                continue;
+            if (grouped && js[x] == 0) {
+                out[x] = in[0].sumGroups(group);                 // a sum is a concatenation: the same payload
+                continue;
+            }
+            h_js.push_back(js[x]);
+            Ts.push_back(T[x]);
+            at.push_back(x);
+        }
+        if (h_js.empty())
+            return out;
+        std::vector<CiphertextBatch> made = makePlanes(ctx, count, Ts);
+        detail::check(csgn_count(ctx.getN(), count, group, t, sources(p).data(), in.size(), h_js.size(), h_js.data(),
+                                 wordsOf(made).data(), detail::stream()),
+                      "csgn_count");
+        for (size_t k = 0; k < at.size(); ++k)
+            out[at[k]] = made[k];
+        return out;
+    }
+    // ragged or mixed: the definition itself, from gather, operator* and sumGroups over one grouped batch
+    const CiphertextBatch all = grouped ? in[0] : CiphertextBatch::concat(in);
+    for (size_t x = 0; x < js.size(); ++x)
+        if (T[x] != 0 && count >= (1ull << 32) / csgn_count_terms(group, 1, js[x]))      // count * C(group, 2^j)
+            throw std::invalid_argument(name + ": ragged operands of 2^32 products or more");
+    for (size_t x = 0; x < js.size(); ++x) {
+        if (T[x] == 0)
+            continue;
+        if (grouped && js[x] == 0) {
+            out[x] = in[0].sumGroups(group);
+            continue;
+        }
+        const uint64_t m = 1ull << js[x], ncomb = csgn_count_terms(group, 1, js[x]);
+        std::vector<std::vector<uint64_t> > idx(m, std::vector<uint64_t>(count * ncomb));
+        std::vector<uint64_t> s(m);
+        for (uint64_t q = 0; q < count; ++q) {
+            for (uint64_t k = 0; k < m; ++k)
+                s[k] = k;
+            for (uint64_t c = 0; c < ncomb; ++c) {
+                for (uint64_t k = 0; k < m; ++k)
+                    idx[k][q * ncomb + c] = grouped ? q * group + s[k] : s[k] * count + q;
+                uint64_t k = m - 1;                              // the successor in lexicographic order
+                while (k > 0 && s[k] == group - m + k)
+                    --k;
+                ++s[k];
+                for (uint64_t i = k + 1; i < m; ++i)
+                    s[i] = s[i - 1] + 1;
+            }
+        }
+        CiphertextBatch prod = all.gather(idx[0]);
+        for (uint64_t k = 1; k < m; ++k)
+            prod = prod * all.gather(idx[k]);
+        out[x] = prod.sumGroups(ncomb);
+    }
+    return out;
+}
+
+void requirePlanes(unsigned planes, const char *who)
+{
+    if (planes < 1 || planes > 64)
+        throw std::invalid_argument(std::string("certFHE::") + who + ": planes must be 1..64");
+}
+
+void requireGroup(const CiphertextBatch &bits, uint64_t group, const char *who)
+{
+    if (group == 0 || bits.size() % group != 0)
+        throw std::invalid_argument(std::string("certFHE::") + who + ": groups of " + std::to_string(group) +
+                                    " in a batch of " + std::to_string(bits.size()));
+}
+
+} // namespace
+
+UIntBatch countOnes(const CiphertextBatch &bits, uint64_t group, unsigned planes)
+{
+    requirePlanes(planes, "countOnes");
+    requireGroup(bits, group, "countOnes");
+    return UIntBatch::fromPlanes(countPlanes(std::vector<CiphertextBatch>(1, bits), group, firstPlanes(planes), "countOnes"));
+}
+
+CiphertextBatch countBit(const CiphertextBatch &bits, uint64_t group, unsigned j)
+{
+    requireGroup(bits, group, "countBit");
+    return countPlanes(std::vector<CiphertextBatch>(1, bits), group, std::vector<unsigned>(1, j), "countBit")[0];
+}
+
+// the planes of a are the plane layout's inputs (a width of 1: the one plane is a grouped batch of groups of 1)
+UIntBatch popcount(const UIntBatch &a, unsigned planes)
+{
+    requirePlanes(planes, "popcount");
+    return UIntBatch::fromPlanes(countPlanes(planesOf(a), a.width(), firstPlanes(planes), "popcount"));
+}
+
+CiphertextBatch popcountBit(const UIntBatch &a, unsigned j)
+{
+    return countPlanes(planesOf(a), a.width(), std::vector<unsigned>(1, j), "popcountBit")[0];
+}
+
+UIntBatch hammingDistance(const UIntBatch &a, const UIntBatch &b, unsigned planes)
+{
+    requirePlanes(planes, "hammingDistance");
+    requireSame(a, b, "hammingDistance");
+    uint64_t t = 0;                                              // of a ^ b, before it is computed
+    for (unsigned j = 0; j < a.width() && a.size(); ++j)
+        t = std::max(t, termsOf(a.plane(j)) + termsOf(b.plane(j)));
+    if (a.size())
+        countSizes(a.context(), a.width(), t, firstPlanes(planes), "hammingDistance");
+    return popcount(a ^ b, planes);
+}
+
+UIntBatch countMatches(const UIntBatch &keys, const UIntBatch &query, unsigned planes)
+{
+    requirePlanes(planes, "countMatches");
+    const Context &ctx = query.context();
+    const uint64_t v = keys.width(), rows = keys.size(), m = query.size();
+    if (!sameContext(keys.context(), ctx))
+        throw std::invalid_argument("certFHE::countMatches: the keys and the query differ in context");
+    if (query.width() != v)
+        throw std::invalid_argument("certFHE::countMatches: the keys and the query differ in width");
+    if (rows == 0)
+        throw std::invalid_argument("certFHE::countMatches: the table has no rows");
+    // sizes first: an equality has P = prod_k (u_k + s_k + 1) terms, plane j then C(rows, 2^j) * P^(2^j)
+    const Planes y(keys), x(query);
+    unsigned long long P = 1;
+    for (uint64_t k = 0; k < v; ++k)
+        if (__builtin_mul_overflow(P, (unsigned long long)(y.terms[k] + x.terms[k] + 1), &P) || P >= kMaxWords)
+            throw std::invalid_argument("certFHE::countMatches: an equality exceeds 2^31 words per element");
+    for (unsigned j = 0; j < planes && j <= 6 && (1ull << j) <= rows && m; ++j) {
+        const uint64_t T = csgn_count_terms(rows, P, j);
+        if (T == 0 || T > (kMaxWords - 1) / ctx.getDefaultN())
+            throw std::invalid_argument("certFHE::countMatches: plane " + std::to_string(j) + " of " +
+                                        std::to_string(rows) + " rows exceeds 2^31 words per element");
+    }
+    if (m == 0)
+        return UIntBatch::fromPlanes(std::vector<CiphertextBatch>(planes, BatchAccess::make(ctx, 0, 1)));
+    if (m >= (1ull << 32) / rows)
+        throw std::invalid_argument("certFHE::countMatches: 2^32 comparisons or more");
+    std::vector<uint64_t> ik(m * rows), iq(m * rows);
+    for (uint64_t e = 0; e < m; ++e)
+        for (uint64_t r = 0; r < rows; ++r) {
+            ik[e * rows + r] = r;
+            iq[e * rows + r] = e;
+        }
+    const CiphertextBatch eq = equalTo(keys.gather(ik), query.gather(iq));
+    return UIntBatch::fromPlanes(countPlanes(std::vector<CiphertextBatch>(1, eq), rows, firstPlanes(planes), "countMatches"));
 }
 
 } // namespace certFHE

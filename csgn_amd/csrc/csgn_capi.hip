@@ -1522,6 +1522,49 @@ int csgn_matmul(uint64_t n_bits, uint64_t rows, uint64_t inner, uint64_t cols, c
     return CSGN_OK;
 }
 
+/* ------------------------------------------------ encrypted bits counted into integers ---- */
+
+uint64_t csgn_count_terms(uint64_t group, uint64_t t, uint64_t j) { return csgn::count_terms(group, t, j); }
+
+const char *csgn_count_kernel(uint64_t n_bits, uint64_t count, uint64_t group, uint64_t t, uint64_t n_in,
+                              uint64_t n_out, const uint64_t *h_js)
+{
+    return csgn::count_kernel_name(n_bits, count, group, t, n_in, n_out, (const u64 *)h_js);
+}
+
+int csgn_count(uint64_t n_bits, uint64_t count, uint64_t group, uint64_t t, const uint64_t *const *h_in, uint64_t n_in,
+               uint64_t n_out, const uint64_t *h_js, uint64_t *const *h_out, void *stream)
+{
+    if (int rc = check_n(n_bits))
+        return rc;
+    REQUIRE(count && group && t && t < (1ull << 62), "count: %llu elements of %llu inputs of %llu terms (each at least 1, "
+            "terms below 2^62)", (unsigned long long)count, (unsigned long long)group, (unsigned long long)t);
+    REQUIRE(n_in == 1 || (n_in == group && n_in <= 64), "count: %llu input batches (1, or the group when it is 2..64)",
+            (unsigned long long)n_in);
+    REQUIRE(n_out >= 1, "count: no planes");
+    REQUIRE(h_in && h_js && h_out, "null host pointer");
+    REQUIRE(csgn::count_shape_ok(count, group, t, n_in, n_out, (const u64 *)h_js),
+            "count: the planes are not strictly ascending with 2^j within the group of %llu", (unsigned long long)group);
+    const uint64_t dl = csgn_default_len(n_bits);
+    for (uint64_t x = 0; x < n_out; ++x) {
+        // the terms of one output element; a count that reaches 2^62 is past every limit
+        uint64_t T = csgn::count_terms(group, t, h_js[x]);
+        if (T == 0)
+            T = ~0ull;
+        if (int rc = check_size(count, T, T, dl, "count: plane %llu", (unsigned long long)h_js[x]))
+            return rc;
+    }
+    if (int rc = check_planes(h_in, nullptr, n_in, "input"))
+        return rc;
+    if (int rc = check_planes((const uint64_t *const *)h_out, nullptr, n_out, "output"))
+        return rc;
+    if (int rc = require_device("csgn_count"))
+        return rc;
+    HIP_TRY(csgn::count(n_bits, count, group, t, (const u64 *const *)h_in, n_in, n_out, (const u64 *)h_js,
+                        (u64 *const *)h_out, S(stream)));
+    return CSGN_OK;
+}
+
 /* ------------------------------------------------------------------ tuning ---- */
 
 int csgn_set_tuning(const char *key, int value)

@@ -215,12 +215,22 @@ const char *matmul_kernel_name(u64 n_bits, u64 rows, u64 inner, u64 cols, u64 ta
 hipError_t matmul(u64 n_bits, u64 rows, u64 inner, u64 cols, const u64 *A, u64 ta, const u64 *B, u64 tb,
                   bool transposed, u64 *C, hipStream_t stream);
 
+// encrypted bits counted into encrypted integers (csgn_count.hip), include/csgn_hip.h's definition: plane j of element q
+// is the sum, over the 2^j-subsets of the element's `group` inputs in lexicographic order, of the products of the
+// subset's inputs.  in: one grouped batch (n_in == 1) or `group` batches of `count` elements; js: n_out strictly
+// ascending planes; out[x]: count * count_terms(group, t, js[x]) * dL words.
+u64 count_terms(u64 group, u64 t, u64 j);      // 0: a zero argument, j > 6, 2^j > group or a count of 2^62 or more
+bool count_shape_ok(u64 count, u64 group, u64 t, u64 n_in, u64 n_out, const u64 *js);   // the arguments, sizes apart
+const char *count_kernel_name(u64 n_bits, u64 count, u64 group, u64 t, u64 n_in, u64 n_out, const u64 *js);
+hipError_t count(u64 n_bits, u64 count, u64 group, u64 t, const u64 *const *in, u64 n_in, u64 n_out, const u64 *js,
+                 u64 *const *out, hipStream_t stream);
+
 // The temporaries of the composed forms and of the gather plan (csgn_scratch.cpp): a plain (hipMalloc) block the calling
 // thread keeps per stream and per user, never the stream-ordered pool.  Returns the block, or nullptr with e set
 // (hipErrorStreamCaptureUnsupported when the call would have to allocate while s is capturing).  owned: the block is
 // past the kept size and belongs to this call; scratch_done frees it behind the call's launches (waits for the device)
 // and passes e through.
-enum ScratchSlot { SCRATCH_UINT_PLAIN, SCRATCH_UINT_LUT, SCRATCH_UINT_READ, SCRATCH_UINT_ADDK, SCRATCH_UINT_FIND, SCRATCH_GATHER, SCRATCH_MATMUL, SCRATCH_SLOTS };
+enum ScratchSlot { SCRATCH_UINT_PLAIN, SCRATCH_UINT_LUT, SCRATCH_UINT_READ, SCRATCH_UINT_ADDK, SCRATCH_UINT_FIND, SCRATCH_GATHER, SCRATCH_MATMUL, SCRATCH_COUNT, SCRATCH_SLOTS };
 u64 *scratch_take(ScratchSlot slot, size_t bytes, hipStream_t s, bool &owned, hipError_t &e);
 hipError_t scratch_done(u64 *block, bool owned, hipError_t e);
 

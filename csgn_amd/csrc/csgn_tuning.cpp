@@ -39,6 +39,8 @@ const Knob kKnobs[TUNE_COUNT] = {
     {"uint_find_rparts", 0},
     {"matmul_form", -1},
     {"matmul_epart", 0},
+    {"count_form", -1},
+    {"count_cpart", 0},
     {"launch_blocks", 0},
 };
 

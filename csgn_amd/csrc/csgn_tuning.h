@@ -58,6 +58,8 @@ enum TuneKey {
     TUNE_UINT_FIND_RPARTS, // ... row parts of one k_uint_find launch at most, 0 = what a launch's workgroups allow (every shape within memory: one launch); a test sets it low to run the host's split of the rows into several launches
     TUNE_MATMUL_FORM,    // products of encrypted bit matrices (csgn_matmul.hip): -1 = per shape, 0 = composed form (both operands tiled by the gather launcher, one uniform multiply), 1 = fused kernel
     TUNE_MATMUL_EPART,   // ... values of e one k_matmul workgroup takes at most, 0 = by the shape (what the LDS holds, cut further until the workgroups fill the chip); a test sets it to choose where the range of e is split
+    TUNE_COUNT_FORM,     // encrypted bits counted into integers (csgn_count.hip): -1 = per shape, 0 = composed form (the factors tiled by the gather launcher, uniform multiplies), 1 = fused kernel
+    TUNE_COUNT_CPART,    // ... combination ranks one k_count workgroup takes at most, 0 = by the shape (what its subset table holds, cut further until the workgroups fill the chip); a test sets it to place the split of the ranks
     TUNE_LAUNCH_BLOCKS,  // 256-thread workgroups one launch takes at most where the host splits a call into launches (launch_blocks, csgn_device.h), 0 = the HIP limit; a test sets it low to run the host's splits
     TUNE_COUNT
 };

@@ -92,6 +92,21 @@
 //     a.shiftRight(s)    plane j = a_{j+s} for j + s < width, ZERO above; every plane ZERO when s >= width
 //     a.rotateLeft(s)    plane j = a_{(j - s) mod width}, s taken mod width
 //
+// COUNTING: countOnes(bits, g, planes) counts the ones among every g consecutive elements of a batch of encrypted bits
+// into an encrypted integer, modulo 2^planes: COUNT(*) of matching rows, the Hamming weight of a word, the Hamming
+// distance of two words.  Bit j of the number of ones among g bits is the elementary symmetric polynomial of degree
+// m = 2^j over F2, so plane j is the left-nested sum, over the m-subsets i_1 < ... < i_m of the group in lexicographic
+// order (the nested loops), of the left-nested products x_{i_1} * ... * x_{i_m}: csgn_count's words
+// (include/csgn_hip.h).  Plane j has C(g, m) * t^m terms for inputs of t terms: with g = 64 fresh bits 64, 2016 and
+// 635 376 terms for planes 0, 1, 2; planes 3, 4, 5 are past any memory, and plane 6 is one term, the AND of all 64 --
+// so countBit / popcountBit name ONE plane.  A plane with 2^j > g is the one-term ZERO of constantBatch.  Plane 0 is
+// sumGroups(g): it shares the payload and costs no launch; the other planes of a uniform batch come from ONE csgn_count
+// (one launch), as does every plane of popcount when all planes of `a` are uniform with one term count.  Ragged
+// operands, or planes of different term counts, are composed from gather, operator* and sumGroups with the same words.
+// Every size is computed before anything is allocated or launched: std::invalid_argument for a group of 0 or one that
+// does not divide size(), `planes` of 0 or above 64, mismatched contexts or widths, or a plane past 2^31 words per
+// element.  An empty batch gives empty planes.
+//
 // Uniform planes run one csgn_uint_step (or csgn_gate_uniform) call per bit; ragged ones (what compact() may return)
 // are composed from the CiphertextBatch operators and Gates.h, with the same words.  Only the running carry or
 // accumulator is kept alive between bits.
@@ -216,6 +231,19 @@ CiphertextBatch readWhere(const UIntBatch &keys, const CiphertextBatch &values, 
 UIntBatch readWhere(const UIntBatch &keys, const UIntBatch &values, const UIntBatch &query, CiphertextBatch *member);
 // element e: parity of the number of rows with keys[r] == query[e]  (distinct keys: membership)
 CiphertextBatch matches(const UIntBatch &keys, const UIntBatch &query);
+
+// element q: the number of ones among bits[q*group .. q*group+group-1], modulo 2^planes; planes >= 1
+UIntBatch countOnes(const CiphertextBatch &bits, uint64_t group, unsigned planes);
+// bit j alone of that number (j = 6 at group 64: the AND of all 64); ZERO where 2^j > group
+CiphertextBatch countBit(const CiphertextBatch &bits, uint64_t group, unsigned j);
+// Hamming weight of every element, modulo 2^planes / its bit j alone
+UIntBatch popcount(const UIntBatch &a, unsigned planes);
+CiphertextBatch popcountBit(const UIntBatch &a, unsigned j);
+// popcount(a ^ b, planes)
+UIntBatch hammingDistance(const UIntBatch &a, const UIntBatch &b, unsigned planes);
+// element e: the number of rows r with keys[r] == query[e], modulo 2^planes: countOnes over the batch whose element
+// e*n + r is equalTo(keys row r, query element e); plane 0 has the words of matches(keys, query)
+UIntBatch countMatches(const UIntBatch &keys, const UIntBatch &query, unsigned planes);
 
 } // namespace certFHE
 

@@ -916,6 +916,53 @@ const char *csgn_matmul_kernel(uint64_t n_bits, uint64_t rows, uint64_t inner, u
 int csgn_matmul(uint64_t n_bits, uint64_t rows, uint64_t inner, uint64_t cols, const uint64_t *d_a, uint64_t t_a,
                 const uint64_t *d_b, uint64_t t_b, int b_transposed, uint64_t *d_out, void *stream);
 
+/* ------------------------------------------------ encrypted bits counted into integers ---- */
+
+/* ENCRYPTED bits counted into ENCRYPTED integers: COUNT(*) of matching rows, the Hamming weight of a word, the Hamming
+ * distance of two words.  Bit j of the number of ones among g bits is the elementary symmetric polynomial of degree
+ * 2^j over F2 (Lucas).
+ * Inputs: g ciphertexts x_0 ... x_{g-1} per output element, each of t terms.
+ * For a plane index j with m = 2^j <= g, output plane j of element q is the left-nested sum (operator+, a
+ * concatenation) of the left-nested products x_{i_1} * x_{i_2} * ... * x_{i_m}.  In each product the left term is slow
+ * and the right term fast, as in the reference's operator*.  The sum runs over the m-subsets i_1 < i_2 < ... < i_m of
+ * {0 ... g-1} in LEXICOGRAPHIC ORDER.  This is the order of the nested loops `for i_1 < i_2 < ...`.
+ *   - Plane j has T_j = C(g, m) * t^m terms.
+ *   - Term p decodes as c = p / t^m and digits d_1 ... d_m of p mod t^m in base t, with d_1 slowest.  Its words are the
+ *     AND over k of term d_k of x_{i_k}, where (i_1 ... i_m) is the subset of lexicographic rank c.
+ *   - Plane j decrypts to bit j of the number of ones.
+ *   - Plane 0 is the concatenation of the inputs: what sumGroups(g) already returns without a launch.
+ *   - With 2^j > g the bit is always 0.  The C ABI refuses such a j.  The classes return the one-term ZERO of
+ *     constantBatch.
+ * Term counts of the definition: g = 64, t = 1: planes 0, 1, 2 have 64, 2016 and 635 376 terms; planes 3, 4, 5 of
+ * g = 64 are past any memory; plane 6 of g = 64 is one term, the AND of all 64; g = 65: plane 6 has 65 terms.  Because
+ * of this, a call names the planes it wants as a list.  It does not give a range. */
+/* C(group, 2^j) * t^(2^j) (host only); 0 for a zero argument, j > 6, 2^j > group, t >= 2^62 or a count of 2^62 or more */
+uint64_t csgn_count_terms(uint64_t group, uint64_t t, uint64_t j);
+/* "k_count", "composed", or "" for an invalid shape (host only, a static string).  "k_count": one kernel writes every
+ * requested plane of every element; a workgroup stages its element's input terms in LDS once, unranks the subsets of
+ * its range of ranks and streams its outputs.  "composed": per plane, the m index lists of the count * C(g, m) pairs
+ * (element, subset), every factor tiled to the pairs by csgn_gather's launcher into a temporary the calling thread
+ * keeps (csgn_uint_addk's rules for its composed form), and m - 1 csgn_mul_uniform, the last straight into the output;
+ * the plane layout is interleaved into one grouped batch first.  Knob "count_form" (-1 per shape, 0 composed, 1 fused)
+ * decides; the words are the same.  Per shape: fused.  A call of count * group >= 2^32 inputs is past the
+ * gather launcher: such a shape is fused whatever the knob says.  Invalid: n_bits 0, the arguments csgn_count refuses
+ * with CSGN_ERR_INVALID, or a plane of 2^62 terms or more. */
+const char *csgn_count_kernel(uint64_t n_bits, uint64_t count, uint64_t group, uint64_t t, uint64_t n_in,
+                              uint64_t n_out, const uint64_t *h_js);
+/* The count over `count` elements.  h_in: a HOST array of n_in device pointers.  n_in == 1, the grouped layout: one
+ * batch of count * group elements, input i of element q is element q * group + i.  n_in == group with 2 <= group <= 64,
+ * the plane layout: input i is a batch of `count` elements (what a UIntBatch hands over).  h_js: n_out strictly
+ * ascending plane indices; h_out[x] takes count * T_{h_js[x]} * dL words.  Inputs may alias one another; no output
+ * overlaps an input or another output.  Checks, in this order, the first that fails giving the status: n_bits; count,
+ * group, t nonzero, t < 2^62, n_in 1 or group (<= 64 when above 1), n_out >= 1, the js strictly ascending with
+ * 2^j <= group, host pointers non-null (CSGN_ERR_INVALID); every T_j * dL below 2^31 words per element and
+ * count * T_j * dL below 2^60 (CSGN_ERR_UNSUPPORTED; computed without wrap-around); null device pointers
+ * (CSGN_ERR_INVALID); the device (CSGN_ERR_NO_DEVICE, no CPU fallback).  Nothing is allocated or launched before every
+ * check has passed.  On the caller's stream, asynchronous; the fused form is one launch for every shape within memory
+ * and graph-capturable. */
+int csgn_count(uint64_t n_bits, uint64_t count, uint64_t group, uint64_t t, const uint64_t *const *h_in, uint64_t n_in,
+               uint64_t n_out, const uint64_t *h_js, uint64_t *const *h_out, void *stream);
+
 /* ------------------------------------------------------------------- tuning ---- */
 
 /* Kernel-choice and sweep knobs ("mul_flat", "mul_touch", "ragged_c", "perm_ballot", ...;
