@@ -393,6 +393,38 @@ class HipPath:
         return ([o[: batch * int(t) * E * dl] for o, t in zip(outs, value_terms)],
                 None if member is None else member[: batch * E * dl])
 
+    def uint_lt_select(self, n_bits: int, batch: int, a, a_terms, b, b_terms, xs, x_terms, ys, y_terms, outs=None,
+                       less=False):
+        """csgn_uint_lt_select: request i is a < b ? xs[i] : ys[i] for the encrypted integers a and b (bit 0 first; plane
+        j a uniform batch of a_terms[j] / b_terms[j] terms), xs[i] / ys[i] uniform planes of x_terms[i] / y_terms[i]
+        terms.  Returns (output tensors, comparison tensor or None): output i has L * (x_terms[i] + y_terms[i]) +
+        y_terms[i] terms per element (L = csgn_uint_lt_terms), fresh ones unless `outs` is given; `less`: True for a
+        fresh tensor of L terms per element, or the tensor to write."""
+        w, m = len(a), len(xs)
+        assert w == len(a_terms) == len(b) == len(b_terms) and m == len(x_terms) == len(ys) == len(y_terms)
+        h_ta = (C.c_uint64 * max(w, 1))(*[int(t) for t in a_terms])
+        h_tb = (C.c_uint64 * max(w, 1))(*[int(t) for t in b_terms])
+        h_tx = (C.c_uint64 * max(m, 1))(*[int(t) for t in x_terms])
+        h_ty = (C.c_uint64 * max(m, 1))(*[int(t) for t in y_terms])
+        L = int(self.lib.csgn_uint_lt_terms(w, h_ta, h_tb))
+        assert L, "bad width or term count"
+        dl = self.default_len(n_bits)
+        sizes = [batch * (L * (int(tx) + int(ty)) + int(ty)) * dl for tx, ty in zip(x_terms, y_terms)]
+        if outs is None:
+            outs = [self.empty_words(max(s, 1)) for s in sizes]
+        if less is True:
+            less = self.empty_words(max(batch * L * dl, 1))
+        elif less is False:
+            less = None
+        h_a = (C.c_void_p * max(w, 1))(*[_ptr(p) for p in a])
+        h_b = (C.c_void_p * max(w, 1))(*[_ptr(p) for p in b])
+        h_x = (C.c_void_p * max(m, 1))(*[_ptr(p) for p in xs])
+        h_y = (C.c_void_p * max(m, 1))(*[_ptr(p) for p in ys])
+        h_out = (C.c_void_p * max(m, 1))(*[_ptr(o) for o in outs])
+        check(self.lib.csgn_uint_lt_select(n_bits, batch, w, h_a, h_ta, h_b, h_tb, m, h_x, h_tx, h_y, h_ty, h_out,
+                                           _ptr(less), self.stream))
+        return [o[:s] for o, s in zip(outs, sizes)], (None if less is None else less[: batch * L * dl])
+
     def matmul(self, n_bits: int, rows: int, inner: int, cols: int, a: torch.Tensor, t_a: int, b: torch.Tensor, t_b: int,
                transposed: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """csgn_matmul: the product over F2 of the encrypted bit matrices `a` (rows x inner, element i*inner + e, t_a

@@ -723,6 +723,139 @@ UIntBatch select(const CiphertextBatch &sel, const UIntBatch &a, const UIntBatch
         [&](unsigned j) { return logicMux(sel, a.plane(j), b.plane(j)); }));
 }
 
+// ------------------------------------------------------------------ selection by a < b (csgn_uint_lt_select)
+
+namespace {
+
+// out_i = logicMux(lessThan(a, b), xs[i], ys[i]) for every request
+std::vector<CiphertextBatch> selectLessPlanes(const UIntBatch &a, const UIntBatch &b, const std::vector<CiphertextBatch> &xs,
+                                              const std::vector<CiphertextBatch> &ys, const char *who)
+{
+    requireSame(a, b, who);
+    const Context &ctx = a.context();
+    const uint64_t m = a.size(), n = xs.size();
+    for (size_t i = 0; i < n; ++i)
+        if (xs[i].size() != m || ys[i].size() != m || !sameContext(xs[i].context(), ctx) || !sameContext(ys[i].context(), ctx))
+            throw std::invalid_argument(std::string("certFHE::") + who +
+                                        ": the selected operands differ from the compared ones in count or context");
+    // every size before anything is allocated
+    const uint64_t L = lessThanTerms(a, b, who);
+    const Planes pa(a), pb(b), px(xs), py(ys);
+    std::vector<uint64_t> T(n);
+    for (size_t i = 0; i < n; ++i)
+        T[i] = gateTerms(CSGN_GATE_MUX, L, px.terms[i], py.terms[i], ctx, who);
+    if (a.width() <= 16 && ((pa.uniform && pb.uniform && px.uniform && py.uniform) || m == 0)) {
+        std::vector<CiphertextBatch> out = makePlanes(ctx, m, T);
+        if (m) {
+            const std::vector<const uint64_t *> sa = sources(pa), sb = sources(pb), sx = sources(px), sy = sources(py);
+            const std::vector<uint64_t *> dst = wordsOf(out);
+            for (uint64_t i0 = 0; i0 < n; i0 += 64)                   // 64 requests a launch
+                detail::check(csgn_uint_lt_select(ctx.getN(), m, a.width(), sa.data(), pa.terms.data(), sb.data(),
+                                                  pb.terms.data(), std::min<uint64_t>(64, n - i0), sx.data() + i0,
+                                                  px.terms.data() + i0, sy.data() + i0, py.terms.data() + i0,
+                                                  dst.data() + i0, nullptr, detail::stream()),
+                              "csgn_uint_lt_select");
+        }
+        return out;
+    }
+    // ragged, or wider than 16 bits: the definition itself through lessThan(a, b) and select's gate
+    std::vector<CiphertextBatch> out;
+    const CiphertextBatch l = lessThanUnchecked(a, b);
+    for (size_t i = 0; i < n; ++i)
+        out.push_back(logicMux(l, xs[i], ys[i]));
+    return out;
+}
+
+void appendPlanes(std::vector<CiphertextBatch> &list, const UIntBatch &a)
+{
+    for (unsigned j = 0; j < a.width(); ++j)
+        list.push_back(a.plane(j));
+}
+
+UIntBatch takePlanes(const std::vector<CiphertextBatch> &planes, size_t first, unsigned width)
+{
+    return UIntBatch::fromPlanes(std::vector<CiphertextBatch>(planes.begin() + first, planes.begin() + first + width));
+}
+
+} // namespace
+
+UIntBatch selectLess(const UIntBatch &a, const UIntBatch &b, const UIntBatch &x, const UIntBatch &y)
+{
+    requireSame(x, y, "selectLess");
+    std::vector<CiphertextBatch> xs, ys;
+    appendPlanes(xs, x);
+    appendPlanes(ys, y);
+    return UIntBatch::fromPlanes(selectLessPlanes(a, b, xs, ys, "selectLess"));
+}
+
+CiphertextBatch selectLess(const UIntBatch &a, const UIntBatch &b, const CiphertextBatch &x, const CiphertextBatch &y)
+{
+    return selectLessPlanes(a, b, std::vector<CiphertextBatch>(1, x), std::vector<CiphertextBatch>(1, y), "selectLess")[0];
+}
+
+UIntBatch min(const UIntBatch &a, const UIntBatch &b)
+{
+    requireSame(a, b, "min");
+    std::vector<CiphertextBatch> xs, ys;
+    appendPlanes(xs, a);
+    appendPlanes(ys, b);
+    return UIntBatch::fromPlanes(selectLessPlanes(a, b, xs, ys, "min"));
+}
+
+UIntBatch max(const UIntBatch &a, const UIntBatch &b)
+{
+    requireSame(a, b, "max");
+    std::vector<CiphertextBatch> xs, ys;
+    appendPlanes(xs, b);
+    appendPlanes(ys, a);
+    return UIntBatch::fromPlanes(selectLessPlanes(a, b, xs, ys, "max"));
+}
+
+void compareExchange(const UIntBatch &a, const UIntBatch &b, const UIntBatch &pa, const UIntBatch &pb, UIntBatch *lo,
+                     UIntBatch *hi, UIntBatch *plo, UIntBatch *phi)
+{
+    requireSame(a, b, "compareExchange");
+    requireSame(pa, pb, "compareExchange");
+    std::vector<CiphertextBatch> xs, ys;
+    if (lo) {
+        appendPlanes(xs, a);
+        appendPlanes(ys, b);
+    }
+    if (hi) {
+        appendPlanes(xs, b);
+        appendPlanes(ys, a);
+    }
+    if (plo) {
+        appendPlanes(xs, pa);
+        appendPlanes(ys, pb);
+    }
+    if (phi) {
+        appendPlanes(xs, pb);
+        appendPlanes(ys, pa);
+    }
+    const std::vector<CiphertextBatch> out = selectLessPlanes(a, b, xs, ys, "compareExchange");
+    size_t at = 0;
+    UIntBatch *const dst[4] = {lo, hi, plo, phi};
+    for (int k = 0; k < 4; ++k)
+        if (dst[k]) {
+            const unsigned width = k < 2 ? a.width() : pa.width();
+            *dst[k] = takePlanes(out, at, width);
+            at += width;
+        }
+}
+
+std::pair<UIntBatch, UIntBatch> minMax(const UIntBatch &a, const UIntBatch &b)
+{
+    requireSame(a, b, "minMax");
+    std::vector<CiphertextBatch> xs, ys;
+    appendPlanes(xs, a);
+    appendPlanes(xs, b);
+    appendPlanes(ys, b);
+    appendPlanes(ys, a);
+    const std::vector<CiphertextBatch> out = selectLessPlanes(a, b, xs, ys, "minMax");
+    return std::make_pair(takePlanes(out, 0, a.width()), takePlanes(out, a.width(), a.width()));
+}
+
 } // namespace certFHE
 
 namespace certFHE {

@@ -1484,6 +1484,67 @@ int csgn_uint_find(uint64_t n_bits, uint64_t batch, uint64_t key_width, const ui
     return CSGN_OK;
 }
 
+/* ------------------------------------------------ selection by an encrypted comparison ---- */
+
+uint64_t csgn_uint_lt_terms(uint64_t width, const uint64_t *h_a_terms, const uint64_t *h_b_terms)
+{
+    return csgn::uint_lt_terms(width, (const u64 *)h_a_terms, (const u64 *)h_b_terms);
+}
+
+const char *csgn_uint_lt_select_kernel(uint64_t n_bits, uint64_t batch, uint64_t width, const uint64_t *h_a_terms,
+                                       const uint64_t *h_b_terms, uint64_t n_out, const uint64_t *h_x_terms,
+                                       const uint64_t *h_y_terms, int with_less)
+{
+    return csgn::uint_lt_select_kernel_name(n_bits, batch, width, (const u64 *)h_a_terms, (const u64 *)h_b_terms, n_out,
+                                            (const u64 *)h_x_terms, (const u64 *)h_y_terms, with_less != 0);
+}
+
+int csgn_uint_lt_select(uint64_t n_bits, uint64_t batch, uint64_t width, const uint64_t *const *h_a,
+                        const uint64_t *h_a_terms, const uint64_t *const *h_b, const uint64_t *h_b_terms, uint64_t n_out,
+                        const uint64_t *const *h_x, const uint64_t *h_x_terms, const uint64_t *const *h_y,
+                        const uint64_t *h_y_terms, uint64_t *const *h_out, uint64_t *d_less, void *stream)
+{
+    if (int rc = check_n(n_bits))
+        return rc;
+    REQUIRE(width >= 1 && width <= csgn::kLtSelMaxWidth, "lt_select: width %llu outside 1..16",
+            (unsigned long long)width);
+    REQUIRE(n_out <= csgn::kLtSelMaxOut, "lt_select: %llu outputs outside 0..64", (unsigned long long)n_out);
+    REQUIRE(n_out >= 1 || d_less, "lt_select: no outputs and no comparison output");
+    REQUIRE(h_a && h_a_terms && h_b && h_b_terms, "null host pointer");
+    REQUIRE(n_out == 0 || (h_x && h_x_terms && h_y && h_y_terms && h_out), "null host pointer");
+    const uint64_t L = csgn::uint_lt_terms(width, (const u64 *)h_a_terms, (const u64 *)h_b_terms);
+    REQUIRE(L != 0, "lt_select: a plane of a or b has no terms, or the term count overflows");
+    for (uint64_t i = 0; i < n_out; ++i)
+        REQUIRE(h_x_terms[i] != 0 && h_y_terms[i] != 0 && h_x_terms[i] < (1ull << 62) && h_y_terms[i] < (1ull << 62),
+                "lt_select: request %llu has a plane of no terms, or of 2^62 or more", (unsigned long long)i);
+    const uint64_t dl = csgn_default_len(n_bits);
+    for (uint64_t i = 0; i < n_out + (d_less ? 1 : 0); ++i) {
+        unsigned long long terms = L;                        // of output i; the last is the comparison's
+        if (i < n_out && (__builtin_mul_overflow((unsigned long long)L, (unsigned long long)(h_x_terms[i] + h_y_terms[i]),
+                                                 &terms) ||
+                          __builtin_add_overflow(terms, (unsigned long long)h_y_terms[i], &terms)))
+            terms = ~0ull;                                   // a count that wraps is past every limit
+        if (int rc = check_size(batch, terms, terms, dl, i < n_out ? "lt_select: output %llu" : "lt_select: the comparison",
+                                (unsigned long long)i))
+            return rc;
+    }
+    if (int rc = check_planes(h_a, h_b, width, "plane of a or b"))
+        return rc;
+    if (int rc = check_planes(h_x, h_y, n_out, "plane of a request"))
+        return rc;
+    if (int rc = check_planes((const uint64_t *const *)h_out, nullptr, n_out, "output"))
+        return rc;
+    if (int rc = require_device("csgn_uint_lt_select"))
+        return rc;
+    if (batch == 0)
+        return CSGN_OK;
+    HIP_TRY(csgn::uint_lt_select(n_bits, batch, width, (const u64 *const *)h_a, (const u64 *)h_a_terms,
+                                 (const u64 *const *)h_b, (const u64 *)h_b_terms, n_out, (const u64 *const *)h_x,
+                                 (const u64 *)h_x_terms, (const u64 *const *)h_y, (const u64 *)h_y_terms,
+                                 (u64 *const *)h_out, (u64 *)d_less, S(stream)));
+    return CSGN_OK;
+}
+
 /* ------------------------------------------------ encrypted bit matrices over F2 ---- */
 
 uint64_t csgn_matmul_terms(uint64_t inner, uint64_t t_a, uint64_t t_b) { return csgn::matmul_terms(inner, t_a, t_b); }

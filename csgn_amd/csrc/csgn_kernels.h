@@ -225,12 +225,23 @@ const char *count_kernel_name(u64 n_bits, u64 count, u64 group, u64 t, u64 n_in,
 hipError_t count(u64 n_bits, u64 count, u64 group, u64 t, const u64 *const *in, u64 n_in, u64 n_out, const u64 *js,
                  u64 *const *out, hipStream_t stream);
 
+// selection by an encrypted comparison (csgn_uint_lt_select.hip), include/csgn_hip.h's definition: output i is
+// (L * (X_i + Y_i)) + Y_i with L = lessThan(a, b), the LT_FIRST / LT_STEP chain.  a and b: w = 1..16 planes, terms ta[j] /
+// tb[j]; requests: n_out = 0..64 pairs of planes, terms tx[i] / ty[i]; less: nullptr = not written (then n_out >= 1).
+constexpr u32 kLtSelMaxWidth = 16, kLtSelMaxOut = 64;
+u64 uint_lt_terms(u64 w, const u64 *ta, const u64 *tb);   // L; 0: invalid argument or a count of 2^62 or more
+const char *uint_lt_select_kernel_name(u64 n_bits, u64 batch, u64 w, const u64 *ta, const u64 *tb, u64 n_out,
+                                       const u64 *tx, const u64 *ty, bool less);
+hipError_t uint_lt_select(u64 n_bits, u64 batch, u64 w, const u64 *const *a, const u64 *ta, const u64 *const *b,
+                          const u64 *tb, u64 n_out, const u64 *const *x, const u64 *tx, const u64 *const *y,
+                          const u64 *ty, u64 *const *out, u64 *less, hipStream_t stream);
+
 // The temporaries of the composed forms and of the gather plan (csgn_scratch.cpp): a plain (hipMalloc) block the calling
 // thread keeps per stream and per user, never the stream-ordered pool.  Returns the block, or nullptr with e set
 // (hipErrorStreamCaptureUnsupported when the call would have to allocate while s is capturing).  owned: the block is
 // past the kept size and belongs to this call; scratch_done frees it behind the call's launches (waits for the device)
 // and passes e through.
-enum ScratchSlot { SCRATCH_UINT_PLAIN, SCRATCH_UINT_LUT, SCRATCH_UINT_READ, SCRATCH_UINT_ADDK, SCRATCH_UINT_FIND, SCRATCH_GATHER, SCRATCH_MATMUL, SCRATCH_COUNT, SCRATCH_SLOTS };
+enum ScratchSlot { SCRATCH_UINT_PLAIN, SCRATCH_UINT_LUT, SCRATCH_UINT_READ, SCRATCH_UINT_ADDK, SCRATCH_UINT_FIND, SCRATCH_GATHER, SCRATCH_MATMUL, SCRATCH_COUNT, SCRATCH_UINT_LT_SELECT, SCRATCH_SLOTS };
 u64 *scratch_take(ScratchSlot slot, size_t bytes, hipStream_t s, bool &owned, hipError_t &e);
 hipError_t scratch_done(u64 *block, bool owned, hipError_t e);
 

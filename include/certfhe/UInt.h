@@ -107,6 +107,21 @@
 // does not divide size(), `planes` of 0 or above 64, mismatched contexts or widths, or a plane past 2^31 words per
 // element.  An empty batch gives empty planes.
 //
+// ORDERING: min(a, b), max(a, b), minMax(a, b), selectLess(a, b, x, y) and compareExchange select by the ENCRYPTED
+// comparison a < b: the step of every oblivious sort, top-k, median filter, arg-min and clamp.  Every output plane is
+// logicMux(lessThan(a, b), x_j, y_j) = (L * (x_j + y_j)) + y_j, the comparison the LEFT operand -- the words of
+// select(lessThan(a, b), x, y), csgn_uint_lt_select's (include/csgn_hip.h) -- and decrypts to x_j where a < b and to y_j
+// elsewhere: A TIE TAKES y.  min pairs (a_j, b_j), max pairs (b_j, a_j); compareExchange(a, b, pa, pb, ...) gives the
+// keys and the payloads that travel with them from the SAME launch: lo = min, hi = max, plo = a < b ? pa : pb,
+// phi = a < b ? pb : pa; on a tie lo = b, hi = a, plo = pb and phi = pa, so equal keys keep their payloads apart.  A null
+// output is skipped.  A plane of the result has L * (tx + ty) + ty terms for request planes of tx and ty terms, L the
+// terms of lessThan(a, b): 3^w - 1 with fresh planes (6560 at w = 8, about 2 MB per output plane and element at
+// N=1247), the same growth as a less-than.  Uniform planes of width <= 16 take one csgn_uint_lt_select per 64 output
+// planes (one launch for all of them; the comparison is never written); ragged planes (a compact() result on any
+// operand) or wider integers are composed from lessThan(a, b) and logicMux with the same words.  Every size is computed
+// before anything is allocated: std::invalid_argument for mismatched contexts, counts or widths, or an output past 2^31
+// words per element.  An empty batch gives empty planes.
+//
 // Uniform planes run one csgn_uint_step (or csgn_gate_uniform) call per bit; ragged ones (what compact() may return)
 // are composed from the CiphertextBatch operators and Gates.h, with the same words.  Only the running carry or
 // accumulator is kept alive between bits.
@@ -116,6 +131,7 @@
 #include <stdint.h>
 
 #include <memory>
+#include <utility>
 #include <vector>
 
 #include "Batch.h"
@@ -198,6 +214,19 @@ CiphertextBatch greaterThan(const UIntBatch &a, uint64_t k);
 CiphertextBatch greaterEqual(const UIntBatch &a, uint64_t k);
 // element i: sel[i] ? a[i] : b[i]
 UIntBatch select(const CiphertextBatch &sel, const UIntBatch &a, const UIntBatch &b);
+
+// element i: a[i] < b[i] ? a[i] : b[i] / the other one; a tie takes b for min and a for max
+UIntBatch min(const UIntBatch &a, const UIntBatch &b);
+UIntBatch max(const UIntBatch &a, const UIntBatch &b);
+// (min, max) from one launch
+std::pair<UIntBatch, UIntBatch> minMax(const UIntBatch &a, const UIntBatch &b);
+// element i: a[i] < b[i] ? x[i] : y[i]; x and y of one width (any), a and b of one width
+UIntBatch selectLess(const UIntBatch &a, const UIntBatch &b, const UIntBatch &x, const UIntBatch &y);
+CiphertextBatch selectLess(const UIntBatch &a, const UIntBatch &b, const CiphertextBatch &x, const CiphertextBatch &y);
+// *lo = min, *hi = max, *plo = a < b ? pa : pb, *phi = a < b ? pb : pa, all from the same launch; null outputs are
+// skipped.  A tie: lo = b, hi = a, plo = pb, phi = pa.  pa and pb of one width (any).
+void compareExchange(const UIntBatch &a, const UIntBatch &b, const UIntBatch &pa, const UIntBatch &pb, UIntBatch *lo,
+                     UIntBatch *hi, UIntBatch *plo, UIntBatch *phi);
 
 // A public table compiled once; copies share the compiled form.  Safe to use from several threads at once.
 class LookupTable {

@@ -878,6 +878,54 @@ int csgn_uint_find(uint64_t n_bits, uint64_t batch, uint64_t key_width, const ui
                    const uint64_t *h_key_terms, uint64_t width, const uint64_t *const *h_values,
                    const uint64_t *h_value_terms, uint64_t *const *h_out, uint64_t *d_member, void *stream);
 
+/* ------------------------------------------------ selection by an encrypted comparison ---- */
+
+/* min, max and compare-exchange of ENCRYPTED integers: every output selected by the ENCRYPTED comparison a < b, the
+ * step of every oblivious sort, top-k, median filter, arg-min and clamp.
+ * Inputs: a and b, integers of `width` = w planes (w in 1..16, bit 0 first) of `batch` elements, plane j uniform with
+ * ta_j / tb_j terms per element; n_out (0..64) requests, request i a pair of uniform planes (X_i, Y_i) of `batch`
+ * elements with tx_i / ty_i terms; optionally the comparison itself.  A fixed composition of the reference's
+ * operator+ / operator* with ONE:
+ *     L      lessThan(a, b) of certfhe/UInt.h:  l_0 = (a_0 + ONE) * b_0,
+ *            l_j = ((a_j + b_j) * (b_j + l_{j-1})) + l_{j-1}   (csgn_uint_step's LT_FIRST and LT_STEP rows),  L = l_{w-1}
+ *     out_i  logicMux(L, X_i, Y_i) = (L * (X_i + Y_i)) + Y_i   (csgn_gate_uniform's MUX row, L the LEFT operand)
+ * out_i decrypts to X_i where a < b and to Y_i elsewhere: a tie takes Y.  min is the requests (a_j, b_j), max the
+ * requests (b_j, a_j), a payload that travels with the smaller key (pa_j, pb_j).
+ * Terms: L_0 = (ta_0 + 1) * tb_0,  L_j = (ta_j + tb_j) * (tb_j + L_{j-1}) + L_{j-1};  T_i = L * (tx_i + ty_i) + ty_i
+ * with L = L_{w-1}.  Fresh 1-term planes: L = 3^w - 1 -- the scheme's own growth, as for csgn_uint_step's comparisons.
+ * Term order (decoding needs no table): term q * (tx_i + ty_i) + c of output i (q < L) is (term q of L) & (term c of
+ * X_i when c < tx_i, else term c - tx_i of Y_i); the last ty_i terms are Y_i's, copied.  Term q of L, for j from w - 1
+ * down to 1 with inner = tb_j + L_{j-1} and M = (ta_j + tb_j) * inner: q >= M lies in the tail copy (no factor of plane
+ * j; go on with q - M); else p = q / inner names term p of a_j (p < ta_j) or term p - ta_j of b_j, and c = q % inner
+ * term c of b_j (c < tb_j, which ends the walk) or entry c - tb_j of l_{j-1}.  At j = 0: p = q / tb_0 names term p of
+ * a_0, or ONE when p = ta_0, ANDed with term q % tb_0 of b_0. */
+/* L (host only); 0 for a width outside 1..16, a null pointer, a plane of 0 terms or a count of 2^62 or more. */
+uint64_t csgn_uint_lt_terms(uint64_t width, const uint64_t *h_a_terms, const uint64_t *h_b_terms);
+/* Which form a csgn_uint_lt_select call of this shape takes (host only, a static string): "k_uint_lt_select" (one kernel
+ * writes every output and the comparison, planes read in place, the comparison never materialised) or "composed"
+ * (LT_FIRST and the LT_STEPs through csgn_uint_step's launcher into a temporary the calling thread keeps
+ * (csgn_uint_addk's rules for its composed form), csgn_gate_uniform's MUX launcher per output, a copy into d_less: what
+ * select(lessThan(a, b), x, y) issues).  Knob "uint_lt_select_form" (-1 per shape, 0 composed, 1 fused) decides; the
+ * words are the same.  Per shape: DESIGN 4.22.  "" for an invalid shape (n_bits 0, a bad width, more than 64 requests,
+ * a bad term count, or no request without the comparison). */
+const char *csgn_uint_lt_select_kernel(uint64_t n_bits, uint64_t batch, uint64_t width, const uint64_t *h_a_terms,
+                                       const uint64_t *h_b_terms, uint64_t n_out, const uint64_t *h_x_terms,
+                                       const uint64_t *h_y_terms, int with_less);
+/* The selection over `batch` elements.  h_a, h_b: HOST arrays of `width` device pointers (plane j: batch * ta_j * dL and
+ * batch * tb_j * dL words), h_x, h_y: HOST arrays of n_out device pointers (batch * tx_i * dL and batch * ty_i * dL
+ * words), h_out: a HOST array of n_out device pointers (output i: batch * T_i * dL words), d_less: batch * L * dL words,
+ * or NULL: the comparison is then not written.  n_out == 0 is allowed only with d_less (h_x, h_x_terms, h_y, h_y_terms
+ * and h_out are then not read).  Inputs may alias one another, X_i = a_j included; no output overlaps an input or
+ * another output.  Checks, in this order, the first that fails giving the status: n_bits; width; n_out; host pointers;
+ * the term counts (CSGN_ERR_INVALID); L * dL and every T_i * dL below 2^31 words per element and batch times that below
+ * 2^60 (CSGN_ERR_UNSUPPORTED; computed without wrap-around); null device pointers (CSGN_ERR_INVALID); the device
+ * (CSGN_ERR_NO_DEVICE, no CPU fallback).  batch == 0 succeeds.  On the caller's stream, asynchronous; the fused form is
+ * one launch for every shape within memory and graph-capturable. */
+int csgn_uint_lt_select(uint64_t n_bits, uint64_t batch, uint64_t width, const uint64_t *const *h_a,
+                        const uint64_t *h_a_terms, const uint64_t *const *h_b, const uint64_t *h_b_terms, uint64_t n_out,
+                        const uint64_t *const *h_x, const uint64_t *h_x_terms, const uint64_t *const *h_y,
+                        const uint64_t *h_y_terms, uint64_t *const *h_out, uint64_t *d_less, void *stream);
+
 /* ------------------------------------------------ encrypted bit matrices over F2 ---- */
 
 /* The product of two ENCRYPTED bit matrices over F2: an inner product of encrypted bit vectors, a secret linear map
