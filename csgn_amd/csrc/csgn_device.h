@@ -3,7 +3,8 @@
 // csgn_gates.hip, csgn_uint.hip, csgn_uint_plain.hip, csgn_uint_addk.hip, csgn_uint_lut.hip, csgn_uint_read.hip,
 // csgn_uint_find.hip, csgn_uint_lt_select.hip, csgn_matmul.hip, csgn_count.hip, csgn_gather.hip):
 // 16-/8-byte unit access and the choice between them, the ONE and ZERO terms' units, FastDiv tables in kernel
-// arguments, the XCD-contiguous block order, CSR pair search, the LDS subset tables of DESIGN §4.15, launch limits,
+// arguments, the XCD-contiguous block order, CSR pair search, the LDS subset tables of DESIGN §4.15 (csgn_selector.h
+// builds the skeleton of the read, find and lt_select kernels on them), launch limits,
 // the term-count limit and the knob-dependent launch choices (csgn_tuning.h).  Everything has internal linkage (one
 // copy per translation unit).
 //
@@ -444,7 +445,8 @@ __device__ inline bool chain_walk(const Args &a, u32 hi, u32 lo, u64 eu, u32 k, 
 // ------------------------------------------------------------------------- subset tables
 // For a workgroup's elements and its slice of KC units of every term, table k holds the AND of every subset of the
 // fresh (one-term) planes [hb[k], hb[k+1]), entry S of element el at units tbase[k] + ((el << h_k) | S) * KC on; the
-// AND of any subset of all the planes is then one to three LDS reads (csgn_uint_lut.hip, csgn_uint_read.hip).
+// AND of any subset of all the planes is then one to three LDS reads (csgn_uint_lut.hip, and through csgn_selector.h
+// csgn_uint_read.hip, csgn_uint_find.hip and csgn_uint_lt_select.hip).
 constexpr u32 kMaxSubsetTables = 3;
 
 // by value in the kernel arguments

@@ -1,0 +1,160 @@
+// csgn_selector.h -- the skeleton of the selector-stream kernels (csgn_uint_read.hip, csgn_uint_find.hip,
+// csgn_uint_lt_select.hip).  Internal linkage, like csgn_device.h.
+//
+// An encrypted SELECTOR STREAM (the EQ rows of an index, the EQ of a key row and a query, the terms of lessThan) is the
+// left operand of a product with one unit of a value plane, written for every output plane in one launch: term
+// q * t_j + c of output j is (entry q of the stream) & (value term c).  A workgroup of 256 threads owns G elements, a
+// slice of KC units of every term and QP entries of the stream, for EVERY output; with fresh planes it builds its
+// subset tables (csgn_device.h) and decodes its entries into an LDS list once, for all of them.  An operation supplies
+// the decode of an entry, the address of the value unit and how it sizes G and QP.
+#pragma once
+
+#include "csgn_device.h"
+
+#include <algorithm>
+
+namespace csgn {
+
+namespace {
+
+// The outputs, by value in the kernel arguments: output j has t[j] value terms per entry of the stream.
+template <u32 N>
+struct SelOutputs {
+    void *out[N];
+    u32 t[N];
+    FastDivTable<N> tk;         // t_j * KC
+    u32 nout;
+
+    // Host: n outputs of terms(j) value terms each and, with `bare`, the stream itself as one more output of one term
+    // per entry.  Returns the sum of the term counts.
+    template <typename Terms>
+    u64 fill(u64 n, Terms terms, bool bare, u32 KC)
+    {
+        nout = (u32)(n + (bare ? 1 : 0));
+        u64 sumt = 0;
+        for (u32 j = 0; j < nout; ++j) {
+            t[j] = j < n ? (u32)terms(j) : 1u;
+            tk.set(j, t[j] * KC);
+            sumt += t[j];
+        }
+        return sumt;
+    }
+};
+
+// The tile of a workgroup, by value in the kernel arguments (uniform, scalar loads): workgroup (element group, unit
+// chunk, q part) owns elements [group * G, + G), units [chunk * KC, + KC) of every term and entries [qpart * QP, + QP).
+struct SelTile {
+    u64 last_mask;
+    u64 batch;                  // elements of this launch
+    u32 U, KC, G, QP, chunks, qparts, nblocks, xcd;
+    u32 base2, lbase;           // byte offsets of the second table set and of the decoded entries in the LDS
+    FastDiv dKC, dQP;
+
+    // Host: the plan's unit slices, parts of QP entries of a stream of Q, and groups of G elements.  G, or the larger of
+    // G and `rows` (k_uint_find's second tile dimension), is halved until one output's stream of a workgroup, G * rows *
+    // QP * max t_j * KC, stays below 2^32 (QP * t_j * KC <= T_j * U < 2^31: G = rows = 1 fits).  Returns the rows left.
+    template <u32 N>
+    u64 set(u64 n_bits, u32 units, const SubsetPlan &sp, u64 entries, u64 Q, const SelOutputs<N> &outs, u64 elements,
+            u64 rows = 1)
+    {
+        const u64 maxt = *std::max_element(outs.t, outs.t + outs.nout);
+        while (elements * rows > 1 && elements * rows * entries * maxt * sp.KC > 0xFFFFFFFFull)
+            elements >= rows ? elements /= 2 : rows /= 2;
+        last_mask = last_word_mask(n_bits);
+        U = units;
+        KC = sp.KC;
+        chunks = sp.chunks;
+        G = (u32)elements;
+        QP = (u32)entries;
+        qparts = (u32)((Q + entries - 1) / entries);
+        dKC = csgn_fastdiv_make(KC);
+        dQP = csgn_fastdiv_make(QP);
+        return rows;
+    }
+};
+
+// What blockIdx.x owns of a stream of Q entries, and its LDS: the tables (two sets at most) and the decoded entries.
+// Mid (k_uint_find's rows): the block id holds one more level of `mids` parts, between the unit chunk and the q part.
+template <typename Unit>
+struct SelBlock {
+    u64 e0;
+    u32 ne, k0, kc, q0, nq, mid;
+    Unit *tab, *tab2;
+    u32 *code;
+};
+
+template <typename Unit, bool Mid = false>
+__device__ inline SelBlock<Unit> sel_block(const SelTile &t, u32 Q, u32 mids = 1u)
+{
+    extern __shared__ __align__(16) unsigned char smem_raw[];
+    const u32 bid = t.xcd ? xcd_contiguous_block(blockIdx.x, t.nblocks) : blockIdx.x;
+    u32 gc = bid / t.qparts;
+    const u32 q0 = (bid - gc * t.qparts) * t.QP, mid = Mid ? gc % mids : 0u;
+    if (Mid)
+        gc /= mids;
+    const u32 group = gc / t.chunks, k0 = (gc - group * t.chunks) * t.KC;
+    const u64 e0 = (u64)group * t.G;
+    return {e0, (u32)min((u64)t.G, t.batch - e0), k0, min(t.KC, t.U - k0), q0, min(t.QP, Q - q0), mid,
+            reinterpret_cast<Unit *>(smem_raw), reinterpret_cast<Unit *>(smem_raw + t.base2),
+            reinterpret_cast<u32 *>(smem_raw + t.lbase)};
+}
+
+// The walk of output j's stream of a workgroup of `tiles` (its elements, times its rows in k_uint_find) by QP entries:
+// lanes take the unit fastest, then the value term, the entry and the tile, so one store instruction writes 64
+// consecutive units of one plane.  body(tile, qi, c, kk, at, v) gives unit kk of the slice of value term c of entry qi
+// its value v and its place `at` in the output, in units; false where the tile has none (a short last row part).
+template <typename Unit, u32 N, typename Body>
+__device__ __forceinline__ void sel_walk(const SelTile &t, const SelBlock<Unit> &b, const SelOutputs<N> &outs, u32 j,
+                                         u32 tiles, Body body)
+{
+    const FastDiv dtk = outs.tk.at(j);
+    Unit *o = reinterpret_cast<Unit *>(outs.out[j]);
+    const u32 len = tiles * t.QP * dtk.d;           // below 2^32 by SelTile::set
+    for (u32 l = threadIdx.x; l < len; l += 256u) {
+        const u32 en = csgn_fastdiv(l, dtk), rem = l - en * dtk.d;
+        const u32 c = csgn_fastdiv(rem, t.dKC), kk = rem - c * t.KC;
+        const u32 tile = csgn_fastdiv(en, t.dQP), qi = en - tile * t.QP;
+        if (qi >= b.nq || kk >= b.kc)
+            continue;
+        u64 at;
+        Unit v;
+        if (body(tile, qi, c, kk, at, v))
+            unit_store<Unit, true>(o + at, v);
+    }
+}
+
+// ------------------------------------------------------------------------------ host side
+
+// The LDS of fresh planes: the tables of G elements (their layout into `first`), then, with G2, a second set for G2
+// elements (into `second`), then the QP decoded entries.  Sets the tile's offsets; returns the bytes.
+inline u32 sel_lds_layout(SelTile &t, SubsetPlan sp, SubsetTables &first, u32 G2 = 0, SubsetTables *second = nullptr)
+{
+    t.base2 = t.lbase = (sp.layout(t.G) + 15u) & ~15u;
+    first = sp.t;
+    if (G2) {
+        t.lbase = (t.base2 + sp.layout(G2) + 15u) & ~15u;
+        *second = sp.t;
+    }
+    return t.lbase + t.QP * 4u;
+}
+
+// The launches of per_group workgroups for every G elements of the batch: offset(e0) points the arguments at element
+// e0, then the Fresh kernel runs with `lds` bytes (sel_lds_layout; 0: planes of several terms) or the other with none.
+template <typename Args, typename Offset>
+inline hipError_t sel_launch(void (*fresh)(Args), void (*multi)(Args), Args &a, u32 lds, u64 max_blocks, u64 batch,
+                             u64 per_group, hipStream_t st, Offset offset)
+{
+    return launch_groups(max_blocks, batch, a.tile.G, per_group, [&](u64 e0, u64 ne, u32 nblocks) {
+        a.tile.batch = ne;
+        a.tile.nblocks = nblocks;
+        offset(e0);
+        if (lds)
+            fresh<<<dim3(nblocks), 256, lds, st>>>(a);
+        else
+            multi<<<dim3(nblocks), 256, 0, st>>>(a);
+    });
+}
+
+} // namespace
+
+} // namespace csgn

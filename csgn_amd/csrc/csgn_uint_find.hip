@@ -1,5 +1,5 @@
 // csgn_uint_find.hip -- an ENCRYPTED table looked up by ENCRYPTED key, every output plane and the membership bit in one
-// launch.  Hand-written CDNA4 (gfx950) HIP; shared helpers in csgn_device.h, design notes in DESIGN.md §4.19.
+// launch.  Hand-written CDNA4 (gfx950) HIP; the kernel skeleton in csgn_selector.h, design notes in DESIGN.md §4.19.
 //
 // The definition (include/csgn_hip.h, csgn_uint_find) is out_j = sum over r < rows, ascending, of EQ(y_r, x) * d_{r,j}
 // and member = sum over r of EQ(y_r, x): the equalTo chain of key row r (left) and the query (right) as the left
@@ -14,11 +14,9 @@
 // q, for EVERY output: it decodes its range once into an LDS list (Sq | Sk << 16) and builds the subset tables of
 // §4.15 (csgn_device.h) twice, for its elements' query planes and -- the "element" being the row -- for its rows' key
 // planes.  A written unit is then 2-6 LDS reads ANDed with one unit of the value row, which every query reads, so it
-// hits in L2.  Lanes walk one output's stream with the unit fastest, then the value term, q, the row and the element,
-// so one store instruction writes 64 consecutive units of one plane.  Multi-term planes take the digits per unit
-// straight from the planes (correct, not fast).
-#include "csgn_device.h"
+// hits in L2.  Multi-term planes take the digits per unit straight from the planes (correct, not fast).
 #include "csgn_hip.h"
+#include "csgn_selector.h"
 
 #include <algorithm>
 
@@ -31,99 +29,81 @@ constexpr u32 kMaxRange = 2048;         // entries of q one workgroup decodes (8
 constexpr u64 kPartUnits = 8192;        // units a workgroup writes at least, where the shape has them
 constexpr u32 kMaxTile = 64;            // elements, and rows, of a workgroup at most
 
-// By value in the kernel arguments (uniform, scalar loads).  A workgroup is (element group, unit chunk, row part, q
-// part): elements [group * G, + G), units [chunk * KC, + KC) of every term, rows [rpart * RP, + RP) and entries
-// [qpart * QP, + QP) of every row's block.  Output w is member (one term per entry, no value factor).
+// By value in the kernel arguments (uniform, scalar loads).  The tile has one more level, between the unit chunk and
+// the q part: rows [rpart * RP, + RP); the stream is every row's block of P entries.  Output w is member (one term per
+// entry, no value factor).
 struct FindArgs {
+    SelTile tile;
+    SelOutputs<kFindMaxPlanes + 1> outs;
     const void *keys[kFindMaxKey];
     const void *query[kFindMaxKey];
     const void *values[kFindMaxPlanes];
-    void *out[kFindMaxPlanes + 1];
-    u32 t[kFindMaxPlanes + 1];                                          // terms of value plane j; 1 for member
-    FastDivTable<kFindMaxPlanes + 1> tk;                                // t_j * KC
     u32 u[kFindMaxKey], s[kFindMaxKey];
-    u64 last_mask;
-    u64 batch;                  // elements of this launch
     u64 E;                      // rows * P of the whole call: T_j = t_j * E
     u32 rows;                   // rows of this launch
-    u32 P, v, w, nout;
-    u32 U, KC, G, RP, QP, chunks, rparts, qparts, nblocks, xcd;
-    SubsetTables tq, tr;        // the query tables of G elements, the key tables of RP rows
-    u32 kbase, lbase;           // byte offsets of the key tables and of the decoded range in the LDS
-    FastDiv dKC, dQP, dRP;
+    u32 P, v, w;
+    u32 RP, rparts;
+    SubsetTables tq, tr;        // the query tables of G elements, the key tables of RP rows (the tile's second set)
+    FastDiv dRP;
 };
+static_assert(sizeof(FindArgs) <= 4096, "the kernel arguments of k_uint_find pass the 4 KiB limit");
 
 template <typename Unit, bool Fresh>
 __global__ void __launch_bounds__(256) k_uint_find(FindArgs a)
 {
-    extern __shared__ __align__(16) unsigned char smem_raw[];
-    Unit *tabq = reinterpret_cast<Unit *>(smem_raw);
-    Unit *tabk = reinterpret_cast<Unit *>(smem_raw + a.kbase);
-    u32 *code = reinterpret_cast<u32 *>(smem_raw + a.lbase);
-    const u32 bid = a.xcd ? xcd_contiguous_block(blockIdx.x, a.nblocks) : blockIdx.x;
-    const u32 gcr = bid / a.qparts, qpart = bid - gcr * a.qparts;
-    const u32 gc = gcr / a.rparts, rpart = gcr - gc * a.rparts;
-    const u32 group = gc / a.chunks, chunk = gc - group * a.chunks;
-    const u64 e0 = (u64)group * a.G;
-    const u32 ne = (u32)min((u64)a.G, a.batch - e0);
-    const u32 k0 = chunk * a.KC, kc = min(a.KC, a.U - k0);
-    const u32 r0 = rpart * a.RP, nr = min(a.RP, a.rows - r0);
-    const u32 q0 = qpart * a.QP, nq = min(a.QP, a.P - q0);
+    const SelTile &t = a.tile;
+    const SelBlock<Unit> b = sel_block<Unit, true>(t, a.P, a.rparts);
+    const u32 r0 = b.mid * a.RP, nr = min(a.RP, a.rows - r0);
 
     if (Fresh) {
         // the range of q: Sq in the low 16 bits, Sk in the high 16 (published by the tables' closing barrier)
-        for (u32 i = threadIdx.x; i < nq; i += 256u) {
-            u32 q = q0 + i, Sk = 0, Sq = 0;
+        for (u32 i = threadIdx.x; i < b.nq; i += 256u) {
+            u32 q = b.q0 + i, Sk = 0, Sq = 0;
             for (u32 k = a.v; k-- > 0u;) {      // k = 0 is the slowest digit: 0 = y_k, 1 = x_k, 2 = ONE
                 const u32 nx = q / 3u, dg = q - nx * 3u;
                 q = nx;
                 Sk |= (dg == 0u ? 1u : 0u) << k;
                 Sq |= (dg == 1u ? 1u : 0u) << k;
             }
-            code[i] = Sq | (Sk << 16);
+            b.code[i] = Sq | (Sk << 16);
         }
-        subset_build(tabq, a.tq, a.query, a.G, a.KC, a.dKC, a.U, a.last_mask, e0, ne, k0, kc);
-        subset_build(tabk, a.tr, a.keys, a.RP, a.KC, a.dKC, a.U, a.last_mask, (u64)r0, nr, k0, kc);
+        subset_build(b.tab, a.tq, a.query, t.G, t.KC, t.dKC, t.U, t.last_mask, b.e0, b.ne, b.k0, b.kc);
+        subset_build(b.tab2, a.tr, a.keys, a.RP, t.KC, t.dKC, t.U, t.last_mask, (u64)r0, nr, b.k0, b.kc);
     }
 
-    for (u32 j = 0; j < a.nout; ++j) {
-        const FastDiv dtk = a.tk.at(j);
-        const u32 tj = a.t[j];
+    for (u32 j = 0; j < a.outs.nout; ++j) {
+        const u32 tj = a.outs.t[j];
         const u64 Tj = (u64)tj * a.E;
         const bool has_value = j < a.w;
         const Unit *d = reinterpret_cast<const Unit *>(has_value ? a.values[j] : nullptr);
-        Unit *o = reinterpret_cast<Unit *>(a.out[j]);
-        const u32 len = ne * a.RP * a.QP * dtk.d;   // (element, row, q, value term, unit), below 2^32 by the plan
-        for (u32 l = threadIdx.x; l < len; l += 256u) {
-            const u32 erq = csgn_fastdiv(l, dtk), rem = l - erq * dtk.d;
-            const u32 c = csgn_fastdiv(rem, a.dKC), kk = rem - c * a.KC;
-            const u32 er = csgn_fastdiv(erq, a.dQP), qi = erq - er * a.QP;
+        // a tile is (element, row), the row the faster
+        sel_walk<Unit>(t, b, a.outs, j, b.ne * a.RP, [&](u32 er, u32 qi, u32 c, u32 kk, u64 &at, Unit &v) {
             const u32 el = csgn_fastdiv(er, a.dRP), rr = er - el * a.RP;
-            if (qi >= nq || kk >= kc || rr >= nr)
-                continue;
-            const u32 k = k0 + kk, r = r0 + rr, q = q0 + qi;
-            const u64 e = e0 + el;
-            Unit v;
+            if (rr >= nr)
+                return false;
+            const u32 k = b.k0 + kk, r = r0 + rr, q = b.q0 + qi;
+            const u64 e = b.e0 + el;
             if (Fresh) {
-                const u32 cd = code[qi];
-                v = subset_and(tabq, a.tq, el, cd & 0xFFFFu, a.KC, kk) & subset_and(tabk, a.tr, rr, cd >> 16, a.KC, kk);
+                const u32 cd = b.code[qi];
+                v = subset_and(b.tab, a.tq, el, cd & 0xFFFFu, t.KC, kk) & subset_and(b.tab2, a.tr, rr, cd >> 16, t.KC, kk);
             } else {
-                v = one_unit(Unit(), k, a.U, a.last_mask);
+                v = one_unit(Unit(), k, t.U, t.last_mask);
                 u32 in = q;
                 for (u32 kb = a.v; kb-- > 0u;) {
                     const u32 uk = a.u[kb], sk = a.s[kb], R = uk + sk + 1u;
                     const u32 nx = in / R, dg = in - nx * R;
                     in = nx;
                     if (dg < uk)
-                        v &= reinterpret_cast<const Unit *>(a.keys[kb])[((u64)r * uk + dg) * a.U + k];
+                        v &= reinterpret_cast<const Unit *>(a.keys[kb])[((u64)r * uk + dg) * t.U + k];
                     else if (dg < uk + sk)
-                        v &= reinterpret_cast<const Unit *>(a.query[kb])[(e * sk + (dg - uk)) * a.U + k];
+                        v &= reinterpret_cast<const Unit *>(a.query[kb])[(e * sk + (dg - uk)) * t.U + k];
                 }
             }
             if (has_value)
-                v &= d[((u64)r * tj + c) * a.U + k];
-            unit_store<Unit, true>(o + (e * Tj + ((u64)r * a.P + q) * tj + c) * a.U + k, v);
-        }
+                v &= d[((u64)r * tj + c) * t.U + k];
+            at = (e * Tj + ((u64)r * a.P + q) * tj + c) * t.U + k;
+            return true;
+        });
     }
 }
 
@@ -154,37 +134,25 @@ hipError_t find_fused(u64 n_bits, u64 batch, u64 v, const u64 *const *query, con
     FindArgs a = {};
     a.v = (u32)v;
     a.w = (u32)w;
-    a.nout = (u32)(w + (member ? 1 : 0));
-    a.U = U;
     a.P = (u32)P;
     a.E = rows * P;
-    a.last_mask = last_word_mask(n_bits);
     bool fresh = true;
     for (u32 k = 0; k < v; ++k) {
         a.u[k] = (u32)u[k];
         a.s[k] = (u32)s[k];
         fresh = fresh && u[k] == 1 && s[k] == 1;
     }
-    u64 sumt = 0, maxt = 1;
-    for (u32 j = 0; j < a.nout; ++j) {
-        a.t[j] = j < w ? (u32)t[j] : 1u;
-        sumt += a.t[j];
-        maxt = std::max<u64>(maxt, a.t[j]);
-    }
-    SubsetPlan sp = subset_plan(fresh ? (u32)v : 0, U, (u32)sizeof(Unit), kTableBudget);
-    a.KC = sp.KC;
-    a.chunks = sp.chunks;
+    const SubsetPlan sp = subset_plan(fresh ? (u32)v : 0, U, (u32)sizeof(Unit), kTableBudget);
+    const u64 sumt = a.outs.fill(w, [&](u32 j) { return t[j]; }, member != nullptr, sp.KC);
     // the range of q a workgroup decodes, then elements and rows in turn until it has kPartUnits to write and four
     // times what its tables cost to build
     const u64 qparts = (P + kMaxRange - 1) / kMaxRange;
     const u64 QP = (P + qparts - 1) / qparts;
-    a.QP = (u32)QP;
-    a.qparts = (u32)((P + QP - 1) / QP);
     const u64 capG = std::min<u64>({sp.max_G, batch, kMaxTile}), capR = std::min<u64>({sp.max_G, rows, kMaxTile});
-    const u64 cell = QP * sumt * a.KC;              // units of one (element, row) of a workgroup
+    const u64 cell = QP * sumt * sp.KC;             // units of one (element, row) of a workgroup
     u64 G = 1, RP = 1;
     for (;;) {
-        const u64 build = (G + RP) * sp.entries * a.KC;
+        const u64 build = (G + RP) * sp.entries * sp.KC;
         if (G * RP * cell >= std::max<u64>(kPartUnits, 4 * build))
             break;
         const bool moreG = 2 * G <= capG, moreR = 2 * RP <= capR;
@@ -195,33 +163,14 @@ hipError_t find_fused(u64 n_bits, u64 batch, u64 v, const u64 *const *query, con
         else
             break;
     }
-    // one output's stream of a workgroup, G * RP * QP * t_j * KC, stays below 2^32 (QP * t_j * KC <= T_j * U < 2^31)
-    while (G * RP > 1 && G * RP * QP * maxt * a.KC > 0xFFFFFFFFull) {
-        if (G >= RP)
-            G /= 2;
-        else
-            RP /= 2;
-    }
-    a.G = (u32)G;
+    RP = a.tile.set(n_bits, U, sp, QP, P, a.outs, G, RP);      // the guard may halve G (a.tile.G) and RP
     a.RP = (u32)RP;
-    a.dKC = csgn_fastdiv_make(a.KC);
-    a.dQP = csgn_fastdiv_make(a.QP);
     a.dRP = csgn_fastdiv_make(a.RP);
-    for (u32 j = 0; j < a.nout; ++j)
-        a.tk.set(j, a.t[j] * a.KC);
-    u32 lds = 0;
-    if (fresh) {
-        SubsetPlan spq = sp, spr = sp;
-        a.kbase = (spq.layout(a.G) + 15u) & ~15u;
-        a.lbase = (a.kbase + spr.layout(a.RP) + 15u) & ~15u;
-        lds = a.lbase + a.QP * 4u;
-        a.tq = spq.t;
-        a.tr = spr.t;
-    }
-    a.xcd = stream_xcd(batch * rows * P * sumt * U);
+    const u32 lds = fresh ? sel_lds_layout(a.tile, sp, a.tq, a.RP, &a.tr) : 0u;
+    a.tile.xcd = stream_xcd(batch * rows * P * sumt * U);
     // rows of one launch: as many parts as a launch's workgroups allow (every shape within memory: all of them), or
     // as knob uint_find_rparts says, which is how the tests reach the launches from row rl > 0 on
-    const u64 per_rpart = (u64)a.chunks * a.qparts;
+    const u64 per_rpart = (u64)a.tile.chunks * a.tile.qparts;
     const int forced_rparts = tune(TUNE_UINT_FIND_RPARTS);
     const u64 max_blocks = launch_blocks();
     const u64 launch_rows = (forced_rparts > 0 ? (u64)forced_rparts : std::max<u64>(1, max_blocks / per_rpart)) * RP;
@@ -229,22 +178,17 @@ hipError_t find_fused(u64 n_bits, u64 batch, u64 v, const u64 *const *query, con
         const u64 nrows = std::min(launch_rows, rows - rl);
         a.rows = (u32)nrows;
         a.rparts = (u32)((nrows + RP - 1) / RP);
-        const hipError_t err = launch_groups(max_blocks, batch, a.G, per_rpart * a.rparts, [&](u64 e0, u64 ne, u32 nblocks) {
-            a.batch = ne;
+        const hipError_t err = sel_launch(k_uint_find<Unit, true>, k_uint_find<Unit, false>, a, lds, max_blocks, batch,
+                                          per_rpart * a.rparts, st, [&](u64 e0) {
             for (u32 k = 0; k < v; ++k) {
                 a.query[k] = reinterpret_cast<const Unit *>(query[k]) + e0 * s[k] * U;
                 a.keys[k] = reinterpret_cast<const Unit *>(keys[k]) + rl * u[k] * U;
             }
-            for (u32 j = 0; j < a.nout; ++j) {
+            for (u32 j = 0; j < a.outs.nout; ++j) {
                 if (j < w)                          // member, output w, has no value plane
                     a.values[j] = reinterpret_cast<const Unit *>(values[j]) + rl * t[j] * U;
-                a.out[j] = reinterpret_cast<Unit *>(j < w ? out[j] : member) + (e0 * a.E + rl * P) * a.t[j] * U;
+                a.outs.out[j] = reinterpret_cast<Unit *>(j < w ? out[j] : member) + (e0 * a.E + rl * P) * a.outs.t[j] * U;
             }
-            a.nblocks = nblocks;
-            if (fresh)
-                k_uint_find<Unit, true><<<dim3(a.nblocks), 256, lds, st>>>(a);
-            else
-                k_uint_find<Unit, false><<<dim3(a.nblocks), 256, 0, st>>>(a);
         });
         if (err != hipSuccess)
             return err;

@@ -1,6 +1,6 @@
 // csgn_uint_lt_select.hip -- selection by an ENCRYPTED comparison: every plane of min, max and both payloads of a
-// compare-exchange, and the comparison itself, in one launch.  Hand-written CDNA4 (gfx950) HIP; shared helpers in
-// csgn_device.h, design notes in DESIGN.md §4.22.
+// compare-exchange, and the comparison itself, in one launch.  Hand-written CDNA4 (gfx950) HIP; the kernel skeleton in
+// csgn_selector.h, design notes in DESIGN.md §4.22.
 //
 // The definition (include/csgn_hip.h, csgn_uint_lt_select) is out_i = (L * (X_i + Y_i)) + Y_i with L = lessThan(a, b),
 // l_0 = (a_0 + ONE) * b_0 and l_j = ((a_j + b_j) * (b_j + l_{j-1})) + l_{j-1}: the comparison is the LEFT operand of
@@ -13,12 +13,10 @@
 // subsets of the element's a planes and b planes.  A workgroup owns G elements, a slice of KC units of every term and
 // one range of q, for EVERY output and for the comparison: it decodes its range once into an LDS list (Sa | Sb << 16)
 // and builds the subset tables of §4.15 (csgn_device.h) twice, for its elements' a planes and their b planes.  A
-// written unit is then 2-6 LDS reads ANDed with one unit of X_i or Y_i.  Lanes walk one output's stream with the unit
-// fastest, then the value term, q and the element, so one store instruction writes 64 consecutive units of one plane.
-// Multi-term a or b planes take the decode per unit straight from the planes (correct, not fast); multi-term X and Y
-// stay on the fast path.
-#include "csgn_device.h"
+// written unit is then 2-6 LDS reads ANDed with one unit of X_i or Y_i.  Multi-term a or b planes take the decode per
+// unit straight from the planes (correct, not fast); multi-term X and Y stay on the fast path.
 #include "csgn_hip.h"
+#include "csgn_selector.h"
 
 #include <algorithm>
 
@@ -32,50 +30,34 @@ constexpr u64 kPartUnits = 8192;        // units a workgroup writes at least, wh
 constexpr u64 kOutUnits = 2048;         // ... and of every output (8 units a lane)
 constexpr u32 kMaxTile = 64;            // elements of a workgroup at most
 
-// By value in the kernel arguments (uniform, scalar loads).  A workgroup is (element group, unit chunk, q part):
-// elements [group * G, + G), units [chunk * KC, + KC) of every term and entries [qpart * QP, + QP) of L.  Output nsel,
-// when there is one, is the comparison itself (one term per entry, no value factor, no tail).
+// By value in the kernel arguments (uniform, scalar loads).  The stream is L; output i has the tx_i + ty_i terms of
+// X_i | Y_i.  Output nsel, when there is one, is the comparison itself (one term per entry, no value factor, no tail).
 struct LtSelArgs {
+    SelTile tile;
+    SelOutputs<kLtSelMaxOut + 1> outs;
     const void *a[kLtSelMaxWidth];
     const void *b[kLtSelMaxWidth];
     const void *x[kLtSelMaxOut];
     const void *y[kLtSelMaxOut];
-    void *out[kLtSelMaxOut + 1];
     u32 tx[kLtSelMaxOut + 1];                                           // terms of X_i
-    u32 ts[kLtSelMaxOut + 1];                                           // tx_i + ty_i; 1 for the comparison
-    FastDivTable<kLtSelMaxOut + 1> tk;                                  // ts_i * KC
     u32 ta[kLtSelMaxWidth], tb[kLtSelMaxWidth];
     FastDivTable<kLtSelMaxWidth> inner;                                 // tb_j + L_{j-1}; tb_0 at j = 0
-    u64 last_mask;
-    u64 batch;                  // elements of this launch
-    u32 L, w, nsel, nout;       // nout = nsel + (the comparison is written)
-    u32 U, KC, G, QP, chunks, qparts, nblocks, xcd;
-    SubsetTables tabs;          // the a tables of G elements; the b tables have the same layout
-    u32 bbase, lbase;           // byte offsets of the b tables and of the decoded range in the LDS
-    FastDiv dKC, dQP;
+    u32 L, w, nsel;
+    SubsetTables tabs;          // the a tables of G elements; the b tables, the tile's second set, have the same layout
 };
 static_assert(sizeof(LtSelArgs) <= 4096, "the kernel arguments of k_uint_lt_select pass the 4 KiB limit");
 
 template <typename Unit, bool Fresh>
 __global__ void __launch_bounds__(256) k_uint_lt_select(LtSelArgs a)
 {
-    extern __shared__ __align__(16) unsigned char smem_raw[];
-    Unit *taba = reinterpret_cast<Unit *>(smem_raw);
-    Unit *tabb = reinterpret_cast<Unit *>(smem_raw + a.bbase);
-    u32 *code = reinterpret_cast<u32 *>(smem_raw + a.lbase);
-    const u32 bid = a.xcd ? xcd_contiguous_block(blockIdx.x, a.nblocks) : blockIdx.x;
-    const u32 gc = bid / a.qparts, qpart = bid - gc * a.qparts;
-    const u32 group = gc / a.chunks, chunk = gc - group * a.chunks;
-    const u64 e0 = (u64)group * a.G;
-    const u32 ne = (u32)min((u64)a.G, a.batch - e0);
-    const u32 k0 = chunk * a.KC, kc = min(a.KC, a.U - k0);
-    const u32 q0 = qpart * a.QP, nq = q0 < a.L ? min(a.QP, a.L - q0) : 0u;
+    const SelTile &t = a.tile;
+    const SelBlock<Unit> b = sel_block<Unit>(t, a.L);
 
     if (Fresh) {
         // the range of q: Sa in the low 16 bits, Sb in the high 16 (published by the tables' closing barrier); with
         // fresh planes inner_j = 3^j, so the term of (a_j + b_j) is a comparison
-        for (u32 i = threadIdx.x; i < nq; i += 256u) {
-            u32 q = q0 + i, Sa = 0, Sb = 0;
+        for (u32 i = threadIdx.x; i < b.nq; i += 256u) {
+            u32 q = b.q0 + i, Sa = 0, Sb = 0;
             bool done = false;
             for (u32 j = a.w - 1u; j > 0u && !done; --j) {
                 const u32 in = a.inner.d[j];
@@ -98,35 +80,27 @@ __global__ void __launch_bounds__(256) k_uint_lt_select(LtSelArgs a)
                 Sa |= q == 0u ? 1u : 0u;
                 Sb |= 1u;
             }
-            code[i] = Sa | (Sb << 16);
+            b.code[i] = Sa | (Sb << 16);
         }
-        subset_build(taba, a.tabs, a.a, a.G, a.KC, a.dKC, a.U, a.last_mask, e0, ne, k0, kc);
-        subset_build(tabb, a.tabs, a.b, a.G, a.KC, a.dKC, a.U, a.last_mask, e0, ne, k0, kc);
+        subset_build(b.tab, a.tabs, a.a, t.G, t.KC, t.dKC, t.U, t.last_mask, b.e0, b.ne, b.k0, b.kc);
+        subset_build(b.tab2, a.tabs, a.b, t.G, t.KC, t.dKC, t.U, t.last_mask, b.e0, b.ne, b.k0, b.kc);
     }
 
-    for (u32 i = 0; i < a.nout; ++i) {
-        const FastDiv dtk = a.tk.at(i);
-        const u32 ts = a.ts[i], txi = a.tx[i], tyi = ts - txi;
+    for (u32 i = 0; i < a.outs.nout; ++i) {
+        const u32 ts = a.outs.t[i], txi = a.tx[i], tyi = ts - txi;
         const bool has_value = i < a.nsel;
         const u64 Ti = has_value ? (u64)a.L * ts + tyi : (u64)a.L;
         const Unit *X = reinterpret_cast<const Unit *>(has_value ? a.x[i] : nullptr);
         const Unit *Y = reinterpret_cast<const Unit *>(has_value ? a.y[i] : nullptr);
-        Unit *o = reinterpret_cast<Unit *>(a.out[i]);
-        const u32 len = ne * a.QP * dtk.d;          // (element, q, value term, unit), below 2^32 by the plan
-        for (u32 l = threadIdx.x; l < len; l += 256u) {
-            const u32 eq = csgn_fastdiv(l, dtk), rem = l - eq * dtk.d;
-            const u32 c = csgn_fastdiv(rem, a.dKC), kk = rem - c * a.KC;
-            const u32 el = csgn_fastdiv(eq, a.dQP), qi = eq - el * a.QP;
-            if (qi >= nq || kk >= kc)
-                continue;
-            const u32 k = k0 + kk, q = q0 + qi;
-            const u64 e = e0 + el;
-            Unit v;
+        sel_walk<Unit>(t, b, a.outs, i, b.ne, [&](u32 el, u32 qi, u32 c, u32 kk, u64 &at, Unit &v) {
+            const u32 k = b.k0 + kk, q = b.q0 + qi;
+            const u64 e = b.e0 + el;
             if (Fresh) {
-                const u32 cd = code[qi];
-                v = subset_and(taba, a.tabs, el, cd & 0xFFFFu, a.KC, kk) & subset_and(tabb, a.tabs, el, cd >> 16, a.KC, kk);
+                const u32 cd = b.code[qi];
+                v = subset_and(b.tab, a.tabs, el, cd & 0xFFFFu, t.KC, kk) &
+                    subset_and(b.tab2, a.tabs, el, cd >> 16, t.KC, kk);
             } else {
-                v = one_unit(Unit(), k, a.U, a.last_mask);
+                v = one_unit(Unit(), k, t.U, t.last_mask);
                 u32 in = q;
                 bool done = false;
                 for (u32 j = a.w - 1u; j > 0u && !done; --j) {
@@ -138,10 +112,10 @@ __global__ void __launch_bounds__(256) k_uint_lt_select(LtSelArgs a)
                     }
                     const u32 p = csgn_fastdiv(in, di), cc = in - p * di.d;
                     const Unit *B = reinterpret_cast<const Unit *>(a.b[j]);
-                    v &= p < taj ? reinterpret_cast<const Unit *>(a.a[j])[(e * taj + p) * a.U + k]
-                                 : B[(e * tbj + (p - taj)) * a.U + k];
+                    v &= p < taj ? reinterpret_cast<const Unit *>(a.a[j])[(e * taj + p) * t.U + k]
+                                 : B[(e * tbj + (p - taj)) * t.U + k];
                     if (cc < tbj) {
-                        v &= B[(e * tbj + cc) * a.U + k];
+                        v &= B[(e * tbj + cc) * t.U + k];
                         done = true;
                     } else {
                         in = cc - tbj;
@@ -151,24 +125,26 @@ __global__ void __launch_bounds__(256) k_uint_lt_select(LtSelArgs a)
                     const FastDiv di = a.inner.at(0);
                     const u32 ta0 = a.ta[0], p = csgn_fastdiv(in, di), cc = in - p * di.d;
                     if (p < ta0)
-                        v &= reinterpret_cast<const Unit *>(a.a[0])[(e * ta0 + p) * a.U + k];
-                    v &= reinterpret_cast<const Unit *>(a.b[0])[(e * di.d + cc) * a.U + k];
+                        v &= reinterpret_cast<const Unit *>(a.a[0])[(e * ta0 + p) * t.U + k];
+                    v &= reinterpret_cast<const Unit *>(a.b[0])[(e * di.d + cc) * t.U + k];
                 }
             }
             if (has_value)
-                v &= c < txi ? X[(e * txi + c) * a.U + k] : Y[(e * tyi + (c - txi)) * a.U + k];
-            unit_store<Unit, true>(o + (e * Ti + (u64)q * ts + c) * a.U + k, v);
-        }
-        if (has_value && qpart == 0u) {             // the tail: Y_i's terms, copied
-            const u32 tail = ne * tyi * a.KC;
+                v &= c < txi ? X[(e * txi + c) * t.U + k] : Y[(e * tyi + (c - txi)) * t.U + k];
+            at = (e * Ti + (u64)q * ts + c) * t.U + k;
+            return true;
+        });
+        if (has_value && b.q0 == 0u) {              // the tail: Y_i's terms, copied
+            Unit *o = reinterpret_cast<Unit *>(a.outs.out[i]);
+            const u32 tail = b.ne * tyi * t.KC;
             for (u32 l = threadIdx.x; l < tail; l += 256u) {
-                const u32 row = csgn_fastdiv(l, a.dKC), kk = l - row * a.KC;
+                const u32 row = csgn_fastdiv(l, t.dKC), kk = l - row * t.KC;
                 const u32 el = row / tyi, c = row - el * tyi;
-                if (kk >= kc)
+                if (kk >= b.kc)
                     continue;
-                const u64 e = e0 + el;
-                const u32 k = k0 + kk;
-                unit_store<Unit, true>(o + (e * Ti + (u64)a.L * ts + c) * a.U + k, Y[(e * tyi + c) * a.U + k]);
+                const u64 e = b.e0 + el;
+                const u32 k = b.k0 + kk;
+                unit_store<Unit, true>(o + (e * Ti + (u64)a.L * ts + c) * t.U + k, Y[(e * tyi + c) * t.U + k]);
             }
         }
     }
@@ -224,10 +200,7 @@ hipError_t lt_select_fused(u64 n_bits, u64 batch, u64 w, const u64 *const *pa, c
     const u64 L = Ls[w - 1];
     a.w = (u32)w;
     a.nsel = (u32)n_out;
-    a.nout = (u32)(n_out + (less ? 1 : 0));
-    a.U = U;
     a.L = (u32)L;
-    a.last_mask = last_word_mask(n_bits);
     bool fresh = true;
     for (u32 j = 0; j < w; ++j) {
         a.ta[j] = (u32)ta[j];
@@ -235,68 +208,41 @@ hipError_t lt_select_fused(u64 n_bits, u64 batch, u64 w, const u64 *const *pa, c
         a.inner.set(j, (u32)(tb[j] + (j ? Ls[j - 1] : 0)));
         fresh = fresh && ta[j] == 1 && tb[j] == 1;
     }
-    u64 sumt = 0, maxt = 1;
-    for (u32 i = 0; i < a.nout; ++i) {
-        a.tx[i] = i < n_out ? (u32)tx[i] : 0u;
-        a.ts[i] = i < n_out ? (u32)(tx[i] + ty[i]) : 1u;
-        sumt += a.ts[i];
-        maxt = std::max<u64>(maxt, a.ts[i]);
-    }
-    SubsetPlan sp = subset_plan(fresh ? (u32)w : 0, U, (u32)sizeof(Unit), kTableBudget);
-    a.KC = sp.KC;
-    a.chunks = sp.chunks;
+    const SubsetPlan sp = subset_plan(fresh ? (u32)w : 0, U, (u32)sizeof(Unit), kTableBudget);
+    const u64 sumt = a.outs.fill(n_out, [&](u32 i) { return tx[i] + ty[i]; }, less != nullptr, sp.KC);
+    for (u32 i = 0; i < n_out; ++i)
+        a.tx[i] = (u32)tx[i];
     // The range of q a workgroup decodes: the shortest with which one element gives it kPartUnits to write, kOutUnits
     // per output (each output is a loop of its own, with its own scalar set-up) and four times what its two table sets
     // cost to build (both sets are per element, so that ratio does not depend on G) -- a batch of a few hundred
     // elements has no other source of workgroups -- then elements until it has as much.
-    const u64 part_units = std::max<u64>({kPartUnits, kOutUnits * a.nout, 8 * sp.entries * a.KC});
-    const u64 want_QP = std::min<u64>({(part_units + sumt * a.KC - 1) / (sumt * a.KC), (u64)kMaxRange, L});
+    const u64 part_units = std::max<u64>({kPartUnits, kOutUnits * a.outs.nout, 8 * sp.entries * sp.KC});
+    const u64 want_QP = std::min<u64>({(part_units + sumt * sp.KC - 1) / (sumt * sp.KC), (u64)kMaxRange, L});
     const u64 qparts = (L + want_QP - 1) / want_QP;
     const u64 QP = (L + qparts - 1) / qparts;
-    a.QP = (u32)QP;
-    a.qparts = (u32)((L + QP - 1) / QP);
     const u64 capG = std::min<u64>({sp.max_G, batch, kMaxTile});
-    const u64 cell = QP * sumt * a.KC;              // units of one element of a workgroup
+    const u64 cell = QP * sumt * sp.KC;             // units of one element of a workgroup
     u64 G = 1;
     while (G * cell < part_units && 2 * G <= capG)
         G *= 2;
-    // one output's stream of a workgroup, G * QP * ts_i * KC, stays below 2^32 (QP * ts_i * KC <= T_i * U < 2^31)
-    while (G > 1 && G * QP * maxt * a.KC > 0xFFFFFFFFull)
-        G /= 2;
-    a.G = (u32)G;
-    a.dKC = csgn_fastdiv_make(a.KC);
-    a.dQP = csgn_fastdiv_make(a.QP);
-    for (u32 i = 0; i < a.nout; ++i)
-        a.tk.set(i, a.ts[i] * a.KC);
-    u32 lds = 0;
-    if (fresh) {
-        a.bbase = (sp.layout(a.G) + 15u) & ~15u;
-        a.lbase = 2u * a.bbase;
-        lds = a.lbase + a.QP * 4u;
-        a.tabs = sp.t;
-    }
-    a.xcd = stream_xcd(batch * (L * sumt) * U);
-    const u64 per_group = (u64)a.chunks * a.qparts;
-    return launch_groups(launch_blocks(), batch, a.G, per_group, [&](u64 e0, u64 ne, u32 nblocks) {
-        a.batch = ne;
+    a.tile.set(n_bits, U, sp, QP, L, a.outs, G);
+    const u32 lds = fresh ? sel_lds_layout(a.tile, sp, a.tabs, a.tile.G, &a.tabs) : 0u;    // one layout, both sets
+    a.tile.xcd = stream_xcd(batch * (L * sumt) * U);
+    return sel_launch(k_uint_lt_select<Unit, true>, k_uint_lt_select<Unit, false>, a, lds, launch_blocks(), batch,
+                      (u64)a.tile.chunks * a.tile.qparts, st, [&](u64 e0) {
         for (u32 j = 0; j < w; ++j) {
             a.a[j] = reinterpret_cast<const Unit *>(pa[j]) + e0 * ta[j] * U;
             a.b[j] = reinterpret_cast<const Unit *>(pb[j]) + e0 * tb[j] * U;
         }
-        for (u32 i = 0; i < a.nout; ++i) {
+        for (u32 i = 0; i < a.outs.nout; ++i) {
             if (i < n_out) {                        // the comparison, output n_out, has no value planes
                 a.x[i] = reinterpret_cast<const Unit *>(x[i]) + e0 * tx[i] * U;
                 a.y[i] = reinterpret_cast<const Unit *>(y[i]) + e0 * ty[i] * U;
-                a.out[i] = reinterpret_cast<Unit *>(out[i]) + e0 * (L * a.ts[i] + ty[i]) * U;
+                a.outs.out[i] = reinterpret_cast<Unit *>(out[i]) + e0 * (L * a.outs.t[i] + ty[i]) * U;
             } else {
-                a.out[i] = reinterpret_cast<Unit *>(less) + e0 * L * U;
+                a.outs.out[i] = reinterpret_cast<Unit *>(less) + e0 * L * U;
             }
         }
-        a.nblocks = nblocks;
-        if (fresh)
-            k_uint_lt_select<Unit, true><<<dim3(a.nblocks), 256, lds, st>>>(a);
-        else
-            k_uint_lt_select<Unit, false><<<dim3(a.nblocks), 256, 0, st>>>(a);
     });
 }
 

@@ -1,5 +1,5 @@
 // csgn_uint_read.hip -- an ENCRYPTED table read at an ENCRYPTED index, every output plane in one launch.
-// Hand-written CDNA4 (gfx950) HIP; shared helpers in csgn_device.h, design notes in DESIGN.md §4.17.
+// Hand-written CDNA4 (gfx950) HIP; the kernel skeleton in csgn_selector.h, design notes in DESIGN.md §4.17.
 //
 // The definition (include/csgn_hip.h, csgn_uint_read) is out_j = sum over r < rows, ascending, of EQ(x, r) * d_{r,j}:
 // csgn_uint_plain's EQ row with k = r as the left operand, plane j of table element r as the right.  Term q * t_j + c of
@@ -17,12 +17,10 @@
 // and one range of the E stream, for EVERY output plane: it builds the subset tables of §4.15 (csgn_device.h: one to
 // three, the AND of every subset of their planes) for its elements in LDS, decodes its range once into an LDS list of
 // (S, r), and every written unit is then 1-3 LDS reads ANDed with one unit of the table row -- a row every element
-// reads, so it hits in L2.  The table build and the decode are spent on all `w` outputs.  Lanes walk one output's
-// stream with the unit fastest, then the table term, the E index and the element, so one store instruction writes 64
-// consecutive units of one plane.  Multi-term index planes take the walk and the digits per unit straight from the
-// planes (correct, not fast).
-#include "csgn_device.h"
+// reads, so it hits in L2.  The table build and the decode are spent on all `w` outputs.  Multi-term index planes take
+// the walk and the digits per unit straight from the planes (correct, not fast).
 #include "csgn_hip.h"
+#include "csgn_selector.h"
 
 #include <algorithm>
 
@@ -34,25 +32,20 @@ constexpr u64 kLdsBudget = 32768;       // bytes of subset tables per workgroup
 constexpr u32 kMaxRange = 2048;         // E-stream entries one workgroup decodes (8 KB of LDS)
 constexpr u64 kPartUnits = 8192;        // units a workgroup writes at least, where the shape has them
 
-// By value in the kernel arguments (uniform, scalar loads).  A workgroup is (element group, unit chunk, part): it owns
-// elements [group * G, + G), units [chunk * KC, + KC) of every term and entries [part * QP, + QP) of the E stream.
+// By value in the kernel arguments (uniform, scalar loads); the stream is the E stream, output j has the terms of table
+// plane j.
 struct ReadArgs {
+    SelTile tile;
+    SelOutputs<kReadMaxPlanes> outs;
     const void *index[kReadMaxIndex];
     const void *table[kReadMaxPlanes];
-    void *out[kReadMaxPlanes];
-    u32 t[kReadMaxPlanes];                                              // terms of table plane j
-    FastDivTable<kReadMaxPlanes> tk;                                    // t_j * KC
     u64 F[kReadMaxIndex];       // prod over i < k of (2 s_i + 1): a whole subtree below bit k (saturated; read only
                                 // where the subtree lies below rows, so at most E)
     u32 s[kReadMaxIndex];
-    u64 last_mask;
-    u64 batch;                  // elements of this launch
-    u32 E, last_row, v, w;
-    u32 U, KC, G, QP, chunks, parts, nblocks, xcd;
+    u32 E, last_row, v;
     SubsetTables tabs;
-    u32 lbase;                  // byte offset of the decoded range in the LDS
-    FastDiv dKC, dQP;
 };
+static_assert(sizeof(ReadArgs) <= 4096, "the kernel arguments of k_uint_read pass the 4 KiB limit");
 
 // q < E: the row r holding entry q of the E stream, and q's index inside r's block (the walk)
 __device__ inline u32 read_walk(const ReadArgs &a, u64 q, u64 &in)
@@ -83,22 +76,14 @@ __device__ inline u32 read_walk(const ReadArgs &a, u64 q, u64 &in)
 template <typename Unit, bool Fresh>
 __global__ void __launch_bounds__(256) k_uint_read(ReadArgs a)
 {
-    extern __shared__ __align__(16) unsigned char smem_raw[];
-    Unit *tab = reinterpret_cast<Unit *>(smem_raw);
-    u32 *code = reinterpret_cast<u32 *>(smem_raw + a.lbase);
-    const u32 bid = a.xcd ? xcd_contiguous_block(blockIdx.x, a.nblocks) : blockIdx.x;
-    const u32 gc = bid / a.parts, part = bid - gc * a.parts;
-    const u32 group = gc / a.chunks, chunk = gc - group * a.chunks;
-    const u64 e0 = (u64)group * a.G;
-    const u32 ne = (u32)min((u64)a.G, a.batch - e0);
-    const u32 k0 = chunk * a.KC, kc = min(a.KC, a.U - k0);
-    const u32 q0 = part * a.QP, nq = min(a.QP, a.E - q0);
+    const SelTile &t = a.tile;
+    const SelBlock<Unit> b = sel_block<Unit>(t, a.E);
 
     if (Fresh) {
         // the range of the E stream: S in the low 16 bits, r in the high 16 (published by the tables' closing barrier)
-        for (u32 i = threadIdx.x; i < nq; i += 256u) {
+        for (u32 i = threadIdx.x; i < b.nq; i += 256u) {
             u64 in;
-            const u32 r = read_walk(a, q0 + i, in);
+            const u32 r = read_walk(a, b.q0 + i, in);
             u32 S = r;
             for (u32 k = a.v; k-- > 0u;) {      // zero bits, the highest the fastest binary digit; digit 0 = x_k
                 if ((r >> k) & 1u)
@@ -107,47 +92,39 @@ __global__ void __launch_bounds__(256) k_uint_read(ReadArgs a)
                     S |= 1u << k;
                 in >>= 1;
             }
-            code[i] = S | (r << 16);
+            b.code[i] = S | (r << 16);
         }
-        subset_build(tab, a.tabs, a.index, a.G, a.KC, a.dKC, a.U, a.last_mask, e0, ne, k0, kc);
+        subset_build(b.tab, a.tabs, a.index, t.G, t.KC, t.dKC, t.U, t.last_mask, b.e0, b.ne, b.k0, b.kc);
     }
 
-    for (u32 j = 0; j < a.w; ++j) {
-        const FastDiv dtk = a.tk.at(j);
-        const u32 tj = a.t[j];
+    for (u32 j = 0; j < a.outs.nout; ++j) {
+        const u32 tj = a.outs.t[j];
         const u64 Tj = (u64)tj * a.E;
         const Unit *d = reinterpret_cast<const Unit *>(a.table[j]);
-        Unit *o = reinterpret_cast<Unit *>(a.out[j]);
-        const u32 len = ne * a.QP * dtk.d;      // (element, E entry, table term, unit), below 2^32 by the plan
-        for (u32 l = threadIdx.x; l < len; l += 256u) {
-            const u32 eq = csgn_fastdiv(l, dtk), rem = l - eq * dtk.d;
-            const u32 c = csgn_fastdiv(rem, a.dKC), kk = rem - c * a.KC;
-            const u32 el = csgn_fastdiv(eq, a.dQP), qi = eq - el * a.QP;
-            if (qi >= nq || kk >= kc)
-                continue;
-            const u32 k = k0 + kk;
-            const u64 e = e0 + el, q = (u64)q0 + qi;
-            Unit v;
+        sel_walk<Unit>(t, b, a.outs, j, b.ne, [&](u32 el, u32 qi, u32 c, u32 kk, u64 &at, Unit &v) {
+            const u32 k = b.k0 + kk;
+            const u64 e = b.e0 + el, q = (u64)b.q0 + qi;
             u32 r;
             if (Fresh) {
-                const u32 cd = code[qi];
+                const u32 cd = b.code[qi];
                 r = cd >> 16;
-                v = subset_and(tab, a.tabs, el, cd & 0xFFFFu, a.KC, kk);
+                v = subset_and(b.tab, a.tabs, el, cd & 0xFFFFu, t.KC, kk);
             } else {
                 u64 in;
                 r = read_walk(a, q, in);
-                v = one_unit(Unit(), k, a.U, a.last_mask);
+                v = one_unit(Unit(), k, t.U, t.last_mask);
                 for (u32 kb = a.v; kb-- > 0u;) {
                     const u64 s = a.s[kb], R = ((r >> kb) & 1u) ? s : s + 1u;
                     const u64 dg = in % R;
                     in /= R;
                     if (dg < s)
-                        v &= reinterpret_cast<const Unit *>(a.index[kb])[(e * s + dg) * a.U + k];
+                        v &= reinterpret_cast<const Unit *>(a.index[kb])[(e * s + dg) * t.U + k];
                 }
             }
-            v &= d[((u64)r * tj + c) * a.U + k];
-            unit_store<Unit, true>(o + ((e * Tj) + q * tj + c) * a.U + k, v);
-        }
+            v &= d[((u64)r * tj + c) * t.U + k];
+            at = ((e * Tj) + q * tj + c) * t.U + k;
+            return true;
+        });
     }
 }
 
@@ -182,11 +159,8 @@ hipError_t read_fused(u64 n_bits, u64 batch, u64 v, const u64 *const *index, con
 {
     ReadArgs a = {};
     a.v = (u32)v;
-    a.w = (u32)w;
-    a.U = U;
     a.E = (u32)E;
     a.last_row = (u32)(rows - 1);
-    a.last_mask = last_word_mask(n_bits);
     bool fresh = true;
     u64 f = 1;
     for (u32 k = 0; k < v; ++k) {
@@ -195,56 +169,31 @@ hipError_t read_fused(u64 n_bits, u64 batch, u64 v, const u64 *const *index, con
         f = sat_mul(f, 2 * s[k] + 1);
         fresh = fresh && s[k] == 1;
     }
-    u64 sumt = 0, maxt = 0;
-    for (u32 j = 0; j < w; ++j) {
-        a.t[j] = (u32)t[j];
-        sumt += t[j];
-        maxt = std::max(maxt, t[j]);
-    }
-    SubsetPlan sp = subset_plan(fresh ? (u32)v : 0, U, (u32)sizeof(Unit), kLdsBudget);
-    a.KC = sp.KC;
-    a.chunks = sp.chunks;
+    const SubsetPlan sp = subset_plan(fresh ? (u32)v : 0, U, (u32)sizeof(Unit), kLdsBudget);
+    const u64 sumt = a.outs.fill(w, [&](u32 j) { return t[j]; }, false, sp.KC);
     // elements per workgroup: enough to give it kPartUnits to write, as many as the tables allow
-    const u64 elem_units = E * sumt * a.KC;
+    const u64 elem_units = E * sumt * sp.KC;
     u64 G = std::max<u64>(1, kPartUnits / elem_units);
     G = std::min<u64>({G, sp.max_G, batch, 64});
     G = std::max<u64>(G, 1);
     // parts of the E stream: each writes kPartUnits or four times its table build, and decodes at most kMaxRange
-    const u64 build = G * sp.entries * a.KC;
+    const u64 build = G * sp.entries * sp.KC;
     const u64 target = std::max<u64>(kPartUnits, 4 * build);
     u64 parts = std::max<u64>(1, G * elem_units / target);
     parts = std::max<u64>(parts, (E + kMaxRange - 1) / kMaxRange);
     parts = std::min<u64>(parts, E);
     const u64 QP = (E + parts - 1) / parts;
-    a.QP = (u32)QP;
-    a.parts = (u32)((E + QP - 1) / QP);
-    // one output's stream of a workgroup, G * QP * t_j * KC, stays below 2^32 (QP * t_j * KC <= T_j * U < 2^31)
-    G = std::min<u64>(G, 0xFFFFFFFFull / (QP * maxt * a.KC));
-    a.G = (u32)std::max<u64>(G, 1);
-    a.dKC = csgn_fastdiv_make(a.KC);
-    a.dQP = csgn_fastdiv_make(a.QP);
+    a.tile.set(n_bits, U, sp, QP, E, a.outs, G);
+    const u32 lds = fresh ? sel_lds_layout(a.tile, sp, a.tabs) : 0u;
+    a.tile.xcd = stream_xcd(batch * E * sumt * U);
     for (u32 j = 0; j < w; ++j)
-        a.tk.set(j, (u32)(t[j] * a.KC));
-    u32 lds = 0;
-    if (fresh) {
-        a.lbase = (sp.layout(a.G) + 15u) & ~15u;
-        lds = a.lbase + a.QP * 4u;
-    }
-    a.tabs = sp.t;
-    a.xcd = stream_xcd(batch * E * sumt * U);
-    return launch_groups(launch_blocks(), batch, a.G, (u64)a.chunks * a.parts, [&](u64 e0, u64 ne, u32 nblocks) {
-        a.batch = ne;
+        a.table[j] = table[j];
+    return sel_launch(k_uint_read<Unit, true>, k_uint_read<Unit, false>, a, lds, launch_blocks(), batch,
+                      (u64)a.tile.chunks * a.tile.qparts, st, [&](u64 e0) {
         for (u32 k = 0; k < v; ++k)
             a.index[k] = reinterpret_cast<const Unit *>(index[k]) + e0 * s[k] * U;
-        for (u32 j = 0; j < w; ++j) {
-            a.table[j] = table[j];
-            a.out[j] = reinterpret_cast<Unit *>(out[j]) + e0 * t[j] * E * U;
-        }
-        a.nblocks = nblocks;
-        if (fresh)
-            k_uint_read<Unit, true><<<dim3(a.nblocks), 256, lds, st>>>(a);
-        else
-            k_uint_read<Unit, false><<<dim3(a.nblocks), 256, 0, st>>>(a);
+        for (u32 j = 0; j < w; ++j)
+            a.outs.out[j] = reinterpret_cast<Unit *>(out[j]) + e0 * t[j] * E * U;
     });
 }
 

@@ -108,12 +108,26 @@ def test_find_batches(hip, knobs, batch):
 
 @pytest.mark.parametrize("n", [1247, 4096])
 def test_find_three_subset_tables_and_unit_slices(hip, knobs, n):
-    """11 planes: three subset tables a set; at N=4096 the tables are built over slices of units."""
+    """11 planes: three subset tables a set, one slice of units at either N: at N=4096 (32 units of 16 bytes a term) a
+    set's tables of one element at whole terms take 40 x 16 x 32 = 20 480 B, not past the kernel's 20 480-byte budget."""
     v, rows, batch = 11, 2, 1
     keys = [rand_terms(n, rows, 1, 900 + k) for k in range(v)]
     query = [rand_terms(n, batch, 1, 930 + k) for k in range(v)]
     values = [rand_terms(n, rows, 1, 960)]
     check_forms(hip, knobs, n, keys, query, values, False, (1,))
+
+
+@pytest.mark.parametrize("n", [5248, 5184])
+def test_find_short_last_unit_slice(hip, knobs, n):
+    """v = 5: one subset table of 32 entries a set.  N = 5248 is 41 units of 16 bytes a term: 32 x 16 x 41 = 20 992 B
+    pass the kernel's 20 480-byte budget, so subset_plan cuts the terms into two slices of 21 units, the last one 20
+    units long.  N = 5184 (81 words, odd) is 81 units of 8 bytes: 32 x 8 x 81 = 20 736 B, slices of 41 and 40 units.
+    Value planes of 1 and 2 terms, and member."""
+    v, rows, batch = 5, 3, 2
+    keys = [rand_terms(n, rows, 1, 1100 + k) for k in range(v)]
+    query = [rand_terms(n, batch, 1, 1130 + k) for k in range(v)]
+    values = [rand_terms(n, rows, tj, 1160 + j) for j, tj in enumerate((1, 2))]
+    check_forms(hip, knobs, n, keys, query, values, True, (-1, 1))
 
 
 def test_find_many_rows(hip, knobs):

@@ -175,6 +175,18 @@ def test_lt_select_unit_slices(hip, knobs):
     ops.check_forms(knobs, [ops.b(3)], [ops.a(8)], False, (1,))
 
 
+@pytest.mark.parametrize("n", [5248, 5184])
+def test_lt_select_short_last_unit_slice(hip, knobs, n):
+    """w = 5: one subset table of 32 entries a set.  N = 5248 is 41 units of 16 bytes a term: 32 x 16 x 41 = 20 992 B
+    pass the kernel's 20 480-byte budget, so subset_plan cuts the terms into two slices of 21 units, the last one 20
+    units long.  N = 5184 (81 words, odd) is 81 units of 8 bytes: 32 x 8 x 81 = 20 736 B, slices of 41 and 40 units.
+    Min and max (requests that alias a and b), whose tail copies walk the same slices, and the comparison."""
+    w = 5
+    ops = operands(hip, n, 2, [1] * w, [1] * w, seed=n % 100)
+    mn, mx = minmax_requests([ops.a(j) for j in range(w)], [ops.b(j) for j in range(w)])
+    ops.check_forms(knobs, mn, mx, True, (-1, 1))
+
+
 @pytest.mark.parametrize("ty", [1, 3])
 @pytest.mark.parametrize("same", [True, False], ids=["y_is_b", "y_distinct"])
 def test_lt_select_tail_terms(hip, knobs, ty, same):

@@ -80,10 +80,25 @@ def test_read_batches(hip, knobs, batch, tmode):
 @pytest.mark.parametrize("v,rows,w,batch", [(10, 1024, 1, 3), (12, 4096, 1, 1), (12, 3000, 2, 1)])
 @pytest.mark.parametrize("n", [1247, 4096])
 def test_read_wide_indices_span_many_workgroups(hip, knobs, v, rows, w, batch, n):
-    """Two and three subset tables; at N=4096 the tables are built over slices of units."""
+    """Two (v = 10) and three (v = 12) subset tables, one slice of units at either N: at N=4096 (32 units of 16 bytes a
+    term) the tables of one element at whole terms take 64 x 16 x 32 = 32 768 B and 48 x 16 x 32 = 24 576 B, neither
+    past the kernel's 32 768-byte budget."""
     index = [rand_terms(n, batch, 1, 900 + k) for k in range(v)]
     table = [rand_terms(n, rows, 1, 950 + j) for j in range(w)]
     check_forms(hip, knobs, n, index, table, (1,))
+
+
+@pytest.mark.parametrize("n", [8320, 8256])
+def test_read_short_last_unit_slice(hip, knobs, n):
+    """v = 5: one subset table of 32 entries.  N = 8320 is 65 units of 16 bytes a term: 32 x 16 x 65 = 33 280 B pass the
+    kernel's 32 768-byte budget, so subset_plan cuts the terms into two slices of 33 units, the last one 32 units long.
+    N = 8256 (129 words, odd) is 129 units of 8 bytes: 32 x 8 x 129 = 33 024 B, slices of 65 and 64 units.  All 32 rows
+    and a partial last row; table planes of 1 and 2 terms."""
+    v, batch = 5, 2
+    index = [rand_terms(n, batch, 1, 1100 + k) for k in range(v)]
+    for rows in (32, 19):
+        table = [rand_terms(n, rows, tj, 1150 + j + rows) for j, tj in enumerate((1, 2))]
+        check_forms(hip, knobs, n, index, table, (-1, 1))
 
 
 def test_read_decrypts(hip, knobs, oracle):
