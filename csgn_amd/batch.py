@@ -393,6 +393,27 @@ class HipPath:
         return ([o[: batch * int(t) * E * dl] for o, t in zip(outs, value_terms)],
                 None if member is None else member[: batch * E * dl])
 
+    def uint_pick(self, n_bits: int, op: int, batch: int, index, index_terms, a, terms: int, rows: int = 0, outs=None):
+        """csgn_uint_pick: the encrypted integer `a` (bit 0 first; every plane a uniform batch of `terms` terms)
+        shifted or rotated by the encrypted distance `index` (plane k a uniform batch of index_terms[k] terms), op =
+        CSGN_UINT_PICK_SHL / SHR / ROTL / ROTR (1..4, rows = 0); or, op = CSGN_UINT_PICK_EACH (5), element e's own array
+        of `rows` rows (the elements e * rows .. e * rows + rows - 1 of `a`'s planes) read at its encrypted index.  One
+        tensor per plane of `a`, terms * E_j terms per element (E_j = csgn_uint_pick_terms); fresh ones unless `outs` is
+        given."""
+        v, w = len(index), len(a)
+        assert v == len(index_terms)
+        h_s = (C.c_uint64 * max(v, 1))(*[int(t) for t in index_terms])
+        E = [int(self.lib.csgn_uint_pick_terms(op, v, h_s, w, rows, j)) for j in range(w)]
+        assert w and all(E), "bad op, width, rows or term count"
+        dl = self.default_len(n_bits)
+        if outs is None:
+            outs = [self.empty_words(max(batch * int(terms) * e * dl, 1)) for e in E]
+        h_x = (C.c_void_p * max(v, 1))(*[_ptr(p) for p in index])
+        h_a = (C.c_void_p * max(w, 1))(*[_ptr(p) for p in a])
+        h_out = (C.c_void_p * max(w, 1))(*[_ptr(o) for o in outs])
+        check(self.lib.csgn_uint_pick(n_bits, op, batch, v, h_x, h_s, w, rows, h_a, int(terms), h_out, self.stream))
+        return [o[: batch * int(terms) * e * dl] for o, e in zip(outs, E)]
+
     def uint_lt_select(self, n_bits: int, batch: int, a, a_terms, b, b_terms, xs, x_terms, ys, y_terms, outs=None,
                        less=False):
         """csgn_uint_lt_select: request i is a < b ? xs[i] : ys[i] for the encrypted integers a and b (bit 0 first; plane

@@ -657,6 +657,8 @@ UIntBatch UIntBatch::rotateLeft(unsigned s) const
     return UIntBatch(mapPlanes(w, noCheck, [&](unsigned j) { return planes_[(j + w - s % w) % w]; }));
 }
 
+UIntBatch UIntBatch::rotateRight(unsigned s) const { return rotateLeft(width() - s % width()); }
+
 // ------------------------------------------------------------------ comparisons and select
 
 CiphertextBatch equalTo(const UIntBatch &a, const UIntBatch &b)
@@ -1140,6 +1142,164 @@ UIntBatch readWhere(const UIntBatch &keys, const UIntBatch &values, const UIntBa
 CiphertextBatch matches(const UIntBatch &keys, const UIntBatch &query)
 {
     return findPlanes(keys, std::vector<CiphertextBatch>(), query, true)[0];
+}
+
+// ------------------------------------------------------------------ shifts, rotates and own arrays by encrypted amounts
+
+namespace {
+
+uint64_t pickRows(int op, uint64_t v, uint64_t w, uint64_t n, uint64_t j)
+{
+    const uint64_t full = v >= 64 ? ~0ull : 1ull << v;
+    switch (op) {
+    case CSGN_UINT_PICK_SHL:
+        return std::min<uint64_t>(j + 1, full);
+    case CSGN_UINT_PICK_SHR:
+        return std::min<uint64_t>(w - j, full);
+    case CSGN_UINT_PICK_EACH:
+        return n;
+    default:
+        return full;
+    }
+}
+
+unsigned pickSource(int op, unsigned w, unsigned j, uint64_t r)
+{
+    switch (op) {
+    case CSGN_UINT_PICK_SHL:
+        return j - (unsigned)r;
+    case CSGN_UINT_PICK_SHR:
+        return j + (unsigned)r;
+    case CSGN_UINT_PICK_ROTL:
+        return (j + w - (unsigned)(r % w)) % w;
+    case CSGN_UINT_PICK_ROTR:
+        return (unsigned)((j + r % w) % w);
+    default:
+        return j;
+    }
+}
+
+// terms of output j by the definition itself, row by row: sum over r < rows of EQ(d, r)'s terms times the source's; 0
+// once it passes kMaxWords (no output that large fits 2^31 words)
+uint64_t pickTermsByRows(int op, const std::vector<uint64_t> &s, const std::vector<uint64_t> &t, uint64_t rows, unsigned j)
+{
+    if (rows > kMaxWords)
+        return 0;                                   // every row has at least one term
+    uint64_t T = 0;
+    for (uint64_t r = 0; r < rows; ++r) {
+        uint64_t p = t[pickSource(op, (unsigned)t.size(), j, r)];
+        for (size_t k = 0; k < s.size() && p <= kMaxWords; ++k)
+            p *= (k < 64 && ((r >> k) & 1u)) ? s[k] : s[k] + 1;
+        T += p;
+        if (p > kMaxWords || T > kMaxWords)
+            return 0;
+    }
+    return T;
+}
+
+// every output plane of one operation: out_j = sum over r < rows_j of equalTo(d, r) * source(j, r)
+std::vector<CiphertextBatch> pickPlanes(int op, const std::vector<CiphertextBatch> &a, uint64_t n, const UIntBatch &d,
+                                        const char *who)
+{
+    const Context &ctx = d.context();
+    const uint64_t v = d.width(), m = d.size();
+    const unsigned w = (unsigned)a.size();
+    const bool each = op == CSGN_UINT_PICK_EACH;
+    const std::string name = std::string("certFHE::") + who;
+    if (each && (n == 0 || (v < 64 && n > (1ull << v))))
+        throw std::invalid_argument(name + ": " + std::to_string(n) + " rows an element, not 1..2^" + std::to_string(v));
+    if (each && m != 0 && n > ~0ull / m)
+        throw std::invalid_argument(name + ": the arrays do not hold n rows for every index");
+    for (unsigned j = 0; j < w; ++j)
+        if (!sameContext(a[j].context(), ctx) || a[j].size() != (each ? n * m : m))
+            throw std::invalid_argument(name + (each ? ": the arrays and the index differ in context, or arrays.size() != n * index.size()"
+                                                     : ": the integer and the distance differ in context or count"));
+    const Planes x(d), src(a);
+    const std::vector<uint64_t> &t = src.terms;
+    bool one_count = true;
+    for (unsigned j = 1; j < w; ++j)
+        one_count = one_count && t[j] == t[0];
+    const bool fused = x.uniform && src.uniform && one_count && v <= 16;
+    std::vector<uint64_t> T(w);
+    for (unsigned j = 0; j < w; ++j) {
+        uint64_t terms = 0;
+        if (m == 0) {
+            terms = 1;                              // an empty batch has no sizes to check: empty planes
+        } else if (fused) {
+            const uint64_t E = csgn_uint_pick_terms(op, v, x.terms.data(), w, each ? n : 0, j);
+            terms = (E == 0 || t[0] == 0 || t[0] > kMaxWords / E) ? 0 : t[0] * E;
+        } else {
+            terms = pickTermsByRows(op, x.terms, t, pickRows(op, v, w, n, j), j);
+        }
+        if (terms == 0)
+            throw std::invalid_argument(name + ": an output plane exceeds 2^31 words per element (the distance is too "
+                                               "wide or has too many terms)");
+        T[j] = checked(terms, ctx, who);
+    }
+    if (fused || m == 0) {
+        std::vector<CiphertextBatch> out = makePlanes(ctx, m, T);
+        if (m)
+            detail::check(csgn_uint_pick(ctx.getN(), op, m, v, sources(x).data(), x.terms.data(), w, each ? n : 0,
+                                         sources(src).data(), t[0], wordsOf(out).data(), detail::stream()),
+                          "csgn_uint_pick");
+        return out;
+    }
+    // ragged planes, planes of different term counts, a wider distance: the definition itself through the operators
+    uint64_t rows_max = 0;
+    for (unsigned j = 0; j < w; ++j)
+        rows_max = std::max(rows_max, pickRows(op, v, w, n, j));
+    std::vector<CiphertextBatch> out;
+    for (uint64_t r = 0; r < rows_max; ++r) {
+        const CiphertextBatch eq = equalTo(d, r);
+        std::vector<uint64_t> idx;
+        if (each) {
+            idx.resize(m);
+            for (uint64_t e = 0; e < m; ++e)
+                idx[e] = e * n + r;
+        }
+        for (unsigned j = 0; j < w; ++j) {
+            if (r >= pickRows(op, v, w, n, j))
+                continue;
+            const CiphertextBatch p = eq * (each ? a[j].gather(idx) : a[pickSource(op, w, j, r)]);
+            if (r == 0)
+                out.push_back(p);
+            else
+                out[j] = out[j] + p;
+        }
+    }
+    return out;
+}
+
+} // namespace
+
+UIntBatch UIntBatch::shiftLeft(const UIntBatch &d) const
+{
+    return UIntBatch(pickPlanes(CSGN_UINT_PICK_SHL, planes_, 0, d, "UIntBatch::shiftLeft"));
+}
+
+UIntBatch UIntBatch::shiftRight(const UIntBatch &d) const
+{
+    return UIntBatch(pickPlanes(CSGN_UINT_PICK_SHR, planes_, 0, d, "UIntBatch::shiftRight"));
+}
+
+UIntBatch UIntBatch::rotateLeft(const UIntBatch &d) const
+{
+    return UIntBatch(pickPlanes(CSGN_UINT_PICK_ROTL, planes_, 0, d, "UIntBatch::rotateLeft"));
+}
+
+UIntBatch UIntBatch::rotateRight(const UIntBatch &d) const
+{
+    return UIntBatch(pickPlanes(CSGN_UINT_PICK_ROTR, planes_, 0, d, "UIntBatch::rotateRight"));
+}
+
+UIntBatch readAtEach(const UIntBatch &arrays, uint64_t n, const UIntBatch &index)
+{
+    return UIntBatch::fromPlanes(pickPlanes(CSGN_UINT_PICK_EACH, planesOf(arrays), n, index, "readAtEach"));
+}
+
+CiphertextBatch readAtEach(const CiphertextBatch &arrays, uint64_t n, const UIntBatch &index)
+{
+    return pickPlanes(CSGN_UINT_PICK_EACH, std::vector<CiphertextBatch>(1, arrays), n, index, "readAtEach")[0];
 }
 
 // ------------------------------------------------------------------ counting (csgn_count)

@@ -1425,6 +1425,78 @@ int csgn_uint_read(uint64_t n_bits, uint64_t batch, uint64_t index_width, const 
     return CSGN_OK;
 }
 
+/* ------------------------------------- shifts, rotates and per-element reads by encrypted amounts ---- */
+
+uint64_t csgn_uint_pick_terms(int op, uint64_t index_width, const uint64_t *h_index_terms, uint64_t width, uint64_t rows,
+                              uint64_t j)
+{
+    return csgn::uint_pick_terms(op, index_width, (const u64 *)h_index_terms, width, rows, j);
+}
+
+const char *csgn_uint_pick_kernel(uint64_t n_bits, int op, uint64_t batch, uint64_t index_width,
+                                  const uint64_t *h_index_terms, uint64_t width, uint64_t rows, uint64_t terms)
+{
+    return csgn::uint_pick_kernel_name(n_bits, op, batch, index_width, (const u64 *)h_index_terms, width, rows, terms);
+}
+
+int csgn_uint_pick_plan(uint64_t n_bits, int op, uint64_t batch, uint64_t index_width, const uint64_t *h_index_terms,
+                        uint64_t width, uint64_t rows, uint64_t terms, int wide_units, uint64_t *h_plan)
+{
+    REQUIRE(h_plan, "null host pointer");
+    REQUIRE(csgn::uint_pick_plan(n_bits, op, batch, index_width, (const u64 *)h_index_terms, width, rows, terms,
+                                 wide_units != 0, (u64 *)h_plan),
+            "pick plan: an invalid shape or an empty batch");
+    return CSGN_OK;
+}
+
+int csgn_uint_pick(uint64_t n_bits, int op, uint64_t batch, uint64_t index_width, const uint64_t *const *h_index,
+                   const uint64_t *h_index_terms, uint64_t width, uint64_t rows, const uint64_t *const *h_a,
+                   uint64_t terms, uint64_t *const *h_out, void *stream)
+{
+    if (int rc = check_n(n_bits))
+        return rc;
+    REQUIRE(op >= CSGN_UINT_PICK_SHL && op <= CSGN_UINT_PICK_EACH, "pick: unknown op %d", op);
+    REQUIRE(index_width >= 1 && index_width <= csgn::kPickMaxIndex, "pick: index width %llu outside 1..16",
+            (unsigned long long)index_width);
+    REQUIRE(width >= 1 && width <= csgn::kPickMaxPlanes, "pick: width %llu outside 1..64", (unsigned long long)width);
+    if (op == CSGN_UINT_PICK_EACH)
+        REQUIRE(rows >= 1 && rows <= (1ull << index_width), "pick: %llu rows outside 1..2^%llu",
+                (unsigned long long)rows, (unsigned long long)index_width);
+    else
+        REQUIRE(rows == 0, "pick: rows must be 0 for a shift or rotate (%llu)", (unsigned long long)rows);
+    REQUIRE(h_index && h_index_terms && h_a && h_out, "null host pointer");
+    REQUIRE(terms != 0 && terms < (1ull << 62), "pick: a source plane of %llu terms", (unsigned long long)terms);
+    const uint64_t dl = csgn_default_len(n_bits);
+    for (uint64_t j = 0; j < width; ++j) {
+        const uint64_t E = csgn::uint_pick_terms(op, index_width, (const u64 *)h_index_terms, width, rows, j);
+        REQUIRE(E != 0, "pick: an index plane has no terms, or the term count overflows");
+        unsigned long long out_terms;                        // of output j; a product that wraps is past every limit
+        if (__builtin_mul_overflow((unsigned long long)terms, (unsigned long long)E, &out_terms))
+            out_terms = ~0ull;
+        if (int rc = check_size(batch, out_terms, out_terms, dl, "pick: output %llu", (unsigned long long)j))
+            return rc;
+    }
+    if (op == CSGN_UINT_PICK_EACH) {
+        unsigned long long src_terms;                        // of an element's array in one source plane
+        if (__builtin_mul_overflow((unsigned long long)terms, (unsigned long long)rows, &src_terms))
+            src_terms = ~0ull;
+        if (!product_below(batch, src_terms, dl, 1ull << 60))
+            return fail(CSGN_ERR_UNSUPPORTED, "pick: %llu arrays of %llu rows: size overflows",
+                        (unsigned long long)batch, (unsigned long long)rows);
+    }
+    if (int rc = require_device("csgn_uint_pick"))
+        return rc;
+    if (batch == 0)
+        return CSGN_OK;
+    if (int rc = check_planes(h_index, nullptr, index_width, "index plane"))
+        return rc;
+    if (int rc = check_planes(h_a, h_out, width, "source plane or output"))
+        return rc;
+    HIP_TRY(csgn::uint_pick(n_bits, op, batch, index_width, (const u64 *const *)h_index, (const u64 *)h_index_terms,
+                            width, rows, (const u64 *const *)h_a, terms, (u64 *const *)h_out, S(stream)));
+    return CSGN_OK;
+}
+
 /* ------------------------------------------------ encrypted tables by encrypted key ---- */
 
 uint64_t csgn_uint_find_terms(uint64_t key_width, const uint64_t *h_key_terms, const uint64_t *h_query_terms)

@@ -236,12 +236,23 @@ hipError_t uint_lt_select(u64 n_bits, u64 batch, u64 w, const u64 *const *a, con
                           const u64 *tb, u64 n_out, const u64 *const *x, const u64 *tx, const u64 *const *y,
                           const u64 *ty, u64 *const *out, u64 *less, hipStream_t stream);
 
+// an encrypted integer shifted, rotated or indexed by an encrypted amount (csgn_uint_pick.hip), include/csgn_hip.h's
+// definition: output j is the sum, ascending in r < rows_j, of EQ(index, r) * a_{src(j, r)}; op = CSGN_UINT_PICK_*.
+// index planes: v = 1..16, terms s[k]; source planes: w = 1..64, every one of t terms; rows: EACH's n, else 0.
+constexpr u32 kPickMaxIndex = 16, kPickMaxPlanes = 64;
+u64 uint_pick_terms(int op, u64 v, const u64 *s, u64 w, u64 rows, u64 j);   // E_j; 0: invalid argument or 2^62 or more
+const char *uint_pick_kernel_name(u64 n_bits, int op, u64 batch, u64 v, const u64 *s, u64 w, u64 rows, u64 t);
+// the fused form's tile: plan = {G, KC, QP, q parts}; wide: 16-byte units where dL is even.  false: invalid shape
+bool uint_pick_plan(u64 n_bits, int op, u64 batch, u64 v, const u64 *s, u64 w, u64 rows, u64 t, bool wide, u64 plan[4]);
+hipError_t uint_pick(u64 n_bits, int op, u64 batch, u64 v, const u64 *const *index, const u64 *s, u64 w, u64 rows,
+                     const u64 *const *src, u64 t, u64 *const *out, hipStream_t stream);
+
 // The temporaries of the composed forms and of the gather plan (csgn_scratch.cpp): a plain (hipMalloc) block the calling
 // thread keeps per stream and per user, never the stream-ordered pool.  Returns the block, or nullptr with e set
 // (hipErrorStreamCaptureUnsupported when the call would have to allocate while s is capturing).  owned: the block is
 // past the kept size and belongs to this call; scratch_done frees it behind the call's launches (waits for the device)
 // and passes e through.
-enum ScratchSlot { SCRATCH_UINT_PLAIN, SCRATCH_UINT_LUT, SCRATCH_UINT_READ, SCRATCH_UINT_ADDK, SCRATCH_UINT_FIND, SCRATCH_GATHER, SCRATCH_MATMUL, SCRATCH_COUNT, SCRATCH_UINT_LT_SELECT, SCRATCH_SLOTS };
+enum ScratchSlot { SCRATCH_UINT_PLAIN, SCRATCH_UINT_LUT, SCRATCH_UINT_READ, SCRATCH_UINT_ADDK, SCRATCH_UINT_FIND, SCRATCH_GATHER, SCRATCH_MATMUL, SCRATCH_COUNT, SCRATCH_UINT_LT_SELECT, SCRATCH_UINT_PICK, SCRATCH_SLOTS };
 u64 *scratch_take(ScratchSlot slot, size_t bytes, hipStream_t s, bool &owned, hipError_t &e);
 hipError_t scratch_done(u64 *block, bool owned, hipError_t e);
 

@@ -1,5 +1,5 @@
 // csgn_selector.h -- the skeleton of the selector-stream kernels (csgn_uint_read.hip, csgn_uint_find.hip,
-// csgn_uint_lt_select.hip).  Internal linkage, like csgn_device.h.
+// csgn_uint_lt_select.hip, csgn_uint_pick.hip).  Internal linkage, like csgn_device.h.
 //
 // An encrypted SELECTOR STREAM (the EQ rows of an index, the EQ of a key row and a query, the terms of lessThan) is the
 // left operand of a product with one unit of a value plane, written for every output plane in one launch: term
@@ -123,7 +123,82 @@ __device__ __forceinline__ void sel_walk(const SelTile &t, const SelBlock<Unit> 
     }
 }
 
+// ------------------------------------------------------------------------------ the E stream of an index
+// The concatenation, ascending in r <= last_row, of the EQ rows of an index (csgn_uint_read.hip's term order), decoded
+// from the position: what k_uint_read and k_uint_pick share.  Args: v, s[k], F[k] (sel_index_fill) and last_row.
+
+// q < E: the row r holding entry q of the E stream, and q's index inside r's block (the walk)
+template <typename Args>
+__device__ inline u32 read_walk(const Args &a, u64 q, u64 &in)
+{
+    u32 r = 0;
+    u64 H = 1;                  // prod of R_k over the bits fixed so far
+    bool tight = true;          // the prefix equals that of rows - 1
+    for (u32 k = a.v; k-- > 0u;) {
+        const u64 s = a.s[k];
+        if (tight && !((a.last_row >> k) & 1u)) {
+            H *= s + 1u;
+            continue;
+        }
+        const u64 c0 = H * (s + 1u) * a.F[k];
+        if (q < c0) {
+            H *= s + 1u;
+            tight = false;
+        } else {
+            q -= c0;
+            r |= 1u << k;
+            H *= s;
+        }
+    }
+    in = q;
+    return r;
+}
+
+// Fresh planes: the workgroup's range of the E stream into its LDS list, S in the low 16 bits, r in the high 16
+// (published by the tables' closing barrier)
+template <typename Args, typename Unit>
+__device__ inline void read_decode(const Args &a, const SelBlock<Unit> &b)
+{
+    for (u32 i = threadIdx.x; i < b.nq; i += 256u) {
+        u64 in;
+        const u32 r = read_walk(a, b.q0 + i, in);
+        u32 S = r;
+        for (u32 k = a.v; k-- > 0u;) {      // zero bits, the highest the fastest binary digit; digit 0 = x_k
+            if ((r >> k) & 1u)
+                continue;
+            if (!(in & 1u))
+                S |= 1u << k;
+            in >>= 1;
+        }
+        b.code[i] = S | (r << 16);
+    }
+}
+
 // ------------------------------------------------------------------------------ host side
+
+// x * y, saturated at kTermLimit
+inline u64 sat_mul(u64 x, u64 y)
+{
+    u64 p;
+    return term_mul(x, y, p) ? p : kTermLimit;
+}
+
+// The index of an E stream into the arguments: v, s[k] and F[k] = prod over i < k of (2 s_i + 1), a whole subtree below
+// bit k (saturated; read only where the subtree lies below the rows, so at most E).  Returns whether every plane is fresh.
+template <typename Args>
+inline bool sel_index_fill(Args &a, u64 v, const u64 *s)
+{
+    a.v = (u32)v;
+    bool fresh = true;
+    u64 f = 1;
+    for (u32 k = 0; k < v; ++k) {
+        a.s[k] = (u32)s[k];
+        a.F[k] = f;
+        f = sat_mul(f, 2 * s[k] + 1);
+        fresh = fresh && s[k] == 1;
+    }
+    return fresh;
+}
 
 // The LDS of fresh planes: the tables of G elements (their layout into `first`), then, with G2, a second set for G2
 // elements (into `second`), then the QP decoded entries.  Sets the tile's offsets; returns the bytes.

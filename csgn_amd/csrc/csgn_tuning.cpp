@@ -42,6 +42,8 @@ const Knob kKnobs[TUNE_COUNT] = {
     {"count_form", -1},
     {"count_cpart", 0},
     {"uint_lt_select_form", -1},
+    {"uint_pick_fused", -1},
+    {"uint_pick_stage", -1},
     {"launch_blocks", 0},
 };
 

@@ -4,7 +4,8 @@
 // The definition (include/csgn_hip.h, csgn_uint_read) is out_j = sum over r < rows, ascending, of EQ(x, r) * d_{r,j}:
 // csgn_uint_plain's EQ row with k = r as the left operand, plane j of table element r as the right.  Term q * t_j + c of
 // output j is (term q of the E stream) & (term c of d_{r,j}), where the E stream is the concatenation, ascending in r,
-// of the EQ rows.  Nothing of it is tabulated: q is decoded by
+// of the EQ rows.  Nothing of it is tabulated: q is decoded (read_walk and read_decode of csgn_selector.h, which
+// csgn_uint_pick.hip shares) by
 //     the walk    from the top index bit down: below a fixed prefix of high bits a whole subtree holds
 //                 prod (2 s_k + 1) terms over its free bits, times the R_k of the bits already fixed, so each step
 //                 either skips the bit-0 subtree (bit 1) or enters it; while the prefix equals that of rows - 1 and
@@ -47,32 +48,6 @@ struct ReadArgs {
 };
 static_assert(sizeof(ReadArgs) <= 4096, "the kernel arguments of k_uint_read pass the 4 KiB limit");
 
-// q < E: the row r holding entry q of the E stream, and q's index inside r's block (the walk)
-__device__ inline u32 read_walk(const ReadArgs &a, u64 q, u64 &in)
-{
-    u32 r = 0;
-    u64 H = 1;                  // prod of R_k over the bits fixed so far
-    bool tight = true;          // the prefix equals that of rows - 1
-    for (u32 k = a.v; k-- > 0u;) {
-        const u64 s = a.s[k];
-        if (tight && !((a.last_row >> k) & 1u)) {
-            H *= s + 1u;
-            continue;
-        }
-        const u64 c0 = H * (s + 1u) * a.F[k];
-        if (q < c0) {
-            H *= s + 1u;
-            tight = false;
-        } else {
-            q -= c0;
-            r |= 1u << k;
-            H *= s;
-        }
-    }
-    in = q;
-    return r;
-}
-
 template <typename Unit, bool Fresh>
 __global__ void __launch_bounds__(256) k_uint_read(ReadArgs a)
 {
@@ -80,20 +55,7 @@ __global__ void __launch_bounds__(256) k_uint_read(ReadArgs a)
     const SelBlock<Unit> b = sel_block<Unit>(t, a.E);
 
     if (Fresh) {
-        // the range of the E stream: S in the low 16 bits, r in the high 16 (published by the tables' closing barrier)
-        for (u32 i = threadIdx.x; i < b.nq; i += 256u) {
-            u64 in;
-            const u32 r = read_walk(a, b.q0 + i, in);
-            u32 S = r;
-            for (u32 k = a.v; k-- > 0u;) {      // zero bits, the highest the fastest binary digit; digit 0 = x_k
-                if ((r >> k) & 1u)
-                    continue;
-                if (!(in & 1u))
-                    S |= 1u << k;
-                in >>= 1;
-            }
-            b.code[i] = S | (r << 16);
-        }
+        read_decode(a, b);
         subset_build(b.tab, a.tabs, a.index, t.G, t.KC, t.dKC, t.U, t.last_mask, b.e0, b.ne, b.k0, b.kc);
     }
 
@@ -130,13 +92,6 @@ __global__ void __launch_bounds__(256) k_uint_read(ReadArgs a)
 
 // ------------------------------------------------------------------------------ host side
 
-// x * y, saturated at kTermLimit
-u64 sat_mul(u64 x, u64 y)
-{
-    u64 p;
-    return term_mul(x, y, p) ? p : kTermLimit;
-}
-
 bool read_shape_ok(u64 v, const u64 *s, u64 rows, u64 w, const u64 *t)
 {
     if (w < 1 || w > kReadMaxPlanes || !t || uint_read_terms(v, s, rows) == 0)
@@ -158,17 +113,9 @@ hipError_t read_fused(u64 n_bits, u64 batch, u64 v, const u64 *const *index, con
                       const u64 *const *table, const u64 *t, u64 *const *out, u64 E, u32 U, hipStream_t st)
 {
     ReadArgs a = {};
-    a.v = (u32)v;
     a.E = (u32)E;
     a.last_row = (u32)(rows - 1);
-    bool fresh = true;
-    u64 f = 1;
-    for (u32 k = 0; k < v; ++k) {
-        a.s[k] = (u32)s[k];
-        a.F[k] = f;
-        f = sat_mul(f, 2 * s[k] + 1);
-        fresh = fresh && s[k] == 1;
-    }
+    const bool fresh = sel_index_fill(a, v, s);
     const SubsetPlan sp = subset_plan(fresh ? (u32)v : 0, U, (u32)sizeof(Unit), kLdsBudget);
     const u64 sumt = a.outs.fill(w, [&](u32 j) { return t[j]; }, false, sp.KC);
     // elements per workgroup: enough to give it kPartUnits to write, as many as the tables allow

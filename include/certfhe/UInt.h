@@ -91,6 +91,27 @@
 //     a.shiftLeft(s)     plane j = a_{j-s} for j >= s, ZERO below; every plane ZERO when s >= width
 //     a.shiftRight(s)    plane j = a_{j+s} for j + s < width, ZERO above; every plane ZERO when s >= width
 //     a.rotateLeft(s)    plane j = a_{(j - s) mod width}, s taken mod width
+//     a.rotateRight(s)   rotateLeft(width - s mod width)
+//
+// SHIFTS, ROTATES AND OWN ARRAYS BY ENCRYPTED AMOUNTS: a.shiftLeft(d), shiftRight(d), rotateLeft(d), rotateRight(d) move
+// every element by ITS OWN encrypted distance d (one context and count; v = d.width()), and readAtEach(arrays, n, index)
+// reads, for element e, row index[e] of the n rows e * n .. e * n + n - 1 of `arrays`: x << (y & 31), the data-dependent
+// rotations of RC5-style ciphers, a barrel shifter, a per-record array, n-way selection.  Output plane j is the
+// left-nested sum, ascending in r < rows_j, of equalTo(d, r) * (a source plane of the same element) -- the EQ row of
+// csgn_uint_plain with k = r as the LEFT operand -- csgn_uint_pick's words (include/csgn_hip.h):
+//     a.shiftLeft(d)     rows_j = min(j + 1, 2^v), source a_{j-r}           (a << d) mod 2^w, 0 where d >= w
+//     a.shiftRight(d)    rows_j = min(w - j, 2^v), source a_{j+r}           a >> d, 0 where d >= w
+//     a.rotateLeft(d)    rows_j = 2^v, source a_{(j-r) mod w}               a rotated left by d mod w
+//     a.rotateRight(d)   rows_j = 2^v, source a_{(j+r) mod w}               a rotated right by d mod w
+//     readAtEach         rows_j = n, source plane j of element e * n + r    arrays[e * n + index[e]], 0 where index[e] >= n
+// Plane j has t * E_j terms for source planes of t terms, E_j the terms of readAt's E over rows_j rows: with fresh planes
+// the top plane of an 8-bit shiftLeft by a 3-bit distance has 27 terms, a plane of a 32-bit rotate by 5 bits 243.
+// Uniform planes of ONE term count under a distance of at most 16 bits take one csgn_uint_pick (one launch for every
+// output plane); ragged planes (a compact() result), planes of different term counts and wider distances are composed
+// from equalTo(d, r), operator*, left-nested operator+ and, for readAtEach, gather, with the same words.  Every size is
+// computed before anything is allocated: std::invalid_argument for mismatched contexts or counts, n of 0 or past
+// 2^index.width(), arrays.size() != n * index.size(), or an output past 2^31 words per element.  An empty batch gives
+// empty planes.
 //
 // COUNTING: countOnes(bits, g, planes) counts the ones among every g consecutive elements of a batch of encrypted bits
 // into an encrypted integer, modulo 2^planes: COUNT(*) of matching rows, the Hamming weight of a word, the Hamming
@@ -194,6 +215,12 @@ class UIntBatch {
     UIntBatch shiftLeft(unsigned s) const;
     UIntBatch shiftRight(unsigned s) const;
     UIntBatch rotateLeft(unsigned s) const;
+    UIntBatch rotateRight(unsigned s) const;
+    // ENCRYPTED distance d, element by element; d of the same context and count, any width
+    UIntBatch shiftLeft(const UIntBatch &d) const;
+    UIntBatch shiftRight(const UIntBatch &d) const;
+    UIntBatch rotateLeft(const UIntBatch &d) const;
+    UIntBatch rotateRight(const UIntBatch &d) const;
 };
 
 UIntBatch operator-(uint64_t k, const UIntBatch &a);
@@ -252,6 +279,10 @@ UIntBatch lookup(const UIntBatch &a, const UIntBatch &b, const LookupTable &f);
 // element e: table[index[e]] where index[e] < table.size(), else 0; one output plane per table plane
 UIntBatch readAt(const UIntBatch &table, const UIntBatch &index);
 CiphertextBatch readAt(const CiphertextBatch &table, const UIntBatch &index);
+
+// element e: arrays[e * n + index[e]] where index[e] < n, else 0; arrays.size() == n * index.size(), 1 <= n <= 2^v
+UIntBatch readAtEach(const UIntBatch &arrays, uint64_t n, const UIntBatch &index);
+CiphertextBatch readAtEach(const CiphertextBatch &arrays, uint64_t n, const UIntBatch &index);
 
 // element e: XOR over rows r with keys[r] == query[e] of values[r]  (distinct keys: the matching value, else 0)
 UIntBatch readWhere(const UIntBatch &keys, const UIntBatch &values, const UIntBatch &query);

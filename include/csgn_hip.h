@@ -926,6 +926,70 @@ int csgn_uint_lt_select(uint64_t n_bits, uint64_t batch, uint64_t width, const u
                         const uint64_t *const *h_x, const uint64_t *h_x_terms, const uint64_t *const *h_y,
                         const uint64_t *h_y_terms, uint64_t *const *h_out, uint64_t *d_less, void *stream);
 
+/* ------------------------------------- shifts, rotates and per-element reads by encrypted amounts ---- */
+
+/* An encrypted integer shifted or rotated by an ENCRYPTED distance, or an array that belongs to the element read at the
+ * element's ENCRYPTED index.  Index: index_width = v planes x_0..x_{v-1} (bit 0 first, v in 1..16) of `batch` elements,
+ * plane k uniform with s_k terms per element.  Source: `width` = w planes a_0..a_{w-1} (1..64), EVERY one uniform with
+ * the same t terms per element; of `batch` elements, or, for EACH, of batch * n elements (element e's array is the
+ * elements e * n .. e * n + n - 1).  Output: w planes of `batch` elements.  A fixed composition of the reference's
+ * operator+ / operator* with ONE, element e with element e:
+ *     out_j = ((EQ(x, 0) * a_{src(j,0)}) + (EQ(x, 1) * a_{src(j,1)})) + ... + (EQ(x, rows_j - 1) * a_{src(j,rows_j-1)})
+ *     EQ(x, r)   csgn_uint_plain's EQ row with k = r, the LEFT operand of every product, exactly as in csgn_uint_read
+ *     op                    rows_j              src(j, r)                         decrypts to
+ *     CSGN_UINT_PICK_SHL    min(j + 1, 2^v)     plane j - r                       (a << x) mod 2^w, 0 where x >= w
+ *     CSGN_UINT_PICK_SHR    min(w - j, 2^v)     plane j + r                       a >> x, 0 where x >= w
+ *     CSGN_UINT_PICK_ROTL   2^v                 plane (j - r) mod w               a rotated left by x mod w
+ *     CSGN_UINT_PICK_ROTR   2^v                 plane (j + r) mod w               a rotated right by x mod w
+ *     CSGN_UINT_PICK_EACH   n = `rows`          plane j of element e * n + r      row x of element e's array, 0 where x >= n
+ * `rows` is n (1 <= n <= 2^v) for EACH and must be 0 for the shifts and rotates.
+ * Terms of output j: t * E_j,  E_j = csgn_uint_read_terms(v, s, rows_j).  Fresh planes: the top plane of an 8-bit SHL by
+ * a 3-bit distance has 27 terms, every plane of a 32-bit rotate by 5 bits 243.
+ * Term order: csgn_uint_read's -- term q * t + c is (entry q of the E stream of rows_j rows) & (term c of the source);
+ * rows are concatenated ascending, so the stream of a shorter output is a prefix of the longest one's. */
+enum csgn_uint_pick_op {
+    CSGN_UINT_PICK_SHL = 1,
+    CSGN_UINT_PICK_SHR = 2,
+    CSGN_UINT_PICK_ROTL = 3,
+    CSGN_UINT_PICK_ROTR = 4,
+    CSGN_UINT_PICK_EACH = 5
+};
+/* E_j (host only); 0 for an unknown op, index_width outside 1..16, width outside 1..64, j >= width, rows != 0 for a
+ * shift or rotate, rows outside 1..2^index_width for EACH, a null pointer, an index plane of 0 terms or a count of 2^62
+ * or more. */
+uint64_t csgn_uint_pick_terms(int op, uint64_t index_width, const uint64_t *h_index_terms, uint64_t width, uint64_t rows,
+                              uint64_t j);
+/* Which form a csgn_uint_pick call of this shape takes (host only, a static string): "k_uint_pick" (one kernel writes
+ * every output plane, planes read in place) or "composed" (per row r: csgn_uint_plain's EQ into a temporary the calling
+ * thread keeps (csgn_uint_addk's rules for its composed form), for EACH csgn_gather_planes of the elements e * n + r --
+ * the list e * n is uploaded, and waited for, once a call --, then csgn_mul_uniform into r's slice of every output that
+ * has the row).  Knob "uint_pick_fused" (-1 per shape, 0 / 1 forced) decides; the words are the same.  Per shape: fused
+ * for every shape (no shape is measured in favour of the composed form; EACH with batch * n of 2^32 or more is fused
+ * whatever the knob says: the gather's counts stop there).  "" for an invalid shape.  Inside the fused form, knob
+ * "uint_pick_stage" (-1 per shape, 0 / 1 forced) chooses whether a workgroup copies its slice of the source planes into
+ * LDS (fresh index planes, where the slice fits; per shape: it does) or reads it with plain global loads; same words. */
+const char *csgn_uint_pick_kernel(uint64_t n_bits, int op, uint64_t batch, uint64_t index_width,
+                                  const uint64_t *h_index_terms, uint64_t width, uint64_t rows, uint64_t terms);
+/* The fused form's tile for this shape (host only), for tests and tools: h_plan[0..3] = elements per workgroup, units of
+ * a unit slice, E-stream entries a workgroup decodes (QP: workgroup part p owns entries [p * QP, (p + 1) * QP) of the
+ * longest output's stream) and the number of such parts.  wide_units: nonzero for the 16-byte-unit kernel (taken when
+ * dL is even and every pointer is 16-byte aligned).  CSGN_ERR_INVALID for an invalid shape or an empty batch. */
+int csgn_uint_pick_plan(uint64_t n_bits, int op, uint64_t batch, uint64_t index_width, const uint64_t *h_index_terms,
+                        uint64_t width, uint64_t rows, uint64_t terms, int wide_units, uint64_t *h_plan);
+/* The operation over `batch` elements.  h_index: a HOST array of index_width device pointers (plane k: batch * s_k * dL
+ * words), h_a: a HOST array of `width` device pointers (plane j: batch * t * dL words, for EACH batch * n * t * dL),
+ * h_out: a HOST array of `width` device pointers (output j: batch * t * E_j * dL words).  Planes may alias one another;
+ * no output overlaps an input or another output.  CSGN_ERR_INVALID: n_bits 0, an unknown op, index_width outside 1..16,
+ * width outside 1..64, rows != 0 for a shift or rotate or outside 1..2^index_width for EACH, `terms` or an s_k of 0 or
+ * past the term limit, a null host array, a null device pointer among the first index_width / width entries.
+ * CSGN_ERR_UNSUPPORTED: an output of 2^31 words per element or more, or a batch times that (or the source) of 2^60 words
+ * or more.  batch == 0 succeeds and touches nothing.  Nothing is allocated or launched before every size is known.  On
+ * the caller's stream, asynchronous; the fused form is one launch and graph-capturable.  No GPU: CSGN_ERR_NO_DEVICE, no
+ * CPU fallback. */
+int csgn_uint_pick(uint64_t n_bits, int op, uint64_t batch, uint64_t index_width, const uint64_t *const *h_index,
+                   const uint64_t *h_index_terms, uint64_t width, uint64_t rows, const uint64_t *const *h_a,
+                   uint64_t terms, uint64_t *const *h_out, void *stream);
+
 /* ------------------------------------------------ encrypted bit matrices over F2 ---- */
 
 /* The product of two ENCRYPTED bit matrices over F2: an inner product of encrypted bit vectors, a secret linear map
