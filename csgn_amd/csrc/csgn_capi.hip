@@ -127,6 +127,25 @@ int check_planes(const uint64_t *const *a, const uint64_t *const *b, uint64_t n,
     return CSGN_OK;
 }
 
+// What csgn_uint_read and csgn_uint_pick both check of an E stream, `op` ("read" / "pick") leading the text: the index
+// width, the width of the table or source and the rows against the index width; and output j of terms * E terms (a
+// product that wraps is past every limit).
+int check_index(const char *op, uint64_t v, const char *width_name, uint64_t width, uint64_t rows)
+{
+    REQUIRE(v >= 1 && v <= csgn::kReadMaxIndex, "%s: index width %llu outside 1..16", op, (unsigned long long)v);
+    REQUIRE(width >= 1 && width <= 64, "%s: %s %llu outside 1..64", op, width_name, (unsigned long long)width);
+    REQUIRE(rows >= 1 && rows <= (1ull << v), "%s: %llu rows outside 1..2^%llu", op, (unsigned long long)rows,
+            (unsigned long long)v);
+    return CSGN_OK;
+}
+int check_index_output(const char *op, uint64_t batch, uint64_t terms, uint64_t E, uint64_t dl, uint64_t j)
+{
+    unsigned long long all;
+    if (__builtin_mul_overflow((unsigned long long)terms, (unsigned long long)E, &all))
+        all = ~0ull;
+    return check_size(batch, all, all, dl, "%s: output %llu", op, (unsigned long long)j);
+}
+
 int check_pair_product(uint64_t t1, uint64_t t2, uint64_t dl)
 {
     if (t1 >= (1ull << 31) || t2 >= (1ull << 31) || !product_below(t1, t2, dl, 1ull << 32))
@@ -1393,22 +1412,14 @@ int csgn_uint_read(uint64_t n_bits, uint64_t batch, uint64_t index_width, const 
 {
     if (int rc = check_n(n_bits))
         return rc;
-    REQUIRE(index_width >= 1 && index_width <= csgn::kReadMaxIndex, "read: index width %llu outside 1..16",
-            (unsigned long long)index_width);
-    REQUIRE(width >= 1 && width <= csgn::kReadMaxPlanes, "read: table width %llu outside 1..64",
-            (unsigned long long)width);
-    REQUIRE(rows >= 1 && rows <= (1ull << index_width), "read: %llu rows outside 1..2^%llu", (unsigned long long)rows,
-            (unsigned long long)index_width);
+    if (int rc = check_index("read", index_width, "table width", width, rows))
+        return rc;
     REQUIRE(h_index && h_index_terms && h_table && h_table_terms && h_out, "null host pointer");
     const uint64_t E = csgn::uint_read_terms(index_width, (const u64 *)h_index_terms, rows);
     REQUIRE(E != 0, "read: an index plane has no terms, or the term count overflows");
-    const uint64_t dl = csgn_default_len(n_bits);
     for (uint64_t j = 0; j < width; ++j) {
         REQUIRE(h_table_terms[j] != 0, "read: table plane %llu has no terms", (unsigned long long)j);
-        unsigned long long terms;                            // of output j; a product that wraps is past every limit
-        if (__builtin_mul_overflow((unsigned long long)h_table_terms[j], (unsigned long long)E, &terms))
-            terms = ~0ull;
-        if (int rc = check_size(batch, terms, terms, dl, "read: output %llu", (unsigned long long)j))
+        if (int rc = check_index_output("read", batch, h_table_terms[j], E, csgn_default_len(n_bits), j))
             return rc;
     }
     if (int rc = require_device("csgn_uint_read"))
@@ -1456,24 +1467,17 @@ int csgn_uint_pick(uint64_t n_bits, int op, uint64_t batch, uint64_t index_width
     if (int rc = check_n(n_bits))
         return rc;
     REQUIRE(op >= CSGN_UINT_PICK_SHL && op <= CSGN_UINT_PICK_EACH, "pick: unknown op %d", op);
-    REQUIRE(index_width >= 1 && index_width <= csgn::kPickMaxIndex, "pick: index width %llu outside 1..16",
-            (unsigned long long)index_width);
-    REQUIRE(width >= 1 && width <= csgn::kPickMaxPlanes, "pick: width %llu outside 1..64", (unsigned long long)width);
-    if (op == CSGN_UINT_PICK_EACH)
-        REQUIRE(rows >= 1 && rows <= (1ull << index_width), "pick: %llu rows outside 1..2^%llu",
-                (unsigned long long)rows, (unsigned long long)index_width);
-    else
-        REQUIRE(rows == 0, "pick: rows must be 0 for a shift or rotate (%llu)", (unsigned long long)rows);
+    if (int rc = check_index("pick", index_width, "width", width, op == CSGN_UINT_PICK_EACH ? rows : 1))
+        return rc;
+    REQUIRE(op == CSGN_UINT_PICK_EACH || rows == 0, "pick: rows must be 0 for a shift or rotate (%llu)",
+            (unsigned long long)rows);
     REQUIRE(h_index && h_index_terms && h_a && h_out, "null host pointer");
     REQUIRE(terms != 0 && terms < (1ull << 62), "pick: a source plane of %llu terms", (unsigned long long)terms);
     const uint64_t dl = csgn_default_len(n_bits);
     for (uint64_t j = 0; j < width; ++j) {
         const uint64_t E = csgn::uint_pick_terms(op, index_width, (const u64 *)h_index_terms, width, rows, j);
         REQUIRE(E != 0, "pick: an index plane has no terms, or the term count overflows");
-        unsigned long long out_terms;                        // of output j; a product that wraps is past every limit
-        if (__builtin_mul_overflow((unsigned long long)terms, (unsigned long long)E, &out_terms))
-            out_terms = ~0ull;
-        if (int rc = check_size(batch, out_terms, out_terms, dl, "pick: output %llu", (unsigned long long)j))
+        if (int rc = check_index_output("pick", batch, terms, E, dl, j))
             return rc;
     }
     if (op == CSGN_UINT_PICK_EACH) {

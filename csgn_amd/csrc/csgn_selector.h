@@ -6,7 +6,9 @@
 // q * t_j + c of output j is (entry q of the stream) & (value term c).  A workgroup of 256 threads owns G elements, a
 // slice of KC units of every term and QP entries of the stream, for EVERY output; with fresh planes it builds its
 // subset tables (csgn_device.h) and decodes its entries into an LDS list once, for all of them.  An operation supplies
-// the decode of an entry, the address of the value unit and how it sizes G and QP.
+// the decode of an entry, the address of the value unit and how it sizes G and QP.  The two operations over the E
+// stream of an index, k_uint_read and k_uint_pick, share those as well: the index in the arguments,
+// the evaluation of an entry in both forms and the tile policy are in the E-stream section below, once.
 #pragma once
 
 #include "csgn_device.h"
@@ -125,22 +127,64 @@ __device__ __forceinline__ void sel_walk(const SelTile &t, const SelBlock<Unit> 
 
 // ------------------------------------------------------------------------------ the E stream of an index
 // The concatenation, ascending in r <= last_row, of the EQ rows of an index (csgn_uint_read.hip's term order), decoded
-// from the position: what k_uint_read and k_uint_pick share.  Args: v, s[k], F[k] (sel_index_fill) and last_row.
+// from the position.  What k_uint_read and k_uint_pick share: the index in the arguments (SelIndex), the walk, the
+// fresh decode, the evaluation of one entry in both forms (read_entry) and the tile policy (ReadTile).
+
+// x * y, saturated at kTermLimit
+inline u64 sat_mul(u64 x, u64 y)
+{
+    u64 p;
+    return term_mul(x, y, p) ? p : kTermLimit;
+}
+
+// The index of an E stream, by value in the kernel arguments (uniform, scalar loads).
+struct SelIndex {
+    const void *index[kReadMaxIndex];
+    u64 F[kReadMaxIndex];       // prod over i < k of (2 s_i + 1): a whole subtree below bit k (saturated; read only
+                                // where the subtree lies below the rows, so at most E)
+    u32 s[kReadMaxIndex];
+    u32 last_row, v;
+    SubsetTables tabs;
+
+    // Host: nv planes of terms[k] terms under `rows` rows.  Returns whether every plane is fresh.
+    bool fill(u64 nv, const u64 *terms, u64 rows)
+    {
+        v = (u32)nv;
+        last_row = (u32)(rows - 1);
+        bool fresh = true;
+        u64 f = 1;
+        for (u32 k = 0; k < v; ++k) {
+            s[k] = (u32)terms[k];
+            F[k] = f;
+            f = sat_mul(f, 2 * terms[k] + 1);
+            fresh = fresh && terms[k] == 1;
+        }
+        return fresh;
+    }
+
+    // Host: the planes of a launch that begins at element e0
+    template <typename Unit>
+    void advance(const u64 *const *planes, u64 e0, u32 U)
+    {
+        for (u32 k = 0; k < v; ++k)
+            index[k] = reinterpret_cast<const Unit *>(planes[k]) + e0 * s[k] * U;
+    }
+};
+static_assert(kReadMaxIndex == kPickMaxIndex, "k_uint_read and k_uint_pick share SelIndex");
 
 // q < E: the row r holding entry q of the E stream, and q's index inside r's block (the walk)
-template <typename Args>
-__device__ inline u32 read_walk(const Args &a, u64 q, u64 &in)
+__device__ inline u32 read_walk(const SelIndex &x, u64 q, u64 &in)
 {
     u32 r = 0;
     u64 H = 1;                  // prod of R_k over the bits fixed so far
     bool tight = true;          // the prefix equals that of rows - 1
-    for (u32 k = a.v; k-- > 0u;) {
-        const u64 s = a.s[k];
-        if (tight && !((a.last_row >> k) & 1u)) {
+    for (u32 k = x.v; k-- > 0u;) {
+        const u64 s = x.s[k];
+        if (tight && !((x.last_row >> k) & 1u)) {
             H *= s + 1u;
             continue;
         }
-        const u64 c0 = H * (s + 1u) * a.F[k];
+        const u64 c0 = H * (s + 1u) * x.F[k];
         if (q < c0) {
             H *= s + 1u;
             tight = false;
@@ -156,14 +200,14 @@ __device__ inline u32 read_walk(const Args &a, u64 q, u64 &in)
 
 // Fresh planes: the workgroup's range of the E stream into its LDS list, S in the low 16 bits, r in the high 16
 // (published by the tables' closing barrier)
-template <typename Args, typename Unit>
-__device__ inline void read_decode(const Args &a, const SelBlock<Unit> &b)
+template <typename Unit>
+__device__ inline void read_decode(const SelIndex &x, const SelBlock<Unit> &b)
 {
     for (u32 i = threadIdx.x; i < b.nq; i += 256u) {
         u64 in;
-        const u32 r = read_walk(a, b.q0 + i, in);
+        const u32 r = read_walk(x, b.q0 + i, in);
         u32 S = r;
-        for (u32 k = a.v; k-- > 0u;) {      // zero bits, the highest the fastest binary digit; digit 0 = x_k
+        for (u32 k = x.v; k-- > 0u;) {      // zero bits, the highest the fastest binary digit; digit 0 = x_k
             if ((r >> k) & 1u)
                 continue;
             if (!(in & 1u))
@@ -174,31 +218,63 @@ __device__ inline void read_decode(const Args &a, const SelBlock<Unit> &b)
     }
 }
 
+// Entry q = b.q0 + qi of the E stream at unit k = b.k0 + kk of element e = b.e0 + el: into v the selector unit, and
+// returns the row.  Fresh: P[S] from the tables, S and the row from the LDS list (the high 16 bits as the operation
+// left them there).  Else the walk, then the digits of q inside the row's block: mixed radix over R_k = r_k ? s_k :
+// s_k + 1 with k = 0 slowest; digit s_k (a zero bit only) selects ONE, any other digit that term of x_k.
+template <typename Unit, bool Fresh>
+__device__ __forceinline__ u32 read_entry(const SelIndex &x, const SelTile &t, const SelBlock<Unit> &b, u32 el, u64 e,
+                                          u32 qi, u64 q, u32 k, u32 kk, Unit &v)
+{
+    if (Fresh) {
+        const u32 cd = b.code[qi];
+        v = subset_and(b.tab, x.tabs, el, cd & 0xFFFFu, t.KC, kk);
+        return cd >> 16;
+    }
+    u64 in;
+    const u32 r = read_walk(x, q, in);
+    v = one_unit(Unit(), k, t.U, t.last_mask);
+    for (u32 kb = x.v; kb-- > 0u;) {
+        const u64 s = x.s[kb], R = ((r >> kb) & 1u) ? s : s + 1u;
+        const u64 dg = in % R;
+        in /= R;
+        if (dg < s)
+            v &= reinterpret_cast<const Unit *>(x.index[kb])[(e * s + dg) * t.U + k];
+    }
+    return r;
+}
+
 // ------------------------------------------------------------------------------ host side
 
-// x * y, saturated at kTermLimit
-inline u64 sat_mul(u64 x, u64 y)
-{
-    u64 p;
-    return term_mul(x, y, p) ? p : kTermLimit;
-}
+// The tile of the E-stream operations over a stream of E entries of which an element writes elem_units units (one
+// KC slice of every term of every output): G elements, `parts` parts of QP entries.
+struct ReadTile {
+    static constexpr u64 kLdsBudget = 32768;    // bytes of subset tables per workgroup
+    static constexpr u32 kMaxRange = 2048;      // E-stream entries one workgroup decodes (8 KB of LDS)
+    static constexpr u64 kPartUnits = 8192;     // units a workgroup writes at least, where the shape has them
+    u64 G, QP, parts;
 
-// The index of an E stream into the arguments: v, s[k] and F[k] = prod over i < k of (2 s_i + 1), a whole subtree below
-// bit k (saturated; read only where the subtree lies below the rows, so at most E).  Returns whether every plane is fresh.
-template <typename Args>
-inline bool sel_index_fill(Args &a, u64 v, const u64 *s)
-{
-    a.v = (u32)v;
-    bool fresh = true;
-    u64 f = 1;
-    for (u32 k = 0; k < v; ++k) {
-        a.s[k] = (u32)s[k];
-        a.F[k] = f;
-        f = sat_mul(f, 2 * s[k] + 1);
-        fresh = fresh && s[k] == 1;
+    // the tables and unit slices of v index planes at U units of unit_bytes
+    static SubsetPlan plan(bool fresh, u64 v, u32 U, u32 unit_bytes)
+    {
+        return subset_plan(fresh ? (u32)v : 0, U, unit_bytes, kLdsBudget);
     }
-    return fresh;
-}
+
+    static ReadTile of(const SubsetPlan &sp, u64 batch, u64 E, u64 elem_units)
+    {
+        // elements per workgroup: enough to give it kPartUnits to write, as many as the tables allow
+        u64 G = std::max<u64>(1, kPartUnits / elem_units);
+        G = std::min<u64>({G, sp.max_G, batch, 64});
+        G = std::max<u64>(G, 1);
+        // parts of the E stream: each writes kPartUnits or four times its table build, and decodes at most kMaxRange
+        const u64 build = G * sp.entries * sp.KC;
+        const u64 target = std::max<u64>(kPartUnits, 4 * build);
+        u64 parts = std::max<u64>(1, G * elem_units / target);
+        parts = std::max<u64>(parts, (E + kMaxRange - 1) / kMaxRange);
+        parts = std::min<u64>(parts, E);
+        return {G, (E + parts - 1) / parts, parts};
+    }
+};
 
 // The LDS of fresh planes: the tables of G elements (their layout into `first`), then, with G2, a second set for G2
 // elements (into `second`), then the QP decoded entries.  Sets the tile's offsets; returns the bytes.

@@ -1,17 +1,18 @@
 // csgn_uint_pick.hip -- an encrypted integer shifted, rotated or indexed by an ENCRYPTED amount, every output plane in
 // one launch.  Hand-written CDNA4 (gfx950) HIP; the kernel skeleton in csgn_selector.h, design notes in DESIGN.md §4.24.
 //
-// The definition (include/csgn_hip.h, csgn_uint_pick) is out_j = sum over r < rows_j, ascending, of
-// EQ(index, r) * a_{src(j, r)}: csgn_uint_read's sum with the value taken from the element's OWN planes -- plane j - r
-// (SHL), j + r (SHR), (j -+ r) mod w (ROTL / ROTR), or plane j of the element's row r (EACH) -- and with the E stream
-// (csgn_uint_read.hip's, decoded by csgn_selector.h's walk) cut per output: rows are concatenated ascending, so the
-// stream of rows_j rows is the first E_j entries of the stream of rows_max rows.  A workgroup decodes its range of THAT
-// stream once, against rows_max, and output j drops the entries q >= E_j; term q * t + c of output j is (entry q) &
-// (term c of the source).  Fresh index planes build the subset tables once per workgroup and spend them, and the
-// decoded list of (S, r), on all w outputs; multi-term index planes take the walk and the digits per unit (correct, not
-// fast).  The value units are per element: where a workgroup's slice of them fits (32 KB, the whole LDS within 64 KB) it
-// is staged in LDS behind the tables and the decoded range, else they are read with plain global loads through the
-// source pointers, which the row selects per lane, from a 512-byte LDS copy of the arguments' array.
+// The definition (include/csgn_hip.h, csgn_uint_pick) is out_j = sum over r < rows_j, ascending, of EQ(index, r) *
+// a_{src(j, r)}: csgn_uint_read's sum with the value taken from the element's OWN planes -- plane j - r (SHL), j + r
+// (SHR), (j -+ r) mod w (ROTL / ROTR), or plane j of the element's row r (EACH) -- and with the E stream
+// (csgn_uint_read.hip's; its index arguments, entry evaluation and tile policy are csgn_selector.h's, for both files)
+// cut per output: rows are concatenated ascending, so the stream of rows_j rows is the first E_j entries of the stream
+// of rows_max rows.  This file keeps the row key, the source map, the E_j cut and the staging.  A workgroup decodes its
+// range of THAT stream once, against rows_max, and output j drops the entries q >= E_j; term q * t + c of output j is
+// (entry q) & (term c of the source).  Fresh index planes build the subset tables once per workgroup and spend them,
+// and the decoded list of (S, r), on all w outputs; multi-term index planes take the walk and the digits per unit
+// (correct, not fast).  The value units are per element: where a workgroup's slice of them fits (32 KB, the whole LDS
+// within 64 KB) it is staged in LDS behind the tables and the decoded range, else they are read with plain global loads
+// through the source pointers, which the row selects per lane, from a 512-byte LDS copy of the arguments' array.
 #include "csgn_hip.h"
 #include "csgn_selector.h"
 
@@ -22,9 +23,6 @@ namespace csgn {
 
 namespace {
 
-constexpr u64 kLdsBudget = 32768;       // bytes of subset tables per workgroup
-constexpr u32 kMaxRange = 2048;         // E-stream entries one workgroup decodes (8 KB of LDS)
-constexpr u64 kPartUnits = 8192;        // units a workgroup writes at least, where the shape has them
 constexpr u64 kStageBytes = 32768;      // of value units a workgroup stages at most
 constexpr u64 kLdsTotal = 65536;        // of LDS a workgroup takes at most, the static pointer table included
 
@@ -33,15 +31,12 @@ constexpr u64 kLdsTotal = 65536;        // of LDS a workgroup takes at most, the
 struct PickArgs {
     SelTile tile;
     SelOutputs<kPickMaxPlanes> outs;
-    const void *index[kPickMaxIndex];
+    SelIndex x;
     const void *src[kPickMaxPlanes];
-    u64 F[kPickMaxIndex];
-    u32 s[kPickMaxIndex];
     u32 E[kPickMaxPlanes];      // E_j: output j takes the entries below it
-    u32 Emax, last_row, v;
+    u32 Emax;
     u32 op, w, n, tsrc;         // n: rows of an element's array (EACH), else 1
     u32 vbase;                  // byte offset of the staged value slice in the LDS (the Stage kernel)
-    SubsetTables tabs;
 };
 static_assert(sizeof(PickArgs) <= 4096, "the kernel arguments of k_uint_pick pass the 4 KiB limit");
 
@@ -80,12 +75,12 @@ __global__ void __launch_bounds__(256) k_uint_pick(PickArgs a)
         }
     }
     if (Fresh) {
-        read_decode(a, b);
+        read_decode(a.x, b);
         for (u32 i = threadIdx.x; i < b.nq; i += 256u) {          // the entries this thread has just decoded
             const u32 cd = b.code[i];
             b.code[i] = (cd & 0xFFFFu) | (pick_row_key(a.op, a.w, cd >> 16) << 16);
         }
-        subset_build(b.tab, a.tabs, a.index, t.G, t.KC, t.dKC, t.U, t.last_mask, b.e0, b.ne, b.k0, b.kc);
+        subset_build(b.tab, a.x.tabs, a.x.index, t.G, t.KC, t.dKC, t.U, t.last_mask, b.e0, b.ne, b.k0, b.kc);
     } else {
         __syncthreads();
     }
@@ -100,24 +95,9 @@ __global__ void __launch_bounds__(256) k_uint_pick(PickArgs a)
             const u64 e = b.e0 + el, q = (u64)b.q0 + qi;
             if (q >= Ej)
                 return false;
-            u32 r;
-            if (Fresh) {
-                const u32 cd = b.code[qi];
-                r = cd >> 16;
-                v = subset_and(b.tab, a.tabs, el, cd & 0xFFFFu, t.KC, kk);
-            } else {
-                u64 in;
-                const u32 row = read_walk(a, q, in);
-                v = one_unit(Unit(), k, t.U, t.last_mask);
-                for (u32 kb = a.v; kb-- > 0u;) {
-                    const u64 s = a.s[kb], R = ((row >> kb) & 1u) ? s : s + 1u;
-                    const u64 dg = in % R;
-                    in /= R;
-                    if (dg < s)
-                        v &= reinterpret_cast<const Unit *>(a.index[kb])[(e * s + dg) * t.U + k];
-                }
-                r = pick_row_key(a.op, a.w, row);
-            }
+            u32 r = read_entry<Unit, Fresh>(a.x, t, b, el, e, qi, q, k, kk, v);
+            if (!Fresh)
+                r = pick_row_key(a.op, a.w, r);         // the decoded list holds the key already
             u32 p = j;                  // the source plane and element (the op is uniform)
             u64 es = e;
             switch (a.op) {
@@ -196,36 +176,13 @@ bool pick_use_fused(int op, u64 batch, u64 rows)
 // with the plain loads or faster on every measured shape
 bool pick_stage() { return tune_choose(TUNE_UINT_PICK_STAGE, true); }
 
-struct PickTile {
-    u64 G, QP, KC, parts;
-};
-
-// The tile of the fused form, as read_fused sizes it, over the units an element really writes: sum_j E_j * t * KC.
-PickTile pick_tile(const SubsetPlan &sp, u64 batch, u64 Emax, u64 sumE, u64 t)
-{
-    const u64 elem_units = sumE * t * sp.KC;
-    u64 G = std::max<u64>(1, kPartUnits / elem_units);
-    G = std::min<u64>({G, sp.max_G, batch, 64});
-    G = std::max<u64>(G, 1);
-    const u64 build = G * sp.entries * sp.KC;
-    const u64 target = std::max<u64>(kPartUnits, 4 * build);
-    u64 parts = std::max<u64>(1, G * elem_units / target);
-    parts = std::max<u64>(parts, (Emax + kMaxRange - 1) / kMaxRange);
-    parts = std::min<u64>(parts, Emax);
-    return {G, (Emax + parts - 1) / parts, sp.KC, parts};
-}
-
 struct PickShape {
     u64 E[kPickMaxPlanes], Emax, sumE, rows_max;
-    bool fresh;
 };
 
 PickShape pick_shape(int op, u64 v, const u64 *s, u64 w, u64 rows)
 {
     PickShape p = {};
-    p.fresh = true;
-    for (u64 k = 0; k < v; ++k)
-        p.fresh = p.fresh && s[k] == 1;
     for (u64 j = 0; j < w; ++j) {
         p.E[j] = uint_pick_terms(op, v, s, w, rows, j);
         p.sumE += p.E[j];
@@ -245,15 +202,15 @@ hipError_t pick_fused(u64 n_bits, int op, u64 batch, u64 v, const u64 *const *in
     a.n = op == CSGN_UINT_PICK_EACH ? (u32)rows : 1u;
     a.tsrc = (u32)t;
     a.Emax = (u32)ps.Emax;
-    a.last_row = (u32)(ps.rows_max - 1);
-    const bool fresh = sel_index_fill(a, v, s);
-    const SubsetPlan sp = subset_plan(fresh ? (u32)v : 0, U, (u32)sizeof(Unit), kLdsBudget);
+    const bool fresh = a.x.fill(v, s, ps.rows_max);
+    const SubsetPlan sp = ReadTile::plan(fresh, v, U, (u32)sizeof(Unit));
     a.outs.fill(w, [&](u32) { return t; }, false, sp.KC);
     for (u32 j = 0; j < w; ++j)
         a.E[j] = (u32)ps.E[j];
-    const PickTile pt = pick_tile(sp, batch, ps.Emax, ps.sumE, t);
-    a.tile.set(n_bits, U, sp, pt.QP, ps.Emax, a.outs, pt.G);
-    u32 lds = fresh ? sel_lds_layout(a.tile, sp, a.tabs) : 0u;
+    // the tile over the units an element really writes, sum_j E_j * t * KC
+    const ReadTile rt = ReadTile::of(sp, batch, ps.Emax, ps.sumE * t * sp.KC);
+    a.tile.set(n_bits, U, sp, rt.QP, ps.Emax, a.outs, rt.G);
+    u32 lds = fresh ? sel_lds_layout(a.tile, sp, a.x.tabs) : 0u;
     // the value slice of a workgroup behind the decoded range, where it fits and the knob or the shape asks for it
     const u64 slice = (u64)a.tile.G * a.n * w * t * sp.KC * sizeof(Unit);
     const bool stage = fresh && slice <= kStageBytes &&
@@ -266,8 +223,7 @@ hipError_t pick_fused(u64 n_bits, int op, u64 batch, u64 v, const u64 *const *in
     return sel_launch(stage ? k_uint_pick<Unit, true, true> : k_uint_pick<Unit, true, false>,
                       k_uint_pick<Unit, false, false>, a, lds, launch_blocks(), batch,
                       (u64)a.tile.chunks * a.tile.qparts, st, [&](u64 e0) {
-        for (u32 k = 0; k < v; ++k)
-            a.index[k] = reinterpret_cast<const Unit *>(index[k]) + e0 * s[k] * U;
+        a.x.template advance<Unit>(index, e0, U);
         for (u32 j = 0; j < w; ++j) {
             a.src[j] = reinterpret_cast<const Unit *>(src[j]) + e0 * a.n * t * U;
             a.outs.out[j] = reinterpret_cast<Unit *>(out[j]) + e0 * t * ps.E[j] * U;
@@ -369,12 +325,13 @@ bool uint_pick_plan(u64 n_bits, int op, u64 batch, u64 v, const u64 *s, u64 w, u
     const u64 dL = (n_bits + 63) / 64;
     wide = wide && dL % 2 == 0;
     const PickShape ps = pick_shape(op, v, s, w, rows);
-    const SubsetPlan sp = subset_plan(ps.fresh ? (u32)v : 0, (u32)(wide ? dL / 2 : dL), wide ? 16u : 8u, kLdsBudget);
-    const PickTile pt = pick_tile(sp, batch, ps.Emax, ps.sumE, t);
-    plan[0] = pt.G;
-    plan[1] = pt.KC;
-    plan[2] = pt.QP;
-    plan[3] = (ps.Emax + pt.QP - 1) / pt.QP;
+    const bool fresh = SelIndex().fill(v, s, ps.rows_max);
+    const SubsetPlan sp = ReadTile::plan(fresh, v, (u32)(wide ? dL / 2 : dL), wide ? 16u : 8u);
+    const ReadTile rt = ReadTile::of(sp, batch, ps.Emax, ps.sumE * t * sp.KC);
+    plan[0] = rt.G;
+    plan[1] = sp.KC;
+    plan[2] = rt.QP;
+    plan[3] = (ps.Emax + rt.QP - 1) / rt.QP;
     return true;
 }
 

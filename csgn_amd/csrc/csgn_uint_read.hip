@@ -4,8 +4,8 @@
 // The definition (include/csgn_hip.h, csgn_uint_read) is out_j = sum over r < rows, ascending, of EQ(x, r) * d_{r,j}:
 // csgn_uint_plain's EQ row with k = r as the left operand, plane j of table element r as the right.  Term q * t_j + c of
 // output j is (term q of the E stream) & (term c of d_{r,j}), where the E stream is the concatenation, ascending in r,
-// of the EQ rows.  Nothing of it is tabulated: q is decoded (read_walk and read_decode of csgn_selector.h, which
-// csgn_uint_pick.hip shares) by
+// of the EQ rows.  Nothing of it is tabulated: q is decoded (csgn_selector.h's E-stream section, which holds the index
+// arguments, the evaluation of an entry in both forms and the tile policy for this file and csgn_uint_pick.hip) by
 //     the walk    from the top index bit down: below a fixed prefix of high bits a whole subtree holds
 //                 prod (2 s_k + 1) terms over its free bits, times the R_k of the bits already fixed, so each step
 //                 either skips the bit-0 subtree (bit 1) or enters it; while the prefix equals that of rows - 1 and
@@ -19,32 +19,23 @@
 // three, the AND of every subset of their planes) for its elements in LDS, decodes its range once into an LDS list of
 // (S, r), and every written unit is then 1-3 LDS reads ANDed with one unit of the table row -- a row every element
 // reads, so it hits in L2.  The table build and the decode are spent on all `w` outputs.  Multi-term index planes take
-// the walk and the digits per unit straight from the planes (correct, not fast).
+// the walk and the digits per unit straight from the planes (correct, not fast).  This file keeps the table address,
+// the outputs' term counts and the composed form.
 #include "csgn_hip.h"
 #include "csgn_selector.h"
-
-#include <algorithm>
 
 namespace csgn {
 
 namespace {
 
-constexpr u64 kLdsBudget = 32768;       // bytes of subset tables per workgroup
-constexpr u32 kMaxRange = 2048;         // E-stream entries one workgroup decodes (8 KB of LDS)
-constexpr u64 kPartUnits = 8192;        // units a workgroup writes at least, where the shape has them
-
-// By value in the kernel arguments (uniform, scalar loads); the stream is the E stream, output j has the terms of table
-// plane j.
+// By value in the kernel arguments (uniform, scalar loads); the stream is the E stream of index x, output j has the terms
+// of table plane j.
 struct ReadArgs {
     SelTile tile;
     SelOutputs<kReadMaxPlanes> outs;
-    const void *index[kReadMaxIndex];
+    SelIndex x;
     const void *table[kReadMaxPlanes];
-    u64 F[kReadMaxIndex];       // prod over i < k of (2 s_i + 1): a whole subtree below bit k (saturated; read only
-                                // where the subtree lies below rows, so at most E)
-    u32 s[kReadMaxIndex];
-    u32 E, last_row, v;
-    SubsetTables tabs;
+    u32 E;
 };
 static_assert(sizeof(ReadArgs) <= 4096, "the kernel arguments of k_uint_read pass the 4 KiB limit");
 
@@ -55,8 +46,8 @@ __global__ void __launch_bounds__(256) k_uint_read(ReadArgs a)
     const SelBlock<Unit> b = sel_block<Unit>(t, a.E);
 
     if (Fresh) {
-        read_decode(a, b);
-        subset_build(b.tab, a.tabs, a.index, t.G, t.KC, t.dKC, t.U, t.last_mask, b.e0, b.ne, b.k0, b.kc);
+        read_decode(a.x, b);
+        subset_build(b.tab, a.x.tabs, a.x.index, t.G, t.KC, t.dKC, t.U, t.last_mask, b.e0, b.ne, b.k0, b.kc);
     }
 
     for (u32 j = 0; j < a.outs.nout; ++j) {
@@ -66,23 +57,7 @@ __global__ void __launch_bounds__(256) k_uint_read(ReadArgs a)
         sel_walk<Unit>(t, b, a.outs, j, b.ne, [&](u32 el, u32 qi, u32 c, u32 kk, u64 &at, Unit &v) {
             const u32 k = b.k0 + kk;
             const u64 e = b.e0 + el, q = (u64)b.q0 + qi;
-            u32 r;
-            if (Fresh) {
-                const u32 cd = b.code[qi];
-                r = cd >> 16;
-                v = subset_and(b.tab, a.tabs, el, cd & 0xFFFFu, t.KC, kk);
-            } else {
-                u64 in;
-                r = read_walk(a, q, in);
-                v = one_unit(Unit(), k, t.U, t.last_mask);
-                for (u32 kb = a.v; kb-- > 0u;) {
-                    const u64 s = a.s[kb], R = ((r >> kb) & 1u) ? s : s + 1u;
-                    const u64 dg = in % R;
-                    in /= R;
-                    if (dg < s)
-                        v &= reinterpret_cast<const Unit *>(a.index[kb])[(e * s + dg) * t.U + k];
-                }
-            }
+            const u32 r = read_entry<Unit, Fresh>(a.x, t, b, el, e, qi, q, k, kk, v);
             v &= d[((u64)r * tj + c) * t.U + k];
             at = ((e * Tj) + q * tj + c) * t.U + k;
             return true;
@@ -114,31 +89,18 @@ hipError_t read_fused(u64 n_bits, u64 batch, u64 v, const u64 *const *index, con
 {
     ReadArgs a = {};
     a.E = (u32)E;
-    a.last_row = (u32)(rows - 1);
-    const bool fresh = sel_index_fill(a, v, s);
-    const SubsetPlan sp = subset_plan(fresh ? (u32)v : 0, U, (u32)sizeof(Unit), kLdsBudget);
+    const bool fresh = a.x.fill(v, s, rows);
+    const SubsetPlan sp = ReadTile::plan(fresh, v, U, (u32)sizeof(Unit));
     const u64 sumt = a.outs.fill(w, [&](u32 j) { return t[j]; }, false, sp.KC);
-    // elements per workgroup: enough to give it kPartUnits to write, as many as the tables allow
-    const u64 elem_units = E * sumt * sp.KC;
-    u64 G = std::max<u64>(1, kPartUnits / elem_units);
-    G = std::min<u64>({G, sp.max_G, batch, 64});
-    G = std::max<u64>(G, 1);
-    // parts of the E stream: each writes kPartUnits or four times its table build, and decodes at most kMaxRange
-    const u64 build = G * sp.entries * sp.KC;
-    const u64 target = std::max<u64>(kPartUnits, 4 * build);
-    u64 parts = std::max<u64>(1, G * elem_units / target);
-    parts = std::max<u64>(parts, (E + kMaxRange - 1) / kMaxRange);
-    parts = std::min<u64>(parts, E);
-    const u64 QP = (E + parts - 1) / parts;
-    a.tile.set(n_bits, U, sp, QP, E, a.outs, G);
-    const u32 lds = fresh ? sel_lds_layout(a.tile, sp, a.tabs) : 0u;
+    const ReadTile rt = ReadTile::of(sp, batch, E, E * sumt * sp.KC);
+    a.tile.set(n_bits, U, sp, rt.QP, E, a.outs, rt.G);
+    const u32 lds = fresh ? sel_lds_layout(a.tile, sp, a.x.tabs) : 0u;
     a.tile.xcd = stream_xcd(batch * E * sumt * U);
     for (u32 j = 0; j < w; ++j)
         a.table[j] = table[j];
     return sel_launch(k_uint_read<Unit, true>, k_uint_read<Unit, false>, a, lds, launch_blocks(), batch,
                       (u64)a.tile.chunks * a.tile.qparts, st, [&](u64 e0) {
-        for (u32 k = 0; k < v; ++k)
-            a.index[k] = reinterpret_cast<const Unit *>(index[k]) + e0 * s[k] * U;
+        a.x.template advance<Unit>(index, e0, U);
         for (u32 j = 0; j < w; ++j)
             a.outs.out[j] = reinterpret_cast<Unit *>(out[j]) + e0 * t[j] * E * U;
     });

@@ -286,23 +286,33 @@ def test_shift_matches_barrel_shifter_lookup(hip, knobs, oracle):
         assert [int(g) for g in got] == [clear_pick(op, w, 0, int(x), int(dd)) for x, dd in zip(xs, ds)], op
 
 
+@pytest.mark.parametrize("s", [[1, 1, 1, 1], [1, 2, 1, 1]], ids=["fresh", "mixed"])
 @pytest.mark.parametrize("n_bits", [129, 1247])
-def test_each_of_equal_arrays_is_the_shared_read(hip, knobs, n_bits):
-    """Every element's array the same table: csgn_uint_read of that one table has IDENTICAL words."""
+def test_each_of_equal_arrays_is_the_shared_read(hip, knobs, n_bits, s):
+    """Every element's array the same table: csgn_uint_read of that one table has IDENTICAL words, in every form of
+    either operation, with fresh index planes (the tables and the decoded list) and mixed ones (the walk and the
+    digits per unit)."""
     v, n, w, batch = 4, 11, 3, 9
-    index = [rand_terms(n_bits, batch, sk, 1300 + k) for k, sk in enumerate([1, 2, 1, 1])]
+    index = [rand_terms(n_bits, batch, sk, 1300 + k) for k, sk in enumerate(s)]
     table = [rand_terms(n_bits, n, 2, 1310 + j) for j in range(w)]
     a = [np.tile(p, (batch, 1, 1)) for p in table]
     dx = [hip.upload(p.ravel()) for p in index]
     dt = [hip.upload(p.ravel()) for p in table]
-    read = [hip.download(o) for o in hip.uint_read(n_bits, batch, dx, [1, 2, 1, 1], n, dt, [2] * w)]
     want = [x.ravel() for x in np_read_fast(n_bits, index, table)]
+    reads = {}
     for fused in (-1, 0, 1):
+        knobs.set("uint_read_fused", fused)
+        reads[fused] = [hip.download(o) for o in hip.uint_read(n_bits, batch, dx, s, n, dt, [2] * w)]
+        for j in range(w):
+            assert np.array_equal(reads[fused][j], want[j]), ("read", fused, j)
+    for fused, stage in ((-1, -1), (0, -1), (1, -1), (1, 0), (1, 1)):
         knobs.set("uint_pick_fused", fused)
+        knobs.set("uint_pick_stage", stage)
         got = run(hip, n_bits, EACH, index, a, n)
         for j in range(w):
-            assert np.array_equal(got[j], read[j]), (fused, j)
-            assert np.array_equal(got[j], want[j]), (fused, j)
+            for rf, read in reads.items():
+                assert np.array_equal(got[j], read[j]), (fused, stage, rf, j)
+            assert np.array_equal(got[j], want[j]), (fused, stage, j)
 
 
 def test_pick_graph_capture_and_replay(hip, knobs):

@@ -6,7 +6,7 @@ copies to pass the 256 MiB memory-side cache.  One JSON line per case: median mi
 E, the algorithmic bytes (outputs written once + index and table planes read once) and the fused form's share of
 8 TB/s.
 
-    python tools/bench_uint_read.py [--n 1247] [--reps 10] [--today-max-gb 2000] [--composed-max-launches 20000]
+    python tools/bench_uint_read.py [--n 1247] [--reps 10] [--today-max-gb 2000] [--composed-max-launches 20000] [--only K]
 """
 import argparse
 import ctypes as C
@@ -66,11 +66,14 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--today-max-gb", type=float, default=2000.0, help="GB of copies today's route makes, at most")
     ap.add_argument("--composed-max-launches", type=int, default=20000)
+    ap.add_argument("--only", type=int, default=-1, help="the one shape to run (its position in the list)")
     args = ap.parse_args()
     hip = HipPath(0)
     lib, n = hip.lib, args.n
     dl = hip.default_len(n)
-    for v, rows, w, m in shapes():
+    for k, (v, rows, w, m) in enumerate(shapes()):
+        if args.only >= 0 and k != args.only:
+            continue
         s = (C.c_uint64 * v)(*([1] * v))
         t = (C.c_uint64 * w)(*([1] * w))
         E = int(lib.csgn_uint_read_terms(v, s, rows))
