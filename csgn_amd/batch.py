@@ -414,6 +414,31 @@ class HipPath:
         check(self.lib.csgn_uint_pick(n_bits, op, batch, v, h_x, h_s, w, rows, h_a, int(terms), h_out, self.stream))
         return [o[: batch * int(terms) * e * dl] for o, e in zip(outs, E)]
 
+    def uint_write(self, n_bits: int, batch: int, index, index_terms, rows: int, value, value_terms, arrays,
+                   array_terms, outs=None):
+        """csgn_uint_write: element e's own array of `rows` rows (the elements e * rows .. e * rows + rows - 1 of the
+        planes `arrays`, plane j uniform with array_terms[j] terms) written with `value` (plane j a uniform batch of
+        value_terms[j] terms) at its encrypted index `index` (bit 0 first; plane k a uniform batch of index_terms[k]
+        terms).  One tensor per plane, A_j terms per array (A_j = csgn_uint_write_offset at r = rows), rows ragged
+        inside it; fresh ones unless `outs` is given."""
+        v, w = len(index), len(value)
+        assert v == len(index_terms) and w == len(value_terms) == len(arrays) == len(array_terms)
+        h_s = (C.c_uint64 * max(v, 1))(*[int(t) for t in index_terms])
+        h_tv = (C.c_uint64 * max(w, 1))(*[int(t) for t in value_terms])
+        h_td = (C.c_uint64 * max(w, 1))(*[int(t) for t in array_terms])
+        A = [int(self.lib.csgn_uint_write_offset(v, h_s, rows, rows, int(tv), int(td)))
+             for tv, td in zip(value_terms, array_terms)]
+        assert w and all(A), "bad index width, rows or term count"
+        dl = self.default_len(n_bits)
+        if outs is None:
+            outs = [self.empty_words(max(batch * a * dl, 1)) for a in A]
+        h_x = (C.c_void_p * max(v, 1))(*[_ptr(p) for p in index])
+        h_v = (C.c_void_p * max(w, 1))(*[_ptr(p) for p in value])
+        h_d = (C.c_void_p * max(w, 1))(*[_ptr(p) for p in arrays])
+        h_out = (C.c_void_p * max(w, 1))(*[_ptr(o) for o in outs])
+        check(self.lib.csgn_uint_write(n_bits, batch, v, h_x, h_s, rows, w, h_v, h_tv, h_d, h_td, h_out, self.stream))
+        return [o[: batch * a * dl] for o, a in zip(outs, A)]
+
     def uint_lt_select(self, n_bits: int, batch: int, a, a_terms, b, b_terms, xs, x_terms, ys, y_terms, outs=None,
                        less=False):
         """csgn_uint_lt_select: request i is a < b ? xs[i] : ys[i] for the encrypted integers a and b (bit 0 first; plane

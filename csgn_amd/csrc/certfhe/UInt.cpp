@@ -1302,6 +1302,118 @@ CiphertextBatch readAtEach(const CiphertextBatch &arrays, uint64_t n, const UInt
     return pickPlanes(CSGN_UINT_PICK_EACH, std::vector<CiphertextBatch>(1, arrays), n, index, "readAtEach")[0];
 }
 
+// ------------------------------------------------------------------ encrypted arrays written at encrypted indices
+
+namespace {
+
+// terms of row r by the definition itself: EQ(index, r)'s terms times (tv + td), plus td; 0 once it passes kMaxWords
+uint64_t writeRowTerms(const std::vector<uint64_t> &s, uint64_t r, uint64_t tv, uint64_t td)
+{
+    uint64_t p = tv + td;
+    for (size_t k = 0; k < s.size() && p <= kMaxWords; ++k)
+        p *= (k < 64 && ((r >> k) & 1u)) ? s[k] : s[k] + 1;
+    return p > kMaxWords ? 0 : p + td;
+}
+
+// every plane of the arrays with row index[e] of array e replaced by value[e]
+std::vector<CiphertextBatch> writePlanes(const std::vector<CiphertextBatch> &arrays, uint64_t n, const UIntBatch &index,
+                                         const std::vector<CiphertextBatch> &value, const char *who)
+{
+    const Context &ctx = index.context();
+    const uint64_t v = index.width(), m = index.size();
+    const unsigned w = (unsigned)arrays.size();
+    const std::string name = std::string("certFHE::") + who;
+    if (value.size() != w)
+        throw std::invalid_argument(name + ": the arrays and the value differ in width");
+    if (n == 0 || (v < 64 && n > (1ull << v)))
+        throw std::invalid_argument(name + ": " + std::to_string(n) + " rows an array, not 1..2^" + std::to_string(v));
+    if (m != 0 && n > ~0ull / m)
+        throw std::invalid_argument(name + ": the arrays do not hold n rows for every index");
+    for (unsigned j = 0; j < w; ++j)
+        if (!sameContext(arrays[j].context(), ctx) || !sameContext(value[j].context(), ctx) || value[j].size() != m ||
+            arrays[j].size() != n * m)
+            throw std::invalid_argument(name + ": the arrays, the index and the value differ in context or count, or "
+                                               "arrays.size() != n * index.size()");
+    if (m == 0)
+        return makePlanes(ctx, 0, std::vector<uint64_t>(w, 1));     // an empty batch has no sizes to check: empty planes
+    const Planes x(index), val(value), d(arrays);
+    const bool fused = x.uniform && val.uniform && d.uniform && v <= 16;
+    const uint64_t limit = (kMaxWords - 1) / ctx.getDefaultN();      // terms of one array
+    const std::string too_large = name + ": an array exceeds 2^31 words (the index is too wide or has too many terms)";
+    if (fused) {
+        // row offsets of period n, on the host in closed form
+        std::vector<CiphertextBatch> out;
+        std::vector<std::vector<uint64_t> > offsets(w, std::vector<uint64_t>(n * m + 1));
+        for (unsigned j = 0; j < w; ++j) {
+            const uint64_t A = csgn_uint_write_offset(v, x.terms.data(), n, n, val.terms[j], d.terms[j]);
+            if (A == 0 || A > limit || m > (1ull << 60) / (A * ctx.getDefaultN()))
+                throw std::invalid_argument(too_large);
+            std::vector<uint64_t> &off = offsets[j];
+            for (uint64_t r = 0; r < n; ++r)
+                off[r] = csgn_uint_write_offset(v, x.terms.data(), n, r, val.terms[j], d.terms[j]);
+            for (uint64_t e = 1; e < m; ++e)
+                for (uint64_t r = 0; r < n; ++r)
+                    off[e * n + r] = e * A + off[r];
+            off[n * m] = m * A;
+        }
+        for (unsigned j = 0; j < w; ++j)
+            out.push_back(BatchAccess::makeRagged(ctx, offsets[j]));
+        detail::check(csgn_uint_write(ctx.getN(), m, v, sources(x).data(), x.terms.data(), n, w, sources(val).data(),
+                                      val.terms.data(), sources(d).data(), d.terms.data(), wordsOf(out).data(),
+                                      detail::stream()),
+                      "csgn_uint_write");
+        return out;
+    }
+    // ragged planes or a wider index: the definition itself through the operators.  Sizes first, by the planes' bounds
+    for (unsigned j = 0; j < w; ++j) {
+        uint64_t A = 0;
+        for (uint64_t r = 0; r < n; ++r) {
+            const uint64_t row = writeRowTerms(x.terms, r, val.terms[j], d.terms[j]);
+            A += row;
+            if (row == 0 || A > limit)
+                throw std::invalid_argument(too_large);
+        }
+    }
+    std::vector<std::vector<CiphertextBatch> > rows(w);
+    std::vector<uint64_t> idx(m);
+    for (uint64_t r = 0; r < n; ++r) {
+        const CiphertextBatch eq = equalTo(index, r);
+        for (uint64_t e = 0; e < m; ++e)
+            idx[e] = e * n + r;
+        for (unsigned j = 0; j < w; ++j)
+            rows[j].push_back(logicMux(eq, value[j], arrays[j].gather(idx)));
+    }
+    // row-major over r to the arrays' layout: element e * n + r is element r * m + e of the concatenation
+    std::vector<uint64_t> perm(n * m);
+    for (uint64_t e = 0; e < m; ++e)
+        for (uint64_t r = 0; r < n; ++r)
+            perm[e * n + r] = r * m + e;
+    std::vector<CiphertextBatch> out;
+    for (unsigned j = 0; j < w; ++j)
+        out.push_back(CiphertextBatch::concat(rows[j]).gather(perm));
+    return out;
+}
+
+} // namespace
+
+UIntBatch writeAtEach(const UIntBatch &arrays, uint64_t n, const UIntBatch &index, const UIntBatch &value)
+{
+    return UIntBatch::fromPlanes(writePlanes(planesOf(arrays), n, index, planesOf(value), "writeAtEach"));
+}
+
+CiphertextBatch writeAtEach(const CiphertextBatch &arrays, uint64_t n, const UIntBatch &index, const CiphertextBatch &value)
+{
+    return writePlanes(std::vector<CiphertextBatch>(1, arrays), n, index, std::vector<CiphertextBatch>(1, value),
+                       "writeAtEach")[0];
+}
+
+UIntBatch writeAt(const UIntBatch &table, const UIntBatch &index, const UIntBatch &value)
+{
+    if (index.size() != 1)
+        throw std::invalid_argument("certFHE::writeAt: one index and one value write one table");
+    return UIntBatch::fromPlanes(writePlanes(planesOf(table), table.size(), index, planesOf(value), "writeAt"));
+}
+
 // ------------------------------------------------------------------ counting (csgn_count)
 
 namespace {

@@ -118,6 +118,15 @@ inline void *stream() { return nullptr; }   // the classes run on the default st
 struct BatchAccess {
     static CiphertextBatch make(const Context &c, uint64_t count, uint64_t terms) { return CiphertextBatch(c, count, terms); }
     static uint64_t *words(CiphertextBatch &b) { return b.payload->data(); }
+    // a fresh RAGGED batch of offsets.size() - 1 elements whose term offsets the host knows in closed form
+    static CiphertextBatch makeRagged(const Context &c, const std::vector<uint64_t> &offsets)
+    {
+        CiphertextBatch b(c, 0, 0);
+        b.count_ = offsets.size() - 1;
+        b.payload = allocWords(offsets.back() * c.getDefaultN());
+        b.offsets_ = offsets;
+        return b;
+    }
 };
 
 // ONE for every element of `like`

@@ -1501,6 +1501,78 @@ int csgn_uint_pick(uint64_t n_bits, int op, uint64_t batch, uint64_t index_width
     return CSGN_OK;
 }
 
+/* ------------------------------------------- encrypted arrays written at encrypted indices ---- */
+
+uint64_t csgn_uint_write_offset(uint64_t index_width, const uint64_t *h_index_terms, uint64_t rows, uint64_t r,
+                                uint64_t t_value, uint64_t t_array)
+{
+    return csgn::uint_write_offset(index_width, (const u64 *)h_index_terms, rows, r, t_value, t_array);
+}
+
+const char *csgn_uint_write_kernel(uint64_t n_bits, uint64_t batch, uint64_t index_width, const uint64_t *h_index_terms,
+                                   uint64_t rows, uint64_t width, const uint64_t *h_value_terms,
+                                   const uint64_t *h_array_terms)
+{
+    return csgn::uint_write_kernel_name(n_bits, batch, index_width, (const u64 *)h_index_terms, rows, width,
+                                        (const u64 *)h_value_terms, (const u64 *)h_array_terms);
+}
+
+int csgn_uint_write_plan(uint64_t n_bits, uint64_t batch, uint64_t index_width, const uint64_t *h_index_terms,
+                         uint64_t rows, uint64_t width, const uint64_t *h_value_terms, const uint64_t *h_array_terms,
+                         int wide_units, uint64_t *h_plan)
+{
+    REQUIRE(h_plan, "null host pointer");
+    REQUIRE(csgn::uint_write_plan(n_bits, batch, index_width, (const u64 *)h_index_terms, rows, width,
+                                  (const u64 *)h_value_terms, (const u64 *)h_array_terms, wide_units != 0,
+                                  (u64 *)h_plan),
+            "write plan: an invalid shape or an empty batch");
+    return CSGN_OK;
+}
+
+int csgn_uint_write(uint64_t n_bits, uint64_t batch, uint64_t index_width, const uint64_t *const *h_index,
+                    const uint64_t *h_index_terms, uint64_t rows, uint64_t width, const uint64_t *const *h_value,
+                    const uint64_t *h_value_terms, const uint64_t *const *h_arrays, const uint64_t *h_array_terms,
+                    uint64_t *const *h_out, void *stream)
+{
+    if (int rc = check_n(n_bits))
+        return rc;
+    if (int rc = check_index("write", index_width, "width", width, rows))
+        return rc;
+    REQUIRE(h_index && h_index_terms && h_value && h_value_terms && h_arrays && h_array_terms && h_out,
+            "null host pointer");
+    const uint64_t E = csgn::uint_read_terms(index_width, (const u64 *)h_index_terms, rows);
+    REQUIRE(E != 0, "write: an index plane has no terms, or the term count overflows");
+    for (uint64_t j = 0; j < width; ++j) {
+        REQUIRE(h_value_terms[j] != 0 && h_value_terms[j] < (1ull << 62), "write: value plane %llu of %llu terms",
+                (unsigned long long)j, (unsigned long long)h_value_terms[j]);
+        REQUIRE(h_array_terms[j] != 0 && h_array_terms[j] < (1ull << 62), "write: array plane %llu of %llu terms",
+                (unsigned long long)j, (unsigned long long)h_array_terms[j]);
+        // A_j = E * (tv + td) + rows * td; a sum or product that wraps is past every limit
+        unsigned long long prod, tail, all;
+        if (__builtin_mul_overflow((unsigned long long)E, (unsigned long long)(h_value_terms[j] + h_array_terms[j]),
+                                   &prod) ||
+            __builtin_mul_overflow((unsigned long long)rows, (unsigned long long)h_array_terms[j], &tail) ||
+            __builtin_add_overflow(prod, tail, &all))
+            all = ~0ull;
+        if (int rc = check_size(batch, all, all, csgn_default_len(n_bits), "write: output %llu", (unsigned long long)j))
+            return rc;
+    }
+    if (int rc = require_device("csgn_uint_write"))
+        return rc;
+    if (batch == 0)
+        return CSGN_OK;
+    if (int rc = check_planes(h_index, nullptr, index_width, "index plane"))
+        return rc;
+    if (int rc = check_planes(h_value, nullptr, width, "value plane"))
+        return rc;
+    if (int rc = check_planes(h_arrays, h_out, width, "array plane or output"))
+        return rc;
+    HIP_TRY(csgn::uint_write(n_bits, batch, index_width, (const u64 *const *)h_index, (const u64 *)h_index_terms, rows,
+                             width, (const u64 *const *)h_value, (const u64 *)h_value_terms,
+                             (const u64 *const *)h_arrays, (const u64 *)h_array_terms, (u64 *const *)h_out, S(stream)));
+    return CSGN_OK;
+}
+
 /* ------------------------------------------------ encrypted tables by encrypted key ---- */
 
 uint64_t csgn_uint_find_terms(uint64_t key_width, const uint64_t *h_key_terms, const uint64_t *h_query_terms)

@@ -247,12 +247,27 @@ bool uint_pick_plan(u64 n_bits, int op, u64 batch, u64 v, const u64 *s, u64 w, u
 hipError_t uint_pick(u64 n_bits, int op, u64 batch, u64 v, const u64 *const *index, const u64 *s, u64 w, u64 rows,
                      const u64 *const *src, u64 t, u64 *const *out, hipStream_t stream);
 
+// encrypted arrays written at encrypted indices (csgn_uint_write.hip), include/csgn_hip.h's definition: row r of element
+// e's array in plane j becomes (EQ(index_e, r) * (value_{e,j} + d_{e*n+r,j})) + d_{e*n+r,j}.  index planes: v = 1..16,
+// terms s[k]; value planes: w = 1..64, terms tv[j]; array planes: batch * rows elements, terms td[j].
+constexpr u32 kWriteMaxIndex = 16, kWriteMaxPlanes = 64;
+// the term offset of row r <= rows inside its array (r = rows: the array's terms A); 0: invalid argument or 2^62 or more
+u64 uint_write_offset(u64 v, const u64 *s, u64 rows, u64 r, u64 tv, u64 td);
+const char *uint_write_kernel_name(u64 n_bits, u64 batch, u64 v, const u64 *s, u64 rows, u64 w, const u64 *tv,
+                                   const u64 *td);
+// the fused form's tile: plan = {G, KC, QP, q parts}; wide: 16-byte units where dL is even.  false: invalid shape
+bool uint_write_plan(u64 n_bits, u64 batch, u64 v, const u64 *s, u64 rows, u64 w, const u64 *tv, const u64 *td,
+                     bool wide, u64 plan[4]);
+hipError_t uint_write(u64 n_bits, u64 batch, u64 v, const u64 *const *index, const u64 *s, u64 rows, u64 w,
+                      const u64 *const *value, const u64 *tv, const u64 *const *arrays, const u64 *td, u64 *const *out,
+                      hipStream_t stream);
+
 // The temporaries of the composed forms and of the gather plan (csgn_scratch.cpp): a plain (hipMalloc) block the calling
 // thread keeps per stream and per user, never the stream-ordered pool.  Returns the block, or nullptr with e set
 // (hipErrorStreamCaptureUnsupported when the call would have to allocate while s is capturing).  owned: the block is
 // past the kept size and belongs to this call; scratch_done frees it behind the call's launches (waits for the device)
 // and passes e through.
-enum ScratchSlot { SCRATCH_UINT_PLAIN, SCRATCH_UINT_LUT, SCRATCH_UINT_READ, SCRATCH_UINT_ADDK, SCRATCH_UINT_FIND, SCRATCH_GATHER, SCRATCH_MATMUL, SCRATCH_COUNT, SCRATCH_UINT_LT_SELECT, SCRATCH_UINT_PICK, SCRATCH_SLOTS };
+enum ScratchSlot { SCRATCH_UINT_PLAIN, SCRATCH_UINT_LUT, SCRATCH_UINT_READ, SCRATCH_UINT_ADDK, SCRATCH_UINT_FIND, SCRATCH_GATHER, SCRATCH_MATMUL, SCRATCH_COUNT, SCRATCH_UINT_LT_SELECT, SCRATCH_UINT_PICK, SCRATCH_UINT_WRITE, SCRATCH_SLOTS };
 u64 *scratch_take(ScratchSlot slot, size_t bytes, hipStream_t s, bool &owned, hipError_t &e);
 hipError_t scratch_done(u64 *block, bool owned, hipError_t e);
 

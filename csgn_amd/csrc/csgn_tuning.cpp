@@ -44,6 +44,7 @@ const Knob kKnobs[TUNE_COUNT] = {
     {"uint_lt_select_form", -1},
     {"uint_pick_fused", -1},
     {"uint_pick_stage", -1},
+    {"uint_write_fused", -1},
     {"launch_blocks", 0},
 };
 

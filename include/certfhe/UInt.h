@@ -67,6 +67,23 @@
 // width past 16, keys.size() != values.size(), no rows, or an output past 2^31 words per element.  An empty query batch
 // gives empty planes.
 //
+// ENCRYPTED ARRAYS WRITTEN AT ENCRYPTED INDICES: writeAtEach(arrays, n, index, value) returns the arrays of readAtEach's
+// layout (element e owns rows e * n .. e * n + n - 1) with row index[e] of array e replaced by value[e]: a private
+// counter table, an oblivious register file, one step of an oblivious RAM, a per-record field update.  Element e * n + r
+// of plane j is logicMux(equalTo(index, r), value_j, arrays_j) = (EQ * (value + d)) + d on elements e and e * n + r --
+// the EQ row of csgn_uint_plain with k = r as the LEFT operand -- csgn_uint_write's words (include/csgn_hip.h).  It
+// decrypts to the arrays, with value[e] in row index[e] where index[e] < n.  Row r has P_r * (tv + td) + td terms for
+// value planes of tv and array planes of td terms, P_r the terms of equalTo(index, r) (fresh planes: 2^zeros(r)), so
+// the result's planes are RAGGED CiphertextBatches in a pattern of period n; their offsets are computed on the host
+// (csgn_uint_write_offset), with no device round trip, and termsOf(e * n + r) gives each row's size.  Everything that
+// takes ragged planes reads them back: readAtEach(writeAtEach(a, n, i, x), n, i) decrypts to x where i < n.
+// writeAt(table, index, value) is the same for ONE index and value and n = table.size().  Uniform operands under an
+// index of at most 16 bits take one csgn_uint_write (one launch for every plane, the rows' raw copies included);
+// ragged operands (a compact() result) and wider indices are composed from equalTo(index, r), gather, logicMux, concat
+// and a permuting gather, with the same words.  Every size is computed before anything is allocated:
+// std::invalid_argument for mismatched contexts, widths or counts, n of 0 or past 2^index.width(), arrays.size() !=
+// n * index.size(), or an array past 2^31 words.  An empty batch gives empty planes.
+//
 // ARITHMETIC WITH A PUBLIC CONSTANT (k < 2^width, the same for every element; std::invalid_argument otherwise) spends no
 // term on k: with m the lowest set bit of k the carry into plane j > m is the chain c_m = a_m, then k_j ? (c * n_j) + a_j
 // : c * a_j (n_j = logicNot(a_j), c the LEFT operand), and the words are csgn_uint_addk's (include/csgn_hip.h):
@@ -283,6 +300,14 @@ CiphertextBatch readAt(const CiphertextBatch &table, const UIntBatch &index);
 // element e: arrays[e * n + index[e]] where index[e] < n, else 0; arrays.size() == n * index.size(), 1 <= n <= 2^v
 UIntBatch readAtEach(const UIntBatch &arrays, uint64_t n, const UIntBatch &index);
 CiphertextBatch readAtEach(const CiphertextBatch &arrays, uint64_t n, const UIntBatch &index);
+
+// the arrays with element e * n + index[e] replaced by value[e] where index[e] < n; arrays.size() == n * index.size(),
+// 1 <= n <= 2^v, value of the arrays' width and the index's count.  The result's planes are ragged (see above)
+UIntBatch writeAtEach(const UIntBatch &arrays, uint64_t n, const UIntBatch &index, const UIntBatch &value);
+CiphertextBatch writeAtEach(const CiphertextBatch &arrays, uint64_t n, const UIntBatch &index,
+                            const CiphertextBatch &value);
+// ONE index and value: the table with row index[0] replaced; writeAtEach with n = table.size()
+UIntBatch writeAt(const UIntBatch &table, const UIntBatch &index, const UIntBatch &value);
 
 // element e: XOR over rows r with keys[r] == query[e] of values[r]  (distinct keys: the matching value, else 0)
 UIntBatch readWhere(const UIntBatch &keys, const UIntBatch &values, const UIntBatch &query);

@@ -990,6 +990,65 @@ int csgn_uint_pick(uint64_t n_bits, int op, uint64_t batch, uint64_t index_width
                    const uint64_t *h_index_terms, uint64_t width, uint64_t rows, const uint64_t *const *h_a,
                    uint64_t terms, uint64_t *const *h_out, void *stream);
 
+/* ------------------------------------------- encrypted arrays written at encrypted indices ---- */
+
+/* ENCRYPTED arrays written at ENCRYPTED indices: a private counter table, an oblivious register file, one step of an
+ * oblivious RAM.  Index: index_width = v planes x_0..x_{v-1} (bit 0 first, v in 1..16) of `batch` elements, plane k
+ * uniform with s_k terms per element.  Value: `width` = w planes (1..64) of `batch` elements, plane j uniform with tv_j
+ * terms.  Arrays: w planes of batch * n elements (`rows` = n, 1 <= n <= 2^v), plane j uniform with td_j terms; element
+ * e's array is the elements e * n .. e * n + n - 1 (csgn_uint_pick's EACH layout).  Output: w planes of batch * n
+ * elements.  A fixed composition of the reference's operator+ / operator* with ONE: element e * n + r of plane j is
+ *     logicMux(EQ(x_e, r), value_{e,j}, d_{e*n+r,j})  =  (EQ(x_e, r) * (value_{e,j} + d_{e*n+r,j})) + d_{e*n+r,j}
+ *     EQ(x, r)   csgn_uint_plain's EQ row with k = r, the LEFT operand of the product, exactly as in csgn_uint_read;
+ *                the sum inside is operator+, a concatenation with the value's terms first
+ * Decrypts to the arrays with row x_e of array e replaced by value_e, and to the arrays unchanged where x_e >= n.
+ * Terms: row r has P_r * (tv_j + td_j) + td_j,  P_r = prod_k R_k(r),  R_k(r) = r_k ? s_k : s_k + 1: the output is
+ * RAGGED over r in a pattern of period n (fresh planes: 2^zeros(r) * (tv + td) + td).  Every whole array has
+ * A_j = E * (tv_j + td_j) + n * td_j terms, E = csgn_uint_read_terms(v, s, n); row r begins at term
+ * csgn_uint_write_offset(v, s, n, r, tv_j, td_j) = csgn_uint_read_terms(v, s, r) * (tv_j + td_j) + r * td_j of its array.
+ * Fresh planes: 62 terms per array and plane at v = 3, n = 8; 13 378 at v = 8, n = 256 -- an equality's growth, as for
+ * csgn_uint_read.
+ * Term order: inside row r, term (q, c) of the product at q * (tv_j + td_j) + c with q the entry of EQ(x, r)
+ * (csgn_uint_read's order inside a block) and c < tv_j the value term, else array term c - tv_j; the td_j terms of
+ * d_{e*n+r,j} follow. */
+/* The term offset of row r inside its array for r in 0..rows (host only); r = rows gives A.  0 for an invalid shape
+ * (index_width outside 1..16, rows outside 1..2^index_width, r > rows, a null pointer, a term count of 0) or a count of
+ * 2^62 or more -- and for r = 0, where the offset IS 0: test validity with r = rows. */
+uint64_t csgn_uint_write_offset(uint64_t index_width, const uint64_t *h_index_terms, uint64_t rows, uint64_t r,
+                                uint64_t t_value, uint64_t t_array);
+/* Which form a csgn_uint_write call of this shape takes (host only, a static string): "k_uint_write" (one kernel writes
+ * every output plane, the rows' raw copies included, planes read in place) or "composed" (per row r: csgn_uint_plain's
+ * EQ into a temporary the calling thread keeps (csgn_uint_addk's rules for its composed form), csgn_gather_planes of the
+ * elements e * n + r -- the list e * n is uploaded, and waited for, once a call --, then per plane csgn_add_uniform of
+ * value and row, csgn_mul_uniform into the row's place and the strided copy of the row behind it).  Knob
+ * "uint_write_fused" (-1 per shape, 0 / 1 forced) decides; the words are the same.  Per shape: fused for every shape
+ * (batch * n of 2^32 or more is fused whatever the knob says: the gather's counts stop there).  "" for an invalid
+ * shape. */
+const char *csgn_uint_write_kernel(uint64_t n_bits, uint64_t batch, uint64_t index_width, const uint64_t *h_index_terms,
+                                   uint64_t rows, uint64_t width, const uint64_t *h_value_terms,
+                                   const uint64_t *h_array_terms);
+/* The fused form's tile for this shape (host only), for tests and tools: h_plan[0..3] = arrays per workgroup, units of a
+ * unit slice, E-stream entries a workgroup decodes (QP: workgroup part p owns entries [p * QP, (p + 1) * QP) of the
+ * stream of `rows` rows) and the number of such parts.  wide_units: nonzero for the 16-byte-unit kernel (taken when dL
+ * is even and every pointer is 16-byte aligned).  CSGN_ERR_INVALID for an invalid shape or an empty batch. */
+int csgn_uint_write_plan(uint64_t n_bits, uint64_t batch, uint64_t index_width, const uint64_t *h_index_terms,
+                         uint64_t rows, uint64_t width, const uint64_t *h_value_terms, const uint64_t *h_array_terms,
+                         int wide_units, uint64_t *h_plan);
+/* The write over `batch` arrays.  h_index: a HOST array of index_width device pointers (plane k: batch * s_k * dL
+ * words), h_value: a HOST array of `width` device pointers (plane j: batch * tv_j * dL words), h_arrays: a HOST array of
+ * `width` device pointers (plane j: batch * rows * td_j * dL words), h_out: a HOST array of `width` device pointers
+ * (output j: batch * A_j * dL words).  Planes may alias one another; no output overlaps an input or another output.
+ * CSGN_ERR_INVALID: n_bits 0, index_width outside 1..16, width outside 1..64, rows outside 1..2^index_width, a term
+ * count of 0 or past the term limit, a null host array, a null device pointer among the first index_width / width
+ * entries.  Limits: every A_j * dL below 2^31 words per array (CSGN_ERR_UNSUPPORTED), batch * that < 2^60.
+ * batch == 0 succeeds and touches nothing.  Nothing is allocated or launched before every size is known.  On the
+ * caller's stream, asynchronous; the fused form is one launch and graph-capturable.  No GPU: CSGN_ERR_NO_DEVICE, no CPU
+ * fallback. */
+int csgn_uint_write(uint64_t n_bits, uint64_t batch, uint64_t index_width, const uint64_t *const *h_index,
+                    const uint64_t *h_index_terms, uint64_t rows, uint64_t width, const uint64_t *const *h_value,
+                    const uint64_t *h_value_terms, const uint64_t *const *h_arrays, const uint64_t *h_array_terms,
+                    uint64_t *const *h_out, void *stream);
+
 /* ------------------------------------------------ encrypted bit matrices over F2 ---- */
 
 /* The product of two ENCRYPTED bit matrices over F2: an inner product of encrypted bit vectors, a secret linear map
