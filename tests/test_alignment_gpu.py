@@ -6,17 +6,37 @@ alignment, so a caller's arena, a torch view at an odd word offset or a pinned b
 at N = 1247 or 4096 -- with unit counts (U = 20, 64) and trip counts the rest of the suite, whose buffers are fresh
 allocations, never gives it.  Here each pointer argument is moved one word into its buffer, alone and then all of them,
 and the words (and bits) must equal the numpy or oracle definition AND the same call on aligned buffers.  N = 1300 (odd
-dL, the 8-byte form either way) is the control.  Outputs carry a guard word on either side.  Run with `pytest -m gpu`."""
+dL, the 8-byte form either way) is the control.  Outputs carry a guard word on either side.  Run with `pytest -m gpu`.
+
+What is covered, entry point by entry point:
+  add (uniform, ragged), multiply (uniform in every form, ragged, planned, async), decrypt (uniform, ragged, product and
+  sum), encrypt (explicit, keyed, the fused chain), compaction, constants, gates, the integer steps and csgn_uint_plain:
+  every pointer alone and all of them, at every N of NS;
+  csgn_uint_lut_apply, csgn_gather (uniform and ragged), csgn_gather_planes, csgn_uint_read, csgn_uint_find,
+  csgn_uint_lt_select, csgn_uint_pick and csgn_uint_write, whose arguments are ARRAYS of device pointers: every pointer
+  class alone, the middle member of every class alone (one plane of many off a 16-byte boundary must already take the
+  8-byte form), and all of them, at every N of NS, in the fused and in the composed form (and the ragged gather at 1
+  and 4 chunks a workgroup), over fresh planes (subset tables in LDS) and planes of 1..3 terms (no tables);
+  the same entry points where a term is cut into unit slices at an even word count (N = 8320 and 5185), KC asserted from
+  csgn_uint_pick_plan and csgn_uint_write_plan;
+  and their later launches (knob launch_blocks) at moved pointers, whose per-launch offsets then count 8-byte units.
+csgn_uint_addk, csgn_matmul and csgn_count keep their one unaligned case each in their own files."""
 import ctypes as C
+from collections import namedtuple
 
 import numpy as np
 import pytest
 import torch
 
 from oracle.binding import glibc_draws
-from tests.model import (ADD_FULL, ADD_HALF, EQ, GATES, GE, GT, LE, LT, NE, STEPS, const_term, csr, explicit_randomness,
-                         gate_terms, hip, make_key, np_add, np_gate, np_mul, np_plain, np_step, planted, rand_terms,
-                         u64s)
+from tests.model import (ADD_FULL, ADD_HALF, EQ, GATES, GE, GT, LE, LT, NE, STEPS, c_terms, const_term, csr,
+                         explicit_randomness, gate_terms, hip, make_key, np_add, np_gate, np_gather, np_gather_offsets,
+                         np_gather_uniform, np_lut, np_mul, np_plain, np_read_fast, np_step, planted, rand_terms,
+                         random_table, tile_index, u64s)
+from tests.model_find import np_find_fast
+from tests.model_lt_select import minmax_requests, np_lt_select_fast
+from tests.model_pick import EACH, OPS, np_pick_fast
+from tests.model_write import np_write_fast
 
 pytestmark = pytest.mark.gpu
 
@@ -25,9 +45,22 @@ KEY_D = {1247: 16, 4096: 32, 128: 8, 1300: 4}
 GUARD = 0x5A5A5A5A5A5A5A5A
 
 
-def patterns(names):
-    """No pointer moved (the reference call), each one alone, then all of them."""
-    return [frozenset()] + [frozenset([x]) for x in names] + ([frozenset(names)] if len(names) > 1 else [])
+def member(cls, i):
+    """The name of pointer i of the class `cls` moved alone."""
+    return "%s[%d]" % (cls, i)
+
+
+def patterns(names, counts=None):
+    """No pointer moved (the reference call), each one alone, then all of them.  Where the arguments are arrays of
+    device pointers the names are the pointer classes and counts[name] is the number of pointers in the class: every
+    class of two or more also gives its middle member moved alone ("table[1]"), after the classes."""
+    names = list(names)
+    lone = [member(x, counts[x] // 2) for x in names if counts and counts.get(x, 1) >= 2]
+    return [frozenset()] + [frozenset([x]) for x in names + lone] + ([frozenset(names)] if len(names) > 1 else [])
+
+
+def is_moved(moved, cls, i):
+    return cls in moved or member(cls, i) in moved
 
 
 # Device copies made for the current call.  A pointer handed to the library must outlive the launch: a tensor dropped
@@ -75,10 +108,21 @@ class Out:
         return h[s:s + (self.k if k is None else int(k))]
 
 
-def same_for_every_pattern(names, call):
-    """call(moved) -> tuple of arrays; all patterns give the words of the aligned call, which is returned."""
+def place_all(hip, arrays, moved, cls):
+    """The pointers of one class, each placed as the pattern says."""
+    return [place(hip, a, is_moved(moved, cls, i)) for i, a in enumerate(arrays)]
+
+
+def outs_for(hip, want, moved, cls):
+    """One guarded output per wanted array, each placed as the pattern says."""
+    return [Out(hip, np.asarray(w).size, is_moved(moved, cls, i)) for i, w in enumerate(want)]
+
+
+def same_for_every_pattern(names, call, counts=None, only=None):
+    """call(moved) -> tuple of arrays; all patterns (`only`: these, the aligned call first) give the words of the aligned
+    call, which is returned."""
     base = None
-    for moved in patterns(names):
+    for moved in only or patterns(names, counts):
         got = tuple(np.asarray(g) for g in call(moved))
         torch.cuda.synchronize()
         HELD.clear()
@@ -543,3 +587,476 @@ def test_uint_plain(hip, knobs, n, fused):
             return (out.words(),)
 
         assert np.array_equal(same_for_every_pattern(names, call)[0], want), (cmp, k)
+
+
+# ------------------------------------------------------------------------------ arrays of device pointers
+
+# One operation on fixed operands: the pointer classes, the pointers in each, call(moved) and the definition's words.
+Case = namedtuple("Case", "names counts call want")
+
+
+def terms_of(planes):
+    return [p.shape[1] for p in planes]
+
+
+def ends(names):
+    """No pointer moved, then all of them."""
+    return [frozenset(), frozenset(names)]
+
+
+def check_case(case, only=None):
+    """Every pattern gives the aligned call's words, and those are the definition's."""
+    got = same_for_every_pattern(case.names, case.call, case.counts, only)
+    assert len(got) == len(case.want)
+    for j, (g, w) in enumerate(zip(got, case.want)):
+        assert np.array_equal(g, np.asarray(w).ravel()), j
+
+
+def words_of(outs):
+    return tuple(o.words() for o in outs)
+
+
+def views(outs):
+    return [o.view for o in outs]
+
+
+def lut_case(hip, n, batch, handle, table, m, ts, seed):
+    planes = [rand_terms(n, batch, t, seed + 7 * i + t) for i, t in enumerate(ts)]
+    want = np_lut(n, planes, table, m)
+    rc, T = c_terms(hip.lib, table, len(ts), m, ts)
+    assert rc == 0 and terms_of(want) == T
+
+    def call(moved):
+        outs = outs_for(hip, want, moved, "out")
+        hip.uint_lut_apply(handle, n, batch, place_all(hip, planes, moved, "planes"), T, outs=views(outs))
+        return words_of(outs)
+
+    return Case(["planes", "out"], {"planes": len(ts), "out": m}, call, want)
+
+
+def gather_planes_case(hip, n, terms, count_in, count_out, idx, seed):
+    dl = (n + 63) // 64
+    planes = [rand_terms(n, count_in, t, seed + j).ravel() for j, t in enumerate(terms)]
+    ref = idx if idx is not None else tile_index(count_in, count_out)
+    want = [np_gather_uniform(p, t, ref, dl) for p, t in zip(planes, terms)]
+
+    def call(moved):
+        outs = outs_for(hip, want, moved, "out")
+        hip.gather_planes(n, place_all(hip, planes, moved, "src"), terms, count_in, count_out,
+                          up(hip, idx) if idx is not None else None, views(outs))
+        return words_of(outs)
+
+    return Case(["src", "out"], {"src": len(terms), "out": len(terms)}, call, want)
+
+
+def read_case(hip, n, batch, s, rows, t, seed):
+    index = [rand_terms(n, batch, sk, seed + 7 * k + sk) for k, sk in enumerate(s)]
+    table = [rand_terms(n, rows, tj, seed + 100 + 11 * j + rows) for j, tj in enumerate(t)]
+    want = np_read_fast(n, index, table)
+
+    def call(moved):
+        outs = outs_for(hip, want, moved, "out")
+        hip.uint_read(n, batch, place_all(hip, index, moved, "index"), s, rows, place_all(hip, table, moved, "table"), t,
+                      outs=views(outs))
+        return words_of(outs)
+
+    return Case(["index", "table", "out"], {"index": len(s), "table": len(t), "out": len(t)}, call, want)
+
+
+def find_case(hip, n, batch, u, s, rows, t, seed):
+    """With the member bit: the last output."""
+    keys = [rand_terms(n, rows, uk, seed + 5 * k + rows) for k, uk in enumerate(u)]
+    query = [rand_terms(n, batch, sk, seed + 50 + 7 * k + sk) for k, sk in enumerate(s)]
+    values = [rand_terms(n, rows, tj, seed + 100 + 11 * j) for j, tj in enumerate(t)]
+    outs, mem = np_find_fast(n, keys, query, values, True)
+    want = list(outs) + [mem]
+    w = len(t)
+
+    def call(moved):
+        outs = outs_for(hip, want[:w], moved, "out")
+        mem = Out(hip, want[w].size, "member" in moved)
+        hip.uint_find(n, batch, place_all(hip, query, moved, "query"), s, rows, place_all(hip, keys, moved, "keys"), u,
+                      place_all(hip, values, moved, "values"), t, outs=views(outs), member=mem.view)
+        return words_of(outs + [mem])
+
+    return Case(["query", "keys", "values", "out", "member"], {"query": len(s), "keys": len(u), "values": w, "out": w},
+                call, want)
+
+
+def lt_select_case(hip, n, batch, ta, tb, seed):
+    """min and max of a and b (request i of min is a_i : b_i, of max b_i : a_i) and the comparison, the last output."""
+    w = len(ta)
+    host = ([rand_terms(n, batch, t, seed + 7 * k + t) for k, t in enumerate(ta)] +
+            [rand_terms(n, batch, t, seed + 50 + 5 * k + t) for k, t in enumerate(tb)])
+    xi, yi = minmax_requests(list(range(w)), list(range(w, 2 * w)))              # planes named by index into host
+    outs, lt = np_lt_select_fast(n, host[:w], host[w:], [host[h] for h in xi], [host[h] for h in yi], True)
+    want = list(outs) + [lt]
+    m = len(xi)
+
+    def call(moved):
+        placed = {}
+
+        def dev(cls, i, h):
+            # one device copy per (plane, moved or not): a request plane that is placed as the operand it names is
+            # handed over as the very same pointer (X_i = a_j), else as a copy of it
+            key = (h, is_moved(moved, cls, i))
+            if key not in placed:
+                placed[key] = place(hip, host[h], key[1])
+            return placed[key]
+
+        da, db = [dev("a", j, j) for j in range(w)], [dev("b", j, w + j) for j in range(w)]
+        dx, dy = [dev("x", i, h) for i, h in enumerate(xi)], [dev("y", i, h) for i, h in enumerate(yi)]
+        outs = outs_for(hip, want[:m], moved, "out")
+        less = Out(hip, want[m].size, "less" in moved)
+        hip.uint_lt_select(n, batch, da, ta, db, tb, dx, [host[h].shape[1] for h in xi], dy,
+                           [host[h].shape[1] for h in yi], outs=views(outs), less=less.view)
+        return words_of(outs + [less])
+
+    return Case(["a", "b", "x", "y", "out", "less"], {"a": w, "b": w, "x": m, "y": m, "out": m}, call, want)
+
+
+def pick_case(hip, n, batch, op, s, w, rows, t, seed):
+    index = [rand_terms(n, batch, sk, seed + 7 * k + sk) for k, sk in enumerate(s)]
+    src = [rand_terms(n, batch * (rows if op == EACH else 1), t, seed + 100 + 11 * j) for j in range(w)]
+    want = np_pick_fast(n, op, index, src, rows)
+
+    def call(moved):
+        outs = outs_for(hip, want, moved, "out")
+        hip.uint_pick(n, op, batch, place_all(hip, index, moved, "index"), s, place_all(hip, src, moved, "src"), t, rows,
+                      outs=views(outs))
+        return words_of(outs)
+
+    return Case(["index", "src", "out"], {"index": len(s), "src": w, "out": w}, call, want)
+
+
+def write_case(hip, n, batch, s, rows, tv, td, seed):
+    index = [rand_terms(n, batch, sk, seed + 7 * k + sk) for k, sk in enumerate(s)]
+    value = [rand_terms(n, batch, t, seed + 100 + 11 * j) for j, t in enumerate(tv)]
+    arrays = [rand_terms(n, batch * rows, t, seed + 500 + 13 * j) for j, t in enumerate(td)]
+    want = np_write_fast(n, index, value, arrays, rows)
+
+    def call(moved):
+        outs = outs_for(hip, want, moved, "out")
+        hip.uint_write(n, batch, place_all(hip, index, moved, "index"), s, rows, place_all(hip, value, moved, "value"), tv,
+                       place_all(hip, arrays, moved, "arrays"), td, outs=views(outs))
+        return words_of(outs)
+
+    w = len(tv)
+    return Case(["index", "value", "arrays", "out"], {"index": len(s), "value": w, "arrays": w, "out": w}, call, want)
+
+
+# -- the forms: the knob set and the form it selects asserted by the entry point's name function -----------------------
+def lut_form(hip, knobs, fused, n, batch, handle):
+    knobs.set("uint_lut_fused", fused)
+    assert hip.lib.csgn_uint_lut_kernel(n, handle, batch) == (b"k_uint_lut" if fused else b"composed")
+
+
+def read_form(hip, knobs, fused, n, batch, s, rows, t):
+    knobs.set("uint_read_fused", fused)
+    name = hip.lib.csgn_uint_read_kernel(n, batch, len(s), u64s(s), rows, len(t), u64s(t))
+    assert name == (b"k_uint_read" if fused else b"composed")
+
+
+def find_form(hip, knobs, fused, n, batch, u, s, rows, t):
+    knobs.set("uint_find_form", fused)
+    name = hip.lib.csgn_uint_find_kernel(n, batch, len(u), u64s(u), u64s(s), rows, len(t), u64s(t), 1)
+    assert name == (b"k_uint_find" if fused else b"composed")
+
+
+def lt_select_form(hip, knobs, fused, n, batch, ta, tb):
+    knobs.set("uint_lt_select_form", fused)
+    tx, ty = minmax_requests(ta, tb)
+    name = hip.lib.csgn_uint_lt_select_kernel(n, batch, len(ta), u64s(ta), u64s(tb), len(tx), u64s(tx), u64s(ty), 1)
+    assert name == (b"k_uint_lt_select" if fused else b"composed")
+
+
+def pick_forms(hip, knobs, n, batch, op, s, w, rows, t, forms=(0, 1)):
+    """Sets the form, then every staging of it, in turn: composed; the fused kernel without and with its LDS value slice."""
+    for fused in forms:
+        knobs.set("uint_pick_fused", fused)
+        name = hip.lib.csgn_uint_pick_kernel(n, op, batch, len(s), u64s(s), w, rows, t)
+        assert name == (b"k_uint_pick" if fused else b"composed")
+        for stage in ((0, 1) if fused else (-1,)):
+            knobs.set("uint_pick_stage", stage)
+            yield fused, stage
+
+
+def write_form(hip, knobs, fused, n, batch, s, rows, tv, td):
+    knobs.set("uint_write_fused", fused)
+    name = hip.lib.csgn_uint_write_kernel(n, batch, len(s), u64s(s), rows, len(tv), u64s(tv), u64s(td))
+    assert name == (b"k_uint_write" if fused else b"composed")
+
+
+BATCH = 3
+LUT_TABLE = [(3 * x) % 16 for x in range(16)]
+MIXED = {2: [2, 1], 3: [2, 1, 3]}                                       # index planes of 1..3 terms: no subset tables
+GATHER_INDEX = np.array([6, 0, 0, 3, 3, 3, 1, 6, 4, 0, 6], dtype=np.uint64)    # 11 of 7 elements: repeats, 2 and 5 skipped
+
+
+@pytest.mark.parametrize("n", NS)
+def test_uint_lut_pointer_arrays(hip, knobs, n):
+    """One handle per term list, applied at every pattern and in both forms: a handle does not remember a unit width."""
+    shapes = [(4, LUT_TABLE, [1, 1, 1, 1]), (4, LUT_TABLE, [1, 2, 1, 1])]
+    if n == 1247:
+        shapes.append((6, random_table(6, 4, 61), [1] * 6))              # two subset tables
+    for w, table, ts in shapes:
+        handle = hip.uint_lut_create(table, w, 4, ts)
+        try:
+            case = lut_case(hip, n, BATCH, handle, table, 4, ts, 2000)
+            for fused in (0, 1):
+                lut_form(hip, knobs, fused, n, BATCH, handle)
+                check_case(case)
+        finally:
+            torch.cuda.synchronize()
+            hip.lib.csgn_uint_lut_destroy(handle)
+
+
+@pytest.mark.parametrize("n", NS)
+def test_gather_uniform_pointers(hip, n):
+    """t = 3, 7 source elements, 11 output elements: by an index list that repeats and skips, and the tile form."""
+    t, count_in, count_out = 3, 7, len(GATHER_INDEX)
+    dl = (n + 63) // 64
+    src = rand_terms(n, count_in, t, 2100).ravel()
+    assert hip.lib.csgn_gather_kernel(n, count_out, 0, 1) == b"k_gather"
+    for idx in (GATHER_INDEX, None):
+        want = np_gather_uniform(src, t, idx if idx is not None else tile_index(count_in, count_out), dl)
+
+        def call(moved):
+            out = Out(hip, want.size, "out" in moved)
+            d_idx = place(hip, idx, "index" in moved) if idx is not None else None
+            hip.gather(n, count_in, place(hip, src, "src" in moved), t, count_out, d_idx, out.view)
+            return (out.words(),)
+
+        names = ["src", "index", "out"] if idx is not None else ["src", "out"]
+        assert np.array_equal(same_for_every_pattern(names, call)[0], want), idx is None
+
+
+@pytest.mark.parametrize("n", NS)
+@pytest.mark.parametrize("chunks", [1, 4])
+def test_gather_ragged_pointers(hip, knobs, n, chunks):
+    """Knob ragged_c: 1 and 4 chunks a workgroup.  The plan writes the output offsets, themselves between guard words."""
+    knobs.set("ragged_c", chunks)
+    sizes = [1, 0, 3, 17, 2, 0, 40]
+    idx = np.array([3, 0, 6, 6, 1, 2, 4, 3, 0, 5, 6], dtype=np.uint64)
+    count_in, count_out = len(sizes), len(idx)
+    dl = (n + 63) // 64
+    src_off = csr(sizes)
+    src = rand_terms(n, 1, sum(sizes), 2200).ravel()
+    want, want_off = np_gather(src, src_off, idx, dl)
+    assert np.array_equal(want_off, np_gather_offsets(src_off, idx))
+    total = int(want_off[-1])
+    assert hip.lib.csgn_gather_kernel(n, count_out, 1, 1) == b"k_gather_ragged"
+
+    def call(moved):
+        d_src, d_soff = place(hip, src, "src" in moved), place(hip, src_off, "src_off" in moved)
+        d_idx = place(hip, idx, "index" in moved)
+        out, out_off = Out(hip, want.size, "out" in moved), Out(hip, count_out + 1, "out_off" in moved)
+        res = (C.c_uint64 * 2)()
+        assert hip.lib.csgn_gather_plan(count_in, d_soff.data_ptr(), count_out, d_idx.data_ptr(), out_off.ptr, res,
+                                        hip.stream) == 0
+        assert (int(res[0]), int(res[1])) == (total, 0)
+        assert hip.lib.csgn_gather(n, count_in, d_src.data_ptr(), d_soff.data_ptr(), 0, count_out, d_idx.data_ptr(),
+                                   out.ptr, out_off.ptr, total, hip.stream) == 0
+        return out.words(), out_off.words()
+
+    got, got_off = same_for_every_pattern(["src", "src_off", "index", "out", "out_off"], call)
+    assert np.array_equal(got_off, want_off)
+    assert np.array_equal(got, want)
+
+
+@pytest.mark.parametrize("n", NS)
+def test_gather_planes_pointer_arrays(hip, n):
+    assert hip.lib.csgn_gather_kernel(n, len(GATHER_INDEX), 0, 3) == b"k_gather"
+    for idx in (GATHER_INDEX, None):
+        check_case(gather_planes_case(hip, n, [1, 2, 3], 7, len(GATHER_INDEX), idx, 2300))
+
+
+@pytest.mark.parametrize("n", NS)
+def test_uint_read_pointer_arrays(hip, knobs, n):
+    shapes = [(s, rows, [1, 2]) for s in ([1, 1, 1], MIXED[3]) for rows in (5, 8)]
+    if n == 1247:
+        shapes.append(([1] * 6, 64, [1]))                                # two subset tables
+    for s, rows, t in shapes:
+        case = read_case(hip, n, BATCH, s, rows, t, 2400)
+        for fused in (0, 1):
+            read_form(hip, knobs, fused, n, BATCH, s, rows, t)
+            check_case(case)
+
+
+@pytest.mark.parametrize("n", NS)
+def test_uint_find_pointer_arrays(hip, knobs, n):
+    """Key width 3, 5 rows, two value planes and the member bit; fresh keys and query, then planes of 1..3 terms."""
+    for u, s in (([1, 1, 1], [1, 1, 1]), ([1, 2, 1], MIXED[3])):
+        case = find_case(hip, n, BATCH, u, s, 5, [1, 2], 2500)
+        for fused in (0, 1):
+            find_form(hip, knobs, fused, n, BATCH, u, s, 5, [1, 2])
+            check_case(case)
+
+
+@pytest.mark.parametrize("n", NS)
+def test_uint_lt_select_pointer_arrays(hip, knobs, n):
+    """Width 3, min and max of a and b, and the comparison; fresh operands, then planes of 1..3 terms."""
+    for ta, tb in (([1, 1, 1], [1, 1, 1]), ([1, 2, 1], MIXED[3])):
+        case = lt_select_case(hip, n, BATCH, ta, tb, 2600)
+        for fused in (0, 1):
+            lt_select_form(hip, knobs, fused, n, BATCH, ta, tb)
+            check_case(case)
+
+
+@pytest.mark.parametrize("n", NS)
+@pytest.mark.parametrize("op", sorted(OPS))
+def test_uint_pick_pointer_arrays(hip, knobs, n, op):
+    """The shifts and rotates at w = 4, v = 2; EACH at v = 3, 5 rows, w = 2.  Source planes of 1 and 2 terms."""
+    op = OPS[op]
+    v, w, rows = (3, 2, 5) if op == EACH else (2, 4, 0)
+    for s in ([1] * v, MIXED[v]):
+        for t in (1, 2):
+            case = pick_case(hip, n, BATCH, op, s, w, rows, t, 2700)
+            for _ in pick_forms(hip, knobs, n, BATCH, op, s, w, rows, t):
+                check_case(case)
+
+
+@pytest.mark.parametrize("n", NS)
+@pytest.mark.parametrize("v,rows,w", [(2, 3, 3), (3, 5, 2)])
+def test_uint_write_pointer_arrays(hip, knobs, n, v, rows, w):
+    for s in ([1] * v, MIXED[v]):
+        for a, b in ((1, 1), (2, 3)):
+            tv, td = [a] * w, [b] * w
+            case = write_case(hip, n, BATCH, s, rows, tv, td, 2800)
+            for fused in (0, 1):
+                write_form(hip, knobs, fused, n, BATCH, s, rows, tv, td)
+                check_case(case)
+
+
+# ------------------------------------------------------------------------------ terms cut into unit slices, even dL
+
+SLICED_N = 8320             # dL = 130
+
+
+def test_unit_slices_at_an_even_word_count_cover_both_unit_sizes(hip):
+    """What N = 8320 with five fresh selector planes is chosen for, from the fused forms' own tiles (csgn_uint_pick_plan,
+    csgn_uint_write_plan): one element's subset table at whole terms, 32 entries x 130 words x 8 B = 33 280 B, passes the
+    32 768 bytes a workgroup has for it, so a term is cut into two slices -- in 16-byte units (no pointer moved) 33 + 32
+    of 65, a short last slice, and in 8-byte units (a pointer moved) 65 + 65 of 130, which no other N of the suite gives
+    the 8-byte kernels (N = 8256: 65 + 64 of 129)."""
+    v, rows, dl = 5, 32, (SLICED_N + 63) // 64
+    s, one = u64s([1] * v), u64s([1])
+    plan = (C.c_uint64 * 4)()
+    seen = set()
+    for wide, unit_bytes, want_kc in ((0, 8, 65), (1, 16, 33)):
+        units = dl * 8 // unit_bytes
+        assert (1 << v) * units * unit_bytes > 32768                   # at whole terms the table does not fit
+        for what in ("pick", "write"):
+            if what == "pick":
+                rc = hip.lib.csgn_uint_pick_plan(SLICED_N, EACH, 2, v, s, 1, rows, 1, wide, plan)
+            else:
+                rc = hip.lib.csgn_uint_write_plan(SLICED_N, 2, v, s, rows, 1, one, one, wide, plan)
+            assert rc == 0 and int(plan[1]) == want_kc, (what, wide, list(plan))
+        assert (1 << v) * want_kc * unit_bytes <= 32768 and want_kc < units <= 2 * want_kc
+        seen.add(("8-byte units, " if not wide else "16-byte units, ") +
+                 ("two even slices" if units == 2 * want_kc else "a short last slice"))
+    assert seen == {"8-byte units, two even slices", "16-byte units, a short last slice"}, seen
+
+
+@pytest.mark.parametrize("entry", ["read", "pick", "write", "lut"])
+def test_unit_slices_at_an_even_word_count(hip, knobs, entry):
+    """N = 8320, five fresh selector planes, the fused form, no pointer moved and all of them (the slices:
+    test_unit_slices_at_an_even_word_count_cover_both_unit_sizes).  32 rows, one plane of one term."""
+    n, batch, s, rows = SLICED_N, 2, [1] * 5, 32
+    if entry == "read":
+        read_form(hip, knobs, 1, n, batch, s, rows, [1])
+        case = read_case(hip, n, batch, s, rows, [1], 3000)
+        check_case(case, ends(case.names))
+    elif entry == "pick":
+        case = pick_case(hip, n, batch, EACH, s, 1, rows, 1, 3100)
+        for _ in pick_forms(hip, knobs, n, batch, EACH, s, 1, rows, 1, forms=(1,)):
+            check_case(case, ends(case.names))
+    elif entry == "write":
+        write_form(hip, knobs, 1, n, batch, s, rows, [1], [1])
+        case = write_case(hip, n, batch, s, rows, [1], [1], 3200)
+        check_case(case, ends(case.names))
+    else:
+        table = random_table(5, 4, 33)
+        handle = hip.uint_lut_create(table, 5, 4, s)
+        try:
+            lut_form(hip, knobs, 1, n, batch, handle)
+            case = lut_case(hip, n, batch, handle, table, 4, s, 3300)
+            check_case(case, ends(case.names))
+        finally:
+            torch.cuda.synchronize()
+            hip.lib.csgn_uint_lut_destroy(handle)
+
+
+@pytest.mark.parametrize("entry", ["find", "lt_select"])
+def test_two_table_sets_cut_into_unit_slices_at_an_even_word_count(hip, knobs, entry):
+    """csgn_uint_find and csgn_uint_lt_select hold two sets of subset tables and give each 20 480 bytes (kTableBudget);
+    subset_plan cuts a term into slices when one element's tables at whole terms, entries x unit bytes x U, pass that.
+    Five fresh planes are one table of 32 entries, and U units of a term are dL words of 8 bytes in either unit size
+    (U = dL units of 8 bytes, or dL / 2 of 16), so the tables take 32 x 8 x dL = 256 dL bytes: past 20 480 from dL = 81
+    on, and the smallest even dL is 82 -- N = 5185, the smallest N of 82 words, whose last word holds ONE bit, so ONE's
+    last unit differs from every other in both unit sizes.  The slices are 41 + 41 units of 8 bytes (a pointer moved) or
+    21 + 20 of 16 (none moved); the odd neighbour N = 5184 of the entry points' own files gives 41 + 40."""
+    dl = next(d for d in range(2, 1000, 2) if 32 * 8 * d > 20480)
+    n = 64 * (dl - 1) + 1
+    assert (dl, n) == (82, 5185) and (n + 63) // 64 == dl and 32 * 8 * (dl - 2) <= 20480
+    batch, one = 2, [1] * 5
+    if entry == "find":
+        find_form(hip, knobs, 1, n, batch, one, one, 3, [1, 2])
+        case = find_case(hip, n, batch, one, one, 3, [1, 2], 3400)
+    else:
+        lt_select_form(hip, knobs, 1, n, batch, one, one)
+        case = lt_select_case(hip, n, batch, one, one, 3500)
+    check_case(case, ends(case.names))
+
+
+# ------------------------------------------------------------------------------ later launches at moved pointers
+
+def later_launch_runs(hip, knobs, entry, n, batch, handles):
+    """(case, forms) pairs of one entry point at the small shapes above, fresh planes and planes of 1..3 terms: forms()
+    sets the fused form's knobs and yields once per variant of it to run.  A lookup table's handle goes to `handles`."""
+    def once(form, *args):
+        return lambda: [form(hip, knobs, 1, n, batch, *args)]
+
+    if entry == "read":
+        return [(read_case(hip, n, batch, s, 5, [1, 2], 4000), once(read_form, s, 5, [1, 2])) for s in ([1, 1, 1], MIXED[3])]
+    if entry == "find":
+        return [(find_case(hip, n, batch, u, s, 5, [1, 2], 4100), once(find_form, u, s, 5, [1, 2]))
+                for u, s in (([1, 1, 1], [1, 1, 1]), ([1, 2, 1], MIXED[3]))]
+    if entry == "lt_select":
+        return [(lt_select_case(hip, n, batch, ta, tb, 4200), once(lt_select_form, ta, tb))
+                for ta, tb in (([1, 1, 1], [1, 1, 1]), ([1, 2, 1], MIXED[3]))]
+    if entry == "pick":
+        return [(pick_case(hip, n, batch, EACH, s, 2, 5, t, 4300),
+                 lambda s=s, t=t: pick_forms(hip, knobs, n, batch, EACH, s, 2, 5, t, forms=(1,)))
+                for s, t in (([1, 1, 1], 1), (MIXED[3], 2))]
+    if entry == "write":
+        return [(write_case(hip, n, batch, s, 5, [a] * 2, [b] * 2, 4400), once(write_form, s, 5, [a] * 2, [b] * 2))
+                for s, a, b in (([1, 1, 1], 1, 1), (MIXED[3], 2, 3))]
+    if entry == "lut":
+        runs = []
+        for ts in ([1, 1, 1, 1], [1, 2, 1, 1]):
+            handles.append(hip.uint_lut_create(LUT_TABLE, 4, 4, ts))
+            runs.append((lut_case(hip, n, batch, handles[-1], LUT_TABLE, 4, ts, 4600), once(lut_form, handles[-1])))
+        return runs
+    idx = np.random.default_rng(45).integers(0, 7, batch).astype(np.uint64)
+    return [(gather_planes_case(hip, n, [1, 2, 3], 7, batch, i, 4500), lambda: [None]) for i in (idx, None)]
+
+
+@pytest.mark.parametrize("entry", ["read", "find", "lt_select", "pick", "write", "lut", "gather_planes"])
+def test_later_launches_at_moved_pointers(hip, knobs, entry):
+    """N = 1247, 37 elements, the fused forms, no pointer moved and all of them: knob launch_blocks at 1 and 3 cuts the
+    batch into several launches (the last one not full), each from its own operand and output offsets, which the host
+    counts in units -- with the pointers moved in 8-byte units, 20 a term."""
+    handles = []
+    try:
+        runs = later_launch_runs(hip, knobs, entry, 1247, 37, handles)
+        assert len(runs) == 2
+        for blocks in (1, 3):
+            knobs.set("launch_blocks", blocks)
+            for case, forms in runs:
+                for _ in forms():
+                    check_case(case, ends(case.names))
+    finally:
+        torch.cuda.synchronize()
+        for h in handles:
+            hip.lib.csgn_uint_lut_destroy(h)
