@@ -508,6 +508,43 @@ class HipPath:
         check(self.lib.csgn_count(n_bits, count, group, t, h_in, len(ins), len(js), h_js, h_out, self.stream))
         return [o[: count * T * dl] for o, T in zip(outs, terms)]
 
+    def wsum_create(self, ns, t: int, js) -> int:
+        """csgn_wsum_create: the plan of the planes `js` (strictly ascending) for classes of ns[c] inputs of weight 2^c
+        and of `t` terms each.  Returns the handle; release it with self.lib.csgn_wsum_destroy."""
+        h_n = (C.c_uint64 * max(len(ns), 1))(*[int(v) for v in ns])
+        h_js = (C.c_uint64 * max(len(js), 1))(*[int(j) for j in js])
+        handle = C.c_void_p()
+        check(self.lib.csgn_wsum_create(len(ns), h_n, t, len(js), h_js, C.byref(handle)))
+        return handle.value
+
+    def wsum_apply(self, handle: int, n_bits: int, count: int, ins, n_out: int, outs=None):
+        """csgn_wsum of a plan: `ins` one tensor per class (None where the class is empty), count * ns[c] elements each,
+        input i of element q at q * ns[c] + i.  Returns one tensor per plane of the plan (fresh ones unless `outs` is
+        given)."""
+        dl = self.default_len(n_bits)
+        terms = [int(self.lib.csgn_wsum_plan_terms(handle, x)) for x in range(n_out)]
+        if outs is None:
+            outs = [self.empty_words(count * T * dl) for T in terms]
+        assert all(o.numel() >= count * T * dl for o, T in zip(outs, terms))
+        h_in = (C.c_void_p * len(ins))(*[None if x is None else _ptr(x) for x in ins])
+        h_out = (C.c_void_p * len(outs))(*[_ptr(o) for o in outs])
+        check(self.lib.csgn_wsum(handle, n_bits, count, h_in, h_out, self.stream))
+        return [o[: count * T * dl] for o, T in zip(outs, terms)]
+
+    def wsum(self, n_bits: int, count: int, ns, t: int, ins, js, outs=None):
+        """csgn_wsum: the bits `js` of the sum of every element's inputs, ns[c] of weight 2^c and of `t` terms each in
+        class c.  Returns one tensor per plane, count elements of csgn_wsum_terms(ns, t, j) terms (fresh ones unless
+        `outs` is given)."""
+        assert len(ins) == len(ns)
+        assert all(x is None or x.numel() >= count * int(k) * t * self.default_len(n_bits) for x, k in zip(ins, ns))
+        handle = self.wsum_create(ns, t, js)
+        try:
+            outs = self.wsum_apply(handle, n_bits, count, ins, len(js), outs)
+            torch.cuda.current_stream(self.device).synchronize()
+        finally:
+            self.lib.csgn_wsum_destroy(handle)
+        return outs
+
     def add_ragged(self, n_bits: int, left: torch.Tensor, off_left: torch.Tensor,
                    right: torch.Tensor, off_right: torch.Tensor,
                    total_terms_out: Optional[int] = None, max_t1: int = 0, max_t2: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:

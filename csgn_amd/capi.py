@@ -180,6 +180,11 @@ SIGNATURES = {
     "csgn_count_terms": (u64, [u64, u64, u64]),
     "csgn_count_kernel": (C.c_char_p, [u64, u64, u64, u64, u64, u64, vp]),
     "csgn_count": (C.c_int, [u64, u64, u64, u64, vp, u64, u64, vp, vp, vp]),
+    "csgn_wsum_terms": (u64, [u64, vp, u64, u64]),
+    "csgn_wsum_create": (C.c_int, [u64, vp, u64, u64, vp, C.POINTER(vp)]),
+    "csgn_wsum_plan_terms": (u64, [vp, u64]),
+    "csgn_wsum_destroy": (None, [vp]),
+    "csgn_wsum": (C.c_int, [vp, u64, u64, vp, vp, vp]),
     "csgn_set_tuning": (C.c_int, [C.c_char_p, C.c_int]),
     "csgn_get_tuning": (C.c_int, [C.c_char_p, C.POINTER(C.c_int)]),
     "csgn_reset_tuning": (None, []),

@@ -1619,4 +1619,292 @@ UIntBatch countMatches(const UIntBatch &keys, const UIntBatch &query, unsigned p
     return UIntBatch::fromPlanes(countPlanes(std::vector<CiphertextBatch>(1, eq), rows, firstPlanes(planes), "countMatches"));
 }
 
+// ------------------------------------------------------------------ sums of integers (csgn_wsum)
+
+namespace {
+
+// does plane j have a count vector: can the classes make up 2^j?  Taking all a class can give, heaviest first, settles
+// it (what is left is a multiple of every lighter weight)
+bool planeHasVector(const std::vector<uint64_t> &n, unsigned j)
+{
+    if (j > 62)
+        return false;
+    uint64_t rest = 1ull << j;
+    for (size_t c = std::min<size_t>(j, n.size() - 1) + 1; c-- > 0 && rest;)
+        rest -= std::min<uint64_t>(n[c], rest >> c) << c;
+    return rest == 0;
+}
+
+// Terms per element of the planes js for classes of n[c] inputs of t terms; 0: the plane has no count vector, it is
+// ZERO.  Throws past 2^31 words.
+std::vector<uint64_t> wsumSizes(const Context &ctx, const std::vector<uint64_t> &n, uint64_t t,
+                                const std::vector<unsigned> &js, const char *who)
+{
+    uint64_t all = 0;
+    for (size_t c = 0; c < n.size(); ++c)
+        all = n[c] > 65536 ? 65537 : all + n[c];
+    if (n.empty() || n.size() > 64 || all > 65536)
+        throw std::invalid_argument(std::string("certFHE::") + who + ": more than 65536 partial products an element");
+    std::vector<uint64_t> T(js.size(), 0);
+    for (size_t x = 0; x < js.size(); ++x) {
+        if (all == 0 || !planeHasVector(n, js[x]))
+            continue;
+        T[x] = csgn_wsum_terms(n.size(), n.data(), t, js[x]);
+        if (T[x] == 0 || T[x] > (kMaxWords - 1) / ctx.getDefaultN())
+            throw std::invalid_argument(std::string("certFHE::") + who + ": plane " + std::to_string(js[x]) +
+                                        " exceeds 2^31 words per element");
+    }
+    return T;
+}
+
+// device plans per (classes, t, planes), kept until the process ends
+const csgn_wsum_plan *wsumPlan(const std::vector<uint64_t> &n, uint64_t t, const std::vector<uint64_t> &js)
+{
+    static std::mutex mutex;
+    static std::map<std::vector<uint64_t>, csgn_wsum_plan *> *plans = new std::map<std::vector<uint64_t>, csgn_wsum_plan *>();
+    std::vector<uint64_t> key(1, t);
+    key.push_back(n.size());
+    key.insert(key.end(), n.begin(), n.end());
+    key.insert(key.end(), js.begin(), js.end());
+    std::lock_guard<std::mutex> lock(mutex);
+    auto it = plans->find(key);
+    if (it != plans->end())
+        return it->second;
+    csgn_wsum_plan *p = nullptr;
+    detail::check(csgn_wsum_create(n.size(), n.data(), t, js.size(), js.data(), &p), "csgn_wsum_create");
+    (*plans)[key] = p;
+    return p;
+}
+
+// the count vectors of plane j in the definition's order, m[c] for c = 0 .. j
+void countVectors(const std::vector<uint64_t> &n, unsigned c, uint64_t rest, std::vector<uint64_t> &m,
+                  std::vector<std::vector<uint64_t> > &out)
+{
+    const uint64_t nc = c < n.size() ? n[c] : 0;
+    if (c == 0) {
+        if (rest <= nc) {
+            m[0] = rest;
+            out.push_back(m);
+        }
+        return;
+    }
+    for (uint64_t k = 0; k <= std::min<uint64_t>(nc, rest >> c); ++k) {
+        m[c] = k;
+        countVectors(n, c - 1, rest - (k << c), m, out);
+    }
+}
+
+// The planes js of the sum of every element's inputs: class c is cls[c], n[c] inputs of weight 2^c an element, input i
+// of element q its element q * n[c] + i (n[c] = 0: cls[c] is not looked at).  T: wsumSizes of the largest term count.
+// One csgn_wsum for uniform classes of one term count, else the definition through the batch operators.
+std::vector<CiphertextBatch> wsumPlanes(const Context &ctx, uint64_t count, const std::vector<CiphertextBatch> &cls,
+                                        const std::vector<uint64_t> &n, const std::vector<unsigned> &js,
+                                        const std::vector<uint64_t> &T, const char *who)
+{
+    const std::string name = std::string("certFHE::") + who;
+    std::vector<CiphertextBatch> out(js.size(), constantBatch(ctx, std::vector<unsigned char>(count, 0)));
+    bool uniform = true;
+    uint64_t t = 0;
+    for (size_t c = 0; c < n.size(); ++c) {
+        if (n[c] == 0)
+            continue;
+        uniform = uniform && cls[c].uniform() && (t == 0 || cls[c].terms() == t);
+        t = cls[c].uniform() ? cls[c].terms() : t;
+    }
+    for (size_t x = 0; x < js.size(); ++x)
+        if (T[x] != 0 && js[x] == 0)
+            out[x] = cls[0].sumGroups(n[0]);                     // a sum is a concatenation: the same payload, no launch
+    if (uniform) {
+        std::vector<uint64_t> h_js, Ts;
+        std::vector<size_t> at;
+        for (size_t x = 0; x < js.size(); ++x) {
+            if (T[x] == 0 || js[x] == 0)
+                continue;
+            h_js.push_back(js[x]);
+            at.push_back(x);
+        }
+        if (h_js.empty())
+            return out;
+        const csgn_wsum_plan *plan = wsumPlan(n, t, h_js);
+        for (size_t k = 0; k < h_js.size(); ++k)                 // the classes' own term count, not the bound T came from
+            Ts.push_back(csgn_wsum_plan_terms(plan, k));
+        std::vector<CiphertextBatch> made = makePlanes(ctx, count, Ts);
+        std::vector<const uint64_t *> src(n.size(), nullptr);
+        for (size_t c = 0; c < n.size(); ++c)
+            if (n[c])
+                src[c] = cls[c].deviceValues();
+        detail::check(csgn_wsum(plan, ctx.getN(), count, src.data(), wordsOf(made).data(), detail::stream()), "csgn_wsum");
+        for (size_t k = 0; k < at.size(); ++k)
+            out[at[k]] = made[k];
+        return out;
+    }
+    // ragged or mixed: the definition itself, vector by vector, from gather, operator*, sumGroups and operator+
+    for (size_t x = 0; x < js.size(); ++x)                       // count * the selections of the plane's vectors
+        if (T[x] != 0 && count >= (1ull << 32) / csgn_wsum_terms(n.size(), n.data(), 1, js[x]))
+            throw std::invalid_argument(name + ": ragged operands of 2^32 products or more");
+    for (size_t x = 0; x < js.size(); ++x) {
+        if (T[x] == 0 || js[x] == 0)
+            continue;
+        std::vector<std::vector<uint64_t> > vectors;
+        std::vector<uint64_t> m(js[x] + 1, 0);
+        countVectors(n, js[x], 1ull << js[x], m, vectors);
+        bool first = true;
+        for (size_t v = 0; v < vectors.size(); ++v) {
+            // the factors of a selection: classes descending, indices ascending; the odometer steps class 0 fastest
+            std::vector<unsigned> fc;                            // class of factor k
+            std::vector<uint64_t> sel;                           // its index within the class
+            std::vector<size_t> start;                           // the first factor of its class
+            for (unsigned c = js[x] + 1; c-- > 0;)
+                for (uint64_t i = 0; i < vectors[v][c]; ++i) {
+                    start.push_back(fc.size() - i);
+                    fc.push_back(c);
+                    sel.push_back(i);
+                }
+            const size_t deg = fc.size();
+            std::vector<std::vector<uint64_t> > idx(deg);
+            uint64_t found = 0;
+            for (bool more = true; more; ++found) {
+                for (size_t k = 0; k < deg; ++k)
+                    idx[k].push_back(sel[k]);
+                more = false;
+                for (size_t k = deg; k-- > 0 && !more;) {        // the last factor that can still move up, class by class
+                    const uint64_t c = fc[k], mc = vectors[v][c], pos = k - start[k];
+                    if (sel[k] < n[c] - mc + pos) {
+                        ++sel[k];
+                        for (size_t i = k + 1; i < start[k] + mc; ++i)
+                            sel[i] = sel[i - 1] + 1;
+                        for (size_t i = start[k] + mc; i < deg; ++i)    // the lighter classes start over
+                            sel[i] = i - start[i];
+                        more = true;
+                    }
+                }
+            }
+            // selection s of element q: factor k is element q * n_c + sel of class c's batch
+            CiphertextBatch prod = cls[0];
+            for (size_t k = 0; k < deg; ++k) {
+                std::vector<uint64_t> all(count * found);
+                for (uint64_t q = 0; q < count; ++q)
+                    for (uint64_t s = 0; s < found; ++s)
+                        all[q * found + s] = q * n[fc[k]] + idx[k][s];
+                const CiphertextBatch factor = cls[fc[k]].gather(all);
+                prod = k == 0 ? factor : prod * factor;
+            }
+            const CiphertextBatch part = prod.sumGroups(found);
+            out[x] = first ? part : out[x] + part;
+            first = false;
+        }
+    }
+    return out;
+}
+
+// the largest term count among the planes that take part: planes 0 .. planes - 1
+uint64_t maxTerms(const UIntBatch &a, size_t planes)
+{
+    uint64_t t = 0;
+    for (unsigned j = 0; j < a.width() && j < planes; ++j)
+        t = std::max(t, termsOf(a.plane(j)));
+    return t;
+}
+
+std::vector<CiphertextBatch> emptyPlanes(const Context &ctx, size_t planes)
+{
+    return std::vector<CiphertextBatch>(planes, BatchAccess::make(ctx, 0, 1));
+}
+
+std::vector<CiphertextBatch> sumPlanes(const UIntBatch &a, uint64_t group, const std::vector<unsigned> &js, const char *who)
+{
+    requireGroup(a.plane(0), group, who);
+    if (a.size() == 0)
+        return emptyPlanes(a.context(), js.size());
+    // classes above the last plane never take part
+    const std::vector<uint64_t> n(std::min<size_t>(a.width(), *std::max_element(js.begin(), js.end()) + 1), group);
+    const std::vector<uint64_t> T = wsumSizes(a.context(), n, maxTerms(a, n.size()), js, who);
+    return wsumPlanes(a.context(), a.size() / group, planesOf(a), n, js, T, who);
+}
+
+// The classes of sum_r a_r * b_r over every `group` consecutive elements, up to class `top`: class c holds, row r
+// slowest, a_i * b_{c-i}, i ascending, a on the left; built from concat, gather and the batch operator*.
+std::vector<CiphertextBatch> productClasses(const UIntBatch &a, const UIntBatch &b, uint64_t group, const std::vector<uint64_t> &n)
+{
+    const uint64_t size = a.size(), count = size / group;
+    const CiphertextBatch L = CiphertextBatch::concat(planesOf(a)), R = CiphertextBatch::concat(planesOf(b));
+    std::vector<CiphertextBatch> cls;
+    for (size_t c = 0; c < n.size(); ++c) {
+        std::vector<uint64_t> il, ir;
+        for (uint64_t q = 0; q < count; ++q)
+            for (uint64_t r = 0; r < group; ++r)
+                for (uint64_t i = 0; i < a.width(); ++i)
+                    if (c >= i && c - i < b.width()) {
+                        il.push_back(i * size + q * group + r);
+                        ir.push_back((c - i) * size + q * group + r);
+                    }
+        cls.push_back(n[c] ? L.gather(il) * R.gather(ir) : L.slice(0, 0));
+    }
+    return cls;
+}
+
+UIntBatch productPlanes(const UIntBatch &a, const UIntBatch &b, uint64_t group, unsigned planes, const char *who)
+{
+    requirePlanes(planes, who);
+    if (a.size() != b.size() || !sameContext(a.context(), b.context()))
+        throw std::invalid_argument(std::string("certFHE::") + who + ": operands differ in count or context");
+    requireGroup(a.plane(0), group, who);
+    const Context &ctx = a.context();
+    if (a.size() == 0)
+        return UIntBatch::fromPlanes(emptyPlanes(ctx, planes));
+    // classes above the last plane never take part
+    std::vector<uint64_t> n(std::min<size_t>(planes, a.width() + b.width() - 1), 0);
+    for (size_t c = 0; c < n.size(); ++c)
+        for (uint64_t i = 0; i < a.width(); ++i)
+            n[c] += (c >= i && c - i < b.width()) ? group : 0;
+    unsigned long long t;
+    if (__builtin_mul_overflow((unsigned long long)maxTerms(a, n.size()), (unsigned long long)maxTerms(b, n.size()), &t) || t >= kMaxWords)
+        throw std::invalid_argument(std::string("certFHE::") + who + ": a partial product exceeds 2^31 words per element");
+    const std::vector<unsigned> js = firstPlanes(planes);
+    const std::vector<uint64_t> T = wsumSizes(ctx, n, t, js, who);
+    return UIntBatch::fromPlanes(wsumPlanes(ctx, a.size() / group, productClasses(a, b, group, n), n, js, T, who));
+}
+
+} // namespace
+
+UIntBatch sumValues(const UIntBatch &a, uint64_t group, unsigned planes)
+{
+    requirePlanes(planes, "sumValues");
+    return UIntBatch::fromPlanes(sumPlanes(a, group, firstPlanes(planes), "sumValues"));
+}
+
+CiphertextBatch sumBit(const UIntBatch &a, uint64_t group, unsigned j)
+{
+    return sumPlanes(a, group, std::vector<unsigned>(1, j), "sumBit")[0];
+}
+
+UIntBatch sumWhere(const CiphertextBatch &mask, const UIntBatch &values, uint64_t group, unsigned planes)
+{
+    requirePlanes(planes, "sumWhere");
+    requireSameBit(mask, values, "sumWhere");
+    requireGroup(mask, group, "sumWhere");
+    const Context &ctx = values.context();
+    if (values.size() == 0)
+        return UIntBatch::fromPlanes(emptyPlanes(ctx, planes));
+    const std::vector<uint64_t> n(std::min<size_t>(values.width(), planes), group);       // classes above the last plane never take part
+    unsigned long long t;
+    if (__builtin_mul_overflow((unsigned long long)termsOf(mask), (unsigned long long)maxTerms(values, n.size()), &t) || t >= kMaxWords)
+        throw std::invalid_argument("certFHE::sumWhere: a masked value exceeds 2^31 words per element");
+    const std::vector<unsigned> js = firstPlanes(planes);
+    const std::vector<uint64_t> T = wsumSizes(ctx, n, t, js, "sumWhere");
+    std::vector<CiphertextBatch> cls;
+    for (size_t c = 0; c < n.size(); ++c)
+        cls.push_back(mask * values.plane((unsigned)c));
+    return UIntBatch::fromPlanes(wsumPlanes(ctx, values.size() / group, cls, n, js, T, "sumWhere"));
+}
+
+UIntBatch mul(const UIntBatch &a, const UIntBatch &b, unsigned planes) { return productPlanes(a, b, 1, planes, "mul"); }
+
+UIntBatch UIntBatch::operator*(const UIntBatch &rhs) const { return mul(*this, rhs, width()); }
+
+UIntBatch innerProduct(const UIntBatch &a, const UIntBatch &b, uint64_t group, unsigned planes)
+{
+    return productPlanes(a, b, group, planes, "innerProduct");
+}
+
 } // namespace certFHE

@@ -1774,6 +1774,89 @@ int csgn_count(uint64_t n_bits, uint64_t count, uint64_t group, uint64_t t, cons
     return CSGN_OK;
 }
 
+/* ------------------------------------------------ encrypted integers summed into integers ---- */
+
+uint64_t csgn_wsum_terms(uint64_t n_classes, const uint64_t *h_n, uint64_t t, uint64_t j)
+{
+    return csgn::wsum_terms(n_classes, (const u64 *)h_n, t, j);
+}
+
+struct csgn_wsum_plan {
+    csgn::WsumPlan plan;
+};
+
+int csgn_wsum_create(uint64_t n_classes, const uint64_t *h_n, uint64_t t, uint64_t n_out, const uint64_t *h_js,
+                     csgn_wsum_plan **plan)
+{
+    REQUIRE(plan, "plan is null");
+    *plan = nullptr;
+    REQUIRE(n_out >= 1 && n_out <= csgn::kWsumMaxPlanes && h_js, "wsum: %llu planes (1..63), or h_js is null",
+            (unsigned long long)n_out);
+    uint64_t T[csgn::kWsumMaxPlanes];
+    const int checked = csgn::wsum_plan_check(n_classes, (const u64 *)h_n, t, n_out, (const u64 *)h_js, (u64 *)T);
+    if (checked == CSGN_ERR_INVALID)
+        return fail(checked, "wsum: %llu classes (1..64) of 1..65536 inputs in all, t = %llu (1..2^62 - 1), planes not "
+                             "strictly ascending within 0..62, or a plane with no count vector",
+                    (unsigned long long)n_classes, (unsigned long long)t);
+    if (checked != CSGN_OK)
+        return fail(checked, "wsum: a plane of 2^31 terms per element or more");
+    if (int rc = require_device("csgn_wsum_create"))
+        return rc;
+    csgn_wsum_plan *p = new csgn_wsum_plan();
+    hipError_t e = hipSuccess;
+    const int rc = csgn::wsum_plan_create(n_classes, (const u64 *)h_n, t, n_out, (const u64 *)h_js, p->plan, e);
+    if (rc != CSGN_OK) {
+        delete p;
+        return rc == CSGN_ERR_HIP ? hip_fail(e, "csgn_wsum_create")
+                                  : fail(rc, "wsum: more than 65536 count vectors, or a monomial of more than 3072 factors");
+    }
+    *plan = p;
+    return CSGN_OK;
+}
+
+uint64_t csgn_wsum_plan_terms(const csgn_wsum_plan *plan, uint64_t x)
+{
+    return plan && x < plan->plan.n_out ? plan->plan.T[x] : 0;
+}
+
+void csgn_wsum_destroy(csgn_wsum_plan *plan)
+{
+    if (!plan)
+        return;
+    csgn::wsum_plan_free(plan->plan);
+    delete plan;
+}
+
+int csgn_wsum(const csgn_wsum_plan *plan, uint64_t n_bits, uint64_t count, const uint64_t *const *h_in,
+              uint64_t *const *h_out, void *stream)
+{
+    if (int rc = check_n(n_bits))
+        return rc;
+    REQUIRE(plan, "plan is null");
+    REQUIRE(count, "wsum: no elements");
+    REQUIRE(h_in && h_out, "null host pointer");
+    const csgn::WsumPlan &p = plan->plan;
+    const uint64_t dl = csgn_default_len(n_bits);
+    for (u32 x = 0; x < p.n_out; ++x)
+        if (int rc = check_size(count, p.T[x], p.T[x], dl, "wsum: plane %u", p.js[x]))
+            return rc;
+    for (u32 c = 0; c < p.C; ++c) {
+        unsigned long long terms;                               // of class c in one element: below 2^47
+        if (__builtin_mul_overflow((unsigned long long)p.n[c], (unsigned long long)p.t, &terms))
+            terms = ~0ull;
+        if (!product_below(count, terms, dl, 1ull << 60))
+            return fail(CSGN_ERR_UNSUPPORTED, "batch of %llu elements: size overflows", (unsigned long long)count);
+    }
+    for (u32 c = 0; c < p.C; ++c)
+        REQUIRE(h_in[c] || p.n[c] == 0, "null device pointer (class %u)", c);
+    if (int rc = check_planes((const uint64_t *const *)h_out, nullptr, p.n_out, "output"))
+        return rc;
+    if (int rc = require_device("csgn_wsum"))
+        return rc;
+    HIP_TRY(csgn::wsum(p, n_bits, count, (const u64 *const *)h_in, (u64 *const *)h_out, S(stream)));
+    return CSGN_OK;
+}
+
 /* ------------------------------------------------------------------ tuning ---- */
 
 int csgn_set_tuning(const char *key, int value)

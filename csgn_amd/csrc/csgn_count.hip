@@ -60,54 +60,6 @@ struct CountArgs {
     FastDiv dIn;                // EG > 1: the staged units of one element, g * t * KC
 };
 
-// C(n, k), exact, for the binomials of an unranking: every one counts subsets of the call's own C(g, m) < 2^31, and so
-// does every value on the way (k <= n - k: they only grow).  The step c * (n - k + i) / i divides exactly and stays
-// below 2^31 * 2^17, so it is done in double precision, whose correctly rounded quotient of an exact division is the
-// integer itself -- a 64-bit integer division costs the device some 200 instructions, and a workgroup's threads each
-// take a dozen binomials before the first store.  Pairs, the common plane, need no division at all.
-__host__ __device__ inline u64 binom(u32 n, u32 k)
-{
-    if (k > n)
-        return 0;
-    if (k > n - k)
-        k = n - k;
-    if (k == 0)
-        return 1;
-    if (k == 1)
-        return n;
-    u64 c = ((u64)n * (n - 1u)) >> 1;
-    if (k == 2)
-        return c;
-    // C(n - k + i, i) from C(n - k + i - 1, i - 1), starting at C(n - k + 2, 2)
-    c = ((u64)(n - k + 2u) * (n - k + 1u)) >> 1;
-    for (u32 i = 3; i <= k; ++i)
-        c = (u64)((double)(c * (n - k + i)) / (double)i);
-    return c;
-}
-
-// the m-subset of {0 .. g-1} of lexicographic rank r: position k takes the largest v for which the subsets whose
-// position k is below v -- C(g - lo, m - k) - C(g - v, m - k) of them under the prefix -- are at most r
-template <typename Put>
-__host__ __device__ inline void unrank(u32 g, u32 m, u64 r, Put put)
-{
-    u32 lo = 0;
-    for (u32 k = 0; k < m; ++k) {
-        const u32 left = m - k;
-        const u64 all = binom(g - lo, left);
-        u32 a = lo, b = g - left + 1;
-        while (b - a > 1) {
-            const u32 mid = a + ((b - a) >> 1);
-            if (all - binom(g - mid, left) <= r)
-                a = mid;
-            else
-                b = mid;
-        }
-        r -= all - binom(g - a, left);
-        put(k, a);
-        lo = a + 1;
-    }
-}
-
 // input i of element e: its first unit (term 0, unit 0)
 template <typename Unit>
 __device__ inline const Unit *count_input(const CountArgs &a, u64 e, u32 i)

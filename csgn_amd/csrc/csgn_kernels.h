@@ -225,6 +225,36 @@ const char *count_kernel_name(u64 n_bits, u64 count, u64 group, u64 t, u64 n_in,
 hipError_t count(u64 n_bits, u64 count, u64 group, u64 t, const u64 *const *in, u64 n_in, u64 n_out, const u64 *js,
                  u64 *const *out, hipStream_t stream);
 
+// encrypted integers summed into encrypted integers (csgn_wsum.hip), include/csgn_hip.h's definition: class c holds n_c
+// ciphertexts of weight 2^c and of t terms each; plane j of an element is the sum, over the count vectors (m_j .. m_0)
+// with sum m_c 2^c = 2^j in ascending order and over their selections (class j slowest), of the products of the selected
+// inputs, classes descending.  A plan compiles the vectors of the requested planes for one (n_c, t); it lives in a
+// csgn_wsum_plan object of the caller's.
+constexpr u32 kWsumMaxClasses = 64, kWsumMaxPlane = 62, kWsumMaxPlanes = 63;
+constexpr u64 kWsumMaxInputs = 65536, kWsumMaxVectors = 65536;
+struct WsumPlan {
+    u32 C = 0, n_out = 0;
+    u64 t = 0;
+    u32 n[kWsumMaxClasses] = {};
+    u32 js[kWsumMaxPlanes] = {};
+    u64 T[kWsumMaxPlanes] = {};         // terms per element of plane js[x]
+    u32 ncls[kWsumMaxPlanes] = {};      // classes 0 .. ncls - 1 take part in plane js[x]
+    u32 nvec[kWsumMaxPlanes] = {}, vbase[kWsumMaxPlanes] = {}, parts[kWsumMaxPlanes] = {};
+    u64 max_part = 0;                   // terms of the largest part
+    u32 sub_bytes = 0;                  // bytes of member indices of the largest part
+    u32 *d_vt = nullptr;                // the vector table (csgn_wsum.hip)
+    std::vector<u32> vt;                // its host copy
+};
+u64 wsum_terms(u64 n_classes, const u64 *n, u64 t, u64 j);   // 0: a bad argument, an empty plane or 2^62 terms or more
+// the arguments of a plan and T[x] of every plane: CSGN_ERR_INVALID (an empty plane among them), else
+// CSGN_ERR_UNSUPPORTED when a plane reaches 2^31 terms
+int wsum_plan_check(u64 n_classes, const u64 *n, u64 t, u64 n_out, const u64 *js, u64 *T);
+// after wsum_plan_check: enumerates and uploads (synchronous); CSGN_ERR_UNSUPPORTED past kWsumMaxVectors vectors or
+// for a monomial of more than 3072 factors
+int wsum_plan_create(u64 n_classes, const u64 *n, u64 t, u64 n_out, const u64 *js, WsumPlan &p, hipError_t &herr);
+void wsum_plan_free(WsumPlan &p);
+hipError_t wsum(const WsumPlan &p, u64 n_bits, u64 count, const u64 *const *in, u64 *const *out, hipStream_t stream);
+
 // selection by an encrypted comparison (csgn_uint_lt_select.hip), include/csgn_hip.h's definition: output i is
 // (L * (X_i + Y_i)) + Y_i with L = lessThan(a, b), the LT_FIRST / LT_STEP chain.  a and b: w = 1..16 planes, terms ta[j] /
 // tb[j]; requests: n_out = 0..64 pairs of planes, terms tx[i] / ty[i]; less: nullptr = not written (then n_out >= 1).

@@ -41,6 +41,7 @@ const Knob kKnobs[TUNE_COUNT] = {
     {"matmul_epart", 0},
     {"count_form", -1},
     {"count_cpart", 0},
+    {"wsum_cpart", 0},
     {"uint_lt_select_form", -1},
     {"uint_pick_fused", -1},
     {"uint_pick_stage", -1},

@@ -145,6 +145,23 @@
 // does not divide size(), `planes` of 0 or above 64, mismatched contexts or widths, or a plane past 2^31 words per
 // element.  An empty batch gives empty planes.
 //
+// SUMS: sumValues(a, g, planes) adds every g consecutive integers of a batch into an encrypted integer modulo
+// 2^planes, sumWhere(mask, values, g, planes) only those whose encrypted mask bit is set (SUM(value) of the matching
+// rows), mul(a, b, planes) multiplies two encrypted integers and innerProduct(a, b, g, planes) adds g products.  All are
+// one weighted sum of encrypted bits (include/csgn_hip.h, csgn_wsum): class c holds the bits of weight 2^c -- plane c of
+// the g rows; mask * values.plane(c); the partial products a_i * b_{c-i}, i ascending, a on the left; those of every
+// row, row slowest -- and bit j of the sum is the sum, over the count vectors (m_j .. m_0) with sum m_c 2^c = 2^j in
+// ascending order and over their selections, of the product of the selected bits, classes descending: no carry is
+// ever materialised.  Term counts of fresh operands, planes 0, 1, 2, ...: the sum of 4 three-bit integers 4, 10, 35,
+// 161, 315; a 4 x 4 -> 8 bit product 1, 2, 4, 10, 34, 129, 383, 511.  A plane with no count vector is the one-term ZERO
+// of constantBatch.  Plane 0 of sumValues is plane(0).sumGroups(g): it shares the payload and costs no launch.
+// Uniform classes of one term count take ONE csgn_wsum (one launch; plans are kept per shape); ragged operands (a
+// compact() result) or planes of different term counts are composed from gather, operator*, sumGroups and operator+ in
+// the definition's loop order, with the same words.  Every size is computed before anything is allocated or launched:
+// std::invalid_argument for a group of 0 or one that does not divide size(), `planes` of 0 or above 64, mismatched
+// contexts or counts, more than 65 536 bits an element, or a plane past 2^31 words per element.  An empty batch gives
+// empty planes.  Multiplication by a PUBLIC constant stays with LookupTable.
+//
 // ORDERING: min(a, b), max(a, b), minMax(a, b), selectLess(a, b, x, y) and compareExchange select by the ENCRYPTED
 // comparison a < b: the step of every oblivious sort, top-k, median filter, arg-min and clamp.  Every output plane is
 // logicMux(lessThan(a, b), x_j, y_j) = (L * (x_j + y_j)) + y_j, the comparison the LEFT operand -- the words of
@@ -212,6 +229,8 @@ class UIntBatch {
 
     UIntBatch operator+(const UIntBatch &rhs) const;
     UIntBatch operator-(const UIntBatch &rhs) const;
+    // a * b modulo 2^width: mul(*this, rhs, width())
+    UIntBatch operator*(const UIntBatch &rhs) const;
 
     // with the public constant k < 2^width (std::invalid_argument otherwise), modulo 2^width
     UIntBatch operator+(uint64_t k) const;
@@ -329,6 +348,16 @@ UIntBatch hammingDistance(const UIntBatch &a, const UIntBatch &b, unsigned plane
 // element e: the number of rows r with keys[r] == query[e], modulo 2^planes: countOnes over the batch whose element
 // e*n + r is equalTo(keys row r, query element e); plane 0 has the words of matches(keys, query)
 UIntBatch countMatches(const UIntBatch &keys, const UIntBatch &query, unsigned planes);
+
+// element q: the sum of a[q*group .. q*group+group-1], modulo 2^planes; planes >= 1 / its bit j alone
+UIntBatch sumValues(const UIntBatch &a, uint64_t group, unsigned planes);
+CiphertextBatch sumBit(const UIntBatch &a, uint64_t group, unsigned j);
+// element q: the sum over the group's rows r of mask[r] ? values[r] : 0, modulo 2^planes: SUM(value) WHERE mask
+UIntBatch sumWhere(const CiphertextBatch &mask, const UIntBatch &values, uint64_t group, unsigned planes);
+// element i: a[i] * b[i] modulo 2^planes; one context and element count, any widths
+UIntBatch mul(const UIntBatch &a, const UIntBatch &b, unsigned planes);
+// element q: the sum over the group's rows r of a[r] * b[r], modulo 2^planes
+UIntBatch innerProduct(const UIntBatch &a, const UIntBatch &b, uint64_t group, unsigned planes);
 
 } // namespace certFHE
 

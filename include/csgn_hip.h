@@ -1134,6 +1134,65 @@ const char *csgn_count_kernel(uint64_t n_bits, uint64_t count, uint64_t group, u
 int csgn_count(uint64_t n_bits, uint64_t count, uint64_t group, uint64_t t, const uint64_t *const *h_in, uint64_t n_in,
                uint64_t n_out, const uint64_t *h_js, uint64_t *const *h_out, void *stream);
 
+/* ------------------------------------------------ encrypted integers summed into integers ---- */
+
+/* ENCRYPTED integers summed into ENCRYPTED integers: SUM(value) of the matching rows, the product of two encrypted
+ * integers, the inner product of two vectors of them.  For bits x_i of public weights 2^{e_i}, bit j of
+ * S = sum 2^{e_i} x_i is C(S, 2^j) mod 2, the coefficient of z^(2^j) in (1 + z)^S; over F2,
+ * (1 + z)^(2^e x) = 1 + x z^(2^e).  So bit j of S is the sum, over the subsets of inputs whose weights add up to
+ * EXACTLY 2^j, of the product of their members.  With all weights 1 this is csgn_count's definition.
+ * Inputs.  An output element has C weight classes, 1 <= C <= 64.
+ *   - Class c holds n_c >= 0 ciphertexts of weight 2^c, each of t terms.
+ *   - t is uniform over the call.
+ *   - sum n_c >= 1 and sum n_c <= 65 536.
+ * Output plane j (j <= 62) of element q is the left-nested sum (operator+, a concatenation) of monomials, in this
+ * order:
+ *   1. Count vectors.  A count vector is (m_j, m_{j-1}, ..., m_0) with sum m_c 2^c = 2^j and 0 <= m_c <= n_c.  Take
+ *      n_c = 0 for c >= C.  Classes above j never take part.
+ *      - The vectors come in ascending lexicographic order, m_j most significant.
+ *      - This is the order of the nested loops `for m_j = 0...: for m_{j-1} = 0...: ...`, with m_0 the remainder,
+ *        skipped when it exceeds n_0.
+ *   2. Selections within a vector.  A selection is (S_j, ..., S_0), S_c an m_c-subset of class c.  S_j is slowest and
+ *      S_0 fastest.  Each class's subsets run in lexicographic order (csgn_count's order).
+ *   3. The monomial of a selection.  It is the left-nested product (operator*, left term slow) of its members:
+ *      classes descending, indices ascending within a class.  It has t^(sum m_c) terms, the first factor's digit
+ *      slowest.
+ * Term count.  T_j = sum over the vectors of prod_c C(n_c, m_c) t^{m_c}.
+ *   - With one class, plane j has exactly csgn_count's words.
+ *   - A plane with no count vector is always 0.  The C ABI refuses it.  The classes return the one-term ZERO.
+ * Term counts of fresh inputs (t = 1), planes 0, 1, 2, ...: the sum of 4 three-bit integers 4, 10, 35, 161, 315; of 8
+ * four-bit integers 8, 36, 330, 6435, 245 149; a 4 x 4 -> 8 bit product 1, 2, 4, 10, 34, 129, 383, 511; the low 8 bits of
+ * an 8 x 8 product 1, 2, 4, 10, 36, 202, 1828, 27 338.  The higher planes of wide groups are past any memory: a call
+ * names the planes it wants as a list. */
+/* T_j (host only).  h_n: n_classes counts.  0 for a bad argument (n_classes outside 1..64, a null h_n, sum n_c outside
+ * 1..65 536, t = 0 or t >= 2^62, j > 62), for a plane with no count vector, or for a count of 2^62 or more. */
+uint64_t csgn_wsum_terms(uint64_t n_classes, const uint64_t *h_n, uint64_t t, uint64_t j);
+/* A plan: the count vectors of the planes h_js (n_out of them, 1..63, strictly ascending) of one shape (n_c, t),
+ * enumerated with pruning and uploaded once, synchronously: per plane and vector the first term, the selections, every
+ * m_c, C(n_c, m_c) and the degree.  Checks, in this order: plan non-null, the arguments csgn_wsum_terms refuses, n_out,
+ * h_js, a plane with no count vector (CSGN_ERR_INVALID); a plane of 2^31 terms or more (CSGN_ERR_UNSUPPORTED); the
+ * device (CSGN_ERR_NO_DEVICE); then, while enumerating, more than 65 536 vectors over the planes, or a monomial of more
+ * than 3072 factors (CSGN_ERR_UNSUPPORTED).  Knob "wsum_cpart" is read here: it forces the selection ranks of a
+ * workgroup's part. */
+typedef struct csgn_wsum_plan csgn_wsum_plan;
+int csgn_wsum_create(uint64_t n_classes, const uint64_t *h_n, uint64_t t, uint64_t n_out, const uint64_t *h_js,
+                     csgn_wsum_plan **plan);
+/* T of the plan's plane x (host only); 0 for a null plan or x past its planes */
+uint64_t csgn_wsum_plan_terms(const csgn_wsum_plan *plan, uint64_t x);
+void csgn_wsum_destroy(csgn_wsum_plan *plan);
+/* The sum over `count` elements in one kernel, k_wsum: a workgroup stages the inputs of the classes that take part in
+ * LDS once, unranks the selections of its part of one count vector and streams its outputs.  h_in: a HOST array of C
+ * device pointers.  Class c is one batch of count * n_c elements; input i of element q is element q * n_c + i.  The
+ * pointer may be null where n_c = 0.  h_out[x] takes count * T_{js[x]} * dL words.  Inputs may alias one another; no
+ * output overlaps an input or another output.  Checks, in this order, the first that fails giving the status: n_bits;
+ * plan, count nonzero, host pointers non-null (CSGN_ERR_INVALID); every T_j * dL below 2^31 words per element and
+ * count * T_j * dL and every class's count * n_c * t * dL below 2^60 (CSGN_ERR_UNSUPPORTED; computed without
+ * wrap-around); null device pointers (CSGN_ERR_INVALID); the device (CSGN_ERR_NO_DEVICE, no CPU fallback).  Nothing is
+ * allocated or launched before every check has passed.  On the caller's stream, asynchronous; one launch for every
+ * shape within memory and graph-capturable. */
+int csgn_wsum(const csgn_wsum_plan *plan, uint64_t n_bits, uint64_t count, const uint64_t *const *h_in,
+              uint64_t *const *h_out, void *stream);
+
 /* ------------------------------------------------------------------- tuning ---- */
 
 /* Kernel-choice and sweep knobs ("mul_flat", "mul_touch", "ragged_c", "perm_ballot", ...;
