@@ -471,6 +471,34 @@ class HipPath:
                                            _ptr(less), self.stream))
         return [o[:s] for o, s in zip(outs, sizes)], (None if less is None else less[: batch * L * dl])
 
+    def uint_arith(self, n_bits: int, op: int, batch: int, a, a_terms, b, b_terms, outs=None, carry=False):
+        """csgn_uint_arith: op = 1 a + b, 2 a - b, 3 a == b, 4 a != b of the encrypted integers a and b (bit 0 first;
+        plane j a uniform batch of a_terms[j] / b_terms[j] terms).  Returns (output tensors, carry tensor or None): the
+        planes of a sum or difference, or the one result of a comparison, of csgn_uint_arith_terms terms per element,
+        fresh ones unless `outs` is given; `carry` (sums and differences): True for a fresh tensor, or the tensor to
+        write."""
+        w = len(a)
+        assert w == len(a_terms) == len(b) == len(b_terms)
+        h_ta = (C.c_uint64 * max(w, 1))(*[int(t) for t in a_terms])
+        h_tb = (C.c_uint64 * max(w, 1))(*[int(t) for t in b_terms])
+        n_out = w if op in (1, 2) else 1
+        T = [int(self.lib.csgn_uint_arith_terms(op, w, h_ta, h_tb, o)) for o in range(n_out)]
+        assert all(T), "bad operation, width or term count"
+        dl = self.default_len(n_bits)
+        sizes = [batch * t * dl for t in T]
+        if outs is None:
+            outs = [self.empty_words(max(s, 1)) for s in sizes]
+        csize = batch * int(self.lib.csgn_uint_arith_terms(op, w, h_ta, h_tb, w)) * dl
+        if carry is True:
+            carry = self.empty_words(max(csize, 1))
+        elif carry is False:
+            carry = None
+        h_a = (C.c_void_p * max(w, 1))(*[_ptr(p) for p in a])
+        h_b = (C.c_void_p * max(w, 1))(*[_ptr(p) for p in b])
+        h_out = (C.c_void_p * max(n_out, 1))(*[_ptr(o) for o in outs])
+        check(self.lib.csgn_uint_arith(n_bits, op, batch, w, h_a, h_ta, h_b, h_tb, h_out, _ptr(carry), self.stream))
+        return [o[:s] for o, s in zip(outs, sizes)], (None if carry is None else carry[:csize])
+
     def matmul(self, n_bits: int, rows: int, inner: int, cols: int, a: torch.Tensor, t_a: int, b: torch.Tensor, t_b: int,
                transposed: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """csgn_matmul: the product over F2 of the encrypted bit matrices `a` (rows x inner, element i*inner + e, t_a

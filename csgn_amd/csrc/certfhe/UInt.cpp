@@ -201,48 +201,99 @@ std::vector<CiphertextBatch> step(int st, const CiphertextBatch *x, const Cipher
 
 // ------------------------------------------------------------------ whole operations
 
-std::vector<CiphertextBatch> add(const UIntBatch &a, const UIntBatch &b)
+// Whether an operation of a and b is one call (csgn_uint_arith, or csgn_uint_lt_select for the comparison) or the
+// per-bit chain below: ragged planes and integers wider than 16 bits take the chain.  Knob uint_arith_form decides for
+// the rest when it is forced (0 the chain, 1 the one call); left per shape, a forced uint_fused keeps the chain, so
+// that csgn_uint_step's two forms can still be run through these operators.
+bool oneCall(unsigned width, bool uniform)
+{
+    if (width > 16 || !uniform)
+        return false;
+    int form = -1, steps = -1;
+    csgn_get_tuning("uint_arith_form", &form);
+    csgn_get_tuning("uint_fused", &steps);
+    return form == 0 ? false : form == 1 ? true : steps == -1;
+}
+
+bool oneCall(const UIntBatch &a, const Planes &pa, const Planes &pb)
+{
+    return oneCall(a.width(), (pa.uniform && pb.uniform) || a.size() == 0);
+}
+
+// csgn_uint_arith into fresh planes of T[j] terms (one result for EQ / NE); *carry_out = the carry of carry_terms terms
+std::vector<CiphertextBatch> arithPlanes(int op, const UIntBatch &a, const Planes &pa, const Planes &pb,
+                                         const std::vector<uint64_t> &T, uint64_t carry_terms, CiphertextBatch *carry_out)
 {
     const Context &ctx = a.context();
-    const unsigned w = a.width();
-    uint64_t c = stepTerms(CSGN_UINT_ADD_HALF, 0, 0, termsOf(a.plane(0)), termsOf(b.plane(0)), ctx, "operator+");
-    if (w > 1)
-        c = stepTerms(CSGN_UINT_ADD_HALF, 1, 0, termsOf(a.plane(0)), termsOf(b.plane(0)), ctx, "operator+");
-    for (unsigned j = 1; j < w; ++j) {
-        const uint64_t ta = termsOf(a.plane(j)), tb = termsOf(b.plane(j));
-        stepTerms(CSGN_UINT_ADD_FULL, 0, c, ta, tb, ctx, "operator+");
-        if (j + 1 < w)
-            c = stepTerms(CSGN_UINT_ADD_FULL, 1, c, ta, tb, ctx, "operator+");
-    }
-    std::vector<CiphertextBatch> r = step(CSGN_UINT_ADD_HALF, nullptr, a.plane(0), b.plane(0), w > 1);
-    std::vector<CiphertextBatch> out(1, r[0]);
-    for (unsigned j = 1; j < w; ++j) {
-        const CiphertextBatch carry = r[1];
-        r = step(CSGN_UINT_ADD_FULL, &carry, a.plane(j), b.plane(j), j + 1 < w);
-        out.push_back(r[0]);
-    }
+    std::vector<CiphertextBatch> out = makePlanes(ctx, a.size(), T);
+    CiphertextBatch carry = BatchAccess::make(ctx, carry_out ? a.size() : 0, carry_terms);
+    if (a.size())
+        detail::check(csgn_uint_arith(ctx.getN(), op, a.size(), a.width(), sources(pa).data(), pa.terms.data(),
+                                      sources(pb).data(), pb.terms.data(), wordsOf(out).data(),
+                                      carry_out ? BatchAccess::words(carry) : nullptr, detail::stream()),
+                      "csgn_uint_arith");
+    if (carry_out)
+        *carry_out = carry;
     return out;
 }
 
-std::vector<CiphertextBatch> sub(const UIntBatch &a, const UIntBatch &b)
+// the planes of a + b; *carry_out (may be null) = the carry out of the top plane
+std::vector<CiphertextBatch> add(const UIntBatch &a, const UIntBatch &b, CiphertextBatch *carry_out, const char *who)
 {
     const Context &ctx = a.context();
     const unsigned w = a.width();
+    std::vector<uint64_t> T(w);
+    uint64_t c = T[0] = stepTerms(CSGN_UINT_ADD_HALF, 0, 0, termsOf(a.plane(0)), termsOf(b.plane(0)), ctx, who);
+    if (w > 1 || carry_out)
+        c = stepTerms(CSGN_UINT_ADD_HALF, 1, 0, termsOf(a.plane(0)), termsOf(b.plane(0)), ctx, who);
+    for (unsigned j = 1; j < w; ++j) {
+        const uint64_t ta = termsOf(a.plane(j)), tb = termsOf(b.plane(j));
+        T[j] = stepTerms(CSGN_UINT_ADD_FULL, 0, c, ta, tb, ctx, who);
+        if (j + 1 < w || carry_out)
+            c = stepTerms(CSGN_UINT_ADD_FULL, 1, c, ta, tb, ctx, who);
+    }
+    const Planes pa(a), pb(b);
+    if (oneCall(a, pa, pb))
+        return arithPlanes(CSGN_UINT_ARITH_ADD, a, pa, pb, T, c, carry_out);
+    std::vector<CiphertextBatch> r = step(CSGN_UINT_ADD_HALF, nullptr, a.plane(0), b.plane(0), w > 1 || carry_out);
+    std::vector<CiphertextBatch> out(1, r[0]);
+    for (unsigned j = 1; j < w; ++j) {
+        const CiphertextBatch carry = r[1];
+        r = step(CSGN_UINT_ADD_FULL, &carry, a.plane(j), b.plane(j), j + 1 < w || carry_out);
+        out.push_back(r[0]);
+    }
+    if (carry_out)
+        *carry_out = r[1];
+    return out;
+}
+
+// the planes of a - b = a + ~b + 1; *carry_out (may be null) = the carry out of the top plane: 1 where a >= b
+std::vector<CiphertextBatch> sub(const UIntBatch &a, const UIntBatch &b, CiphertextBatch *carry_out, const char *who)
+{
+    const Context &ctx = a.context();
+    const unsigned w = a.width();
+    std::vector<uint64_t> T(w);
     uint64_t c = 1;
     for (unsigned j = 0; j < w; ++j) {
-        const uint64_t ta = termsOf(a.plane(j)), tnb = gateTerms(CSGN_GATE_NOT, 0, termsOf(b.plane(j)), 0, ctx, "operator-");
-        stepTerms(CSGN_UINT_ADD_FULL, 0, c, ta, tnb, ctx, "operator-");
-        if (j + 1 < w)
-            c = stepTerms(CSGN_UINT_ADD_FULL, 1, c, ta, tnb, ctx, "operator-");
+        const uint64_t ta = termsOf(a.plane(j)), tnb = gateTerms(CSGN_GATE_NOT, 0, termsOf(b.plane(j)), 0, ctx, who);
+        T[j] = stepTerms(CSGN_UINT_ADD_FULL, 0, c, ta, tnb, ctx, who);
+        if (j + 1 < w || carry_out)
+            c = stepTerms(CSGN_UINT_ADD_FULL, 1, c, ta, tnb, ctx, who);
     }
+    const Planes pa(a), pb(b);
+    if (oneCall(a, pa, pb))
+        return arithPlanes(CSGN_UINT_ARITH_SUB, a, pa, pb, T, c, carry_out);
     CiphertextBatch carry = ones(a.plane(0));                // a + ~b + 1: the first carry in is ONE
     std::vector<CiphertextBatch> out;
     for (unsigned j = 0; j < w; ++j) {
-        const std::vector<CiphertextBatch> r = step(CSGN_UINT_ADD_FULL, &carry, a.plane(j), logicNot(b.plane(j)), j + 1 < w);
+        const bool more = j + 1 < w || carry_out;
+        const std::vector<CiphertextBatch> r = step(CSGN_UINT_ADD_FULL, &carry, a.plane(j), logicNot(b.plane(j)), more);
         out.push_back(r[0]);
-        if (j + 1 < w)
+        if (more)
             carry = r[1];
     }
+    if (carry_out)
+        *carry_out = carry;
     return out;
 }
 
@@ -256,8 +307,22 @@ uint64_t lessThanTerms(const UIntBatch &a, const UIntBatch &b, const char *who)
     return l;
 }
 
-CiphertextBatch lessThanUnchecked(const UIntBatch &a, const UIntBatch &b)
+// lessThan(a, b) after lessThanTerms, of `terms` terms when the caller has them (0: the chain alone): the comparison
+// alone from csgn_uint_lt_select (no requests, d_less), or the chain
+CiphertextBatch lessThanUnchecked(const UIntBatch &a, const UIntBatch &b, uint64_t terms = 0)
 {
+    if (terms) {
+        const Planes pa(a), pb(b);
+        if (oneCall(a, pa, pb)) {
+            CiphertextBatch out = BatchAccess::make(a.context(), a.size(), terms);
+            if (a.size())
+                detail::check(csgn_uint_lt_select(a.context().getN(), a.size(), a.width(), sources(pa).data(),
+                                                  pa.terms.data(), sources(pb).data(), pb.terms.data(), 0, nullptr, nullptr,
+                                                  nullptr, nullptr, nullptr, BatchAccess::words(out), detail::stream()),
+                              "csgn_uint_lt_select");
+            return out;
+        }
+    }
     CiphertextBatch l = step(CSGN_UINT_LT_FIRST, nullptr, a.plane(0), b.plane(0), false)[0];
     for (unsigned j = 1; j < a.width(); ++j)
         l = step(CSGN_UINT_LT_STEP, &l, a.plane(j), b.plane(j), false)[0];
@@ -273,12 +338,17 @@ uint64_t equalToTerms(const UIntBatch &a, const UIntBatch &b, const char *who)
     return e;
 }
 
-CiphertextBatch equalToUnchecked(const UIntBatch &a, const UIntBatch &b)
+// equalTo(a, b) after equalToTerms, or its logicNot when `negate`; `terms`: the result's
+CiphertextBatch equalToUnchecked(const UIntBatch &a, const UIntBatch &b, uint64_t terms, bool negate)
 {
+    const Planes pa(a), pb(b);
+    if (oneCall(a, pa, pb))
+        return arithPlanes(negate ? CSGN_UINT_ARITH_NE : CSGN_UINT_ARITH_EQ, a, pa, pb, std::vector<uint64_t>(1, terms), 0,
+                           nullptr)[0];
     CiphertextBatch e = logicXnor(a.plane(0), b.plane(0));
     for (unsigned j = 1; j < a.width(); ++j)
         e = step(CSGN_UINT_EQ_STEP, &e, a.plane(j), b.plane(j), false)[0];
-    return e;
+    return negate ? logicNot(e) : e;
 }
 
 // ------------------------------------------------------------------ comparisons with a public constant
@@ -543,13 +613,25 @@ std::vector<uint64_t> UIntBatch::decrypt(const SecretKey &key) const
 UIntBatch UIntBatch::operator+(const UIntBatch &rhs) const
 {
     requireSame(*this, rhs, "UIntBatch::operator+");
-    return UIntBatch(certFHE::add(*this, rhs));   // the helper above, not the member
+    return UIntBatch(certFHE::add(*this, rhs, nullptr, "operator+"));   // the helper above, not the member
 }
 
 UIntBatch UIntBatch::operator-(const UIntBatch &rhs) const
 {
     requireSame(*this, rhs, "UIntBatch::operator-");
-    return UIntBatch(sub(*this, rhs));
+    return UIntBatch(certFHE::sub(*this, rhs, nullptr, "operator-"));
+}
+
+UIntBatch UIntBatch::add(const UIntBatch &rhs, CiphertextBatch *carry_out) const
+{
+    requireSame(*this, rhs, "UIntBatch::add");
+    return UIntBatch(certFHE::add(*this, rhs, carry_out, "UIntBatch::add"));
+}
+
+UIntBatch UIntBatch::sub(const UIntBatch &rhs, CiphertextBatch *carry_out) const
+{
+    requireSame(*this, rhs, "UIntBatch::sub");
+    return UIntBatch(certFHE::sub(*this, rhs, carry_out, "UIntBatch::sub"));
 }
 
 UIntBatch UIntBatch::operator+(uint64_t k) const { return UIntBatch(addPlain(*this, k, false, nullptr, "UIntBatch::operator+")); }
@@ -661,32 +743,31 @@ UIntBatch UIntBatch::rotateRight(unsigned s) const { return rotateLeft(width() -
 
 // ------------------------------------------------------------------ comparisons and select
 
+const char *arithRoute(unsigned width, bool uniform_planes) { return oneCall(width, uniform_planes) ? "call" : "chain"; }
+
 CiphertextBatch equalTo(const UIntBatch &a, const UIntBatch &b)
 {
     requireSame(a, b, "equalTo");
-    equalToTerms(a, b, "equalTo");
-    return equalToUnchecked(a, b);
+    return equalToUnchecked(a, b, equalToTerms(a, b, "equalTo"), false);
 }
 
 CiphertextBatch notEqualTo(const UIntBatch &a, const UIntBatch &b)
 {
     requireSame(a, b, "notEqualTo");
-    gateTerms(CSGN_GATE_NOT, 0, equalToTerms(a, b, "notEqualTo"), 0, a.context(), "notEqualTo");
-    return logicNot(equalToUnchecked(a, b));
+    return equalToUnchecked(a, b, gateTerms(CSGN_GATE_NOT, 0, equalToTerms(a, b, "notEqualTo"), 0, a.context(), "notEqualTo"),
+                            true);
 }
 
 CiphertextBatch lessThan(const UIntBatch &a, const UIntBatch &b)
 {
     requireSame(a, b, "lessThan");
-    lessThanTerms(a, b, "lessThan");
-    return lessThanUnchecked(a, b);
+    return lessThanUnchecked(a, b, lessThanTerms(a, b, "lessThan"));
 }
 
 CiphertextBatch greaterThan(const UIntBatch &a, const UIntBatch &b)
 {
     requireSame(a, b, "greaterThan");
-    lessThanTerms(b, a, "greaterThan");
-    return lessThanUnchecked(b, a);
+    return lessThanUnchecked(b, a, lessThanTerms(b, a, "greaterThan"));
 }
 
 CiphertextBatch lessEqual(const UIntBatch &a, const UIntBatch &b)

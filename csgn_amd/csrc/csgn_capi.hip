@@ -1693,6 +1693,57 @@ int csgn_uint_lt_select(uint64_t n_bits, uint64_t batch, uint64_t width, const u
     return CSGN_OK;
 }
 
+/* ------------------------------------------------ sums, differences and equality of two integers ---- */
+
+uint64_t csgn_uint_arith_terms(int op, uint64_t width, const uint64_t *h_a_terms, const uint64_t *h_b_terms,
+                               uint64_t output)
+{
+    return csgn::uint_arith_terms(op, width, (const u64 *)h_a_terms, (const u64 *)h_b_terms, output);
+}
+
+const char *csgn_uint_arith_kernel(uint64_t n_bits, int op, uint64_t batch, uint64_t width, const uint64_t *h_a_terms,
+                                   const uint64_t *h_b_terms, int with_carry)
+{
+    return csgn::uint_arith_kernel_name(n_bits, op, batch, width, (const u64 *)h_a_terms, (const u64 *)h_b_terms,
+                                        with_carry != 0);
+}
+
+int csgn_uint_arith(uint64_t n_bits, int op, uint64_t batch, uint64_t width, const uint64_t *const *h_a,
+                    const uint64_t *h_a_terms, const uint64_t *const *h_b, const uint64_t *h_b_terms,
+                    uint64_t *const *h_out, uint64_t *d_carry, void *stream)
+{
+    if (int rc = check_n(n_bits))
+        return rc;
+    REQUIRE(op >= CSGN_UINT_ARITH_ADD && op <= CSGN_UINT_ARITH_NE, "arith: unknown operation %d", op);
+    REQUIRE(width >= 1 && width <= csgn::kArithMaxWidth, "arith: width %llu outside 1..16", (unsigned long long)width);
+    REQUIRE(h_a && h_a_terms && h_b && h_b_terms && h_out, "null host pointer");
+    const bool sum = op <= CSGN_UINT_ARITH_SUB;
+    REQUIRE(sum || !d_carry, "arith: a comparison has no carry output");
+    const uint64_t outputs = sum ? width + (d_carry ? 1 : 0) : 1;
+    const uint64_t dl = csgn_default_len(n_bits);
+    for (uint64_t o = 0; o < outputs; ++o)
+        REQUIRE(csgn::uint_arith_terms(op, width, (const u64 *)h_a_terms, (const u64 *)h_b_terms, o) != 0,
+                "arith: a plane of a or b has no terms, or the term count of output %llu overflows", (unsigned long long)o);
+    for (uint64_t o = 0; o < outputs; ++o) {
+        const uint64_t terms = csgn::uint_arith_terms(op, width, (const u64 *)h_a_terms, (const u64 *)h_b_terms, o);
+        if (int rc = check_size(batch, terms, terms, dl, sum && o == width ? "arith: the carry" : "arith: output %llu",
+                                (unsigned long long)o))
+            return rc;
+    }
+    if (int rc = check_planes(h_a, h_b, width, "plane of a or b"))
+        return rc;
+    if (int rc = check_planes((const uint64_t *const *)h_out, nullptr, sum ? width : 1, "output"))
+        return rc;
+    if (int rc = require_device("csgn_uint_arith"))
+        return rc;
+    if (batch == 0)
+        return CSGN_OK;
+    HIP_TRY(csgn::uint_arith(n_bits, op, batch, width, (const u64 *const *)h_a, (const u64 *)h_a_terms,
+                             (const u64 *const *)h_b, (const u64 *)h_b_terms, (u64 *const *)h_out, (u64 *)d_carry,
+                             S(stream)));
+    return CSGN_OK;
+}
+
 /* ------------------------------------------------ encrypted bit matrices over F2 ---- */
 
 uint64_t csgn_matmul_terms(uint64_t inner, uint64_t t_a, uint64_t t_b) { return csgn::matmul_terms(inner, t_a, t_b); }

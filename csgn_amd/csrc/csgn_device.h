@@ -446,7 +446,7 @@ __device__ inline bool chain_walk(const Args &a, u32 hi, u32 lo, u64 eu, u32 k, 
 // For a workgroup's elements and its slice of KC units of every term, table k holds the AND of every subset of the
 // fresh (one-term) planes [hb[k], hb[k+1]), entry S of element el at units tbase[k] + ((el << h_k) | S) * KC on; the
 // AND of any subset of all the planes is then one to three LDS reads (csgn_uint_lut.hip, and through csgn_selector.h
-// csgn_uint_read.hip, csgn_uint_find.hip and csgn_uint_lt_select.hip).
+// csgn_uint_read.hip, csgn_uint_find.hip, csgn_uint_lt_select.hip and csgn_uint_arith.hip).
 constexpr u32 kMaxSubsetTables = 3;
 
 // by value in the kernel arguments
@@ -502,7 +502,9 @@ __device__ inline Unit subset_and(const Unit *tab, const SubsetTables &t, u32 el
 }
 
 // The host plan: the table split and the unit slices of `planes` fresh planes (0: no tables) at U units of unit_bytes
-// per term within `budget` bytes of LDS per workgroup; layout(G) places the tables of G elements.
+// per term within `budget` bytes of LDS per workgroup; layout(G) places the tables of G elements.  min_tables asks for
+// that many tables (no more than planes or kMaxSubsetTables) where the planes alone would get fewer: smaller tables and
+// one more LDS read per AND, for an operation that writes few terms per element (csgn_uint_arith.hip).
 struct SubsetPlan {
     SubsetTables t;
     u64 entries;              // table units per element and unit of a term
@@ -521,13 +523,13 @@ struct SubsetPlan {
     }
 };
 
-inline SubsetPlan subset_plan(u32 planes, u32 U, u32 unit_bytes, u64 budget)
+inline SubsetPlan subset_plan(u32 planes, u32 U, u32 unit_bytes, u64 budget, u32 min_tables = 1)
 {
     SubsetPlan p = {};
     p.unit_bytes = unit_bytes;
     // one table up to 5 planes, two up to 10, three above; the low tables take the odd planes
     if (planes) {
-        p.t.ntab = planes <= 5 ? 1 : planes <= 10 ? 2 : 3;
+        p.t.ntab = std::max(planes <= 5 ? 1u : planes <= 10 ? 2u : 3u, std::min({min_tables, planes, kMaxSubsetTables}));
         for (u32 k = 0; k < p.t.ntab; ++k) {
             const u32 h = (planes - p.t.hb[k] + (p.t.ntab - k) - 1) / (p.t.ntab - k);
             p.t.hb[k + 1] = p.t.hb[k] + h;

@@ -266,6 +266,15 @@ hipError_t uint_lt_select(u64 n_bits, u64 batch, u64 w, const u64 *const *a, con
                           const u64 *tb, u64 n_out, const u64 *const *x, const u64 *tx, const u64 *const *y,
                           const u64 *ty, u64 *const *out, u64 *less, hipStream_t stream);
 
+// a + b, a - b, a == b, a != b of two encrypted integers (csgn_uint_arith.hip), include/csgn_hip.h's definition: the
+// ADD_HALF / ADD_FULL and XNOR / EQ_STEP chains of csgn_uint_step; op = CSGN_UINT_ARITH_*.  a and b: w = 1..16 planes,
+// terms ta[j] / tb[j]; out: w planes (EQ / NE: one); carry: the carry out of the top plane, nullptr = not computed.
+constexpr u32 kArithMaxWidth = 16;
+u64 uint_arith_terms(int op, u64 w, const u64 *ta, const u64 *tb, u64 output);   // 0: invalid argument or 2^62 or more
+const char *uint_arith_kernel_name(u64 n_bits, int op, u64 batch, u64 w, const u64 *ta, const u64 *tb, bool carry);
+hipError_t uint_arith(u64 n_bits, int op, u64 batch, u64 w, const u64 *const *a, const u64 *ta, const u64 *const *b,
+                      const u64 *tb, u64 *const *out, u64 *carry, hipStream_t stream);
+
 // an encrypted integer shifted, rotated or indexed by an encrypted amount (csgn_uint_pick.hip), include/csgn_hip.h's
 // definition: output j is the sum, ascending in r < rows_j, of EQ(index, r) * a_{src(j, r)}; op = CSGN_UINT_PICK_*.
 // index planes: v = 1..16, terms s[k]; source planes: w = 1..64, every one of t terms; rows: EACH's n, else 0.
@@ -297,7 +306,7 @@ hipError_t uint_write(u64 n_bits, u64 batch, u64 v, const u64 *const *index, con
 // (hipErrorStreamCaptureUnsupported when the call would have to allocate while s is capturing).  owned: the block is
 // past the kept size and belongs to this call; scratch_done frees it behind the call's launches (waits for the device)
 // and passes e through.
-enum ScratchSlot { SCRATCH_UINT_PLAIN, SCRATCH_UINT_LUT, SCRATCH_UINT_READ, SCRATCH_UINT_ADDK, SCRATCH_UINT_FIND, SCRATCH_GATHER, SCRATCH_MATMUL, SCRATCH_COUNT, SCRATCH_UINT_LT_SELECT, SCRATCH_UINT_PICK, SCRATCH_UINT_WRITE, SCRATCH_SLOTS };
+enum ScratchSlot { SCRATCH_UINT_PLAIN, SCRATCH_UINT_LUT, SCRATCH_UINT_READ, SCRATCH_UINT_ADDK, SCRATCH_UINT_FIND, SCRATCH_GATHER, SCRATCH_MATMUL, SCRATCH_COUNT, SCRATCH_UINT_LT_SELECT, SCRATCH_UINT_PICK, SCRATCH_UINT_WRITE, SCRATCH_UINT_ARITH, SCRATCH_SLOTS };
 u64 *scratch_take(ScratchSlot slot, size_t bytes, hipStream_t s, bool &owned, hipError_t &e);
 hipError_t scratch_done(u64 *block, bool owned, hipError_t e);
 

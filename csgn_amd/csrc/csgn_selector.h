@@ -1,6 +1,6 @@
 // csgn_selector.h -- the skeleton of the selector-stream kernels (csgn_uint_read.hip, csgn_uint_find.hip,
-// csgn_uint_lt_select.hip, csgn_uint_pick.hip, csgn_uint_write.hip).  Internal linkage, like
-// csgn_device.h.
+// csgn_uint_lt_select.hip, csgn_uint_pick.hip, csgn_uint_write.hip; csgn_uint_arith.hip takes the
+// tile, the LDS layout, the launches and eq_digits, §4.28).  Internal linkage, like csgn_device.h.
 //
 // An encrypted SELECTOR STREAM (the EQ rows of an index, the EQ of a key row and a query, the terms of lessThan) is the
 // left operand of a product with one unit of a value plane, written for every output plane in one launch: term
@@ -123,6 +123,25 @@ __device__ __forceinline__ void sel_walk(const SelTile &t, const SelBlock<Unit> 
         Unit v;
         if (body(tile, qi, c, kk, at, v))
             unit_store<Unit, true>(o + at, v);
+    }
+}
+
+// ------------------------------------------------------------------------------ the EQ of two integers
+// Entry `in` of equalTo(left, right) over v planes (k_uint_find's key row against the query, k_uint_arith's a against
+// b): its mixed-radix digits with plane 0 slowest, digit < tl_k a term of left plane k, < tl_k + tr_k a term of right
+// plane k, else ONE.  term(side, k, i) takes term i of plane k of the left (side 0) or right (side 1) integer; ONE
+// takes nothing.  Fresh: every tl_k = tr_k = 1, the digits are base 3.
+template <bool Fresh, typename Term>
+__device__ __forceinline__ void eq_digits(u32 in, u32 v, const u32 *tl, const u32 *tr, Term term)
+{
+    for (u32 kb = v; kb-- > 0u;) {
+        const u32 uk = Fresh ? 1u : tl[kb], sk = Fresh ? 1u : tr[kb], R = uk + sk + 1u;
+        const u32 nx = in / R, dg = in - nx * R;
+        in = nx;
+        if (dg < uk)
+            term(0u, kb, dg);
+        else if (dg < uk + sk)
+            term(1u, kb, dg - uk);
     }
 }
 

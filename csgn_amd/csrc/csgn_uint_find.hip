@@ -58,14 +58,9 @@ __global__ void __launch_bounds__(256) k_uint_find(FindArgs a)
     if (Fresh) {
         // the range of q: Sq in the low 16 bits, Sk in the high 16 (published by the tables' closing barrier)
         for (u32 i = threadIdx.x; i < b.nq; i += 256u) {
-            u32 q = b.q0 + i, Sk = 0, Sq = 0;
-            for (u32 k = a.v; k-- > 0u;) {      // k = 0 is the slowest digit: 0 = y_k, 1 = x_k, 2 = ONE
-                const u32 nx = q / 3u, dg = q - nx * 3u;
-                q = nx;
-                Sk |= (dg == 0u ? 1u : 0u) << k;
-                Sq |= (dg == 1u ? 1u : 0u) << k;
-            }
-            b.code[i] = Sq | (Sk << 16);
+            u32 S[2] = {0u, 0u};                // k = 0 is the slowest digit: 0 = y_k, 1 = x_k, 2 = ONE
+            eq_digits<true>(b.q0 + i, a.v, a.u, a.s, [&](u32 side, u32 k, u32) { S[side] |= 1u << k; });
+            b.code[i] = S[1] | (S[0] << 16);
         }
         subset_build(b.tab, a.tq, a.query, t.G, t.KC, t.dKC, t.U, t.last_mask, b.e0, b.ne, b.k0, b.kc);
         subset_build(b.tab2, a.tr, a.keys, a.RP, t.KC, t.dKC, t.U, t.last_mask, (u64)r0, nr, b.k0, b.kc);
@@ -88,16 +83,10 @@ __global__ void __launch_bounds__(256) k_uint_find(FindArgs a)
                 v = subset_and(b.tab, a.tq, el, cd & 0xFFFFu, t.KC, kk) & subset_and(b.tab2, a.tr, rr, cd >> 16, t.KC, kk);
             } else {
                 v = one_unit(Unit(), k, t.U, t.last_mask);
-                u32 in = q;
-                for (u32 kb = a.v; kb-- > 0u;) {
-                    const u32 uk = a.u[kb], sk = a.s[kb], R = uk + sk + 1u;
-                    const u32 nx = in / R, dg = in - nx * R;
-                    in = nx;
-                    if (dg < uk)
-                        v &= reinterpret_cast<const Unit *>(a.keys[kb])[((u64)r * uk + dg) * t.U + k];
-                    else if (dg < uk + sk)
-                        v &= reinterpret_cast<const Unit *>(a.query[kb])[(e * sk + (dg - uk)) * t.U + k];
-                }
+                eq_digits<false>(q, a.v, a.u, a.s, [&](u32 side, u32 kb, u32 i) {
+                    v &= side == 0u ? reinterpret_cast<const Unit *>(a.keys[kb])[((u64)r * a.u[kb] + i) * t.U + k]
+                                    : reinterpret_cast<const Unit *>(a.query[kb])[(e * a.s[kb] + i) * t.U + k];
+                });
             }
             if (has_value)
                 v &= d[((u64)r * tj + c) * t.U + k];

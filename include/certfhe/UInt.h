@@ -13,6 +13,8 @@
 //     lessEqual          logicNot(lessThan(b, a))
 //     greaterEqual       logicNot(lessThan(a, b))
 //     select(s, a, b)    logicMux(s, a_j, b_j) on every plane                                          s ? a : b
+// a.add(b, &carry) and a.sub(b, &carry) also hand out the carry that leaves the top plane (the last ADD_FULL's output 1):
+// the bit a widening add or a multi-word sum needs; the carry of sub decrypts to 1 where a >= b.
 //
 // SIZES GROW WITH WIDTH -- the scheme's own nature: with fresh 1-term planes the top plane of a sum has 2^(w-1) + 1
 // terms, an equality 3^w and a less-than 3^w - 1 (at N=1247, 160 bytes a term: an 8-bit equality is about 1 MB per
@@ -177,9 +179,15 @@
 // before anything is allocated: std::invalid_argument for mismatched contexts, counts or widths, or an output past 2^31
 // words per element.  An empty batch gives empty planes.
 //
-// Uniform planes run one csgn_uint_step (or csgn_gate_uniform) call per bit; ragged ones (what compact() may return)
-// are composed from the CiphertextBatch operators and Gates.h, with the same words.  Only the running carry or
-// accumulator is kept alive between bits.
+// a + b, a - b, a.add / a.sub, equalTo(a, b) and notEqualTo(a, b) on uniform planes of width <= 16 are ONE call,
+// csgn_uint_arith (include/csgn_hip.h): one launch writes every plane and the carry, each term decoded from its position,
+// and no running carry or equality is ever written; lessThan(a, b) and greaterThan(a, b) take csgn_uint_lt_select with
+// no requests, the comparison alone.  Wider integers and ragged planes (what compact() may return) take the chain the
+// table above spells: one csgn_uint_step (or csgn_gate_uniform) call per bit on uniform planes, the CiphertextBatch
+// operators and Gates.h on ragged ones, only the running carry or accumulator alive between bits -- the same words
+// either way.  Knob uint_arith_form (csgn_set_tuning, or CSGN_UINT_ARITH_FORM when the library loads) forces the chain
+// (0) or the one call (1); left alone (-1), a forced uint_fused keeps the chain, so that both forms of csgn_uint_step can
+// be run through these operators.  arithRoute names the route.  lessEqual and greaterEqual keep the chain and logicNot.
 #ifndef CERTFHE_UINT_H
 #define CERTFHE_UINT_H
 
@@ -229,6 +237,11 @@ class UIntBatch {
 
     UIntBatch operator+(const UIntBatch &rhs) const;
     UIntBatch operator-(const UIntBatch &rhs) const;
+    // a + b and a - b with the carry that leaves the top plane, for every width and for ragged planes (carry_out may
+    // be null: the same as the operators).  The carry of add decrypts to 1 where a + b >= 2^width, that of sub
+    // (a + ~b + 1) to 1 where a >= b.
+    UIntBatch add(const UIntBatch &rhs, CiphertextBatch *carry_out) const;
+    UIntBatch sub(const UIntBatch &rhs, CiphertextBatch *carry_out) const;
     // a * b modulo 2^width: mul(*this, rhs, width())
     UIntBatch operator*(const UIntBatch &rhs) const;
 
@@ -262,6 +275,12 @@ class UIntBatch {
 UIntBatch operator-(uint64_t k, const UIntBatch &a);
 
 // one encrypted bit per element
+// The route a + b, a - b, equalTo, notEqualTo, lessThan and greaterThan take for operands of `width` planes, every one
+// of them uniform or not, under the calling thread's knobs (a static string): "call" (csgn_uint_arith /
+// csgn_uint_lt_select, in the form their own knobs choose) or "chain" (one step per bit).  No device work.  For
+// diagnostics and for the tests that must show which route a forced knob gave (tests/test_uint_arith_cpp.py): the
+// route is a speed matter, the words are the same, and a program should not branch on it.
+const char *arithRoute(unsigned width, bool uniform_planes);
 CiphertextBatch equalTo(const UIntBatch &a, const UIntBatch &b);
 CiphertextBatch notEqualTo(const UIntBatch &a, const UIntBatch &b);
 CiphertextBatch lessThan(const UIntBatch &a, const UIntBatch &b);

@@ -926,6 +926,54 @@ int csgn_uint_lt_select(uint64_t n_bits, uint64_t batch, uint64_t width, const u
                         const uint64_t *const *h_x, const uint64_t *h_x_terms, const uint64_t *const *h_y,
                         const uint64_t *h_y_terms, uint64_t *const *h_out, uint64_t *d_less, void *stream);
 
+/* ------------------------------------------- sums, differences and equality of two integers ---- */
+
+/* a + b, a - b, a == b and a != b of two ENCRYPTED integers, every plane of the result and the carry out of the top
+ * plane in one launch: what certfhe/UInt.h's operator+, operator-, equalTo and notEqualTo compute.
+ * Inputs: a and b, integers of `width` = w planes (w in 1..16, bit 0 first) of `batch` elements, plane j uniform with
+ * ta_j / tb_j terms per element.  The words are those of the csgn_uint_step chains, term for term; a product of a left
+ * term p and a right term q is term p * t_right + q:
+ *     ADD  s_0, c_0 = ADD_HALF(a_0, b_0);  s_j, c_j = ADD_FULL(c_{j-1}, a_j, b_j);  the carry-out is c_{w-1}
+ *     SUB  nb_j = b_j + ONE (csgn_gate_uniform's NOT), c_{-1} = ONE;  s_j, c_j = ADD_FULL(c_{j-1}, a_j, nb_j);
+ *          a + ~b + 1: the carry-out c_{w-1} decrypts to 1 where a >= b
+ *     EQ   e_0 = (a_0 + b_0) + ONE (the XNOR gate);  e_j = EQ_STEP(e_{j-1}, a_j, b_j);  the result is e_{w-1}
+ *     NE   EQ + ONE
+ * Terms: with tn_j = tb_j (SUB: tb_j + 1) and C_{-1} = 0 (SUB: 1), C_j = ta_j * tn_j + (ta_j + tn_j) * C_{j-1}; plane j
+ * has ta_j + tn_j + C_{j-1} terms and the carry-out C_{w-1}.  EQ has prod_j (ta_j + tb_j + 1) terms, NE one more.  Fresh
+ * 1-term planes: plane j of a sum has 2^j + 1 terms and its carry-out 2^w - 1; EQ has 3^w.
+ * Term order (decoding needs no table): plane j is [a_j's terms | nb_j's terms | the entries of c_{j-1}], the ONE of
+ * nb_j last (plane 0 of SUB ends in two ONEs: nothing cancels).  Entry q of c_j, for q < ta_j * tn_j, is term q / tn_j
+ * of a_j ANDed with term q % tn_j of nb_j, which ends the walk; else, with q' = q - ta_j * tn_j, it is term
+ * q' / C_{j-1} of the concatenation a_j | nb_j ANDed with entry q' % C_{j-1} of c_{j-1}.  Entry q of EQ is the
+ * mixed-radix number whose fastest digit belongs to plane w - 1 and whose slowest to plane 0: digit d of plane j names
+ * term d of a_j, term d - ta_j of b_j, or ONE (csgn_uint_find's decode of a key row against a query). */
+enum { CSGN_UINT_ARITH_ADD = 1, CSGN_UINT_ARITH_SUB, CSGN_UINT_ARITH_EQ, CSGN_UINT_ARITH_NE };
+/* Terms per element of one output (host only): output j < width is plane j of ADD / SUB and output `width` their
+ * carry-out; output 0 is the result of EQ / NE.  0 for an unknown op, a width outside 1..16, a null pointer, a plane of
+ * 0 terms, an output the op does not have, or a count of 2^62 or more. */
+uint64_t csgn_uint_arith_terms(int op, uint64_t width, const uint64_t *h_a_terms, const uint64_t *h_b_terms,
+                               uint64_t output);
+/* Which form a csgn_uint_arith call of this shape takes (host only, a static string): "k_uint_arith" (one kernel writes
+ * every plane and the carry, operands read in place, no running value materialised) or "composed" (the per-bit chain
+ * above through csgn_uint_step's and csgn_gate_uniform's launchers, the running value in a temporary the calling thread
+ * keeps (csgn_uint_addk's rules for its composed form)).  Knob "uint_arith_form" (-1 per shape, 0 the chain, 1 the one
+ * launch) decides; the words are the same.  Per shape: DESIGN 4.28.  "" for an invalid shape (n_bits 0, an unknown op,
+ * a bad width, a bad term count, or a carry asked of EQ / NE). */
+const char *csgn_uint_arith_kernel(uint64_t n_bits, int op, uint64_t batch, uint64_t width, const uint64_t *h_a_terms,
+                                   const uint64_t *h_b_terms, int with_carry);
+/* The operation over `batch` elements.  h_a, h_b: HOST arrays of `width` device pointers (plane j: batch * ta_j * dL and
+ * batch * tb_j * dL words), h_out: a HOST array of `width` device pointers for ADD / SUB (plane j: batch * T_j * dL
+ * words) and of one for EQ / NE, d_carry: batch * C_{w-1} * dL words, or NULL: the carry is then neither computed nor
+ * written; it must be NULL for EQ / NE.  Inputs may alias one another; no output overlaps an input or another output.
+ * Checks, in this order, the first that fails giving the status: n_bits; op; width; host pointers (and a carry asked of
+ * a comparison); the term counts (CSGN_ERR_INVALID); every output's T * dL below 2^31 words per element and batch
+ * times that below 2^60 (CSGN_ERR_UNSUPPORTED; computed without wrap-around); null device pointers (CSGN_ERR_INVALID);
+ * the device (CSGN_ERR_NO_DEVICE, no CPU fallback).  batch == 0 succeeds.  On the caller's stream, asynchronous; the
+ * fused form is one launch for every shape within memory and graph-capturable. */
+int csgn_uint_arith(uint64_t n_bits, int op, uint64_t batch, uint64_t width, const uint64_t *const *h_a,
+                    const uint64_t *h_a_terms, const uint64_t *const *h_b, const uint64_t *h_b_terms,
+                    uint64_t *const *h_out, uint64_t *d_carry, void *stream);
+
 /* ------------------------------------- shifts, rotates and per-element reads by encrypted amounts ---- */
 
 /* An encrypted integer shifted or rotated by an ENCRYPTED distance, or an array that belongs to the element read at the
