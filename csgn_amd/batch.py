@@ -611,6 +611,29 @@ class HipPath:
                                                    _ptr(mask), _ptr(bits), _ptr(scratch), self.stream))
         return bits[:batch]
 
+    def uint_decrypt(self, n_bits: int, batch: int, planes, terms, mask: torch.Tensor, offsets=None, max_terms=None,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """csgn_uint_decrypt: bit j of word e = Dec(element e of planes[j]), one 64-bit word per element (a fresh int64
+        tensor unless `out` is given).  terms[j]: plane j's terms per element, 0 for a ragged plane, which then needs
+        offsets[j] (its CSR offsets on the device, batch + 1 words) and max_terms[j] (a bound on one element's terms);
+        the entries of `offsets` and `max_terms` at uniform planes are not read (None will do)."""
+        w = len(planes)
+        assert w == len(terms)
+        ragged = [j for j in range(w) if int(terms[j]) == 0]
+        h_planes = (C.c_void_p * max(w, 1))(*[None if p is None else _ptr(p) for p in planes])
+        h_terms = (C.c_uint64 * max(w, 1))(*[int(t) for t in terms])
+        h_off = h_total = h_max = None
+        if ragged:
+            assert offsets is not None and max_terms is not None
+            h_off = (C.c_void_p * w)(*[_ptr(offsets[j]) if j in ragged else None for j in range(w)])
+            h_total = (C.c_uint64 * w)(*[int(self.download(offsets[j][-1:])[0]) if j in ragged else 0 for j in range(w)])
+            h_max = (C.c_uint64 * w)(*[int(max_terms[j]) if j in ragged else 0 for j in range(w)])
+        if out is None:
+            out = torch.empty(max(batch, 1), dtype=torch.int64, device=self.device)
+        check(self.lib.csgn_uint_decrypt(n_bits, batch, w, h_planes, h_terms, h_off, h_total, h_max, _ptr(mask),
+                                         _ptr(out), self.stream))
+        return out[:batch]
+
     def decrypt_combined_uniform(self, n_bits: int, batch: int, t1: int, t2: int, left: torch.Tensor,
                                  right: torch.Tensor, mask: torch.Tensor, product: bool) -> torch.Tensor:
         """Dec(L*R) (product=True) or Dec(L+R) without materialising the result."""

@@ -152,6 +152,69 @@ CiphertextBatch CiphertextBatch::encrypt(const SecretKey &key, const std::vector
     return out;
 }
 
+// The planes of an encrypted integer (UInt.h): ONE block of width * count ciphertexts, one upload, one csgn_encrypt_keyed
+// from stream position 0 -- ciphertext j * count + i is element i of plane j, the position the per-plane seeded form
+// gives it --, plane j a view at word j * count * dL.  With count * dL odd the views would sit on 8-byte boundaries and
+// put every later kernel on its 8-byte path: such a batch (and an empty one) is encrypted plane by plane.
+std::vector<CiphertextBatch> CiphertextBatch::encryptPlanes(const SecretKey &key, const std::vector<unsigned char> &bits,
+                                                            uint64_t count, unsigned width, const uint64_t *seed)
+{
+    if (!key.certFHEContext)
+        throw std::logic_error("certFHE::UIntBatch::encrypt: key has no Context");
+    const Context &c = *key.certFHEContext;
+    const uint64_t dl = c.getDefaultN();
+    std::vector<CiphertextBatch> planes;
+    if (count == 0 || (count * dl) % 2 != 0) {
+        for (unsigned j = 0; j < width; ++j) {
+            const std::vector<unsigned char> plane(bits.begin() + (size_t)j * count, bits.begin() + (size_t)(j + 1) * count);
+            planes.push_back(seed ? encrypt(key, plane, *seed, (uint64_t)j * count) : encrypt(key, plane));
+        }
+        return planes;
+    }
+    key.ensureMask();
+    std::shared_ptr<DevicePayload> block = detail::allocWords((uint64_t)width * count * dl);
+    csgn_rng rng;
+    if (seed)
+        detail::check(csgn_rng_from_seed(&rng, *seed, 8), "csgn_rng_from_seed");
+    else
+        detail::check(csgn_rng_from_os(&rng, 8), "csgn_rng_from_os");
+    encryptInto(c.getN(), (uint64_t)key.length, key.s, key.device_mask->data(), bits, rng, 0, block->data());
+    volatile uint32_t *wipe = rng.key;
+    for (int i = 0; i < 8; ++i)
+        wipe[i] = 0;
+    for (unsigned j = 0; j < width; ++j)
+        planes.push_back(detail::BatchAccess::makeView(c, count, 1, block, (uint64_t)j * count * dl));
+    return planes;
+}
+
+// One csgn_uint_decrypt over all planes, one copy of 8 bytes per element to the host, one synchronisation.
+std::vector<uint64_t> CiphertextBatch::decryptPlanes(const std::vector<CiphertextBatch> &planes, const SecretKey &key)
+{
+    const uint64_t count = planes[0].size(), w = planes.size();
+    std::vector<uint64_t> values(count, 0);
+    if (count == 0)
+        return values;
+    key.ensureMask();
+    std::vector<const uint64_t *> words(w), offsets(w, nullptr);
+    std::vector<uint64_t> terms(w), totals(w, 0), bounds(w, 0);
+    for (uint64_t j = 0; j < w; ++j) {
+        const CiphertextBatch &p = planes[j];
+        words[j] = p.deviceValues();
+        terms[j] = p.uniform() ? p.terms_ : 0;
+        if (terms[j] == 0) {                       // ragged, or a batch of no terms at all
+            offsets[j] = p.deviceOffsets();
+            totals[j] = p.totalTerms();
+            bounds[j] = p.maxTerms();
+        }
+    }
+    std::shared_ptr<DevicePayload> out = detail::allocWords(count);
+    detail::check(csgn_uint_decrypt(planes[0].ctx.getN(), count, w, words.data(), terms.data(), offsets.data(),
+                                    totals.data(), bounds.data(), key.device_mask->data(), out->data(), detail::stream()),
+                  "csgn_uint_decrypt");
+    detail::downloadBytes(values.data(), out->data(), count * 8);      // synchronises
+    return values;
+}
+
 CiphertextBatch CiphertextBatch::pack(const std::vector<Ciphertext> &items)
 {
     if (items.empty())

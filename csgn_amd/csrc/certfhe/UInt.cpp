@@ -476,22 +476,29 @@ CiphertextBatch zeros(const UIntBatch &a)
 
 UIntBatch::UIntBatch(const std::vector<CiphertextBatch> &planes) : planes_(planes) {}
 
+namespace {
+// the bit bytes of every plane, plane after plane, in one pass over the values
+std::vector<unsigned char> bitPlanes(const std::vector<uint64_t> &values, unsigned width)
+{
+    const size_t count = values.size();
+    std::vector<unsigned char> bits((size_t)width * count);
+    for (size_t i = 0; i < count; ++i)
+        for (unsigned j = 0; j < width; ++j)
+            bits[(size_t)j * count + i] = (unsigned char)((values[i] >> j) & 1u);
+    return bits;
+}
+} // namespace
+
 UIntBatch UIntBatch::encrypt(const SecretKey &key, const std::vector<uint64_t> &values, unsigned width)
 {
     requireFits(values, width, "encrypt");
-    std::vector<CiphertextBatch> planes;
-    for (unsigned j = 0; j < width; ++j)
-        planes.push_back(CiphertextBatch::encrypt(key, bitPlane(values, j)));
-    return UIntBatch(planes);
+    return UIntBatch(BatchAccess::encryptPlanes(key, bitPlanes(values, width), values.size(), width, nullptr));
 }
 
 UIntBatch UIntBatch::encrypt(const SecretKey &key, const std::vector<uint64_t> &values, unsigned width, uint64_t seed)
 {
     requireFits(values, width, "encrypt");
-    std::vector<CiphertextBatch> planes;
-    for (unsigned j = 0; j < width; ++j)
-        planes.push_back(CiphertextBatch::encrypt(key, bitPlane(values, j), seed, (uint64_t)j * values.size()));
-    return UIntBatch(planes);
+    return UIntBatch(BatchAccess::encryptPlanes(key, bitPlanes(values, width), values.size(), width, &seed));
 }
 
 UIntBatch UIntBatch::constant(const Context &context, const std::vector<uint64_t> &values, unsigned width)
@@ -599,16 +606,52 @@ UIntBatch UIntBatch::concat(const std::vector<UIntBatch> &parts)
     return UIntBatch(planes);
 }
 
-std::vector<uint64_t> UIntBatch::decrypt(const SecretKey &key) const
+namespace {
+// Whether a list of one-bit batches is decrypted by one csgn_uint_decrypt or batch by batch: knob uint_decrypt_form at 0
+// says batch by batch, and so does a ragged batch with an element past the call's bound for ragged planes (4096 terms,
+// include/csgn_hip.h).  Left per shape (-1) the one call is taken: DESIGN 4.29.
+const uint64_t kPackedRaggedBound = 4096;
+
+bool packedCall(const std::vector<CiphertextBatch> &bits)
 {
-    std::vector<uint64_t> values(size(), 0);
-    for (unsigned j = 0; j < width(); ++j) {
-        const std::vector<unsigned char> bits = planes_[j].decrypt(key);
+    int form = -1;
+    csgn_get_tuning("uint_decrypt_form", &form);
+    if (form == 0)
+        return false;
+    for (size_t j = 0; j < bits.size(); ++j)
+        if (!bits[j].uniform() && termsOf(bits[j]) > kPackedRaggedBound)
+            return false;
+    return true;
+}
+} // namespace
+
+std::vector<uint64_t> decryptPacked(const std::vector<CiphertextBatch> &bits, const SecretKey &key)
+{
+    if (bits.empty() || bits.size() > 64)
+        throw std::invalid_argument("certFHE::decryptPacked: 1..64 batches");
+    for (size_t j = 1; j < bits.size(); ++j)
+        if (bits[j].size() != bits[0].size() || !sameContext(bits[j].context(), bits[0].context()))
+            throw std::invalid_argument("certFHE::decryptPacked: batches differ in count or context");
+    if (packedCall(bits))
+        return BatchAccess::decryptPlanes(bits, key);
+    std::vector<uint64_t> values(bits[0].size(), 0);
+    for (size_t j = 0; j < bits.size(); ++j) {
+        const std::vector<unsigned char> plane = bits[j].decrypt(key);
         for (size_t i = 0; i < values.size(); ++i)
-            values[i] |= (uint64_t)(bits[i] & 1u) << j;
+            values[i] |= (uint64_t)(plane[i] & 1u) << j;
     }
     return values;
 }
+
+const char *decryptRoute(const UIntBatch &a)
+{
+    std::vector<CiphertextBatch> planes;
+    for (unsigned j = 0; j < a.width(); ++j)
+        planes.push_back(a.plane(j));
+    return packedCall(planes) ? "call" : "planes";
+}
+
+std::vector<uint64_t> UIntBatch::decrypt(const SecretKey &key) const { return decryptPacked(planes_, key); }
 
 UIntBatch UIntBatch::operator+(const UIntBatch &rhs) const
 {

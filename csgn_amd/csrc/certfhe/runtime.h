@@ -127,6 +127,31 @@ struct BatchAccess {
         b.offsets_ = offsets;
         return b;
     }
+    // a uniform batch that IS words [at, at + count * terms * dL) of `block`: a view (DevicePayload::parent) that keeps
+    // the whole block alive
+    static CiphertextBatch makeView(const Context &c, uint64_t count, uint64_t terms,
+                                    const std::shared_ptr<DevicePayload> &block, uint64_t at)
+    {
+        CiphertextBatch b(c, 0, terms);
+        b.count_ = count;
+        std::shared_ptr<DevicePayload> view = std::make_shared<DevicePayload>();
+        view->ptr = block->data() + at;
+        view->words = count * terms * c.getDefaultN();
+        view->capacity = (size_t)view->words * 8;
+        view->device = block->device;
+        view->parent = block;
+        b.payload = view;
+        return b;
+    }
+    static std::vector<CiphertextBatch> encryptPlanes(const SecretKey &key, const std::vector<unsigned char> &bits,
+                                                      uint64_t count, unsigned width, const uint64_t *seed)
+    {
+        return CiphertextBatch::encryptPlanes(key, bits, count, width, seed);
+    }
+    static std::vector<uint64_t> decryptPlanes(const std::vector<CiphertextBatch> &planes, const SecretKey &key)
+    {
+        return CiphertextBatch::decryptPlanes(planes, key);
+    }
 };
 
 // ONE for every element of `like`

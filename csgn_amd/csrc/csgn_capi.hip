@@ -1744,6 +1744,61 @@ int csgn_uint_arith(uint64_t n_bits, int op, uint64_t batch, uint64_t width, con
     return CSGN_OK;
 }
 
+/* ------------------------------------------------ one-bit batches decrypted into one word per element ---- */
+
+const char *csgn_uint_decrypt_kernel(uint64_t n_bits, uint64_t batch, uint64_t n_planes, const uint64_t *h_terms)
+{
+    return csgn::uint_decrypt_kernel_name(n_bits, batch, n_planes, (const u64 *)h_terms);
+}
+
+int csgn_uint_decrypt(uint64_t n_bits, uint64_t batch, uint64_t n_planes, const uint64_t *const *h_planes,
+                      const uint64_t *h_terms, const uint64_t *const *h_offsets, const uint64_t *h_total_terms,
+                      const uint64_t *h_max_terms, const uint64_t *d_mask, uint64_t *d_values, void *stream)
+{
+    if (int rc = check_n(n_bits))
+        return rc;
+    REQUIRE(n_planes >= 1 && n_planes <= csgn::kUintDecryptMaxPlanes, "uint_decrypt: %llu planes outside 1..64",
+            (unsigned long long)n_planes);
+    REQUIRE(batch >= 1, "uint_decrypt: an empty batch");
+    REQUIRE(h_planes && h_terms, "null host pointer");
+    for (uint64_t j = 0; j < n_planes; ++j) {
+        if (h_terms[j] != 0)
+            continue;
+        REQUIRE(h_offsets && h_total_terms && h_max_terms, "uint_decrypt: plane %llu is ragged: null host pointer",
+                (unsigned long long)j);
+        REQUIRE(!product_below(batch, h_max_terms[j], 1, h_total_terms[j]),
+                "uint_decrypt: plane %llu: max_terms = %llu cannot hold: %llu elements of at most that many terms are "
+                "fewer than total_terms = %llu", (unsigned long long)j, (unsigned long long)h_max_terms[j],
+                (unsigned long long)batch, (unsigned long long)h_total_terms[j]);
+    }
+    const uint64_t dl = csgn_default_len(n_bits);
+    for (uint64_t j = 0; j < n_planes; ++j) {
+        const bool ragged = h_terms[j] == 0;
+        if (int rc = check_size(ragged ? 1 : batch, ragged ? h_max_terms[j] : h_terms[j],
+                                ragged ? h_total_terms[j] : h_terms[j], dl, "uint_decrypt: plane %llu",
+                                (unsigned long long)j))
+            return rc;
+    }
+    for (uint64_t j = 0; j < n_planes; ++j)
+        if (h_terms[j] == 0 && h_max_terms[j] > csgn::kLongTerms)
+            return fail(CSGN_ERR_UNSUPPORTED, "uint_decrypt: ragged plane %llu has elements of up to %llu terms (more "
+                        "than %llu): decrypt it on its own", (unsigned long long)j, (unsigned long long)h_max_terms[j],
+                        (unsigned long long)csgn::kLongTerms);
+    if (int rc = require_device("csgn_uint_decrypt"))
+        return rc;
+    for (uint64_t j = 0; j < n_planes; ++j) {
+        const bool ragged = h_terms[j] == 0;
+        REQUIRE(h_planes[j] || (ragged && h_total_terms[j] == 0), "null device pointer (plane %llu)",
+                (unsigned long long)j);
+        REQUIRE(!ragged || h_offsets[j], "null device pointer (offsets of plane %llu)", (unsigned long long)j);
+    }
+    REQUIRE(d_mask && d_values, "null device pointer");
+    HIP_TRY(csgn::uint_decrypt(n_bits, batch, n_planes, (const u64 *const *)h_planes, (const u64 *)h_terms,
+                               (const u64 *const *)h_offsets, (const u64 *)h_max_terms, (const u64 *)d_mask,
+                               (u64 *)d_values, S(stream)));
+    return CSGN_OK;
+}
+
 /* ------------------------------------------------ encrypted bit matrices over F2 ---- */
 
 uint64_t csgn_matmul_terms(uint64_t inner, uint64_t t_a, uint64_t t_b) { return csgn::matmul_terms(inner, t_a, t_b); }

@@ -138,7 +138,7 @@ __global__ void __launch_bounds__(256) k_term_hits_seg(const Unit *__restrict__ 
 // range, which k_hits_parity_chunks folds -- one huge ciphertext among many small ones costs neither
 // a wave per small one nor one lonely workgroup for the big one (round 2: a single workgroup walked
 // the 128 KB bitmap of a 1 M-term ciphertext, 3.1 TB/s for the batch).
-constexpr u64 kLongTerms = 4096;
+// (kLongTerms: csgn_kernels.h -- csgn_uint_decrypt.hip draws its line for ragged planes there too)
 constexpr u64 kChunkTerms = 65536;
 
 // work area of the ragged pass 2 (after the hit bitmap): [n_long, n_entries, pad, pad][slot -> ciphertext:

@@ -86,6 +86,9 @@ hipError_t copy_list(const CopyEntry *d_entries, const u32 *d_first, u32 n_entri
 hipError_t add_ragged(u64 n_bits, u64 batch, const u64 *L, const u64 *offL, const u64 *R,
                       const u64 *offR, u64 *out, u64 *offOut, u64 total_terms_out, hipStream_t s,
                       bool device_end = false, u64 max_t1 = 0, u64 max_t2 = 0);
+// A ciphertext of more terms is "long": the ragged pass 2 of decrypt folds it chunk by chunk, and uint_decrypt refuses a
+// ragged plane whose bound is above it.
+constexpr u64 kLongTerms = 4096;
 // max_terms (ragged batches): an upper bound on the terms of one ciphertext, 0 = unknown
 hipError_t decrypt(u64 n_bits, u64 batch, u64 terms_uniform, u64 total_terms, const u64 *terms,
                    const u64 *off, const u64 *mask, uint8_t *bits, void *scratch, hipStream_t s, u64 max_terms = 0);
@@ -317,5 +320,15 @@ hipError_t combine_bits(const uint8_t *a, const uint8_t *b, u64 n, bool is_produ
 size_t decrypt_combined_scratch_bytes(u64 batch, u64 t1, u64 t2);
 hipError_t decrypt_combined(u64 n_bits, u64 batch, u64 t1, u64 t2, const u64 *L, const u64 *R,
                             const u64 *mask, bool is_product, uint8_t *bits, void *scratch, hipStream_t s);
+
+// n_planes = 1..64 one-bit batches decrypted into one word per element (csgn_uint_decrypt.hip), include/csgn_hip.h's
+// definition: bit j of values[e] = Dec(element e of plane j).  terms[j]: plane j's terms per element, 0 = ragged; a
+// ragged plane j has CSR offsets off[j] (device, batch + 1) and a bound max_terms[j] <= kLongTerms on one element's
+// terms (off and max_terms may be nullptr when no plane is ragged).  No scratch.
+constexpr u32 kUintDecryptMaxPlanes = 64;
+// "k_uint_decrypt", "k_zero_words+k_uint_decrypt" (some uniform plane is cut into chunks), "": invalid shape
+const char *uint_decrypt_kernel_name(u64 n_bits, u64 batch, u64 n_planes, const u64 *terms);
+hipError_t uint_decrypt(u64 n_bits, u64 batch, u64 n_planes, const u64 *const *planes, const u64 *terms,
+                        const u64 *const *off, const u64 *max_terms, const u64 *mask, u64 *values, hipStream_t stream);
 
 } // namespace csgn

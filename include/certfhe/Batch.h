@@ -42,6 +42,12 @@ class CiphertextBatch {
     CiphertextBatch(const Context &c, uint64_t count, uint64_t terms);
     const uint64_t *deviceOffsets() const;             // CSR offsets in HBM
     uint64_t maxTerms() const;
+    // What UInt.h's UIntBatch::encrypt and decryptPacked are made of (reached through detail::BatchAccess).
+    // encryptPlanes: bits holds `width` planes of `count` bytes, plane after plane; seed: the reproducible form, or
+    // null.  decryptPlanes: 1..64 batches of one context and count, one csgn_uint_decrypt.
+    static std::vector<CiphertextBatch> encryptPlanes(const SecretKey &key, const std::vector<unsigned char> &bits,
+                                                      uint64_t count, unsigned width, const uint64_t *seed);
+    static std::vector<uint64_t> decryptPlanes(const std::vector<CiphertextBatch> &planes, const SecretKey &key);
 
   public:
     // Encrypts bits[i] under `key` on the device: same distribution as SecretKey::encrypt

@@ -188,6 +188,18 @@
 // either way.  Knob uint_arith_form (csgn_set_tuning, or CSGN_UINT_ARITH_FORM when the library loads) forces the chain
 // (0) or the one call (1); left alone (-1), a forced uint_fused keeps the chain, so that both forms of csgn_uint_step can
 // be run through these operators.  arithRoute names the route.  lessEqual and greaterEqual keep the chain and logicNot.
+//
+// THE TWO ENDS.  UIntBatch::encrypt (both overloads) makes ONE block of width * count ciphertexts, lays the bit bytes
+// plane after plane in one host pass, uploads them once and runs one csgn_encrypt_keyed from stream position 0; plane j
+// is a VIEW at word j * count * dL of that block, so a plane -- also one handed on by plane(j) after the UIntBatch is
+// gone -- keeps the whole block alive.  The seeded planes are word for word CiphertextBatch::encrypt(key, bits_j, seed,
+// j * count).  With count * dL odd the views would sit on 8-byte boundaries and put every later kernel on its 8-byte
+// path, so such a batch is encrypted plane by plane, each plane a block of its own.  UIntBatch::decrypt is
+// decryptPacked(planes, key): one csgn_uint_decrypt (include/csgn_hip.h) reads every term of every plane once and
+// writes one word per element, then one copy of 8 bytes per element to the host and one synchronisation.  Knob
+// uint_decrypt_form (csgn_set_tuning, or CSGN_UINT_DECRYPT_FORM when the library loads) at 0 keeps one
+// CiphertextBatch::decrypt per plane, which is also what a ragged plane with an element of more than 4096 terms makes
+// the whole list take; decryptRoute names the route.  The values are the same.
 #ifndef CERTFHE_UINT_H
 #define CERTFHE_UINT_H
 
@@ -273,6 +285,15 @@ class UIntBatch {
 };
 
 UIntBatch operator-(uint64_t k, const UIntBatch &a);
+
+// Bit j of element e is Dec(bits[j][e]): 1 to 64 one-bit batches of one context and count (std::invalid_argument
+// otherwise) packed into one word per element.  The batches need not be an integer's planes: a carry, a membership
+// bit, the outputs of compareExchange pack the same way.  An empty batch gives an empty vector.
+std::vector<uint64_t> decryptPacked(const std::vector<CiphertextBatch> &bits, const SecretKey &key);
+// The route UIntBatch::decrypt takes for `a` under the calling thread's knobs (a static string): "call" (one
+// csgn_uint_decrypt) or "planes" (one CiphertextBatch::decrypt per plane).  No device work; for diagnostics and tests,
+// like arithRoute.
+const char *decryptRoute(const UIntBatch &a);
 
 // one encrypted bit per element
 // The route a + b, a - b, equalTo, notEqualTo, lessThan and greaterThan take for operands of `width` planes, every one

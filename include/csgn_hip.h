@@ -974,6 +974,42 @@ int csgn_uint_arith(uint64_t n_bits, int op, uint64_t batch, uint64_t width, con
                     const uint64_t *h_a_terms, const uint64_t *const *h_b, const uint64_t *h_b_terms,
                     uint64_t *const *h_out, uint64_t *d_carry, void *stream);
 
+/* ------------------------------------- one-bit batches decrypted into one word per element ---- */
+
+/* n_planes one-bit batches of `batch` elements decrypted in ONE pass into one 64-bit word per element: what
+ * certfhe/UInt.h's UIntBatch::decrypt and decryptPacked compute.
+ *     bit j of d_values[e] = Dec(element e of plane j) = XOR over the element's terms of (the term covers the key mask)
+ *     bits n_planes .. 63 are 0; an element of 0 terms gives 0
+ * Every word of d_values[0 .. batch) is written whatever it held before, and nothing beside them.  The planes need not
+ * be an integer's: any list of one-bit batches of one count packs this way (a carry, a membership bit, the outputs of
+ * a compare-exchange).  Plane j is uniform with h_terms[j] >= 1 terms per element (batch * h_terms[j] * dL words), or,
+ * with h_terms[j] == 0, ragged: h_offsets[j] are its CSR term offsets on the device (batch + 1 words, offsets[0] = 0),
+ * h_total_terms[j] = offsets[batch] and h_max_terms[j] a bound on the terms of ONE element (csgn_decrypt_ragged_bounded's
+ * rules: a bound that does not hold is the caller's error; one that is not tight costs nothing).  h_offsets, h_total_terms and h_max_terms are read only at ragged planes and may be NULL when there are
+ * none.  d_mask is the dL-word key mask (csgn_key_mask).  The call takes no scratch: no hit bitmap and no partial
+ * parity go through HBM.
+ * One kernel, k_uint_decrypt, reads every term of every plane exactly once: a workgroup owns a range of elements for ALL
+ * planes and writes their words with plain stores.  Only an element of a uniform plane with more terms than knob
+ * "uint_decrypt_chunk" (0: by shape, 1024; never above 4096) is cut into chunks, each of which XORs one bit into the
+ * word with a 64-bit atomic; in that form, and only in it, a zero fill of d_values (a kernel) runs first.  A ragged
+ * plane is never cut, which is why its bound may not pass 4096 terms (decrypt such a plane with
+ * csgn_decrypt_ragged_bounded).  Knob "launch_blocks" or the HIP grid limit may split the kernel into several launches.
+ * Checks, in this order, the first that fails giving the status, all of them before any device call: n_bits
+ * (CSGN_ERR_INVALID at 0, CSGN_ERR_UNSUPPORTED past 16 KiB a term); n_planes in 1..64 and batch >= 1; the host pointers
+ * h_planes and h_terms; for every ragged plane h_offsets, h_total_terms and h_max_terms present and
+ * batch * max_terms >= total_terms (CSGN_ERR_INVALID); every plane below 2^31 words per element and 2^60 per batch
+ * (CSGN_ERR_UNSUPPORTED; computed without wrap-around); a ragged bound above 4096 (CSGN_ERR_UNSUPPORTED); the device
+ * (CSGN_ERR_NO_DEVICE, no CPU fallback); null device pointers (CSGN_ERR_INVALID; the words of a ragged plane of no terms
+ * may be NULL).  On the caller's stream, asynchronous, graph-capturable. */
+int csgn_uint_decrypt(uint64_t n_bits, uint64_t batch, uint64_t n_planes, const uint64_t *const *h_planes,
+                      const uint64_t *h_terms, const uint64_t *const *h_offsets, const uint64_t *h_total_terms,
+                      const uint64_t *h_max_terms, const uint64_t *d_mask, uint64_t *d_values, void *stream);
+/* Which launches a csgn_uint_decrypt call of this shape makes under the calling thread's knobs (host only, a static
+ * string): "k_uint_decrypt" (every plane owned: plain stores, no atomics) or "k_zero_words+k_uint_decrypt" (some
+ * uniform plane has more terms than the chunk and is cut).  h_terms as above (0: ragged, never cut).  "" for an invalid
+ * shape (n_bits 0, batch 0, n_planes outside 1..64, a null pointer). */
+const char *csgn_uint_decrypt_kernel(uint64_t n_bits, uint64_t batch, uint64_t n_planes, const uint64_t *h_terms);
+
 /* ------------------------------------- shifts, rotates and per-element reads by encrypted amounts ---- */
 
 /* An encrypted integer shifted or rotated by an ENCRYPTED distance, or an array that belongs to the element read at the
