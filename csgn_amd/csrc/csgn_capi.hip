@@ -1501,6 +1501,16 @@ int csgn_uint_pick(uint64_t n_bits, int op, uint64_t batch, uint64_t index_width
     return CSGN_OK;
 }
 
+int csgn_uint_pick_rows_offsets(uint64_t index_width, const uint64_t *h_index_terms, uint64_t rows,
+                                const uint64_t *h_row_terms, uint64_t *h_src_off, uint64_t *h_out_off)
+{
+    REQUIRE(csgn::uint_pick_rows_offsets(index_width, (const u64 *)h_index_terms, rows, (const u64 *)h_row_terms,
+                                         (u64 *)h_src_off, (u64 *)h_out_off),
+            "pick rows: index width outside 1..16, rows outside 1..2^width, a null pointer, a term count of 0 or a count "
+            "of 2^62 or more");
+    return CSGN_OK;
+}
+
 /* ------------------------------------------- encrypted arrays written at encrypted indices ---- */
 
 uint64_t csgn_uint_write_offset(uint64_t index_width, const uint64_t *h_index_terms, uint64_t rows, uint64_t r,

@@ -288,6 +288,10 @@ const char *uint_pick_kernel_name(u64 n_bits, int op, u64 batch, u64 v, const u6
 bool uint_pick_plan(u64 n_bits, int op, u64 batch, u64 v, const u64 *s, u64 w, u64 rows, u64 t, bool wide, u64 plan[4]);
 hipError_t uint_pick(u64 n_bits, int op, u64 batch, u64 v, const u64 *const *index, const u64 *s, u64 w, u64 rows,
                      const u64 *const *src, u64 t, u64 *const *out, hipStream_t stream);
+// EACH over arrays whose row r has T[r] terms (include/csgn_hip.h, csgn_uint_pick_rows_offsets; host only): src_off /
+// out_off get the rows + 1 term offsets of the rows in an array and of their blocks in an output element.  false: an
+// invalid shape or a count of 2^62 or more
+bool uint_pick_rows_offsets(u64 v, const u64 *s, u64 rows, const u64 *T, u64 *src_off, u64 *out_off);
 
 // encrypted arrays written at encrypted indices (csgn_uint_write.hip), include/csgn_hip.h's definition: row r of element
 // e's array in plane j becomes (EQ(index_e, r) * (value_{e,j} + d_{e*n+r,j})) + d_{e*n+r,j}.  index planes: v = 1..16,

@@ -311,6 +311,29 @@ u64 uint_pick_terms(int op, u64 v, const u64 *s, u64 w, u64 rows, u64 j)
     return rj ? uint_read_terms(v, s, rj) : 0;
 }
 
+bool uint_pick_rows_offsets(u64 v, const u64 *s, u64 rows, const u64 *T, u64 *src_off, u64 *out_off)
+{
+    if (!T || !src_off || !out_off || uint_read_terms(v, s, rows) == 0)
+        return false;
+    u64 so = 0, oo = 0;
+    for (u64 r = 0; r < rows; ++r) {
+        src_off[r] = so;
+        out_off[r] = oo;
+        u64 P = 1, block;               // P_r = prod_k (r_k ? s_k : s_k + 1): the terms of EQ(index, r); at most E
+        for (u64 k = 0; k < v; ++k)
+            P = sat_mul(P, ((r >> k) & 1u) ? s[k] : s[k] + 1);
+        if (T[r] == 0 || T[r] >= kTermLimit || !term_mul(P, T[r], block))
+            return false;
+        so += T[r];
+        oo += block;
+        if (so >= kTermLimit || oo >= kTermLimit)
+            return false;
+    }
+    src_off[rows] = so;
+    out_off[rows] = oo;
+    return true;
+}
+
 const char *uint_pick_kernel_name(u64 n_bits, int op, u64 batch, u64 v, const u64 *s, u64 w, u64 rows, u64 t)
 {
     if (n_bits == 0 || !pick_shape_ok(op, v, s, w, rows, t))

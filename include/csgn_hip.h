@@ -1074,6 +1074,24 @@ int csgn_uint_pick(uint64_t n_bits, int op, uint64_t batch, uint64_t index_width
                    const uint64_t *h_index_terms, uint64_t width, uint64_t rows, const uint64_t *const *h_a,
                    uint64_t terms, uint64_t *const *h_out, void *stream);
 
+/* EACH over arrays whose ROWS differ in size -- the layout csgn_uint_write (below) leaves, and the sizes of the read that
+ * follows it.  Index: index_width = v planes (1..16), plane k uniform with s_k terms.  An array has `rows` = n rows
+ * (1 <= n <= 2^v), row r of T[r] >= 1 terms -- the same in every array of the plane --, so an array has A = sum_r T[r]
+ * terms and row r begins at term sum_{r' < r} T[r'] of it (a written plane: T[r] = P_r * (tv + td) + td).
+ * The read of such a plane by csgn_uint_pick EACH's definition -- element e: the left-nested sum, ascending in r < n, of
+ * EQ(x_e, r) * (row r of array e), EQ the LEFT operand -- is UNIFORM: Tout = sum_r P_r * T[r] terms per element,
+ * P_r = prod_k (r_k ? s_k : s_k + 1); row r's block begins at term sum_{r' < r} P_{r'} * T[r'], and term in * T[r] + c
+ * of the block is (entry in of EQ(x, r), in csgn_uint_read's order) & (term c of the row).  With every T[r] = t these
+ * are csgn_uint_pick EACH's words and Tout = t * csgn_uint_pick_terms.  Fresh v = 3, n = 8 over a table written once
+ * from one-term planes: T = 17, 9, 9, 5, 9, 5, 5, 3 (A = 62), Tout = 277; in general 2 * 5^v + 3^v.
+ * This entry point gives the offsets (host only): h_src_off[r] and h_out_off[r] for r in 0..rows -- rows + 1 entries
+ * each -- are row r's first term inside an array and its block's first term inside an output element; entry `rows`
+ * holds A and Tout.  CSGN_ERR_INVALID for index_width outside 1..16, rows outside 1..2^index_width, a null pointer, a
+ * term count of 0, or a count of 2^62 or more (nothing wraps).  The library has no launch for this read yet: the classes
+ * compose it (certfhe/UInt.h, readAtEach over ragged planes). */
+int csgn_uint_pick_rows_offsets(uint64_t index_width, const uint64_t *h_index_terms, uint64_t rows,
+                                const uint64_t *h_row_terms, uint64_t *h_src_off, uint64_t *h_out_off);
+
 /* ------------------------------------------- encrypted arrays written at encrypted indices ---- */
 
 /* ENCRYPTED arrays written at ENCRYPTED indices: a private counter table, an oblivious register file, one step of an
