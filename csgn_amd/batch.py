@@ -414,6 +414,32 @@ class HipPath:
         check(self.lib.csgn_uint_pick(n_bits, op, batch, v, h_x, h_s, w, rows, h_a, int(terms), h_out, self.stream))
         return [o[: batch * int(terms) * e * dl] for o, e in zip(outs, E)]
 
+    def uint_pick_rows(self, n_bits: int, batch: int, index, index_terms, rows: int, arrays, row_terms, outs=None):
+        """csgn_uint_pick_rows: element e's own array of `rows` rows read at its encrypted index `index` (bit 0 first;
+        plane k a uniform batch of index_terms[k] terms) where the rows differ in size -- row r of plane j has
+        row_terms[j][r] terms in every array, the layout csgn_uint_write leaves.  One uniform tensor per plane, Tout_j
+        terms per element (csgn_uint_pick_rows_offsets); fresh ones unless `outs` is given.  The sizes are checked
+        (csgn_uint_pick_rows_check) before anything is allocated."""
+        v, w = len(index), len(arrays)
+        assert v == len(index_terms) and w == len(row_terms) and all(len(t) == rows for t in row_terms)
+        h_s = (C.c_uint64 * max(v, 1))(*[int(t) for t in index_terms])
+        h_T = (C.c_uint64 * max(w * rows, 1))(*[int(t) for plane in row_terms for t in plane])
+        check(self.lib.csgn_uint_pick_rows_check(n_bits, batch, v, h_s, rows, w, h_T))
+        src, out = (C.c_uint64 * (rows + 1))(), (C.c_uint64 * (rows + 1))()
+        Tout = []
+        for j in range(w):
+            h_Tj = (C.c_uint64 * rows)(*[int(t) for t in row_terms[j]])
+            check(self.lib.csgn_uint_pick_rows_offsets(v, h_s, rows, h_Tj, src, out))
+            Tout.append(int(out[rows]))
+        dl = self.default_len(n_bits)
+        if outs is None:
+            outs = [self.empty_words(max(batch * t * dl, 1)) for t in Tout]
+        h_x = (C.c_void_p * max(v, 1))(*[_ptr(p) for p in index])
+        h_a = (C.c_void_p * max(w, 1))(*[_ptr(p) for p in arrays])
+        h_out = (C.c_void_p * max(w, 1))(*[_ptr(o) for o in outs])
+        check(self.lib.csgn_uint_pick_rows(n_bits, batch, v, h_x, h_s, rows, w, h_a, h_T, h_out, self.stream))
+        return [o[: batch * t * dl] for o, t in zip(outs, Tout)]
+
     def uint_write(self, n_bits: int, batch: int, index, index_terms, rows: int, value, value_terms, arrays,
                    array_terms, outs=None):
         """csgn_uint_write: element e's own array of `rows` rows (the elements e * rows .. e * rows + rows - 1 of the

@@ -1321,6 +1321,49 @@ uint64_t pickTermsByRows(int op, const std::vector<uint64_t> &s, const std::vect
     return T;
 }
 
+// Whether the terms of a plane's elements have period n over m arrays -- termsOf(e * n + r) == termsOf(r) for every e,
+// read from the host offsets --, and the n counts into rows.  A uniform plane has it, with a constant.
+bool periodRows(const CiphertextBatch &p, uint64_t n, uint64_t m, uint64_t *rows)
+{
+    if (p.uniform()) {
+        std::fill(rows, rows + n, p.terms());
+        return true;
+    }
+    for (uint64_t r = 0; r < n; ++r)
+        rows[r] = p.termsOf(r);
+    for (uint64_t e = 1; e < m; ++e)
+        for (uint64_t r = 0; r < n; ++r)
+            if (p.termsOf(e * n + r) != rows[r])
+                return false;
+    return true;
+}
+
+// The route of readAtEach (readAtEachRoute): "pick" -- uniform planes of one count under a uniform index of at most 16
+// bits: csgn_uint_pick --, "rows" -- a uniform index of at most 16 bits over planes of period n, what writeAtEach
+// returns: csgn_uint_pick_rows, the rows' counts plane-major into *rows --, else "loop", the class-level loop of
+// pickPlanes.  No device work.
+const char *eachRoute(const std::vector<CiphertextBatch> &a, uint64_t n, const UIntBatch &d, std::vector<uint64_t> *rows)
+{
+    const uint64_t v = d.width(), m = d.size();
+    if (a.empty() || v > 16 || n == 0 || n > (1ull << v) || (m != 0 && n > ~0ull / m))
+        return "loop";
+    for (unsigned k = 0; k < v; ++k)
+        if (!d.plane(k).uniform())
+            return "loop";
+    bool one_count = true;
+    for (size_t j = 0; j < a.size(); ++j)
+        one_count = one_count && a[j].uniform() && a[j].terms() == a[0].terms();
+    if (one_count)
+        return "pick";
+    std::vector<uint64_t> T(a.size() * n);
+    for (size_t j = 0; j < a.size(); ++j)
+        if (a[j].size() != n * m || !periodRows(a[j], n, m, &T[j * n]))
+            return "loop";
+    if (rows)
+        rows->swap(T);
+    return "rows";
+}
+
 // every output plane of one operation: out_j = sum over r < rows_j of equalTo(d, r) * source(j, r)
 std::vector<CiphertextBatch> pickPlanes(int op, const std::vector<CiphertextBatch> &a, uint64_t n, const UIntBatch &d,
                                         const char *who)
@@ -1344,6 +1387,9 @@ std::vector<CiphertextBatch> pickPlanes(int op, const std::vector<CiphertextBatc
     for (unsigned j = 1; j < w; ++j)
         one_count = one_count && t[j] == t[0];
     const bool fused = x.uniform && src.uniform && one_count && v <= 16;
+    // planes of period n, what writeAtEach returns: one csgn_uint_pick_rows, uniform outputs
+    std::vector<uint64_t> row_terms;
+    const bool rows = each && !fused && m != 0 && w != 0 && std::string(eachRoute(a, n, d, &row_terms)) == "rows";
     std::vector<uint64_t> T(w);
     for (unsigned j = 0; j < w; ++j) {
         uint64_t terms = 0;
@@ -1352,6 +1398,10 @@ std::vector<CiphertextBatch> pickPlanes(int op, const std::vector<CiphertextBatc
         } else if (fused) {
             const uint64_t E = csgn_uint_pick_terms(op, v, x.terms.data(), w, each ? n : 0, j);
             terms = (E == 0 || t[0] == 0 || t[0] > kMaxWords / E) ? 0 : t[0] * E;
+        } else if (rows) {
+            std::vector<uint64_t> so(n + 1), oo(n + 1);
+            if (csgn_uint_pick_rows_offsets(v, x.terms.data(), n, &row_terms[j * n], so.data(), oo.data()) == CSGN_OK)
+                terms = oo[n] > kMaxWords ? 0 : oo[n];
         } else {
             terms = pickTermsByRows(op, x.terms, t, pickRows(op, v, w, n, j), j);
         }
@@ -1368,7 +1418,18 @@ std::vector<CiphertextBatch> pickPlanes(int op, const std::vector<CiphertextBatc
                           "csgn_uint_pick");
         return out;
     }
-    // ragged planes, planes of different term counts, a wider distance: the definition itself through the operators
+    if (rows) {
+        // every size before anything is allocated: the check is the launching call's own, on the host
+        detail::check(csgn_uint_pick_rows_check(ctx.getN(), m, v, x.terms.data(), n, w, row_terms.data()),
+                      "csgn_uint_pick_rows_check");
+        std::vector<CiphertextBatch> out = makePlanes(ctx, m, T);
+        detail::check(csgn_uint_pick_rows(ctx.getN(), m, v, sources(x).data(), x.terms.data(), n, w, sources(src).data(),
+                                          row_terms.data(), wordsOf(out).data(), detail::stream()),
+                      "csgn_uint_pick_rows");
+        return out;
+    }
+    // ragged planes without a period, planes of different term counts under a wider distance: the definition itself
+    // through the operators
     uint64_t rows_max = 0;
     for (unsigned j = 0; j < w; ++j)
         rows_max = std::max(rows_max, pickRows(op, v, w, n, j));
@@ -1419,6 +1480,11 @@ UIntBatch UIntBatch::rotateRight(const UIntBatch &d) const
 UIntBatch readAtEach(const UIntBatch &arrays, uint64_t n, const UIntBatch &index)
 {
     return UIntBatch::fromPlanes(pickPlanes(CSGN_UINT_PICK_EACH, planesOf(arrays), n, index, "readAtEach"));
+}
+
+const char *readAtEachRoute(const UIntBatch &arrays, uint64_t n, const UIntBatch &index)
+{
+    return eachRoute(planesOf(arrays), n, index, nullptr);
 }
 
 CiphertextBatch readAtEach(const CiphertextBatch &arrays, uint64_t n, const UIntBatch &index)

@@ -1511,6 +1511,78 @@ int csgn_uint_pick_rows_offsets(uint64_t index_width, const uint64_t *h_index_te
     return CSGN_OK;
 }
 
+// Everything csgn_uint_pick_rows decides before it touches a device, and csgn_uint_pick_rows_check's whole body.
+static int pick_rows_check(uint64_t n_bits, uint64_t batch, uint64_t index_width, const uint64_t *h_index_terms,
+                           uint64_t rows, uint64_t width, const uint64_t *h_row_terms)
+{
+    if (int rc = check_n(n_bits))
+        return rc;
+    if (int rc = check_index("pick rows", index_width, "width", width, rows))
+        return rc;
+    REQUIRE(h_index_terms && h_row_terms, "null host pointer");
+    uint64_t A[csgn::kPickMaxPlanes], Tout[csgn::kPickMaxPlanes];
+    REQUIRE(csgn::uint_pick_rows_sizes(index_width, (const u64 *)h_index_terms, rows, width, (const u64 *)h_row_terms,
+                                       (u64 *)A, (u64 *)Tout),
+            "pick rows: a term count of 0 or a count of 2^62 or more");
+    const uint64_t dl = csgn_default_len(n_bits);
+    for (uint64_t j = 0; j < width; ++j) {
+        if (int rc = check_size(batch, Tout[j], Tout[j], dl, "pick rows: output %llu", (unsigned long long)j))
+            return rc;
+        if (!product_below(batch, A[j], dl, 1ull << 60))
+            return fail(CSGN_ERR_UNSUPPORTED, "pick rows: %llu arrays of %llu terms: size overflows",
+                        (unsigned long long)batch, (unsigned long long)A[j]);
+    }
+    return CSGN_OK;
+}
+
+int csgn_uint_pick_rows_check(uint64_t n_bits, uint64_t batch, uint64_t index_width, const uint64_t *h_index_terms,
+                              uint64_t rows, uint64_t width, const uint64_t *h_row_terms)
+{
+    return pick_rows_check(n_bits, batch, index_width, h_index_terms, rows, width, h_row_terms);
+}
+
+const char *csgn_uint_pick_rows_kernel(uint64_t n_bits, uint64_t batch, uint64_t index_width,
+                                       const uint64_t *h_index_terms, uint64_t rows, uint64_t width,
+                                       const uint64_t *h_row_terms)
+{
+    if (pick_rows_check(n_bits, batch, index_width, h_index_terms, rows, width, h_row_terms) != CSGN_OK)
+        return "";
+    return csgn::uint_pick_rows_kernel_name();
+}
+
+int csgn_uint_pick_rows_decode(uint64_t index_width, const uint64_t *h_index_terms, uint64_t rows,
+                               const uint64_t *h_row_terms, uint64_t position, uint64_t *h_out)
+{
+    const int rc = csgn::uint_pick_rows_decode(index_width, (const u64 *)h_index_terms, rows, (const u64 *)h_row_terms,
+                                               position, (u64 *)h_out);
+    if (rc == CSGN_ERR_UNSUPPORTED)
+        return fail(rc, "pick rows decode: an array or an output element of 2^32 terms or more");
+    REQUIRE(rc == CSGN_OK, "pick rows decode: an invalid shape, a null pointer, or position %llu past the output",
+            (unsigned long long)position);
+    return CSGN_OK;
+}
+
+int csgn_uint_pick_rows(uint64_t n_bits, uint64_t batch, uint64_t index_width, const uint64_t *const *h_index,
+                        const uint64_t *h_index_terms, uint64_t rows, uint64_t width, const uint64_t *const *h_arrays,
+                        const uint64_t *h_row_terms, uint64_t *const *h_out, void *stream)
+{
+    if (int rc = pick_rows_check(n_bits, batch, index_width, h_index_terms, rows, width, h_row_terms))
+        return rc;
+    REQUIRE(h_index && h_arrays && h_out, "null host pointer");
+    if (int rc = require_device("csgn_uint_pick_rows"))
+        return rc;
+    if (batch == 0)
+        return CSGN_OK;
+    if (int rc = check_planes(h_index, nullptr, index_width, "index plane"))
+        return rc;
+    if (int rc = check_planes(h_arrays, h_out, width, "array plane or output"))
+        return rc;
+    HIP_TRY(csgn::uint_pick_rows(n_bits, batch, index_width, (const u64 *const *)h_index, (const u64 *)h_index_terms,
+                                 rows, width, (const u64 *const *)h_arrays, (const u64 *)h_row_terms,
+                                 (u64 *const *)h_out, S(stream)));
+    return CSGN_OK;
+}
+
 /* ------------------------------------------- encrypted arrays written at encrypted indices ---- */
 
 uint64_t csgn_uint_write_offset(uint64_t index_width, const uint64_t *h_index_terms, uint64_t rows, uint64_t r,

@@ -292,6 +292,14 @@ hipError_t uint_pick(u64 n_bits, int op, u64 batch, u64 v, const u64 *const *ind
 // out_off get the rows + 1 term offsets of the rows in an array and of their blocks in an output element.  false: an
 // invalid shape or a count of 2^62 or more
 bool uint_pick_rows_offsets(u64 v, const u64 *s, u64 rows, const u64 *T, u64 *src_off, u64 *out_off);
+// that read in one launch (csgn_uint_pick_rows.hip), include/csgn_hip.h's definition.  T: w * rows counts, plane-major.
+// A[j] / Tout[j] of every plane (host only); false: an invalid shape or a count of 2^62 or more
+bool uint_pick_rows_sizes(u64 v, const u64 *s, u64 rows, u64 w, const u64 *T, u64 *A, u64 *Tout);
+const char *uint_pick_rows_kernel_name();       // of a valid shape under the calling thread's knob
+// (r, in, c) of output position `position` by the kernel's own search and division (host only); a csgn_status
+int uint_pick_rows_decode(u64 v, const u64 *s, u64 rows, const u64 *T, u64 position, u64 out[3]);
+hipError_t uint_pick_rows(u64 n_bits, u64 batch, u64 v, const u64 *const *index, const u64 *s, u64 rows, u64 w,
+                          const u64 *const *arrays, const u64 *T, u64 *const *out, hipStream_t stream);
 
 // encrypted arrays written at encrypted indices (csgn_uint_write.hip), include/csgn_hip.h's definition: row r of element
 // e's array in plane j becomes (EQ(index_e, r) * (value_{e,j} + d_{e*n+r,j})) + d_{e*n+r,j}.  index planes: v = 1..16,
@@ -313,7 +321,7 @@ hipError_t uint_write(u64 n_bits, u64 batch, u64 v, const u64 *const *index, con
 // (hipErrorStreamCaptureUnsupported when the call would have to allocate while s is capturing).  owned: the block is
 // past the kept size and belongs to this call; scratch_done frees it behind the call's launches (waits for the device)
 // and passes e through.
-enum ScratchSlot { SCRATCH_UINT_PLAIN, SCRATCH_UINT_LUT, SCRATCH_UINT_READ, SCRATCH_UINT_ADDK, SCRATCH_UINT_FIND, SCRATCH_GATHER, SCRATCH_MATMUL, SCRATCH_COUNT, SCRATCH_UINT_LT_SELECT, SCRATCH_UINT_PICK, SCRATCH_UINT_WRITE, SCRATCH_UINT_ARITH, SCRATCH_SLOTS };
+enum ScratchSlot { SCRATCH_UINT_PLAIN, SCRATCH_UINT_LUT, SCRATCH_UINT_READ, SCRATCH_UINT_ADDK, SCRATCH_UINT_FIND, SCRATCH_GATHER, SCRATCH_MATMUL, SCRATCH_COUNT, SCRATCH_UINT_LT_SELECT, SCRATCH_UINT_PICK, SCRATCH_UINT_WRITE, SCRATCH_UINT_ARITH, SCRATCH_UINT_PICK_ROWS, SCRATCH_SLOTS };
 u64 *scratch_take(ScratchSlot slot, size_t bytes, hipStream_t s, bool &owned, hipError_t &e);
 hipError_t scratch_done(u64 *block, bool owned, hipError_t e);
 

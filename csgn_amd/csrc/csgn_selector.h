@@ -1,6 +1,7 @@
 // csgn_selector.h -- the skeleton of the selector-stream kernels (csgn_uint_read.hip, csgn_uint_find.hip,
-// csgn_uint_lt_select.hip, csgn_uint_pick.hip, csgn_uint_write.hip; csgn_uint_arith.hip takes the
-// tile, the LDS layout, the launches and eq_digits, §4.28).  Internal linkage, like csgn_device.h.
+// csgn_uint_lt_select.hip, csgn_uint_pick.hip, csgn_uint_pick_rows.hip, csgn_uint_write.hip; DESIGN.md §4.23;
+// csgn_uint_arith.hip takes the tile, the LDS layout, the launches and eq_digits, §4.28).  Internal linkage, like
+// csgn_device.h.
 //
 // An encrypted SELECTOR STREAM (the EQ rows of an index, the EQ of a key row and a query, the terms of lessThan) is the
 // left operand of a product with one unit of a value plane, written for every output plane in one launch: term
@@ -8,8 +9,9 @@
 // slice of KC units of every term and QP entries of the stream, for EVERY output; with fresh planes it builds its
 // subset tables (csgn_device.h) and decodes its entries into an LDS list once, for all of them.  An operation supplies
 // the decode of an entry, the address of the value unit and how it sizes G and QP.  The operations over the E stream
-// of an index, k_uint_read, k_uint_pick and k_uint_write, share those as well: the index in the
-// arguments, the evaluation of an entry in both forms and the tile policy are in the E-stream section below, once.
+// of an index, k_uint_read, k_uint_pick, k_uint_pick_rows and k_uint_write, share those as well:
+// the index in the arguments, the evaluation of an entry in both forms and the tile policy are in the E-stream section
+// below, once.
 #pragma once
 
 #include "csgn_device.h"

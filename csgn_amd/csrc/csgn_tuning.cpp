@@ -46,6 +46,7 @@ const Knob kKnobs[TUNE_COUNT] = {
     {"uint_pick_fused", -1},
     {"uint_pick_stage", -1},
     {"uint_write_fused", -1},
+    {"uint_pick_rows_form", -1},
     {"uint_decrypt_form", -1},
     {"uint_decrypt_chunk", 0},
     {"uint_arith_form", -1},

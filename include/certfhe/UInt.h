@@ -79,6 +79,12 @@
 // the result's planes are RAGGED CiphertextBatches in a pattern of period n; their offsets are computed on the host
 // (csgn_uint_write_offset), with no device round trip, and termsOf(e * n + r) gives each row's size.  Everything that
 // takes ragged planes reads them back: readAtEach(writeAtEach(a, n, i, x), n, i) decrypts to x where i < n.
+// THE READ THAT FOLLOWS: readAtEach over planes whose terms have period n -- termsOf(e * n + r) == termsOf(r) for every
+// e, which is what writeAtEach returns; a uniform plane has it with a constant -- under a uniform index of at most 16
+// bits is one csgn_uint_pick_rows (include/csgn_hip.h): one launch for every plane, straight from the written planes,
+// and the result's planes are UNIFORM CiphertextBatches (sum over r of P_r * termsOf(r) terms an element), with the
+// words, in the order, that the class-level loop over the same operands gives.  Its sizes are checked on the host
+// (csgn_uint_pick_rows_check) before anything is allocated.  readAtEachRoute names the route.
 // writeAt(table, index, value) is the same for ONE index and value and n = table.size().  Uniform operands under an
 // index of at most 16 bits take one csgn_uint_write (one launch for every plane, the rows' raw copies included);
 // ragged operands (a compact() result) and wider indices are composed from equalTo(index, r), gather, logicMux, concat
@@ -359,6 +365,12 @@ CiphertextBatch readAt(const CiphertextBatch &table, const UIntBatch &index);
 // element e: arrays[e * n + index[e]] where index[e] < n, else 0; arrays.size() == n * index.size(), 1 <= n <= 2^v
 UIntBatch readAtEach(const UIntBatch &arrays, uint64_t n, const UIntBatch &index);
 CiphertextBatch readAtEach(const CiphertextBatch &arrays, uint64_t n, const UIntBatch &index);
+// The route readAtEach takes for these operands (a static string): "pick" (uniform planes of one term count under a
+// uniform index of at most 16 bits: one csgn_uint_pick), "rows" (planes whose terms have period n under such an index --
+// writeAtEach's results: one csgn_uint_pick_rows) or "loop" (anything else, a compact()ed index for one: equalTo, gather,
+// operator* and operator+ row by row).  No device work; for diagnostics and tests, like arithRoute and decryptRoute: the
+// words are the same on every route.
+const char *readAtEachRoute(const UIntBatch &arrays, uint64_t n, const UIntBatch &index);
 
 // the arrays with element e * n + index[e] replaced by value[e] where index[e] < n; arrays.size() == n * index.size(),
 // 1 <= n <= 2^v, value of the arrays' width and the index's count.  The result's planes are ragged (see above)

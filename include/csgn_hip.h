@@ -1087,10 +1087,50 @@ int csgn_uint_pick(uint64_t n_bits, int op, uint64_t batch, uint64_t index_width
  * This entry point gives the offsets (host only): h_src_off[r] and h_out_off[r] for r in 0..rows -- rows + 1 entries
  * each -- are row r's first term inside an array and its block's first term inside an output element; entry `rows`
  * holds A and Tout.  CSGN_ERR_INVALID for index_width outside 1..16, rows outside 1..2^index_width, a null pointer, a
- * term count of 0, or a count of 2^62 or more (nothing wraps).  The library has no launch for this read yet: the classes
- * compose it (certfhe/UInt.h, readAtEach over ragged planes). */
+ * term count of 0, or a count of 2^62 or more (nothing wraps). */
 int csgn_uint_pick_rows_offsets(uint64_t index_width, const uint64_t *h_index_terms, uint64_t rows,
                                 const uint64_t *h_row_terms, uint64_t *h_src_off, uint64_t *h_out_off);
+/* The read itself is csgn_uint_pick_rows (below).  Its planes may have different rows: h_row_terms holds width * rows
+ * counts, plane-major (plane j's T_j[r] at j * rows + r), so plane j has A_j terms per array and Tout_j per output.
+ *
+ * csgn_uint_pick_rows_check: HOST ONLY, it never touches a device.  Exactly the status csgn_uint_pick_rows returns before
+ * it launches anything (that call's first statement is this function's body): CSGN_ERR_INVALID for n_bits 0, index_width
+ * outside 1..16, rows outside 1..2^index_width, width outside 1..64, a null pointer, a count of 0, or whatever
+ * csgn_uint_pick_rows_offsets refuses for some plane; CSGN_ERR_UNSUPPORTED for a plane with Tout_j * dL of 2^31 words per
+ * element or more, or batch * A_j * dL or batch * Tout_j * dL of 2^60 words or more (computed without wrap).  batch == 0 is
+ * CSGN_OK.  A test that wants to know whether a size is refused asks here, never the launching call. */
+int csgn_uint_pick_rows_check(uint64_t n_bits, uint64_t batch, uint64_t index_width, const uint64_t *h_index_terms,
+                              uint64_t rows, uint64_t width, const uint64_t *h_row_terms);
+/* Which form a csgn_uint_pick_rows call of this shape takes (host only, a static string): "k_uint_pick_rows" (one kernel
+ * writes every output plane, arrays read in place) or "composed" (per row r: csgn_uint_plain's EQ into a temporary the
+ * calling thread keeps (csgn_uint_addk's rules for its composed form), then per plane a pitched copy of the row into a
+ * dense temporary and csgn_mul_uniform into the row's block at pitch Tout_j).  Knob "uint_pick_rows_form" (-1 per shape,
+ * 0 composed, 1 fused) decides; the words are the same.  Per shape: fused for every shape.  "" where
+ * csgn_uint_pick_rows_check refuses the arguments. */
+const char *csgn_uint_pick_rows_kernel(uint64_t n_bits, uint64_t batch, uint64_t index_width,
+                                       const uint64_t *h_index_terms, uint64_t rows, uint64_t width,
+                                       const uint64_t *h_row_terms);
+/* h_out[0..2] = (r, in, c) of output position `position` < Tout of ONE plane with the rows h_row_terms[0..rows): the row
+ * whose block holds the position, the entry of EQ(x, r) and the term of the row (host only).  It runs the very search of
+ * the rows' output offsets and the division by T[r] that the kernel's lanes run, compiled for the host, so the walk can
+ * be checked on a CPU.  CSGN_ERR_INVALID for a shape csgn_uint_pick_rows_offsets refuses, a null pointer or a position
+ * of Tout or more; CSGN_ERR_UNSUPPORTED where A or Tout reaches 2^32 (the kernel's records are 32-bit; a launch refuses
+ * such a plane long before). */
+int csgn_uint_pick_rows_decode(uint64_t index_width, const uint64_t *h_index_terms, uint64_t rows,
+                               const uint64_t *h_row_terms, uint64_t position, uint64_t *h_out);
+/* The read over `batch` arrays.  h_index: a HOST array of index_width device pointers (plane k: batch * s_k * dL words),
+ * h_arrays: a HOST array of `width` device pointers (plane j: batch * A_j * dL words, csgn_uint_write's output layout),
+ * h_out: a HOST array of `width` device pointers (output j: batch * Tout_j * dL words, uniform).  Planes may alias one
+ * another; no output overlaps an input or another output.  Statuses: csgn_uint_pick_rows_check's, then CSGN_ERR_INVALID
+ * for a null host array or a null device pointer among the first index_width / width entries.  batch == 0 succeeds and
+ * touches nothing.  The fused form is one launch.  The calling thread keeps the row tables of the shapes it has used, on
+ * the host and on the device (up to 128 tables; planes with equal rows share one): the first call of a shape uploads
+ * them and waits for the copy, a repeated call uploads nothing, is asynchronous on the caller's stream and can be
+ * captured into a graph (a first call under capture is refused: hipErrorStreamCaptureUnsupported).  No GPU:
+ * CSGN_ERR_NO_DEVICE, no CPU fallback. */
+int csgn_uint_pick_rows(uint64_t n_bits, uint64_t batch, uint64_t index_width, const uint64_t *const *h_index,
+                        const uint64_t *h_index_terms, uint64_t rows, uint64_t width, const uint64_t *const *h_arrays,
+                        const uint64_t *h_row_terms, uint64_t *const *h_out, void *stream);
 
 /* ------------------------------------------- encrypted arrays written at encrypted indices ---- */
 
