@@ -2,6 +2,8 @@
 // Hand-written CDNA4 (gfx950) HIP; shared helpers in csgn_device.h, design notes in DESIGN.md.
 #include "csgn_device.h"
 
+#include <type_traits>
+
 namespace csgn {
 
 namespace {
@@ -81,6 +83,135 @@ __global__ void __launch_bounds__(256) k_mul_flat(const Unit *__restrict__ L,
             unit_store<Unit, true>(out + (PITCH ? oidx[m] : (u64)g), l[m] & r[m]);
     }
     if (pf_on)
+        asm volatile("" ::"v"(pf_val));
+}
+
+// x / d for x < 2^15 by one 24-bit multiply and a shift: m = ceil(2^s / d) with s = 15 + ceil(log2 d).  Exact, since
+// m * d - 2^s < d <= 2^(s - 15) puts x * m / 2^s less than 1 / d above x / d; m <= 2^16, so x * m stays below 2^31.
+// d = 1 is m = 2^15, s = 15: no special case.
+struct Div15 {
+    u32 m, s;
+};
+
+inline Div15 div15_make(u32 d)
+{
+    u32 l = 0;
+    while ((1u << l) < d)
+        ++l;
+    const u32 s = 15u + l;
+    return Div15{(u32)(((1ull << s) + d - 1) / d), s};
+}
+
+__device__ inline u32 div15(u32 x, Div15 d) { return (u32)__umul24(x, d.m) >> d.s; }
+
+// csgn_fastdiv as a select instead of an early return: on a block-uniform numerator it is scalar code with no branch
+// for a kernel-argument load to hide behind.
+__device__ inline u32 fastdiv_sel(u32 n, const FastDiv &f)
+{
+    const u32 t = (u32)(((u64)n * f.magic) >> 32);
+    const u32 q = (t + ((n - t) >> 1)) >> f.shift;
+    return f.d == 1u ? n : q;
+}
+
+// One struct, read whole at the top of the kernel: every field arrives behind the same wait.
+struct FlatBlkArgs {
+    const void *L;
+    const void *R;
+    void *out;
+    u32 last;           // total_units - 1
+    u32 nblocks;        // the grid, for the XCD order (gridDim.x is a load of its own)
+    u32 t1;
+    FastDiv dPU, dCU, dU;   // .d: units per pair, per row, per term
+    Div15 rCU, rU;      // rCU: short rows only
+    u32 pf_rows, total_rows, opitch;
+};
+
+// base[idx] for an index whose byte offset fits 32 bits: a scalar base and one 32-bit lane offset in the instruction
+template <typename Unit>
+__device__ inline Unit *at32(Unit *base, u32 idx)
+{
+    using Byte = std::conditional_t<std::is_const<Unit>::value, const char, char>;
+    return reinterpret_cast<Unit *>(reinterpret_cast<Byte *>(base) + idx * (u32)sizeof(Unit));
+}
+
+// k_mul_flat with the index of a workgroup's FIRST unit decomposed once, on the scalar unit, for products of at least
+// one workgroup's 256*MF units (PU >= 256*MF; smaller pairs stay with k_mul_flat).  The first unit g0 = bid*256*MF
+// depends on blockIdx.x and the arguments alone, so (pair0, row i0, column c0, k0 = c0 mod U) are scalar registers, and
+// a lane places itself from its offset o < 256*MF into the workgroup:
+//   * the column is x = c0 + o; LONG rows (CU >= 256*MF) wrap at most once (x >= CU), short rows di = x / CU times,
+//     x < CU + 256*MF < 2^12 by a Div15;
+//   * k = (k0 + o) mod U by a Div15, whatever the wrap (a row is whole terms); the host guarantees U + 256*MF <= 2^15
+//     and, for at32, CU + 256*MF <= 2^28;
+//   * left operands of consecutive pairs are contiguous, so the left term is row grow0 + di of the LAUNCH and a pair
+//     boundary does not show; the right operand and a pitched output move on by one pair where o reaches the end of
+//     pair0 (PU >= 256*MF: at most once).  Bases are scalar, a lane adds a 32-bit offset.
+// Loads are unconditional on a clamped offset as in k_mul_flat, and so is the store: the lanes past the launch's last
+// unit repeat that unit -- same address, same value -- so the kernel has no branch (PF apart) and every argument is
+// loaded at its top.  PF: the left-term prefetch of k_mul_flat, compiled in only for launches that have pf_rows.
+// The scalar prologue is measured, not minimal: the same vector code behind twelve fewer scalar instructions ran the
+// bench launch 4 % slower than k_mul_flat -- A/B any change to it.
+template <typename Unit, int MF, bool XCD, bool PITCH, bool LONG, bool PF>
+__global__ void __launch_bounds__(256) k_mul_flat_blk(const FlatBlkArgs a)
+{
+    constexpr u32 B = 256u * MF;
+    const u32 U = a.dU.d, CU = a.dCU.d, PU = a.dPU.d;
+    const u32 bid = XCD ? xcd_contiguous_block(blockIdx.x, a.nblocks) : blockIdx.x;
+    const u32 g0 = bid * B;
+    const u32 pair0 = fastdiv_sel(g0, a.dPU), rr0 = g0 - pair0 * PU;
+    const u32 i0 = fastdiv_sel(rr0, a.dCU), c0 = rr0 - i0 * CU;
+    const u32 k0 = c0 - fastdiv_sel(c0, a.dU) * U;
+    const u32 grow0 = pair0 * a.t1 + i0;                // row of the launch
+    const u32 live = a.last - g0;                       // the launch's last unit, from g0
+    const u32 to_pair = PU - rr0;                       // short rows: offsets from here on belong to pair0 + 1
+    const bool last_row = i0 + 1u == a.t1;              // LONG: the one wrap is also a pair's end
+    const Unit *Lb = reinterpret_cast<const Unit *>(a.L);
+    const Unit *Lr = Lb + (u64)grow0 * U;
+    const Unit *Rp = reinterpret_cast<const Unit *>(a.R) + (u64)pair0 * CU;
+    Unit *Ob = reinterpret_cast<Unit *>(a.out) + (PITCH ? (u64)pair0 * a.opitch + rr0 : (u64)g0);
+    const u32 r_back = last_row ? 0u : CU;              // LONG: a wrapped lane's column, seen from pair0's right operand
+    const u32 o_skip = PITCH ? a.opitch - PU : 0u;      // units between two pairs' products
+    const int minus_U = -(int)U;
+    Unit l[MF], r[MF], pf_val;
+    u32 oo[MF];
+    bool next[MF];
+    bool pf_on = false;
+#pragma unroll
+    for (int m = 0; m < MF; ++m) {
+        const u32 o = min((u32)m * 256u + threadIdx.x, live);
+        const u32 x = c0 + o, kx = k0 + o;
+        const u32 k = (u32)(__mul24((int)div15(kx, a.rU), minus_U) + (int)kx);
+        u32 di, c;
+        if (LONG) {
+            const bool w = x >= CU;
+            di = w ? 1u : 0u;
+            c = x - (w ? CU : 0u);
+            l[m] = *at32(Lr, (w ? U : 0u) + k);
+            r[m] = *at32(Rp, x - (w ? r_back : 0u));
+            next[m] = w && last_row;
+        } else {
+            di = div15(x, a.rCU);
+            c = x - __umul24(di, CU);
+            next[m] = o >= to_pair;
+            l[m] = *at32(Lr, __umul24(di, U) + k);
+            r[m] = *at32(Rp, c + (next[m] ? CU : 0u));
+        }
+        oo[m] = o;
+        if (PF && m == 0) {
+            const u32 grow = grow0 + di + a.pf_rows;
+            if (c < U && grow < a.total_rows) {
+                pf_val = Lb[(u64)grow * U + c];
+                pf_on = true;
+            }
+        }
+    }
+#pragma unroll
+    for (int m = 0; m < MF; ++m) {
+        if (PITCH)      // the skip can be most of 2^32 units: a 64-bit index
+            unit_store<Unit, true>(Ob + ((u64)oo[m] + (next[m] ? o_skip : 0u)), l[m] & r[m]);
+        else
+            unit_store<Unit, true>(at32(Ob, oo[m]), l[m] & r[m]);
+    }
+    if (PF && pf_on)
         asm volatile("" ::"v"(pf_val));
 }
 
@@ -1453,6 +1584,21 @@ hipError_t mul_uniform_chunk(u32 U, u64 pairs, u64 call_pairs, u32 t1, u32 t2, c
         }
         const FastDiv dPU = csgn_fastdiv_make((u32)PU), dCU = csgn_fastdiv_make(t2 * U),
                       dU = csgn_fastdiv_make(U);
+        // a pair of at least one workgroup's units: the workgroup decomposes its first unit once (k_mul_flat_blk);
+        // long rows need U + 256*mf within a Div15 for k and 32-bit byte offsets into a row (short rows have both:
+        // U <= CU < 256*mf)
+        const u32 wg_units = 256u * (u32)mf, CU = t2 * U;
+        const bool long_rows = CU >= wg_units;
+        const bool blk = PU >= wg_units && (!long_rows || (U + wg_units <= (1u << 15) && CU + wg_units <= (1u << 28)));
+        FlatBlkArgs fa = {};
+        fa.t1 = t1;
+        fa.dPU = dPU;
+        fa.dCU = dCU;
+        fa.dU = dU;
+        fa.rCU = div15_make(long_rows ? 1u : CU);
+        fa.rU = div15_make(U);
+        fa.pf_rows = pfr;
+        fa.opitch = opitch;
         for (u64 p0 = 0; p0 < pairs; p0 += pairs_per) {
             const u64 np = (pairs - p0 < pairs_per) ? pairs - p0 : pairs_per;
             const u32 tot = (u32)(np * PU);
@@ -1471,9 +1617,32 @@ hipError_t mul_uniform_chunk(u32 U, u64 pairs, u64 call_pairs, u32 t1, u32 t2, c
                 else if (plan.touch & 2)
                     k_touch<<<ceil_div_u64(rl, 256u), 256, 0, s>>>(reinterpret_cast<const u32 *>(Rc), rl, lb / 4);
             }
-#define CSGN_FLAT(MF)                                                                                  \
+            fa.L = Lc;
+            fa.R = Rc;
+            fa.out = Oc;
+            fa.last = tot - 1u;
+            fa.nblocks = blocks;
+            fa.total_rows = trows;
+#define CSGN_FLAT_BLK(MF, LONG, PF)                                                                    \
     do {                                                                                               \
         if (opitch)                                                                                    \
+            k_mul_flat_blk<Unit, MF, true, true, LONG, PF><<<blocks, 256, 0, s>>>(fa);                 \
+        else if (tune.xcd)                                                                             \
+            k_mul_flat_blk<Unit, MF, true, false, LONG, PF><<<blocks, 256, 0, s>>>(fa);                \
+        else                                                                                           \
+            k_mul_flat_blk<Unit, MF, false, false, LONG, PF><<<blocks, 256, 0, s>>>(fa);               \
+    } while (0)
+#define CSGN_FLAT(MF)                                                                                  \
+    do {                                                                                               \
+        if (blk && long_rows && pfr)                                                                   \
+            CSGN_FLAT_BLK(MF, true, true);                                                             \
+        else if (blk && long_rows)                                                                     \
+            CSGN_FLAT_BLK(MF, true, false);                                                            \
+        else if (blk && pfr)                                                                           \
+            CSGN_FLAT_BLK(MF, false, true);                                                            \
+        else if (blk)                                                                                  \
+            CSGN_FLAT_BLK(MF, false, false);                                                           \
+        else if (opitch)                                                                               \
             k_mul_flat<Unit, MF, true, true><<<blocks, 256, 0, s>>>(Lc, Rc, Oc, tot, t1, t2, U, dPU, dCU, dU, pfr, trows, opitch);  \
         else if (tune.xcd)                                                                             \
             k_mul_flat<Unit, MF, true><<<blocks, 256, 0, s>>>(Lc, Rc, Oc, tot, t1, t2, U, dPU, dCU, dU, pfr, trows);  \
@@ -1487,6 +1656,7 @@ hipError_t mul_uniform_chunk(u32 U, u64 pairs, u64 call_pairs, u32 t1, u32 t2, c
             default: CSGN_FLAT(8); break;
             }
 #undef CSGN_FLAT
+#undef CSGN_FLAT_BLK
             hipError_t e = hipGetLastError();
             if (e != hipSuccess)
                 return e;
