@@ -525,6 +525,31 @@ class HipPath:
         check(self.lib.csgn_uint_arith(n_bits, op, batch, w, h_a, h_ta, h_b, h_tb, h_out, _ptr(carry), self.stream))
         return [o[:s] for o, s in zip(outs, sizes)], (None if carry is None else carry[:csize])
 
+    def uint_bitwise(self, n_bits: int, op: int, batch: int, a, a_terms, b=None, b_terms=None, sel=None, sel_terms: int = 0,
+                     outs=None):
+        """csgn_uint_bitwise: op = 1 a & b, 2 a | b, 3 a ^ b, 4 ~a, 5 sel ? a : b, 6 sel ? a : 0 of the encrypted
+        integers a and b (bit 0 first; plane j a uniform batch of a_terms[j] / b_terms[j] terms) and the one-bit batch
+        `sel` of sel_terms terms.  Operands the op does not read may be left out.  Returns the output planes, of
+        csgn_uint_bitwise_terms terms per element, fresh ones unless `outs` is given."""
+        w = len(a)
+        with_b, with_sel = op in (1, 2, 3, 5), op in (5, 6)
+        assert w == len(a_terms) and (not with_b or w == len(b) == len(b_terms)) and (not with_sel or sel is not None)
+        h_ta = (C.c_uint64 * max(w, 1))(*[int(t) for t in a_terms])
+        h_tb = (C.c_uint64 * max(w, 1))(*[int(t) for t in b_terms]) if with_b else None
+        T = [int(self.lib.csgn_uint_bitwise_terms(op, int(sel_terms), int(a_terms[j]), int(b_terms[j]) if with_b else 0))
+             for j in range(w)]
+        assert w and all(T), "bad operation, width or term count"
+        dl = self.default_len(n_bits)
+        sizes = [batch * t * dl for t in T]
+        if outs is None:
+            outs = [self.empty_words(max(s, 1)) for s in sizes]
+        h_a = (C.c_void_p * w)(*[_ptr(p) for p in a])
+        h_b = (C.c_void_p * w)(*[_ptr(p) for p in b]) if with_b else None
+        h_out = (C.c_void_p * w)(*[_ptr(o) for o in outs])
+        check(self.lib.csgn_uint_bitwise(n_bits, op, batch, w, _ptr(sel) if with_sel else None, int(sel_terms), h_a, h_ta,
+                                         h_b, h_tb, h_out, self.stream))
+        return [o[:s] for o, s in zip(outs, sizes)]
+
     def matmul(self, n_bits: int, rows: int, inner: int, cols: int, a: torch.Tensor, t_a: int, b: torch.Tensor, t_b: int,
                transposed: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """csgn_matmul: the product over F2 of the encrypted bit matrices `a` (rows x inner, element i*inner + e, t_a

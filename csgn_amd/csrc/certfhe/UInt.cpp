@@ -154,6 +154,59 @@ std::vector<CiphertextBatch> mapPlanes(unsigned n, Check check, Make make)
 
 void noCheck(unsigned) {}
 
+// ------------------------------------------------------------------ the plane-by-plane operators
+
+// Whether an operator that works plane by plane is one csgn_uint_bitwise call: every operand plane uniform.  Ragged
+// planes (and empty batches) take the CiphertextBatch operators and Gates.h plane by plane, with the same words.
+bool bitwiseCall(int op, uint64_t ts, const std::vector<uint64_t> &ta, const std::vector<uint64_t> &tb, bool uniform)
+{
+    if (!uniform || ta.empty() || ta.size() > 64 || (!tb.empty() && tb.size() != ta.size()))
+        return false;
+    for (size_t j = 0; j < ta.size(); ++j)
+        if (csgn_uint_bitwise_terms(op, ts, ta[j], tb.empty() ? 0 : tb[j]) == 0)
+            return false;                                 // a shape the call would refuse
+    return true;
+}
+
+// Output planes of `op` over the planes pa (and pb, sel where the op reads them): check(j) for every plane first, so
+// that nothing is allocated before all sizes fit; then ONE csgn_uint_bitwise call into fresh planes, or make(j) plane
+// by plane.
+template <typename Check, typename Make>
+std::vector<CiphertextBatch> bitwisePlanes(int op, const CiphertextBatch *sel, const Planes &pa, const Planes *pb,
+                                           Check check, Make make)
+{
+    const unsigned w = (unsigned)pa.list.size();
+    const uint64_t count = pa.list[0]->size(), ts = sel ? termsOf(*sel) : 0;
+    const bool uniform = pa.uniform && (!pb || pb->uniform) && (!sel || sel->uniform());
+    if (count == 0 || !bitwiseCall(op, ts, pa.terms, pb ? pb->terms : std::vector<uint64_t>(), uniform))
+        return mapPlanes(w, check, make);
+    std::vector<uint64_t> T(w);
+    for (unsigned j = 0; j < w; ++j) {
+        check(j);
+        T[j] = csgn_uint_bitwise_terms(op, ts, pa.terms[j], pb ? pb->terms[j] : 0);
+    }
+    const Context &ctx = pa.list[0]->context();
+    std::vector<CiphertextBatch> out = makePlanes(ctx, count, T);
+    detail::check(csgn_uint_bitwise(ctx.getN(), op, count, w, sel ? sel->deviceValues() : nullptr, ts, sources(pa).data(),
+                                    pa.terms.data(), pb ? sources(*pb).data() : nullptr, pb ? pb->terms.data() : nullptr,
+                                    wordsOf(out).data(), detail::stream()),
+                  "csgn_uint_bitwise");
+    return out;
+}
+
+// mask * planes[j] for every plane: the classes of sumWhere and the planes of keepWhere
+std::vector<CiphertextBatch> keepPlanes(const CiphertextBatch &mask, const std::vector<CiphertextBatch> &planes, const char *who)
+{
+    const Planes pa(planes);
+    return bitwisePlanes(
+        CSGN_UINT_BITWISE_KEEP, &mask, pa, nullptr,
+        [&](unsigned j) {
+            const uint64_t ts = termsOf(mask), ta = pa.terms[j];
+            checked(ta && ts > (kMaxWords / ta) ? 0 : ts * ta, mask.context(), who);
+        },
+        [&](unsigned j) { return mask * planes[j]; });
+}
+
 // ------------------------------------------------------------------ one step
 
 bool allUniform(const CiphertextBatch *x, const CiphertextBatch &a, const CiphertextBatch &b)
@@ -700,16 +753,18 @@ UIntBatch UIntBatch::operator-() const { return UIntBatch(addPlain(*this, maskOf
 
 UIntBatch UIntBatch::operator~() const
 {
-    return UIntBatch(mapPlanes(
-        width(), [&](unsigned j) { gateTerms(CSGN_GATE_NOT, 0, termsOf(planes_[j]), 0, context(), "UIntBatch::operator~"); },
+    return UIntBatch(bitwisePlanes(
+        CSGN_UINT_BITWISE_NOT, nullptr, Planes(*this), nullptr,
+        [&](unsigned j) { gateTerms(CSGN_GATE_NOT, 0, termsOf(planes_[j]), 0, context(), "UIntBatch::operator~"); },
         [&](unsigned j) { return logicNot(planes_[j]); }));
 }
 
 UIntBatch UIntBatch::operator&(const UIntBatch &rhs) const
 {
     requireSame(*this, rhs, "UIntBatch::operator&");
-    return UIntBatch(mapPlanes(
-        width(),
+    const Planes pb(rhs);
+    return UIntBatch(bitwisePlanes(
+        CSGN_UINT_BITWISE_AND, nullptr, Planes(*this), &pb,
         [&](unsigned j) {
             const uint64_t ta = termsOf(planes_[j]), tb = termsOf(rhs.planes_[j]);
             checked(tb && ta > (kMaxWords / tb) ? 0 : ta * tb, context(), "UIntBatch::operator&");
@@ -720,8 +775,9 @@ UIntBatch UIntBatch::operator&(const UIntBatch &rhs) const
 UIntBatch UIntBatch::operator|(const UIntBatch &rhs) const
 {
     requireSame(*this, rhs, "UIntBatch::operator|");
-    return UIntBatch(mapPlanes(
-        width(),
+    const Planes pb(rhs);
+    return UIntBatch(bitwisePlanes(
+        CSGN_UINT_BITWISE_OR, nullptr, Planes(*this), &pb,
         [&](unsigned j) {
             gateTerms(CSGN_GATE_OR, 0, termsOf(planes_[j]), termsOf(rhs.planes_[j]), context(), "UIntBatch::operator|");
         },
@@ -731,8 +787,9 @@ UIntBatch UIntBatch::operator|(const UIntBatch &rhs) const
 UIntBatch UIntBatch::operator^(const UIntBatch &rhs) const
 {
     requireSame(*this, rhs, "UIntBatch::operator^");
-    return UIntBatch(mapPlanes(
-        width(),
+    const Planes pb(rhs);
+    return UIntBatch(bitwisePlanes(
+        CSGN_UINT_BITWISE_XOR, nullptr, Planes(*this), &pb,
         [&](unsigned j) { checked(termsOf(planes_[j]) + termsOf(rhs.planes_[j]), context(), "UIntBatch::operator^"); },
         [&](unsigned j) { return planes_[j] + rhs.planes_[j]; }));
 }
@@ -754,13 +811,21 @@ UIntBatch UIntBatch::operator|(uint64_t k) const
 UIntBatch UIntBatch::operator^(uint64_t k) const
 {
     requireConstant(*this, k, "UIntBatch::operator^");
-    return UIntBatch(mapPlanes(
-        width(),
-        [&](unsigned j) {
-            if ((k >> j) & 1u)
-                gateTerms(CSGN_GATE_NOT, 0, termsOf(planes_[j]), 0, context(), "UIntBatch::operator^");
-        },
-        [&](unsigned j) { return (k >> j) & 1u ? logicNot(planes_[j]) : planes_[j]; }));
+    // only the planes with a set bit of k are computed (one call); the others share the source's payload
+    std::vector<CiphertextBatch> flip;
+    std::vector<unsigned> at(width(), 0);
+    for (unsigned j = 0; j < width(); ++j)
+        if ((k >> j) & 1u) {
+            at[j] = (unsigned)flip.size();
+            flip.push_back(planes_[j]);
+        }
+    if (flip.empty())
+        return *this;
+    const std::vector<CiphertextBatch> flipped = bitwisePlanes(
+        CSGN_UINT_BITWISE_NOT, nullptr, Planes(flip), nullptr,
+        [&](unsigned i) { gateTerms(CSGN_GATE_NOT, 0, termsOf(flip[i]), 0, context(), "UIntBatch::operator^"); },
+        [&](unsigned i) { return logicNot(flip[i]); });
+    return UIntBatch(mapPlanes(width(), noCheck, [&](unsigned j) { return (k >> j) & 1u ? flipped[at[j]] : planes_[j]; }));
 }
 
 UIntBatch UIntBatch::shiftLeft(unsigned s) const
@@ -841,12 +906,30 @@ UIntBatch select(const CiphertextBatch &sel, const UIntBatch &a, const UIntBatch
 {
     requireSame(a, b, "select");
     requireSameBit(sel, a, "select");
-    return UIntBatch::fromPlanes(mapPlanes(
-        a.width(),
+    const Planes pb(b);
+    return UIntBatch::fromPlanes(bitwisePlanes(
+        CSGN_UINT_BITWISE_SELECT, &sel, Planes(a), &pb,
         [&](unsigned j) {
             gateTerms(CSGN_GATE_MUX, termsOf(sel), termsOf(a.plane(j)), termsOf(b.plane(j)), a.context(), "select");
         },
         [&](unsigned j) { return logicMux(sel, a.plane(j), b.plane(j)); }));
+}
+
+UIntBatch keepWhere(const CiphertextBatch &mask, const UIntBatch &a)
+{
+    requireSameBit(mask, a, "keepWhere");
+    if (a.size() == 0)
+        return UIntBatch::fromPlanes(std::vector<CiphertextBatch>(a.width(), BatchAccess::make(a.context(), 0, 1)));
+    std::vector<CiphertextBatch> planes;
+    for (unsigned j = 0; j < a.width(); ++j)
+        planes.push_back(a.plane(j));
+    return UIntBatch::fromPlanes(keepPlanes(mask, planes, "keepWhere"));
+}
+
+const char *bitwiseRoute(int op, uint64_t sel_terms, const std::vector<uint64_t> &a_terms, const std::vector<uint64_t> &b_terms,
+                         bool uniform_planes)
+{
+    return bitwiseCall(op, sel_terms, a_terms, b_terms, uniform_planes) ? "call" : "planes";
 }
 
 // ------------------------------------------------------------------ selection by a < b (csgn_uint_lt_select)
@@ -2082,9 +2165,10 @@ UIntBatch sumWhere(const CiphertextBatch &mask, const UIntBatch &values, uint64_
         throw std::invalid_argument("certFHE::sumWhere: a masked value exceeds 2^31 words per element");
     const std::vector<unsigned> js = firstPlanes(planes);
     const std::vector<uint64_t> T = wsumSizes(ctx, n, t, js, "sumWhere");
-    std::vector<CiphertextBatch> cls;
+    std::vector<CiphertextBatch> low;
     for (size_t c = 0; c < n.size(); ++c)
-        cls.push_back(mask * values.plane((unsigned)c));
+        low.push_back(values.plane((unsigned)c));
+    const std::vector<CiphertextBatch> cls = keepPlanes(mask, low, "sumWhere");
     return UIntBatch::fromPlanes(wsumPlanes(ctx, values.size() / group, cls, n, js, T, "sumWhere"));
 }
 

@@ -1826,6 +1826,55 @@ int csgn_uint_arith(uint64_t n_bits, int op, uint64_t batch, uint64_t width, con
     return CSGN_OK;
 }
 
+/* ------------------------------------------------ the plane-by-plane operators of two integers ---- */
+
+uint64_t csgn_uint_bitwise_terms(int op, uint64_t t_sel, uint64_t t_a, uint64_t t_b)
+{
+    return csgn::uint_bitwise_terms(op, t_sel, t_a, t_b);
+}
+
+const char *csgn_uint_bitwise_kernel(uint64_t n_bits, int op, uint64_t batch, uint64_t width, uint64_t t_sel,
+                                     const uint64_t *h_a_terms, const uint64_t *h_b_terms)
+{
+    return csgn::uint_bitwise_kernel_name(n_bits, op, batch, width, t_sel, (const u64 *)h_a_terms, (const u64 *)h_b_terms);
+}
+
+int csgn_uint_bitwise(uint64_t n_bits, int op, uint64_t batch, uint64_t width, const uint64_t *d_sel, uint64_t t_sel,
+                      const uint64_t *const *h_a, const uint64_t *h_a_terms, const uint64_t *const *h_b,
+                      const uint64_t *h_b_terms, uint64_t *const *h_out, void *stream)
+{
+    if (int rc = check_n(n_bits))
+        return rc;
+    REQUIRE(op >= CSGN_UINT_BITWISE_AND && op <= CSGN_UINT_BITWISE_KEEP, "bitwise: unknown operation %d", op);
+    REQUIRE(width >= 1 && width <= csgn::kBitwiseMaxPlanes, "bitwise: width %llu outside 1..64", (unsigned long long)width);
+    const bool with_b = op != CSGN_UINT_BITWISE_NOT && op != CSGN_UINT_BITWISE_KEEP;
+    const bool with_sel = op == CSGN_UINT_BITWISE_SELECT || op == CSGN_UINT_BITWISE_KEEP;
+    REQUIRE(h_a && h_a_terms && h_out && (!with_b || (h_b && h_b_terms)), "null host pointer");
+    if (int rc = check_planes(h_a, with_b ? h_b : nullptr, width, "plane of a or b"))
+        return rc;
+    if (int rc = check_planes((const uint64_t *const *)h_out, nullptr, width, "output"))
+        return rc;
+    REQUIRE(!with_sel || d_sel, "null device pointer (selector)");
+    const uint64_t dl = csgn_default_len(n_bits);
+    for (uint64_t j = 0; j < width; ++j)
+        REQUIRE(csgn::uint_bitwise_terms(op, t_sel, h_a_terms[j], with_b ? h_b_terms[j] : 0) != 0,
+                "bitwise: an operand of plane %llu has no terms, or the plane's term count overflows",
+                (unsigned long long)j);
+    for (uint64_t j = 0; j < width; ++j) {
+        const uint64_t terms = csgn::uint_bitwise_terms(op, t_sel, h_a_terms[j], with_b ? h_b_terms[j] : 0);
+        if (int rc = check_size(batch, terms, terms, dl, "bitwise: plane %llu", (unsigned long long)j))
+            return rc;
+    }
+    if (int rc = require_device("csgn_uint_bitwise"))
+        return rc;
+    if (batch == 0)
+        return CSGN_OK;
+    HIP_TRY(csgn::uint_bitwise(n_bits, op, batch, width, (const u64 *)d_sel, t_sel, (const u64 *const *)h_a,
+                               (const u64 *)h_a_terms, (const u64 *const *)h_b, (const u64 *)h_b_terms,
+                               (u64 *const *)h_out, S(stream)));
+    return CSGN_OK;
+}
+
 /* ------------------------------------------------ one-bit batches decrypted into one word per element ---- */
 
 const char *csgn_uint_decrypt_kernel(uint64_t n_bits, uint64_t batch, uint64_t n_planes, const uint64_t *h_terms)

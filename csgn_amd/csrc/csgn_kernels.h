@@ -278,6 +278,15 @@ const char *uint_arith_kernel_name(u64 n_bits, int op, u64 batch, u64 w, const u
 hipError_t uint_arith(u64 n_bits, int op, u64 batch, u64 w, const u64 *const *a, const u64 *ta, const u64 *const *b,
                       const u64 *tb, u64 *const *out, u64 *carry, hipStream_t stream);
 
+// a & b, a | b, a ^ b, ~a, select(s, a, b) and s * a of encrypted integers, plane by plane (csgn_uint_bitwise.hip),
+// include/csgn_hip.h's definition; op = CSGN_UINT_BITWISE_*.  a and b: w = 1..64 planes, terms ta[j] / tb[j]; sel: one
+// batch of ts terms; out: w planes.  Operands the op does not read: their counts are ignored, their pointers may be null.
+constexpr u32 kBitwiseMaxPlanes = 64;
+u64 uint_bitwise_terms(int op, u64 ts, u64 ta, u64 tb);   // 0: unknown op, a zero count that is read, or 2^62 or more
+const char *uint_bitwise_kernel_name(u64 n_bits, int op, u64 batch, u64 w, u64 ts, const u64 *ta, const u64 *tb);
+hipError_t uint_bitwise(u64 n_bits, int op, u64 batch, u64 w, const u64 *sel, u64 ts, const u64 *const *a, const u64 *ta,
+                        const u64 *const *b, const u64 *tb, u64 *const *out, hipStream_t stream);
+
 // an encrypted integer shifted, rotated or indexed by an encrypted amount (csgn_uint_pick.hip), include/csgn_hip.h's
 // definition: output j is the sum, ascending in r < rows_j, of EQ(index, r) * a_{src(j, r)}; op = CSGN_UINT_PICK_*.
 // index planes: v = 1..16, terms s[k]; source planes: w = 1..64, every one of t terms; rows: EACH's n, else 0.

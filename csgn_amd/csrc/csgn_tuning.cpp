@@ -49,6 +49,7 @@ const Knob kKnobs[TUNE_COUNT] = {
     {"uint_pick_rows_form", -1},
     {"uint_decrypt_form", -1},
     {"uint_decrypt_chunk", 0},
+    {"uint_bitwise_form", -1},
     {"uint_arith_form", -1},
     {"launch_blocks", 0},
 };

@@ -68,6 +68,7 @@ enum TuneKey {
     TUNE_UINT_PICK_ROWS_FORM, // knob "uint_pick_rows_form": arrays whose rows differ in size read at encrypted indices, the read after csgn_uint_write (csgn_uint_pick_rows.hip): -1 = per shape, 0 = composed form (the tuned launchers row by row), 1 = fused kernel
     TUNE_UINT_DECRYPT_FORM, // knob "uint_decrypt_form": UIntBatch::decrypt and decryptPacked of the classes (certfhe/UInt.h): -1 = per shape, 0 = one CiphertextBatch::decrypt per plane, 1 = one csgn_uint_decrypt call; the C call itself is always the kernel
     TUNE_UINT_DECRYPT_CHUNK, // knob "uint_decrypt_chunk": csgn_uint_decrypt (csgn_uint_decrypt.hip): the most terms of one element of a uniform plane a wave takes before the element is cut into chunks that meet in the value word by atomics, 0 = by shape (1024), never more than 4096; a test sets it low to place the cut
+    TUNE_UINT_BITWISE_FORM, // knob "uint_bitwise_form": a & b, a | b, a ^ b, ~a, select and keepWhere of encrypted integers (csgn_uint_bitwise.hip): -1 = per shape, 0 = plane by plane (csgn_gate_uniform's, csgn_mul_uniform's and csgn_add_uniform's launchers), 1 = the one kernel for every plane
     TUNE_UINT_ARITH_FORM, // knob "uint_arith_form": a + b, a - b, a == b, a != b of encrypted integers (csgn_uint_arith.hip): -1 = per shape, 0 = the per-bit chain (csgn_uint_step's and csgn_gate_uniform's launchers plane by plane), 1 = the one launch
     TUNE_LAUNCH_BLOCKS,  // 256-thread workgroups one launch takes at most where the host splits a call into launches (launch_blocks, csgn_device.h), 0 = the HIP limit; a test sets it low to run the host's splits
     TUNE_COUNT

@@ -195,6 +195,20 @@
 // (0) or the one call (1); left alone (-1), a forced uint_fused keeps the chain, so that both forms of csgn_uint_step can
 // be run through these operators.  arithRoute names the route.  lessEqual and greaterEqual keep the chain and logicNot.
 //
+// THE PLANE-BY-PLANE OPERATORS IN ONE CALL: a & b, a | b, a ^ b, ~a, a ^ k, select(s, a, b) and keepWhere(mask, a) on
+// uniform planes are ONE csgn_uint_bitwise (include/csgn_hip.h) for every plane, whatever the planes' term counts:
+//     keepWhere(mask, a)  mask * a_j on every plane, the mask the LEFT operand                         mask ? a : 0
+// the WHERE of a query applied to a whole integer, and what sumWhere builds its classes with; a plane has ts * ta_j
+// terms for a mask of ts terms.  a ^ k passes only the planes with a set bit of k; the others go on sharing the source's
+// payload.  hammingDistance takes the call through a ^ b.  The C call writes all planes from one kernel or issues the
+// launchers of the CiphertextBatch operators and Gates.h plane by plane, by shape and by knob uint_bitwise_form
+// (csgn_set_tuning, or CSGN_UINT_BITWISE_FORM when the library loads: 0 the launchers, 1 the kernel; left alone, a forced
+// gate_fused keeps the launchers, so that both forms of csgn_gate_uniform can be run through these operators).  Ragged
+// planes (what compact() may return) and empty batches take the CiphertextBatch operators and Gates.h plane by plane --
+// the same words on every route.  Every plane's size is checked before anything is allocated: std::invalid_argument for
+// mismatched contexts, widths or counts, or a plane past 2^31 words per element; keepWhere of an empty batch gives empty
+// planes.  bitwiseRoute names the route.
+//
 // THE TWO ENDS.  UIntBatch::encrypt (both overloads) makes ONE block of width * count ciphertexts, lays the bit bytes
 // plane after plane in one host pass, uploads them once and runs one csgn_encrypt_keyed from stream position 0; plane j
 // is a VIEW at word j * count * dL of that block, so a plane -- also one handed on by plane(j) after the UIntBatch is
@@ -323,6 +337,15 @@ CiphertextBatch greaterThan(const UIntBatch &a, uint64_t k);
 CiphertextBatch greaterEqual(const UIntBatch &a, uint64_t k);
 // element i: sel[i] ? a[i] : b[i]
 UIntBatch select(const CiphertextBatch &sel, const UIntBatch &a, const UIntBatch &b);
+// element i: mask[i] ? a[i] : 0; plane j is mask * a_j.  mask of a's context and count
+UIntBatch keepWhere(const CiphertextBatch &mask, const UIntBatch &a);
+// The route a & b, a | b, a ^ b, ~a, select and keepWhere take (op: CSGN_UINT_BITWISE_* of csgn_hip.h) for a selector of
+// sel_terms terms and planes of a_terms[j] / b_terms[j] terms (operands the op does not read: 0 / empty), every plane
+// uniform or not (a static string): "call" (one csgn_uint_bitwise, in the form its knob chooses) or "planes" (the
+// CiphertextBatch operators and Gates.h plane by plane; also for a shape the call would refuse).  No device work; for
+// diagnostics and tests, like arithRoute: the words are the same.
+const char *bitwiseRoute(int op, uint64_t sel_terms, const std::vector<uint64_t> &a_terms, const std::vector<uint64_t> &b_terms,
+                         bool uniform_planes);
 
 // element i: a[i] < b[i] ? a[i] : b[i] / the other one; a tie takes b for min and a for max
 UIntBatch min(const UIntBatch &a, const UIntBatch &b);

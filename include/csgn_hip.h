@@ -974,6 +974,55 @@ int csgn_uint_arith(uint64_t n_bits, int op, uint64_t batch, uint64_t width, con
                     const uint64_t *h_a_terms, const uint64_t *const *h_b, const uint64_t *h_b_terms,
                     uint64_t *const *h_out, uint64_t *d_carry, void *stream);
 
+/* ------------------------------------- the plane-by-plane operators of encrypted integers ---- */
+
+/* a & b, a | b, a ^ b, ~a, select(s, a, b) and the mask s * a of ENCRYPTED integers, every plane in one launch: what
+ * certfhe/UInt.h's operator&, operator|, operator^, operator~, select and keepWhere compute.
+ * Inputs: a and b, integers of `width` = w planes (w in 1..64, bit 0 first) of `batch` elements, plane j uniform with
+ * h_a_terms[j] = ta / h_b_terms[j] = tb terms per element, and d_sel, ONE batch of t_sel = ts terms per element.
+ * Output plane j is the composition of the reference's operator+ (concatenation) and operator* (all-pairs AND, row i
+ * = the left operand's term i against every term of the right one) the class operators make of plane j, word for
+ * word, in the order of the Gates table above:
+ *     op       plane j                                          terms
+ *     AND      a_j * b_j                                        ta * tb
+ *     OR       (a_j + b_j) + (a_j * b_j)                        ta + tb + ta * tb
+ *     XOR      a_j + b_j                                        ta + tb
+ *     NOT      a_j + ONE                                        ta + 1
+ *     SELECT   (s * (a_j + b_j)) + b_j                          ts * (ta + tb) + tb
+ *     KEEP     s * a_j   (the selector is the LEFT operand)     ts * ta
+ * SELECT decrypts to s ? a : b and KEEP to s ? a : 0, element by element. */
+enum { CSGN_UINT_BITWISE_AND = 1, CSGN_UINT_BITWISE_OR, CSGN_UINT_BITWISE_XOR,
+       CSGN_UINT_BITWISE_NOT, CSGN_UINT_BITWISE_SELECT, CSGN_UINT_BITWISE_KEEP };
+/* Terms per element of one output plane (host only); csgn_gate_terms' count for OR, NOT and MUX.  0 for an unknown op,
+ * for a zero count of an operand the op reads (a: every op; b: AND, OR, XOR, SELECT; the selector: SELECT, KEEP), or
+ * for a count of 2^62 or more.  The counts of operands the op does not read are ignored. */
+uint64_t csgn_uint_bitwise_terms(int op, uint64_t t_sel, uint64_t t_a, uint64_t t_b);
+/* Which form a csgn_uint_bitwise call of this shape takes under the calling thread's knobs (host only, a static
+ * string): "k_uint_bitwise" (ONE kernel for every plane: a workgroup belongs to one plane, a lane writes one 16- or
+ * 8-byte unit; its arguments hold the tables of all 64 planes, so a call is one launch, split by elements only at
+ * knob "launch_blocks" and at HIP's limit of 2^32 lanes) or "planes" (csgn_mul_uniform's, csgn_add_uniform's and
+ * csgn_gate_uniform's launchers plane by plane, each writing its output plane: one to three launches a plane).  Knob
+ * "uint_bitwise_form" (-1 per shape, 0 planes, 1 the kernel) decides; left at -1, a forced knob "gate_fused" gives
+ * the planes, and a shape of which one element of all planes does not fit one launch's lanes takes the planes
+ * whatever the knob says.  The words are the same.  Per shape: DESIGN 4.31.  "" for an invalid shape (n_bits 0, an
+ * unknown op, a width outside 1..64, a null pointer to counts the op reads, a bad term count). */
+const char *csgn_uint_bitwise_kernel(uint64_t n_bits, int op, uint64_t batch, uint64_t width, uint64_t t_sel,
+                                     const uint64_t *h_a_terms, const uint64_t *h_b_terms);
+/* The operation over `batch` elements.  h_a, h_b, h_out: HOST arrays of `width` device pointers (plane j: batch * ta_j
+ * * dL, batch * tb_j * dL and batch * T_j * dL words), d_sel: batch * ts * dL words.  The pointers and counts of an
+ * operand the op does not read are not looked at and may be NULL / 0.  Inputs may alias one another in any way (a & a,
+ * b_j == a_{j-1} after a public rotate, the selector a plane of a); no output overlaps an input or another output.
+ * Checks, in this order, the first that fails giving the status: n_bits; op; width; the host arrays and the device
+ * pointers in them and d_sel (CSGN_ERR_INVALID); the term counts (CSGN_ERR_INVALID); every plane's T * dL below 2^31
+ * words per element and batch times that below 2^60 (CSGN_ERR_UNSUPPORTED; computed without wrap-around); the device
+ * (CSGN_ERR_NO_DEVICE, no CPU fallback).  batch == 0 succeeds.  On the caller's stream, asynchronous,
+ * graph-capturable; no scratch in either form. */
+int csgn_uint_bitwise(uint64_t n_bits, int op, uint64_t batch, uint64_t width,
+                      const uint64_t *d_sel, uint64_t t_sel,
+                      const uint64_t *const *h_a, const uint64_t *h_a_terms,
+                      const uint64_t *const *h_b, const uint64_t *h_b_terms,
+                      uint64_t *const *h_out, void *stream);
+
 /* ------------------------------------- one-bit batches decrypted into one word per element ---- */
 
 /* n_planes one-bit batches of `batch` elements decrypted in ONE pass into one 64-bit word per element: what
