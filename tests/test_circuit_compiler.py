@@ -14,105 +14,11 @@ import pytest
 
 from csgn_amd import capi
 from csgn_amd.capi import check
-from tests.model import Described, config5, lib, random_circuit
+from tests.model import Described, config5, decrypt_masked, evaluate, execute, lib, random_circuit
 
 REUSE, PLACE, FUSE, PUSHDOWN, HOIST = 1, 2, 4, 8, 16
 CORE, ALL = 7, 23
 FOREVER = 2 ** 31 - 1
-
-
-def evaluate(d, inputs):
-    """Every value of the description, element by element: [batch, terms, dl] uint64 arrays."""
-    vals = []
-    for node in d.nodes:
-        if node[0] == "in":
-            vals.append(inputs[len(vals)])
-        elif node[0] == "add":
-            vals.append(np.concatenate([vals[node[1]], vals[node[2]]], axis=1))
-        else:
-            a, b = vals[node[1]], vals[node[2]]
-            vals.append((a[:, :, None, :] & b[:, None, :, :]).reshape(d.batch, -1, d.dl))
-    return vals
-
-
-def decrypt_masked(vals, mask):
-    hits = np.all((vals & mask) == mask, axis=2)               # [batch, terms]
-    return (hits.sum(axis=1) & 1).astype(np.uint8)
-
-
-def execute(d, plan, inputs, mask):
-    """Run the PLAN: kept nodes only, in order, every read and write at the plan's byte offsets and pitches."""
-    block = np.zeros(plan["bytes"] // 8 + 8, dtype=np.uint64)
-    rng = np.random.default_rng(5)
-    block[:] = rng.integers(0, 2 ** 63, size=block.size, dtype=np.uint64)       # stale bytes must never matter
-    dl, B = d.dl, d.batch
-
-    def view(v):
-        pv = plan["values"][v]
-        base, pitch, t = pv["offset"] // 8, pv["pitch"], d.terms[v]
-        assert pv["offset"] % 8 == 0 and pitch >= t * dl
-        idx = base + np.arange(B)[:, None] * pitch + np.arange(t * dl)[None, :]
-        return idx
-
-    def read(v):
-        pv = plan["values"][v]
-        assert pv["region"] and pv["parent"] < 0 and pv["pitch"] == d.terms[v] * dl, f"value {v} is read but not dense"
-        return block[view(v)].reshape(B, d.terms[v], dl)
-
-    def write(v, words):
-        block[view(v)] = words.reshape(B, -1)
-
-    for v, node in enumerate(d.nodes):
-        if node[0] == "in":
-            assert plan["values"][v]["addressable"]
-            write(v, inputs[v])
-    def copy_operand(op, side):
-        """operand `side` of add `op` into its slice of the sum (what the add's own copy, or the prologue launch, does)"""
-        ta = d.terms[op["a"]]
-        out = plan["values"][op["out"]]
-        base, pitch = out["offset"] // 8, out["pitch"]
-        v = op["b"] if side else op["a"]
-        idx = base + (ta * dl if side else 0) + np.arange(B)[:, None] * pitch + np.arange(d.terms[v] * dl)[None, :]
-        block[idx] = read(v).reshape(B, -1)
-
-    # the prologue: every hoisted copy (its source is an input) before the first node
-    for op in plan["ops"]:
-        if op["kind"] == 0 and not op["elided"]:
-            for side, key in ((0, "hoist_a"), (1, "hoist_b")):
-                if op[key]:
-                    assert d.nodes[op["b"] if side else op["a"]][0] == "in" and not op["placed_b" if side else "placed_a"]
-                    copy_operand(op, side)
-    bits = {}
-    for i, op in enumerate(plan["ops"]):
-        if op["elided"]:
-            continue
-        if op["kind"] == 1:
-            a, b = read(op["a"]), read(op["b"])
-            write(op["out"], (a[:, :, None, :] & b[:, None, :, :]).reshape(B, -1, dl))
-        elif op["kind"] == 0:
-            ta = d.terms[op["a"]]
-            out = plan["values"][op["out"]]
-            base, pitch = out["offset"] // 8, out["pitch"]
-            if op["placed_a"]:
-                pa = plan["values"][op["a"]]
-                assert pa["parent"] == op["out"] and pa["offset"] == out["offset"] and pa["pitch"] == pitch
-            elif not op["hoist_a"]:
-                copy_operand(op, 0)
-            if not op["placed_b"] and not op["hoist_b"]:
-                copy_operand(op, 1)
-            elif op["placed_b"]:
-                pb = plan["values"][op["b"]]
-                assert pb["parent"] == op["out"] and pb["offset"] == out["offset"] + ta * dl * 8 and pb["pitch"] == pitch
-        elif op["kind"] == 2:
-            def ev(ei):
-                e = plan["exprs"][ei]
-                if e["kind"] < 0:
-                    return decrypt_masked(read(e["value"]), mask)
-                l, r = ev(e["l"]), ev(e["r"])
-                return (l & r) if e["kind"] == 1 else (l ^ r)
-            bid = sum(1 for o in plan["ops"][:i] if o["kind"] == 2)
-            bits[bid] = ev(op["expr"]) if op["expr"] >= 0 else decrypt_masked(read(op["a"]), mask)
-    return block, bits, read
 
 
 def check_regions(plan):
