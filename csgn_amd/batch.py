@@ -393,6 +393,43 @@ class HipPath:
         return ([o[: batch * int(t) * E * dl] for o, t in zip(outs, value_terms)],
                 None if member is None else member[: batch * E * dl])
 
+    def uint_first(self, n_bits: int, batch: int, group: int, mask, mask_terms, values=(), value_terms=(), outs=None,
+                   any=False, labels=None, label_bits=(), label_outs=None):
+        """csgn_uint_first: of the `group` rows of every output element the FIRST whose encrypted mask bit is set.
+        `mask`: one grouped tensor of batch * group elements (every row of mask_terms[0] terms) or `group` tensors of
+        `batch` elements (row r of mask_terms[r] terms); `values`: grouped planes, plane j uniform with value_terms[j]
+        terms; `labels`: the rows' public constants, `label_bits` the strictly ascending planes of them to write.
+        Returns (output tensors, any tensor or None, label tensors): output j of Q * value_terms[j] terms per element
+        (Q = csgn_uint_first_terms(group, mask_terms, group)), any of Q, label plane i of csgn_uint_first_label_terms;
+        fresh ones unless `outs` / `label_outs` are given; `any`: True for a fresh tensor, or the tensor to write."""
+        g, w, nl = int(group), len(values), len(label_bits)
+        assert len(mask) in (1, g) and len(mask_terms) == g and w == len(value_terms)
+        h_s = (C.c_uint64 * max(g, 1))(*[int(t) for t in mask_terms])
+        h_t = (C.c_uint64 * max(w, 1))(*[int(t) for t in value_terms])
+        h_l = (C.c_uint64 * max(g, 1))(*[int(x) for x in (labels if nl else [0] * g)])
+        h_b = (C.c_uint64 * max(nl, 1))(*[int(x) for x in label_bits])
+        Q = int(self.lib.csgn_uint_first_terms(g, h_s, g))
+        T = [int(self.lib.csgn_uint_first_label_terms(g, h_s, h_l, int(x))) for x in label_bits]
+        assert (Q or not (w or any is not False)) and all(T), "bad group, term count or label plane"
+        dl = self.default_len(n_bits)
+        if outs is None:
+            outs = [self.empty_words(max(batch * int(t) * Q * dl, 1)) for t in value_terms]
+        if label_outs is None:
+            label_outs = [self.empty_words(max(batch * x * dl, 1)) for x in T]
+        if any is True:
+            any = self.empty_words(max(batch * Q * dl, 1))
+        elif any is False:
+            any = None
+        h_m = (C.c_void_p * len(mask))(*[_ptr(p) for p in mask])
+        h_d = (C.c_void_p * max(w, 1))(*[_ptr(p) for p in values])
+        h_out = (C.c_void_p * max(w, 1))(*[_ptr(o) for o in outs])
+        h_lo = (C.c_void_p * max(nl, 1))(*[_ptr(o) for o in label_outs])
+        check(self.lib.csgn_uint_first(n_bits, batch, g, h_m, len(mask), h_s, w, h_d, h_t, h_out, _ptr(any), nl, h_l, h_b,
+                                       h_lo, self.stream))
+        return ([o[: batch * int(t) * Q * dl] for o, t in zip(outs, value_terms)],
+                None if any is None else any[: batch * Q * dl],
+                [o[: batch * x * dl] for o, x in zip(label_outs, T)])
+
     def uint_pick(self, n_bits: int, op: int, batch: int, index, index_terms, a, terms: int, rows: int = 0, outs=None):
         """csgn_uint_pick: the encrypted integer `a` (bit 0 first; every plane a uniform batch of `terms` terms)
         shifted or rotated by the encrypted distance `index` (plane k a uniform batch of index_terms[k] terms), op =

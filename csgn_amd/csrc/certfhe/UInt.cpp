@@ -2181,4 +2181,217 @@ UIntBatch innerProduct(const UIntBatch &a, const UIntBatch &b, uint64_t group, u
     return productPlanes(a, b, group, planes, "innerProduct");
 }
 
+// ------------------------------------------------------------------ the first row whose mask bit is set
+
+namespace {
+
+// Per shape (measured): the call for every group it takes.
+bool firstCall(uint64_t group, bool uniform_operands) { return uniform_operands && group >= 1 && group <= 64; }
+
+struct Priority {
+    std::vector<CiphertextBatch> values, any, labels;    // one per value plane; none or one; one per label plane
+};
+
+// Of every element's `group` rows the first whose mask bit is set: its value planes, with want_any the OR of the mask
+// and, with label_planes, planes 0 .. label_planes - 1 of its public label.  mask: one batch, the grouped layout (row r
+// of element q is element q * group + r), or `group` batches of one element count, the plane layout; values: grouped.
+// Every size first; then ONE csgn_uint_first for uniform operands, else the definition through the batch operators.
+Priority priority(const std::vector<CiphertextBatch> &mask, uint64_t group, const std::vector<CiphertextBatch> &values,
+                  bool want_any, const std::vector<uint64_t> &labels, unsigned label_planes, const char *who)
+{
+    const std::string name = std::string("certFHE::") + who;
+    const Context &ctx = mask[0].context();
+    const bool grouped = mask.size() == 1;
+    if (group == 0 || group > 64 || (grouped && mask[0].size() % group != 0))
+        throw std::invalid_argument(name + ": groups of " + std::to_string(group) + " (1..64) in a batch of " +
+                                    std::to_string(mask[0].size()));
+    const uint64_t count = grouped ? mask[0].size() / group : mask[0].size();
+    for (size_t r = 0; r < mask.size(); ++r)
+        if (!sameContext(mask[r].context(), ctx) || mask[r].size() != mask[0].size())
+            throw std::invalid_argument(name + ": the mask rows differ in count or context");
+    for (size_t j = 0; j < values.size(); ++j)
+        if (!sameContext(values[j].context(), ctx) || values[j].size() != count * group)
+            throw std::invalid_argument(name + ": the values differ from the mask in count or context");
+    Priority out;
+    if (count == 0) {
+        out.values = emptyPlanes(ctx, values.size());
+        out.any = emptyPlanes(ctx, want_any ? 1 : 0);
+        out.labels = emptyPlanes(ctx, label_planes);
+        return out;
+    }
+    // sizes, from the largest term count of a ragged operand: a bound for every element of it
+    const Planes pm(mask), pv(values);
+    std::vector<uint64_t> s(group);
+    bool one_s = true;
+    for (uint64_t r = 0; r < group; ++r) {
+        s[r] = std::max<uint64_t>(pm.terms[grouped ? 0 : r], 1);
+        one_s = one_s && s[r] == s[0];
+    }
+    const std::string too_large = name + ": an output exceeds 2^31 words per element (the group is too large or the mask "
+                                         "has too many terms)";
+    const uint64_t Q = values.empty() && !want_any ? 0 : csgn_uint_first_terms(group, s.data(), group);
+    if ((!values.empty() || want_any) && (Q == 0 || Q >= kMaxWords))
+        throw std::invalid_argument(too_large);
+    std::vector<uint64_t> T(values.size() + (want_any ? 1 : 0)), Tlab, bits;
+    for (size_t j = 0; j < T.size(); ++j) {
+        const uint64_t tj = j < values.size() ? std::max<uint64_t>(pv.terms[j], 1) : 1;
+        if (tj > kMaxWords / Q)
+            throw std::invalid_argument(too_large);
+        T[j] = checked(tj * Q, ctx, who);
+    }
+    std::vector<size_t> at;                                     // the label planes that exist
+    for (unsigned i = 0; i < label_planes; ++i) {
+        bool reached = false;
+        for (uint64_t r = 0; r < group; ++r)
+            reached = reached || ((labels[r] >> i) & 1u);
+        if (!reached)
+            continue;
+        const uint64_t Ti = csgn_uint_first_label_terms(group, s.data(), labels.data(), i);
+        if (Ti == 0 || Ti >= kMaxWords)
+            throw std::invalid_argument(too_large);
+        Tlab.push_back(checked(Ti, ctx, who));
+        bits.push_back(i);
+        at.push_back(i);
+    }
+    out.labels.assign(label_planes, constantBatch(ctx, std::vector<unsigned char>(count, 0)));
+    const bool uniform = pm.uniform && pv.uniform && (!grouped || one_s);
+    if (firstCall(group, uniform)) {
+        std::vector<CiphertextBatch> made = makePlanes(ctx, count, T), lab = makePlanes(ctx, count, Tlab);
+        std::vector<uint64_t *> dst = wordsOf(made);
+        uint64_t *any = want_any ? dst.back() : nullptr;
+        if (!T.empty() || !Tlab.empty())
+            detail::check(csgn_uint_first(ctx.getN(), count, group, sources(pm).data(), mask.size(), s.data(), values.size(),
+                                          sources(pv).data(), pv.terms.data(), dst.data(), any, bits.size(), labels.data(),
+                                          bits.data(), wordsOf(lab).data(), detail::stream()),
+                          "csgn_uint_first");
+        if (want_any) {
+            out.any.push_back(made.back());
+            made.pop_back();
+        }
+        out.values = made;
+        for (size_t k = 0; k < at.size(); ++k)
+            out.labels[at[k]] = lab[k];
+        return out;
+    }
+    // ragged: the definition itself through the batch operators, row by row
+    std::vector<CiphertextBatch> lab(at.size(), mask[0]);
+    std::vector<bool> started(at.size(), false);
+    std::vector<uint64_t> idx(count);
+    CiphertextBatch run = mask[0];
+    for (uint64_t r = 0; r < group; ++r) {
+        for (uint64_t q = 0; q < count; ++q)
+            idx[q] = q * group + r;
+        const CiphertextBatch m = grouped ? mask[0].gather(idx) : mask[r];
+        const CiphertextBatch F = r == 0 ? m : run * m;
+        if (r + 1 < group)
+            run = r == 0 ? logicNot(m) : run * logicNot(m);
+        for (size_t j = 0; j < values.size(); ++j) {
+            const CiphertextBatch p = F * values[j].gather(idx);
+            if (r == 0)
+                out.values.push_back(p);
+            else
+                out.values[j] = out.values[j] + p;
+        }
+        if (want_any) {
+            if (r == 0)
+                out.any.push_back(F);
+            else
+                out.any[0] = out.any[0] + F;
+        }
+        for (size_t k = 0; k < at.size(); ++k) {
+            if (!((labels[r] >> at[k]) & 1u))
+                continue;
+            lab[k] = started[k] ? lab[k] + F : F;
+            started[k] = true;
+        }
+    }
+    for (size_t k = 0; k < at.size(); ++k)
+        out.labels[at[k]] = lab[k];
+    return out;
+}
+
+std::vector<uint64_t> indexLabels(uint64_t group)
+{
+    std::vector<uint64_t> L(group);
+    for (uint64_t r = 0; r < group; ++r)
+        L[r] = r;
+    return L;
+}
+
+// the planes of a as mask rows, bit 0 first (the plane layout; a width of 1: one grouped batch of groups of 1)
+std::vector<CiphertextBatch> rowsOf(const UIntBatch &a, bool from_top)
+{
+    std::vector<CiphertextBatch> rows = planesOf(a);
+    if (from_top)
+        std::reverse(rows.begin(), rows.end());
+    return rows;
+}
+
+} // namespace
+
+const char *firstRoute(uint64_t group, bool uniform_operands) { return firstCall(group, uniform_operands) ? "call" : "loop"; }
+
+UIntBatch firstWhere(const CiphertextBatch &mask, const UIntBatch &values, uint64_t group, CiphertextBatch *any)
+{
+    const Priority p = priority(std::vector<CiphertextBatch>(1, mask), group, planesOf(values), any != nullptr,
+                                std::vector<uint64_t>(), 0, "firstWhere");
+    if (any)
+        *any = p.any[0];
+    return UIntBatch::fromPlanes(p.values);
+}
+
+CiphertextBatch firstWhere(const CiphertextBatch &mask, const CiphertextBatch &values, uint64_t group, CiphertextBatch *any)
+{
+    const Priority p = priority(std::vector<CiphertextBatch>(1, mask), group, std::vector<CiphertextBatch>(1, values),
+                                any != nullptr, std::vector<uint64_t>(), 0, "firstWhere");
+    if (any)
+        *any = p.any[0];
+    return p.values[0];
+}
+
+CiphertextBatch anyOf(const CiphertextBatch &bits, uint64_t group)
+{
+    return priority(std::vector<CiphertextBatch>(1, bits), group, std::vector<CiphertextBatch>(), true,
+                    std::vector<uint64_t>(), 0, "anyOf").any[0];
+}
+
+UIntBatch firstIndex(const CiphertextBatch &mask, uint64_t group, unsigned planes, CiphertextBatch *any)
+{
+    requirePlanes(planes, "firstIndex");
+    const Priority p = priority(std::vector<CiphertextBatch>(1, mask), group, std::vector<CiphertextBatch>(), any != nullptr,
+                                indexLabels(std::min<uint64_t>(group, 64)), planes, "firstIndex");
+    if (any)
+        *any = p.any[0];
+    return UIntBatch::fromPlanes(p.labels);
+}
+
+UIntBatch lowestSetIndex(const UIntBatch &a, unsigned planes, CiphertextBatch *nonzero)
+{
+    requirePlanes(planes, "lowestSetIndex");
+    const Priority p = priority(rowsOf(a, false), a.width(), std::vector<CiphertextBatch>(), nonzero != nullptr,
+                                indexLabels(a.width()), planes, "lowestSetIndex");
+    if (nonzero)
+        *nonzero = p.any[0];
+    return UIntBatch::fromPlanes(p.labels);
+}
+
+UIntBatch lowestSetBit(const UIntBatch &a)
+{
+    std::vector<uint64_t> L(a.width());
+    for (unsigned r = 0; r < a.width(); ++r)
+        L[r] = 1ull << r;
+    return UIntBatch::fromPlanes(priority(rowsOf(a, false), a.width(), std::vector<CiphertextBatch>(), false, L, a.width(),
+                                          "lowestSetBit").labels);
+}
+
+UIntBatch bitLength(const UIntBatch &a, unsigned planes)
+{
+    requirePlanes(planes, "bitLength");
+    std::vector<uint64_t> L(a.width());
+    for (unsigned r = 0; r < a.width(); ++r)
+        L[r] = a.width() - r;
+    return UIntBatch::fromPlanes(priority(rowsOf(a, true), a.width(), std::vector<CiphertextBatch>(), false, L, planes,
+                                          "bitLength").labels);
+}
+
 } // namespace certFHE

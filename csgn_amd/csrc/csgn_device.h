@@ -1,7 +1,7 @@
 // csgn_device.h -- helpers shared by the kernel translation units (csgn_mul.hip, csgn_add.hip, csgn_decrypt.hip,
 // csgn_encrypt.hip, csgn_permute.hip, csgn_compact.hip, csgn_harness.hip, and the uniform-batch families
 // csgn_gates.hip, csgn_uint.hip, csgn_uint_plain.hip, csgn_uint_addk.hip, csgn_uint_lut.hip, csgn_uint_read.hip,
-// csgn_uint_find.hip, csgn_uint_lt_select.hip, csgn_uint_decrypt.hip, csgn_matmul.hip, csgn_count.hip, csgn_wsum.hip, csgn_gather.hip):
+// csgn_uint_find.hip, csgn_uint_first.hip, csgn_uint_lt_select.hip, csgn_uint_decrypt.hip, csgn_matmul.hip, csgn_count.hip, csgn_wsum.hip, csgn_gather.hip):
 // 16-/8-byte unit access and the choice between them, the ONE and ZERO terms' units, FastDiv tables in kernel
 // arguments, the XCD-contiguous block order, CSR pair search, the LDS subset tables of DESIGN §4.15 (csgn_selector.h
 // builds the skeleton of the read, find and lt_select kernels on them), launch limits,
@@ -455,11 +455,15 @@ struct SubsetTables {
 };
 
 // The build by a 256-thread workgroup for its elements [e0, e0 + ne) of G and units [k0, k0 + kc) of a KC-unit slice
-// (dKC: KC), plane i of the elements from plane[i] on; every table is complete at the closing barrier.
+// (dKC: KC), plane i of the elements from plane[i] on, an element's term `pitch` units after the one before (0: U, a
+// plane of its own; csgn_uint_first.hip's grouped rows lie group * U apart); every table is complete at the closing
+// barrier.
 template <typename Unit>
 __device__ inline void subset_build(Unit *tab, const SubsetTables &t, const void *const *plane, u32 G, u32 KC,
-                                    const FastDiv &dKC, u32 U, u64 last_mask, u64 e0, u32 ne, u32 k0, u32 kc)
+                                    const FastDiv &dKC, u32 U, u64 last_mask, u64 e0, u32 ne, u32 k0, u32 kc,
+                                    u32 pitch = 0u)
 {
+    const u32 eu = pitch ? pitch : U;
     // entry 0 of every table is ONE; level b fills entries [2^b, 2^(b+1)) from [0, 2^b) and plane hb[k] + b
     for (u32 tb = 0; tb < t.ntab; ++tb) {
         const u32 h = t.hb[tb + 1] - t.hb[tb];
@@ -482,7 +486,7 @@ __device__ inline void subset_build(Unit *tab, const SubsetTables &t, const void
                 if (el >= ne || kk >= kc)
                     continue;
                 const u32 at = t.tbase[tb] + ((el << h) | s) * KC + kk;
-                tab[at] = tab[at - (1u << b) * KC] & p[(e0 + el) * U + k0 + kk];
+                tab[at] = tab[at - (1u << b) * KC] & p[(e0 + el) * eu + k0 + kk];
             }
         }
     }

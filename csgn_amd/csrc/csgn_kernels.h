@@ -210,6 +210,17 @@ hipError_t uint_find(u64 n_bits, u64 batch, u64 v, const u64 *const *query, cons
                      const u64 *const *keys, const u64 *u, u64 w, const u64 *const *values, const u64 *t,
                      u64 *const *out, u64 *member, hipStream_t stream);
 
+// the first row whose encrypted mask bit is set (csgn_uint_first.hip), include/csgn_hip.h's definition: F_r = n_0 * ... *
+// n_{r-1} * m_r, output j the sum, ascending in r < g, of F_r * d_{r,j}, any that of F_r, label plane i that of the F_r
+// whose public label has bit label_bits[i].  mask: one grouped batch (n_mask == 1) or g batches of `batch` elements, row
+// r of s[r] terms; values: w = 0..64 grouped planes, terms t[j]; any, label_out: nullptr / n_labels == 0 = not written.
+constexpr u32 kFirstMaxGroup = 64, kFirstMaxPlanes = 64, kFirstMaxLabels = 64;
+u64 uint_first_terms(u64 g, const u64 *s, u64 row);    // P_row, Q for row == g; 0: invalid argument or 2^62 or more
+u64 uint_first_label_terms(u64 g, const u64 *s, const u64 *labels, u64 bit);   // 0 also where no label has the bit
+hipError_t uint_first(u64 n_bits, u64 batch, u64 g, const u64 *const *mask, u64 n_mask, const u64 *s, u64 w,
+                      const u64 *const *values, const u64 *t, u64 *const *out, u64 *any, u64 n_labels,
+                      const u64 *labels, const u64 *label_bits, u64 *const *label_out, hipStream_t stream);
+
 // the product of two encrypted bit matrices over F2 (csgn_matmul.hip), include/csgn_hip.h's definition: C[i,k] is the
 // sum, ascending in e < inner, of A[i,e] * B[e,k].  A: rows * inner elements of ta terms, B: inner * cols elements of
 // tb terms (transposed: element k * inner + e), C: rows * cols elements of inner * ta * tb terms.

@@ -209,6 +209,29 @@
 // mismatched contexts, widths or counts, or a plane past 2^31 words per element; keepWhere of an empty batch gives empty
 // planes.  bitwiseRoute names the route.
 //
+// PRIORITY: firstWhere(mask, values, g) gives, of every g consecutive rows, the value of the FIRST one whose encrypted
+// mask bit is set -- the LIMIT 1 / EXISTS of a private query, first-fit, a priority encoder or arbiter; anyOf(bits, g)
+// is the OR of every g bits (a true "is there any match", where matches and member are the PARITY), firstIndex the
+// index of that row, and of an integer's own planes lowestSetIndex is find-first-set, lowestSetBit is a & -a and
+// bitLength the position of the highest set bit plus one.  All are csgn_uint_first's words (include/csgn_hip.h): with
+// n_r = logicNot(m_r),
+//     F_0 = m_0,  F_r = (((n_0 * n_1) * ...) * n_{r-1}) * m_r        exactly one F_r decrypts to 1: the first set row's
+//     firstWhere plane j     ((F_0 * d_{0,j}) + (F_1 * d_{1,j})) + ... + (F_{g-1} * d_{g-1,j}), F the LEFT operand
+//     anyOf, *any, *nonzero  (F_0 + F_1) + ... + F_{g-1}
+//     plane i of an index    the left-nested sum, ascending in r, of F_r over the rows whose PUBLIC label has bit i
+// with the labels r (firstIndex, lowestSetIndex), 1 << r (lowestSetBit: plane r is F_r itself) and width - r over the
+// planes taken from the top (bitLength).  Everything decrypts to 0 where no mask bit is set; *any tells.  A row of s_r
+// terms has P_r = s_r * prod_{i<r} (s_i + 1) entries, the stream Q = prod_r (s_r + 1) - 1: with fresh masks P_r = 2^r and
+// Q = 2^g - 1, so firstWhere over 8 fresh rows writes 255 * t terms a plane and the bit length of a fresh 16-bit integer
+// 65 535 terms in all -- the scheme's own growth, much gentler than an equality's 3^v.  A label plane that no row's label
+// reaches, or one past the labels' width, is the one-term ZERO of constantBatch.  Uniform operands (in the grouped
+// layout: of one mask term count) take ONE csgn_uint_first, one launch for every plane, *any and the label planes;
+// ragged operands (a compact() result) are composed from gather, logicNot, operator* and left-nested operator+ in the
+// definition's loop order, with the same words.  firstRoute names the route.  Every size is computed before anything
+// is allocated or launched: std::invalid_argument for a group of 0 or above 64 or one that does not divide size(),
+// mismatched contexts or counts, `planes` of 0 or above 64, or an output past 2^31 words per element.  An empty batch
+// gives empty planes.
+//
 // THE TWO ENDS.  UIntBatch::encrypt (both overloads) makes ONE block of width * count ciphertexts, lays the bit bytes
 // plane after plane in one host pass, uploads them once and runs one csgn_encrypt_keyed from stream position 0; plane j
 // is a VIEW at word j * count * dL of that block, so a plane -- also one handed on by plane(j) after the UIntBatch is
@@ -433,6 +456,27 @@ UIntBatch sumWhere(const CiphertextBatch &mask, const UIntBatch &values, uint64_
 UIntBatch mul(const UIntBatch &a, const UIntBatch &b, unsigned planes);
 // element q: the sum over the group's rows r of a[r] * b[r], modulo 2^planes
 UIntBatch innerProduct(const UIntBatch &a, const UIntBatch &b, uint64_t group, unsigned planes);
+
+
+// element q: values[q*group + r] for the first r with mask[q*group + r] set, 0 when none; *any (may be null): the OR
+UIntBatch firstWhere(const CiphertextBatch &mask, const UIntBatch &values, uint64_t group, CiphertextBatch *any = nullptr);
+CiphertextBatch firstWhere(const CiphertextBatch &mask, const CiphertextBatch &values, uint64_t group,
+                           CiphertextBatch *any = nullptr);
+// element q: the OR of bits[q*group .. q*group+group-1]
+CiphertextBatch anyOf(const CiphertextBatch &bits, uint64_t group);
+// element q: the r of the first set mask[q*group + r], modulo 2^planes (0 when none; *any tells)
+UIntBatch firstIndex(const CiphertextBatch &mask, uint64_t group, unsigned planes, CiphertextBatch *any = nullptr);
+// of an integer's own planes (the plane layout): the index of the lowest set bit modulo 2^planes (0 where a == 0;
+// *nonzero tells), a & -a, and the bit length modulo 2^planes (labels width - r over the planes taken from the top; 0
+// where a == 0)
+UIntBatch lowestSetIndex(const UIntBatch &a, unsigned planes, CiphertextBatch *nonzero = nullptr);
+UIntBatch lowestSetBit(const UIntBatch &a);
+UIntBatch bitLength(const UIntBatch &a, unsigned planes);
+// The route the seven functions above take for groups of `group` rows (an integer's planes: its width), every operand
+// uniform -- and, in the grouped layout, the mask of one term count -- or not (a static string): "call" (one
+// csgn_uint_first) or "loop" (gather, logicNot, operator* and operator+ row by row; also for a group the call would
+// refuse).  No device work; for diagnostics and tests, like arithRoute: the words are the same.
+const char *firstRoute(uint64_t group, bool uniform_operands);
 
 } // namespace certFHE
 

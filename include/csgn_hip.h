@@ -878,6 +878,58 @@ int csgn_uint_find(uint64_t n_bits, uint64_t batch, uint64_t key_width, const ui
                    const uint64_t *h_key_terms, uint64_t width, const uint64_t *const *h_values,
                    const uint64_t *h_value_terms, uint64_t *const *h_out, uint64_t *d_member, void *stream);
 
+/* ------------------------------------------------ the first row whose encrypted mask bit is set ---- */
+
+/* PRIORITY: of the `group` = g rows of an output element (g in 1..64), the value of the FIRST one whose ENCRYPTED mask
+ * bit is set -- the LIMIT 1 / EXISTS of a private query, first-fit, a priority encoder, find-first-set.
+ * Mask: bits m_0..m_{g-1} per element, row r uniform with s_r >= 1 terms.  Values, optionally: `width` planes
+ * d_0..d_{width-1} (0..64), plane j uniform with t_j terms; row r of output element e is element e * g + r of the plane
+ * (the grouped layout of csgn_count).  Labels, optionally: one PUBLIC 64-bit constant L_r per row.  A fixed composition
+ * of the reference's operator+ / operator* with ONE:
+ *     n_r    = m_r + ONE                                  (csgn_gate_uniform's NOT: m_r's terms, then ONE)
+ *     F_0    = m_0;   F_r = (((n_0 * n_1) * ...) * n_{r-1}) * m_r      (left-nested, the running product the LEFT operand)
+ *     out_j  = ((F_0 * d_{0,j}) + (F_1 * d_{1,j})) + ... + (F_{g-1} * d_{g-1,j})        (left-nested, F the LEFT operand)
+ *     any    =  (F_0 + F_1) + ... + F_{g-1}
+ *     lab_i  =  the left-nested sum, ascending in r, of F_r over the rows r with bit i of L_r set
+ * Exactly one F_r decrypts to 1 when any mask bit is set, the first; none does otherwise.  out_j decrypts to bit j of
+ * the first set row's value, any to the OR of the mask bits, lab_i to bit i of the first set row's label; all to 0 when
+ * no mask bit is set.  With L_r = r the label planes are the index of the first set row, with L_r = 1 << r the one-hot
+ * F_r themselves.
+ * Terms: P_r = s_r * prod_{i<r} (s_i + 1);  the F stream has Q = sum_r P_r = prod_r (s_r + 1) - 1 entries;
+ * T_j = Q * t_j,  T_any = Q,  T_lab_i = the sum of P_r over the rows with bit i of L_r set.  Fresh masks: P_r = 2^r,
+ * Q = 2^g - 1.
+ * Term order (decoding needs no table): row r's entries form a block of P_r entries, blocks ascending in r; entry `in`
+ * of block r has mixed-radix digits with that of m_r (base s_r) fastest, then those of n_{r-1} .. n_0 (base s_i + 1),
+ * n_0 slowest; a digit d < s_i selects term d of m_i, the digit s_i of an n_i selects ONE.  Term q * t_j + c of out_j is
+ * (entry q of the stream) & (term c of d_{r(q),j}), c fastest; any is the bare stream; lab_i is the bare stream with the
+ * blocks of the rows whose label lacks bit i left out. */
+/* P_row for row < group, Q for row == group (host only); 0 for group outside 1..64, a null pointer, a row of 0 terms,
+ * row > group or a count of 2^62 or more. */
+uint64_t csgn_uint_first_terms(uint64_t group, const uint64_t *h_mask_terms, uint64_t row);
+/* T_lab_bit (host only); 0 for the same refusals, for bit > 63 or when no label has the bit: such a plane does not
+ * exist for the C ABI, as with csgn_count's 2^j > group. */
+uint64_t csgn_uint_first_label_terms(uint64_t group, const uint64_t *h_mask_terms, const uint64_t *h_labels,
+                                     uint64_t bit);
+/* The selection over `batch` output elements.  h_mask: a HOST array of n_mask device pointers.  n_mask == 1, the
+ * grouped layout: one batch of batch * group elements, row r of element e its element e * group + r; the g counts of
+ * h_mask_terms must then be equal.  n_mask == group (>= 2), the plane layout: row r is a batch of `batch` elements of
+ * its own s_r terms -- what an integer's planes hand over.  h_values: a HOST array of `width` device pointers (plane j:
+ * batch * group * t_j * dL words, always grouped), h_out: `width` device pointers (output j: batch * T_j * dL words),
+ * d_any: batch * Q * dL words, or NULL: not computed.  h_label_bits: n_labels (0..64) strictly ascending bit indices,
+ * each naming a plane that exists; h_labels: the g constants, read only when n_labels > 0; h_label_out: n_labels device
+ * pointers (plane i: batch * T_lab * dL words).  At least one of width, d_any and n_labels asks for something.  Inputs
+ * may alias one another in any way; no output overlaps an input or another output.
+ * Checks, the first that fails giving the status, all before any device call: n_bits; group, n_mask, width, n_labels
+ * and nothing asked for; host pointers; term counts, label bits and the grouped layout's counts (CSGN_ERR_INVALID);
+ * every output's T * dL below 2^31 words per element and batch * that < 2^60 (CSGN_ERR_UNSUPPORTED); null device
+ * pointers (CSGN_ERR_INVALID; not read when batch == 0); the device (CSGN_ERR_NO_DEVICE, no CPU fallback).  batch == 0
+ * succeeds.  On the caller's stream, asynchronous, no scratch, graph-capturable: ONE launch of k_uint_first, split by
+ * elements only at knob "launch_blocks" and at the HIP grid limit. */
+int csgn_uint_first(uint64_t n_bits, uint64_t batch, uint64_t group, const uint64_t *const *h_mask, uint64_t n_mask,
+                    const uint64_t *h_mask_terms, uint64_t width, const uint64_t *const *h_values,
+                    const uint64_t *h_value_terms, uint64_t *const *h_out, uint64_t *d_any, uint64_t n_labels,
+                    const uint64_t *h_labels, const uint64_t *h_label_bits, uint64_t *const *h_label_out, void *stream);
+
 /* ------------------------------------------------ selection by an encrypted comparison ---- */
 
 /* min, max and compare-exchange of ENCRYPTED integers: every output selected by the ENCRYPTED comparison a < b, the
