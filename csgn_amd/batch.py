@@ -430,6 +430,42 @@ class HipPath:
                 None if any is None else any[: batch * Q * dl],
                 [o[: batch * x * dl] for o, x in zip(label_outs, T)])
 
+    def uint_nth(self, n_bits: int, batch: int, group: int, slot: int, mask, mask_terms: int, values=(), value_terms=(),
+                 outs=None, valid=False, labels=None, label_bits=(), label_outs=None):
+        """csgn_uint_nth: of the `group` rows of every output element the (slot + 1)-th whose encrypted mask bit is set.
+        `mask`: one grouped tensor of batch * group elements or `group` tensors of `batch` elements, every row of
+        `mask_terms` terms; `values`: grouped planes, plane j uniform with value_terms[j] terms; `labels`: the rows'
+        public constants, `label_bits` the strictly ascending planes of them to write.  Returns (output tensors, valid
+        tensor or None, label tensors): output j of Q * value_terms[j] terms per element (Q = csgn_uint_nth_terms(group,
+        mask_terms, slot, group)), valid of Q, label plane i of csgn_uint_nth_label_terms; fresh ones unless `outs` /
+        `label_outs` are given; `valid`: True for a fresh tensor, or the tensor to write."""
+        g, s, tm, w, nl = int(group), int(slot), int(mask_terms), len(values), len(label_bits)
+        assert len(mask) in (1, g) and w == len(value_terms)
+        h_t = (C.c_uint64 * max(w, 1))(*[int(t) for t in value_terms])
+        h_l = (C.c_uint64 * max(g, 1))(*[int(x) for x in (labels if nl else [0] * g)])
+        h_b = (C.c_uint64 * max(nl, 1))(*[int(x) for x in label_bits])
+        Q = int(self.lib.csgn_uint_nth_terms(g, tm, s, g))
+        T = [int(self.lib.csgn_uint_nth_label_terms(g, tm, s, h_l, int(x))) for x in label_bits]
+        assert Q and all(T), "bad group, slot, term count or label plane"
+        dl = self.default_len(n_bits)
+        if outs is None:
+            outs = [self.empty_words(max(batch * int(t) * Q * dl, 1)) for t in value_terms]
+        if label_outs is None:
+            label_outs = [self.empty_words(max(batch * x * dl, 1)) for x in T]
+        if valid is True:
+            valid = self.empty_words(max(batch * Q * dl, 1))
+        elif valid is False:
+            valid = None
+        h_m = (C.c_void_p * len(mask))(*[_ptr(p) for p in mask])
+        h_d = (C.c_void_p * max(w, 1))(*[_ptr(p) for p in values])
+        h_out = (C.c_void_p * max(w, 1))(*[_ptr(o) for o in outs])
+        h_lo = (C.c_void_p * max(nl, 1))(*[_ptr(o) for o in label_outs])
+        check(self.lib.csgn_uint_nth(n_bits, batch, g, s, h_m, len(mask), tm, w, h_d, h_t, h_out, _ptr(valid), nl, h_l,
+                                     h_b, h_lo, self.stream))
+        return ([o[: batch * int(t) * Q * dl] for o, t in zip(outs, value_terms)],
+                None if valid is None else valid[: batch * Q * dl],
+                [o[: batch * x * dl] for o, x in zip(label_outs, T)])
+
     def uint_pick(self, n_bits: int, op: int, batch: int, index, index_terms, a, terms: int, rows: int = 0, outs=None):
         """csgn_uint_pick: the encrypted integer `a` (bit 0 first; every plane a uniform batch of `terms` terms)
         shifted or rotated by the encrypted distance `index` (plane k a uniform batch of index_terms[k] terms), op =

@@ -161,6 +161,10 @@ SIGNATURES = {
     "csgn_uint_first_label_terms": (u64, [u64, C.POINTER(u64), C.POINTER(u64), u64]),
     "csgn_uint_first": (C.c_int, [u64, u64, u64, C.POINTER(vp), u64, C.POINTER(u64), u64, C.POINTER(vp), C.POINTER(u64),
                                   C.POINTER(vp), vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(vp), vp]),
+    "csgn_uint_nth_terms": (u64, [u64, u64, u64, u64]),
+    "csgn_uint_nth_label_terms": (u64, [u64, u64, u64, C.POINTER(u64), u64]),
+    "csgn_uint_nth": (C.c_int, [u64, u64, u64, u64, C.POINTER(vp), u64, u64, u64, C.POINTER(vp), C.POINTER(u64),
+                                C.POINTER(vp), vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(vp), vp]),
     "csgn_uint_lt_terms": (u64, [u64, C.POINTER(u64), C.POINTER(u64)]),
     "csgn_uint_pick_terms": (u64, [C.c_int, u64, C.POINTER(u64), u64, u64, u64]),
     "csgn_uint_pick_kernel": (C.c_char_p, [u64, C.c_int, u64, u64, C.POINTER(u64), u64, u64, u64]),

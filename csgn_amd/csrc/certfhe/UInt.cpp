@@ -2394,4 +2394,252 @@ UIntBatch bitLength(const UIntBatch &a, unsigned planes)
                                           "bitLength").labels);
 }
 
+// ------------------------------------------------------------------ the k-th row whose mask bit is set
+
+namespace {
+
+// Per shape (measured): the call for every group it takes.
+bool nthCall(uint64_t group, bool uniform_operands) { return uniform_operands && group >= 1 && group <= 64; }
+
+// Of every element's `group` rows the (slot + 1)-th whose mask bit is set: its value planes, with want_valid "more than
+// slot bits are set" and, with label_planes, planes 0 .. label_planes - 1 of its public label (Priority's any holds
+// valid).  mask: one batch, the grouped layout, or `group` batches of one element count, the plane layout; values:
+// grouped.  Every size first (check_only: nothing else); then ONE csgn_uint_nth for uniform operands of one mask term
+// count, else the definition through the batch operators.
+Priority selectNth(const std::vector<CiphertextBatch> &mask, uint64_t group, uint64_t slot,
+                   const std::vector<CiphertextBatch> &values, bool want_valid, const std::vector<uint64_t> &labels,
+                   unsigned label_planes, const char *who, bool check_only = false)
+{
+    const std::string name = std::string("certFHE::") + who;
+    const Context &ctx = mask[0].context();
+    const bool grouped = mask.size() == 1;
+    if (group == 0 || group > 64 || (grouped && mask[0].size() % group != 0))
+        throw std::invalid_argument(name + ": groups of " + std::to_string(group) + " (1..64) in a batch of " +
+                                    std::to_string(mask[0].size()));
+    if (slot >= group)
+        throw std::invalid_argument(name + ": slot " + std::to_string(slot) + " of a group of " + std::to_string(group));
+    const uint64_t count = grouped ? mask[0].size() / group : mask[0].size();
+    for (size_t r = 0; r < mask.size(); ++r)
+        if (!sameContext(mask[r].context(), ctx) || mask[r].size() != mask[0].size())
+            throw std::invalid_argument(name + ": the mask rows differ in count or context");
+    for (size_t j = 0; j < values.size(); ++j)
+        if (!sameContext(values[j].context(), ctx) || values[j].size() != count * group)
+            throw std::invalid_argument(name + ": the values differ from the mask in count or context");
+    Priority out;
+    if (count == 0) {
+        out.values = emptyPlanes(ctx, values.size());
+        out.any = emptyPlanes(ctx, want_valid ? 1 : 0);
+        out.labels = emptyPlanes(ctx, label_planes);
+        return out;
+    }
+    // sizes, from the largest term count of any row and of a ragged operand: a bound for every element
+    const Planes pm(mask), pv(values);
+    uint64_t tm = 1;
+    bool one_t = true;
+    for (size_t r = 0; r < mask.size(); ++r) {
+        tm = std::max(tm, pm.terms[r]);
+        one_t = one_t && pm.terms[r] == pm.terms[0];
+    }
+    const std::string too_large = name + ": an output exceeds 2^31 words per element (the group is too large for the "
+                                         "slot or the mask has too many terms)";
+    const uint64_t Q = csgn_uint_nth_terms(group, tm, slot, group);
+    if (Q == 0 || Q >= kMaxWords)
+        throw std::invalid_argument(too_large);
+    checked(Q, ctx, who);                                       // the stream itself, whatever is asked for
+    std::vector<uint64_t> T(values.size() + (want_valid ? 1 : 0)), Tlab, bits;
+    for (size_t j = 0; j < T.size(); ++j) {
+        const uint64_t tj = j < values.size() ? std::max<uint64_t>(pv.terms[j], 1) : 1;
+        if (tj > kMaxWords / Q)
+            throw std::invalid_argument(too_large);
+        T[j] = checked(tj * Q, ctx, who);
+    }
+    std::vector<size_t> at;                                     // the label planes that exist
+    for (unsigned i = 0; i < label_planes; ++i) {
+        bool reached = false;
+        for (uint64_t r = slot; r < group; ++r)
+            reached = reached || ((labels[r] >> i) & 1u);
+        if (!reached)
+            continue;
+        const uint64_t Ti = csgn_uint_nth_label_terms(group, tm, slot, labels.data(), i);
+        if (Ti == 0 || Ti >= kMaxWords)
+            throw std::invalid_argument(too_large);
+        Tlab.push_back(checked(Ti, ctx, who));
+        bits.push_back(i);
+        at.push_back(i);
+    }
+    if (check_only)
+        return out;
+    out.labels.assign(label_planes, constantBatch(ctx, std::vector<unsigned char>(count, 0)));
+    if (nthCall(group, pm.uniform && pv.uniform && one_t)) {
+        std::vector<CiphertextBatch> made = makePlanes(ctx, count, T), lab = makePlanes(ctx, count, Tlab);
+        std::vector<uint64_t *> dst = wordsOf(made);
+        uint64_t *valid = want_valid ? dst.back() : nullptr;
+        if (!T.empty() || !Tlab.empty())
+            detail::check(csgn_uint_nth(ctx.getN(), count, group, slot, sources(pm).data(), mask.size(), tm, values.size(),
+                                        sources(pv).data(), pv.terms.data(), dst.data(), valid, bits.size(), labels.data(),
+                                        bits.data(), wordsOf(lab).data(), detail::stream()),
+                          "csgn_uint_nth");
+        if (want_valid) {
+            out.any.push_back(made.back());
+            made.pop_back();
+        }
+        out.values = made;
+        for (size_t k = 0; k < at.size(); ++k)
+            out.labels[at[k]] = lab[k];
+        return out;
+    }
+    // ragged operands or rows of different term counts: the definition itself through the batch operators
+    std::vector<CiphertextBatch> rows;                          // m_r
+    std::vector<uint64_t> idx(count);
+    for (uint64_t r = 0; r < group; ++r) {
+        for (uint64_t q = 0; q < count; ++q)
+            idx[q] = q * group + r;
+        rows.push_back(grouped ? mask[0].gather(idx) : mask[r]);
+    }
+    std::vector<CiphertextBatch> lab(at.size(), mask[0]);
+    std::vector<bool> started(at.size(), false);
+    bool first_row = true;
+    for (uint64_t r = slot; r < group; ++r, first_row = false) {
+        CiphertextBatch G = rows[r];
+        bool first_term = true;
+        for (uint64_t d = slot; d <= r; ++d) {
+            if ((slot & ~d) != 0)                               // C(d, slot) is even
+                continue;
+            std::vector<uint64_t> sub(d);                       // the d-subsets of the rows below r, lexicographic
+            for (uint64_t k = 0; k < d; ++k)
+                sub[k] = k;
+            for (bool more = true; more;) {
+                CiphertextBatch p = d == 0 ? rows[r] : rows[sub[0]];
+                for (uint64_t k = 1; k < d; ++k)
+                    p = p * rows[sub[k]];
+                if (d != 0)
+                    p = p * rows[r];
+                G = first_term ? p : G + p;
+                first_term = false;
+                more = false;
+                for (uint64_t k = d; k-- > 0;)
+                    if (sub[k] != r - d + k) {                  // the last position that can still move up
+                        ++sub[k];
+                        for (uint64_t i = k + 1; i < d; ++i)
+                            sub[i] = sub[i - 1] + 1;
+                        more = true;
+                        break;
+                    }
+            }
+        }
+        for (uint64_t q = 0; q < count; ++q)
+            idx[q] = q * group + r;
+        for (size_t j = 0; j < values.size(); ++j) {
+            const CiphertextBatch p = G * values[j].gather(idx);
+            if (first_row)
+                out.values.push_back(p);
+            else
+                out.values[j] = out.values[j] + p;
+        }
+        if (want_valid) {
+            if (first_row)
+                out.any.push_back(G);
+            else
+                out.any[0] = out.any[0] + G;
+        }
+        for (size_t k = 0; k < at.size(); ++k) {
+            if (!((labels[r] >> at[k]) & 1u))
+                continue;
+            lab[k] = started[k] ? lab[k] + G : G;
+            started[k] = true;
+        }
+    }
+    for (size_t k = 0; k < at.size(); ++k)
+        out.labels[at[k]] = lab[k];
+    return out;
+}
+
+} // namespace
+
+const char *nthRoute(uint64_t group, bool uniform_operands) { return nthCall(group, uniform_operands) ? "call" : "loop"; }
+
+UIntBatch nthWhere(const CiphertextBatch &mask, const UIntBatch &values, uint64_t group, uint64_t slot, CiphertextBatch *valid)
+{
+    const Priority p = selectNth(std::vector<CiphertextBatch>(1, mask), group, slot, planesOf(values), valid != nullptr,
+                                 std::vector<uint64_t>(), 0, "nthWhere");
+    if (valid)
+        *valid = p.any[0];
+    return UIntBatch::fromPlanes(p.values);
+}
+
+CiphertextBatch nthWhere(const CiphertextBatch &mask, const CiphertextBatch &values, uint64_t group, uint64_t slot,
+                         CiphertextBatch *valid)
+{
+    const Priority p = selectNth(std::vector<CiphertextBatch>(1, mask), group, slot, std::vector<CiphertextBatch>(1, values),
+                                 valid != nullptr, std::vector<uint64_t>(), 0, "nthWhere");
+    if (valid)
+        *valid = p.any[0];
+    return p.values[0];
+}
+
+std::vector<UIntBatch> takeWhere(const CiphertextBatch &mask, const UIntBatch &values, uint64_t group, uint64_t k,
+                                 std::vector<CiphertextBatch> *valid)
+{
+    if (k == 0 || k > group)
+        throw std::invalid_argument("certFHE::takeWhere: " + std::to_string(k) + " rows of groups of " +
+                                    std::to_string(group));
+    const std::vector<CiphertextBatch> m(1, mask), v = planesOf(values);
+    for (uint64_t s = 0; s < k; ++s)                            // every slot's sizes before the first launch
+        selectNth(m, group, s, v, valid != nullptr, std::vector<uint64_t>(), 0, "takeWhere", true);
+    std::vector<UIntBatch> out;
+    if (valid)
+        valid->clear();
+    for (uint64_t s = 0; s < k; ++s) {
+        const Priority p = selectNth(m, group, s, v, valid != nullptr, std::vector<uint64_t>(), 0, "takeWhere");
+        out.push_back(UIntBatch::fromPlanes(p.values));
+        if (valid)
+            valid->push_back(p.any[0]);
+    }
+    return out;
+}
+
+UIntBatch nthIndex(const CiphertextBatch &mask, uint64_t group, uint64_t slot, unsigned planes, CiphertextBatch *valid)
+{
+    requirePlanes(planes, "nthIndex");
+    const Priority p = selectNth(std::vector<CiphertextBatch>(1, mask), group, slot, std::vector<CiphertextBatch>(),
+                                 valid != nullptr, indexLabels(std::min<uint64_t>(group, 64)), planes, "nthIndex");
+    if (valid)
+        *valid = p.any[0];
+    return UIntBatch::fromPlanes(p.labels);
+}
+
+UIntBatch nthSetIndex(const UIntBatch &a, uint64_t slot, unsigned planes, CiphertextBatch *valid)
+{
+    requirePlanes(planes, "nthSetIndex");
+    const Priority p = selectNth(rowsOf(a, false), a.width(), slot, std::vector<CiphertextBatch>(), valid != nullptr,
+                                 indexLabels(a.width()), planes, "nthSetIndex");
+    if (valid)
+        *valid = p.any[0];
+    return UIntBatch::fromPlanes(p.labels);
+}
+
+CiphertextBatch atLeast(const CiphertextBatch &bits, uint64_t group, uint64_t k)
+{
+    const std::vector<CiphertextBatch> m(1, bits);
+    if (k == 0 || k > group) {                                  // a public answer: ONE, or ZERO; the group is still checked
+        if (group == 0 || group > 64 || bits.size() % group != 0)
+            throw std::invalid_argument("certFHE::atLeast: groups of " + std::to_string(group) + " (1..64) in a batch of " +
+                                        std::to_string(bits.size()));
+        if (bits.size() == 0)
+            return emptyPlanes(bits.context(), 1)[0];
+        return constantBatch(bits.context(), std::vector<unsigned char>(bits.size() / group, k == 0 ? 1 : 0));
+    }
+    return selectNth(m, group, k - 1, std::vector<CiphertextBatch>(), true, std::vector<uint64_t>(), 0, "atLeast").any[0];
+}
+
+CiphertextBatch popcountAtLeast(const UIntBatch &a, uint64_t k)
+{
+    if (a.size() == 0)
+        return emptyPlanes(a.context(), 1)[0];
+    if (k == 0 || k > a.width())
+        return constantBatch(a.context(), std::vector<unsigned char>(a.size(), k == 0 ? 1 : 0));
+    return selectNth(rowsOf(a, false), a.width(), k - 1, std::vector<CiphertextBatch>(), true, std::vector<uint64_t>(), 0,
+                     "popcountAtLeast").any[0];
+}
+
 } // namespace certFHE

@@ -1790,6 +1790,83 @@ int csgn_uint_first(uint64_t n_bits, uint64_t batch, uint64_t group, const uint6
     return CSGN_OK;
 }
 
+/* ------------------------------------------------ the k-th row whose encrypted mask bit is set ---- */
+
+uint64_t csgn_uint_nth_terms(uint64_t group, uint64_t t_mask, uint64_t slot, uint64_t row)
+{
+    return csgn::uint_nth_terms(group, t_mask, slot, row);
+}
+
+uint64_t csgn_uint_nth_label_terms(uint64_t group, uint64_t t_mask, uint64_t slot, const uint64_t *h_labels, uint64_t bit)
+{
+    return csgn::uint_nth_label_terms(group, t_mask, slot, (const u64 *)h_labels, bit);
+}
+
+int csgn_uint_nth(uint64_t n_bits, uint64_t batch, uint64_t group, uint64_t slot, const uint64_t *const *h_mask,
+                  uint64_t n_mask, uint64_t t_mask, uint64_t width, const uint64_t *const *h_values,
+                  const uint64_t *h_value_terms, uint64_t *const *h_out, uint64_t *d_valid, uint64_t n_labels,
+                  const uint64_t *h_labels, const uint64_t *h_label_bits, uint64_t *const *h_label_out, void *stream)
+{
+    if (int rc = check_n(n_bits))
+        return rc;
+    REQUIRE(group >= 1 && group <= csgn::kNthMaxGroup, "nth: group %llu outside 1..64", (unsigned long long)group);
+    REQUIRE(slot < group, "nth: slot %llu of a group of %llu", (unsigned long long)slot, (unsigned long long)group);
+    REQUIRE(n_mask == 1 || (n_mask == group && group >= 2), "nth: %llu mask batches for a group of %llu (1 or the group)",
+            (unsigned long long)n_mask, (unsigned long long)group);
+    REQUIRE(width <= csgn::kNthMaxPlanes, "nth: value width %llu outside 0..64", (unsigned long long)width);
+    REQUIRE(n_labels <= csgn::kNthMaxLabels, "nth: %llu label planes outside 0..64", (unsigned long long)n_labels);
+    REQUIRE(width >= 1 || d_valid || n_labels >= 1, "nth: no value planes, no valid output and no label planes");
+    REQUIRE(h_mask, "null host pointer");
+    REQUIRE(width == 0 || (h_values && h_value_terms && h_out), "null host pointer");
+    REQUIRE(n_labels == 0 || (h_labels && h_label_bits && h_label_out), "null host pointer");
+    REQUIRE(t_mask != 0 && t_mask < (1ull << 62), "nth: the mask rows have no terms, or too many");
+    const uint64_t Q = csgn::uint_nth_terms(group, t_mask, slot, group);
+    REQUIRE(Q != 0, "nth: the term count overflows");
+    for (uint64_t j = 0; j < width; ++j)
+        REQUIRE(h_value_terms[j] != 0, "nth: value plane %llu has no terms", (unsigned long long)j);
+    for (uint64_t i = 0; i < n_labels; ++i) {
+        REQUIRE(h_label_bits[i] <= 63 && (i == 0 || h_label_bits[i] > h_label_bits[i - 1]),
+                "nth: label bits must be strictly ascending and below 64 (plane %llu)", (unsigned long long)i);
+        REQUIRE(csgn::uint_nth_label_terms(group, t_mask, slot, (const u64 *)h_labels, h_label_bits[i]) != 0,
+                "nth: no row from the slot on has label bit %llu, or the plane's term count overflows",
+                (unsigned long long)h_label_bits[i]);
+    }
+    const uint64_t dl = csgn_default_len(n_bits);
+    /* the stream itself, which the kernel indexes in 32 bits whatever is asked for, then every output */
+    if (int rc = check_size(batch, Q, Q, dl, "nth: the selector stream"))
+        return rc;
+    for (uint64_t j = 0; j < width + (d_valid ? 1 : 0); ++j) {
+        unsigned long long terms;                            // of output j; the last is valid's
+        if (__builtin_mul_overflow((unsigned long long)Q, (unsigned long long)(j < width ? h_value_terms[j] : 1), &terms))
+            terms = ~0ull;
+        if (int rc = check_size(batch, terms, terms, dl, j < width ? "nth: output %llu" : "nth: valid",
+                                (unsigned long long)j))
+            return rc;
+    }
+    for (uint64_t i = 0; i < n_labels; ++i) {
+        const uint64_t terms = csgn::uint_nth_label_terms(group, t_mask, slot, (const u64 *)h_labels, h_label_bits[i]);
+        if (int rc = check_size(batch, terms, terms, dl, "nth: label plane %llu", (unsigned long long)h_label_bits[i]))
+            return rc;
+    }
+    if (batch != 0) {
+        if (int rc = check_planes(h_mask, nullptr, n_mask, "mask"))
+            return rc;
+        if (int rc = check_planes(h_values, h_out, width, "value plane or output"))
+            return rc;
+        if (int rc = check_planes(h_label_out, nullptr, n_labels, "label output"))
+            return rc;
+    }
+    if (int rc = require_device("csgn_uint_nth"))
+        return rc;
+    if (batch == 0)
+        return CSGN_OK;
+    HIP_TRY(csgn::uint_nth(n_bits, batch, group, slot, (const u64 *const *)h_mask, n_mask, t_mask, width,
+                           (const u64 *const *)h_values, (const u64 *)h_value_terms, (u64 *const *)h_out, (u64 *)d_valid,
+                           n_labels, (const u64 *)h_labels, (const u64 *)h_label_bits, (u64 *const *)h_label_out,
+                           S(stream)));
+    return CSGN_OK;
+}
+
 /* ------------------------------------------------ selection by an encrypted comparison ---- */
 
 uint64_t csgn_uint_lt_terms(uint64_t width, const uint64_t *h_a_terms, const uint64_t *h_b_terms)

@@ -221,6 +221,19 @@ hipError_t uint_first(u64 n_bits, u64 batch, u64 g, const u64 *const *mask, u64 
                       const u64 *const *values, const u64 *t, u64 *const *out, u64 *any, u64 n_labels,
                       const u64 *labels, const u64 *label_bits, u64 *const *label_out, hipStream_t stream);
 
+// the (slot + 1)-th row whose encrypted mask bit is set (csgn_uint_nth.hip), include/csgn_hip.h's definition: G_{r,s} the
+// sum over d in s..r with C(d, s) odd and the d-subsets of the rows below r, lexicographic, of m_{i_1} * ... * m_{i_d} *
+// m_r; output j the sum, ascending in r, of G_{r,s} * d_{r,j}, valid that of G_{r,s}, label plane i that of the G_{r,s}
+// whose public label has bit label_bits[i].  mask: one grouped batch (n_mask == 1) or g batches of `batch` elements,
+// every row of tm terms; values: w = 0..64 grouped planes, terms t[j]; valid, label_out: nullptr / n_labels == 0 = not
+// written.
+constexpr u32 kNthMaxGroup = 64, kNthMaxPlanes = 64, kNthMaxLabels = 64;
+u64 uint_nth_terms(u64 g, u64 t, u64 slot, u64 row);    // P_{row,slot}, Q_slot for row == g; 0: invalid or 2^62 or more
+u64 uint_nth_label_terms(u64 g, u64 t, u64 slot, const u64 *labels, u64 bit);   // 0 also where no row >= slot has the bit
+hipError_t uint_nth(u64 n_bits, u64 batch, u64 g, u64 slot, const u64 *const *mask, u64 n_mask, u64 tm, u64 w,
+                    const u64 *const *values, const u64 *t, u64 *const *out, u64 *valid, u64 n_labels, const u64 *labels,
+                    const u64 *label_bits, u64 *const *label_out, hipStream_t stream);
+
 // the product of two encrypted bit matrices over F2 (csgn_matmul.hip), include/csgn_hip.h's definition: C[i,k] is the
 // sum, ascending in e < inner, of A[i,e] * B[e,k].  A: rows * inner elements of ta terms, B: inner * cols elements of
 // tb terms (transposed: element k * inner + e), C: rows * cols elements of inner * ta * tb terms.

@@ -1,6 +1,6 @@
 // csgn_selector.h -- the skeleton of the selector-stream kernels (csgn_uint_read.hip, csgn_uint_find.hip,
-// csgn_uint_lt_select.hip, csgn_uint_pick.hip, csgn_uint_pick_rows.hip, csgn_uint_write.hip, csgn_uint_first.hip;
-// DESIGN.md §4.23; csgn_uint_arith.hip takes the tile, the LDS layout, the launches and eq_digits, §4.28).  Internal
+// csgn_uint_lt_select.hip, csgn_uint_pick.hip, csgn_uint_pick_rows.hip, csgn_uint_write.hip, csgn_uint_first.hip,
+// csgn_uint_nth.hip; csgn_uint_arith.hip takes the tile, the LDS layout, the launches and eq_digits, §4.28).  Internal
 // linkage, like csgn_device.h.
 //
 // An encrypted SELECTOR STREAM (the EQ rows of an index, the EQ of a key row and a query, the terms of lessThan) is the

@@ -232,6 +232,34 @@
 // mismatched contexts or counts, `planes` of 0 or above 64, or an output past 2^31 words per element.  An empty batch
 // gives empty planes.
 //
+// SELECTION BY RANK: nthWhere(mask, values, g, s) gives, of every g consecutive rows, the value of the (s + 1)-th one
+// whose encrypted mask bit is set -- LIMIT k / OFFSET s of a private query, the oblivious compaction of the matching
+// rows to the front (takeWhere: slots 0 .. k-1), select_k on a bit vector; nthIndex is the index of that row and
+// nthSetIndex the position of the (s + 1)-th set bit of an integer; atLeast(bits, g, k) is "at least k of every g bits
+// are set" -- HAVING COUNT(*) >= k, k-of-n voting -- without the count planes and the comparison that countOnes and
+// lessThan would spend on it, and popcountAtLeast(a ^ b, k) the Hamming-distance threshold (hammingDistance(a, b) <= r
+// is logicNot(popcountAtLeast(a ^ b, r + 1))).  All are csgn_uint_nth's words (include/csgn_hip.h): with [x] for "x is
+// odd", for a row r >= s
+//     G_{r,s} = the left-nested sum, over d ascending in s..r with [C(d, s)] and over the d-subsets i_1 < ... < i_d of
+//               the rows below r in lexicographic order, of (((m_{i_1} * m_{i_2}) * ...) * m_{i_d}) * m_r
+//     nthWhere plane j     ((G_{s,s} * d_{s,j}) + (G_{s+1,s} * d_{s+1,j})) + ... + (G_{g-1,s} * d_{g-1,j}), G the LEFT operand
+//     atLeast, *valid      (G_{s,s} + G_{s+1,s}) + ... + G_{g-1,s}                     (atLeast(bits, g, k): s = k - 1)
+//     plane i of an index  the left-nested sum, ascending in r >= s, of G_{r,s} over the rows whose PUBLIC label has bit i
+// ("exactly s of the rows above r are set" is symmetric, so its ANF is the sum of the elementary symmetric polynomials
+// e_d with [C(d, s)]).  Exactly one G_{r,s} decrypts to 1 when more than s mask bits are set: the (s + 1)-th set row's;
+// everything decrypts to 0 otherwise, and *valid tells.  Every row has the same t terms in one call; the stream has
+// Q_s = sum over d with [C(d, s)] of C(g, d+1) * t^(d+1) entries: fresh masks of 8 rows give 255, 127, 135, 71, 93, 29,
+// 9, 1 for s = 0..7, Q_0 = 2^g - 1 is firstWhere's count, and the HIGH slots of wide groups stay small (65 entries for
+// the 63rd set bit of a fresh 64-bit integer) while the low slots of wide groups are past any memory and are refused.
+// atLeast(bits, g, 0) is the one-term ONE and atLeast(bits, g, k > g) the one-term ZERO of constantBatch, as is a label
+// plane no row from the slot on reaches.  Uniform operands whose mask rows have one term count take ONE csgn_uint_nth
+// per slot, one launch for every plane, *valid and the label planes; ragged operands (a compact() result) and rows of
+// different term counts are composed from gather, operator* and left-nested operator+ in the definition's loop order,
+// with the same words.  nthRoute names the route.  Every size is computed before anything is allocated or launched:
+// std::invalid_argument for a group of 0 or above 64 or one that does not divide size(), slot >= group, a k of
+// takeWhere of 0 or above the group, `planes` of 0 or above 64, mismatched contexts or counts, or an output past 2^31
+// words per element.  An empty batch gives empty planes.
+//
 // THE TWO ENDS.  UIntBatch::encrypt (both overloads) makes ONE block of width * count ciphertexts, lays the bit bytes
 // plane after plane in one host pass, uploads them once and runs one csgn_encrypt_keyed from stream position 0; plane j
 // is a VIEW at word j * count * dL of that block, so a plane -- also one handed on by plane(j) after the UIntBatch is
@@ -477,6 +505,30 @@ UIntBatch bitLength(const UIntBatch &a, unsigned planes);
 // csgn_uint_first) or "loop" (gather, logicNot, operator* and operator+ row by row; also for a group the call would
 // refuse).  No device work; for diagnostics and tests, like arithRoute: the words are the same.
 const char *firstRoute(uint64_t group, bool uniform_operands);
+
+// element q: values[q*group + r] for the (slot + 1)-th r with mask[q*group + r] set, 0 when at most `slot` are; *valid
+// (may be null): more than `slot` are set
+UIntBatch nthWhere(const CiphertextBatch &mask, const UIntBatch &values, uint64_t group, uint64_t slot,
+                   CiphertextBatch *valid = nullptr);
+CiphertextBatch nthWhere(const CiphertextBatch &mask, const CiphertextBatch &values, uint64_t group, uint64_t slot,
+                         CiphertextBatch *valid = nullptr);
+// slots 0 .. k-1 (k in 1..group; one call a slot): the matching rows compacted to the front, in order; (*valid)[s]
+std::vector<UIntBatch> takeWhere(const CiphertextBatch &mask, const UIntBatch &values, uint64_t group, uint64_t k,
+                                 std::vector<CiphertextBatch> *valid = nullptr);
+// element q: the r of the (slot + 1)-th set mask[q*group + r], modulo 2^planes (0 when there is none; *valid tells)
+UIntBatch nthIndex(const CiphertextBatch &mask, uint64_t group, uint64_t slot, unsigned planes,
+                   CiphertextBatch *valid = nullptr);
+// of an integer's own planes (the plane layout): the position of the (slot + 1)-th set bit, modulo 2^planes
+UIntBatch nthSetIndex(const UIntBatch &a, uint64_t slot, unsigned planes, CiphertextBatch *valid = nullptr);
+// element q: at least k of bits[q*group .. q*group+group-1] are set (*valid of slot k - 1; k == 0: ONE; k > group: ZERO)
+CiphertextBatch atLeast(const CiphertextBatch &bits, uint64_t group, uint64_t k);
+// at least k of a's bits are set (the plane layout); hammingDistance(a, b) <= r is logicNot(popcountAtLeast(a ^ b, r + 1))
+CiphertextBatch popcountAtLeast(const UIntBatch &a, uint64_t k);
+// The route the seven functions above take for groups of `group` rows (an integer's planes: its width), every operand
+// uniform and the mask rows of one term count, or not (a static string): "call" (one csgn_uint_nth a slot) or "loop"
+// (gather, operator* and operator+ subset by subset; also for a group the call would refuse).  No device work; for
+// diagnostics and tests, like firstRoute: the words are the same.
+const char *nthRoute(uint64_t group, bool uniform_operands);
 
 } // namespace certFHE
 

@@ -930,6 +930,66 @@ int csgn_uint_first(uint64_t n_bits, uint64_t batch, uint64_t group, const uint6
                     const uint64_t *h_value_terms, uint64_t *const *h_out, uint64_t *d_any, uint64_t n_labels,
                     const uint64_t *h_labels, const uint64_t *h_label_bits, uint64_t *const *h_label_out, void *stream);
 
+/* ------------------------------------------------ the k-th row whose encrypted mask bit is set ---- */
+
+/* SELECT: of the `group` = g rows of an output element (g in 1..64), the value of the (slot + 1)-th one whose ENCRYPTED
+ * mask bit is set -- LIMIT k / OFFSET s of a private query, oblivious compaction of the matching rows to the front,
+ * select_k on a bit vector -- and "at least slot + 1 of these bits are set": HAVING COUNT(*) >= k, k-of-n voting, a
+ * Hamming-distance threshold.
+ * Mask: bits m_0..m_{g-1} per element, EVERY row uniform with the same t >= 1 terms (as in csgn_count: the digit blocks
+ * have one size).  Values, optionally: `width` planes d_0..d_{width-1} (0..64), plane j uniform with t_j terms; row r of
+ * output element e is element e * g + r of the plane (the grouped layout of csgn_uint_first).  Labels, optionally: one
+ * PUBLIC 64-bit constant L_r per row.  Slot s: public, 0-based, s < g.  Write [x] for "x is odd".  A fixed composition of
+ * the reference's operator+ / operator*: for a row r >= s
+ *     G_{r,s} = the left-nested sum, over d ascending in s..r with [C(d, s)],
+ *               over the d-subsets i_1 < ... < i_d of {0..r-1} in lexicographic order (csgn_count's order),
+ *               of ((((m_{i_1} * m_{i_2}) * ...) * m_{i_d}) * m_r)          (d = 0, which only s = 0 has: m_r alone)
+ *     out_j   = ((G_{s,s} * d_{s,j}) + (G_{s+1,s} * d_{s+1,j})) + ... + (G_{g-1,s} * d_{g-1,j})     G the LEFT operand
+ *     valid   =  (G_{s,s} + G_{s+1,s}) + ... + G_{g-1,s}
+ *     lab_i   =  the left-nested sum, ascending in r >= s, of G_{r,s} over the rows with bit i of L_r set
+ * "Exactly s of the r rows above are set" is a symmetric function, so its ANF is a sum of elementary symmetric
+ * polynomials e_d, the ones with [C(d, s)]; G_{r,s} multiplies it by m_r.  Exactly one G_{r,s} decrypts to 1 when more
+ * than s mask bits are set, and r is then the (s + 1)-th set row; none does otherwise.  out_j decrypts to bit j of that
+ * row's value, valid to "at least s + 1 bits are set" (every monomial has a unique largest row, so valid is the minimal
+ * ANF of that threshold), lab_i to bit i of that row's label; all to 0 when at most s bits are set.
+ * Terms: P_{r,s} = sum over d in s..r with [C(d, s)] of C(r, d) * t^(d+1);  the G stream has Q_s = sum_r P_{r,s} = sum
+ * over d of [C(d, s)] * C(g, d+1) * t^(d+1) entries;  T_j = Q_s * t_j,  T_valid = Q_s,  T_lab_i = the sum of P_{r,s} over
+ * the rows r >= s with bit i of L_r set.  Fresh masks: Q_0 = 2^g - 1 (csgn_uint_first's terms as a multiset, in another
+ * order), Q_{g-1} = 1; g = 8 gives 255, 127, 135, 71, 93, 29, 9, 1 for s = 0..7, and Q_62 = 65 at g = 64.
+ * Term order (decoding needs no table): blocks ascending in r; inside block r segments ascending in d; inside a segment
+ * the subsets by lexicographic rank; inside a subset the digits in base t, i_1's slowest and m_r's fastest.  Term
+ * q * t_j + c of out_j is (entry q of the stream) & (term c of d_{r(q),j}), c fastest; valid is the bare stream; lab_i is
+ * the bare stream with the blocks of the rows whose label lacks bit i left out. */
+/* P_{row,slot} for row < group (0 for a row below the slot: it has no entries), Q_slot for row == group (host only); 0 for
+ * group outside 1..64, slot >= group, t_mask of 0 or of 2^62 or more, row > group or a count of 2^62 or more: binomials
+ * and powers saturate, they never wrap. */
+uint64_t csgn_uint_nth_terms(uint64_t group, uint64_t t_mask, uint64_t slot, uint64_t row);
+/* T_lab_bit (host only); 0 for the same refusals, for a null pointer, for bit > 63 or when no row >= slot has the bit:
+ * such a plane does not exist for the C ABI, as with csgn_uint_first's. */
+uint64_t csgn_uint_nth_label_terms(uint64_t group, uint64_t t_mask, uint64_t slot, const uint64_t *h_labels,
+                                   uint64_t bit);
+/* The selection of ONE slot over `batch` output elements (slots share no entries; a caller that wants slots 0..k-1 makes
+ * k calls).  h_mask: a HOST array of n_mask device pointers.  n_mask == 1, the grouped layout: one batch of batch * group
+ * elements, row r of element e its element e * group + r.  n_mask == group (>= 2), the plane layout: row r is a batch of
+ * `batch` elements -- what an integer's planes hand over.  Either way every row has t_mask terms.  h_values: a HOST
+ * array of `width` device pointers (plane j: batch * group * t_j * dL words, always grouped), h_out: `width` device
+ * pointers (output j: batch * T_j * dL words), d_valid: batch * Q_slot * dL words, or NULL: not computed.  h_label_bits:
+ * n_labels (0..64) strictly ascending bit indices, each naming a plane that exists; h_labels: the g constants, read only
+ * when n_labels > 0; h_label_out: n_labels device pointers (plane i: batch * T_lab * dL words).  At least one of width,
+ * d_valid and n_labels asks for something.  Inputs may alias one another in any way; no output overlaps an input or
+ * another output.
+ * Checks, the first that fails giving the status, all before any device call: n_bits; group, slot, n_mask, width,
+ * n_labels and nothing asked for; host pointers; term counts (t_mask, Q_slot of 2^62 or more, the value planes') and
+ * label bits (CSGN_ERR_INVALID); the stream's Q_slot * dL and every output's T * dL below 2^31 words per element and
+ * batch * that < 2^60 (CSGN_ERR_UNSUPPORTED, no wrap-around; the stream is sized whatever is asked for, because the
+ * kernel indexes it); null device pointers (CSGN_ERR_INVALID; not read when batch == 0); the device (CSGN_ERR_NO_DEVICE,
+ * no CPU fallback).  batch == 0 succeeds.  On the caller's stream, asynchronous, no scratch, no plan object,
+ * graph-capturable: ONE launch of k_uint_nth, split by elements only at knob "launch_blocks" and at the HIP grid limit. */
+int csgn_uint_nth(uint64_t n_bits, uint64_t batch, uint64_t group, uint64_t slot, const uint64_t *const *h_mask,
+                  uint64_t n_mask, uint64_t t_mask, uint64_t width, const uint64_t *const *h_values,
+                  const uint64_t *h_value_terms, uint64_t *const *h_out, uint64_t *d_valid, uint64_t n_labels,
+                  const uint64_t *h_labels, const uint64_t *h_label_bits, uint64_t *const *h_label_out, void *stream);
+
 /* ------------------------------------------------ selection by an encrypted comparison ---- */
 
 /* min, max and compare-exchange of ENCRYPTED integers: every output selected by the ENCRYPTED comparison a < b, the
