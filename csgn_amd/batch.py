@@ -660,6 +660,27 @@ class HipPath:
         check(self.lib.csgn_count(n_bits, count, group, t, h_in, len(ins), len(js), h_js, h_out, self.stream))
         return [o[: count * T * dl] for o, T in zip(outs, terms)]
 
+    def count_prefix(self, n_bits: int, count: int, group: int, t: int, ins, js, exclusive: bool = False, outs=None):
+        """csgn_count_prefix: for every row r of every element's `group` inputs, the bits of the number of ones among
+        the rows up to r (before r when `exclusive`).  `ins`, `js`: as in count, with 2^j <= group - exclusive.  Returns
+        one block per plane (fresh ones unless `outs` is given): row r is `count` elements from term
+        count * csgn_count_prefix_offset(group, t, j, exclusive, r) on, the block count * offset(.., group) terms."""
+        dl = self.default_len(n_bits)
+        ex = 1 if exclusive else 0
+        terms = [int(self.lib.csgn_count_prefix_offset(group, t, int(j), ex, group)) for j in js]
+        assert all(terms), "bad group, term count or plane"
+        assert len(ins) in (1, group)
+        need = (count * group if len(ins) == 1 else count) * t * dl
+        assert all(x.numel() >= need for x in ins)
+        if outs is None:
+            outs = [self.empty_words(count * A * dl) for A in terms]
+        assert all(o.numel() >= count * A * dl for o, A in zip(outs, terms))
+        h_in = (C.c_void_p * len(ins))(*[_ptr(x) for x in ins])
+        h_js = (C.c_uint64 * len(js))(*[int(j) for j in js])
+        h_out = (C.c_void_p * len(outs))(*[_ptr(o) for o in outs])
+        check(self.lib.csgn_count_prefix(n_bits, count, group, t, ex, h_in, len(ins), len(js), h_js, h_out, self.stream))
+        return [o[: count * A * dl] for o, A in zip(outs, terms)]
+
     def wsum_create(self, ns, t: int, js) -> int:
         """csgn_wsum_create: the plan of the planes `js` (strictly ascending) for classes of ns[c] inputs of weight 2^c
         and of `t` terms each.  Returns the handle; release it with self.lib.csgn_wsum_destroy."""

@@ -205,6 +205,8 @@ SIGNATURES = {
     "csgn_count_terms": (u64, [u64, u64, u64]),
     "csgn_count_kernel": (C.c_char_p, [u64, u64, u64, u64, u64, u64, vp]),
     "csgn_count": (C.c_int, [u64, u64, u64, u64, vp, u64, u64, vp, vp, vp]),
+    "csgn_count_prefix_offset": (u64, [u64, u64, u64, u64, u64]),
+    "csgn_count_prefix": (C.c_int, [u64, u64, u64, u64, u64, vp, u64, u64, vp, vp, vp]),
     "csgn_wsum_terms": (u64, [u64, vp, u64, u64]),
     "csgn_wsum_create": (C.c_int, [u64, vp, u64, u64, vp, C.POINTER(vp)]),
     "csgn_wsum_plan_terms": (u64, [vp, u64]),

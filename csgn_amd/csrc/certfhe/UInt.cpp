@@ -1892,6 +1892,136 @@ UIntBatch countMatches(const UIntBatch &keys, const UIntBatch &query, unsigned p
     return UIntBatch::fromPlanes(countPlanes(std::vector<CiphertextBatch>(1, eq), rows, firstPlanes(planes), "countMatches"));
 }
 
+// ------------------------------------------------------------------ running counts (csgn_count_prefix)
+
+namespace {
+
+bool prefixCall(bool uniform_operands) { return uniform_operands; }
+
+// rows[r][x]: plane js[x] of the number of ones among the first r + 1 - exclusive inputs of every element (countPlanes'
+// layouts).  Every size first; then one csgn_count_prefix for uniform inputs of one term count -- one block a plane, the
+// rows views into it --, else the definition row by row: the gathered prefix through countPlanes.
+std::vector<std::vector<CiphertextBatch> > prefixPlanes(const std::vector<CiphertextBatch> &in, uint64_t group,
+                                                        const std::vector<unsigned> &js, bool exclusive, const char *who)
+{
+    const std::string name = std::string("certFHE::") + who;
+    const Context &ctx = in[0].context();
+    const bool grouped = in.size() == 1;
+    const uint64_t count = grouped ? in[0].size() / group : in[0].size(), ex = exclusive ? 1 : 0, dl = ctx.getDefaultN();
+    std::vector<std::vector<CiphertextBatch> > rows(group);
+    if (count == 0) {
+        for (uint64_t r = 0; r < group; ++r)
+            rows[r].assign(js.size(), BatchAccess::make(ctx, 0, 1));
+        return rows;
+    }
+    const Planes p(in);
+    uint64_t t = 0;
+    bool one_t = true;
+    for (size_t i = 0; i < p.terms.size(); ++i) {
+        one_t = one_t && p.terms[i] == p.terms[0];
+        t = p.terms[i] > t ? p.terms[i] : t;
+    }
+    // sizes, of the last row, the longest, and from the largest term count: a bound for every row and element
+    const std::vector<uint64_t> T = countSizes(ctx, group - ex, t, js, who);
+    const CiphertextBatch zero = constantBatch(ctx, std::vector<unsigned char>(count, 0));
+    for (uint64_t r = 0; r < group; ++r)
+        rows[r].assign(js.size(), zero);
+    if (prefixCall(p.uniform && one_t)) {
+        std::vector<uint64_t> h_js, words;
+        std::vector<size_t> at;
+        for (size_t x = 0; x < js.size(); ++x) {
+            if (T[x] == 0)
+                continue;
+            const uint64_t A = csgn_count_prefix_offset(group, t, js[x], ex, group);
+            unsigned long long w;
+            if (A == 0 || __builtin_mul_overflow((unsigned long long)count, (unsigned long long)A, &w) ||
+                __builtin_mul_overflow(w, (unsigned long long)dl, &w) || w >= (1ull << 60))
+                throw std::invalid_argument(name + ": plane " + std::to_string(js[x]) + " of the rows of groups of " +
+                                            std::to_string(group) + " exceeds 2^60 words");
+            h_js.push_back(js[x]);
+            words.push_back(w);
+            at.push_back(x);
+        }
+        if (h_js.empty())
+            return rows;
+        std::vector<std::shared_ptr<detail::DevicePayload> > blocks;
+        std::vector<uint64_t *> dst;
+        for (size_t k = 0; k < h_js.size(); ++k) {
+            blocks.push_back(detail::allocWords(words[k]));
+            dst.push_back(blocks[k]->data());
+        }
+        detail::check(csgn_count_prefix(ctx.getN(), count, group, t, ex, sources(p).data(), in.size(), h_js.size(),
+                                        h_js.data(), dst.data(), detail::stream()),
+                      "csgn_count_prefix");
+        for (size_t k = 0; k < at.size(); ++k)
+            for (uint64_t r = 0; r < group; ++r) {
+                const uint64_t off = csgn_count_prefix_offset(group, t, h_js[k], ex, r);
+                const uint64_t next = csgn_count_prefix_offset(group, t, h_js[k], ex, r + 1);
+                if (r + 1 - ex >= (1ull << h_js[k]))             // a shorter row keeps the ZERO of constantBatch
+                    rows[r][at[k]] = BatchAccess::makeView(ctx, count, next - off, blocks[k], count * off * dl);
+            }
+        return rows;
+    }
+    // ragged or mixed: the definition itself, the count of the gathered prefix row by row
+    for (uint64_t r = 0; r < group; ++r) {
+        const uint64_t nr = r + 1 - ex;
+        if (nr == 0)
+            continue;
+        if (grouped) {
+            std::vector<uint64_t> idx(count * nr);
+            for (uint64_t q = 0; q < count; ++q)
+                for (uint64_t i = 0; i < nr; ++i)
+                    idx[q * nr + i] = q * group + i;
+            rows[r] = countPlanes(std::vector<CiphertextBatch>(1, in[0].gather(idx)), nr, js, who);
+        } else {
+            rows[r] = countPlanes(std::vector<CiphertextBatch>(in.begin(), in.begin() + nr), nr, js, who);
+        }
+    }
+    return rows;
+}
+
+std::vector<UIntBatch> asIntegers(const std::vector<std::vector<CiphertextBatch> > &rows)
+{
+    std::vector<UIntBatch> out;
+    out.reserve(rows.size());
+    for (size_t r = 0; r < rows.size(); ++r)
+        out.push_back(UIntBatch::fromPlanes(rows[r]));
+    return out;
+}
+
+} // namespace
+
+std::vector<UIntBatch> runningCount(const CiphertextBatch &bits, uint64_t group, unsigned planes, bool exclusive)
+{
+    requirePlanes(planes, "runningCount");
+    requireGroup(bits, group, "runningCount");
+    return asIntegers(prefixPlanes(std::vector<CiphertextBatch>(1, bits), group, firstPlanes(planes), exclusive,
+                                   "runningCount"));
+}
+
+std::vector<CiphertextBatch> runningCountBit(const CiphertextBatch &bits, uint64_t group, unsigned j, bool exclusive)
+{
+    requireGroup(bits, group, "runningCountBit");
+    const std::vector<std::vector<CiphertextBatch> > rows =
+        prefixPlanes(std::vector<CiphertextBatch>(1, bits), group, std::vector<unsigned>(1, j), exclusive, "runningCountBit");
+    std::vector<CiphertextBatch> out;
+    for (size_t r = 0; r < rows.size(); ++r)
+        out.push_back(rows[r][0]);
+    return out;
+}
+
+// the planes of a are the plane layout's inputs (a width of 1: the one plane is a grouped batch of groups of 1)
+std::vector<UIntBatch> prefixPopcount(const UIntBatch &a, unsigned planes, bool exclusive)
+{
+    requirePlanes(planes, "prefixPopcount");
+    return asIntegers(prefixPlanes(planesOf(a), a.width(), firstPlanes(planes), exclusive, "prefixPopcount"));
+}
+
+const char *runningCountRoute(uint64_t group, bool uniform_operands)
+{
+    return group != 0 && prefixCall(uniform_operands) ? "csgn_count_prefix" : "loop";
+}
+
 // ------------------------------------------------------------------ sums of integers (csgn_wsum)
 
 namespace {

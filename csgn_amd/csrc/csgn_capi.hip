@@ -2164,6 +2164,50 @@ int csgn_count(uint64_t n_bits, uint64_t count, uint64_t group, uint64_t t, cons
     return CSGN_OK;
 }
 
+uint64_t csgn_count_prefix_offset(uint64_t group, uint64_t t, uint64_t j, uint64_t exclusive, uint64_t r)
+{
+    return csgn::count_prefix_offset(group, t, j, exclusive, r);
+}
+
+int csgn_count_prefix(uint64_t n_bits, uint64_t count, uint64_t group, uint64_t t, uint64_t exclusive,
+                      const uint64_t *const *h_in, uint64_t n_in, uint64_t n_out, const uint64_t *h_js,
+                      uint64_t *const *h_out, void *stream)
+{
+    if (int rc = check_n(n_bits))
+        return rc;
+    REQUIRE(count && group && t && t < (1ull << 62), "count prefix: %llu elements of %llu inputs of %llu terms (each at "
+            "least 1, terms below 2^62)", (unsigned long long)count, (unsigned long long)group, (unsigned long long)t);
+    REQUIRE(exclusive <= 1, "count prefix: exclusive is %llu (0 or 1)", (unsigned long long)exclusive);
+    REQUIRE(n_in == 1 || (n_in == group && n_in <= 64), "count prefix: %llu input batches (1, or the group when it is "
+            "2..64)", (unsigned long long)n_in);
+    REQUIRE(n_out >= 1, "count prefix: no planes");
+    REQUIRE(h_in && h_js && h_out, "null host pointer");
+    REQUIRE(csgn::count_prefix_shape_ok(count, group, t, exclusive, n_in, n_out, (const u64 *)h_js),
+            "count prefix: the planes are not strictly ascending with 2^j within the %llu inputs of the last row",
+            (unsigned long long)(group - exclusive));
+    const uint64_t dl = csgn_default_len(n_bits);
+    for (uint64_t x = 0; x < n_out; ++x) {
+        // the terms of the last row, the longest, and of the rows together; a count that reaches 2^62 is past every limit
+        uint64_t T = csgn::count_terms(group - exclusive, t, h_js[x]);
+        uint64_t A = csgn::count_prefix_offset(group, t, h_js[x], exclusive, group);
+        if (T == 0)
+            T = ~0ull;
+        if (A == 0)
+            A = ~0ull;
+        if (int rc = check_size(count, T, A, dl, "count prefix: plane %llu", (unsigned long long)h_js[x]))
+            return rc;
+    }
+    if (int rc = check_planes(h_in, nullptr, n_in, "input"))
+        return rc;
+    if (int rc = check_planes((const uint64_t *const *)h_out, nullptr, n_out, "output"))
+        return rc;
+    if (int rc = require_device("csgn_count_prefix"))
+        return rc;
+    HIP_TRY(csgn::count_prefix(n_bits, count, group, t, exclusive, (const u64 *const *)h_in, n_in, n_out,
+                               (const u64 *)h_js, (u64 *const *)h_out, S(stream)));
+    return CSGN_OK;
+}
+
 /* ------------------------------------------------ encrypted integers summed into integers ---- */
 
 uint64_t csgn_wsum_terms(uint64_t n_classes, const uint64_t *h_n, uint64_t t, uint64_t j)

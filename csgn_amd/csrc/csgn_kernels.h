@@ -252,6 +252,14 @@ const char *count_kernel_name(u64 n_bits, u64 count, u64 group, u64 t, u64 n_in,
 hipError_t count(u64 n_bits, u64 count, u64 group, u64 t, const u64 *const *in, u64 n_in, u64 n_out, const u64 *js,
                  u64 *const *out, hipStream_t stream);
 
+// running counts of encrypted bits (csgn_count_prefix.hip), include/csgn_hip.h's definition: row r of plane j is count's
+// plane j of the element's first r + 1 - exclusive inputs, or the one ZERO term where 2^j passes them; out[x]: the rows
+// one after the other, row r `count` elements from term count * count_prefix_offset(.., r) on.
+u64 count_prefix_offset(u64 group, u64 t, u64 j, u64 exclusive, u64 r);   // r = group: A_j; 0: invalid or 2^62 or more
+bool count_prefix_shape_ok(u64 count, u64 group, u64 t, u64 exclusive, u64 n_in, u64 n_out, const u64 *js);
+hipError_t count_prefix(u64 n_bits, u64 count, u64 group, u64 t, u64 exclusive, const u64 *const *in, u64 n_in,
+                        u64 n_out, const u64 *js, u64 *const *out, hipStream_t stream);
+
 // encrypted integers summed into encrypted integers (csgn_wsum.hip), include/csgn_hip.h's definition: class c holds n_c
 // ciphertexts of weight 2^c and of t terms each; plane j of an element is the sum, over the count vectors (m_j .. m_0)
 // with sum m_c 2^c = 2^j in ascending order and over their selections (class j slowest), of the products of the selected

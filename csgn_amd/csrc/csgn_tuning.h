@@ -59,7 +59,7 @@ enum TuneKey {
     TUNE_MATMUL_FORM,    // products of encrypted bit matrices (csgn_matmul.hip): -1 = per shape, 0 = composed form (both operands tiled by the gather launcher, one uniform multiply), 1 = fused kernel
     TUNE_MATMUL_EPART,   // ... values of e one k_matmul workgroup takes at most, 0 = by the shape (what the LDS holds, cut further until the workgroups fill the chip); a test sets it to choose where the range of e is split
     TUNE_COUNT_FORM,     // encrypted bits counted into integers (csgn_count.hip): -1 = per shape, 0 = composed form (the factors tiled by the gather launcher, uniform multiplies), 1 = fused kernel
-    TUNE_COUNT_CPART,    // ... combination ranks one k_count workgroup takes at most, 0 = by the shape (what its subset table holds, cut further until the workgroups fill the chip); a test sets it to place the split of the ranks
+    TUNE_COUNT_CPART,    // ... combination ranks one k_count workgroup takes at most, 0 = by the shape (what its subset table holds, cut further until the workgroups fill the chip), and one k_count_prefix workgroup (csgn_count_prefix.hip) of the ranks of a plane's rows together; a test sets it to place the split of the ranks
     TUNE_WSUM_CPART,     // encrypted integers summed into integers (csgn_wsum.hip): selection ranks one k_wsum workgroup takes at most, 0 = by the shape (what its index table holds, no more than 1024 terms); read when a plan is created; a test sets it to place the split of the ranks
     TUNE_UINT_LT_SELECT_FORM, // selection by an encrypted comparison (csgn_uint_lt_select.hip): -1 = per shape, 0 = composed form (the LT steps and one MUX gate per output through the tuned launchers), 1 = fused kernel
     TUNE_UINT_PICK_FORM, // knob "uint_pick_fused": shifts, rotates and per-element reads by an encrypted amount (csgn_uint_pick.hip): -1 = per shape, 0 = composed form (the tuned launchers row by row), 1 = fused kernel

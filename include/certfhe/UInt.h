@@ -153,6 +153,19 @@
 // does not divide size(), `planes` of 0 or above 64, mismatched contexts or widths, or a plane past 2^31 words per
 // element.  An empty batch gives empty planes.
 //
+// RUNNING COUNTS: runningCount(bits, g, planes) returns g integers, entry r the number of ones among the group's rows
+// 0..r (with `exclusive`: among the rows before r) -- a cumulative count, the rank of a row among the matching rows, the
+// segment number of a row from "a segment starts here" flags; runningCountBit names one plane (j = 0: the running
+// parity) and prefixPopcount(a, planes) is the rank function of an integer's own bits.  Entry r has word for word the
+// planes of countOnes over the gathered rows: C(n_r, 2^j) * t^(2^j) terms with n_r = r + 1 - exclusive, and the
+// one-term ZERO of constantBatch where 2^j > n_r.  Uniform inputs of one term count take ONE csgn_count_prefix
+// (include/csgn_hip.h; one launch): it writes one block a plane, the rows of all g entries one after the other, and
+// the entries are views that keep the block alive -- 16 fresh flags: 136, 681, 6191, 24 317 and 16 terms per element
+// for planes 0 to 4.  Planes with 2^j > g - exclusive are ZERO without a launch.  Ragged operands, or inputs of
+// different term counts, take the definition's loop: the gathered prefix through countOnes' route, row by row, with
+// the same words.  runningCountRoute names the route.  Every size is computed before anything is allocated or
+// launched: std::invalid_argument as for countOnes, the size that of the last row.  An empty batch gives empty planes.
+//
 // SUMS: sumValues(a, g, planes) adds every g consecutive integers of a batch into an encrypted integer modulo
 // 2^planes, sumWhere(mask, values, g, planes) only those whose encrypted mask bit is set (SUM(value) of the matching
 // rows), mul(a, b, planes) multiplies two encrypted integers and innerProduct(a, b, g, planes) adds g products.  All are
@@ -474,6 +487,19 @@ UIntBatch hammingDistance(const UIntBatch &a, const UIntBatch &b, unsigned plane
 // element e: the number of rows r with keys[r] == query[e], modulo 2^planes: countOnes over the batch whose element
 // e*n + r is equalTo(keys row r, query element e); plane 0 has the words of matches(keys, query)
 UIntBatch countMatches(const UIntBatch &keys, const UIntBatch &query, unsigned planes);
+
+// entry r, 0 <= r < group: element q is the number of ones among bits[q*group .. q*group+r] -- with `exclusive` among
+// the r bits before row r --, modulo 2^planes: word for word countOnes of those rows, ZERO planes included
+std::vector<UIntBatch> runningCount(const CiphertextBatch &bits, uint64_t group, unsigned planes, bool exclusive = false);
+// bit j alone of every entry (j = 0: the running parity)
+std::vector<CiphertextBatch> runningCountBit(const CiphertextBatch &bits, uint64_t group, unsigned j, bool exclusive = false);
+// of an integer's own planes (the plane layout): entry i is the number of set bits among bits 0..i of a -- below bit i
+// with `exclusive`: the rank function of a bit vector --, modulo 2^planes
+std::vector<UIntBatch> prefixPopcount(const UIntBatch &a, unsigned planes, bool exclusive = false);
+// The route the three functions above take for groups of `group` rows (an integer's planes: its width), every input
+// uniform with one term count, or not (a static string): "csgn_count_prefix" (one call, one launch) or "loop" (the
+// gathered prefix through countOnes' route row by row).  No device work, like nthRoute: the words are the same.
+const char *runningCountRoute(uint64_t group, bool uniform_operands);
 
 // element q: the sum of a[q*group .. q*group+group-1], modulo 2^planes; planes >= 1 / its bit j alone
 UIntBatch sumValues(const UIntBatch &a, uint64_t group, unsigned planes);

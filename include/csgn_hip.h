@@ -1437,6 +1437,41 @@ const char *csgn_count_kernel(uint64_t n_bits, uint64_t count, uint64_t group, u
 int csgn_count(uint64_t n_bits, uint64_t count, uint64_t group, uint64_t t, const uint64_t *const *h_in, uint64_t n_in,
                uint64_t n_out, const uint64_t *h_js, uint64_t *const *h_out, void *stream);
 
+/* RUNNING counts of encrypted bits: for every row r of a group, how many of the rows up to and including r (exclusive
+ * = 0) or before r (exclusive = 1) have their bit set -- a cumulative count, the rank of a row among the matching rows,
+ * the segment number of a row, the rank function of a bit vector, a running parity (plane 0).
+ * Inputs: csgn_count's, g = group inputs x_0 ... x_{g-1} of t terms per element, in either layout.  Row r, 0 <= r < g,
+ * counts the inputs x_0 ... x_{n_r - 1}, n_r = r + 1 - exclusive.  For a plane j with m = 2^j:
+ *   - m <= n_r: output (r, j) of element q is WORD FOR WORD csgn_count's plane j of those n_r inputs: the m-subsets of
+ *     {0 ... n_r - 1} in lexicographic order, term p = rank * t^m + digits (d_1 slowest), the AND of the factors' terms;
+ *     T_{r,j} = C(n_r, m) * t^m terms.
+ *   - m > n_r (n_r = 0 among them): the one all-zero term, the ZERO of constantBatch; T_{r,j} = 1.
+ * Layout, by row: h_out[x] is one block for plane j = h_js[x]; in it row r is a uniform batch of `count` elements of
+ * T_{r,j} terms each that begins at term count * off_j(r), off_j(r) the sum of T_{r',j} over r' < r:
+ *   inclusive off_j(r) = min(r, m - 1) + C(r + 1, m + 1) * t^m,  exclusive off_j(r) = min(r, m) + C(r, m + 1) * t^m.
+ * A_j = off_j(g); the block takes count * A_j * dL words.  Every row is a uniform batch every other entry point takes;
+ * with even dL every row begins on a 16-byte boundary whenever the block does.
+ * Term counts: fresh flags, g = 16: A_j = 136, 681, 6191, 24 317 and 16 for planes 0 to 4; g = 64: 2080 and 43 681 for
+ * planes 0 and 1. */
+/* off_j(r), r in 0..group, r = group giving A_j (host only).  0 for an invalid shape (a zero argument, exclusive above
+ * 1, j > 6, 2^j > group - exclusive, t >= 2^62, r > group) or a value of 2^62 or more -- and for r = 0, whose offset IS
+ * 0: test a shape's validity with r = group. */
+uint64_t csgn_count_prefix_offset(uint64_t group, uint64_t t, uint64_t j, uint64_t exclusive, uint64_t r);
+/* The running counts of `count` elements in one kernel, k_count_prefix.  h_in, n_in: as in csgn_count.  h_js: n_out
+ * strictly ascending plane indices with 2^j <= group - exclusive (a higher plane is ZERO in every row: the classes
+ * return it without a launch).  Inputs may alias one another; no output overlaps an input or another output.  Checks,
+ * in this order, the first that fails giving the status: n_bits; count, group, t nonzero, t < 2^62, exclusive 0 or 1,
+ * n_in 1 or group (<= 64 when above 1), n_out >= 1, host pointers non-null, the js strictly ascending with 2^j <=
+ * group - exclusive (CSGN_ERR_INVALID); every T_{r,j} * dL below 2^31 words and count * A_j * dL below 2^60
+ * (CSGN_ERR_UNSUPPORTED; computed without wrap-around); null device pointers (CSGN_ERR_INVALID); the device
+ * (CSGN_ERR_NO_DEVICE, no CPU fallback).  Nothing is allocated or launched before every check has passed.  On the
+ * caller's stream, asynchronous; one launch for every shape within memory (the ZERO terms of the short rows are
+ * written by it too) and graph-capturable.  Knob "count_cpart" places the split of the ranks over workgroups as it does
+ * for k_count. */
+int csgn_count_prefix(uint64_t n_bits, uint64_t count, uint64_t group, uint64_t t, uint64_t exclusive,
+                      const uint64_t *const *h_in, uint64_t n_in, uint64_t n_out, const uint64_t *h_js,
+                      uint64_t *const *h_out, void *stream);
+
 /* ------------------------------------------------ encrypted integers summed into integers ---- */
 
 /* ENCRYPTED integers summed into ENCRYPTED integers: SUM(value) of the matching rows, the product of two encrypted
