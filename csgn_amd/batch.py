@@ -513,6 +513,14 @@ class HipPath:
         check(self.lib.csgn_uint_pick_rows(n_bits, batch, v, h_x, h_s, rows, w, h_a, h_T, h_out, self.stream))
         return [o[: batch * t * dl] for o, t in zip(outs, Tout)]
 
+    SCRATCH_STATS = ("blocks", "bytes", "retired", "mallocs", "frees", "tables", "tables_retired", "tables_freed")
+
+    def scratch_stats(self) -> dict:
+        """csgn_scratch_stats (host only): the calling thread's scratch blocks and row tables, by SCRATCH_STATS' names."""
+        out = (C.c_uint64 * 8)()
+        check(self.lib.csgn_scratch_stats(out))
+        return dict(zip(self.SCRATCH_STATS, (int(x) for x in out)))
+
     def uint_write(self, n_bits: int, batch: int, index, index_terms, rows: int, value, value_terms, arrays,
                    array_terms, outs=None):
         """csgn_uint_write: element e's own array of `rows` rows (the elements e * rows .. e * rows + rows - 1 of the

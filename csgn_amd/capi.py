@@ -175,6 +175,7 @@ SIGNATURES = {
     "csgn_uint_pick_rows_check": (C.c_int, [u64, u64, u64, C.POINTER(u64), u64, u64, C.POINTER(u64)]),
     "csgn_uint_pick_rows_kernel": (C.c_char_p, [u64, u64, u64, C.POINTER(u64), u64, u64, C.POINTER(u64)]),
     "csgn_uint_pick_rows_decode": (C.c_int, [u64, C.POINTER(u64), u64, C.POINTER(u64), u64, C.POINTER(u64)]),
+    "csgn_scratch_stats": (C.c_int, [C.POINTER(u64)]),
     "csgn_uint_pick_rows": (C.c_int, [u64, u64, u64, C.POINTER(vp), C.POINTER(u64), u64, u64, C.POINTER(vp),
                                       C.POINTER(u64), C.POINTER(vp), vp]),
     "csgn_uint_write_offset": (u64, [u64, C.POINTER(u64), u64, u64, u64, u64]),

@@ -1550,6 +1550,14 @@ const char *csgn_uint_pick_rows_kernel(uint64_t n_bits, uint64_t batch, uint64_t
     return csgn::uint_pick_rows_kernel_name();
 }
 
+int csgn_scratch_stats(uint64_t h_out[8])
+{
+    REQUIRE(h_out, "null host pointer");
+    csgn::scratch_stats((u64 *)h_out);
+    csgn::uint_pick_rows_stats((u64 *)h_out + 5);
+    return CSGN_OK;
+}
+
 int csgn_uint_pick_rows_decode(uint64_t index_width, const uint64_t *h_index_terms, uint64_t rows,
                                const uint64_t *h_row_terms, uint64_t position, uint64_t *h_out)
 {

@@ -339,6 +339,9 @@ bool uint_pick_rows_sizes(u64 v, const u64 *s, u64 rows, u64 w, const u64 *T, u6
 const char *uint_pick_rows_kernel_name();       // of a valid shape under the calling thread's knob
 // (r, in, c) of output position `position` by the kernel's own search and division (host only); a csgn_status
 int uint_pick_rows_decode(u64 v, const u64 *s, u64 rows, const u64 *T, u64 position, u64 out[3]);
+// the calling thread's row tables (host only): {tables kept, device copies retired, device copies freed}.  A copy that a
+// capturing stream has used is retired, not freed, when its table leaves the cache or the device changes.
+void uint_pick_rows_stats(u64 out[3]);
 hipError_t uint_pick_rows(u64 n_bits, u64 batch, u64 v, const u64 *const *index, const u64 *s, u64 rows, u64 w,
                           const u64 *const *arrays, const u64 *T, u64 *const *out, hipStream_t stream);
 
@@ -361,10 +364,14 @@ hipError_t uint_write(u64 n_bits, u64 batch, u64 v, const u64 *const *index, con
 // thread keeps per stream and per user, never the stream-ordered pool.  Returns the block, or nullptr with e set
 // (hipErrorStreamCaptureUnsupported when the call would have to allocate while s is capturing).  owned: the block is
 // past the kept size and belongs to this call; scratch_done frees it behind the call's launches (waits for the device)
-// and passes e through.
+// and passes e through.  A kept block handed out while s is capturing is never freed before the thread ends: where
+// growth or eviction would free it, it is retired instead, so a graph that holds it stays replayable.  Eviction (a
+// ninth stream in one slot) takes the block used least recently.  scratch_stats: the calling thread's {blocks kept,
+// bytes kept, blocks retired, hipMalloc calls of scratch_take, hipFree calls of scratch_take and scratch_done}.
 enum ScratchSlot { SCRATCH_UINT_PLAIN, SCRATCH_UINT_LUT, SCRATCH_UINT_READ, SCRATCH_UINT_ADDK, SCRATCH_UINT_FIND, SCRATCH_GATHER, SCRATCH_MATMUL, SCRATCH_COUNT, SCRATCH_UINT_LT_SELECT, SCRATCH_UINT_PICK, SCRATCH_UINT_WRITE, SCRATCH_UINT_ARITH, SCRATCH_UINT_PICK_ROWS, SCRATCH_SLOTS };
 u64 *scratch_take(ScratchSlot slot, size_t bytes, hipStream_t s, bool &owned, hipError_t &e);
 hipError_t scratch_done(u64 *block, bool owned, hipError_t e);
+void scratch_stats(u64 out[5]);
 
 hipError_t small_ops(u64 n_bits, u64 count, const ::csgn_small_op *ops, hipStream_t s);
 size_t decrypt_scratch_bytes(u64 batch, u64 total_terms);

@@ -159,18 +159,38 @@ struct RowsTable {
     bool fits = false;                  // every count below 2^32: the records hold it
     PickRow *dev = nullptr;
     int device = -1;
+    bool captured = false;              // dev was handed to a launch on a capturing stream: a graph may hold it
 };
 
 // The calling thread's tables, the most recently used last.  A table that leaves takes its device copy with it (hipFree
-// waits for the launches that read it); at thread or process exit the copies go the way csgn_scratch.cpp's blocks do.
+// waits for the launches that read it) -- unless a capturing stream has seen the copy: a graph may then hold it, and it is
+// retired, to be freed when the thread ends (csgn_scratch.cpp's rule for its blocks).  At thread or process exit the
+// copies, kept and retired, go the way csgn_scratch.cpp's blocks do.
 constexpr size_t kRowsTables = 2 * kPickMaxPlanes;
 struct RowsCache {
     std::vector<std::unique_ptr<RowsTable>> v;
+    std::vector<PickRow *> retired;
+    u64 freed = 0;
+    void drop(RowsTable &t)             // t's device copy leaves: the table does, or the device has changed
+    {
+        if (!t.dev)
+            return;
+        if (t.captured) {
+            retired.push_back(t.dev);
+        } else {
+            (void)hipFree(t.dev);
+            ++freed;
+        }
+        t.dev = nullptr;
+        t.captured = false;
+    }
     ~RowsCache()
     {
         for (auto &t : v)
             if (t->dev)
                 (void)hipFree(t->dev);
+        for (PickRow *p : retired)
+            (void)hipFree(p);
     }
 };
 thread_local RowsCache g_rows;
@@ -212,38 +232,36 @@ RowsTable *rows_table(u64 v, const u64 *s, u64 n, const u64 *T)
         }
     }
     if (list.size() >= kRowsTables) {
-        if (list.front()->dev)
-            (void)hipFree(list.front()->dev);
+        g_rows.drop(*list.front());
         list.erase(list.begin());
     }
     list.push_back(std::move(t));
     return list.back().get();
 }
 
-// the table's device copy on the current device; uploaded (synchronously) on first use, which a capturing stream refuses
+// the table's device copy on the current device; uploaded (synchronously) on first use, which a capturing stream refuses.
+// A copy that a capturing stream uses is marked (RowsCache::drop).
 hipError_t rows_upload(RowsTable &t, hipStream_t st)
 {
     int device = 0;
     hipError_t e = hipGetDevice(&device);
     if (e != hipSuccess)
         return e;
-    if (t.dev && t.device == device)
-        return hipSuccess;
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone)
-        return hipErrorStreamCaptureUnsupported;
-    if (t.dev) {
-        (void)hipFree(t.dev);
-        t.dev = nullptr;
+    const bool capturing = hipStreamIsCapturing(st, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone;
+    if (t.dev && t.device == device) {
+        t.captured = t.captured || capturing;
+        return hipSuccess;
     }
+    if (capturing)
+        return hipErrorStreamCaptureUnsupported;
+    g_rows.drop(t);
     if ((e = hipMalloc(reinterpret_cast<void **>(&t.dev), t.rows.size() * sizeof(PickRow))) != hipSuccess)
         return e;
     t.device = device;
     e = hipMemcpy(t.dev, t.rows.data(), t.rows.size() * sizeof(PickRow), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(t.dev);
-        t.dev = nullptr;
-    }
+    if (e != hipSuccess)
+        g_rows.drop(t);
     return e;
 }
 
@@ -448,6 +466,13 @@ bool uint_pick_rows_sizes(u64 v, const u64 *s, u64 n, u64 w, const u64 *T, u64 *
         Tout[j] = rs.table[j]->Tout;
     }
     return true;
+}
+
+void uint_pick_rows_stats(u64 out[3])
+{
+    out[0] = g_rows.v.size();
+    out[1] = g_rows.retired.size();
+    out[2] = g_rows.freed;
 }
 
 const char *uint_pick_rows_kernel_name() { return rows_use_fused() ? "k_uint_pick_rows" : "composed"; }

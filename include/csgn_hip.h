@@ -33,9 +33,18 @@
  *   - Every function returns CSGN_OK (0) or a negative csgn_status; csgn_last_error() gives
  *     a thread-local message.  The reference has no error convention at all;
  *     misuse that is UB there is a reported error here.
- *   - Thread safety: no hidden global state except per-thread items (the error string and the
- *     ragged planner's small device scratch); one host thread (or process) per GPU may call
- *     concurrently.
+ *   - Thread safety: no hidden global state except per-thread items: the error string, the
+ *     tuning knobs, the ragged planner's small device scratch, the temporary blocks of the
+ *     composed forms and of csgn_gather_plan (one per user and stream, at most 8 streams per
+ *     user, the least recently used evicted; csgn_uint_addk has the rules) and the row tables of
+ *     csgn_uint_pick_rows (up to 128, least recently used evicted).  A thread's device memory is
+ *     returned when the thread ends; csgn_scratch_stats reports it.  One host thread (or
+ *     process) per GPU may call concurrently.
+ *   - Graphs: a graph that captured a composed-form call or a csgn_uint_pick_rows call holds
+ *     the capturing thread's temporary block or row table.  Such memory is never freed while
+ *     that thread lives: where growth, eviction or a change of device would free it, it is
+ *     retired instead and returned at thread exit.  The graph stays replayable for as long as
+ *     the capturing thread lives, and no longer.
  *   - There is NO CPU fallback: without a gfx950 device every compute call fails with
  *     CSGN_ERR_NO_DEVICE.
  */
@@ -711,7 +720,9 @@ const char *csgn_uint_addk_kernel(uint64_t n_bits, uint64_t batch, uint64_t widt
  * stream, asynchronous; the fused form is one launch and graph-capturable.  The composed form is asynchronous once its
  * thread's block for that stream is large enough; a call that has to allocate or grow it calls hipMalloc (refused with
  * CSGN_ERR_HIP while the stream is capturing), and a temporary past 256 MiB is allocated for the call and freed behind
- * it, which waits for the device.  No GPU: CSGN_ERR_NO_DEVICE, no CPU fallback. */
+ * it, which waits for the device.  A thread keeps blocks for 8 streams per composed form; a ninth stream evicts the one
+ * used least recently.  A call whose block is large enough can be captured into a graph; that block is then kept until
+ * the thread ends, whatever grows or is evicted ("Graphs" at the top).  No GPU: CSGN_ERR_NO_DEVICE, no CPU fallback. */
 int csgn_uint_addk(uint64_t n_bits, uint64_t batch, uint64_t width, uint64_t k, int negate_out,
                    const uint64_t *const *h_planes, const uint64_t *h_terms, uint64_t *const *h_outs, uint64_t *d_carry,
                    void *stream);
@@ -1279,6 +1290,13 @@ const char *csgn_uint_pick_rows_kernel(uint64_t n_bits, uint64_t batch, uint64_t
  * such a plane long before). */
 int csgn_uint_pick_rows_decode(uint64_t index_width, const uint64_t *h_index_terms, uint64_t rows,
                                const uint64_t *h_row_terms, uint64_t position, uint64_t *h_out);
+/* The calling thread's device memory behind the composed forms, csgn_gather_plan and csgn_uint_pick_rows (host only, it
+ * never touches a device): h_out[0] temporary blocks kept, [1] their bytes, [2] blocks retired (handed out under capture,
+ * then replaced by growth or eviction; freed at thread exit), [3] hipMalloc calls made for temporaries, [4] hipFree calls
+ * made for them (a temporary past 256 MiB is allocated for its call and freed behind it: one of each), [5] row tables
+ * kept, [6] row-table device copies retired, [7] row-table device copies freed.  The counts run from the thread's start.
+ * CSGN_ERR_INVALID for a null pointer. */
+int csgn_scratch_stats(uint64_t h_out[8]);
 /* The read over `batch` arrays.  h_index: a HOST array of index_width device pointers (plane k: batch * s_k * dL words),
  * h_arrays: a HOST array of `width` device pointers (plane j: batch * A_j * dL words, csgn_uint_write's output layout),
  * h_out: a HOST array of `width` device pointers (output j: batch * Tout_j * dL words, uniform).  Planes may alias one
@@ -1287,7 +1305,8 @@ int csgn_uint_pick_rows_decode(uint64_t index_width, const uint64_t *h_index_ter
  * touches nothing.  The fused form is one launch.  The calling thread keeps the row tables of the shapes it has used, on
  * the host and on the device (up to 128 tables; planes with equal rows share one): the first call of a shape uploads
  * them and waits for the copy, a repeated call uploads nothing, is asynchronous on the caller's stream and can be
- * captured into a graph (a first call under capture is refused: hipErrorStreamCaptureUnsupported).  No GPU:
+ * captured into a graph (a first call under capture is refused: hipErrorStreamCaptureUnsupported).  A device copy that
+ * a capturing stream has used is kept until the thread ends, whatever leaves the cache ("Graphs" at the top).  No GPU:
  * CSGN_ERR_NO_DEVICE, no CPU fallback. */
 int csgn_uint_pick_rows(uint64_t n_bits, uint64_t batch, uint64_t index_width, const uint64_t *const *h_index,
                         const uint64_t *h_index_terms, uint64_t rows, uint64_t width, const uint64_t *const *h_arrays,
