@@ -606,6 +606,39 @@ class HipPath:
         check(self.lib.csgn_uint_arith(n_bits, op, batch, w, h_a, h_ta, h_b, h_tb, h_out, _ptr(carry), self.stream))
         return [o[:s] for o, s in zip(outs, sizes)], (None if carry is None else carry[:csize])
 
+    def uint_add_where_terms(self, terms, sel_terms: int, k: int):
+        """csgn_uint_add_where_terms: the terms per element of every plane of a + (sel ? k : 0) and, last, of the
+        carry-out; None for an invalid shape."""
+        w = len(terms)
+        h_terms = (C.c_uint64 * max(w, 1))(*[int(t) for t in terms])
+        out = (C.c_uint64 * (w + 1))()
+        return list(out) if self.lib.csgn_uint_add_where_terms(w, k, int(sel_terms), h_terms, out) else None
+
+    def uint_add_where(self, n_bits: int, batch: int, planes, terms, sel, sel_terms: int, k: int, outs=None, carry=False):
+        """csgn_uint_add_where: the w-bit integer `planes` (bit 0 first; plane j a uniform batch of terms[j] terms per
+        element) plus the public constant k in the elements whose encrypted flag `sel` (a uniform batch of sel_terms
+        terms; may be None for k = 0) is set.  Returns (output tensors, carry tensor or None), fresh tensors unless
+        `outs` is given; `carry`: True for a fresh tensor, or the tensor to write."""
+        w = len(planes)
+        assert w == len(terms)
+        T = self.uint_add_where_terms(terms, sel_terms, k)
+        assert T, "bad width, constant or term count"
+        dl = self.default_len(n_bits)
+        sizes = [batch * t * dl for t in T[:w]]
+        if outs is None:
+            outs = [self.empty_words(max(s, 1)) for s in sizes]
+        csize = batch * T[w] * dl
+        if carry is True:
+            carry = self.empty_words(max(csize, 1))
+        elif carry is False:
+            carry = None
+        h_terms = (C.c_uint64 * w)(*[int(t) for t in terms])
+        h_planes = (C.c_void_p * w)(*[_ptr(p) for p in planes])
+        h_outs = (C.c_void_p * w)(*[_ptr(o) for o in outs])
+        check(self.lib.csgn_uint_add_where(n_bits, batch, w, k, _ptr(sel), int(sel_terms), h_planes, h_terms, h_outs,
+                                           _ptr(carry), self.stream))
+        return [o[:s] for o, s in zip(outs, sizes)], (None if carry is None else carry[:csize])
+
     def uint_bitwise(self, n_bits: int, op: int, batch: int, a, a_terms, b=None, b_terms=None, sel=None, sel_terms: int = 0,
                      outs=None):
         """csgn_uint_bitwise: op = 1 a & b, 2 a | b, 3 a ^ b, 4 ~a, 5 sel ? a : b, 6 sel ? a : 0 of the encrypted

@@ -193,6 +193,8 @@ SIGNATURES = {
     "csgn_uint_arith_kernel": (C.c_char_p, [u64, C.c_int, u64, u64, C.POINTER(u64), C.POINTER(u64), C.c_int]),
     "csgn_uint_arith": (C.c_int, [u64, C.c_int, u64, u64, C.POINTER(vp), C.POINTER(u64), C.POINTER(vp), C.POINTER(u64),
                                   C.POINTER(vp), vp, vp]),
+    "csgn_uint_add_where_terms": (C.c_int, [u64, u64, u64, C.POINTER(u64), C.POINTER(u64)]),
+    "csgn_uint_add_where": (C.c_int, [u64, u64, u64, u64, vp, u64, C.POINTER(vp), C.POINTER(u64), C.POINTER(vp), vp, vp]),
     "csgn_uint_bitwise_terms": (u64, [C.c_int, u64, u64, u64]),
     "csgn_uint_bitwise_kernel": (C.c_char_p, [u64, C.c_int, u64, u64, u64, C.POINTER(u64), C.POINTER(u64)]),
     "csgn_uint_bitwise": (C.c_int, [u64, C.c_int, u64, u64, vp, u64, C.POINTER(vp), C.POINTER(u64), C.POINTER(vp),

@@ -932,6 +932,148 @@ const char *bitwiseRoute(int op, uint64_t sel_terms, const std::vector<uint64_t>
     return bitwiseCall(op, sel_terms, a_terms, b_terms, uniform_planes) ? "call" : "planes";
 }
 
+// ------------------------------------------------------------------ a public constant where an encrypted flag is set
+
+namespace {
+
+// Whether addWhere is one csgn_uint_add_where call or the loop below: a ragged mask or plane and integers wider than 32
+// bits take the loop.  Knob uint_add_where_form decides for the rest when it is forced (0 the loop, 1 the call); per
+// shape (measured): the call, but for the class addWhereLoses names.
+bool addWhereCall(unsigned width, bool uniform)
+{
+    if (width > 32 || !uniform)
+        return false;
+    int form = -1;
+    csgn_get_tuning("uint_add_where_form", &form);
+    return form != 0;
+}
+
+// The shape class the one launch lost to the loop's launches (0.60 and 0.62 of the loop's speed at 32 and
+// 16 fresh planes, k = 1, 0.7 and 1.4 GB of outputs; level at 8 planes): one-term planes and flag, ONE set bit in k with 16
+// planes or more above it -- every entry a long prefix product, two terms written for every term staged -- and outputs
+// of 256 MiB or more, where the loop is no longer bound by its launches.  Only where the knob leaves the choice open.
+bool addWhereLoses(const std::vector<uint64_t> &ta, uint64_t ts, uint64_t k, uint64_t count, const Context &ctx)
+{
+    int form = -1;
+    csgn_get_tuning("uint_add_where_form", &form);
+    const unsigned w = (unsigned)ta.size();
+    if (form != -1 || ts != 1 || (k & (k - 1)) != 0 || w - (unsigned)__builtin_ctzll(k) < 16)
+        return false;
+    for (unsigned j = 0; j < w; ++j)
+        if (ta[j] != 1)
+            return false;
+    return count * (2 * (uint64_t)w + 1) * ctx.getDefaultN() * 8 >= (256ull << 20);
+}
+
+// the planes of a + (mask ? k : 0) (csgn_uint_add_where's definition); *carry_out = the last carry
+std::vector<CiphertextBatch> addWherePlanes(const CiphertextBatch &mask, const UIntBatch &a, uint64_t k,
+                                            CiphertextBatch *carry_out, const char *who)
+{
+    requireSameBit(mask, a, who);
+    requireConstant(a, k, who);
+    const unsigned w = a.width();
+    const Context &ctx = a.context();
+    if (a.size() == 0) {
+        if (carry_out)
+            *carry_out = BatchAccess::make(ctx, 0, 1);
+        return std::vector<CiphertextBatch>(w, BatchAccess::make(ctx, 0, 1));
+    }
+    std::vector<CiphertextBatch> out;
+    if (k == 0) {                                         // the source payloads themselves
+        for (unsigned j = 0; j < w; ++j)
+            out.push_back(a.plane(j));
+        if (carry_out)
+            *carry_out = zeros(a);
+        return out;
+    }
+    // every size first: T_j = ta_j + tn_j + C_{j-1}, C_j = ta_j * tn_j + (ta_j + tn_j) * C_{j-1}, each held at 2^31, past
+    // which `checked` refuses it (the products of two such counts fit 64 bits)
+    const Planes in(a);
+    const uint64_t ts = termsOf(mask);
+    const auto sat = [](uint64_t x) { return x < kMaxWords ? x : kMaxWords; };
+    std::vector<uint64_t> T(w);
+    uint64_t c = 0;
+    for (unsigned j = 0; j < w; ++j) {
+        const uint64_t ta = sat(in.terms[j]), tn = ((k >> j) & 1u) ? sat(ts) : 0, ab = sat(ta + tn);
+        T[j] = checked(sat(ab + c), ctx, who);
+        if (j + 1 < w || carry_out)
+            c = sat(sat(ta * tn) + sat(ab * c));
+    }
+    if (carry_out)
+        checked(c, ctx, who);
+    if (addWhereCall(w, in.uniform && mask.uniform()) && !addWhereLoses(in.terms, ts, k, a.size(), ctx)) {
+        out = makePlanes(ctx, a.size(), T);
+        CiphertextBatch carry = BatchAccess::make(ctx, carry_out ? a.size() : 0, carry_out ? c : 1);
+        detail::check(csgn_uint_add_where(ctx.getN(), a.size(), w, k, mask.deviceValues(), ts, sources(in).data(),
+                                          in.terms.data(), wordsOf(out).data(),
+                                          carry_out ? BatchAccess::words(carry) : nullptr, detail::stream()),
+                      "csgn_uint_add_where");
+        if (carry_out)
+            *carry_out = carry;
+        return out;
+    }
+    // the loop: the definition itself through the batch operators
+    const unsigned m = (unsigned)__builtin_ctzll(k);
+    CiphertextBatch carry = mask;                         // c_{j-1}, from plane m on
+    for (unsigned j = 0; j < w; ++j) {
+        const CiphertextBatch &aj = a.plane(j);
+        const bool more = j + 1 < w || carry_out;
+        if (j < m) {
+            out.push_back(aj);
+        } else if (j == m) {
+            out.push_back(aj + mask);
+            if (more)
+                carry = aj * mask;
+        } else if ((k >> j) & 1u) {
+            const CiphertextBatch ab = aj + mask;
+            out.push_back(ab + carry);
+            if (more)
+                carry = (aj * mask) + (ab * carry);
+        } else {
+            out.push_back(aj + carry);
+            if (more)
+                carry = aj * carry;
+        }
+    }
+    if (carry_out)
+        *carry_out = carry;
+    return out;
+}
+
+} // namespace
+
+UIntBatch addWhere(const CiphertextBatch &mask, const UIntBatch &a, uint64_t k, CiphertextBatch *carry_out)
+{
+    return UIntBatch::fromPlanes(addWherePlanes(mask, a, k, carry_out, "addWhere"));
+}
+
+UIntBatch subWhere(const CiphertextBatch &mask, const UIntBatch &a, uint64_t k)
+{
+    requireConstant(a, k, "subWhere");
+    return UIntBatch::fromPlanes(addWherePlanes(mask, a, (0 - k) & maskOf(a.width()), nullptr, "subWhere"));
+}
+
+UIntBatch incrementWhere(const CiphertextBatch &mask, const UIntBatch &a, CiphertextBatch *carry_out)
+{
+    return UIntBatch::fromPlanes(addWherePlanes(mask, a, 1, carry_out, "incrementWhere"));
+}
+
+UIntBatch decrementWhere(const CiphertextBatch &mask, const UIntBatch &a)
+{
+    return UIntBatch::fromPlanes(addWherePlanes(mask, a, maskOf(a.width()), nullptr, "decrementWhere"));
+}
+
+const char *addWhereRoute(unsigned width, bool uniform_operands) { return addWhereCall(width, uniform_operands) ? "call" : "loop"; }
+
+const char *addWhereRoute(const CiphertextBatch &mask, const UIntBatch &a, uint64_t k)
+{
+    const Planes in(a);
+    return k != 0 && a.size() != 0 && addWhereCall(a.width(), in.uniform && mask.uniform()) &&
+                   !addWhereLoses(in.terms, termsOf(mask), k, a.size(), a.context())
+               ? "call"
+               : "loop";
+}
+
 // ------------------------------------------------------------------ selection by a < b (csgn_uint_lt_select)
 
 namespace {

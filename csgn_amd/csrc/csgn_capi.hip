@@ -1987,6 +1987,50 @@ int csgn_uint_arith(uint64_t n_bits, int op, uint64_t batch, uint64_t width, con
     return CSGN_OK;
 }
 
+/* ------------------------------------------------ a public constant added where an encrypted flag is set ---- */
+
+int csgn_uint_add_where_terms(uint64_t width, uint64_t k, uint64_t t_sel, const uint64_t *h_terms, uint64_t *h_out_terms)
+{
+    return csgn::uint_add_where_terms(width, k, t_sel, (const u64 *)h_terms, (u64 *)h_out_terms) ? 1 : 0;
+}
+
+int csgn_uint_add_where(uint64_t n_bits, uint64_t batch, uint64_t width, uint64_t k, const uint64_t *d_sel,
+                        uint64_t t_sel, const uint64_t *const *h_planes, const uint64_t *h_terms,
+                        uint64_t *const *h_outs, uint64_t *d_carry, void *stream)
+{
+    if (int rc = check_n(n_bits))
+        return rc;
+    REQUIRE(width >= 1 && width <= csgn::kAddWhereMaxWidth, "add_where: width %llu outside 1..32",
+            (unsigned long long)width);
+    REQUIRE((k >> width) == 0, "add_where: k = %llu does not fit in %llu bits", (unsigned long long)k,
+            (unsigned long long)width);
+    REQUIRE(h_planes && h_terms && h_outs, "null host pointer");
+    const uint64_t outputs = width + (d_carry ? 1 : 0);
+    const uint64_t dl = csgn_default_len(n_bits);
+    for (uint64_t o = 0; o < outputs; ++o)
+        REQUIRE(csgn::uint_add_where_output_terms(width, k, t_sel, (const u64 *)h_terms, o) != 0,
+                "add_where: the flag or a plane has no terms, or the term count of output %llu overflows",
+                (unsigned long long)o);
+    for (uint64_t o = 0; o < outputs; ++o) {
+        const uint64_t terms = csgn::uint_add_where_output_terms(width, k, t_sel, (const u64 *)h_terms, o);
+        if (int rc = check_size(batch, terms, terms, dl, o == width ? "add_where: the carry" : "add_where: output %llu",
+                                (unsigned long long)o))
+            return rc;
+    }
+    if (int rc = check_planes(h_planes, nullptr, width, "plane"))
+        return rc;
+    if (int rc = check_planes((const uint64_t *const *)h_outs, nullptr, width, "output"))
+        return rc;
+    REQUIRE(k == 0 || d_sel, "add_where: null device pointer (the flag)");
+    if (int rc = require_device("csgn_uint_add_where"))
+        return rc;
+    if (batch == 0)
+        return CSGN_OK;
+    HIP_TRY(csgn::uint_add_where(n_bits, batch, width, k, (const u64 *)d_sel, t_sel, (const u64 *const *)h_planes,
+                                 (const u64 *)h_terms, (u64 *const *)h_outs, (u64 *)d_carry, S(stream)));
+    return CSGN_OK;
+}
+
 /* ------------------------------------------------ the plane-by-plane operators of two integers ---- */
 
 uint64_t csgn_uint_bitwise_terms(int op, uint64_t t_sel, uint64_t t_a, uint64_t t_b)

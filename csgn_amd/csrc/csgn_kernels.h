@@ -310,6 +310,16 @@ const char *uint_arith_kernel_name(u64 n_bits, int op, u64 batch, u64 w, const u
 hipError_t uint_arith(u64 n_bits, int op, u64 batch, u64 w, const u64 *const *a, const u64 *ta, const u64 *const *b,
                       const u64 *tb, u64 *const *out, u64 *carry, hipStream_t stream);
 
+// a + (s ? k : 0) of an encrypted integer, an encrypted flag and a public constant (csgn_uint_add_where.hip),
+// include/csgn_hip.h's definition: uint_arith's ADD chain with b_j = s where k_j = 1 and no b_j where k_j = 0.  a: w =
+// 1..32 planes, terms ta[j]; sel: one batch of ts terms (may be null for k = 0); out: w planes; carry: nullptr = not
+// computed.
+constexpr u32 kAddWhereMaxWidth = 32;
+bool uint_add_where_terms(u64 w, u64 k, u64 ts, const u64 *ta, u64 *T);   // T[0..w]; false: invalid or 2^62 or more
+u64 uint_add_where_output_terms(u64 w, u64 k, u64 ts, const u64 *ta, u64 output);   // 0: invalid or 2^62 or more
+hipError_t uint_add_where(u64 n_bits, u64 batch, u64 w, u64 k, const u64 *sel, u64 ts, const u64 *const *a,
+                          const u64 *ta, u64 *const *out, u64 *carry, hipStream_t stream);
+
 // a & b, a | b, a ^ b, ~a, select(s, a, b) and s * a of encrypted integers, plane by plane (csgn_uint_bitwise.hip),
 // include/csgn_hip.h's definition; op = CSGN_UINT_BITWISE_*.  a and b: w = 1..64 planes, terms ta[j] / tb[j]; sel: one
 // batch of ts terms; out: w planes.  Operands the op does not read: their counts are ignored, their pointers may be null.

@@ -35,6 +35,7 @@ const Knob kKnobs[TUNE_COUNT] = {
     {"uint_lut_fused", -1},
     {"uint_read_fused", -1},
     {"uint_addk_fused", -1},
+    {"uint_add_where_form", -1},
     {"uint_find_form", -1},
     {"uint_find_rparts", 0},
     {"matmul_form", -1},

@@ -54,6 +54,7 @@ enum TuneKey {
     TUNE_UINT_LUT_FUSED, // public lookup tables (csgn_uint_lut.hip): -1 = per shape, 0 = composed form (the tuned launchers monomial by monomial), 1 = fused kernel
     TUNE_UINT_READ_FUSED, // encrypted tables read at encrypted indices (csgn_uint_read.hip): -1 = per shape, 0 = composed form (the tuned launchers row by row), 1 = fused kernel
     TUNE_UINT_ADDK_FUSED, // integer + public constant (csgn_uint_addk.hip): -1 = per shape, 0 = composed form (the tuned launchers plane by plane), 1 = fused kernel
+    TUNE_UINT_ADD_WHERE_FORM, // knob "uint_add_where_form": addWhere, subWhere, incrementWhere and decrementWhere of the classes (certfhe/UInt.h): -1 = per shape, 0 = the loop over the planes through the batch operators, 1 = one csgn_uint_add_where call where it can run; the C call itself is always the kernel
     TUNE_UINT_FIND_FORM, // encrypted tables looked up by encrypted key (csgn_uint_find.hip): -1 = per shape, 0 = composed form (the tuned launchers row by row), 1 = fused kernel
     TUNE_UINT_FIND_RPARTS, // ... row parts of one k_uint_find launch at most, 0 = what a launch's workgroups allow (every shape within memory: one launch); a test sets it low to run the host's split of the rows into several launches
     TUNE_MATMUL_FORM,    // products of encrypted bit matrices (csgn_matmul.hip): -1 = per shape, 0 = composed form (both operands tiled by the gather launcher, one uniform multiply), 1 = fused kernel

@@ -106,6 +106,30 @@
 // (one kernel for every plane and the carry-out); ragged ones are composed from the CiphertextBatch operators and
 // Gates.h with the same words.  Every plane's size is checked before anything is allocated.
 //
+// A PUBLIC CONSTANT WHERE AN ENCRYPTED FLAG IS SET (k < 2^width, the same for every element; std::invalid_argument
+// otherwise): addWhere(mask, a, k) is a + (mask ? k : 0) mod 2^w -- a private counter hits += [key == q], a vote, a
+// conditional accumulation of a public amount, the carry-in of an add, a conditional + 1.  It spends terms only where k
+// has a set bit: the ADD chain of a + b with b_j = mask where k_j = 1 and NO b_j where k_j = 0, csgn_uint_add_where's
+// words (include/csgn_hip.h).  With m the lowest set bit of k:
+//     addWhere(mask, a, k)       k == 0: the planes of a themselves (the same payloads).  out_j = a_j (j < m), a_m + mask
+//                                (c = a_m * mask), then k_j ? (a_j + mask) + c : a_j + c, with the carry
+//                                k_j ? (a_j * mask) + ((a_j + mask) * c) : a_j * c
+//     ..., &carry)               the same planes, and the c left after the top plane (ZERO when k == 0)
+//     subWhere(mask, a, k)       addWhere(mask, a, (2^w - k) mod 2^w); its carry is no borrow and is not offered
+//     incrementWhere(mask, a)    k = 1                decrementWhere(mask, a)    k = 2^w - 1
+// Sizes, fresh a and mask, all planes and the carry together (through a + keepWhere(mask, constant): 518 at w = 8, 131 086
+// at w = 16, and nothing past 16 planes):
+//     w = 8, k = 1      17 (2 a plane, carry 1)              w = 8, k = 0x64    31 (1,1,2,2,2,3,5,8; carry 7)
+//     w = 8, k = 0xFF   518 (2,3,5,9,17,33,65,129; 255)      w = 16, k = 1      33              w = 32, k = 1      65
+// Uniform operands of width <= 32 take ONE csgn_uint_add_where (one launch for every plane and the carry) -- but for
+// the shape class the launch lost to the loop's launches in DESIGN 4.35 (0.6 of their speed): one-term planes and mask
+// under a k of ONE set bit with 16 planes or more above it, at 256 MiB of outputs or more, which stays on the loop; a
+// ragged mask or plane (a compact() result) and widths 33..64 take the loop too, the table above through CiphertextBatch::operator+ / operator* in exactly
+// its order, with the same words.  Knob uint_add_where_form (csgn_set_tuning, or CSGN_UINT_ADD_WHERE_FORM when the
+// library loads) forces the loop (0) or the call where it can run (1); addWhereRoute names the route.  Every size is
+// computed before anything is allocated: std::invalid_argument for mismatched contexts or counts, k >= 2^w, or an output
+// past 2^31 words per element.  An empty batch gives empty planes.
+//
 // BITWISE OPERATORS AND SHIFTS.  Between two integers of one width, context and count, per plane:
 //     a & b              a_j * b_j            a | b     logicOr(a_j, b_j)            a ^ b     a_j + b_j
 // With a public constant (k < 2^width) and for a public distance s nothing is computed on ciphertext words beyond a
@@ -410,6 +434,21 @@ UIntBatch keepWhere(const CiphertextBatch &mask, const UIntBatch &a);
 // diagnostics and tests, like arithRoute: the words are the same.
 const char *bitwiseRoute(int op, uint64_t sel_terms, const std::vector<uint64_t> &a_terms, const std::vector<uint64_t> &b_terms,
                          bool uniform_planes);
+
+// element i: a[i] + (mask[i] ? k : 0) mod 2^width, k < 2^width public (the block "A PUBLIC CONSTANT WHERE AN ENCRYPTED
+// FLAG IS SET" above); mask of a's context and count.  *carry_out (may be null) = the bit that left the top plane.
+UIntBatch addWhere(const CiphertextBatch &mask, const UIntBatch &a, uint64_t k, CiphertextBatch *carry_out = nullptr);
+UIntBatch subWhere(const CiphertextBatch &mask, const UIntBatch &a, uint64_t k);          // addWhere(mask, a, (2^w - k) mod 2^w)
+UIntBatch incrementWhere(const CiphertextBatch &mask, const UIntBatch &a, CiphertextBatch *carry_out = nullptr);   // k = 1
+UIntBatch decrementWhere(const CiphertextBatch &mask, const UIntBatch &a);                // k = 2^w - 1
+// The route addWhere and its kin take for an integer of `width` planes, the mask and every plane uniform or not, under
+// the calling thread's knobs (a static string): "call" (one csgn_uint_add_where) or "loop" (the table through the
+// CiphertextBatch operators).  No device work; for diagnostics and tests, like arithRoute: the words are the same.
+const char *addWhereRoute(unsigned width, bool uniform_operands);
+// The same for one call's operands, with the per-shape rule of the measurement: the loop also for the shape class the
+// one launch lost (one-term planes and mask, one set bit in k with 16 planes or more above it, 256 MiB of outputs or
+// more), and for k = 0 and an empty batch, which launch nothing.
+const char *addWhereRoute(const CiphertextBatch &mask, const UIntBatch &a, uint64_t k);
 
 // element i: a[i] < b[i] ? a[i] : b[i] / the other one; a tie takes b for min and a for max
 UIntBatch min(const UIntBatch &a, const UIntBatch &b);

@@ -1097,6 +1097,51 @@ int csgn_uint_arith(uint64_t n_bits, int op, uint64_t batch, uint64_t width, con
                     const uint64_t *h_a_terms, const uint64_t *const *h_b, const uint64_t *h_b_terms,
                     uint64_t *const *h_out, uint64_t *d_carry, void *stream);
 
+/* ------------------------------------- a public constant added where an encrypted flag is set ---- */
+
+/* csgn_uint_add_where: a + (s ? k : 0) mod 2^w, every plane of the result and the carry out of the top plane in one
+ * launch: what certfhe/UInt.h's addWhere, subWhere, incrementWhere and decrementWhere compute.  The inputs are:
+ *   - a, an integer of w planes a_0 ... a_{w-1}, bit 0 first, plane j uniform with ta_j terms per element;
+ *   - s, one uniform batch of ts terms per element, one encrypted bit per element;
+ *   - k < 2^w, public and the same for every element.
+ * The operation is a fixed composition of the reference's operator+ (concatenation) and operator* (all-pairs AND, the
+ * left term slow).  It is the ADD chain of csgn_uint_step with b_j = s where k_j = 1 and b_j ABSENT where k_j = 0:
+ *     k == 0:            out_j = a_j for every j (a copy: the same terms in the same order); carry-out = ZERO (one term)
+ *     m = lowest set bit of k
+ *     j <  m:            out_j = a_j
+ *     j == m:            out_m = a_m + s                      c = a_m * s                          (ADD_HALF(a_m, s))
+ *     j >  m, k_j = 1:   out_j = (a_j + s) + c                c = (a_j * s) + ((a_j + s) * c)      (ADD_FULL(c, a_j, s))
+ *     j >  m, k_j = 0:   out_j = a_j + c                      c = a_j * c                          (ADD_FULL without b: a_j the LEFT operand)
+ *     carry-out (optional, output index w) = the c left after j = w-1
+ * Terms.  Let tn_j = k_j ? ts : 0 and C_{m-1} = 0.  Then T_j = ta_j + tn_j + C_{j-1} and C_j = ta_j * tn_j + (ta_j +
+ * tn_j) * C_{j-1}.  The carry-out has C_{w-1} terms.  This is csgn_uint_arith's ADD formula with tb_j := tn_j.  Fresh a
+ * and s: a + (s ? 1 : 0) has 2 terms in every plane and a carry of 1, 2w + 1 in all, for every width.
+ * Order.  It is also that formula's order.  Plane j is [a_j | s (k_j = 1) | the entries of c_{j-1}].  Entry q of c_j,
+ * for q < ta_j * tn_j, is term q / tn_j of a_j ANDed with term q % tn_j of s, which ends the walk.  Otherwise, with q' =
+ * q - ta_j * tn_j, it is term q' / C_{j-1} of the concatenation a_j | s ANDed with entry q' % C_{j-1} of c_{j-1}.
+ * In clear bits: where k_j = 1, c' = maj(a_j, s, c); where k_j = 0, c' = a_j * c.  An entry may hold several terms of
+ * s: they pile up through (a_j + s) * c, and nothing cancels.
+ * Derived operations add no words:
+ *     a - (s ? k : 0) = a + (s ? (2^w - k) mod 2^w : 0), planes only: its carry is not a borrow
+ *     increment and decrement where set are k = 1 and k = 2^w - 1 */
+/* width + 1 counts into h_out_terms, the last the carry-out's (host only).  Returns 1, or 0 (h_out_terms not written) for
+ * a width outside 1..32, k >= 2^width, a null pointer, t_sel or a plane of 0 terms, or a count of 2^62 or more. */
+int csgn_uint_add_where_terms(uint64_t width, uint64_t k, uint64_t t_sel, const uint64_t *h_terms, uint64_t *h_out_terms);
+/* The operation over `batch` elements.  h_planes and h_outs are HOST arrays of `width` device pointers: plane j takes
+ * batch * h_terms[j] * dL words and output j batch * T_j * dL words.  d_carry takes batch * C_{w-1} * dL words, or is
+ * NULL: the carry is then neither computed nor written.  Inputs may alias one another; d_sel may BE a plane of a.  No
+ * output overlaps an input or another output.  Checks, in this order, the first that fails giving the status: n_bits;
+ * the width and k; the host pointers; the term counts (CSGN_ERR_INVALID); every output's T * dL below 2^31 words per
+ * element and batch times that below 2^60 (CSGN_ERR_UNSUPPORTED; computed without wrap-around); null device pointers,
+ * among them d_sel where k != 0 (CSGN_ERR_INVALID); the device (CSGN_ERR_NO_DEVICE, no CPU fallback).  batch == 0
+ * succeeds.  Nothing is allocated or launched before every check has passed.  On the caller's stream, asynchronous; one
+ * launch for every shape within memory (k_uint_add_where) and graph-capturable.  The width stops at 32 here
+ * because the kernel's arguments stay within 4 KB; certfhe/UInt.h composes wider integers. */
+int csgn_uint_add_where(uint64_t n_bits, uint64_t batch, uint64_t width, uint64_t k,
+                        const uint64_t *d_sel, uint64_t t_sel,
+                        const uint64_t *const *h_planes, const uint64_t *h_terms,
+                        uint64_t *const *h_outs, uint64_t *d_carry, void *stream);
+
 /* ------------------------------------- the plane-by-plane operators of encrypted integers ---- */
 
 /* a & b, a | b, a ^ b, ~a, select(s, a, b) and the mask s * a of ENCRYPTED integers, every plane in one launch: what
