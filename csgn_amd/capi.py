@@ -220,6 +220,7 @@ SIGNATURES = {
     "csgn_reset_tuning": (None, []),
     "csgn_tuning_name": (C.c_char_p, [C.c_int]),
     "csgn_debug_fastdiv": (C.c_uint32, [C.c_uint32, C.c_uint32]),
+    "csgn_debug_block_order": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32]),
 }
 
 

@@ -2,6 +2,7 @@
 // Argument validation, error reporting and stream plumbing only; the kernels live in the other translation units, behind
 // the launchers of csgn_kernels.h.  There is deliberately no CPU fallback anywhere in this library.
 #include "csgn_capi_util.h"
+#include "csgn_device.h"
 #include "csgn_tuning.h"
 
 #include <sys/random.h>
@@ -2369,6 +2370,13 @@ const char *csgn_tuning_name(int index) { return csgn::tune_name(index); }
 uint32_t csgn_debug_fastdiv(uint32_t n, uint32_t d)
 {
     return csgn_fastdiv(n, csgn_fastdiv_make(d));
+}
+
+/* debug hook used by the CPU tests to pin the workgroup orders of csgn_device.h: xcd_grouped_block, whose group 0 is
+ * xcd_contiguous_block */
+uint32_t csgn_debug_block_order(uint32_t b, uint32_t nblocks, uint32_t group)
+{
+    return csgn::xcd_grouped_block(b, nblocks, group);
 }
 
 } // extern "C"

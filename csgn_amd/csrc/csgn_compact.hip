@@ -1520,7 +1520,7 @@ hipError_t compact_launch(u32 U, u64 dL, u64 batch, u64 total_terms, u64 max_ter
     const size_t lds = main_lds_bytes(g.capT, wide_groups ? kCRWide : kCR);
     const int grid = tune(TUNE_COMPACT_GRID) > 0 ? tune(TUNE_COMPACT_GRID) : 512;      // two workgroups per CU
     if (wide_groups)
-        k_compact_main<Unit, kCRWide><<<(u32)min(ng, (u64)grid / 2), kCT, lds, s>>>(a);       // one workgroup per CU
+        k_compact_main<Unit, kCRWide><<<(u32)min(ng, max((u64)grid / 2, (u64)1)), kCT, lds, s>>>(a);   // one workgroup per CU (compact_grid = 1: one in all)
     else
         k_compact_main<Unit, kCR><<<(u32)min(ng, (u64)grid), kCT, lds, s>>>(a);
     return hipGetLastError();

@@ -95,11 +95,13 @@ inline u64 launch_blocks()
 // a speed matter only, never correctness).  Remapping the block id so that XCD x owns the
 // x-th contiguous eighth of the logical block range makes every XCD's L2 write back one
 // sequential address stream instead of every 8th 4 KiB chunk: +5 % on a pure fill
-// (tools/wbench.hip: 6.9 -> 7.3 TB/s).  Bijective for any grid size.
-__device__ inline u32 xcd_contiguous_block(u32 b, u32 nblocks)
+// (tools/wbench.hip: 6.9 -> 7.3 TB/s).  Bijective for any grid size, and only on the grid of the launch itself:
+// nblocks is that launch's workgroup count.  Callable from the host so that the CPU tests pin it
+// (csgn_debug_block_order, tests/test_capi_symbols.py).
+__host__ __device__ inline u32 xcd_contiguous_block(u32 b, u32 nblocks)
 {
     const u32 q = nblocks >> 3, r = nblocks & 7u, x = b & 7u;
-    return x * q + min(x, r) + (b >> 3);
+    return x * q + (x < r ? x : r) + (b >> 3);
 }
 
 // The same with the XCDs taking GROUPS of `group` consecutive logical blocks in turn (XCD x owns groups x, x + 8, ...)
@@ -108,7 +110,7 @@ __device__ inline u32 xcd_contiguous_block(u32 b, u32 nblocks)
 // is spread over all eight XCDs instead of being the tail of ONE (round 5: 640 such workgroups, 6 % of the output,
 // were 2.5 rounds of 32 CUs at the end of a launch the other 224 CUs had left).  group = 0: the contiguous eighths.
 // Bijective for any grid size: the blocks past the last whole round of 8 groups keep their own index.
-__device__ inline u32 xcd_grouped_block(u32 b, u32 nblocks, u32 group)
+__host__ __device__ inline u32 xcd_grouped_block(u32 b, u32 nblocks, u32 group)
 {
     if (group == 0u)
         return xcd_contiguous_block(b, nblocks);

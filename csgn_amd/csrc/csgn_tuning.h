@@ -5,7 +5,12 @@
 // value of the environment variable CSGN_<KEY IN CAPITALS> sampled ONCE when libcsgn_hip.so is
 // loaded; after that only csgn_set_tuning()/csgn_reset_tuning() (include/csgn_hip.h) change it.
 // No compute entry point reaches getenv.  Knobs select among kernels that compute the same
-// words: results never depend on them (tests/test_gpu_parity.py drives every form through them).
+// words: results never depend on them.  The GPU tests drive the forms through them: tests/test_gpu_parity.py (the
+// multiply, encrypt, decrypt, permutation, compaction and ragged forms), each operation's own tests/test_*_gpu.py and
+// class-level tests/test_*_cpp.py (its form knob), tests/test_launch_split_gpu.py (launch_blocks),
+// tests/test_block_order_gpu.py (stream_xcd), tests/test_ragged_order_gpu.py (the ragged block orders and slices) and
+// tests/test_knob_forms_gpu.py (mul_bs, mul_xcd = 2, the compaction's grid, shared_gpu).  tests/test_tuning_ledger.py
+// names the file for every knob and fails for a knob that none sets; zero_memset is the one exemption.
 #pragma once
 
 namespace csgn {

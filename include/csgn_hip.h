@@ -1622,6 +1622,10 @@ const char *csgn_tuning_name(int index);
  * use (csgn_amd/csrc/csgn_common.h); lets the CPU tests pin it without a GPU. */
 uint32_t csgn_debug_fastdiv(uint32_t n, uint32_t d);
 
+/* Debug hook: the logical index that workgroup b of a launch of nblocks workgroups takes under the XCD block orders
+ * the kernels use (csgn_amd/csrc/csgn_device.h): group = 0 is xcd_contiguous_block, group > 0 xcd_grouped_block. */
+uint32_t csgn_debug_block_order(uint32_t b, uint32_t nblocks, uint32_t group);
+
 #ifdef __cplusplus
 }
 #endif

@@ -99,6 +99,53 @@ def test_fastdiv_helper_is_exact(lib):
             assert lib.csgn_debug_fastdiv(n, d) == n // d, (n, d)
 
 
+BLOCK_ORDER_GROUPS = (0, 1, 2, 3, 5, 64, 100)
+
+
+def test_block_orders_are_bijections_with_the_documented_runs(lib):
+    """xcd_contiguous_block and xcd_grouped_block (csgn_device.h) through csgn_debug_block_order, for every grid of 1 to
+    4104 workgroups (eight rounds of group 64 and a tail of 8) and every group the kernels run with or a test sets.
+    Workgroup b runs on XCD b % 8.
+    Every (grid, group): the image of [0, nblocks) is [0, nblocks).
+    group 0: the workgroups of XCD x, in order of b, take one run of consecutive indices, and the runs of x = 0..7 follow
+    one another from 0: XCD x owns the x-th contiguous eighth.
+    group > 0: every workgroup at or past the last whole round of 8 * group keeps its index; inside the whole rounds
+    the workgroups of XCD x, in order of b, take runs of `group` consecutive indices: groups x, x + 8, x + 16, ...
+    Then grids around kMaxBlocks256 = (2^32 - 1) / 256, every residue mod 8: the first and the last 64 workgroups land
+    inside the grid, on different indices (the arithmetic is 32-bit)."""
+    from tests.cpp_driver import build
+    fill = C.CDLL(build("tests/cpp/block_order_fill.cpp", "tests/cpp/libblock_order_fill.so", libs=("csgn_hip",),
+                        shared=True)).block_order_fill
+    fill.argtypes, fill.restype = [C.c_uint32, C.c_uint32, C.c_void_p], None
+    top = 4104
+    ident = np.arange(top, dtype=np.uint32)
+    img = np.empty(top, dtype=np.uint32)
+    for group in BLOCK_ORDER_GROUPS:
+        for nb in range(1, top + 1):
+            img[:] = 0xFFFFFFFF
+            fill(nb, group, img.ctypes.data)
+            got = img[:nb]
+            assert np.array_equal(np.sort(got), ident[:nb]), (nb, group, "not a bijection")
+            if group == 0:
+                runs = np.concatenate([got[x::8] for x in range(8)])
+                assert np.array_equal(runs, ident[:nb]), (nb, "XCD runs are not the contiguous eighths, in order")
+                continue
+            full = nb - nb % (8 * group)
+            assert np.array_equal(got[full:], ident[full:nb]), (nb, group, "a workgroup of the tail moved")
+            rounds = full // (8 * group)
+            for x in range(8 if rounds else 0):
+                mine = got[x:full:8].reshape(rounds, group)
+                starts = (np.arange(rounds, dtype=np.uint32) * 8 + x) * group
+                assert np.array_equal(mine, starts[:, None] + ident[None, :group]), (nb, group, x)
+    k_max_blocks_256 = (2**32 - 1) // 256
+    for nb in range(k_max_blocks_256 - 8, k_max_blocks_256 + 2):
+        for group in BLOCK_ORDER_GROUPS:
+            ends = list(range(64)) + list(range(nb - 64, nb))
+            got = [lib.csgn_debug_block_order(b, nb, group) for b in ends]
+            assert all(0 <= g < nb for g in got) and len(set(got)) == len(ends), (nb, group)
+    assert lib.csgn_debug_block_order(5, 19, 0) == 13 and lib.csgn_debug_block_order(9, 19, 1) == 9   # by hand
+
+
 def test_plane_entry_points_reject_in_order(lib):
     """csgn_uint_plain and csgn_uint_addk over the sweep of tests/test_uint_plain_cpu.py: the status is that of the
     first check that fails -- n_bits, the comparison, width and constant, host pointers, the term counts (INVALID),

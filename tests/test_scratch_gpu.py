@@ -12,6 +12,7 @@ everything back when it ends: the counts below are exact whatever ran before.
 Shapes: N = 1247 (even dL: 16-byte units) and 1300 (odd dL: 8-byte units), index width 3 with planes of 1..3 terms, 5
 rows (8 in the nine-stream read), a small batch of 7 and a large one of 56.  Run with `pytest -m gpu` on an MI355X."""
 import ctypes as C
+import gc
 import threading
 
 import numpy as np
@@ -457,9 +458,20 @@ def test_a_temporary_past_the_kept_size_belongs_to_its_call(hip):
 # ------------------------------------------------------------------------------ capture
 
 def capture(stream, body):
+    """body() captured on `stream`.  The capture is in torch's global error mode, where a HIP call that capture forbids,
+    from any thread, breaks the capture and can end the process; a cyclic collection that starts inside it may finalize whatever an earlier test
+    left behind, device memory and graphs among it, and torch.cuda.graph no longer collects before it begins.  So the
+    garbage goes first and the collector stays off until the capture has ended."""
     g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=stream):
-        body()
+    gc.collect()
+    was_on = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.graph(g, stream=stream):
+            body()
+    finally:
+        if was_on:
+            gc.enable()
     torch.cuda.synchronize()
     return g
 
