@@ -639,6 +639,35 @@ class HipPath:
                                            _ptr(carry), self.stream))
         return [o[:s] for o, s in zip(outs, sizes)], (None if carry is None else carry[:csize])
 
+    def uint_linear_plan(self, n_bits: int, batch: int, terms, rows, constant: int = 0):
+        """csgn_uint_linear_plan: [unit bytes, units per element, G, tiles, workgroups per tile, launches, tile budget,
+        plane groups] of a csgn_uint_linear call of this shape under the calling thread's knobs."""
+        h_terms = (C.c_uint64 * max(len(terms), 1))(*[int(t) for t in terms])
+        h_rows = (C.c_uint64 * max(len(rows), 1))(*[int(r) for r in rows])
+        plan = (C.c_uint64 * 8)()
+        check(self.lib.csgn_uint_linear_plan(n_bits, batch, len(terms), h_terms, len(rows), h_rows, int(constant), plan))
+        return [int(x) for x in plan]
+
+    def uint_linear(self, n_bits: int, batch: int, planes, terms, rows, constant: int = 0, outs=None):
+        """csgn_uint_linear: the public matrix `rows` over F2 (rows[j]: the mask of the input planes output plane j
+        sums) applied to the encrypted integer `planes` (bit 0 first; plane i a uniform batch of terms[i] terms per
+        element), plus ONE in the planes whose bit of `constant` is set.  Returns the output planes, of
+        csgn_uint_linear_terms terms per element, fresh ones unless `outs` is given."""
+        w, m = len(planes), len(rows)
+        assert w == len(terms)
+        h_terms = (C.c_uint64 * max(w, 1))(*[int(t) for t in terms])
+        T = [int(self.lib.csgn_uint_linear_terms(w, h_terms, int(rows[j]), (int(constant) >> j) & 1)) for j in range(m)]
+        assert m and all(T), "bad width, row or term count"
+        dl = self.default_len(n_bits)
+        sizes = [batch * t * dl for t in T]
+        if outs is None:
+            outs = [self.empty_words(max(s, 1)) for s in sizes]
+        h_in = (C.c_void_p * w)(*[_ptr(p) for p in planes])
+        h_rows = (C.c_uint64 * m)(*[int(r) for r in rows])
+        h_out = (C.c_void_p * m)(*[_ptr(o) for o in outs])
+        check(self.lib.csgn_uint_linear(n_bits, batch, w, h_in, h_terms, m, h_rows, int(constant), h_out, self.stream))
+        return [o[:s] for o, s in zip(outs, sizes)]
+
     def uint_bitwise(self, n_bits: int, op: int, batch: int, a, a_terms, b=None, b_terms=None, sel=None, sel_terms: int = 0,
                      outs=None):
         """csgn_uint_bitwise: op = 1 a & b, 2 a | b, 3 a ^ b, 4 ~a, 5 sel ? a : b, 6 sel ? a : 0 of the encrypted

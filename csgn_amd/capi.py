@@ -199,7 +199,12 @@ SIGNATURES = {
     "csgn_uint_bitwise_kernel": (C.c_char_p, [u64, C.c_int, u64, u64, u64, C.POINTER(u64), C.POINTER(u64)]),
     "csgn_uint_bitwise": (C.c_int, [u64, C.c_int, u64, u64, vp, u64, C.POINTER(vp), C.POINTER(u64), C.POINTER(vp),
                                     C.POINTER(u64), C.POINTER(vp), vp]),
-    "csgn_uint_decrypt_kernel": (C.c_char_p, [u64, u64, u64, C.POINTER(u64)]),
+    "csgn_uint_linear_terms": (u64, [u64, C.POINTER(u64), u64, C.c_int]),
+    "csgn_uint_linear_decode": (C.c_int, [u64, C.POINTER(u64), u64, C.c_int, u64, C.POINTER(u64), C.POINTER(u64)]),
+    "csgn_uint_linear_plan": (C.c_int, [u64, u64, u64, C.POINTER(u64), u64, C.POINTER(u64), u64, C.POINTER(u64)]),
+    "csgn_uint_linear": (C.c_int, [u64, u64, u64, C.POINTER(vp), C.POINTER(u64), u64, C.POINTER(u64), u64,
+                                   C.POINTER(vp), vp]),
+    "csgn_uint_decrypt_kernel":(C.c_char_p, [u64, u64, u64, C.POINTER(u64)]),
     "csgn_uint_decrypt": (C.c_int, [u64, u64, u64, C.POINTER(vp), C.POINTER(u64), C.POINTER(vp), C.POINTER(u64),
                                     C.POINTER(u64), vp, vp, vp]),
     "csgn_matmul_terms": (u64, [u64, u64, u64]),

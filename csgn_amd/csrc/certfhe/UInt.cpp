@@ -1074,6 +1074,266 @@ const char *addWhereRoute(const CiphertextBatch &mask, const UIntBatch &a, uint6
                : "loop";
 }
 
+// ------------------------------------------------------------------ public linear maps over F2 (csgn_uint_linear)
+
+namespace {
+
+void requireMatrixWidth(unsigned w, const char *who)
+{
+    if (w < 1 || w > 64)
+        throw std::invalid_argument(std::string("certFHE::F2Matrix::") + who + ": width must be 1..64");
+}
+
+void requireMatrixConstant(unsigned w, uint64_t k, const char *who)
+{
+    requireMatrixWidth(w, who);
+    if (w < 64 && (k >> w))
+        throw std::invalid_argument(std::string("certFHE::F2Matrix::") + who + ": the constant does not fit in the width");
+}
+
+uint64_t lowBits(unsigned w) { return w >= 64 ? ~0ull : (1ull << w) - 1; }
+
+// rows[j] = the mask of the input bits i with source(j) == i, for the maps that move bits (-1: none)
+template <typename Source>
+std::vector<uint64_t> movedRows(unsigned w, Source source)
+{
+    std::vector<uint64_t> rows(w, 0);
+    for (unsigned j = 0; j < w; ++j) {
+        const int i = source(j);
+        if (i >= 0)
+            rows[j] = 1ull << i;
+    }
+    return rows;
+}
+
+} // namespace
+
+F2Matrix F2Matrix::fromRows(const std::vector<uint64_t> &rows, unsigned in_width)
+{
+    requireMatrixWidth(in_width, "fromRows");
+    requireMatrixWidth((unsigned)(rows.size() > 64 ? 65 : rows.size()), "fromRows");
+    for (size_t j = 0; j < rows.size(); ++j)
+        if (rows[j] & ~lowBits(in_width))
+            throw std::invalid_argument("certFHE::F2Matrix::fromRows: a row names a bit at or above the input width");
+    return F2Matrix(rows, in_width);
+}
+
+F2Matrix F2Matrix::identity(unsigned w)
+{
+    requireMatrixWidth(w, "identity");
+    return F2Matrix(movedRows(w, [](unsigned j) { return (int)j; }), w);
+}
+
+F2Matrix F2Matrix::shiftLeft(unsigned w, unsigned s)
+{
+    requireMatrixWidth(w, "shiftLeft");
+    return F2Matrix(movedRows(w, [&](unsigned j) { return j >= s ? (int)(j - s) : -1; }), w);
+}
+
+F2Matrix F2Matrix::shiftRight(unsigned w, unsigned s)
+{
+    requireMatrixWidth(w, "shiftRight");
+    return F2Matrix(movedRows(w, [&](unsigned j) { return s < w && j < w - s ? (int)(j + s) : -1; }), w);
+}
+
+F2Matrix F2Matrix::rotateLeft(unsigned w, unsigned s)
+{
+    requireMatrixWidth(w, "rotateLeft");
+    return F2Matrix(movedRows(w, [&](unsigned j) { return (int)((j + w - s % w) % w); }), w);
+}
+
+F2Matrix F2Matrix::rotateRight(unsigned w, unsigned s)
+{
+    requireMatrixWidth(w, "rotateRight");
+    return rotateLeft(w, w - s % w);
+}
+
+F2Matrix F2Matrix::mask(unsigned w, uint64_t k)
+{
+    requireMatrixConstant(w, k, "mask");
+    return F2Matrix(movedRows(w, [&](unsigned j) { return (k >> j) & 1u ? (int)j : -1; }), w);
+}
+
+F2Matrix F2Matrix::clmul(unsigned w, uint64_t k)
+{
+    requireMatrixConstant(w, k, "clmul");
+    std::vector<uint64_t> rows(w, 0);
+    for (unsigned j = 0; j < w; ++j)
+        for (unsigned i = 0; i <= j; ++i)                 // bit j of the product: the XOR of x_{j-i} over the set k_i
+            if ((k >> i) & 1u)
+                rows[j] |= 1ull << (j - i);
+    return F2Matrix(rows, w);
+}
+
+F2Matrix F2Matrix::gfMul(unsigned w, uint64_t k, uint64_t poly)
+{
+    requireMatrixConstant(w, k, "gfMul");
+    if (w < 64 && (poly >> w) > 1)
+        throw std::invalid_argument("certFHE::F2Matrix::gfMul: the polynomial has a term above X^w");
+    const uint64_t low = poly & lowBits(w);
+    std::vector<uint64_t> rows(w, 0);
+    uint64_t c = k;                                       // k * X^i mod poly: column i
+    for (unsigned i = 0; i < w; ++i) {
+        for (unsigned j = 0; j < w; ++j)
+            if ((c >> j) & 1u)
+                rows[j] |= 1ull << i;
+        const bool carry = (c >> (w - 1)) & 1u;
+        c = (c << 1) & lowBits(w);
+        if (carry)
+            c ^= low;
+    }
+    return F2Matrix(rows, w);
+}
+
+F2Matrix F2Matrix::grayEncode(unsigned w)
+{
+    requireMatrixWidth(w, "grayEncode");
+    return identity(w) ^ shiftRight(w, 1);
+}
+
+F2Matrix F2Matrix::grayDecode(unsigned w)
+{
+    requireMatrixWidth(w, "grayDecode");
+    std::vector<uint64_t> rows(w);
+    for (unsigned j = 0; j < w; ++j)
+        rows[j] = lowBits(w) & ~lowBits(j);
+    return F2Matrix(rows, w);
+}
+
+uint64_t F2Matrix::apply(uint64_t x) const
+{
+    uint64_t y = 0;
+    for (size_t j = 0; j < rows_.size(); ++j)
+        y |= (uint64_t)(__builtin_popcountll(rows_[j] & x) & 1) << j;
+    return y;
+}
+
+F2Matrix F2Matrix::operator^(const F2Matrix &rhs) const
+{
+    if (in_ != rhs.in_ || rows_.size() != rhs.rows_.size())
+        throw std::invalid_argument("certFHE::F2Matrix::operator^: the maps differ in shape");
+    std::vector<uint64_t> rows(rows_);
+    for (size_t j = 0; j < rows.size(); ++j)
+        rows[j] ^= rhs.rows_[j];
+    return F2Matrix(rows, in_);
+}
+
+F2Matrix F2Matrix::operator*(const F2Matrix &rhs) const
+{
+    if (in_ != rhs.outWidth())
+        throw std::invalid_argument("certFHE::F2Matrix::operator*: the left map's input width is not the right map's output width");
+    std::vector<uint64_t> rows(rows_.size(), 0);
+    for (size_t j = 0; j < rows.size(); ++j)
+        for (unsigned i = 0; i < in_; ++i)
+            if ((rows_[j] >> i) & 1u)
+                rows[j] ^= rhs.rows_[i];                  // a bit both branches contribute cancels here
+    return F2Matrix(rows, rhs.in_);
+}
+
+namespace {
+
+// what linearMap does with row j: the constant batch, the source plane's own payload, or a computed plane
+enum { LINEAR_CONSTANT, LINEAR_SHARED, LINEAR_COMPUTED };
+
+int linearKind(uint64_t row, bool one)
+{
+    if (row == 0)
+        return LINEAR_CONSTANT;
+    return (row & (row - 1)) == 0 && !one ? LINEAR_SHARED : LINEAR_COMPUTED;
+}
+
+void requireLinear(const UIntBatch &a, const F2Matrix &m, uint64_t constant, const char *who)
+{
+    if (a.width() != m.inWidth())
+        throw std::invalid_argument(std::string("certFHE::") + who + ": the integer's width is not the map's input width");
+    if (m.outWidth() < 64 && (constant >> m.outWidth()))
+        throw std::invalid_argument(std::string("certFHE::") + who + ": the constant does not fit in the map's output width");
+}
+
+bool linearComputes(const F2Matrix &m, uint64_t constant)
+{
+    for (unsigned j = 0; j < m.outWidth(); ++j)
+        if (linearKind(m.rows()[j], (constant >> j) & 1u) == LINEAR_COMPUTED)
+            return true;
+    return false;
+}
+
+} // namespace
+
+UIntBatch linearMap(const UIntBatch &a, const F2Matrix &m, uint64_t constant)
+{
+    requireLinear(a, m, constant, "linearMap");
+    const unsigned w = a.width(), mw = m.outWidth();
+    const Context &ctx = a.context();
+    if (a.size() == 0)
+        return UIntBatch::fromPlanes(std::vector<CiphertextBatch>(mw, BatchAccess::make(ctx, 0, 1)));
+    // every size first
+    const Planes in(a);
+    std::vector<uint64_t> rows, T;                        // the computed rows, their counts
+    std::vector<unsigned> at(mw, 0);
+    uint64_t ones_of = 0;                                 // their constant bits
+    for (unsigned j = 0; j < mw; ++j) {
+        const uint64_t row = m.rows()[j];
+        const bool one = (constant >> j) & 1u;
+        if (linearKind(row, one) != LINEAR_COMPUTED)
+            continue;
+        at[j] = (unsigned)rows.size();
+        ones_of |= (uint64_t)one << rows.size();
+        rows.push_back(row);
+        T.push_back(checked(csgn_uint_linear_terms(w, in.terms.data(), row, one ? 1 : 0), ctx, "linearMap"));
+    }
+    std::vector<CiphertextBatch> computed;
+    if (!rows.empty() && in.uniform) {
+        computed = makePlanes(ctx, a.size(), T);
+        detail::check(csgn_uint_linear(ctx.getN(), a.size(), w, sources(in).data(), in.terms.data(), rows.size(),
+                                       rows.data(), ones_of, wordsOf(computed).data(), detail::stream()),
+                      "csgn_uint_linear");
+    } else if (!rows.empty()) {                           // the loop: the definition through the batch operators
+        const CiphertextBatch one = ones(a.plane(0));
+        for (size_t r = 0; r < rows.size(); ++r) {
+            unsigned i = (unsigned)__builtin_ctzll(rows[r]);
+            CiphertextBatch sum = a.plane(i);
+            for (++i; i < w; ++i)
+                if ((rows[r] >> i) & 1u)
+                    sum = sum + a.plane(i);
+            computed.push_back((ones_of >> r) & 1u ? sum + one : sum);
+        }
+    }
+    std::vector<CiphertextBatch> out;
+    bool have_zero = false, have_one = false;
+    CiphertextBatch zero = a.plane(0), one = a.plane(0);  // one shared payload for every constant plane of a kind
+    for (unsigned j = 0; j < mw; ++j) {
+        const uint64_t row = m.rows()[j];
+        const bool bit = (constant >> j) & 1u;
+        switch (linearKind(row, bit)) {
+        case LINEAR_SHARED: out.push_back(a.plane((unsigned)__builtin_ctzll(row))); break;
+        case LINEAR_COMPUTED: out.push_back(computed[at[j]]); break;
+        default:
+            if (bit && !have_one) {
+                one = ones(a.plane(0));
+                have_one = true;
+            } else if (!bit && !have_zero) {
+                zero = zeros(a);
+                have_zero = true;
+            }
+            out.push_back(bit ? one : zero);
+        }
+    }
+    return UIntBatch::fromPlanes(out);
+}
+
+CiphertextBatch parity(const UIntBatch &a, uint64_t mask)
+{
+    requireConstant(a, mask, "parity");
+    return linearMap(a, F2Matrix::fromRows(std::vector<uint64_t>(1, mask), a.width())).plane(0);
+}
+
+const char *linearRoute(const UIntBatch &a, const F2Matrix &m, uint64_t constant)
+{
+    requireLinear(a, m, constant, "linearRoute");
+    return a.size() != 0 && Planes(a).uniform && linearComputes(m, constant) ? "call" : "loop";
+}
+
 // ------------------------------------------------------------------ selection by a < b (csgn_uint_lt_select)
 
 namespace {

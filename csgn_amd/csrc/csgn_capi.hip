@@ -2081,6 +2081,86 @@ int csgn_uint_bitwise(uint64_t n_bits, int op, uint64_t batch, uint64_t width, c
     return CSGN_OK;
 }
 
+/* ------------------------------------------------ a public matrix over F2 applied to an integer ---- */
+
+uint64_t csgn_uint_linear_terms(uint64_t in_width, const uint64_t *h_terms, uint64_t row, int constant_bit)
+{
+    return csgn::uint_linear_terms(in_width, (const u64 *)h_terms, row, constant_bit);
+}
+
+int csgn_uint_linear_decode(uint64_t in_width, const uint64_t *h_terms, uint64_t row, int constant_bit, uint64_t q,
+                            uint64_t *h_plane, uint64_t *h_term)
+{
+    return csgn::uint_linear_decode(in_width, (const u64 *)h_terms, row, constant_bit, q, (u64 *)h_plane, (u64 *)h_term) ? 1 : 0;
+}
+
+namespace {
+
+/* what csgn_uint_linear_plan and csgn_uint_linear check before they look at a device pointer; other_host_arrays: the
+ * caller's own host arrays (the plan's table; the call's pointer arrays) are there */
+int check_linear(uint64_t n_bits, uint64_t batch, uint64_t in_width, const uint64_t *h_terms, uint64_t out_width,
+                 const uint64_t *h_rows, uint64_t constant, bool other_host_arrays)
+{
+    if (int rc = check_n(n_bits))
+        return rc;
+    REQUIRE(in_width >= 1 && in_width <= csgn::kLinearMaxPlanes, "linear: in_width %llu outside 1..64",
+            (unsigned long long)in_width);
+    if (int rc = check_width(out_width, constant))
+        return rc;
+    REQUIRE(h_terms && h_rows && other_host_arrays, "null host pointer");
+    for (uint64_t j = 0; j < out_width; ++j)
+        REQUIRE(in_width == 64 || (h_rows[j] >> in_width) == 0, "linear: row %llu names a plane at or above in_width",
+                (unsigned long long)j);
+    for (uint64_t i = 0; i < in_width; ++i)
+        REQUIRE(h_terms[i] != 0 && h_terms[i] < (1ull << 62), "linear: input plane %llu has no terms or 2^62 or more",
+                (unsigned long long)i);
+    for (uint64_t j = 0; j < out_width; ++j)
+        REQUIRE(csgn::uint_linear_terms(in_width, (const u64 *)h_terms, h_rows[j], (int)((constant >> j) & 1u)) != 0,
+                "linear: the term count of row %llu overflows", (unsigned long long)j);
+    const uint64_t dl = csgn_default_len(n_bits);
+    for (uint64_t i = 0; i < in_width; ++i)
+        if (int rc = check_size(batch, h_terms[i], h_terms[i], dl, "linear: input plane %llu", (unsigned long long)i))
+            return rc;
+    for (uint64_t j = 0; j < out_width; ++j) {
+        const uint64_t terms = csgn::uint_linear_terms(in_width, (const u64 *)h_terms, h_rows[j], (int)((constant >> j) & 1u));
+        if (int rc = check_size(batch, terms, terms, dl, "linear: output %llu", (unsigned long long)j))
+            return rc;
+    }
+    return CSGN_OK;
+}
+
+} // namespace
+
+int csgn_uint_linear_plan(uint64_t n_bits, uint64_t batch, uint64_t in_width, const uint64_t *h_terms, uint64_t out_width,
+                          const uint64_t *h_rows, uint64_t constant, uint64_t *h_plan)
+{
+    if (int rc = check_linear(n_bits, batch, in_width, h_terms, out_width, h_rows, constant, h_plan != nullptr))
+        return rc;
+    REQUIRE(csgn::uint_linear_plan(n_bits, batch, in_width, (const u64 *)h_terms, out_width, (const u64 *)h_rows, constant,
+                                   (u64 *)h_plan),
+            "linear: invalid shape");
+    return CSGN_OK;
+}
+
+int csgn_uint_linear(uint64_t n_bits, uint64_t batch, uint64_t in_width, const uint64_t *const *h_in,
+                     const uint64_t *h_terms, uint64_t out_width, const uint64_t *h_rows, uint64_t constant,
+                     uint64_t *const *h_out, void *stream)
+{
+    if (int rc = check_linear(n_bits, batch, in_width, h_terms, out_width, h_rows, constant, h_in && h_out))
+        return rc;
+    if (int rc = check_planes(h_in, nullptr, in_width, "input plane"))
+        return rc;
+    if (int rc = check_planes((const uint64_t *const *)h_out, nullptr, out_width, "output"))
+        return rc;
+    if (int rc = require_device("csgn_uint_linear"))
+        return rc;
+    if (batch == 0)
+        return CSGN_OK;
+    HIP_TRY(csgn::uint_linear(n_bits, batch, in_width, (const u64 *const *)h_in, (const u64 *)h_terms, out_width,
+                              (const u64 *)h_rows, constant, (u64 *const *)h_out, S(stream)));
+    return CSGN_OK;
+}
+
 /* ------------------------------------------------ one-bit batches decrypted into one word per element ---- */
 
 const char *csgn_uint_decrypt_kernel(uint64_t n_bits, uint64_t batch, uint64_t n_planes, const uint64_t *h_terms)

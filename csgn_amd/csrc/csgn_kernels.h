@@ -329,6 +329,19 @@ const char *uint_bitwise_kernel_name(u64 n_bits, int op, u64 batch, u64 w, u64 t
 hipError_t uint_bitwise(u64 n_bits, int op, u64 batch, u64 w, const u64 *sel, u64 ts, const u64 *const *a, const u64 *ta,
                         const u64 *const *b, const u64 *tb, u64 *const *out, hipStream_t stream);
 
+// a public matrix over F2 applied to an encrypted integer (csgn_uint_linear.hip), include/csgn_hip.h's definition:
+// output j is the left-nested sum, ascending in i, of the input planes bit i of rows[j] names, then ONE where bit j of
+// `constant` is set; a zero row is the one-term constant.  in: nin = 1..64 planes, terms ta[i]; out: nout = 1..64 planes.
+constexpr u32 kLinearMaxPlanes = 64;
+u64 uint_linear_terms(u64 nin, const u64 *ta, u64 row, int constant_bit);   // 0: invalid or 2^62 or more
+// the input plane and term output term q of a row copies (plane nin: ONE, nin + 1: ZERO); false: invalid or q past the row
+bool uint_linear_decode(u64 nin, const u64 *ta, u64 row, int constant_bit, u64 q, u64 *plane, u64 *term);
+// plan[8]: unit bytes for 16-byte-aligned pointers, units per element, G, tiles, workgroups per tile, launches under the
+// calling thread's launch_blocks, the tile budget in units, plane groups; false: an invalid shape
+bool uint_linear_plan(u64 n_bits, u64 batch, u64 nin, const u64 *ta, u64 nout, const u64 *rows, u64 constant, u64 *plan);
+hipError_t uint_linear(u64 n_bits, u64 batch, u64 nin, const u64 *const *in, const u64 *ta, u64 nout, const u64 *rows,
+                       u64 constant, u64 *const *out, hipStream_t stream);
+
 // an encrypted integer shifted, rotated or indexed by an encrypted amount (csgn_uint_pick.hip), include/csgn_hip.h's
 // definition: output j is the sum, ascending in r < rows_j, of EQ(index, r) * a_{src(j, r)}; op = CSGN_UINT_PICK_*.
 // index planes: v = 1..16, terms s[k]; source planes: w = 1..64, every one of t terms; rows: EACH's n, else 0.

@@ -130,6 +130,23 @@
 // computed before anything is allocated: std::invalid_argument for mismatched contexts or counts, k >= 2^w, or an output
 // past 2^31 words per element.  An empty batch gives empty planes.
 //
+// PUBLIC LINEAR MAPS OVER F2.  linearMap(a, m, constant) applies the public matrix m (class F2Matrix: one 64-bit row
+// mask over a's planes per output plane) to every element and XORs the public constant: SHA-2's sigma functions, an
+// xorshift step, Gray codes, CRC steps, AES MixColumns, a carry-less product or a product in GF(2^w) with a public
+// factor, a masked parity.  No ciphertext is multiplied: csgn_uint_linear's words (include/csgn_hip.h),
+//     plane j = ((a_{i1} + a_{i2}) + ...) + a_{im} [+ ONE where constant_j = 1],   i1 < i2 < ... the set bits of row j
+// so a row of m bits over fresh planes has m (+ 1) terms, where the chain a.rotateRight(7) ^ a.rotateRight(18) ^ ...
+// copies the running sum once per link and takes m - 1 launches.  What is PUBLIC cancels before anything runs:
+// F2Matrix::operator* composes two maps over F2 and operator^ adds them, so a term two branches both contribute is gone
+// from the matrix (grayDecode(w) * grayEncode(w) IS identity(w)), where the chain keeps it in the ciphertext twice.
+// A row of exactly one bit and no constant returns the SAME payload as the source plane, as the public shifts do; a
+// zero row returns the constant batch (ZERO, or ONE under a constant bit); such rows are left out of the call, and if
+// nothing is left nothing is launched.  Uniform planes take ONE csgn_uint_linear for all other rows (k_uint_linear,
+// DESIGN 4.36); a ragged plane (a compact() result) takes the loop, the same table through CiphertextBatch::operator+
+// and the constant batches, with the same words.  linearRoute names the route.  Every size is computed before anything
+// is allocated or launched: std::invalid_argument for a.width() != m.inWidth(), a constant of outWidth() bits or more,
+// or an output past 2^31 words per element.  An empty batch gives empty planes.  parity(a, mask) is the one-row map.
+//
 // BITWISE OPERATORS AND SHIFTS.  Between two integers of one width, context and count, per plane:
 //     a & b              a_j * b_j            a | b     logicOr(a_j, b_j)            a ^ b     a_j + b_j
 // With a public constant (k < 2^width) and for a public distance s nothing is computed on ciphertext words beyond a
@@ -449,6 +466,49 @@ const char *addWhereRoute(unsigned width, bool uniform_operands);
 // one launch lost (one-term planes and mask, one set bit in k with 16 planes or more above it, 256 MiB of outputs or
 // more), and for k = 0 and an empty batch, which launch nothing.
 const char *addWhereRoute(const CiphertextBatch &mask, const UIntBatch &a, uint64_t k);
+
+// A public matrix over F2 (the block "PUBLIC LINEAR MAPS OVER F2" above): outWidth() rows, row j the mask of the input
+// bits (bit i: input bit i, below inWidth()) whose XOR is output bit j.  Host only, no device work.  Widths are 1..64;
+// std::invalid_argument otherwise, for a row bit at or above the input width, and for operands of mismatched shapes.
+class F2Matrix {
+    std::vector<uint64_t> rows_;
+    unsigned in_;
+    F2Matrix(const std::vector<uint64_t> &rows, unsigned in_width) : rows_(rows), in_(in_width) {}
+
+  public:
+    static F2Matrix fromRows(const std::vector<uint64_t> &rows, unsigned in_width);
+    static F2Matrix identity(unsigned w);
+    static F2Matrix shiftLeft(unsigned w, unsigned s);      // x << s mod 2^w (s >= w: zero)
+    static F2Matrix shiftRight(unsigned w, unsigned s);     // x >> s
+    static F2Matrix rotateLeft(unsigned w, unsigned s);     // s taken mod w
+    static F2Matrix rotateRight(unsigned w, unsigned s);
+    static F2Matrix mask(unsigned w, uint64_t k);           // x & k, k < 2^w
+    static F2Matrix clmul(unsigned w, uint64_t k);          // the carry-less product x * k mod 2^w, k < 2^w
+    // x * k in GF(2^w) = F2[X] / poly, k < 2^w; poly holds the terms below X^w, and may hold X^w itself where it fits
+    // (0x11B and 0x1B both name AES's field at w = 8)
+    static F2Matrix gfMul(unsigned w, uint64_t k, uint64_t poly);
+    static F2Matrix grayEncode(unsigned w);                 // x ^ (x >> 1)
+    static F2Matrix grayDecode(unsigned w);                 // its inverse: bit j = the XOR of bits j .. w - 1
+
+    unsigned inWidth() const { return in_; }
+    unsigned outWidth() const { return (unsigned)rows_.size(); }
+    const std::vector<uint64_t> &rows() const { return rows_; }
+    uint64_t apply(uint64_t x) const;                       // the clear map: bit j = parity(rows[j] & x)
+    F2Matrix operator^(const F2Matrix &rhs) const;          // x -> (*this)(x) ^ rhs(x); one shape
+    // composition over F2: x -> (*this)(rhs(x)); inWidth() == rhs.outWidth().  Public duplicates cancel here.
+    F2Matrix operator*(const F2Matrix &rhs) const;
+    bool operator==(const F2Matrix &rhs) const { return in_ == rhs.in_ && rows_ == rhs.rows_; }
+};
+
+// element i: m(a[i]) ^ constant, of width m.outWidth(); a.width() == m.inWidth(), constant < 2^outWidth()
+UIntBatch linearMap(const UIntBatch &a, const F2Matrix &m, uint64_t constant = 0);
+// element i: the parity of a[i] & mask, one encrypted bit; mask < 2^width.  mask == 0 gives ZERO.
+CiphertextBatch parity(const UIntBatch &a, uint64_t mask);
+// The route linearMap takes (a static string): "call" (one csgn_uint_linear for every row that is neither a single
+// input bit nor a constant) or "loop" (the CiphertextBatch operators row by row: a ragged plane; also when no row is
+// left to compute or the batch is empty, which launch nothing).  No device work; for diagnostics and tests, like
+// arithRoute: the words are the same.
+const char *linearRoute(const UIntBatch &a, const F2Matrix &m, uint64_t constant = 0);
 
 // element i: a[i] < b[i] ? a[i] : b[i] / the other one; a tie takes b for min and a for max
 UIntBatch min(const UIntBatch &a, const UIntBatch &b);

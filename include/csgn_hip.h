@@ -1191,6 +1191,63 @@ int csgn_uint_bitwise(uint64_t n_bits, int op, uint64_t batch, uint64_t width,
                       const uint64_t *const *h_b, const uint64_t *h_b_terms,
                       uint64_t *const *h_out, void *stream);
 
+/* ------------------------------------- a public matrix over F2 applied to an encrypted integer ---- */
+
+/* csgn_uint_linear: a PUBLIC linear (affine) map over F2 of an ENCRYPTED integer, every output plane in one launch:
+ * what certfhe/UInt.h's linearMap and parity compute -- SHA-2's sigma functions, xorshift steps, Gray codes, CRC steps,
+ * AES MixColumns, a carry-less product with a public factor, a product with a public constant in GF(2^w), a masked
+ * parity.  Over F2 a public matrix costs no multiplication: an output plane is a concatenation of input planes.
+ * Inputs:
+ *   - in_width uniform planes a_0 ... a_{in_width-1} (in_width in 1..64, bit 0 first), plane i of h_terms[i] = ta_i >= 1
+ *     terms per element;
+ *   - out_width rows (1..64): row j is the 64-bit mask M_j = h_rows[j] over the input planes (a bit at or above
+ *     in_width: CSGN_ERR_INVALID);
+ *   - `constant`, whose bit j adds ONE to plane j (a bit at or above out_width: CSGN_ERR_INVALID).
+ * Output plane j is the left-nested sum (the reference's operator+: concatenation), ascending in i, of the a_i with bit
+ * i of M_j set, followed by + ONE where constant_j = 1 (the form of NOT in the Gates table):
+ *     plane j = ((a_{i1} + a_{i2}) + ...) + a_{im} [+ ONE]         T_j = sum over i in M_j of ta_i, + constant_j
+ * A row with M_j = 0 is the one-term constant: ZERO (zero words) for constant_j = 0, ONE for 1; T_j = 1.  Rows may
+ * repeat.  Input pointers may alias one another; no output overlaps an input or another output.
+ * Nothing cancels on the device: what is public cancels on the host, in the matrix (certfhe/UInt.h's F2Matrix composes
+ * two maps over F2 before anything runs). */
+/* T_j of one row (host only).  0 for an in_width outside 1..64, a null pointer, a plane of 0 terms, a row bit at or above
+ * in_width, a constant_bit other than 0 or 1, or a count of 2^62 or more. */
+uint64_t csgn_uint_linear_terms(uint64_t in_width, const uint64_t *h_terms, uint64_t row, int constant_bit);
+/* The decode by position (host only): the input plane *h_plane and the term *h_term of it that term q < T_j of the row
+ * copies.  *h_plane = in_width means ONE and in_width + 1 means ZERO (*h_term = 0).  It runs the two functions the
+ * kernel runs (the segment search and the s-th set bit of the mask; csgn_uint_linear.hip).  Returns 1, or 0 (nothing
+ * written) for arguments csgn_uint_linear_terms refuses, q >= T_j or a null pointer. */
+int csgn_uint_linear_decode(uint64_t in_width, const uint64_t *h_terms, uint64_t row, int constant_bit, uint64_t q,
+                            uint64_t *h_plane, uint64_t *h_term);
+/* How a call of this shape is cut under the calling thread's knob "launch_blocks" (host only, no device work).  The
+ * grid is tile-major: a tile is G elements of ALL output planes, every plane's units of a tile rounded up to whole
+ * 256-lane workgroups, and launches are cut at whole tiles only.
+ *     h_plan[0]  bytes of the unit one lane writes when every pointer is 16-byte aligned: 16 for an even number of
+ *                words per term, else 8 (a call with a pointer off alignment takes 8-byte units: twice the units, the
+ *                same G rule)
+ *     h_plan[1]  units per element over all output planes
+ *     h_plan[2]  G, the elements per tile: (tile budget / units per element), at least 1 and at most `batch`
+ *     h_plan[3]  tiles = ceil(batch / G)
+ *     h_plan[4]  workgroups per tile
+ *     h_plan[5]  launches (0 for batch == 0)
+ *     h_plan[6]  the tile budget in units (DESIGN 4.36 says how it was chosen)
+ *     h_plan[7]  plane groups: 1, unless ONE tile of all planes passes HIP's limit of 2^32 lanes a launch; the planes
+ *                then go in that many runs of consecutive planes, each with launches of its own
+ * The same checks as csgn_uint_linear, in its order, up to the sizes; it lets a caller ask for every refusal first. */
+int csgn_uint_linear_plan(uint64_t n_bits, uint64_t batch, uint64_t in_width, const uint64_t *h_terms,
+                          uint64_t out_width, const uint64_t *h_rows, uint64_t constant, uint64_t h_plan[8]);
+/* The operation over `batch` elements.  h_in and h_out are HOST arrays of in_width / out_width device pointers: input
+ * plane i takes batch * ta_i * dL words and output j batch * T_j * dL words.  Checks, in this order, the first that
+ * fails giving the status: n_bits; the widths and the constant; the host arrays; row bits at or above in_width and the
+ * term counts (CSGN_ERR_INVALID); every ta_i * dL and T_j * dL below 2^31 words per element and batch times that below
+ * 2^60 (CSGN_ERR_UNSUPPORTED; computed without wrap-around); null device pointers (CSGN_ERR_INVALID); the device
+ * (CSGN_ERR_NO_DEVICE, no CPU fallback).  batch == 0 succeeds.  On the caller's stream, asynchronous and
+ * graph-capturable: k_uint_linear, one launch for every shape csgn_uint_linear_plan gives one; no
+ * scratch, no allocation, no synchronisation. */
+int csgn_uint_linear(uint64_t n_bits, uint64_t batch, uint64_t in_width, const uint64_t *const *h_in,
+                     const uint64_t *h_terms, uint64_t out_width, const uint64_t *h_rows, uint64_t constant,
+                     uint64_t *const *h_out, void *stream);
+
 /* ------------------------------------- one-bit batches decrypted into one word per element ---- */
 
 /* n_planes one-bit batches of `batch` elements decrypted in ONE pass into one 64-bit word per element: what
