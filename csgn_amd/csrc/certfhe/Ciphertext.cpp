@@ -200,8 +200,14 @@ uint64_t *Ciphertext::getValues() const
 {
     const std::shared_ptr<DevicePayload> p = current();
     if (!host_v && len && p) {
-        host_v = allocMirror(len);                                 // pinned when large: the copy is one DMA
-        detail::downloadBytes(host_v, p->ptr, (size_t)len * 8);
+        uint64_t *mirror = allocMirror(len);                       // pinned when large: the copy is one DMA
+        try {
+            detail::downloadBytes(mirror, p->ptr, (size_t)len * 8);
+        } catch (...) {                                            // an unfilled mirror is never published: the next call copies again
+            freeMirror(mirror);
+            throw;
+        }
+        host_v = mirror;
     }
     return host_v;
 }

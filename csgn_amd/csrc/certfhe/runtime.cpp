@@ -89,23 +89,28 @@ struct BlockCache {
     }
 };
 // The cache lives on the heap behind a thread_local guard: objects with static storage can
-// outlive the guard at process exit, and then simply free their block directly.
+// outlive the guard at process exit, and then simply free their block directly.  That the guard
+// is gone is kept in a plain bool of its own, not in the guard: a store into an object whose
+// destructor is running is dead to the compiler (it was dropped, and a thread's last allocations
+// then made a second cache that nobody released).
 thread_local BlockCache *g_cache_ptr = nullptr;
+thread_local bool g_cache_dead = false;
 struct CacheGuard {
     ~CacheGuard()
     {
+        g_cache_dead = true;
         delete g_cache_ptr;
         g_cache_ptr = nullptr;
-        dead = true;
     }
-    bool dead = false;
 };
 thread_local CacheGuard g_cache_guard;
 
 BlockCache *cache()
 {
-    if (!g_cache_ptr && !g_cache_guard.dead)
+    if (!g_cache_ptr && !g_cache_dead) {
+        (void)&g_cache_guard;           // (made with the cache, so that it is destroyed with the thread)
         g_cache_ptr = new BlockCache();
+    }
     return g_cache_ptr;
 }
 }
@@ -145,17 +150,24 @@ void awaitByte(volatile unsigned char *slot, unsigned char armed)
     syncDevice();
 }
 
+namespace {
+// the message check() throws; reads csgn_last_error(), so make it before the next C-ABI call
+std::string failure(int rc, const char *what)
+{
+    return std::string("certFHE (MI355X): ") + what + " failed [" + std::to_string(rc) + "]: " + csgn_last_error();
+}
+}
+
 void check(int rc, const char *what)
 {
-    if (rc == CSGN_OK)
-        return;
-    std::string msg = std::string("certFHE (MI355X): ") + what + " failed [" + std::to_string(rc) +
-                      "]: " + csgn_last_error();
-    throw std::runtime_error(msg);
+    if (rc != CSGN_OK)
+        throw std::runtime_error(failure(rc, what));
 }
 
 void selectDevice(int device)
 {
+    if (device != g_device)
+        releaseBlockCache();            // the cached blocks are the old device's: not to be handed out on the new one
     g_requested = device;
     g_device = -1;
     ensureDevice();
@@ -277,9 +289,16 @@ void *pinnedTake(size_t bytes, size_t *capacity)
     }
     void *host = nullptr, *alias = nullptr;
     int rc = csgn_host_alloc(&host, &alias, *capacity);
-    if (rc != CSGN_OK && pool.cached) {            // the system refuses more locked pages: drop what is cached, retry once
-        releasePinnedPool();
-        rc = csgn_host_alloc(&host, &alias, *capacity);
+    if (rc != CSGN_OK) {                           // the system refuses more locked pages: drop what is cached, retry once
+        bool cached;
+        {
+            std::lock_guard<std::mutex> hold(pool.lock);
+            cached = pool.cached != 0;
+        }
+        if (cached) {
+            releasePinnedPool();
+            rc = csgn_host_alloc(&host, &alias, *capacity);
+        }
     }
     check(rc, "csgn_host_alloc");
     return host;
@@ -465,6 +484,8 @@ struct DeferQueue {
     void evaluate(bool foreign, std::vector<std::shared_ptr<DevicePayload> > &values)
     {
         const size_t n = pending.size();
+        if (n > kDeferBatch)                       // (deferSmallOp never lets the queue grow past a slot, whatever failed)
+            throw std::logic_error("certFHE: the deferred queue holds more operations than a record slot");
         // One or two operations (a short sum in front of a large product: `big * (a + b)`): the ordinary kernels, one
         // launch each, in queue order -- the record path's fixed costs (the event, records read over the link: 8 us a
         // flush against 2.7 us a launch) only pay from a handful of operations on.
@@ -542,13 +563,24 @@ struct DeferQueue {
             op.kind = nd.product ? 1u : 0u;
             op.reserved = 0;
         }
-        for (int l = 0; l <= max_level; ++l) {
+        // A launch that was issued reads this slot's records whether or not the flush then fails: the slot's event must
+        // stand behind it all the same, or the slot would be rewritten unguarded eight flushes later.  Where the event
+        // cannot be recorded the stream is drained instead, and the flush fails.
+        int rc = CSGN_OK;
+        for (int l = 0; l <= max_level && rc == CSGN_OK; ++l) {
             const size_t cnt = start[(size_t)l + 1] - start[(size_t)l];
             if (cnt)
-                check(csgn_small_ops(n_bits, cnt, d + start[(size_t)l], stream()), "csgn_small_ops");
+                rc = csgn_small_ops(n_bits, cnt, d + start[(size_t)l], stream());
         }
-        check(csgn_event_record(slot_event[cur], stream()), "csgn_event_record");
-        slot_used[cur] = true;
+        std::string error = rc == CSGN_OK ? std::string() : failure(rc, "csgn_small_ops");
+        rc = csgn_event_record(slot_event[cur], stream());
+        if (rc != CSGN_OK && error.empty())
+            error = failure(rc, "csgn_event_record");
+        slot_used[cur] = rc == CSGN_OK;
+        if (!slot_used[cur])
+            (void)csgn_stream_sync(stream());
+        if (!error.empty())
+            throw std::runtime_error(error);
         for (size_t i = 0; i < n; ++i) {
             const LazyNode &nd = *pending[i];
             std::shared_ptr<DevicePayload> v = std::make_shared<DevicePayload>();
@@ -566,12 +598,12 @@ namespace {
 // The calling thread's queue, made on first use.  When the thread ends, what is pending is evaluated (results somebody
 // still points at must exist) or, failing that, marked failed, and the thread lets go of the queue: nodes that other
 // threads still hold keep it alive.  Nothing is deferred on the thread from then on.
+thread_local bool g_queue_dead = false;          // (outside ThreadQueue, as g_cache_dead is outside CacheGuard)
 struct ThreadQueue {
     std::shared_ptr<DeferQueue> q;
-    bool dead = false;
     ~ThreadQueue()
     {
-        dead = true;
+        g_queue_dead = true;
         if (!q)
             return;
         {
@@ -593,9 +625,12 @@ const std::shared_ptr<DeferQueue> &threadQueue()
 {
     // the device first: the HIP runtime's own thread_local state is then made before g_thread_queue, so it is destroyed
     // after it, and the flush at the thread's end still has a runtime to call
+    static const std::shared_ptr<DeferQueue> none;
     ensureDevice();
+    if (g_queue_dead)
+        return none;
     ThreadQueue &t = g_thread_queue;
-    if (!t.q && !t.dead) {
+    if (!t.q) {
         t.q = std::make_shared<DeferQueue>();
         t.q->device = g_device;
     }
@@ -613,6 +648,8 @@ bool deferralOn() { return g_defer_on.load(); }
 
 void flushDeferred()
 {
+    if (g_queue_dead)
+        return;
     const std::shared_ptr<DeferQueue> &q = g_thread_queue.q;
     if (!q)
         return;
@@ -662,8 +699,11 @@ std::shared_ptr<LazyNode> deferSmallOp(bool product, uint64_t n_bits, uint64_t d
     if ((fa && fa->device != q->device) || (fb && fb->device != q->device))
         return std::shared_ptr<LazyNode>();          // operands of another GPU: the immediate path reports that
     std::lock_guard<std::mutex> hold(q->lock);
-    if (!q->pending.empty() && q->n_bits != n_bits)
-        q->flushLocked();                            // one launch serves one term size
+    // A full queue is evaluated BEFORE the new node is taken, and so is one of another term size (one launch serves one
+    // term size).  A flush that throws leaves the queue as it was and nothing of this operation in it: the operator
+    // throws, the queue never holds more than kDeferBatch nodes -- a record slot -- and the next operation tries again.
+    if (q->pending.size() >= kDeferBatch || (!q->pending.empty() && q->n_bits != n_bits))
+        q->flushLocked();
     // operands of this queue evaluated already (by the flush above, or another thread's valueOf): kDone, since this
     // queue can only fail when its thread has ended
     if (na && na->state.load(std::memory_order_relaxed) != LazyNode::kPending) {
@@ -686,8 +726,6 @@ std::shared_ptr<LazyNode> deferSmallOp(bool product, uint64_t n_bits, uint64_t d
     nd->t2 = (uint32_t)t2;
     nd->product = product;
     q->pending.push_back(nd);
-    if (q->pending.size() >= kDeferBatch)
-        q->flushLocked();
     return nd;
 }
 

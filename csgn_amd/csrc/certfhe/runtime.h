@@ -85,6 +85,9 @@ void releaseBlockCache();
 //      the lock loads `state` with acquire and reads `value` or owner->error only after it has seen kDone or kFailed.
 //   3. No thread holds two queue locks: an operand pending in another thread's queue is evaluated through valueOf()
 //      before the caller's own queue is locked.
+//   4. A flush that throws changes no node and leaves owner->pending as it was.  deferSmallOp evaluates a full queue
+//      BEFORE it makes the new node: an operator whose flush throws leaves nothing of itself queued, and pending never
+//      holds more than kDeferBatch nodes, which is what one record slot of the flush holds.
 const uint32_t kDeferMaxTerms = 8;
 const size_t kDeferBatch = 256;
 struct DeferQueue;
