@@ -24,9 +24,9 @@ ROCM_LIB ?= $(dir $(HIPCC))../lib
 .PHONY: all tools check clean
 all: $(LIBDIR)/libcsgn_hip.so $(LIBDIR)/libcsgn_shard.so $(LIBDIR)/libcertFHE.so $(LIBDIR)/libcertFHE_shard.so
 
-$(LIBDIR)/libcsgn_shard.so: $(CSRC)/csgn_shard.hip include/csgn_shard.h include/csgn_hip.h
+$(LIBDIR)/libcsgn_shard.so: $(CSRC)/csgn_shard.hip $(CSRC)/csgn_shard_comm.cpp $(CSRC)/csgn_shard_internal.h include/csgn_shard.h include/csgn_hip.h
 	mkdir -p $(LIBDIR)
-	$(HIPCC) --offload-arch=gfx950 -O2 -std=c++17 -fPIC -shared -Iinclude -o $@ $(CSRC)/csgn_shard.hip -L$(ROCM_LIB) -lrccl
+	$(HIPCC) --offload-arch=gfx950 -O2 -std=c++17 -fPIC -shared -Iinclude -o $@ $(CSRC)/csgn_shard.hip $(CSRC)/csgn_shard_comm.cpp -L$(ROCM_LIB) -lrccl
 
 tools: tools/bin/shard_mul tools/bin/bench_mul tools/bin/bench_native
 

@@ -99,12 +99,14 @@ def build_shard(force: bool = False, verbose: bool = False) -> str:
     counts.  Links librccl directly; kept apart from libcsgn_hip.so so that single-GPU users do
     not map the 570 MB RCCL image."""
     os.makedirs(LIBDIR, exist_ok=True)
-    src = os.path.join(CSRC, "csgn_shard.hip")
-    deps = [src, os.path.join(INCLUDE, "csgn_shard.h"), os.path.join(INCLUDE, "csgn_hip.h")]
+    # the kernel (device compiler) and the communicator code (plain C++ over the HIP runtime API and RCCL)
+    srcs = [os.path.join(CSRC, "csgn_shard.hip"), os.path.join(CSRC, "csgn_shard_comm.cpp")]
+    deps = srcs + [os.path.join(CSRC, "csgn_shard_internal.h"), os.path.join(INCLUDE, "csgn_shard.h"),
+                   os.path.join(INCLUDE, "csgn_hip.h")]
     if force or _stale(SHARD_LIB, deps):
         rocm_lib = os.path.join(os.path.dirname(os.path.dirname(_hipcc())), "lib")
         cmd = [_hipcc(), "--offload-arch=gfx950", "-O2", "-std=c++17", "-fPIC", "-shared", "-I" + INCLUDE,
-               "-o", SHARD_LIB, src, "-L" + rocm_lib, "-lrccl"]
+               "-o", SHARD_LIB] + srcs + ["-L" + rocm_lib, "-lrccl"]
         if verbose:
             print(" ".join(cmd))
         subprocess.check_call(cmd)

@@ -229,9 +229,34 @@ bool stub_is_live(const void *p)
     return g_live.count(reinterpret_cast<uintptr_t>(p)) != 0;
 }
 
+void (*stub_stream_hook)(void *stream) = nullptr;
+int stub_device() { return t_device; }
+void stub_set_device(int device) { t_device = device; }
+int stub_allocate(const char *entry, void **out, size_t bytes, int kind) { return allocate(entry, out, bytes, kind); }
+int stub_release(const char *entry, void *p, int kind) { return release(entry, p, kind); }
+int stub_enter(const char *entry, const void *p0, const void *p1, size_t bytes, uint64_t n_bits)
+{
+    std::lock_guard<std::mutex> hold(g_lock);
+    const int rc = enter(entry);
+    log(entry, p0, p1, bytes, n_bits, rc);
+    return rc;
+}
+void stub_check(const char *entry, const void *p, size_t bytes, int kind)
+{
+    std::lock_guard<std::mutex> hold(g_lock);
+    inside(entry, p, bytes, kind);
+}
+void stub_set_error(const std::string &text) { t_error = text; }
+void stub_die(const char *entry, const char *what, const void *p, size_t bytes) { die(entry, what, p, bytes); }
+
 } // namespace capi_stub
 
 using namespace capi_stub;
+
+// stream order, where something under the stub models it (capi_stub.h): before the lock, the hook may wait
+#define STREAM(stream)                 \
+    if (stub_stream_hook)              \
+        stub_stream_hook(stream)
 
 // a call that only enters, checks and logs under the lock, then works outside it
 #define ENTER(entry, p0, p1, bytes, n_bits, checks)          \
@@ -274,33 +299,38 @@ int csgn_host_alloc(void **h_ptr, void **d_alias, size_t bytes)
 }
 int csgn_host_free(void *h_ptr) { return release("csgn_host_free", h_ptr, kPinned); }
 
-int csgn_memcpy_h2d(void *d_dst, const void *h_src, size_t bytes, void *)
+int csgn_memcpy_h2d(void *d_dst, const void *h_src, size_t bytes, void *stream)
 {
+    STREAM(stream);
     ENTER("csgn_memcpy_h2d", d_dst, h_src, bytes, 0, (inside("csgn_memcpy_h2d", d_dst, bytes, kDevice), host_side("csgn_memcpy_h2d", h_src, bytes)));
     memcpy(d_dst, h_src, bytes);
     return CSGN_OK;
 }
-int csgn_memcpy_d2h(void *h_dst, const void *d_src, size_t bytes, void *)
+int csgn_memcpy_d2h(void *h_dst, const void *d_src, size_t bytes, void *stream)
 {
+    STREAM(stream);
     ENTER("csgn_memcpy_d2h", h_dst, d_src, bytes, 0, (inside("csgn_memcpy_d2h", d_src, bytes, kDevice), host_side("csgn_memcpy_d2h", h_dst, bytes)));
     memcpy(h_dst, d_src, bytes);
     return CSGN_OK;
 }
-int csgn_memcpy_d2d(void *d_dst, const void *d_src, size_t bytes, void *)
+int csgn_memcpy_d2d(void *d_dst, const void *d_src, size_t bytes, void *stream)
 {
+    STREAM(stream);
     ENTER("csgn_memcpy_d2d", d_dst, d_src, bytes, 0, (inside("csgn_memcpy_d2d", d_dst, bytes, kDevice), inside("csgn_memcpy_d2d", d_src, bytes, kDevice)));
     memmove(d_dst, d_src, bytes);
     return CSGN_OK;
 }
-int csgn_memset(void *d_dst, int value, size_t bytes, void *)
+int csgn_memset(void *d_dst, int value, size_t bytes, void *stream)
 {
+    STREAM(stream);
     ENTER("csgn_memset", d_dst, nullptr, bytes, 0, inside("csgn_memset", d_dst, bytes, kDevice));
     memset(d_dst, value, bytes);
     return CSGN_OK;
 }
 
-int csgn_stream_sync(void *)
+int csgn_stream_sync(void *stream)
 {
+    STREAM(stream);
     ENTER("csgn_stream_sync", nullptr, nullptr, 0, 0, (void)0);
     return CSGN_OK;
 }
@@ -326,8 +356,9 @@ static void live_event(const char *entry, void *event)
     if (it == g_live.end() || it->second.kind != kEvent)
         die(entry, "not a live event", event, 0);
 }
-int csgn_event_record(void *event, void *)
+int csgn_event_record(void *event, void *stream)
 {
+    STREAM(stream);
     ENTER("csgn_event_record", event, nullptr, 0, 0, live_event("csgn_event_record", event));
     return CSGN_OK;
 }
@@ -337,8 +368,9 @@ int csgn_event_sync(void *event)
     return CSGN_OK;
 }
 
-int csgn_synth_fill(uint64_t seed, uint64_t n_bits, uint64_t first_word, uint64_t n_words, uint64_t *d_out, void *)
+int csgn_synth_fill(uint64_t seed, uint64_t n_bits, uint64_t first_word, uint64_t n_words, uint64_t *d_out, void *stream)
 {
+    STREAM(stream);
     ENTER("csgn_synth_fill", d_out, nullptr, n_words * 8, n_bits, inside("csgn_synth_fill", d_out, n_words * 8, kDevice));
     csgn_oracle_synth_fill(seed, n_bits, first_word, n_words, d_out);
     return CSGN_OK;
@@ -361,8 +393,9 @@ int csgn_key_mask(uint64_t n_bits, const uint64_t *h_key, uint64_t d, uint64_t *
 }
 
 int csgn_mul_uniform(uint64_t n_bits, uint64_t batch, uint64_t t1, uint64_t t2, const uint64_t *d_left, const uint64_t *d_right,
-                     uint64_t *d_out, uint64_t out_slots, void *)
+                     uint64_t *d_out, uint64_t out_slots, void *stream)
 {
+    STREAM(stream);
     const uint64_t dl = dl_of(n_bits), slots = out_slots ? out_slots : t1 * t2;
     ENTER("csgn_mul_uniform", d_out, nullptr, (size_t)(t1 << 32 | t2), n_bits,
           (inside("csgn_mul_uniform", d_left, batch * t1 * dl * 8, kDevice), inside("csgn_mul_uniform", d_right, batch * t2 * dl * 8, kDevice),
@@ -373,8 +406,9 @@ int csgn_mul_uniform(uint64_t n_bits, uint64_t batch, uint64_t t1, uint64_t t2, 
 }
 
 int csgn_add_uniform(uint64_t n_bits, uint64_t batch, uint64_t t1, uint64_t t2, const uint64_t *d_left, const uint64_t *d_right,
-                     uint64_t *d_out, void *)
+                     uint64_t *d_out, void *stream)
 {
+    STREAM(stream);
     const uint64_t dl = dl_of(n_bits);
     ENTER("csgn_add_uniform", d_out, nullptr, (size_t)(t1 << 32 | t2), n_bits,
           (inside("csgn_add_uniform", d_left, batch * t1 * dl * 8, kDevice), inside("csgn_add_uniform", d_right, batch * t2 * dl * 8, kDevice),
@@ -384,8 +418,9 @@ int csgn_add_uniform(uint64_t n_bits, uint64_t batch, uint64_t t1, uint64_t t2, 
     return CSGN_OK;
 }
 
-int csgn_small_ops(uint64_t n_bits, uint64_t count, const csgn_small_op *d_ops, void *)
+int csgn_small_ops(uint64_t n_bits, uint64_t count, const csgn_small_op *d_ops, void *stream)
 {
+    STREAM(stream);
     const uint64_t dl = dl_of(n_bits);
     {
         std::lock_guard<std::mutex> hold(g_lock);
@@ -411,8 +446,9 @@ int csgn_small_ops(uint64_t n_bits, uint64_t count, const csgn_small_op *d_ops, 
 }
 
 int csgn_encrypt_explicit(uint64_t n_bits, uint64_t d, uint64_t batch, const uint8_t *d_plain, const uint64_t *d_rnd,
-                          const uint32_t *d_chosen, const uint8_t *d_last, const uint64_t *d_mask, uint64_t *d_out, void *)
+                          const uint32_t *d_chosen, const uint8_t *d_last, const uint64_t *d_mask, uint64_t *d_out, void *stream)
 {
+    STREAM(stream);
     const uint64_t dl = dl_of(n_bits);
     ENTER("csgn_encrypt_explicit", d_out, nullptr, batch, n_bits,
           (inside("csgn_encrypt_explicit", d_plain, batch, kDevice), inside("csgn_encrypt_explicit", d_rnd, batch * dl * 8, kDevice),
@@ -447,8 +483,9 @@ int csgn_encrypt_explicit(uint64_t n_bits, uint64_t d, uint64_t batch, const uin
 size_t csgn_decrypt_scratch_bytes(uint64_t batch, uint64_t total_terms) { return (size_t)((total_terms + 7) / 8 + 8 * batch); }
 
 int csgn_decrypt_uniform(uint64_t n_bits, uint64_t batch, uint64_t terms, const uint64_t *d_terms, const uint64_t *d_mask,
-                         uint8_t *d_bits, void *d_scratch, void *)
+                         uint8_t *d_bits, void *d_scratch, void *stream)
 {
+    STREAM(stream);
     const uint64_t dl = dl_of(n_bits);
     ENTER("csgn_decrypt_uniform", d_bits, d_terms, (size_t)terms, n_bits,
           (inside("csgn_decrypt_uniform", d_terms, batch * terms * dl * 8, kDevice), inside("csgn_decrypt_uniform", d_mask, dl * 8, kDevice),
@@ -463,8 +500,9 @@ int csgn_decrypt_uniform(uint64_t n_bits, uint64_t batch, uint64_t terms, const 
 size_t csgn_bitlen_scratch_bytes(uint64_t len_words) { return (size_t)(len_words + 1) * 8; }
 
 int csgn_decrypt_bitlen(uint64_t n_bits, uint64_t d, uint64_t len_words, const uint64_t *d_v, const uint64_t *d_bitlen,
-                        const uint64_t *d_key, uint8_t *d_bit, void *d_scratch, void *)
+                        const uint64_t *d_key, uint8_t *d_bit, void *d_scratch, void *stream)
 {
+    STREAM(stream);
     ENTER("csgn_decrypt_bitlen", d_bit, d_v, (size_t)len_words, n_bits,
           (inside("csgn_decrypt_bitlen", d_v, len_words * 8, kDevice), inside("csgn_decrypt_bitlen", d_bitlen, len_words * 8, kDevice),
            inside("csgn_decrypt_bitlen", d_key, d * 8, kDevice), inside_either("csgn_decrypt_bitlen (the bit)", d_bit, 1),
@@ -474,8 +512,9 @@ int csgn_decrypt_bitlen(uint64_t n_bits, uint64_t d, uint64_t len_words, const u
 }
 
 int csgn_permute_bitlen(uint64_t n_bits, uint64_t len_words, const uint64_t *d_v, const uint64_t *d_bitlen, const uint32_t *d_perm,
-                        uint64_t *d_out, void *d_scratch, void *)
+                        uint64_t *d_out, void *d_scratch, void *stream)
 {
+    STREAM(stream);
     ENTER("csgn_permute_bitlen", d_out, d_v, (size_t)len_words, n_bits,
           (inside("csgn_permute_bitlen", d_v, len_words * 8, kDevice), inside("csgn_permute_bitlen", d_bitlen, len_words * 8, kDevice),
            inside("csgn_permute_bitlen", d_perm, n_bits * 4, kDevice), inside("csgn_permute_bitlen", d_out, dl_of(n_bits) * 8, kDevice),
@@ -486,8 +525,9 @@ int csgn_permute_bitlen(uint64_t n_bits, uint64_t len_words, const uint64_t *d_v
 }
 
 int csgn_permute_uniform(uint64_t n_bits, uint64_t batch, uint64_t terms_in, int per_term, const uint64_t *d_terms,
-                         const uint32_t *d_perm, uint64_t *d_out, void *)
+                         const uint32_t *d_perm, uint64_t *d_out, void *stream)
 {
+    STREAM(stream);
     const uint64_t dl = dl_of(n_bits), terms_out = per_term ? terms_in : 1;
     ENTER("csgn_permute_uniform", d_out, d_terms, (size_t)terms_in, n_bits,
           (inside("csgn_permute_uniform", d_terms, batch * terms_in * dl * 8, kDevice), inside("csgn_permute_uniform", d_perm, n_bits * 4, kDevice),

@@ -65,6 +65,23 @@ std::vector<Alloc> stub_live();             // live allocations of every kind
 size_t stub_live_count(int kind);
 bool stub_is_live(const void *p);
 
+// ---- what capi_stub_shard.cpp (the entries ShardedBatch.cpp adds) and fake_hip_rccl.cpp (HIP and RCCL under the
+// communicator code) share with this stub: ONE current device per thread, ONE table of live blocks, one call log.
+// Called first, with its stream, by every entry that takes one; null (the default) = nothing.  The fake sets it to "wait
+// until this stream is no longer busy", which gives a call behind a collective the gathered data, as stream order does.
+extern void (*stub_stream_hook)(void *stream);
+int stub_device();                          // the calling thread's current device (-1: none yet)
+void stub_set_device(int device);
+// csgn_malloc / csgn_free under another name (counted, logged, refusable under `entry`)
+int stub_allocate(const char *entry, void **out, size_t bytes, int kind);
+int stub_release(const char *entry, void *p, int kind);
+// counts and logs a call of `entry`; the status to return at once (an injected failure), or CSGN_OK
+int stub_enter(const char *entry, const void *p0, const void *p1, size_t bytes, uint64_t n_bits);
+// [p, p + bytes) lies in one live block of `kind` made on the current device, or the program ends with status 3
+void stub_check(const char *entry, const void *p, size_t bytes, int kind);
+void stub_set_error(const std::string &text);   // what csgn_last_error() says on this thread
+[[noreturn]] void stub_die(const char *entry, const char *what, const void *p, size_t bytes);
+
 } // namespace capi_stub
 
 #endif

@@ -43,7 +43,7 @@ def test_fails_loudly_without_gpu(driver):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("count,n,d", [(1000, 1247, 16), (70001, 1247, 16), (257, 4096, 32), (5, 64, 2)])
+@pytest.mark.parametrize("count,n,d", [(1, 1247, 16), (1000, 1247, 16), (70001, 1247, 16), (257, 4096, 32), (5, 64, 2)])
 def test_sharded_batch_equals_the_one_gpu_batch(driver, count, n, d):
     p = run(driver, "compare", count, n, d)
     assert "FAIL" not in p.stdout and p.stdout.count("OK ") >= 28
