@@ -668,6 +668,65 @@ class HipPath:
         check(self.lib.csgn_uint_linear(n_bits, batch, w, h_in, h_terms, m, h_rows, int(constant), h_out, self.stream))
         return [o[:s] for o, s in zip(outs, sizes)]
 
+    @staticmethod
+    def _plain_sum_arrays(terms, planes_entries):
+        """Host arrays of a csgn_uint_plain_sum shape: planes_entries[x] is the list of (cmp, k) of output plane x."""
+        flat = [e for entries in planes_entries for e in entries]
+        first = [0]
+        for entries in planes_entries:
+            first.append(first[-1] + len(entries))
+        h_terms = (C.c_uint64 * max(len(terms), 1))(*[int(t) for t in terms])
+        h_first = (C.c_uint64 * len(first))(*first)
+        h_cmp = (C.c_int * max(len(flat), 1))(*[int(c) for c, _ in flat])
+        h_k = (C.c_uint64 * max(len(flat), 1))(*[int(k) for _, k in flat])
+        return h_terms, h_first, h_cmp, h_k
+
+    def uint_plain_sum_launches(self, n_bits: int, batch: int, terms, planes_entries, constant: int = 0):
+        """csgn_uint_plain_sum_launches: [unit bytes, lane items per element, plane groups, launches, elements and
+        workgroups of the first launch] of a csgn_uint_plain_sum call of this shape under the calling thread's knobs."""
+        h_terms, h_first, h_cmp, h_k = self._plain_sum_arrays(terms, planes_entries)
+        plan = (C.c_uint64 * 6)()
+        check(self.lib.csgn_uint_plain_sum_launches(n_bits, batch, len(terms), h_terms, len(planes_entries), h_first, h_cmp,
+                                                    h_k, int(constant), plan))
+        return [int(x) for x in plan]
+
+    def uint_plain_sum_create(self, terms, planes_entries, constant: int = 0) -> int:
+        """csgn_uint_plain_sum_create: the plan of the output planes planes_entries[x] = [(cmp, k), ...] over input
+        planes of terms[j] terms per element, plus ONE in the planes whose bit of `constant` is set.  Returns the handle;
+        release it with self.lib.csgn_uint_plain_sum_destroy."""
+        h_terms, h_first, h_cmp, h_k = self._plain_sum_arrays(terms, planes_entries)
+        handle = C.c_void_p()
+        check(self.lib.csgn_uint_plain_sum_create(len(terms), h_terms, len(planes_entries), h_first, h_cmp, h_k,
+                                                  int(constant), C.byref(handle)))
+        return handle.value
+
+    def uint_plain_sum_apply(self, handle: int, n_bits: int, batch: int, planes, n_out: int, outs=None):
+        """csgn_uint_plain_sum of a plan over the encrypted integer `planes` (bit 0 first).  Returns the output planes,
+        of csgn_uint_plain_sum_plan_terms terms per element, fresh ones unless `outs` is given."""
+        dl = self.default_len(n_bits)
+        T = [int(self.lib.csgn_uint_plain_sum_plan_terms(handle, x)) for x in range(n_out)]
+        assert all(T), "not a plane of the plan"
+        sizes = [batch * t * dl for t in T]
+        if outs is None:
+            outs = [self.empty_words(max(s, 1)) for s in sizes]
+        assert all(o.numel() >= s for o, s in zip(outs, sizes))
+        h_in = (C.c_void_p * len(planes))(*[_ptr(p) for p in planes])
+        h_out = (C.c_void_p * n_out)(*[_ptr(o) for o in outs])
+        check(self.lib.csgn_uint_plain_sum(handle, n_bits, batch, h_in, h_out, self.stream))
+        return [o[:s] for o, s in zip(outs, sizes)]
+
+    def uint_plain_sum(self, n_bits: int, batch: int, planes, terms, planes_entries, constant: int = 0, outs=None):
+        """csgn_uint_plain_sum with a plan of its own: output plane x is the sum of csgn_uint_plain(cmp, k) of `planes`
+        over planes_entries[x] = [(cmp, k), ...], plus ONE where bit x of `constant` is set."""
+        assert len(planes) == len(terms)
+        handle = self.uint_plain_sum_create(terms, planes_entries, constant)
+        try:
+            outs = self.uint_plain_sum_apply(handle, n_bits, batch, planes, len(planes_entries), outs)
+            torch.cuda.current_stream(self.device).synchronize()
+        finally:
+            self.lib.csgn_uint_plain_sum_destroy(handle)
+        return outs
+
     def uint_bitwise(self, n_bits: int, op: int, batch: int, a, a_terms, b=None, b_terms=None, sel=None, sel_terms: int = 0,
                      outs=None):
         """csgn_uint_bitwise: op = 1 a & b, 2 a | b, 3 a ^ b, 4 ~a, 5 sel ? a : b, 6 sel ? a : 0 of the encrypted

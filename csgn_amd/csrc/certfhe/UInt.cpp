@@ -1334,6 +1334,285 @@ const char *linearRoute(const UIntBatch &a, const F2Matrix &m, uint64_t constant
     return a.size() != 0 && Planes(a).uniform && linearComputes(m, constant) ? "call" : "loop";
 }
 
+// ------------------------------------------------------------------ ranges, sets, step functions (csgn_uint_plain_sum)
+
+namespace {
+
+typedef std::pair<int, uint64_t> PlainEntry;              // (CSGN_UINT_PLAIN_*, k)
+typedef std::vector<PlainEntry> PlainEntries;
+
+// device plans per (width, terms, entries, constant), kept until the process ends
+const csgn_uint_plain_sum_plan *plainSumPlan(const std::vector<uint64_t> &terms, const std::vector<uint64_t> &first,
+                                             const std::vector<int> &cmp, const std::vector<uint64_t> &k, uint64_t constant)
+{
+    static std::mutex mutex;
+    static std::map<std::vector<uint64_t>, csgn_uint_plain_sum_plan *> *plans =
+        new std::map<std::vector<uint64_t>, csgn_uint_plain_sum_plan *>();
+    std::vector<uint64_t> key(1, constant);
+    key.push_back(terms.size());
+    key.insert(key.end(), terms.begin(), terms.end());
+    key.insert(key.end(), first.begin(), first.end());
+    key.insert(key.end(), cmp.begin(), cmp.end());
+    key.insert(key.end(), k.begin(), k.end());
+    std::lock_guard<std::mutex> lock(mutex);
+    auto it = plans->find(key);
+    if (it != plans->end())
+        return it->second;
+    csgn_uint_plain_sum_plan *p = nullptr;
+    detail::check(csgn_uint_plain_sum_create(terms.size(), terms.data(), first.size() - 1, first.data(), cmp.data(), k.data(),
+                                             constant, &p),
+                  "csgn_uint_plain_sum_create");
+    (*plans)[key] = p;
+    return p;
+}
+
+// what plainSum does with a plane: the constant batch, one comparison's own call, or a computed plane
+enum { SUM_CONSTANT, SUM_SINGLE, SUM_COMPUTED };
+
+int plainSumKind(const PlainEntries &entries, bool one)
+{
+    if (entries.empty())
+        return SUM_CONSTANT;
+    return entries.size() == 1 && !one ? SUM_SINGLE : SUM_COMPUTED;
+}
+
+const char *whoOf(int cmp)
+{
+    static const char *const names[] = {"", "equalTo", "notEqualTo", "lessThan", "lessEqual", "greaterThan", "greaterEqual"};
+    return names[cmp];
+}
+
+// The planes of csgn_uint_plain_sum's definition over a: plane x sums the comparisons planes[x], + ONE where bit x of
+// `constant` is set.  Every size first; one plan and one launch for the computed planes of uniform inputs, else the
+// definition through the batch operators.
+std::vector<CiphertextBatch> plainSum(const UIntBatch &a, const std::vector<PlainEntries> &planes, uint64_t constant,
+                                      const char *who)
+{
+    const unsigned w = a.width(), m = (unsigned)planes.size();
+    const Context &ctx = a.context();
+    const Planes in(a);
+    std::vector<uint64_t> first(1, 0), k, T;
+    std::vector<int> cmp;
+    uint64_t ones_of = 0;
+    for (unsigned x = 0; x < m; ++x) {
+        const bool one = (constant >> x) & 1u;
+        std::vector<int> c;
+        std::vector<uint64_t> ks;
+        for (size_t i = 0; i < planes[x].size(); ++i) {
+            c.push_back(planes[x][i].first);
+            ks.push_back(planes[x][i].second);
+        }
+        checked(csgn_uint_plain_sum_terms(w, in.terms.data(), c.size(), c.data(), ks.data(), one ? 1 : 0), ctx, who);
+        if (plainSumKind(planes[x], one) != SUM_COMPUTED)
+            continue;
+        ones_of |= (uint64_t)one << T.size();
+        T.push_back(csgn_uint_plain_sum_terms(w, in.terms.data(), c.size(), c.data(), ks.data(), one ? 1 : 0));
+        cmp.insert(cmp.end(), c.begin(), c.end());
+        k.insert(k.end(), ks.begin(), ks.end());
+        first.push_back(cmp.size());
+    }
+    if (cmp.size() > 65536)
+        throw std::invalid_argument(std::string("certFHE::") + who + ": more than 65536 comparisons in one call");
+    if (a.size() == 0)
+        return std::vector<CiphertextBatch>(m, BatchAccess::make(ctx, 0, 1));
+    std::vector<CiphertextBatch> computed;
+    if (!T.empty() && in.uniform) {
+        const csgn_uint_plain_sum_plan *plan = plainSumPlan(in.terms, first, cmp, k, ones_of);
+        computed = makePlanes(ctx, a.size(), T);
+        detail::check(csgn_uint_plain_sum(plan, ctx.getN(), a.size(), sources(in).data(), wordsOf(computed).data(),
+                                          detail::stream()),
+                      "csgn_uint_plain_sum");
+    }
+    std::vector<CiphertextBatch> out;
+    size_t next = 0;
+    for (unsigned x = 0; x < m; ++x) {
+        const bool one = (constant >> x) & 1u;
+        switch (plainSumKind(planes[x], one)) {
+        case SUM_CONSTANT: out.push_back(one ? ones(a.plane(0)) : zeros(a)); break;
+        case SUM_SINGLE:
+            out.push_back(comparePlain(planes[x][0].first, a, planes[x][0].second, whoOf(planes[x][0].first)));
+            break;
+        default:
+            if (in.uniform) {
+                out.push_back(computed[next++]);
+                break;
+            }
+            CiphertextBatch sum = comparePlain(planes[x][0].first, a, planes[x][0].second, who);
+            for (size_t i = 1; i < planes[x].size(); ++i)
+                sum = sum + comparePlain(planes[x][i].first, a, planes[x][i].second, who);
+            out.push_back(one ? sum + ones(a.plane(0)) : sum);
+        }
+    }
+    return out;
+}
+
+void requireBelow(const UIntBatch &a, uint64_t v, const char *who, const char *what)
+{
+    if (a.width() < 64 && (v >> a.width()) != 0)
+        throw std::invalid_argument(std::string("certFHE::") + who + ": " + what + " does not fit in the width");
+}
+
+// the entries of lo <= a <= hi appended; returns true when the range is everything (+ ONE)
+bool rangeEntries(const UIntBatch &a, uint64_t lo, uint64_t hi, const char *who, PlainEntries &entries)
+{
+    if (lo > hi)
+        throw std::invalid_argument(std::string("certFHE::") + who + ": lo is above hi");
+    requireBelow(a, hi, who, "a bound");
+    const uint64_t top = maskOf(a.width());
+    if (lo == 0 && hi == top)
+        return true;
+    if (lo == 0) {
+        entries.push_back(PlainEntry(CSGN_UINT_PLAIN_LE, hi));
+    } else if (hi == top) {
+        entries.push_back(PlainEntry(CSGN_UINT_PLAIN_GE, lo));
+    } else {
+        entries.push_back(PlainEntry(CSGN_UINT_PLAIN_LT, hi + 1));
+        entries.push_back(PlainEntry(CSGN_UINT_PLAIN_LT, lo));
+    }
+    return false;
+}
+
+PlainEntries setEntries(const UIntBatch &a, const std::vector<uint64_t> &set, const char *who)
+{
+    std::vector<uint64_t> keys(set);
+    std::sort(keys.begin(), keys.end());
+    keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
+    PlainEntries entries;
+    for (size_t i = 0; i < keys.size(); ++i) {
+        requireBelow(a, keys[i], who, "a value of the set");
+        entries.push_back(PlainEntry(CSGN_UINT_PLAIN_EQ, keys[i]));
+    }
+    return entries;
+}
+
+void requireOutWidth(unsigned out_width, const std::vector<uint64_t> &values, const char *who)
+{
+    if (out_width < 1 || out_width > 64)
+        throw std::invalid_argument(std::string("certFHE::") + who + ": out_width must be 1..64");
+    for (size_t i = 0; i < values.size(); ++i)
+        if (out_width < 64 && (values[i] >> out_width) != 0)
+            throw std::invalid_argument(std::string("certFHE::") + who + ": a value does not fit in out_width");
+}
+
+// planes and constant of the step function
+uint64_t stepEntries(const UIntBatch &a, const std::vector<uint64_t> &thresholds, const std::vector<uint64_t> &values,
+                     unsigned out_width, const char *who, std::vector<PlainEntries> &planes)
+{
+    requireOutWidth(out_width, values, who);
+    if (values.size() != thresholds.size() + 1)
+        throw std::invalid_argument(std::string("certFHE::") + who + ": m thresholds take m + 1 values");
+    for (size_t i = 0; i < thresholds.size(); ++i) {
+        requireBelow(a, thresholds[i], who, "a threshold");
+        if (thresholds[i] == 0 || (i && thresholds[i] <= thresholds[i - 1]))
+            throw std::invalid_argument(std::string("certFHE::") + who + ": thresholds must ascend strictly from 1 on");
+    }
+    planes.assign(out_width, PlainEntries());
+    for (unsigned j = 0; j < out_width; ++j)
+        for (size_t i = 0; i < thresholds.size(); ++i)
+            if (((values[i] ^ values[i + 1]) >> j) & 1u)
+                planes[j].push_back(PlainEntry(CSGN_UINT_PLAIN_LT, thresholds[i]));
+    return values.back();
+}
+
+std::vector<uint64_t> bucketValues(const std::vector<uint64_t> &thresholds, unsigned planes, const char *who)
+{
+    if (planes < 1 || planes > 64 || (planes < 64 && (thresholds.size() >> planes) != 0))
+        throw std::invalid_argument(std::string("certFHE::") + who + ": the bucket index does not fit in the planes");
+    std::vector<uint64_t> values(thresholds.size() + 1);
+    for (size_t i = 0; i < values.size(); ++i)
+        values[i] = i;
+    return values;
+}
+
+} // namespace
+
+CiphertextBatch inRange(const UIntBatch &a, uint64_t lo, uint64_t hi)
+{
+    std::vector<PlainEntries> planes(1);
+    const bool all = rangeEntries(a, lo, hi, "inRange", planes[0]);
+    return plainSum(a, planes, all ? 1 : 0, "inRange")[0];
+}
+
+CiphertextBatch outOfRange(const UIntBatch &a, uint64_t lo, uint64_t hi)
+{
+    std::vector<PlainEntries> planes(1);
+    if (rangeEntries(a, lo, hi, "outOfRange", planes[0])) {
+        const CiphertextBatch one = plainSum(a, planes, 1, "outOfRange")[0];
+        return a.size() ? one + ones(a.plane(0)) : one;
+    }
+    return plainSum(a, planes, 1, "outOfRange")[0];
+}
+
+CiphertextBatch inRanges(const UIntBatch &a, const std::vector<std::pair<uint64_t, uint64_t> > &intervals)
+{
+    std::vector<PlainEntries> planes(1);
+    uint64_t constant = 0;
+    for (size_t i = 0; i < intervals.size(); ++i) {
+        if (i && intervals[i].first <= intervals[i - 1].second)
+            throw std::invalid_argument("certFHE::inRanges: the intervals must be disjoint and ascend");
+        if (rangeEntries(a, intervals[i].first, intervals[i].second, "inRanges", planes[0]))
+            constant = 1;
+    }
+    return plainSum(a, planes, constant, "inRanges")[0];
+}
+
+CiphertextBatch isIn(const UIntBatch &a, const std::vector<uint64_t> &set)
+{
+    return plainSum(a, std::vector<PlainEntries>(1, setEntries(a, set, "isIn")), 0, "isIn")[0];
+}
+
+CiphertextBatch notIn(const UIntBatch &a, const std::vector<uint64_t> &set)
+{
+    return plainSum(a, std::vector<PlainEntries>(1, setEntries(a, set, "notIn")), 1, "notIn")[0];
+}
+
+UIntBatch stepFunction(const UIntBatch &a, const std::vector<uint64_t> &thresholds, const std::vector<uint64_t> &values,
+                       unsigned out_width)
+{
+    std::vector<PlainEntries> planes;
+    const uint64_t constant = stepEntries(a, thresholds, values, out_width, "stepFunction", planes);
+    return UIntBatch::fromPlanes(plainSum(a, planes, constant, "stepFunction"));
+}
+
+UIntBatch bucketOf(const UIntBatch &a, const std::vector<uint64_t> &thresholds, unsigned planes)
+{
+    const std::vector<uint64_t> values = bucketValues(thresholds, planes, "bucketOf");
+    std::vector<PlainEntries> entries;
+    const uint64_t constant = stepEntries(a, thresholds, values, planes, "bucketOf", entries);
+    return UIntBatch::fromPlanes(plainSum(a, entries, constant, "bucketOf"));
+}
+
+UIntBatch lookupSparse(const UIntBatch &a, const std::vector<uint64_t> &keys, const std::vector<uint64_t> &values,
+                       unsigned out_width, uint64_t otherwise)
+{
+    requireOutWidth(out_width, values, "lookupSparse");
+    requireOutWidth(out_width, std::vector<uint64_t>(1, otherwise), "lookupSparse");
+    if (keys.size() != values.size())
+        throw std::invalid_argument("certFHE::lookupSparse: every key takes one value");
+    std::map<uint64_t, uint64_t> table;                   // distinct keys ascending; the first of equal keys counts
+    for (size_t i = 0; i < keys.size(); ++i) {
+        requireBelow(a, keys[i], "lookupSparse", "a key");
+        table.insert(std::make_pair(keys[i], values[i]));
+    }
+    std::vector<PlainEntries> planes(out_width);
+    for (unsigned j = 0; j < out_width; ++j)
+        for (std::map<uint64_t, uint64_t>::const_iterator it = table.begin(); it != table.end(); ++it)
+            if (((it->second ^ otherwise) >> j) & 1u)
+                planes[j].push_back(PlainEntry(CSGN_UINT_PLAIN_EQ, it->first));
+    return UIntBatch::fromPlanes(plainSum(a, planes, otherwise, "lookupSparse"));
+}
+
+const char *plainSumRoute(const UIntBatch &a, const std::vector<uint64_t> &thresholds, const std::vector<uint64_t> &values,
+                          unsigned out_width)
+{
+    std::vector<PlainEntries> planes;
+    const uint64_t constant = stepEntries(a, thresholds, values, out_width, "plainSumRoute", planes);
+    bool computes = false;
+    for (unsigned j = 0; j < out_width; ++j)
+        computes = computes || plainSumKind(planes[j], (constant >> j) & 1u) == SUM_COMPUTED;
+    return a.size() != 0 && Planes(a).uniform && computes ? "call" : "loop";
+}
+
 // ------------------------------------------------------------------ selection by a < b (csgn_uint_lt_select)
 
 namespace {

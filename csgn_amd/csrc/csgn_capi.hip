@@ -2161,6 +2161,153 @@ int csgn_uint_linear(uint64_t n_bits, uint64_t batch, uint64_t in_width, const u
     return CSGN_OK;
 }
 
+/* ------------------------------------------------ sums of comparisons against public constants ---- */
+
+uint64_t csgn_uint_plain_sum_terms(uint64_t width, const uint64_t *h_terms, uint64_t n_entries, const int *h_cmp,
+                                   const uint64_t *h_k, int constant_bit)
+{
+    return csgn::uint_plain_sum_terms(width, (const u64 *)h_terms, n_entries, h_cmp, (const u64 *)h_k, constant_bit);
+}
+
+int csgn_uint_plain_sum_decode(uint64_t width, const uint64_t *h_terms, uint64_t n_entries, const int *h_cmp,
+                               const uint64_t *h_k, int constant_bit, uint64_t q, uint64_t *h_level_plane,
+                               uint64_t *h_level_term, uint64_t *h_n_factors)
+{
+    return csgn::uint_plain_sum_decode(width, (const u64 *)h_terms, n_entries, h_cmp, (const u64 *)h_k, constant_bit, q,
+                                       (u64 *)h_level_plane, (u64 *)h_level_term, (u64 *)h_n_factors) ? 1 : 0;
+}
+
+namespace {
+
+/* what csgn_uint_plain_sum_plan and csgn_uint_plain_sum_create check before the device, in the documented order */
+int check_plain_sum(uint64_t width, const uint64_t *h_terms, uint64_t n_out, const uint64_t *h_first, const int *h_cmp,
+                    const uint64_t *h_k, uint64_t constant, bool records, csgn::PlainSumPlan &pl)
+{
+    REQUIRE(width >= 1 && width <= 64, "plain sum: width %llu outside 1..64", (unsigned long long)width);
+    if (int rc = check_width(n_out, constant))
+        return rc;
+    REQUIRE(h_terms && h_first, "null host pointer");
+    REQUIRE(h_first[0] == 0, "plain sum: h_first[0] is %llu, not 0", (unsigned long long)h_first[0]);
+    for (uint64_t x = 0; x < n_out; ++x)
+        REQUIRE(h_first[x] <= h_first[x + 1], "plain sum: h_first descends at plane %llu", (unsigned long long)x);
+    REQUIRE(h_first[n_out] == 0 || (h_cmp && h_k), "null host pointer");
+    if (h_first[n_out] > csgn::kPlainSumMaxEntries)
+        return fail(CSGN_ERR_UNSUPPORTED, "plain sum: %llu entries (at most 65536 a plan)",
+                    (unsigned long long)h_first[n_out]);
+    for (uint64_t j = 0; j < width; ++j)
+        REQUIRE(h_terms[j] != 0 && h_terms[j] < (1ull << 62), "plain sum: input plane %llu has no terms or 2^62 or more",
+                (unsigned long long)j);
+    for (uint64_t i = 0; i < h_first[n_out]; ++i) {
+        REQUIRE(h_cmp[i] >= CSGN_UINT_PLAIN_EQ && h_cmp[i] <= CSGN_UINT_PLAIN_GE, "plain sum: entry %llu: unknown "
+                "comparison %d", (unsigned long long)i, h_cmp[i]);
+        REQUIRE(width == 64 || (h_k[i] >> width) == 0, "plain sum: entry %llu: constant %llu does not fit in %llu bits",
+                (unsigned long long)i, (unsigned long long)h_k[i], (unsigned long long)width);
+    }
+    const int rc = csgn::uint_plain_sum_shape(width, (const u64 *)h_terms, n_out, (const u64 *)h_first, h_cmp,
+                                              (const u64 *)h_k, constant, records, pl);
+    if (rc == CSGN_ERR_INVALID)
+        return fail(rc, "plain sum: the term count of an entry or of a plane overflows");
+    if (rc != CSGN_OK)
+        return fail(rc, "plain sum: a plane of 2^31 terms per element or more");
+    return CSGN_OK;
+}
+
+/* the sizes of a call: every input and output plane below 2^31 words per element and 2^60 per batch */
+int check_plain_sum_sizes(const csgn::PlainSumPlan &p, uint64_t n_bits, uint64_t batch)
+{
+    const uint64_t dl = csgn_default_len(n_bits);
+    for (u32 j = 0; j < p.w; ++j)
+        if (int rc = check_size(batch, p.t[j], p.t[j], dl, "plain sum: input plane %u", j))
+            return rc;
+    for (u32 x = 0; x < p.n_out; ++x)
+        if (int rc = check_size(batch, p.T[x], p.T[x], dl, "plain sum: output %u", x))
+            return rc;
+    return CSGN_OK;
+}
+
+} // namespace
+
+struct csgn_uint_plain_sum_plan {
+    csgn::PlainSumPlan plan;
+};
+
+int csgn_uint_plain_sum_launches(uint64_t n_bits, uint64_t batch, uint64_t width, const uint64_t *h_terms, uint64_t n_out,
+                                 const uint64_t *h_first, const int *h_cmp, const uint64_t *h_k, uint64_t constant,
+                                 uint64_t *h_plan)
+{
+    if (int rc = check_n(n_bits))
+        return rc;
+    csgn::PlainSumPlan pl;
+    if (int rc = check_plain_sum(width, h_terms, n_out, h_first, h_cmp, h_k, constant, false, pl))
+        return rc;
+    REQUIRE(h_plan, "null host pointer");
+    if (int rc = check_plain_sum_sizes(pl, n_bits, batch))
+        return rc;
+    csgn::uint_plain_sum_plan(pl, n_bits, batch, (u64 *)h_plan);
+    return CSGN_OK;
+}
+
+int csgn_uint_plain_sum_create(uint64_t width, const uint64_t *h_terms, uint64_t n_out, const uint64_t *h_first,
+                               const int *h_cmp, const uint64_t *h_k, uint64_t constant, csgn_uint_plain_sum_plan **plan)
+{
+    REQUIRE(plan, "plan is null");
+    *plan = nullptr;
+    csgn_uint_plain_sum_plan *p = new csgn_uint_plain_sum_plan();
+    int rc = check_plain_sum(width, h_terms, n_out, h_first, h_cmp, h_k, constant, true, p->plan);
+    if (rc == CSGN_OK)
+        rc = require_device("csgn_uint_plain_sum_create");
+    if (rc == CSGN_OK) {
+        hipError_t e = hipSuccess;
+        if (csgn::uint_plain_sum_create(p->plan, e) != CSGN_OK)
+            rc = hip_fail(e, "csgn_uint_plain_sum_create");
+    }
+    if (rc != CSGN_OK) {
+        delete p;
+        return rc;
+    }
+    *plan = p;
+    return CSGN_OK;
+}
+
+uint64_t csgn_uint_plain_sum_plan_terms(const csgn_uint_plain_sum_plan *plan, uint64_t x)
+{
+    return plan && x < plan->plan.n_out ? plan->plan.T[x] : 0;
+}
+
+void csgn_uint_plain_sum_destroy(csgn_uint_plain_sum_plan *plan)
+{
+    if (!plan)
+        return;
+    csgn::uint_plain_sum_free(plan->plan);
+    delete plan;
+}
+
+int csgn_uint_plain_sum(const csgn_uint_plain_sum_plan *plan, uint64_t n_bits, uint64_t batch,
+                        const uint64_t *const *h_planes, uint64_t *const *h_out, void *stream)
+{
+    if (int rc = check_n(n_bits))
+        return rc;
+    REQUIRE(h_planes && h_out, "null host pointer");
+    if (!plan) {                      /* no plan exists without a device: say so before calling the pointer null */
+        if (int rc = require_device("csgn_uint_plain_sum"))
+            return rc;
+        return fail(CSGN_ERR_INVALID, "plan is null");
+    }
+    const csgn::PlainSumPlan &p = plan->plan;
+    if (int rc = check_plain_sum_sizes(p, n_bits, batch))
+        return rc;
+    if (int rc = check_planes(h_planes, nullptr, p.w, "input plane"))
+        return rc;
+    if (int rc = check_planes((const uint64_t *const *)h_out, nullptr, p.n_out, "output"))
+        return rc;
+    if (int rc = require_device("csgn_uint_plain_sum"))
+        return rc;
+    if (batch == 0)
+        return CSGN_OK;
+    HIP_TRY(csgn::uint_plain_sum(p, n_bits, batch, (const u64 *const *)h_planes, (u64 *const *)h_out, S(stream)));
+    return CSGN_OK;
+}
+
 /* ------------------------------------------------ one-bit batches decrypted into one word per element ---- */
 
 const char *csgn_uint_decrypt_kernel(uint64_t n_bits, uint64_t batch, uint64_t n_planes, const uint64_t *h_terms)

@@ -1,10 +1,12 @@
 // csgn_chain.h -- the host side of the left-nested chains over the planes a_j and n_j = a_j + ONE that
-// csgn_uint_plain.hip and csgn_uint_addk.hip evaluate: the chain's description, its term counts,
+// csgn_uint_plain.hip, csgn_uint_plain_sum.hip and csgn_uint_addk.hip evaluate: the
+// chain's description, its term counts, one comparison's chain (plain_shape) with its cut and radix-1 levels,
 // the level table of the fused kernels (decoded by csgn_device.h's chain_term / chain_walk) and the composed form that
 // runs it level by level through the tuned launchers.  Host code only.  Internal.
 #pragma once
 
 #include "csgn_device.h"
+#include "csgn_hip.h"
 
 namespace csgn {
 
@@ -82,6 +84,76 @@ void chain_fill(const Chain *c, u32 w, u32 end, const u64 *t, Args &a)
         }
         a.rad.set(j, d);
     }
+}
+
+// ------------------------------------------------------------------------------ one comparison
+// csgn_uint_plain.hip and csgn_uint_plain_sum.hip: the chain the kernels decode and the composed form runs, or ZERO.
+struct PlainShape {
+    bool zero = false, neg = false;
+    u32 w = 0;
+    Chain c;
+    u64 T = 0;                             // terms of the result
+};
+
+// false: invalid argument or a term count past kTermLimit
+inline bool plain_shape(int cmp, u64 w, u64 k, const u64 *t, PlainShape &sh)
+{
+    sh = PlainShape();
+    if (cmp < CSGN_UINT_PLAIN_EQ || cmp > CSGN_UINT_PLAIN_GE || !chain_arguments(w, k, t))
+        return false;
+    sh.w = (u32)w;
+    const u64 all = w == 64 ? ~0ull : (1ull << w) - 1;
+    // NE = NOT EQ, LE = NOT GT, GE = NOT LT
+    const int base_cmp = cmp == CSGN_UINT_PLAIN_NE ? CSGN_UINT_PLAIN_EQ
+                       : cmp == CSGN_UINT_PLAIN_LE ? CSGN_UINT_PLAIN_GT
+                       : cmp == CSGN_UINT_PLAIN_GE ? CSGN_UINT_PLAIN_LT : cmp;
+    sh.neg = base_cmp != cmp;
+    if ((base_cmp == CSGN_UINT_PLAIN_LT && k == 0) || (base_cmp == CSGN_UINT_PLAIN_GT && k == all)) {
+        sh.zero = true;
+        sh.T = sh.neg ? 2 : 1;
+        return true;
+    }
+    Chain &c = sh.c;
+    if (base_cmp == CSGN_UINT_PLAIN_EQ) {
+        c.nfac = ~k & all;                                       // g_j = k_j ? a_j : n_j, all factors
+    } else if (base_cmp == CSGN_UINT_PLAIN_LT) {
+        c.base = (u32)__builtin_ctzll(k);                        // l = n_m
+        c.sum = c.tail_n = k & (all << c.base << 1);             // l = (l * a_j) + n_j where k_j = 1
+        c.nfac = ~k & all & (all << c.base << 1);                // l = l * n_j where k_j = 0
+        c.nfac |= 1ull << c.base;
+    } else {
+        c = chain_greater(w, k);
+    }
+    c.top = sh.w - 1;
+    if (!chain_terms(c, t))
+        return false;
+    sh.T = c.L[c.top] + (sh.neg ? 1 : 0);
+    return sh.T < kTermLimit;
+}
+
+// the cut of a run of R terms: the fewest top levels whose digits cover a run (their product of radices >= R); levels
+// [cut, top] are walked per term, the rest is kept per run
+inline u32 plain_cut(const PlainShape &sh, const u64 *t, u32 R)
+{
+    if (sh.zero)
+        return 1u;
+    u32 cut = sh.w;
+    u64 span = 1;
+    while (cut > sh.c.base + 1 && span < R) {
+        --cut;
+        span *= t[cut] + ((sh.c.nfac >> cut) & 1u);
+    }
+    return cut;
+}
+
+// the levels above the base whose factor has one term (radix 1): the walk moves no digit there
+inline u64 plain_radix1(const PlainShape &sh, const u64 *t)
+{
+    u64 unit = 0;
+    for (u32 j = sh.c.base + 1; !sh.zero && j < sh.w; ++j)
+        if (t[j] + ((sh.c.nfac >> j) & 1u) == 1u)
+            unit |= 1ull << j;
+    return unit;
 }
 
 // The composed form: levels [c.base, end) through the tuned launchers, each level's value written whole before the

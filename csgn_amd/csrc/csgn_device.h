@@ -1,7 +1,7 @@
 // csgn_device.h -- helpers shared by the kernel translation units (csgn_mul.hip, csgn_add.hip, csgn_decrypt.hip,
 // csgn_encrypt.hip, csgn_permute.hip, csgn_compact.hip, csgn_harness.hip, and the uniform-batch families
 // csgn_gates.hip, csgn_uint.hip, csgn_uint_plain.hip, csgn_uint_addk.hip, csgn_uint_lut.hip, csgn_uint_read.hip,
-// csgn_uint_find.hip, csgn_uint_first.hip, csgn_uint_nth.hip, csgn_uint_lt_select.hip, csgn_uint_decrypt.hip, csgn_matmul.hip, csgn_count.hip, csgn_count_prefix.hip, csgn_uint_add_where.hip, csgn_uint_linear.hip, csgn_wsum.hip, csgn_gather.hip):
+// csgn_uint_find.hip, csgn_uint_first.hip, csgn_uint_nth.hip, csgn_uint_lt_select.hip, csgn_uint_decrypt.hip, csgn_matmul.hip, csgn_count.hip, csgn_count_prefix.hip, csgn_uint_add_where.hip, csgn_uint_linear.hip, csgn_uint_plain_sum.hip, csgn_wsum.hip, csgn_gather.hip):
 // 16-/8-byte unit access and the choice between them, the ONE and ZERO terms' units, FastDiv tables in kernel
 // arguments, the XCD-contiguous block order, CSR pair search, the LDS subset tables of DESIGN §4.15 (csgn_selector.h
 // builds the skeleton of the read, find and lt_select kernels on them), launch limits,
@@ -422,26 +422,94 @@ __device__ inline Unit chain_term(const Args &a, u32 j, u64 elem_units, u32 i, u
     return i < tj ? v : one;
 }
 
-// levels j = hi down to lo (inclusive, lo >= base) applied to idx; returns true when a tail or the base ended the walk
-template <typename Unit, typename Args>
-__device__ inline bool chain_walk(const Args &a, u32 hi, u32 lo, u64 eu, u32 k, Unit one, u32 &idx, Unit &v)
+// levels j = hi down to lo (inclusive, lo >= base) applied to idx, factor(j, i) called for term i of level j's list
+// (i == t_j: the ONE of n_j); returns true when a tail or the base ended the walk.  Host and device: the decode by
+// position of csgn_uint_plain_sum_decode is this walk with a factor that records its arguments.
+template <typename Args, typename Factor>
+__host__ __device__ inline bool chain_walk_each(const Args &a, u32 hi, u32 lo, u32 &idx, Factor factor)
 {
     for (u32 j = hi + 1u; j-- > lo;) {
         if (j == a.base) {
-            v &= chain_term<Unit>(a, j, eu, idx, k, one);
+            factor(j, idx);
             return true;
         }
         const u32 pe = a.pend[j];
         if (idx >= pe) {                                  // a sum level's tail: a_j, or n_j
-            v &= chain_term<Unit>(a, j, eu, idx - pe, k, one);
+            factor(j, idx - pe);
             return true;
         }
         const FastDiv dr = a.rad.at(j);
         const u32 q = csgn_fastdiv(idx, dr), d = idx - q * dr.d;
         idx = q;
-        v &= chain_term<Unit>(a, j, eu, d, k, one);
+        factor(j, d);
     }
     return false;
+}
+
+// the same with the factors ANDed into v
+template <typename Unit, typename Args>
+__device__ inline bool chain_walk(const Args &a, u32 hi, u32 lo, u64 eu, u32 k, Unit one, u32 &idx, Unit &v)
+{
+    return chain_walk_each(a, hi, lo, idx, [&](u32 j, u32 i) { v &= chain_term<Unit>(a, j, eu, i, k, one); });
+}
+
+// One lane's run of a comparison: unit k of the nt consecutive terms from t0 on of the chain `a`
+// describes (plane, t, pend, rad, base, U), written to o, o + U, ...  Levels [cut, top] are walked per term, loading only
+// where the digit moves (radix above 1; `unit`: the radix-1 levels) or a tail ends the walk; the AND of the levels below
+// the cut is kept in registers, keyed by the index that reaches the cut.  zero: the value is ZERO, no level is read;
+// neg: term T - 1 is the appended ONE.
+template <typename Unit, typename Args>
+__device__ inline void chain_run(const Args &a, u32 top, u32 cut, u32 zero, u32 neg, u32 T, u64 unit, u64 eu, u32 k,
+                                 Unit one, u32 t0, u32 nt, Unit *o)
+{
+    // the radix-1 factors of the fast levels: every term that passes the cut carries all of them
+    Unit fast_unit = one;
+    for (u32 j = top + 1u; !zero && j-- > cut;)
+        if ((unit >> j) & 1u)
+            fast_unit &= chain_term<Unit>(a, j, eu, 0u, k, one);
+    u32 key = 0xFFFFFFFFu;                                // the index that reached the cut, and the AND below it
+    Unit below = one;
+    for (u32 q = 0; q < nt; ++q) {
+        const u32 idx0 = t0 + q;
+        Unit v = one;
+        if (neg && idx0 == T - 1u) {
+            // the appended ONE
+        } else if (zero) {
+            v = zero_unit(Unit());
+        } else {
+            u32 idx = idx0, stop = 0xFFFFFFFFu;
+            for (u32 j = top + 1u; j-- > cut;) {
+                const u32 pe = a.pend[j];
+                if (idx >= pe) {                          // a sum level's tail
+                    v &= chain_term<Unit>(a, j, eu, idx - pe, k, one);
+                    stop = j;
+                    break;
+                }
+                if ((unit >> j) & 1u)
+                    continue;                             // d = 0, idx unchanged: f_j[0] is in fast_unit
+                const FastDiv dr = a.rad.at(j);
+                const u32 qq = csgn_fastdiv(idx, dr), d = idx - qq * dr.d;
+                idx = qq;
+                v &= chain_term<Unit>(a, j, eu, d, k, one);
+            }
+            if (stop != 0xFFFFFFFFu) {
+                // a tail at level `stop` carries the radix-1 factors above it only (a short list: tails are a small
+                // share of any large result)
+                for (u32 j = top + 1u; j-- > stop + 1u;)
+                    if ((unit >> j) & 1u)
+                        v &= chain_term<Unit>(a, j, eu, 0u, k, one);
+            } else {
+                v &= fast_unit;
+                if (idx != key) {
+                    key = idx;
+                    below = one;
+                    chain_walk<Unit>(a, cut - 1u, a.base, eu, k, one, idx, below);
+                }
+                v &= below;
+            }
+        }
+        unit_store<Unit, true>(o + (u64)q * a.U, v);
+    }
 }
 
 // ------------------------------------------------------------------------- subset tables

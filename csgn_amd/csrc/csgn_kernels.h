@@ -342,6 +342,41 @@ bool uint_linear_plan(u64 n_bits, u64 batch, u64 nin, const u64 *ta, u64 nout, c
 hipError_t uint_linear(u64 n_bits, u64 batch, u64 nin, const u64 *const *in, const u64 *ta, u64 nout, const u64 *rows,
                        u64 constant, u64 *const *out, hipStream_t stream);
 
+// sums of comparisons of one encrypted integer against public constants (csgn_uint_plain_sum.hip), include/csgn_hip.h's
+// definition: output plane x is the left-nested sum of the csgn_uint_plain results of its entries
+// (cmp[i], k[i]), first[x] <= i < first[x + 1], then ONE where bit x of `constant` is set; a plane of no entry is the
+// one-term constant.  A plan holds the shape and, on the device, every entry's level record; it lives in a
+// csgn_uint_plain_sum_plan object of the caller's.
+constexpr u32 kPlainSumMaxPlanes = 64;
+constexpr u64 kPlainSumMaxEntries = 65536;
+struct PlainSumPlan {
+    u32 w = 0, n_out = 0, stride = 0;   // input planes, output planes, words of a record
+    u64 constant = 0;
+    u64 t[64] = {};                     // terms per element of input plane j
+    u64 T[kPlainSumMaxPlanes] = {};     // terms per element of output plane x
+    u32 runs[kPlainSumMaxPlanes] = {};  // its runs of up to 16 terms, the constant's included
+    u32 efirst[kPlainSumMaxPlanes + 1] = {};
+    std::vector<u32> rec;               // the records' host copy
+    u32 *d_rec = nullptr;
+};
+// T of one plane; 0: an argument csgn_uint_plain_terms refuses, a null array, a constant_bit other than 0 / 1 or 2^62
+u64 uint_plain_sum_terms(u64 width, const u64 *terms, u64 n_entries, const int *cmp, const u64 *k, int constant_bit);
+// the factors of term q of one plane as (plane, term) pairs (plane width: ONE, width + 1: ZERO); false: refused, q past
+// the plane, more than kPlainSumMaxEntries entries or a plane of 2^31 terms or more
+bool uint_plain_sum_decode(u64 width, const u64 *terms, u64 n_entries, const int *cmp, const u64 *k, int constant_bit,
+                           u64 q, u64 *level_plane, u64 *level_term, u64 *n_factors);
+// the shape of a plan (host only; records: with the level records): CSGN_ERR_INVALID, else CSGN_ERR_UNSUPPORTED past
+// kPlainSumMaxEntries entries or for a plane of 2^31 terms or more
+int uint_plain_sum_shape(u64 width, const u64 *terms, u64 n_out, const u64 *first, const int *cmp, const u64 *k,
+                         u64 constant, bool records, PlainSumPlan &pl);
+int uint_plain_sum_create(PlainSumPlan &pl, hipError_t &herr);   // uploads the records (synchronous); CSGN_ERR_HIP
+void uint_plain_sum_free(PlainSumPlan &pl);
+// plan[6]: unit bytes for 16-byte-aligned pointers, lane items per element, plane groups, launches under the calling
+// thread's launch_blocks, elements and workgroups of the first launch
+void uint_plain_sum_plan(const PlainSumPlan &pl, u64 n_bits, u64 batch, u64 *plan);
+hipError_t uint_plain_sum(const PlainSumPlan &pl, u64 n_bits, u64 batch, const u64 *const *planes, u64 *const *out,
+                          hipStream_t stream);
+
 // an encrypted integer shifted, rotated or indexed by an encrypted amount (csgn_uint_pick.hip), include/csgn_hip.h's
 // definition: output j is the sum, ascending in r < rows_j, of EQ(index, r) * a_{src(j, r)}; op = CSGN_UINT_PICK_*.
 // index planes: v = 1..16, terms s[k]; source planes: w = 1..64, every one of t terms; rows: EACH's n, else 0.

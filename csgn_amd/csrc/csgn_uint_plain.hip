@@ -14,7 +14,9 @@
 // Reads per written unit do not grow with w, by an odometer: a lane writes unit k of a RUN of consecutive terms, walks
 // only the top (fast) levels that span a run per term, and keeps the AND of the levels below that cut in registers,
 // keyed by the index that reaches the cut; consecutive terms share it until the fast digits wrap.  A fast level of radix
-// 1 moves no digit: its factor is a per-lane constant, loaded once per lane, not per term.
+// 1 moves no digit: its factor is a per-lane constant, loaded once per lane, not per term.  The run
+// itself is csgn_device.h's chain_run, which csgn_uint_plain_sum.hip calls too; the chain's shape, its cut and its
+// radix-1 levels are csgn_chain.h's plain_shape, plain_cut and plain_radix1.
 #include "csgn_chain.h"
 #include "csgn_hip.h"
 
@@ -64,103 +66,10 @@ __global__ void __launch_bounds__(256) k_uint_plain(PlainArgs a)
     const u64 eu = (u64)e * a.U;                          // element e's first unit of a 1-term-per-element list
     const Unit one = one_unit(Unit(), k, a.U, a.last_mask);
     Unit *o = reinterpret_cast<Unit *>(a.out) + ((u64)e * a.T + t0) * a.U + k;
-    // the radix-1 factors of the fast levels: every term that passes the cut carries all of them
-    Unit fast_unit = one;
-    for (u32 j = a.top + 1u; !a.zero && j-- > a.cut;)
-        if ((a.unit >> j) & 1u)
-            fast_unit &= chain_term<Unit>(a, j, eu, 0u, k, one);
-    u32 key = 0xFFFFFFFFu;                                // the index that reached the cut, and the AND below it
-    Unit below = one;
-    for (u32 q = 0; q < nt; ++q) {
-        const u32 idx0 = t0 + q;
-        Unit v = one;
-        if (a.neg && idx0 == a.T - 1u) {
-            // the appended ONE
-        } else if (a.zero) {
-            v = zero_unit(Unit());
-        } else {
-            // the fast levels, loading only where the digit moves (|f_j| > 1) or a tail ends the walk
-            u32 idx = idx0, stop = 0xFFFFFFFFu;
-            for (u32 j = a.top + 1u; j-- > a.cut;) {
-                const u32 pe = a.pend[j];
-                if (idx >= pe) {                          // a sum level's tail
-                    v &= chain_term<Unit>(a, j, eu, idx - pe, k, one);
-                    stop = j;
-                    break;
-                }
-                if ((a.unit >> j) & 1u)
-                    continue;                             // d = 0, idx unchanged: f_j[0] is in fast_unit
-                const FastDiv dr = a.rad.at(j);
-                const u32 q = csgn_fastdiv(idx, dr), d = idx - q * dr.d;
-                idx = q;
-                v &= chain_term<Unit>(a, j, eu, d, k, one);
-            }
-            const bool done = stop != 0xFFFFFFFFu;
-            if (done) {
-                // a tail at level `stop` carries the radix-1 factors above it only (a short list: tails are a small
-                // share of any large result)
-                for (u32 j = a.top + 1u; j-- > stop + 1u;)
-                    if ((a.unit >> j) & 1u)
-                        v &= chain_term<Unit>(a, j, eu, 0u, k, one);
-            } else {
-                v &= fast_unit;
-                if (idx != key) {
-                    key = idx;
-                    below = one;
-                    chain_walk<Unit>(a, a.cut - 1u, a.base, eu, k, one, idx, below);
-                }
-                v &= below;
-            }
-        }
-        unit_store<Unit, true>(o + (u64)q * a.U, v);
-    }
+    chain_run<Unit>(a, a.top, a.cut, a.zero, a.neg, a.T, a.unit, eu, k, one, t0, nt, o);
 }
 
 // ------------------------------------------------------------------------------ the definitions on the host
-
-// One comparison: the chain (csgn_chain.h) the kernel decodes and the composed form runs, or ZERO.
-struct PlainShape {
-    bool zero = false, neg = false;
-    u32 w = 0;
-    Chain c;
-    u64 T = 0;                             // terms of the result
-};
-
-// false: invalid argument or a term count past kTermLimit
-bool plain_shape(int cmp, u64 w, u64 k, const u64 *t, PlainShape &sh)
-{
-    sh = PlainShape();
-    if (cmp < CSGN_UINT_PLAIN_EQ || cmp > CSGN_UINT_PLAIN_GE || !chain_arguments(w, k, t))
-        return false;
-    sh.w = (u32)w;
-    const u64 all = w == 64 ? ~0ull : (1ull << w) - 1;
-    // NE = NOT EQ, LE = NOT GT, GE = NOT LT
-    const int base_cmp = cmp == CSGN_UINT_PLAIN_NE ? CSGN_UINT_PLAIN_EQ
-                       : cmp == CSGN_UINT_PLAIN_LE ? CSGN_UINT_PLAIN_GT
-                       : cmp == CSGN_UINT_PLAIN_GE ? CSGN_UINT_PLAIN_LT : cmp;
-    sh.neg = base_cmp != cmp;
-    if ((base_cmp == CSGN_UINT_PLAIN_LT && k == 0) || (base_cmp == CSGN_UINT_PLAIN_GT && k == all)) {
-        sh.zero = true;
-        sh.T = sh.neg ? 2 : 1;
-        return true;
-    }
-    Chain &c = sh.c;
-    if (base_cmp == CSGN_UINT_PLAIN_EQ) {
-        c.nfac = ~k & all;                                       // g_j = k_j ? a_j : n_j, all factors
-    } else if (base_cmp == CSGN_UINT_PLAIN_LT) {
-        c.base = (u32)__builtin_ctzll(k);                        // l = n_m
-        c.sum = c.tail_n = k & (all << c.base << 1);             // l = (l * a_j) + n_j where k_j = 1
-        c.nfac = ~k & all & (all << c.base << 1);                // l = l * n_j where k_j = 0
-        c.nfac |= 1ull << c.base;
-    } else {
-        c = chain_greater(w, k);
-    }
-    c.top = sh.w - 1;
-    if (!chain_terms(c, t))
-        return false;
-    sh.T = c.L[c.top] + (sh.neg ? 1 : 0);
-    return sh.T < kTermLimit;
-}
 
 // Fused unless forced, and for w = 1 (one copy and at most one constant: the composed form is those tuned launchers).
 bool plain_use_fused(const PlainShape &sh)
@@ -185,19 +94,9 @@ hipError_t plain_fused(const PlainShape &sh, u64 n_bits, u64 batch, const u64 *c
     a.IPE = a.runs * U;
     a.dU = csgn_fastdiv_make(U);
     a.dIPE = csgn_fastdiv_make(a.IPE);
-    // the cut: the fewest top levels whose digits cover a run (their product of radices >= R); the rest is kept per run
-    a.cut = sh.zero ? 1u : sh.w;
-    if (!sh.zero) {
-        u64 span = 1;
-        while (a.cut > sh.c.base + 1 && span < a.R) {
-            --a.cut;
-            span *= t[a.cut] + ((sh.c.nfac >> a.cut) & 1u);
-        }
-    }
+    a.cut = plain_cut(sh, t, a.R);
     chain_fill(sh.zero ? nullptr : &sh.c, sh.w, sh.w, t, a);
-    for (u32 j = sh.c.base + 1; !sh.zero && j < sh.w; ++j)
-        if (a.rad.d[j] == 1u)
-            a.unit |= 1ull << j;
+    a.unit = plain_radix1(sh, t);
     a.xcd = stream_xcd(batch * sh.T * U);
     const u64 per = std::max<u64>(1, 0xFFFFFF00ull / a.IPE);            // elements per launch: < 2^32 lane items
     for (u64 e0 = 0; e0 < batch; e0 += per) {

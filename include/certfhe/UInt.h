@@ -147,6 +147,35 @@
 // is allocated or launched: std::invalid_argument for a.width() != m.inWidth(), a constant of outWidth() bits or more,
 // or an output past 2^31 words per element.  An empty batch gives empty planes.  parity(a, mask) is the one-row map.
 //
+// RANGES, SETS AND STEP FUNCTIONS OF PUBLIC CONSTANTS.  Over F2 they are sums (operator+, concatenation) of the
+// comparisons above of ONE integer, plus at most one ONE: csgn_uint_plain_sum's words (include/csgn_hip.h).  With
+// P(cmp, k) the words of the comparison of a with the public k (lessThan(a, k) is P(LT, k), ...), top = 2^w - 1:
+//     inRange(a, lo, hi)      lo == 0 and hi == top: the constant ONE;  lo == 0: lessEqual(a, hi)'s words;
+//                             hi == top: greaterEqual(a, lo)'s words;  otherwise P(LT, hi + 1) + P(LT, lo)
+//     outOfRange(a, lo, hi)   inRange's words followed by + ONE (over the full range that is ONE + ONE, two terms)
+//     inRanges(a, intervals)  the sum, in order, of the inRange entries of the disjoint ascending intervals
+//                             [lo_0, hi_0], [lo_1, hi_1], ... (hi_i < lo_{i+1}); a full interval [0, top] is + ONE
+//     isIn(a, set)            the sum of P(EQ, k_i) over the distinct values of the set, ascending (sorted and
+//                             deduplicated on the host: a duplicate would cancel over F2); notIn: followed by + ONE
+//     stepFunction(a, thresholds, values, out_width)
+//                             thresholds 0 < t_1 < ... < t_m <= top and m + 1 values below 2^out_width: the result is
+//                             v_i where t_i <= a < t_{i+1} (v_0 below t_1).  Plane j is the sum, ascending in i, of
+//                             P(LT, t_i) over the i with bit j of v_{i-1} ^ v_i set, + ONE where bit j of v_m is set
+//     bucketOf(a, thresholds, planes)    the step function with the values 0, 1, ..., m: the index of a's bucket
+//     lookupSparse(a, keys, values, out_width, otherwise)
+//                             values[i] where a == keys[i] (the first of equal keys counts), `otherwise` elsewhere.
+//                             Plane j is the sum, over the distinct keys ascending, of P(EQ, k_i) where bit j of
+//                             v_i ^ otherwise is set, + ONE where bit j of otherwise is set: a public table on integers
+//                             of any width whose cost grows with the number of keys, not with 2^w
+// A plane of no entry is the constant batch (ZERO, or ONE); a plane that is exactly one comparison is that comparison's
+// call (csgn_uint_plain); uniform planes take ONE plan and ONE csgn_uint_plain_sum (k_uint_plain_sum) for
+// all other planes, the plan cached for the process like the csgn_wsum plans; a ragged plane takes the definition
+// through the batch operators, as the comparisons do.  plainSumRoute names the route.  Every size is computed by the
+// host-only entry points before anything is allocated or launched: std::invalid_argument for lo > hi, a bound, key or
+// threshold of 2^w or more, intervals or thresholds out of order, a threshold of 0, a wrong number of values, a value
+// of 2^out_width or more, out_width outside 1..64, or an output past 2^31 words per element.  An empty batch gives
+// empty planes.
+//
 // BITWISE OPERATORS AND SHIFTS.  Between two integers of one width, context and count, per plane:
 //     a & b              a_j * b_j            a | b     logicOr(a_j, b_j)            a ^ b     a_j + b_j
 // With a public constant (k < 2^width) and for a public distance s nothing is computed on ciphertext words beyond a
@@ -509,6 +538,28 @@ CiphertextBatch parity(const UIntBatch &a, uint64_t mask);
 // left to compute or the batch is empty, which launch nothing).  No device work; for diagnostics and tests, like
 // arithRoute: the words are the same.
 const char *linearRoute(const UIntBatch &a, const F2Matrix &m, uint64_t constant = 0);
+
+// element i: lo <= a[i] <= hi, one encrypted bit / its negation; lo <= hi < 2^width
+CiphertextBatch inRange(const UIntBatch &a, uint64_t lo, uint64_t hi);
+CiphertextBatch outOfRange(const UIntBatch &a, uint64_t lo, uint64_t hi);
+// element i: a[i] lies in one of the disjoint ascending intervals (lo, hi)
+CiphertextBatch inRanges(const UIntBatch &a, const std::vector<std::pair<uint64_t, uint64_t> > &intervals);
+// element i: a[i] is / is not a value of the set (any order, duplicates allowed); an empty set gives ZERO / ONE
+CiphertextBatch isIn(const UIntBatch &a, const std::vector<uint64_t> &set);
+CiphertextBatch notIn(const UIntBatch &a, const std::vector<uint64_t> &set);
+// element i: values[number of thresholds <= a[i]], of out_width bits; thresholds strictly ascending in 1 .. 2^width - 1
+UIntBatch stepFunction(const UIntBatch &a, const std::vector<uint64_t> &thresholds, const std::vector<uint64_t> &values,
+                       unsigned out_width);
+// element i: the number of thresholds <= a[i], of `planes` bits (thresholds.size() < 2^planes)
+UIntBatch bucketOf(const UIntBatch &a, const std::vector<uint64_t> &thresholds, unsigned planes);
+// element i: values[r] where a[i] == keys[r], else `otherwise`, of out_width bits
+UIntBatch lookupSparse(const UIntBatch &a, const std::vector<uint64_t> &keys, const std::vector<uint64_t> &values,
+                       unsigned out_width, uint64_t otherwise = 0);
+// The route stepFunction(a, thresholds, values, out_width) takes (a static string): "call" (one csgn_uint_plain_sum for
+// every plane that is neither a constant nor a single comparison) or "loop" (the comparisons and operator+ plane by
+// plane: a ragged plane; also when no plane is left to compute or the batch is empty).  No device work.
+const char *plainSumRoute(const UIntBatch &a, const std::vector<uint64_t> &thresholds, const std::vector<uint64_t> &values,
+                          unsigned out_width);
 
 // element i: a[i] < b[i] ? a[i] : b[i] / the other one; a tie takes b for min and a for max
 UIntBatch min(const UIntBatch &a, const UIntBatch &b);

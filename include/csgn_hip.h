@@ -1248,6 +1248,86 @@ int csgn_uint_linear(uint64_t n_bits, uint64_t batch, uint64_t in_width, const u
                      const uint64_t *h_terms, uint64_t out_width, const uint64_t *h_rows, uint64_t constant,
                      uint64_t *const *h_out, void *stream);
 
+/* ------------------------------------- sums of comparisons against public constants ---- */
+
+/* csgn_uint_plain_sum: sums over F2 of comparisons of ONE ENCRYPTED integer against PUBLIC constants, every output
+ * plane in one launch: what certfhe/UInt.h's inRange, inRanges, isIn, stepFunction, bucketOf and lookupSparse compute.
+ * A range lo <= a <= hi is [a < hi + 1] + [a < lo]; membership in a set is the sum of the disjoint [a == k_i]; bit j of a
+ * step function is the sum of [a < t_i] over the thresholds where bit j of the value changes.  None of them multiplies
+ * beyond what each comparison multiplies.
+ * Inputs:
+ *   - width uniform planes a_0 ... a_{w-1} (width in 1..64, bit 0 first), plane j of h_terms[j] = t_j >= 1 terms per
+ *     element;
+ *   - n_out output planes (1..64).  The entries of plane x are h_first[x] .. h_first[x+1] - 1 (h_first[0] = 0, h_first
+ *     non-descending, n_out + 1 values) of the parallel host arrays h_cmp[] (CSGN_UINT_PLAIN_EQ .. GE) and h_k[] (each
+ *     below 2^width);
+ *   - `constant`, whose bit x adds ONE to plane x (a bit at or above n_out: CSGN_ERR_INVALID).
+ * Output plane x is the left-nested sum (the reference's operator+: concatenation) of its entries' csgn_uint_plain
+ * results, in order and word for word -- the ONE that NE / LE / GE append and the one-term ZERO of LT k = 0 and
+ * GT k = 2^w - 1 included --, followed by + ONE where constant_x = 1:
+ *     plane x = ((P(cmp_i1, k_i1) + P(cmp_i2, k_i2)) + ...) + P(cmp_im, k_im) [+ ONE]
+ *     T_x = sum over the plane's entries of csgn_uint_plain_terms(cmp_i, width, k_i, h_terms), + constant_x
+ * A plane with no entry is the one-term constant: ZERO (zero words) for constant_x = 0, ONE for 1; T_x = 1
+ * (csgn_uint_linear's rule for an empty row).  Input pointers may alias one another; no output overlaps an input or
+ * another output.  Nothing cancels on the device: an entry named twice is written twice (and cancels over F2 only at
+ * decryption); certfhe/UInt.h sorts and deduplicates on the host. */
+/* T of ONE plane of n_entries entries (host only).  0 for anything csgn_uint_plain_terms refuses in an entry, a null
+ * array (h_cmp and h_k may be null when n_entries = 0), a constant_bit other than 0 or 1, or a count of 2^62 or more. */
+uint64_t csgn_uint_plain_sum_terms(uint64_t width, const uint64_t *h_terms, uint64_t n_entries, const int *h_cmp,
+                                   const uint64_t *h_k, int constant_bit);
+/* The decode by position (host only): term q < T of ONE plane is the AND of *h_n_factors (1..64) terms, factor f being
+ * term h_level_term[f] of input plane h_level_plane[f]; plane `width` means ONE and `width + 1` means ZERO (term 0):
+ * the ONE of a factor a_j + ONE, the ONE an entry or the plane appends, the ZERO of an entry or of an empty plane.
+ * Factors come from the top plane down.  It runs the functions the kernel runs: the entry search (sum_entry,
+ * csgn_uint_plain_sum.hip) over the entries' first terms, then the chain walk (chain_walk_each, csgn_device.h) over
+ * the entry's level record.  Returns 1, or 0 (nothing written) for arguments csgn_uint_plain_sum_terms refuses, more
+ * than 65536 entries, a plane of 2^31 terms or more, q >= T or a null pointer. */
+int csgn_uint_plain_sum_decode(uint64_t width, const uint64_t *h_terms, uint64_t n_entries, const int *h_cmp,
+                               const uint64_t *h_k, int constant_bit, uint64_t q, uint64_t h_level_plane[65],
+                               uint64_t h_level_term[65], uint64_t *h_n_factors);
+/* How a call of this shape is cut under the calling thread's knob "launch_blocks" (host only, no device work).  A lane
+ * item is (element, plane, run of up to 16 consecutive terms of ONE entry, unit); the plane's constant is a run of its
+ * own.  The grid is plane-major: every plane's items of the launch's elements rounded up to whole 256-lane workgroups.
+ * Launches are cut at elements: ne elements go where  sum over the planes of ceil(ne * items_x / 256)  workgroups fit,
+ * bounded by  ne * items / 256 + planes  (one element goes whole whatever the knob says).
+ *     h_plan[0]  bytes of the unit one lane writes when every pointer is 16-byte aligned: 16 for an even number of
+ *                words per term, else 8 (a call with a pointer off alignment takes 8-byte units: twice the units)
+ *     h_plan[1]  lane items per element over all output planes
+ *     h_plan[2]  plane groups: 1, unless ONE element of all planes passes HIP's limit of 2^32 lanes a launch; the planes
+ *                then go in that many runs of consecutive planes, each with launches of its own
+ *     h_plan[3]  launches (0 for batch == 0)
+ *     h_plan[4]  elements of the first launch
+ *     h_plan[5]  workgroups of the first launch
+ * The same checks as csgn_uint_plain_sum_create, in its order, then h_plan, then the sizes of csgn_uint_plain_sum. */
+int csgn_uint_plain_sum_launches(uint64_t n_bits, uint64_t batch, uint64_t width, const uint64_t *h_terms,
+                                 uint64_t n_out, const uint64_t *h_first, const int *h_cmp, const uint64_t *h_k,
+                                 uint64_t constant, uint64_t h_plan[6]);
+/* The plan of one shape: every entry's level record (base, top, cut, the zero / neg flags, the radix-1 mask, pend[],
+ * the FastDivs and T, with the entry's first run and first term in its plane) built from the chain of csgn_uint_plain
+ * and uploaded once, synchronously.  Checks, in this order: `plan`; width; n_out and the constant; h_terms and h_first,
+ * h_first[0] = 0 and non-descending, h_cmp and h_k where there is an entry (CSGN_ERR_INVALID); more than 65536 entries
+ * (CSGN_ERR_UNSUPPORTED); the planes' term counts, the comparisons and constants of the entries, the term counts of the
+ * results (CSGN_ERR_INVALID); an output plane of 2^31 terms per element or more (CSGN_ERR_UNSUPPORTED); the device
+ * (CSGN_ERR_NO_DEVICE, no CPU fallback).  Release with csgn_uint_plain_sum_destroy (null is ignored).  A plan is
+ * immutable: any number of threads and streams may launch from it. */
+typedef struct csgn_uint_plain_sum_plan csgn_uint_plain_sum_plan;
+int csgn_uint_plain_sum_create(uint64_t width, const uint64_t *h_terms, uint64_t n_out, const uint64_t *h_first,
+                               const int *h_cmp, const uint64_t *h_k, uint64_t constant,
+                               csgn_uint_plain_sum_plan **plan);
+/* T_x of plane x of the plan; 0 for a null plan or x >= n_out */
+uint64_t csgn_uint_plain_sum_plan_terms(const csgn_uint_plain_sum_plan *plan, uint64_t x);
+void csgn_uint_plain_sum_destroy(csgn_uint_plain_sum_plan *plan);
+/* The operation over `batch` elements.  h_planes and h_out are HOST arrays of width / n_out device pointers: input
+ * plane j takes batch * t_j * dL words and output x batch * T_x * dL words.  Checks, in this order: n_bits; the host
+ * arrays; the plan (a null plan is CSGN_ERR_NO_DEVICE where there is no device -- no plan exists there -- and
+ * CSGN_ERR_INVALID otherwise); every t_j * dL and T_x * dL below 2^31 words per element and batch times that below
+ * 2^60 (CSGN_ERR_UNSUPPORTED); null device pointers, all `width` inputs and n_out outputs (CSGN_ERR_INVALID); the
+ * device (CSGN_ERR_NO_DEVICE, no CPU fallback).  batch == 0 succeeds.  On the caller's stream, asynchronous and
+ * graph-capturable: k_uint_plain_sum, one launch for every shape csgn_uint_plain_sum_launches gives one;
+ * no scratch, no allocation, no synchronisation. */
+int csgn_uint_plain_sum(const csgn_uint_plain_sum_plan *plan, uint64_t n_bits, uint64_t batch,
+                        const uint64_t *const *h_planes, uint64_t *const *h_out, void *stream);
+
 /* ------------------------------------- one-bit batches decrypted into one word per element ---- */
 
 /* n_planes one-bit batches of `batch` elements decrypted in ONE pass into one 64-bit word per element: what
