@@ -727,6 +727,68 @@ class HipPath:
             self.lib.csgn_uint_plain_sum_destroy(handle)
         return outs
 
+    @staticmethod
+    def _bilinear_arrays(ta, tb, planes_pairs):
+        """Host arrays of a csgn_uint_bilinear shape: planes_pairs[x] is the list of (left, right) of output plane x."""
+        flat = [e for pairs in planes_pairs for e in pairs]
+        first = [0]
+        for pairs in planes_pairs:
+            first.append(first[-1] + len(pairs))
+        h_ta = (C.c_uint64 * max(len(ta), 1))(*[int(t) for t in ta])
+        h_tb = (C.c_uint64 * max(len(tb), 1))(*[int(t) for t in tb])
+        h_first = (C.c_uint64 * len(first))(*first)
+        h_left = (C.c_uint64 * max(len(flat), 1))(*[int(i) for i, _ in flat])
+        h_right = (C.c_uint64 * max(len(flat), 1))(*[int(l) for _, l in flat])
+        return h_ta, h_tb, h_first, h_left, h_right
+
+    def uint_bilinear_launches(self, n_bits: int, batch: int, ta, tb, planes_pairs, constant: int = 0):
+        """csgn_uint_bilinear_launches: [unit bytes, units per element, G, tiles, workgroups per tile, launches,
+        workgroups of the first launch, plane groups, staged, units a workgroup walks, operand units per element, the
+        LDS budget in bytes] of a csgn_uint_bilinear call of this shape under the calling thread's knobs."""
+        h_ta, h_tb, h_first, h_left, h_right = self._bilinear_arrays(ta, tb, planes_pairs)
+        plan = (C.c_uint64 * 12)()
+        check(self.lib.csgn_uint_bilinear_launches(n_bits, batch, len(ta), h_ta, len(tb), h_tb, len(planes_pairs), h_first,
+                                                   h_left, h_right, int(constant), plan))
+        return [int(x) for x in plan]
+
+    def uint_bilinear_create(self, ta, tb, planes_pairs, constant: int = 0) -> int:
+        """csgn_uint_bilinear_create: the plan of the output planes planes_pairs[x] = [(left, right), ...] over planes
+        a_i of ta[i] and b_l of tb[l] terms per element, plus ONE in the planes whose bit of `constant` is set.  Returns
+        the handle; release it with self.lib.csgn_uint_bilinear_destroy."""
+        h_ta, h_tb, h_first, h_left, h_right = self._bilinear_arrays(ta, tb, planes_pairs)
+        handle = C.c_void_p()
+        check(self.lib.csgn_uint_bilinear_create(len(ta), h_ta, len(tb), h_tb, len(planes_pairs), h_first, h_left, h_right,
+                                                 int(constant), C.byref(handle)))
+        return handle.value
+
+    def uint_bilinear_apply(self, handle: int, n_bits: int, batch: int, a, b, n_out: int, outs=None):
+        """csgn_uint_bilinear of a plan over the encrypted integers `a` and `b` (bit 0 first).  Returns the output
+        planes, of csgn_uint_bilinear_plan_terms terms per element, fresh ones unless `outs` is given."""
+        dl = self.default_len(n_bits)
+        T = [int(self.lib.csgn_uint_bilinear_plan_terms(handle, x)) for x in range(n_out)]
+        assert all(T), "not a plane of the plan"
+        sizes = [batch * t * dl for t in T]
+        if outs is None:
+            outs = [self.empty_words(max(s, 1)) for s in sizes]
+        assert all(o.numel() >= s for o, s in zip(outs, sizes))
+        h_a = (C.c_void_p * len(a))(*[_ptr(p) for p in a])
+        h_b = (C.c_void_p * len(b))(*[_ptr(p) for p in b])
+        h_out = (C.c_void_p * n_out)(*[_ptr(o) for o in outs])
+        check(self.lib.csgn_uint_bilinear(handle, n_bits, batch, h_a, h_b, h_out, self.stream))
+        return [o[:s] for o, s in zip(outs, sizes)]
+
+    def uint_bilinear(self, n_bits: int, batch: int, a, ta, b, tb, planes_pairs, constant: int = 0, outs=None):
+        """csgn_uint_bilinear with a plan of its own: output plane x is the sum of a[left] * b[right] over
+        planes_pairs[x] = [(left, right), ...], plus ONE where bit x of `constant` is set."""
+        assert len(a) == len(ta) and len(b) == len(tb)
+        handle = self.uint_bilinear_create(ta, tb, planes_pairs, constant)
+        try:
+            outs = self.uint_bilinear_apply(handle, n_bits, batch, a, b, len(planes_pairs), outs)
+            torch.cuda.current_stream(self.device).synchronize()
+        finally:
+            self.lib.csgn_uint_bilinear_destroy(handle)
+        return outs
+
     def uint_bitwise(self, n_bits: int, op: int, batch: int, a, a_terms, b=None, b_terms=None, sel=None, sel_terms: int = 0,
                      outs=None):
         """csgn_uint_bitwise: op = 1 a & b, 2 a | b, 3 a ^ b, 4 ~a, 5 sel ? a : b, 6 sel ? a : 0 of the encrypted

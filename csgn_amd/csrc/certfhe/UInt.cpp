@@ -1185,6 +1185,28 @@ F2Matrix F2Matrix::gfMul(unsigned w, uint64_t k, uint64_t poly)
     return F2Matrix(rows, w);
 }
 
+F2Matrix F2Matrix::gfSquare(unsigned w, uint64_t poly)
+{
+    requireMatrixWidth(w, "gfSquare");
+    if (w < 64 && (poly >> w) > 1)
+        throw std::invalid_argument("certFHE::F2Matrix::gfSquare: the polynomial has a term above X^w");
+    const uint64_t low = poly & lowBits(w);
+    std::vector<uint64_t> rows(w, 0);
+    uint64_t c = 1;                                       // X^(2i) mod poly: column i, since (sum x_i X^i)^2 = sum x_i X^(2i)
+    for (unsigned i = 0; i < w; ++i) {
+        for (unsigned j = 0; j < w; ++j)
+            if ((c >> j) & 1u)
+                rows[j] |= 1ull << i;
+        for (int twice = 0; twice < 2; ++twice) {
+            const bool carry = (c >> (w - 1)) & 1u;
+            c = (c << 1) & lowBits(w);
+            if (carry)
+                c ^= low;
+        }
+    }
+    return F2Matrix(rows, w);
+}
+
 F2Matrix F2Matrix::grayEncode(unsigned w)
 {
     requireMatrixWidth(w, "grayEncode");
@@ -1332,6 +1354,314 @@ const char *linearRoute(const UIntBatch &a, const F2Matrix &m, uint64_t constant
 {
     requireLinear(a, m, constant, "linearRoute");
     return a.size() != 0 && Planes(a).uniform && linearComputes(m, constant) ? "call" : "loop";
+}
+
+// ------------------------------------------------------------------ public bilinear forms over F2 (csgn_uint_bilinear)
+
+namespace {
+
+typedef F2Bilinear::Pair BilinearPair;
+typedef std::vector<std::vector<BilinearPair> > BilinearRows;
+
+void requireFormWidth(unsigned w, const char *who)
+{
+    if (w < 1 || w > 64)
+        throw std::invalid_argument(std::string("certFHE::F2Bilinear::") + who + ": width must be 1..64");
+}
+
+// the pairs named an odd number of times, sorted by (left, right)
+std::vector<BilinearPair> cancelPairs(std::vector<BilinearPair> pairs)
+{
+    std::sort(pairs.begin(), pairs.end());
+    std::vector<BilinearPair> kept;
+    for (size_t i = 0; i < pairs.size();) {
+        size_t j = i;
+        while (j < pairs.size() && pairs[j] == pairs[i])
+            ++j;
+        if ((j - i) & 1u)
+            kept.push_back(pairs[i]);
+        i = j;
+    }
+    return kept;
+}
+
+} // namespace
+
+F2Bilinear F2Bilinear::fromPairs(const BilinearRows &rows, unsigned left_width, unsigned right_width)
+{
+    requireFormWidth(left_width, "fromPairs");
+    requireFormWidth(right_width, "fromPairs");
+    requireFormWidth((unsigned)(rows.size() > 64 ? 65 : rows.size()), "fromPairs");
+    BilinearRows kept;
+    for (size_t j = 0; j < rows.size(); ++j) {
+        for (size_t i = 0; i < rows[j].size(); ++i)
+            if (rows[j][i].first >= left_width || rows[j][i].second >= right_width)
+                throw std::invalid_argument("certFHE::F2Bilinear::fromPairs: a pair names a bit at or above its width");
+        kept.push_back(cancelPairs(rows[j]));
+    }
+    return F2Bilinear(kept, left_width, right_width);
+}
+
+F2Bilinear F2Bilinear::clmulWide(unsigned w)
+{
+    requireFormWidth(w, "clmulWide");
+    if (w > 32)
+        throw std::invalid_argument("certFHE::F2Bilinear::clmulWide: the product of a width above 32 has more than 64 planes");
+    BilinearRows rows(2 * w - 1);
+    for (unsigned i = 0; i < w; ++i)                      // ascending (i, l) in every row
+        for (unsigned l = 0; l < w; ++l)
+            rows[i + l].push_back(BilinearPair(i, l));
+    return F2Bilinear(rows, w, w);
+}
+
+F2Bilinear F2Bilinear::clmul(unsigned w)
+{
+    requireFormWidth(w, "clmul");
+    BilinearRows rows(w);
+    for (unsigned i = 0; i < w; ++i)
+        for (unsigned l = 0; i + l < w; ++l)
+            rows[i + l].push_back(BilinearPair(i, l));
+    return F2Bilinear(rows, w, w);
+}
+
+F2Bilinear F2Bilinear::gfMul(unsigned w, uint64_t poly)
+{
+    requireFormWidth(w, "gfMul");
+    if (w < 64 && (poly >> w) > 1)
+        throw std::invalid_argument("certFHE::F2Bilinear::gfMul: the polynomial has a term above X^w");
+    const uint64_t low = poly & lowBits(w);
+    std::vector<uint64_t> red(2 * w - 1);                 // X^k mod poly
+    uint64_t c = 1;
+    for (unsigned k = 0; k < 2 * w - 1; ++k) {
+        red[k] = c;
+        const bool carry = (c >> (w - 1)) & 1u;
+        c = (c << 1) & lowBits(w);
+        if (carry)
+            c ^= low;
+    }
+    BilinearRows rows(w);
+    for (unsigned i = 0; i < w; ++i)
+        for (unsigned l = 0; l < w; ++l)
+            for (unsigned j = 0; j < w; ++j)
+                if ((red[i + l] >> j) & 1u)
+                    rows[j].push_back(BilinearPair(i, l));
+    return F2Bilinear(rows, w, w);
+}
+
+F2Bilinear F2Bilinear::bitwiseAnd(unsigned w)
+{
+    requireFormWidth(w, "bitwiseAnd");
+    BilinearRows rows(w);
+    for (unsigned j = 0; j < w; ++j)
+        rows[j].push_back(BilinearPair(j, j));
+    return F2Bilinear(rows, w, w);
+}
+
+F2Bilinear F2Bilinear::dotBits(unsigned w)
+{
+    requireFormWidth(w, "dotBits");
+    BilinearRows rows(1);
+    for (unsigned j = 0; j < w; ++j)
+        rows[0].push_back(BilinearPair(j, j));
+    return F2Bilinear(rows, w, w);
+}
+
+uint64_t F2Bilinear::apply(uint64_t x, uint64_t y) const
+{
+    uint64_t z = 0;
+    for (size_t j = 0; j < rows_.size(); ++j) {
+        uint64_t bit = 0;
+        for (size_t i = 0; i < rows_[j].size(); ++i)
+            bit ^= (x >> rows_[j][i].first) & (y >> rows_[j][i].second) & 1u;
+        z |= bit << j;
+    }
+    return z;
+}
+
+F2Bilinear F2Bilinear::operator^(const F2Bilinear &rhs) const
+{
+    if (left_ != rhs.left_ || right_ != rhs.right_ || rows_.size() != rhs.rows_.size())
+        throw std::invalid_argument("certFHE::F2Bilinear::operator^: the forms differ in shape");
+    BilinearRows rows(rows_);
+    for (size_t j = 0; j < rows.size(); ++j) {
+        rows[j].insert(rows[j].end(), rhs.rows_[j].begin(), rhs.rows_[j].end());
+        rows[j] = cancelPairs(rows[j]);                   // a pair both forms contribute cancels here
+    }
+    return F2Bilinear(rows, left_, right_);
+}
+
+F2Bilinear F2Bilinear::compose(const F2Matrix &on_a, const F2Matrix &on_b) const
+{
+    if (on_a.outWidth() != left_ || on_b.outWidth() != right_)
+        throw std::invalid_argument("certFHE::F2Bilinear::compose: a map's output width is not the form's width");
+    BilinearRows rows(rows_.size());
+    for (size_t j = 0; j < rows.size(); ++j) {
+        for (size_t p = 0; p < rows_[j].size(); ++p) {
+            const uint64_t ma = on_a.rows()[rows_[j][p].first], mb = on_b.rows()[rows_[j][p].second];
+            for (unsigned i = 0; i < on_a.inWidth(); ++i)
+                if ((ma >> i) & 1u)
+                    for (unsigned l = 0; l < on_b.inWidth(); ++l)
+                        if ((mb >> l) & 1u)
+                            rows[j].push_back(BilinearPair(i, l));
+        }
+        rows[j] = cancelPairs(rows[j]);
+    }
+    return F2Bilinear(rows, on_a.inWidth(), on_b.inWidth());
+}
+
+F2Bilinear operator*(const F2Matrix &m, const F2Bilinear &form)
+{
+    if (m.inWidth() != form.outWidth())
+        throw std::invalid_argument("certFHE::operator*: the map's input width is not the form's output width");
+    BilinearRows rows(m.outWidth());
+    for (size_t j = 0; j < rows.size(); ++j) {
+        for (unsigned x = 0; x < m.inWidth(); ++x)
+            if ((m.rows()[j] >> x) & 1u)
+                rows[j].insert(rows[j].end(), form.rows()[x].begin(), form.rows()[x].end());
+    }
+    return F2Bilinear::fromPairs(rows, form.leftWidth(), form.rightWidth());
+}
+
+namespace {
+
+// device plans per (terms, rows, constant), kept until the process ends
+const csgn_uint_bilinear_plan *bilinearPlan(const std::vector<uint64_t> &ta, const std::vector<uint64_t> &tb,
+                                            const std::vector<uint64_t> &first, const std::vector<uint64_t> &left,
+                                            const std::vector<uint64_t> &right, uint64_t constant)
+{
+    static std::mutex mutex;
+    static std::map<std::vector<uint64_t>, csgn_uint_bilinear_plan *> *plans =
+        new std::map<std::vector<uint64_t>, csgn_uint_bilinear_plan *>();
+    std::vector<uint64_t> key(1, constant);
+    key.push_back(ta.size());
+    key.push_back(tb.size());
+    key.insert(key.end(), ta.begin(), ta.end());
+    key.insert(key.end(), tb.begin(), tb.end());
+    key.insert(key.end(), first.begin(), first.end());
+    key.insert(key.end(), left.begin(), left.end());
+    key.insert(key.end(), right.begin(), right.end());
+    std::lock_guard<std::mutex> lock(mutex);
+    auto it = plans->find(key);
+    if (it != plans->end())
+        return it->second;
+    csgn_uint_bilinear_plan *p = nullptr;
+    detail::check(csgn_uint_bilinear_create(ta.size(), ta.data(), tb.size(), tb.data(), first.size() - 1, first.data(),
+                                            left.data(), right.data(), constant, &p),
+                  "csgn_uint_bilinear_create");
+    (*plans)[key] = p;
+    return p;
+}
+
+void requireBilinear(const UIntBatch &a, const UIntBatch &b, const F2Bilinear &form, uint64_t constant, const char *who)
+{
+    if (a.width() != form.leftWidth() || b.width() != form.rightWidth())
+        throw std::invalid_argument(std::string("certFHE::") + who + ": an integer's width is not the form's");
+    if (a.size() != b.size() || !sameContext(a.context(), b.context()))
+        throw std::invalid_argument(std::string("certFHE::") + who + ": operands differ in count or context");
+    if (form.outWidth() < 64 && (constant >> form.outWidth()))
+        throw std::invalid_argument(std::string("certFHE::") + who + ": the constant does not fit in the form's output width");
+}
+
+unsigned requireOneWidth(const UIntBatch &a, const UIntBatch &b, const char *who)
+{
+    if (a.width() != b.width())
+        throw std::invalid_argument(std::string("certFHE::") + who + ": operands differ in width");
+    return a.width();
+}
+
+} // namespace
+
+UIntBatch bilinearMap(const UIntBatch &a, const UIntBatch &b, const F2Bilinear &form, uint64_t constant)
+{
+    requireBilinear(a, b, form, constant, "bilinearMap");
+    const unsigned m = form.outWidth();
+    const Context &ctx = a.context();
+    // every size first
+    const Planes pa(a), pb(b);
+    std::vector<uint64_t> first(1, 0), left, right, T;
+    for (unsigned x = 0; x < m; ++x) {
+        const std::vector<F2Bilinear::Pair> &row = form.rows()[x];
+        for (size_t i = 0; i < row.size(); ++i) {
+            left.push_back(row[i].first);
+            right.push_back(row[i].second);
+        }
+        T.push_back(checked(csgn_uint_bilinear_terms(pa.terms.size(), pa.terms.data(), pb.terms.size(), pb.terms.data(),
+                                                     row.size(), left.data() + first.back(), right.data() + first.back(),
+                                                     (int)((constant >> x) & 1u)),
+                            ctx, "bilinearMap"));
+        first.push_back(left.size());
+    }
+    if (a.size() == 0)
+        return UIntBatch::fromPlanes(std::vector<CiphertextBatch>(m, BatchAccess::make(ctx, 0, 1)));
+    if (pa.uniform && pb.uniform) {
+        if (left.empty()) {                               // csgn_uint_bilinear_create reads no entry array then
+            left.push_back(0);
+            right.push_back(0);
+        }
+        const csgn_uint_bilinear_plan *plan = bilinearPlan(pa.terms, pb.terms, first, left, right, constant);
+        std::vector<CiphertextBatch> out = makePlanes(ctx, a.size(), T);
+        detail::check(csgn_uint_bilinear(plan, ctx.getN(), a.size(), sources(pa).data(), sources(pb).data(),
+                                         wordsOf(out).data(), detail::stream()),
+                      "csgn_uint_bilinear");
+        return UIntBatch::fromPlanes(out);
+    }
+    // the loop: each integer's planes in one batch (plane i's element e at i * count + e), then per output plane the
+    // named operand planes gathered pair by pair, ONE element-wise product, and sumGroups, which copies nothing
+    const uint64_t count = a.size();
+    std::vector<CiphertextBatch> parts_a, parts_b;
+    for (unsigned i = 0; i < a.width(); ++i)
+        parts_a.push_back(a.plane(i));
+    for (unsigned l = 0; l < b.width(); ++l)
+        parts_b.push_back(b.plane(l));
+    const CiphertextBatch all_a = CiphertextBatch::concat(parts_a), all_b = CiphertextBatch::concat(parts_b);
+    std::vector<CiphertextBatch> out;
+    for (unsigned x = 0; x < m; ++x) {
+        const std::vector<F2Bilinear::Pair> &row = form.rows()[x];
+        const bool one = (constant >> x) & 1u;
+        if (row.empty()) {
+            out.push_back(one ? ones(a.plane(0)) : zeros(a));
+            continue;
+        }
+        std::vector<uint64_t> li, ri;
+        li.reserve(count * row.size());
+        ri.reserve(count * row.size());
+        for (uint64_t e = 0; e < count; ++e)
+            for (size_t i = 0; i < row.size(); ++i) {
+                li.push_back(row[i].first * count + e);
+                ri.push_back(row[i].second * count + e);
+            }
+        const CiphertextBatch sum = (all_a.gather(li) * all_b.gather(ri)).sumGroups(row.size());
+        out.push_back(one ? sum + ones(a.plane(0)) : sum);
+    }
+    return UIntBatch::fromPlanes(out);
+}
+
+UIntBatch clmul(const UIntBatch &a, const UIntBatch &b)
+{
+    return bilinearMap(a, b, F2Bilinear::clmul(requireOneWidth(a, b, "clmul")));
+}
+
+UIntBatch clmulWide(const UIntBatch &a, const UIntBatch &b)
+{
+    return bilinearMap(a, b, F2Bilinear::clmulWide(requireOneWidth(a, b, "clmulWide")));
+}
+
+UIntBatch gfMul(const UIntBatch &a, const UIntBatch &b, uint64_t poly)
+{
+    return bilinearMap(a, b, F2Bilinear::gfMul(requireOneWidth(a, b, "gfMul"), poly));
+}
+
+CiphertextBatch dotBits(const UIntBatch &a, const UIntBatch &b)
+{
+    return bilinearMap(a, b, F2Bilinear::dotBits(requireOneWidth(a, b, "dotBits"))).plane(0);
+}
+
+const char *bilinearRoute(const UIntBatch &a, const UIntBatch &b, const F2Bilinear &form, uint64_t constant)
+{
+    requireBilinear(a, b, form, constant, "bilinearRoute");
+    if (a.size() == 0)
+        return "none";
+    return Planes(a).uniform && Planes(b).uniform ? "k_uint_bilinear" : "loop";
 }
 
 // ------------------------------------------------------------------ ranges, sets, step functions (csgn_uint_plain_sum)

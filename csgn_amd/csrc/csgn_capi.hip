@@ -2308,6 +2308,165 @@ int csgn_uint_plain_sum(const csgn_uint_plain_sum_plan *plan, uint64_t n_bits, u
     return CSGN_OK;
 }
 
+/* ------------------------------------------------ a public bilinear form of two encrypted integers ---- */
+
+uint64_t csgn_uint_bilinear_terms(uint64_t wa, const uint64_t *h_ta, uint64_t wb, const uint64_t *h_tb, uint64_t n_entries,
+                                  const uint64_t *h_left, const uint64_t *h_right, int constant_bit)
+{
+    return csgn::uint_bilinear_terms(wa, (const u64 *)h_ta, wb, (const u64 *)h_tb, n_entries, (const u64 *)h_left,
+                                     (const u64 *)h_right, constant_bit);
+}
+
+int csgn_uint_bilinear_decode(uint64_t wa, const uint64_t *h_ta, uint64_t wb, const uint64_t *h_tb, uint64_t n_entries,
+                              const uint64_t *h_left, const uint64_t *h_right, int constant_bit, uint64_t q,
+                              uint64_t *h_entry, uint64_t *h_left_term, uint64_t *h_right_term)
+{
+    return csgn::uint_bilinear_decode(wa, (const u64 *)h_ta, wb, (const u64 *)h_tb, n_entries, (const u64 *)h_left,
+                                      (const u64 *)h_right, constant_bit, q, (u64 *)h_entry, (u64 *)h_left_term,
+                                      (u64 *)h_right_term) ? 1 : 0;
+}
+
+namespace {
+
+/* what csgn_uint_bilinear_launches and csgn_uint_bilinear_create check before the device, in the documented order */
+int check_bilinear(uint64_t wa, const uint64_t *h_ta, uint64_t wb, const uint64_t *h_tb, uint64_t n_out,
+                   const uint64_t *h_first, const uint64_t *h_left, const uint64_t *h_right, uint64_t constant,
+                   csgn::BilinearPlan &pl)
+{
+    REQUIRE(wa >= 1 && wa <= 64, "bilinear: wa %llu outside 1..64", (unsigned long long)wa);
+    REQUIRE(wb >= 1 && wb <= 64, "bilinear: wb %llu outside 1..64", (unsigned long long)wb);
+    if (int rc = check_width(n_out, constant))
+        return rc;
+    REQUIRE(h_ta && h_tb && h_first, "null host pointer");
+    REQUIRE(h_first[0] == 0, "bilinear: h_first[0] is %llu, not 0", (unsigned long long)h_first[0]);
+    for (uint64_t x = 0; x < n_out; ++x)
+        REQUIRE(h_first[x] <= h_first[x + 1], "bilinear: h_first descends at plane %llu", (unsigned long long)x);
+    REQUIRE(h_first[n_out] == 0 || (h_left && h_right), "null host pointer");
+    if (h_first[n_out] > csgn::kBilinearMaxEntries)
+        return fail(CSGN_ERR_UNSUPPORTED, "bilinear: %llu entries (at most 262144 a plan)",
+                    (unsigned long long)h_first[n_out]);
+    for (uint64_t i = 0; i < wa; ++i)
+        REQUIRE(h_ta[i] != 0 && h_ta[i] < (1ull << 62), "bilinear: plane %llu of a has no terms or 2^62 or more",
+                (unsigned long long)i);
+    for (uint64_t l = 0; l < wb; ++l)
+        REQUIRE(h_tb[l] != 0 && h_tb[l] < (1ull << 62), "bilinear: plane %llu of b has no terms or 2^62 or more",
+                (unsigned long long)l);
+    for (uint64_t i = 0; i < h_first[n_out]; ++i)
+        REQUIRE(h_left[i] < wa && h_right[i] < wb, "bilinear: entry %llu names plane (%llu, %llu) of (%llu, %llu)",
+                (unsigned long long)i, (unsigned long long)h_left[i], (unsigned long long)h_right[i],
+                (unsigned long long)wa, (unsigned long long)wb);
+    const int rc = csgn::uint_bilinear_shape(wa, (const u64 *)h_ta, wb, (const u64 *)h_tb, n_out, (const u64 *)h_first,
+                                             (const u64 *)h_left, (const u64 *)h_right, constant, pl);
+    if (rc == CSGN_ERR_INVALID)
+        return fail(rc, "bilinear: the term count of an entry or of a plane overflows");
+    if (rc != CSGN_OK)
+        return fail(rc, "bilinear: a plane of 2^31 terms per element or more");
+    return CSGN_OK;
+}
+
+/* the sizes of a call: every input and output plane below 2^31 words per element and 2^60 per batch */
+int check_bilinear_sizes(const csgn::BilinearPlan &p, uint64_t n_bits, uint64_t batch)
+{
+    const uint64_t dl = csgn_default_len(n_bits);
+    for (u32 i = 0; i < p.wa; ++i)
+        if (int rc = check_size(batch, p.ta[i], p.ta[i], dl, "bilinear: plane %u of a", i))
+            return rc;
+    for (u32 l = 0; l < p.wb; ++l)
+        if (int rc = check_size(batch, p.tb[l], p.tb[l], dl, "bilinear: plane %u of b", l))
+            return rc;
+    for (u32 x = 0; x < p.n_out; ++x)
+        if (int rc = check_size(batch, p.T[x], p.T[x], dl, "bilinear: output %u", x))
+            return rc;
+    return CSGN_OK;
+}
+
+} // namespace
+
+struct csgn_uint_bilinear_plan {
+    csgn::BilinearPlan plan;
+};
+
+int csgn_uint_bilinear_launches(uint64_t n_bits, uint64_t batch, uint64_t wa, const uint64_t *h_ta, uint64_t wb,
+                                const uint64_t *h_tb, uint64_t n_out, const uint64_t *h_first, const uint64_t *h_left,
+                                const uint64_t *h_right, uint64_t constant, uint64_t *h_plan)
+{
+    if (int rc = check_n(n_bits))
+        return rc;
+    csgn::BilinearPlan pl;
+    if (int rc = check_bilinear(wa, h_ta, wb, h_tb, n_out, h_first, h_left, h_right, constant, pl))
+        return rc;
+    REQUIRE(h_plan, "null host pointer");
+    if (int rc = check_bilinear_sizes(pl, n_bits, batch))
+        return rc;
+    csgn::uint_bilinear_launches(pl, n_bits, batch, (u64 *)h_plan);
+    return CSGN_OK;
+}
+
+int csgn_uint_bilinear_create(uint64_t wa, const uint64_t *h_ta, uint64_t wb, const uint64_t *h_tb, uint64_t n_out,
+                              const uint64_t *h_first, const uint64_t *h_left, const uint64_t *h_right, uint64_t constant,
+                              csgn_uint_bilinear_plan **plan)
+{
+    REQUIRE(plan, "plan is null");
+    *plan = nullptr;
+    csgn_uint_bilinear_plan *p = new csgn_uint_bilinear_plan();
+    int rc = check_bilinear(wa, h_ta, wb, h_tb, n_out, h_first, h_left, h_right, constant, p->plan);
+    if (rc == CSGN_OK)
+        rc = require_device("csgn_uint_bilinear_create");
+    if (rc == CSGN_OK) {
+        hipError_t e = hipSuccess;
+        if (csgn::uint_bilinear_create(p->plan, e) != CSGN_OK)
+            rc = hip_fail(e, "csgn_uint_bilinear_create");
+    }
+    if (rc != CSGN_OK) {
+        delete p;
+        return rc;
+    }
+    *plan = p;
+    return CSGN_OK;
+}
+
+uint64_t csgn_uint_bilinear_plan_terms(const csgn_uint_bilinear_plan *plan, uint64_t x)
+{
+    return plan && x < plan->plan.n_out ? plan->plan.T[x] : 0;
+}
+
+void csgn_uint_bilinear_destroy(csgn_uint_bilinear_plan *plan)
+{
+    if (!plan)
+        return;
+    csgn::uint_bilinear_free(plan->plan);
+    delete plan;
+}
+
+int csgn_uint_bilinear(const csgn_uint_bilinear_plan *plan, uint64_t n_bits, uint64_t batch, const uint64_t *const *h_a,
+                       const uint64_t *const *h_b, uint64_t *const *h_out, void *stream)
+{
+    if (int rc = check_n(n_bits))
+        return rc;
+    REQUIRE(h_a && h_b && h_out, "null host pointer");
+    if (!plan) {                      /* no plan exists without a device: say so before calling the pointer null */
+        if (int rc = require_device("csgn_uint_bilinear"))
+            return rc;
+        return fail(CSGN_ERR_INVALID, "plan is null");
+    }
+    const csgn::BilinearPlan &p = plan->plan;
+    if (int rc = check_bilinear_sizes(p, n_bits, batch))
+        return rc;
+    if (int rc = check_planes(h_a, nullptr, p.wa, "plane of a"))
+        return rc;
+    if (int rc = check_planes(h_b, nullptr, p.wb, "plane of b"))
+        return rc;
+    if (int rc = check_planes((const uint64_t *const *)h_out, nullptr, p.n_out, "output"))
+        return rc;
+    if (int rc = require_device("csgn_uint_bilinear"))
+        return rc;
+    if (batch == 0)
+        return CSGN_OK;
+    HIP_TRY(csgn::uint_bilinear(p, n_bits, batch, (const u64 *const *)h_a, (const u64 *const *)h_b, (u64 *const *)h_out,
+                                S(stream)));
+    return CSGN_OK;
+}
+
 /* ------------------------------------------------ one-bit batches decrypted into one word per element ---- */
 
 const char *csgn_uint_decrypt_kernel(uint64_t n_bits, uint64_t batch, uint64_t n_planes, const uint64_t *h_terms)

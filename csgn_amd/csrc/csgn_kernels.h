@@ -377,6 +377,44 @@ void uint_plain_sum_plan(const PlainSumPlan &pl, u64 n_bits, u64 batch, u64 *pla
 hipError_t uint_plain_sum(const PlainSumPlan &pl, u64 n_bits, u64 batch, const u64 *const *planes, u64 *const *out,
                           hipStream_t stream);
 
+// a public bilinear form over F2 of two encrypted integers (csgn_uint_bilinear.hip), include/csgn_hip.h's definition:
+// output plane x is the left-nested sum of the products a_left[i] * b_right[i] of its entries, first[x] <= i <
+// first[x + 1], then ONE where bit x of `constant` is set; a plane of no entry is the one-term constant.  A plan holds
+// the shape and, on the device, the plane tables and every entry's first term and pair; it lives in a
+// csgn_uint_bilinear_plan object of the caller's.
+constexpr u32 kBilinearMaxPlanes = 64;
+constexpr u64 kBilinearMaxEntries = 262144;
+struct BilinearPlan {
+    u32 wa = 0, wb = 0, n_out = 0;
+    bool eq = false;                    // every ta equal, every tb equal, ta * tb below 2^31: the entry by division
+    u64 constant = 0;
+    u64 ta[kBilinearMaxPlanes] = {}, tb[kBilinearMaxPlanes] = {};   // terms per element of the input planes
+    u64 T[kBilinearMaxPlanes] = {};     // terms per element of output plane x
+    u32 efirst[kBilinearMaxPlanes + 1] = {};
+    std::vector<u32> start, lr;         // per entry: its first term in its plane; left | right << 8
+    void *d_tab = nullptr;
+};
+// T of one plane; 0: a width outside 1..64, a null array, a plane of 0 terms, an index at or past its width, a
+// constant_bit other than 0 / 1 or 2^62 terms or more
+u64 uint_bilinear_terms(u64 wa, const u64 *ta, u64 wb, const u64 *tb, u64 n_entries, const u64 *left, const u64 *right,
+                        int constant_bit);
+// the entry and the (left, right) terms of term q of one plane (entry n_entries: ONE, n_entries + 1: ZERO); false:
+// refused, q past the plane, more than kBilinearMaxEntries entries or a plane of 2^31 terms or more
+bool uint_bilinear_decode(u64 wa, const u64 *ta, u64 wb, const u64 *tb, u64 n_entries, const u64 *left, const u64 *right,
+                          int constant_bit, u64 q, u64 *entry, u64 *left_term, u64 *right_term);
+// the shape of a plan (host only): CSGN_ERR_INVALID, else CSGN_ERR_UNSUPPORTED past kBilinearMaxEntries entries or for
+// a plane of 2^31 terms or more
+int uint_bilinear_shape(u64 wa, const u64 *ta, u64 wb, const u64 *tb, u64 n_out, const u64 *first, const u64 *left,
+                        const u64 *right, u64 constant, BilinearPlan &pl);
+int uint_bilinear_create(BilinearPlan &pl, hipError_t &herr);   // uploads the tables (synchronous); CSGN_ERR_HIP
+void uint_bilinear_free(BilinearPlan &pl);
+// plan[12]: unit bytes for 16-byte-aligned pointers, units per element, G, tiles, workgroups per tile, launches under
+// the calling thread's launch_blocks, workgroups of the first launch, plane groups, staged, units a workgroup walks,
+// operand units per element, the LDS budget in bytes
+void uint_bilinear_launches(const BilinearPlan &pl, u64 n_bits, u64 batch, u64 *plan);
+hipError_t uint_bilinear(const BilinearPlan &pl, u64 n_bits, u64 batch, const u64 *const *a, const u64 *const *b,
+                         u64 *const *out, hipStream_t stream);
+
 // an encrypted integer shifted, rotated or indexed by an encrypted amount (csgn_uint_pick.hip), include/csgn_hip.h's
 // definition: output j is the sum, ascending in r < rows_j, of EQ(index, r) * a_{src(j, r)}; op = CSGN_UINT_PICK_*.
 // index planes: v = 1..16, terms s[k]; source planes: w = 1..64, every one of t terms; rows: EACH's n, else 0.

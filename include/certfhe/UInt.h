@@ -147,6 +147,24 @@
 // is allocated or launched: std::invalid_argument for a.width() != m.inWidth(), a constant of outWidth() bits or more,
 // or an output past 2^31 words per element.  An empty batch gives empty planes.  parity(a, mask) is the one-row map.
 //
+// PUBLIC BILINEAR FORMS OVER F2 OF TWO ENCRYPTED INTEGERS.  bilinearMap(a, b, form, constant) evaluates the public form
+// (class F2Bilinear: per output plane the list of pairs (i, l) whose products a_i * b_l are summed) on every element and
+// XORs the public constant: clmul(a, b), the step of GHASH / POLYVAL and of every polynomial MAC; gfMul(a, b, poly), the
+// product in GF(2^w) (AES's inversion as x^254, Reed-Solomon, Shamir shares over GF(256)); a secret bit matrix applied
+// to a secret vector; dotBits(a, b) = parity(a & b).  No carry exists: csgn_uint_bilinear's words (include/csgn_hip.h),
+//     plane j = ((a_i1 * b_l1 + a_i2 * b_l2) + ...) + a_im * b_lm [+ ONE where constant_j = 1]
+// the pairs of row j ascending by (i, l), so over fresh planes a row of m pairs has m (+ 1) terms.  What is PUBLIC
+// cancels before anything runs: F2Bilinear keeps every row sorted with nothing twice, F2Matrix * F2Bilinear applies a
+// linear map after the form and F2Bilinear::compose applies linear maps to its arguments, so gfMul(w, poly) IS the
+// reduction matrix times clmulWide(w).  Squaring in GF(2^w) is LINEAR (F2Matrix::gfSquare, through linearMap): an
+// inversion chain multiplies only where it must.  A row of no pair is the constant batch (ZERO, or ONE under a constant
+// bit).  Uniform planes take ONE plan, cached for the process like the csgn_uint_plain_sum plans, and ONE
+// csgn_uint_bilinear for all planes (k_uint_bilinear); a ragged plane (a compact() result) takes the loop:
+// two concat, then per output plane two gather, ONE operator* and sumGroups, with the same words.  bilinearRoute names the
+// route.  Every size is computed before anything is allocated or launched: std::invalid_argument for widths that are
+// not the form's, operands of different counts or contexts, a constant of outWidth() bits or more, or an output past
+// 2^31 words per element.  An empty batch gives empty planes.
+//
 // RANGES, SETS AND STEP FUNCTIONS OF PUBLIC CONSTANTS.  Over F2 they are sums (operator+, concatenation) of the
 // comparisons above of ONE integer, plus at most one ONE: csgn_uint_plain_sum's words (include/csgn_hip.h).  With
 // P(cmp, k) the words of the comparison of a with the public k (lessThan(a, k) is P(LT, k), ...), top = 2^w - 1:
@@ -516,6 +534,7 @@ class F2Matrix {
     // x * k in GF(2^w) = F2[X] / poly, k < 2^w; poly holds the terms below X^w, and may hold X^w itself where it fits
     // (0x11B and 0x1B both name AES's field at w = 8)
     static F2Matrix gfMul(unsigned w, uint64_t k, uint64_t poly);
+    static F2Matrix gfSquare(unsigned w, uint64_t poly);    // x * x in the same field: squaring is linear over F2
     static F2Matrix grayEncode(unsigned w);                 // x ^ (x >> 1)
     static F2Matrix grayDecode(unsigned w);                 // its inverse: bit j = the XOR of bits j .. w - 1
 
@@ -538,6 +557,56 @@ CiphertextBatch parity(const UIntBatch &a, uint64_t mask);
 // left to compute or the batch is empty, which launch nothing).  No device work; for diagnostics and tests, like
 // arithRoute: the words are the same.
 const char *linearRoute(const UIntBatch &a, const F2Matrix &m, uint64_t constant = 0);
+
+// A public bilinear form over F2 of two integers (the block "PUBLIC BILINEAR FORMS OVER F2" above): outWidth() rows, row
+// j the list of the pairs (i, l) -- bit i of x below leftWidth(), bit l of y below rightWidth() -- whose products x_i y_l
+// XOR to output bit j.  Host only, no device work.  A row is kept sorted by (left, right) with nothing twice: duplicates
+// cancel over F2 here, where they are public.  Widths are 1..64; std::invalid_argument otherwise, for an index at or
+// above its width, and for operands of mismatched shapes.
+class F2Bilinear {
+  public:
+    typedef std::pair<unsigned, unsigned> Pair;             // (bit of x, bit of y)
+
+  private:
+    std::vector<std::vector<Pair> > rows_;
+    unsigned left_, right_;
+    F2Bilinear(const std::vector<std::vector<Pair> > &rows, unsigned left, unsigned right)
+        : rows_(rows), left_(left), right_(right) {}
+
+  public:
+    // any order, repetitions allowed: a pair named an even number of times is gone
+    static F2Bilinear fromPairs(const std::vector<std::vector<Pair> > &rows, unsigned left_width, unsigned right_width);
+    static F2Bilinear clmul(unsigned w);                    // the carry-less product x * y mod 2^w: the low w planes
+    static F2Bilinear clmulWide(unsigned w);                // all 2w - 1 planes of it, w <= 32
+    // x * y in GF(2^w) = F2[X] / poly; poly as in F2Matrix::gfMul
+    static F2Bilinear gfMul(unsigned w, uint64_t poly);
+    static F2Bilinear bitwiseAnd(unsigned w);               // x & y
+    static F2Bilinear dotBits(unsigned w);                  // parity(x & y): one plane
+
+    unsigned leftWidth() const { return left_; }
+    unsigned rightWidth() const { return right_; }
+    unsigned outWidth() const { return (unsigned)rows_.size(); }
+    const std::vector<std::vector<Pair> > &rows() const { return rows_; }
+    uint64_t apply(uint64_t x, uint64_t y) const;           // the clear form
+    F2Bilinear operator^(const F2Bilinear &rhs) const;      // (x, y) -> (*this)(x, y) ^ rhs(x, y); one shape
+    // the form after linear maps of its arguments: (x, y) -> (*this)(on_a(x), on_b(y))
+    F2Bilinear compose(const F2Matrix &on_a, const F2Matrix &on_b) const;
+    bool operator==(const F2Bilinear &rhs) const { return left_ == rhs.left_ && right_ == rhs.right_ && rows_ == rhs.rows_; }
+};
+// the linear map after the form: (x, y) -> m(form(x, y)); m.inWidth() == form.outWidth().  gfMul(w, poly) IS the
+// reduction matrix times clmulWide(w) for w <= 32.
+F2Bilinear operator*(const F2Matrix &m, const F2Bilinear &form);
+
+// element i: form(a[i], b[i]) ^ constant, of width form.outWidth(); a.width() == form.leftWidth(), b.width() ==
+// form.rightWidth(), constant < 2^outWidth().  a and b may be the same integer.
+UIntBatch bilinearMap(const UIntBatch &a, const UIntBatch &b, const F2Bilinear &form, uint64_t constant = 0);
+UIntBatch clmul(const UIntBatch &a, const UIntBatch &b);        // one width w; w planes
+UIntBatch clmulWide(const UIntBatch &a, const UIntBatch &b);    // one width w <= 32; 2w - 1 planes
+UIntBatch gfMul(const UIntBatch &a, const UIntBatch &b, uint64_t poly);
+CiphertextBatch dotBits(const UIntBatch &a, const UIntBatch &b);   // parity(a[i] & b[i]), one encrypted bit
+// The route bilinearMap takes (a static string): "k_uint_bilinear" (one csgn_uint_bilinear for all planes), "loop" (the
+// CiphertextBatch operators plane by plane: a ragged plane) or "none" (an empty batch: nothing is launched).  No device work.
+const char *bilinearRoute(const UIntBatch &a, const UIntBatch &b, const F2Bilinear &form, uint64_t constant = 0);
 
 // element i: lo <= a[i] <= hi, one encrypted bit / its negation; lo <= hi < 2^width
 CiphertextBatch inRange(const UIntBatch &a, uint64_t lo, uint64_t hi);

@@ -1328,6 +1328,102 @@ void csgn_uint_plain_sum_destroy(csgn_uint_plain_sum_plan *plan);
 int csgn_uint_plain_sum(const csgn_uint_plain_sum_plan *plan, uint64_t n_bits, uint64_t batch,
                         const uint64_t *const *h_planes, uint64_t *const *h_out, void *stream);
 
+/* ------------------------------------- a public bilinear form of two encrypted integers ---- */
+
+/* csgn_uint_bilinear: a PUBLIC bilinear form over F2 of TWO ENCRYPTED integers, every output plane in one launch: what
+ * certfhe/UInt.h's bilinearMap, clmul, clmulWide, gfMul and dotBits compute -- the carry-less product of GHASH /
+ * POLYVAL and of every polynomial MAC, the product in GF(2^w) (AES's inversion, Reed-Solomon, Shamir shares over
+ * GF(256)), a secret bit matrix applied to a secret vector, parity(a & b).  No carry exists: an output bit is a sum
+ * over F2 of products of one bit of a and one bit of b.
+ * Inputs:
+ *   - wa uniform planes a_0 ... a_{wa-1} (wa in 1..64, bit 0 first), plane i of h_ta[i] = ta_i >= 1 terms per element,
+ *     and wb planes b_0 ... b_{wb-1} (wb in 1..64) of h_tb[l] = tb_l >= 1;
+ *   - n_out output planes (1..64).  The entries of plane x are h_first[x] .. h_first[x+1] - 1 (h_first[0] = 0, h_first
+ *     non-descending, n_out + 1 values) of the parallel host arrays h_left[] (each below wa) and h_right[] (each below
+ *     wb);
+ *   - `constant`, whose bit x adds ONE to plane x (a bit at or above n_out: CSGN_ERR_INVALID).
+ * Output plane x is the left-nested sum (the reference's operator+: concatenation) of the products (the reference's
+ * operator*: every pair of terms ANDed, the left term slow) of its entries, in the order given, followed by + ONE where
+ * constant_x = 1:
+ *     plane x = ((a_l1 * b_r1 + a_l2 * b_r2) + ...) + a_lm * b_rm [+ ONE]
+ *     T_x = sum over the plane's entries of ta_left * tb_right, + constant_x
+ * A plane with no entry is the one-term constant: ZERO (zero words) for constant_x = 0, ONE for 1; T_x = 1
+ * (csgn_uint_linear's rule for an empty row).  Input pointers may alias in any way -- a and b may be the same planes,
+ * which gives squares --; no output overlaps an input or another output.  Nothing cancels on the device: an entry
+ * named twice is written twice (and cancels over F2 only at decryption); certfhe/UInt.h's F2Bilinear sorts and cancels
+ * on the host. */
+/* T of ONE plane of n_entries entries (host only).  0 for a width outside 1..64, a null array (h_left and h_right may
+ * be null when n_entries = 0), a plane of 0 terms or 2^62 or more, an entry at or above its width, a constant_bit other
+ * than 0 or 1, or a count of 2^62 or more (computed without wrap-around). */
+uint64_t csgn_uint_bilinear_terms(uint64_t wa, const uint64_t *h_ta, uint64_t wb, const uint64_t *h_tb,
+                                  uint64_t n_entries, const uint64_t *h_left, const uint64_t *h_right, int constant_bit);
+/* The decode by position (host only): term q < T of ONE plane is term *h_left_term of a_left ANDed with term
+ * *h_right_term of b_right of entry *h_entry.  *h_entry = n_entries means ONE and n_entries + 1 means ZERO (both terms
+ * 0).  It runs the two functions the kernel runs (bilinear_entry: one division where all ta are equal and all tb are
+ * equal, else the search over the entries' first terms; bilinear_split; csgn_uint_bilinear.hip).  Returns 1, or 0
+ * (nothing written) for arguments csgn_uint_bilinear_terms refuses, more than 262144 entries, a plane of 2^31 terms or
+ * more, q >= T or a null pointer. */
+int csgn_uint_bilinear_decode(uint64_t wa, const uint64_t *h_ta, uint64_t wb, const uint64_t *h_tb, uint64_t n_entries,
+                              const uint64_t *h_left, const uint64_t *h_right, int constant_bit, uint64_t q,
+                              uint64_t *h_entry, uint64_t *h_left_term, uint64_t *h_right_term);
+/* How a call of this shape is cut under the calling thread's knob "launch_blocks" (host only, no device work).  The
+ * grid is tile-major: a tile is G elements of ALL output planes, and the stream of a tile is (plane, element, term,
+ * unit) with the unit fastest, ge * h_plan[1] units for a tile of ge elements.  Workgroup b of a launch belongs to tile
+ * b / S (S = h_plan[4]) of the launch and is its workgroup s = b % S: lane l writes the positions s * chunk + l,
+ * + 256, ... below min((s + 1) * chunk, the tile's units).  Launches are cut at whole tiles only: max(1, launch_blocks
+ * / S) tiles each.
+ *     h_plan[0]   bytes of the unit one lane writes when every pointer is 16-byte aligned: 16 for an even number of
+ *                 words per term, else 8 (a call with a pointer off alignment takes 8-byte units: twice the units, the
+ *                 same rules)
+ *     h_plan[1]   units per element over all output planes
+ *     h_plan[2]   G, the elements per tile.  Staged: as many as h_plan[11] bytes hold the operand units of (h_plan[10]
+ *                 units an element); else (tile budget / units per element); at least 1, at most `batch`, and no more
+ *                 than keep a tile within 2^31 units
+ *     h_plan[3]   tiles = ceil(batch / G) (0 for batch == 0)
+ *     h_plan[4]   S, the workgroups per tile: (G * units per element / least), at least 1, where a workgroup walks at
+ *                 `least` 2048 units and, staged, 4 times the units it stages (G * h_plan[10]); summed over the plane
+ *                 groups
+ *     h_plan[5]   launches (0 for batch == 0)
+ *     h_plan[6]   workgroups of the first launch (0 for batch == 0)
+ *     h_plan[7]   plane groups: 1, unless ONE element of all planes passes 2^31 units; G is then 1 and the planes go in
+ *                 that many runs of consecutive planes, each a stream and a launch sequence of its own
+ *     h_plan[8]   1 when the shape is STAGED: every workgroup copies its tile's operand units to LDS once and reads
+ *                 them there.  A shape is staged when one element's operand units fit h_plan[11] bytes and the form
+ *                 writes at least twice the units it reads; else both operand units of a written unit are loaded from
+ *                 memory.  A function of the shape, not a knob
+ *     h_plan[9]   chunk, the units a workgroup walks: the tile's G * units per element in S even parts, rounded up
+ *                 to a multiple of 256 (of the first plane group)
+ *     h_plan[10]  operand units per element: (sum of ta + sum of tb) * units per term
+ *     h_plan[11]  the LDS budget for operand units, in bytes
+ * The same checks as csgn_uint_bilinear_create, in its order, then h_plan, then the sizes of csgn_uint_bilinear. */
+int csgn_uint_bilinear_launches(uint64_t n_bits, uint64_t batch, uint64_t wa, const uint64_t *h_ta, uint64_t wb,
+                                const uint64_t *h_tb, uint64_t n_out, const uint64_t *h_first, const uint64_t *h_left,
+                                const uint64_t *h_right, uint64_t constant, uint64_t h_plan[12]);
+/* The plan of one shape: the planes' term counts and divisors, the entry table and, per plane, the entries' first
+ * terms, uploaded once, synchronously.  Checks, in this order: `plan`; wa; wb; n_out and the constant; h_ta, h_tb and
+ * h_first, h_first[0] = 0 and non-descending, h_left and h_right where there is an entry (CSGN_ERR_INVALID); more than
+ * 262144 entries (CSGN_ERR_UNSUPPORTED); the planes' term counts, the entries' indices, the term counts of the output
+ * planes (CSGN_ERR_INVALID); an output plane of 2^31 terms per element or more (CSGN_ERR_UNSUPPORTED); the device
+ * (CSGN_ERR_NO_DEVICE, no CPU fallback).  Release with csgn_uint_bilinear_destroy (null is ignored).  A plan is
+ * immutable: any number of threads and streams may launch from it. */
+typedef struct csgn_uint_bilinear_plan csgn_uint_bilinear_plan;
+int csgn_uint_bilinear_create(uint64_t wa, const uint64_t *h_ta, uint64_t wb, const uint64_t *h_tb, uint64_t n_out,
+                              const uint64_t *h_first, const uint64_t *h_left, const uint64_t *h_right,
+                              uint64_t constant, csgn_uint_bilinear_plan **plan);
+/* T_x of plane x of the plan; 0 for a null plan or x >= n_out */
+uint64_t csgn_uint_bilinear_plan_terms(const csgn_uint_bilinear_plan *plan, uint64_t x);
+void csgn_uint_bilinear_destroy(csgn_uint_bilinear_plan *plan);
+/* The operation over `batch` elements.  h_a, h_b and h_out are HOST arrays of wa / wb / n_out device pointers: plane i
+ * of a takes batch * ta_i * dL words, plane l of b batch * tb_l * dL and output x batch * T_x * dL words.  Checks, in
+ * this order: n_bits; the host arrays; the plan (a null plan is CSGN_ERR_NO_DEVICE where there is no device -- no plan
+ * exists there -- and CSGN_ERR_INVALID otherwise); every ta_i * dL, tb_l * dL and T_x * dL below 2^31 words per element
+ * and batch times that below 2^60 (CSGN_ERR_UNSUPPORTED); null device pointers, a, then b, then the outputs
+ * (CSGN_ERR_INVALID); the device (CSGN_ERR_NO_DEVICE, no CPU fallback).  batch == 0 succeeds.  On the caller's stream,
+ * asynchronous and graph-capturable: k_uint_bilinear, one launch for every shape
+ * csgn_uint_bilinear_launches gives one; no scratch, no allocation, no synchronisation. */
+int csgn_uint_bilinear(const csgn_uint_bilinear_plan *plan, uint64_t n_bits, uint64_t batch,
+                       const uint64_t *const *h_a, const uint64_t *const *h_b, uint64_t *const *h_out, void *stream);
+
 /* ------------------------------------- one-bit batches decrypted into one word per element ---- */
 
 /* n_planes one-bit batches of `batch` elements decrypted in ONE pass into one 64-bit word per element: what
