@@ -10,7 +10,7 @@ CXX     ?= g++
 CSRC    := csgn_amd/csrc
 LIBDIR  := csgn_amd/lib
 HIP_SRC := $(addprefix $(CSRC)/,csgn_capi.hip csgn_circuit.hip csgn_mul.hip csgn_add.hip csgn_smallops.hip csgn_decrypt.hip csgn_encrypt.hip \
-                                csgn_permute.hip csgn_compact.hip csgn_harness.hip csgn_bitlen.hip csgn_gates.hip csgn_uint.hip csgn_uint_plain.hip csgn_uint_addk.hip csgn_uint_lut.hip csgn_uint_read.hip csgn_uint_find.hip csgn_uint_first.hip csgn_uint_nth.hip csgn_uint_lt_select.hip csgn_uint_pick.hip csgn_uint_pick_rows.hip csgn_uint_write.hip csgn_uint_arith.hip csgn_uint_bitwise.hip csgn_uint_decrypt.hip csgn_matmul.hip csgn_count.hip csgn_count_prefix.hip csgn_uint_add_where.hip csgn_uint_linear.hip csgn_uint_plain_sum.hip csgn_uint_bilinear.hip csgn_wsum.hip csgn_gather.hip \
+                                csgn_permute.hip csgn_compact.hip csgn_harness.hip csgn_bitlen.hip csgn_gates.hip csgn_uint.hip csgn_uint_plain.hip csgn_uint_addk.hip csgn_uint_lut.hip csgn_uint_read.hip csgn_uint_find.hip csgn_uint_first.hip csgn_uint_nth.hip csgn_uint_lt_select.hip csgn_uint_pick.hip csgn_uint_pick_rows.hip csgn_uint_write.hip csgn_uint_arith.hip csgn_uint_bitwise.hip csgn_uint_decrypt.hip csgn_matmul.hip csgn_count.hip csgn_count_prefix.hip csgn_uint_add_where.hip csgn_uint_linear.hip csgn_uint_plain_sum.hip csgn_uint_bilinear.hip csgn_uint_poly.hip csgn_wsum.hip csgn_gather.hip \
                                 csgn_tuning.cpp csgn_scratch.cpp)
 OBJDIR  := $(LIBDIR)/obj
 HIP_OBJ := $(patsubst $(CSRC)/%,$(OBJDIR)/%.o,$(basename $(HIP_SRC)))

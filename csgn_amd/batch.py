@@ -789,6 +789,72 @@ class HipPath:
             self.lib.csgn_uint_bilinear_destroy(handle)
         return outs
 
+    @staticmethod
+    def _poly_arrays(terms, planes_monomials):
+        """Host arrays of a csgn_uint_poly shape: planes_monomials[x] is the list of monomials of output plane x, each
+        a sequence of input plane indices."""
+        mons = [m for plane in planes_monomials for m in plane]
+        first = [0]
+        for plane in planes_monomials:
+            first.append(first[-1] + len(plane))
+        mfirst = [0]
+        for m in mons:
+            mfirst.append(mfirst[-1] + len(m))
+        factors = [int(f) for m in mons for f in m]
+        h_terms = (C.c_uint64 * max(len(terms), 1))(*[int(t) for t in terms])
+        h_first = (C.c_uint64 * len(first))(*first)
+        h_mfirst = (C.c_uint64 * len(mfirst))(*mfirst)
+        h_factor = (C.c_uint64 * max(len(factors), 1))(*factors)
+        return h_terms, h_first, h_mfirst, h_factor
+
+    def uint_poly_launches(self, n_bits: int, batch: int, terms, planes_monomials, constant: int = 0):
+        """csgn_uint_poly_launches: [unit bytes, units per element, G, tiles, workgroups per tile, launches, workgroups
+        of the first launch, plane groups, staged, units a workgroup walks, operand units per element, the LDS budget in
+        bytes, the monomial by division, the factor terms' mode] of a csgn_uint_poly call of this shape under the
+        calling thread's knobs."""
+        h_terms, h_first, h_mfirst, h_factor = self._poly_arrays(terms, planes_monomials)
+        plan = (C.c_uint64 * 14)()
+        check(self.lib.csgn_uint_poly_launches(n_bits, batch, len(terms), h_terms, len(planes_monomials), h_first, h_mfirst,
+                                               h_factor, int(constant), plan))
+        return [int(x) for x in plan]
+
+    def uint_poly_create(self, terms, planes_monomials, constant: int = 0) -> int:
+        """csgn_uint_poly_create: the plan of the output planes planes_monomials[x] = [(f1, f2, ...), ...] over input
+        planes of terms[i] terms per element, plus ONE in the planes whose bit of `constant` is set.  Returns the handle;
+        release it with self.lib.csgn_uint_poly_destroy."""
+        h_terms, h_first, h_mfirst, h_factor = self._poly_arrays(terms, planes_monomials)
+        handle = C.c_void_p()
+        check(self.lib.csgn_uint_poly_create(len(terms), h_terms, len(planes_monomials), h_first, h_mfirst, h_factor,
+                                             int(constant), C.byref(handle)))
+        return handle.value
+
+    def uint_poly_apply(self, handle: int, n_bits: int, batch: int, planes, n_out: int, outs=None):
+        """csgn_uint_poly of a plan over the encrypted input planes.  Returns the output planes, of
+        csgn_uint_poly_plan_terms terms per element, fresh ones unless `outs` is given."""
+        dl = self.default_len(n_bits)
+        T = [int(self.lib.csgn_uint_poly_plan_terms(handle, x)) for x in range(n_out)]
+        assert all(T), "not a plane of the plan"
+        sizes = [batch * t * dl for t in T]
+        if outs is None:
+            outs = [self.empty_words(max(s, 1)) for s in sizes]
+        assert all(o.numel() >= s for o, s in zip(outs, sizes))
+        h_in = (C.c_void_p * len(planes))(*[_ptr(p) for p in planes])
+        h_out = (C.c_void_p * n_out)(*[_ptr(o) for o in outs])
+        check(self.lib.csgn_uint_poly(handle, n_bits, batch, h_in, h_out, self.stream))
+        return [o[:s] for o, s in zip(outs, sizes)]
+
+    def uint_poly(self, n_bits: int, batch: int, planes, terms, planes_monomials, constant: int = 0, outs=None):
+        """csgn_uint_poly with a plan of its own: output plane x is the sum over planes_monomials[x] of the products of
+        the input planes each monomial names, plus ONE where bit x of `constant` is set."""
+        assert len(planes) == len(terms)
+        handle = self.uint_poly_create(terms, planes_monomials, constant)
+        try:
+            outs = self.uint_poly_apply(handle, n_bits, batch, planes, len(planes_monomials), outs)
+            torch.cuda.current_stream(self.device).synchronize()
+        finally:
+            self.lib.csgn_uint_poly_destroy(handle)
+        return outs
+
     def uint_bitwise(self, n_bits: int, op: int, batch: int, a, a_terms, b=None, b_terms=None, sel=None, sel_terms: int = 0,
                      outs=None):
         """csgn_uint_bitwise: op = 1 a & b, 2 a | b, 3 a ^ b, 4 ~a, 5 sel ? a : b, 6 sel ? a : 0 of the encrypted

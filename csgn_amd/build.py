@@ -25,7 +25,7 @@ CERTFHE_SHARD_LIB = os.path.join(LIBDIR, "libcertFHE_shard.so")
 
 HIP_SOURCES = ["csgn_capi.hip", "csgn_circuit.hip", "csgn_mul.hip", "csgn_add.hip", "csgn_smallops.hip", "csgn_decrypt.hip", "csgn_encrypt.hip",
                "csgn_permute.hip", "csgn_compact.hip", "csgn_harness.hip", "csgn_bitlen.hip", "csgn_gates.hip", "csgn_uint.hip", "csgn_uint_plain.hip",
-               "csgn_uint_addk.hip", "csgn_uint_lut.hip", "csgn_uint_read.hip", "csgn_uint_find.hip", "csgn_uint_first.hip", "csgn_uint_nth.hip", "csgn_uint_lt_select.hip", "csgn_uint_pick.hip", "csgn_uint_pick_rows.hip", "csgn_uint_write.hip", "csgn_uint_arith.hip", "csgn_uint_bitwise.hip", "csgn_uint_decrypt.hip", "csgn_matmul.hip", "csgn_count.hip", "csgn_count_prefix.hip", "csgn_uint_add_where.hip", "csgn_uint_linear.hip", "csgn_uint_plain_sum.hip", "csgn_uint_bilinear.hip", "csgn_wsum.hip", "csgn_gather.hip",
+               "csgn_uint_addk.hip", "csgn_uint_lut.hip", "csgn_uint_read.hip", "csgn_uint_find.hip", "csgn_uint_first.hip", "csgn_uint_nth.hip", "csgn_uint_lt_select.hip", "csgn_uint_pick.hip", "csgn_uint_pick_rows.hip", "csgn_uint_write.hip", "csgn_uint_arith.hip", "csgn_uint_bitwise.hip", "csgn_uint_decrypt.hip", "csgn_matmul.hip", "csgn_count.hip", "csgn_count_prefix.hip", "csgn_uint_add_where.hip", "csgn_uint_linear.hip", "csgn_uint_plain_sum.hip", "csgn_uint_bilinear.hip", "csgn_uint_poly.hip", "csgn_wsum.hip", "csgn_gather.hip",
                "csgn_tuning.cpp", "csgn_scratch.cpp"]
 HIP_HEADERS = ["csgn_common.h", "csgn_kernels.h", "csgn_device.h", "csgn_selector.h", "csgn_chain.h", "csgn_tuning.h", "csgn_capi_util.h"]
 OBJDIR = os.path.join(LIBDIR, "obj")

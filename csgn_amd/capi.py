@@ -225,6 +225,16 @@ SIGNATURES = {
     "csgn_uint_bilinear_plan_terms": (u64, [vp, u64]),
     "csgn_uint_bilinear_destroy": (None, [vp]),
     "csgn_uint_bilinear": (C.c_int, [vp, u64, u64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp]),
+    "csgn_uint_poly_terms": (u64, [u64, C.POINTER(u64), u64, C.POINTER(u64), C.POINTER(u64), C.c_int]),
+    "csgn_uint_poly_decode": (C.c_int, [u64, C.POINTER(u64), u64, C.POINTER(u64), C.POINTER(u64), C.c_int, u64,
+                                        C.POINTER(u64), C.POINTER(u64)]),
+    "csgn_uint_poly_launches": (C.c_int, [u64, u64, u64, C.POINTER(u64), u64, C.POINTER(u64), C.POINTER(u64),
+                                          C.POINTER(u64), u64, C.POINTER(u64)]),
+    "csgn_uint_poly_create": (C.c_int, [u64, C.POINTER(u64), u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), u64,
+                                        C.POINTER(vp)]),
+    "csgn_uint_poly_plan_terms": (u64, [vp, u64]),
+    "csgn_uint_poly_destroy": (None, [vp]),
+    "csgn_uint_poly": (C.c_int, [vp, u64, u64, C.POINTER(vp), C.POINTER(vp), vp]),
     "csgn_uint_decrypt_kernel":(C.c_char_p, [u64, u64, u64, C.POINTER(u64)]),
     "csgn_uint_decrypt": (C.c_int, [u64, u64, u64, C.POINTER(vp), C.POINTER(u64), C.POINTER(vp), C.POINTER(u64),
                                     C.POINTER(u64), vp, vp, vp]),

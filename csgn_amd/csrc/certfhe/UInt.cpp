@@ -1664,6 +1664,595 @@ const char *bilinearRoute(const UIntBatch &a, const UIntBatch &b, const F2Biline
     return Planes(a).uniform && Planes(b).uniform ? "k_uint_bilinear" : "loop";
 }
 
+// ------------------------------------------------------------------ public polynomial maps over F2 (csgn_uint_poly)
+
+namespace {
+
+typedef F2Polynomial::Monomial PolyMonomial;
+typedef F2Polynomial::Rows PolyRows;
+
+const unsigned kPolyMaxDegree = 8, kPolyMaxVariables = 256;
+const size_t kPolyMaxMonomials = 262144;
+
+// ascending by (degree, then the variables)
+bool monomialLess(const PolyMonomial &x, const PolyMonomial &y)
+{
+    return x.size() != y.size() ? x.size() < y.size() : x < y;
+}
+
+// One row in canonical form: the variables of a monomial ascending with none twice, the monomials named an odd number
+// of times ascending; an empty monomial flips *constant.  std::invalid_argument past degree 8.
+std::vector<PolyMonomial> cancelMonomials(std::vector<PolyMonomial> monomials, bool *constant, const char *who)
+{
+    for (size_t i = 0; i < monomials.size(); ++i) {
+        PolyMonomial &m = monomials[i];
+        std::sort(m.begin(), m.end());
+        m.erase(std::unique(m.begin(), m.end()), m.end());
+        if (m.size() > kPolyMaxDegree)
+            throw std::invalid_argument(std::string("certFHE::F2Polynomial::") + who + ": a monomial of degree above 8");
+    }
+    std::sort(monomials.begin(), monomials.end(), monomialLess);
+    std::vector<PolyMonomial> kept;
+    for (size_t i = 0; i < monomials.size();) {
+        size_t j = i;
+        while (j < monomials.size() && monomials[j] == monomials[i])
+            ++j;
+        if ((j - i) & 1u) {
+            if (monomials[i].empty())
+                *constant = !*constant;
+            else
+                kept.push_back(monomials[i]);
+        }
+        i = j;
+    }
+    return kept;
+}
+
+unsigned requirePolyWidths(const std::vector<unsigned> &widths, const char *who)
+{
+    unsigned total = 0;
+    if (widths.empty())
+        throw std::invalid_argument(std::string("certFHE::F2Polynomial::") + who + ": no operand");
+    for (size_t o = 0; o < widths.size(); ++o) {
+        if (widths[o] < 1 || widths[o] > 64)
+            throw std::invalid_argument(std::string("certFHE::F2Polynomial::") + who + ": width must be 1..64");
+        total += widths[o];
+        if (total > kPolyMaxVariables)
+            throw std::invalid_argument(std::string("certFHE::F2Polynomial::") + who + ": more than 256 bits of operands");
+    }
+    return total;
+}
+
+void requirePolyCount(const PolyRows &rows, const char *who)
+{
+    size_t n = 0;
+    for (size_t j = 0; j < rows.size(); ++j)
+        n += rows[j].size();
+    if (n > kPolyMaxMonomials)
+        throw std::invalid_argument(std::string("certFHE::F2Polynomial::") + who + ": more than 262144 monomials");
+}
+
+// the rows with an empty monomial added where the constant has a bit: fromMonomials folds it back
+F2Polynomial polynomialOf(PolyRows rows, const std::vector<unsigned> &widths, uint64_t constant)
+{
+    for (size_t j = 0; j < rows.size() && j < 64; ++j)
+        if ((constant >> j) & 1u)
+            rows[j].push_back(PolyMonomial());
+    return F2Polynomial::fromMonomials(rows, widths);
+}
+
+// variable of bit i of operand o
+std::vector<unsigned> polyBases(const std::vector<unsigned> &widths)
+{
+    std::vector<unsigned> base(widths.size() + 1, 0);
+    for (size_t o = 0; o < widths.size(); ++o)
+        base[o + 1] = base[o] + widths[o];
+    return base;
+}
+
+PolyMonomial monomialOf(unsigned a)
+{
+    return PolyMonomial(1, a);
+}
+
+PolyMonomial monomialOf(unsigned a, unsigned b)
+{
+    PolyMonomial m(1, a);
+    m.push_back(b);
+    return m;
+}
+
+void requirePolyWidth(unsigned w, const char *who)
+{
+    if (w < 1 || w > 64)
+        throw std::invalid_argument(std::string("certFHE::F2Polynomial::") + who + ": width must be 1..64");
+}
+
+} // namespace
+
+F2Polynomial F2Polynomial::fromMonomials(const Rows &rows, const std::vector<unsigned> &widths)
+{
+    const char *who = "fromMonomials";
+    const unsigned variables = requirePolyWidths(widths, who);
+    if (rows.size() < 1 || rows.size() > 64)
+        throw std::invalid_argument("certFHE::F2Polynomial::fromMonomials: 1..64 rows");
+    Rows kept;
+    uint64_t constant = 0;
+    for (size_t j = 0; j < rows.size(); ++j) {
+        for (size_t i = 0; i < rows[j].size(); ++i)
+            for (size_t k = 0; k < rows[j][i].size(); ++k)
+                if (rows[j][i][k] >= variables)
+                    throw std::invalid_argument(
+                        "certFHE::F2Polynomial::fromMonomials: a monomial names a variable at or above the operands' bits");
+        bool one = false;
+        kept.push_back(cancelMonomials(rows[j], &one, who));
+        constant |= (uint64_t)one << j;
+    }
+    requirePolyCount(kept, who);
+    return F2Polynomial(kept, widths, constant);
+}
+
+F2Polynomial F2Polynomial::linear(const F2Matrix &m)
+{
+    Rows rows(m.outWidth());
+    for (unsigned j = 0; j < m.outWidth(); ++j)
+        for (unsigned i = 0; i < m.inWidth(); ++i)
+            if ((m.rows()[j] >> i) & 1u)
+                rows[j].push_back(monomialOf(i));
+    return fromMonomials(rows, std::vector<unsigned>(1, m.inWidth()));
+}
+
+F2Polynomial F2Polynomial::bilinear(const F2Bilinear &f)
+{
+    Rows rows(f.outWidth());
+    for (unsigned j = 0; j < f.outWidth(); ++j)
+        for (size_t i = 0; i < f.rows()[j].size(); ++i)
+            rows[j].push_back(monomialOf(f.rows()[j][i].first, f.leftWidth() + f.rows()[j][i].second));
+    std::vector<unsigned> widths(1, f.leftWidth());
+    widths.push_back(f.rightWidth());
+    return fromMonomials(rows, widths);
+}
+
+F2Polynomial F2Polynomial::fromLookupTable(const LookupTable &f)
+{
+    const unsigned w = f.inWidth();
+    Rows rows(f.outWidth());
+    const std::vector<uint64_t> &anf = f.anf();
+    for (uint64_t s = 0; s < anf.size(); ++s) {
+        if (anf[s] == 0)
+            continue;
+        Monomial mono;
+        for (unsigned i = 0; i < w; ++i)
+            if ((s >> i) & 1u)
+                mono.push_back(i);
+        for (unsigned j = 0; j < f.outWidth(); ++j)
+            if ((anf[s] >> j) & 1u)
+                rows[j].push_back(mono);
+    }
+    return fromMonomials(rows, std::vector<unsigned>(1, w));
+}
+
+F2Polynomial F2Polynomial::ch(unsigned w)
+{
+    requirePolyWidth(w, "ch");
+    Rows rows(w);
+    for (unsigned j = 0; j < w; ++j) {
+        rows[j].push_back(monomialOf(j, w + j));
+        rows[j].push_back(monomialOf(j, 2 * w + j));
+        rows[j].push_back(monomialOf(2 * w + j));
+    }
+    return fromMonomials(rows, std::vector<unsigned>(3, w));
+}
+
+F2Polynomial F2Polynomial::maj(unsigned w)
+{
+    requirePolyWidth(w, "maj");
+    Rows rows(w);
+    for (unsigned j = 0; j < w; ++j) {
+        rows[j].push_back(monomialOf(j, w + j));
+        rows[j].push_back(monomialOf(j, 2 * w + j));
+        rows[j].push_back(monomialOf(w + j, 2 * w + j));
+    }
+    return fromMonomials(rows, std::vector<unsigned>(3, w));
+}
+
+F2Polynomial F2Polynomial::chi(unsigned w)
+{
+    requirePolyWidth(w, "chi");
+    Rows rows(w);
+    for (unsigned j = 0; j < w; ++j) {
+        rows[j].push_back(monomialOf(j));
+        rows[j].push_back(monomialOf(2 * w + j));
+        rows[j].push_back(monomialOf(w + j, 2 * w + j));
+    }
+    return fromMonomials(rows, std::vector<unsigned>(3, w));
+}
+
+F2Polynomial F2Polynomial::andAll(unsigned w, unsigned k)
+{
+    requirePolyWidth(w, "andAll");
+    if (k < 1 || k > kPolyMaxDegree)
+        throw std::invalid_argument("certFHE::F2Polynomial::andAll: 1..8 operands");
+    Rows rows(w);
+    for (unsigned j = 0; j < w; ++j) {
+        Monomial m;
+        for (unsigned o = 0; o < k; ++o)
+            m.push_back(o * w + j);
+        rows[j].push_back(m);
+    }
+    return fromMonomials(rows, std::vector<unsigned>(k, w));
+}
+
+F2Polynomial F2Polynomial::mux(unsigned w)
+{
+    requirePolyWidth(w, "mux");
+    Rows rows(w);
+    for (unsigned j = 0; j < w; ++j) {
+        rows[j].push_back(monomialOf(0, 1 + j));
+        rows[j].push_back(monomialOf(0, 1 + w + j));
+        rows[j].push_back(monomialOf(1 + w + j));
+    }
+    std::vector<unsigned> widths(1, 1);
+    widths.push_back(w);
+    widths.push_back(w);
+    return fromMonomials(rows, widths);
+}
+
+unsigned F2Polynomial::variables() const
+{
+    unsigned total = 0;
+    for (size_t o = 0; o < widths_.size(); ++o)
+        total += widths_[o];
+    return total;
+}
+
+uint64_t F2Polynomial::apply(const std::vector<uint64_t> &operands) const
+{
+    if (operands.size() != widths_.size())
+        throw std::invalid_argument("certFHE::F2Polynomial::apply: the number of operands is not the form's");
+    std::vector<unsigned char> bit;
+    for (size_t o = 0; o < widths_.size(); ++o)
+        for (unsigned i = 0; i < widths_[o]; ++i)
+            bit.push_back((unsigned char)((operands[o] >> i) & 1u));
+    uint64_t z = 0;
+    for (size_t j = 0; j < rows_.size(); ++j) {
+        uint64_t sum = 0;
+        for (size_t i = 0; i < rows_[j].size(); ++i) {
+            uint64_t p = 1;
+            for (size_t k = 0; k < rows_[j][i].size(); ++k)
+                p &= bit[rows_[j][i][k]];
+            sum ^= p;
+        }
+        z |= sum << j;
+    }
+    return z ^ constant_;
+}
+
+F2Polynomial F2Polynomial::operator^(const F2Polynomial &rhs) const
+{
+    if (widths_ != rhs.widths_ || rows_.size() != rhs.rows_.size())
+        throw std::invalid_argument("certFHE::F2Polynomial::operator^: the forms differ in shape");
+    Rows rows(rows_);
+    for (size_t j = 0; j < rows.size(); ++j)
+        rows[j].insert(rows[j].end(), rhs.rows_[j].begin(), rhs.rows_[j].end());
+    return polynomialOf(rows, widths_, constant_ ^ rhs.constant_);
+}
+
+F2Polynomial F2Polynomial::operator&(const F2Polynomial &rhs) const
+{
+    if (widths_ != rhs.widths_ || rows_.size() != rhs.rows_.size())
+        throw std::invalid_argument("certFHE::F2Polynomial::operator&: the forms differ in shape");
+    Rows rows(rows_.size());
+    for (size_t j = 0; j < rows.size(); ++j) {
+        std::vector<Monomial> p(rows_[j]), q(rhs.rows_[j]);
+        if ((constant_ >> j) & 1u)
+            p.push_back(Monomial());
+        if ((rhs.constant_ >> j) & 1u)
+            q.push_back(Monomial());
+        if (p.size() * q.size() > 16 * kPolyMaxMonomials)
+            throw std::invalid_argument("certFHE::F2Polynomial::operator&: more than 262144 monomials");
+        for (size_t a = 0; a < p.size(); ++a)
+            for (size_t b = 0; b < q.size(); ++b) {
+                Monomial m(p[a]);
+                m.insert(m.end(), q[b].begin(), q[b].end());
+                rows[j].push_back(m);
+            }
+    }
+    return fromMonomials(rows, widths_);
+}
+
+F2Polynomial F2Polynomial::compose(const std::vector<F2Matrix> &on) const
+{
+    if (on.size() != widths_.size())
+        throw std::invalid_argument("certFHE::F2Polynomial::compose: one map per operand");
+    std::vector<unsigned> widths;
+    for (size_t o = 0; o < on.size(); ++o) {
+        if (on[o].outWidth() != widths_[o])
+            throw std::invalid_argument("certFHE::F2Polynomial::compose: a map's output width is not the operand's width");
+        widths.push_back(on[o].inWidth());
+    }
+    requirePolyWidths(widths, "compose");
+    const std::vector<unsigned> old_base = polyBases(widths_), new_base = polyBases(widths);
+    std::vector<std::vector<unsigned> > image(variables());   // old variable -> the new variables it is the sum of
+    for (size_t o = 0; o < on.size(); ++o)
+        for (unsigned i = 0; i < widths_[o]; ++i)
+            for (unsigned k = 0; k < on[o].inWidth(); ++k)
+                if ((on[o].rows()[i] >> k) & 1u)
+                    image[old_base[o] + i].push_back(new_base[o] + k);
+    Rows rows(rows_.size());
+    size_t total = 0;
+    for (size_t j = 0; j < rows.size(); ++j) {
+        for (size_t i = 0; i < rows_[j].size(); ++i) {
+            std::vector<Monomial> acc(1, Monomial());         // the product of the factors' sums, expanded
+            for (size_t k = 0; k < rows_[j][i].size(); ++k) {
+                const std::vector<unsigned> &sum = image[rows_[j][i][k]];
+                if (acc.size() * sum.size() > 16 * kPolyMaxMonomials)
+                    throw std::invalid_argument("certFHE::F2Polynomial::compose: more than 262144 monomials");
+                std::vector<Monomial> next;
+                next.reserve(acc.size() * sum.size());
+                for (size_t a = 0; a < acc.size(); ++a)
+                    for (size_t v = 0; v < sum.size(); ++v) {
+                        next.push_back(acc[a]);
+                        next.back().push_back(sum[v]);
+                    }
+                acc.swap(next);
+            }
+            rows[j].insert(rows[j].end(), acc.begin(), acc.end());
+            if (rows[j].size() > 16 * kPolyMaxMonomials) {    // cancel what has gathered before going on
+                bool one = false;
+                rows[j] = cancelMonomials(rows[j], &one, "compose");
+                if (one)
+                    rows[j].push_back(Monomial());
+                if (rows[j].size() > kPolyMaxMonomials)
+                    throw std::invalid_argument("certFHE::F2Polynomial::compose: more than 262144 monomials");
+            }
+        }
+        bool one = false;
+        rows[j] = cancelMonomials(rows[j], &one, "compose");
+        if (one)
+            rows[j].push_back(Monomial());
+        total += rows[j].size();
+        if (total > kPolyMaxMonomials)
+            throw std::invalid_argument("certFHE::F2Polynomial::compose: more than 262144 monomials");
+    }
+    return polynomialOf(rows, widths, constant_);
+}
+
+F2Polynomial operator*(const F2Matrix &m, const F2Polynomial &form)
+{
+    if (m.inWidth() != form.outWidth())
+        throw std::invalid_argument("certFHE::operator*: the map's input width is not the form's output width");
+    PolyRows rows(m.outWidth());
+    uint64_t constant = 0;
+    for (size_t j = 0; j < rows.size(); ++j)
+        for (unsigned x = 0; x < m.inWidth(); ++x)
+            if ((m.rows()[j] >> x) & 1u) {
+                rows[j].insert(rows[j].end(), form.rows()[x].begin(), form.rows()[x].end());
+                constant ^= ((form.constant() >> x) & 1u) << j;
+            }
+    return polynomialOf(rows, form.widths(), constant);
+}
+
+namespace {
+
+// device plans per (terms, rows, constant), kept until the process ends
+const csgn_uint_poly_plan *polyPlan(const std::vector<uint64_t> &terms, const std::vector<uint64_t> &first,
+                                    const std::vector<uint64_t> &mfirst, const std::vector<uint64_t> &factor,
+                                    uint64_t constant)
+{
+    static std::mutex mutex;
+    static std::map<std::vector<uint64_t>, csgn_uint_poly_plan *> *plans =
+        new std::map<std::vector<uint64_t>, csgn_uint_poly_plan *>();
+    std::vector<uint64_t> key(1, constant);
+    key.push_back(terms.size());
+    key.push_back(first.size());
+    key.insert(key.end(), terms.begin(), terms.end());
+    key.insert(key.end(), first.begin(), first.end());
+    key.insert(key.end(), mfirst.begin(), mfirst.end());
+    key.insert(key.end(), factor.begin(), factor.end());
+    std::lock_guard<std::mutex> lock(mutex);
+    auto it = plans->find(key);
+    if (it != plans->end())
+        return it->second;
+    csgn_uint_poly_plan *p = nullptr;
+    detail::check(csgn_uint_poly_create(terms.size(), terms.data(), first.size() - 1, first.data(), mfirst.data(),
+                                        factor.data(), constant, &p),
+                  "csgn_uint_poly_create");
+    (*plans)[key] = p;
+    return p;
+}
+
+// what polyMap does with row j: the constant batch, the source plane's own payload, or a computed plane
+enum { POLY_CONSTANT, POLY_SHARED, POLY_COMPUTED };
+
+int polyKind(const std::vector<PolyMonomial> &row, bool one)
+{
+    if (row.empty())
+        return POLY_CONSTANT;
+    return row.size() == 1 && row[0].size() == 1 && !one ? POLY_SHARED : POLY_COMPUTED;
+}
+
+// the constant of a call: the form's own XOR the caller's
+uint64_t requirePoly(const std::vector<UIntBatch> &operands, const F2Polynomial &f, uint64_t constant, const char *who)
+{
+    if (operands.size() != f.widths().size())
+        throw std::invalid_argument(std::string("certFHE::") + who + ": the number of operands is not the form's");
+    for (size_t o = 0; o < operands.size(); ++o) {
+        if (operands[o].width() != f.widths()[o])
+            throw std::invalid_argument(std::string("certFHE::") + who + ": an integer's width is not the form's");
+        if (operands[o].size() != operands[0].size() || !sameContext(operands[o].context(), operands[0].context()))
+            throw std::invalid_argument(std::string("certFHE::") + who + ": operands differ in count or context");
+    }
+    if (f.outWidth() < 64 && (constant >> f.outWidth()))
+        throw std::invalid_argument(std::string("certFHE::") + who + ": the constant does not fit in the form's output width");
+    return constant ^ f.constant();
+}
+
+std::vector<CiphertextBatch> polyPlanes(const std::vector<UIntBatch> &operands)
+{
+    std::vector<CiphertextBatch> planes;
+    for (size_t o = 0; o < operands.size(); ++o)
+        for (unsigned i = 0; i < operands[o].width(); ++i)
+            planes.push_back(operands[o].plane(i));
+    return planes;
+}
+
+bool polyComputes(const F2Polynomial &f, uint64_t constant)
+{
+    for (unsigned j = 0; j < f.outWidth(); ++j)
+        if (polyKind(f.rows()[j], (constant >> j) & 1u) == POLY_COMPUTED)
+            return true;
+    return false;
+}
+
+unsigned requireOneWidthOf(const std::vector<UIntBatch> &operands, const char *who)
+{
+    if (operands.empty() || operands.size() > kPolyMaxDegree)
+        throw std::invalid_argument(std::string("certFHE::") + who + ": 1..8 operands");
+    for (size_t o = 1; o < operands.size(); ++o)
+        if (operands[o].width() != operands[0].width())
+            throw std::invalid_argument(std::string("certFHE::") + who + ": operands differ in width");
+    return operands[0].width();
+}
+
+std::vector<UIntBatch> three(const UIntBatch &a, const UIntBatch &b, const UIntBatch &c)
+{
+    std::vector<UIntBatch> v(1, a);
+    v.push_back(b);
+    v.push_back(c);
+    return v;
+}
+
+} // namespace
+
+UIntBatch polyMap(const std::vector<UIntBatch> &operands, const F2Polynomial &f, uint64_t constant)
+{
+    constant = requirePoly(operands, f, constant, "polyMap");
+    const unsigned m = f.outWidth();
+    const Context &ctx = operands[0].context();
+    const uint64_t count = operands[0].size();
+    // every size first
+    const std::vector<CiphertextBatch> planes = polyPlanes(operands);
+    const Planes in(planes);
+    std::vector<uint64_t> first(1, 0), mfirst(1, 0), factor, T;
+    std::vector<unsigned> at(m, 0), computed_rows;
+    uint64_t ones_of = 0;                                 // the computed rows' constant bits
+    for (unsigned x = 0; x < m; ++x) {
+        const std::vector<PolyMonomial> &row = f.rows()[x];
+        const bool one = (constant >> x) & 1u;
+        if (polyKind(row, one) != POLY_COMPUTED)
+            continue;
+        const size_t m0 = mfirst.size() - 1;
+        for (size_t i = 0; i < row.size(); ++i) {
+            factor.insert(factor.end(), row[i].begin(), row[i].end());
+            mfirst.push_back(factor.size());
+        }
+        at[x] = (unsigned)computed_rows.size();
+        ones_of |= (uint64_t)one << computed_rows.size();
+        computed_rows.push_back(x);
+        T.push_back(checked(csgn_uint_poly_terms(in.terms.size(), in.terms.data(), row.size(), mfirst.data() + m0,
+                                                 factor.data(), one ? 1 : 0),
+                            ctx, "polyMap"));
+        first.push_back(mfirst.size() - 1);
+    }
+    if (count == 0)
+        return UIntBatch::fromPlanes(std::vector<CiphertextBatch>(m, BatchAccess::make(ctx, 0, 1)));
+    std::vector<CiphertextBatch> computed;
+    if (!computed_rows.empty() && in.uniform) {
+        const csgn_uint_poly_plan *plan = polyPlan(in.terms, first, mfirst, factor, ones_of);
+        computed = makePlanes(ctx, count, T);
+        detail::check(csgn_uint_poly(plan, ctx.getN(), count, sources(in).data(), wordsOf(computed).data(), detail::stream()),
+                      "csgn_uint_poly");
+    } else if (!computed_rows.empty()) {
+        // the loop: every operand plane in one batch (plane v's element e at v * count + e), then per output plane and
+        // per degree d present, ascending, the d named planes gathered monomial by monomial, d - 1 element-wise
+        // products and sumGroups, which copies nothing; operator+ between the degree groups, then + ONE
+        const CiphertextBatch all = CiphertextBatch::concat(planes);
+        for (size_t r = 0; r < computed_rows.size(); ++r) {
+            const std::vector<PolyMonomial> &row = f.rows()[computed_rows[r]];
+            std::vector<CiphertextBatch> sum;             // at most one: the running sum
+            for (size_t i = 0; i < row.size();) {
+                const size_t d = row[i].size();
+                size_t j = i;
+                while (j < row.size() && row[j].size() == d)
+                    ++j;
+                std::vector<CiphertextBatch> prod;        // at most one: the running product
+                for (size_t k = 0; k < d; ++k) {
+                    std::vector<uint64_t> idx;
+                    idx.reserve(count * (j - i));
+                    for (uint64_t e = 0; e < count; ++e)
+                        for (size_t q = i; q < j; ++q)
+                            idx.push_back(row[q][k] * count + e);
+                    const CiphertextBatch g = all.gather(idx);
+                    if (prod.empty())
+                        prod.push_back(g);
+                    else
+                        prod[0] = prod[0] * g;
+                }
+                const CiphertextBatch group = prod[0].sumGroups(j - i);
+                if (sum.empty())
+                    sum.push_back(group);
+                else
+                    sum[0] = sum[0] + group;
+                i = j;
+            }
+            computed.push_back((ones_of >> r) & 1u ? sum[0] + ones(planes[0]) : sum[0]);
+        }
+    }
+    std::vector<CiphertextBatch> out;
+    bool have_zero = false, have_one = false;
+    CiphertextBatch zero = planes[0], one = planes[0];    // one shared payload for every constant plane of a kind
+    for (unsigned x = 0; x < m; ++x) {
+        const bool bit = (constant >> x) & 1u;
+        switch (polyKind(f.rows()[x], bit)) {
+        case POLY_SHARED: out.push_back(planes[f.rows()[x][0][0]]); break;
+        case POLY_COMPUTED: out.push_back(computed[at[x]]); break;
+        default:
+            if (bit && !have_one) {
+                one = ones(planes[0]);
+                have_one = true;
+            } else if (!bit && !have_zero) {
+                zero = zeros(operands[0]);
+                have_zero = true;
+            }
+            out.push_back(bit ? one : zero);
+        }
+    }
+    return UIntBatch::fromPlanes(out);
+}
+
+UIntBatch ch(const UIntBatch &e, const UIntBatch &f, const UIntBatch &g)
+{
+    const std::vector<UIntBatch> ops = three(e, f, g);
+    return polyMap(ops, F2Polynomial::ch(requireOneWidthOf(ops, "ch")));
+}
+
+UIntBatch maj(const UIntBatch &a, const UIntBatch &b, const UIntBatch &c)
+{
+    const std::vector<UIntBatch> ops = three(a, b, c);
+    return polyMap(ops, F2Polynomial::maj(requireOneWidthOf(ops, "maj")));
+}
+
+UIntBatch chi(const UIntBatch &a, const UIntBatch &b, const UIntBatch &c)
+{
+    const std::vector<UIntBatch> ops = three(a, b, c);
+    return polyMap(ops, F2Polynomial::chi(requireOneWidthOf(ops, "chi")));
+}
+
+UIntBatch andAll(const std::vector<UIntBatch> &operands)
+{
+    const unsigned w = requireOneWidthOf(operands, "andAll");
+    return polyMap(operands, F2Polynomial::andAll(w, (unsigned)operands.size()));
+}
+
+const char *polyRoute(const std::vector<UIntBatch> &operands, const F2Polynomial &f, uint64_t constant)
+{
+    constant = requirePoly(operands, f, constant, "polyRoute");
+    if (operands[0].size() == 0 || !polyComputes(f, constant))
+        return "none";
+    return Planes(polyPlanes(operands)).uniform ? "k_uint_poly" : "loop";
+}
+
 // ------------------------------------------------------------------ ranges, sets, step functions (csgn_uint_plain_sum)
 
 namespace {

@@ -2467,6 +2467,156 @@ int csgn_uint_bilinear(const csgn_uint_bilinear_plan *plan, uint64_t n_bits, uin
     return CSGN_OK;
 }
 
+/* ------------------------------------------------ a public polynomial over F2 of encrypted planes ---- */
+
+uint64_t csgn_uint_poly_terms(uint64_t n_in, const uint64_t *h_terms, uint64_t n_monomials, const uint64_t *h_mfirst,
+                              const uint64_t *h_factor, int constant_bit)
+{
+    return csgn::uint_poly_terms(n_in, (const u64 *)h_terms, n_monomials, (const u64 *)h_mfirst, (const u64 *)h_factor,
+                                 constant_bit);
+}
+
+int csgn_uint_poly_decode(uint64_t n_in, const uint64_t *h_terms, uint64_t n_monomials, const uint64_t *h_mfirst,
+                          const uint64_t *h_factor, int constant_bit, uint64_t q, uint64_t *h_monomial,
+                          uint64_t *h_factor_terms)
+{
+    return csgn::uint_poly_decode(n_in, (const u64 *)h_terms, n_monomials, (const u64 *)h_mfirst, (const u64 *)h_factor,
+                                  constant_bit, q, (u64 *)h_monomial, (u64 *)h_factor_terms) ? 1 : 0;
+}
+
+namespace {
+
+/* what csgn_uint_poly_launches and csgn_uint_poly_create check before the device, in the documented order */
+int check_poly(uint64_t n_in, const uint64_t *h_terms, uint64_t n_out, const uint64_t *h_first, const uint64_t *h_mfirst,
+               const uint64_t *h_factor, uint64_t constant, csgn::PolyPlan &pl)
+{
+    REQUIRE(n_in >= 1 && n_in <= csgn::kPolyMaxIn, "poly: n_in %llu outside 1..256", (unsigned long long)n_in);
+    if (int rc = check_width(n_out, constant))
+        return rc;
+    REQUIRE(h_terms && h_first, "null host pointer");
+    REQUIRE(h_first[0] == 0, "poly: h_first[0] is %llu, not 0", (unsigned long long)h_first[0]);
+    for (uint64_t x = 0; x < n_out; ++x)
+        REQUIRE(h_first[x] <= h_first[x + 1], "poly: h_first descends at plane %llu", (unsigned long long)x);
+    const uint64_t nm = h_first[n_out];
+    REQUIRE(nm == 0 || (h_mfirst && h_factor), "null host pointer");
+    if (nm > csgn::kPolyMaxMonomials)
+        return fail(CSGN_ERR_UNSUPPORTED, "poly: %llu monomials (at most 262144 a plan)", (unsigned long long)nm);
+    for (uint64_t i = 0; i < n_in; ++i)
+        REQUIRE(h_terms[i] != 0 && h_terms[i] < (1ull << 62), "poly: input plane %llu has no terms or 2^62 or more",
+                (unsigned long long)i);
+    REQUIRE(nm == 0 || h_mfirst[0] == 0, "poly: h_mfirst[0] is not 0");
+    for (uint64_t m = 0; m < nm; ++m) {
+        REQUIRE(h_mfirst[m] < h_mfirst[m + 1] && h_mfirst[m + 1] - h_mfirst[m] <= csgn::kPolyMaxDegree,
+                "poly: monomial %llu has a degree outside 1..8", (unsigned long long)m);
+        for (uint64_t j = h_mfirst[m]; j < h_mfirst[m + 1]; ++j)
+            REQUIRE(h_factor[j] < n_in, "poly: monomial %llu names plane %llu of %llu", (unsigned long long)m,
+                    (unsigned long long)h_factor[j], (unsigned long long)n_in);
+    }
+    const int rc = csgn::uint_poly_shape(n_in, (const u64 *)h_terms, n_out, (const u64 *)h_first, (const u64 *)h_mfirst,
+                                         (const u64 *)h_factor, constant, pl);
+    if (rc == CSGN_ERR_INVALID)
+        return fail(rc, "poly: the term count of a monomial or of a plane overflows");
+    if (rc != CSGN_OK)
+        return fail(rc, "poly: a plane of 2^31 terms per element or more");
+    return CSGN_OK;
+}
+
+/* the sizes of a call: every input and output plane below 2^31 words per element and 2^60 per batch */
+int check_poly_sizes(const csgn::PolyPlan &p, uint64_t n_bits, uint64_t batch)
+{
+    const uint64_t dl = csgn_default_len(n_bits);
+    for (u32 i = 0; i < p.n_in; ++i)
+        if (int rc = check_size(batch, p.tin[i], p.tin[i], dl, "poly: input plane %u", i))
+            return rc;
+    for (u32 x = 0; x < p.n_out; ++x)
+        if (int rc = check_size(batch, p.T[x], p.T[x], dl, "poly: output %u", x))
+            return rc;
+    return CSGN_OK;
+}
+
+} // namespace
+
+struct csgn_uint_poly_plan {
+    csgn::PolyPlan plan;
+};
+
+int csgn_uint_poly_launches(uint64_t n_bits, uint64_t batch, uint64_t n_in, const uint64_t *h_terms, uint64_t n_out,
+                            const uint64_t *h_first, const uint64_t *h_mfirst, const uint64_t *h_factor, uint64_t constant,
+                            uint64_t *h_plan)
+{
+    if (int rc = check_n(n_bits))
+        return rc;
+    csgn::PolyPlan pl;
+    if (int rc = check_poly(n_in, h_terms, n_out, h_first, h_mfirst, h_factor, constant, pl))
+        return rc;
+    REQUIRE(h_plan, "null host pointer");
+    if (int rc = check_poly_sizes(pl, n_bits, batch))
+        return rc;
+    csgn::uint_poly_launches(pl, n_bits, batch, (u64 *)h_plan);
+    return CSGN_OK;
+}
+
+int csgn_uint_poly_create(uint64_t n_in, const uint64_t *h_terms, uint64_t n_out, const uint64_t *h_first,
+                          const uint64_t *h_mfirst, const uint64_t *h_factor, uint64_t constant, csgn_uint_poly_plan **plan)
+{
+    REQUIRE(plan, "plan is null");
+    *plan = nullptr;
+    csgn_uint_poly_plan *p = new csgn_uint_poly_plan();
+    int rc = check_poly(n_in, h_terms, n_out, h_first, h_mfirst, h_factor, constant, p->plan);
+    if (rc == CSGN_OK)
+        rc = require_device("csgn_uint_poly_create");
+    if (rc == CSGN_OK) {
+        hipError_t e = hipSuccess;
+        if (csgn::uint_poly_create(p->plan, e) != CSGN_OK)
+            rc = hip_fail(e, "csgn_uint_poly_create");
+    }
+    if (rc != CSGN_OK) {
+        delete p;
+        return rc;
+    }
+    *plan = p;
+    return CSGN_OK;
+}
+
+uint64_t csgn_uint_poly_plan_terms(const csgn_uint_poly_plan *plan, uint64_t x)
+{
+    return plan && x < plan->plan.n_out ? plan->plan.T[x] : 0;
+}
+
+void csgn_uint_poly_destroy(csgn_uint_poly_plan *plan)
+{
+    if (!plan)
+        return;
+    csgn::uint_poly_free(plan->plan);
+    delete plan;
+}
+
+int csgn_uint_poly(const csgn_uint_poly_plan *plan, uint64_t n_bits, uint64_t batch, const uint64_t *const *h_in,
+                   uint64_t *const *h_out, void *stream)
+{
+    if (int rc = check_n(n_bits))
+        return rc;
+    REQUIRE(h_in && h_out, "null host pointer");
+    if (!plan) {                      /* no plan exists without a device: say so before calling the pointer null */
+        if (int rc = require_device("csgn_uint_poly"))
+            return rc;
+        return fail(CSGN_ERR_INVALID, "plan is null");
+    }
+    const csgn::PolyPlan &p = plan->plan;
+    if (int rc = check_poly_sizes(p, n_bits, batch))
+        return rc;
+    if (int rc = check_planes(h_in, nullptr, p.n_in, "input plane"))
+        return rc;
+    if (int rc = check_planes((const uint64_t *const *)h_out, nullptr, p.n_out, "output"))
+        return rc;
+    if (int rc = require_device("csgn_uint_poly"))
+        return rc;
+    if (batch == 0)
+        return CSGN_OK;
+    HIP_TRY(csgn::uint_poly(p, n_bits, batch, (const u64 *const *)h_in, (u64 *const *)h_out, S(stream)));
+    return CSGN_OK;
+}
+
 /* ------------------------------------------------ one-bit batches decrypted into one word per element ---- */
 
 const char *csgn_uint_decrypt_kernel(uint64_t n_bits, uint64_t batch, uint64_t n_planes, const uint64_t *h_terms)

@@ -1,7 +1,7 @@
 // csgn_device.h -- helpers shared by the kernel translation units (csgn_mul.hip, csgn_add.hip, csgn_decrypt.hip,
 // csgn_encrypt.hip, csgn_permute.hip, csgn_compact.hip, csgn_harness.hip, and the uniform-batch families
 // csgn_gates.hip, csgn_uint.hip, csgn_uint_plain.hip, csgn_uint_addk.hip, csgn_uint_lut.hip, csgn_uint_read.hip,
-// csgn_uint_find.hip, csgn_uint_first.hip, csgn_uint_nth.hip, csgn_uint_lt_select.hip, csgn_uint_decrypt.hip, csgn_matmul.hip, csgn_count.hip, csgn_count_prefix.hip, csgn_uint_add_where.hip, csgn_uint_linear.hip, csgn_uint_plain_sum.hip, csgn_uint_bilinear.hip, csgn_wsum.hip, csgn_gather.hip):
+// csgn_uint_find.hip, csgn_uint_first.hip, csgn_uint_nth.hip, csgn_uint_lt_select.hip, csgn_uint_decrypt.hip, csgn_matmul.hip, csgn_count.hip, csgn_count_prefix.hip, csgn_uint_add_where.hip, csgn_uint_linear.hip, csgn_uint_plain_sum.hip, csgn_uint_bilinear.hip, csgn_uint_poly.hip, csgn_wsum.hip, csgn_gather.hip):
 // 16-/8-byte unit access and the choice between them, the ONE and ZERO terms' units, FastDiv tables in kernel
 // arguments, the XCD-contiguous block order, CSR pair search, the LDS subset tables of DESIGN §4.15 (csgn_selector.h
 // builds the skeleton of the read, find and lt_select kernels on them), launch limits,

@@ -415,6 +415,50 @@ void uint_bilinear_launches(const BilinearPlan &pl, u64 n_bits, u64 batch, u64 *
 hipError_t uint_bilinear(const BilinearPlan &pl, u64 n_bits, u64 batch, const u64 *const *a, const u64 *const *b,
                          u64 *const *out, hipStream_t stream);
 
+// a public polynomial over F2 of encrypted planes (csgn_uint_poly.hip), include/csgn_hip.h's definition: output plane x
+// is the left-nested sum of its monomials, mfirst[x] <= m < mfirst[x + 1], each the left-nested product of 1 to 8
+// input planes, then ONE where bit x of `constant` is set; a plane of no monomial is the one-term constant.  A plan
+// holds the shape and, on the device, the plane tables and one 16-byte record per monomial; it lives in a
+// csgn_uint_poly_plan object of the caller's.
+constexpr u32 kPolyMaxIn = 256;
+constexpr u32 kPolyMaxOut = 64;
+constexpr u32 kPolyMaxDegree = 8;
+constexpr u64 kPolyMaxMonomials = 262144;
+struct PolyPlan {
+    u32 n_in = 0, n_out = 0;
+    bool teq = false;                   // every input plane has tin[0] terms, below 2^31
+    bool eq = false;                    // teq, and every monomial has degree `deg`, tin[0]^deg below 2^31: the monomial by division
+    u32 deg = 0;
+    u64 constant = 0;
+    u64 tin[kPolyMaxIn] = {};           // terms per element of the input planes
+    u64 T[kPolyMaxOut] = {};            // terms per element of output plane x
+    u32 mfirst[kPolyMaxOut + 1] = {};
+    std::vector<u32> rec;               // per monomial, four words: its first term in its plane, its degree, its
+                                        // factors one byte each (the first factor in the low byte of word 2)
+    void *d_tab = nullptr;
+};
+// T of one plane whose monomial m has the factors factor[mfirst[m] .. mfirst[m + 1] - 1]; 0: n_in outside 1..256, a
+// null array, a plane of 0 terms, a degree outside 1..8, a factor at or past n_in, a constant_bit other than 0 / 1 or
+// 2^62 terms or more
+u64 uint_poly_terms(u64 n_in, const u64 *terms, u64 n_monomials, const u64 *mfirst, const u64 *factor, int constant_bit);
+// the monomial and the factors' term indices (8 values, 0 past the degree) of term q of one plane (monomial
+// n_monomials: ONE, n_monomials + 1: ZERO); false: refused, q past the plane, more than kPolyMaxMonomials monomials or
+// a plane of 2^31 terms or more
+bool uint_poly_decode(u64 n_in, const u64 *terms, u64 n_monomials, const u64 *mfirst, const u64 *factor, int constant_bit,
+                      u64 q, u64 *monomial, u64 *factor_terms);
+// the shape of a plan (host only): CSGN_ERR_INVALID, else CSGN_ERR_UNSUPPORTED past kPolyMaxMonomials monomials or for a
+// plane of 2^31 terms or more
+int uint_poly_shape(u64 n_in, const u64 *terms, u64 n_out, const u64 *first, const u64 *mfirst, const u64 *factor,
+                    u64 constant, PolyPlan &pl);
+int uint_poly_create(PolyPlan &pl, hipError_t &herr);   // uploads the tables (synchronous); CSGN_ERR_HIP
+void uint_poly_free(PolyPlan &pl);
+// plan[14]: unit bytes for 16-byte-aligned pointers, units per element, G, tiles, workgroups per tile, launches under
+// the calling thread's launch_blocks, workgroups of the first launch, plane groups, staged, units a workgroup walks,
+// operand units per element, the LDS budget in bytes, the monomial by division (eq), the factor terms' mode (0: every
+// plane has one term, 1: one shared divisor, 2: a divisor per plane)
+void uint_poly_launches(const PolyPlan &pl, u64 n_bits, u64 batch, u64 *plan);
+hipError_t uint_poly(const PolyPlan &pl, u64 n_bits, u64 batch, const u64 *const *in, u64 *const *out, hipStream_t stream);
+
 // an encrypted integer shifted, rotated or indexed by an encrypted amount (csgn_uint_pick.hip), include/csgn_hip.h's
 // definition: output j is the sum, ascending in r < rows_j, of EQ(index, r) * a_{src(j, r)}; op = CSGN_UINT_PICK_*.
 // index planes: v = 1..16, terms s[k]; source planes: w = 1..64, every one of t terms; rows: EACH's n, else 0.

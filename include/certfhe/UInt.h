@@ -165,6 +165,33 @@
 // not the form's, operands of different counts or contexts, a constant of outWidth() bits or more, or an output past
 // 2^31 words per element.  An empty batch gives empty planes.
 //
+// PUBLIC POLYNOMIAL MAPS OVER F2.  polyMap(operands, f, constant) evaluates the public polynomial f (class
+// F2Polynomial: per output plane a set of monomials, each a set of bits of the operands) on every element and XORs the
+// public constant: a sparse polynomial of mixed degree up to 8 over several integers of 256 bits in all -- SHA-2's
+// Ch(e, f, g) = ef + eg + g and Maj(a, b, c) = ab + ac + bc, Keccak's chi a + c + bc, a Simon round, a full adder's
+// carry, a k-way AND, a & b & ~c, a gfMul plus an affine term, an S-box ANF with few monomials.  No carry exists:
+// csgn_uint_poly's words (include/csgn_hip.h) over the operands' planes concatenated in order,
+//     plane j = ((M_1 + M_2) + ...) + M_m [+ ONE where constant_j = 1],   M = ((p_f1 * p_f2) * ...) * p_fd
+// the monomials of row j ascending by (degree, then the factor list), the factors of a monomial ascending:
+//     form                   terms of a plane over fresh planes        over planes of t terms
+//     ch, maj, chi           3                                         ch 2 t^2 + t, maj 3 t^2, chi 2 t + t^2
+//     andAll of k operands   1                                         t^k
+//     mux                    3                                         2 t^2 + t (s of t terms too)
+//     a monomial of degree d 1                                         t^d: degree 8 of 2-term planes has 256
+// What is PUBLIC cancels before anything runs: a monomial named an even number of times is gone, and a variable named
+// twice inside a monomial is named once (x x = x is an identity of the function; the C ABI would multiply the plane with
+// itself, t^2 terms: the words differ, the value does not).  F2Polynomial::linear(m) has exactly linearMap's words and
+// F2Polynomial::bilinear(f) exactly bilinearMap's.  A row that is exactly one monomial of degree 1 with no constant
+// returns the SAME payload as the source plane; a row of no monomial is the constant batch (ZERO, or ONE under a constant
+// bit); such rows are left out of the call, and if nothing is left nothing is launched.  Uniform planes take ONE plan,
+// cached for the process like the csgn_uint_bilinear plans, and ONE csgn_uint_poly for all other rows (k_uint_poly,
+// DESIGN 4.39); a ragged plane (a compact() result) takes the loop: one concat of all operand planes, then per output
+// plane and per degree d present, ascending, d gather, d - 1 operator* and sumGroups, operator+ between the degree
+// groups, + ONE, with the same words.  polyRoute names the route.  Every size is computed before anything is allocated or
+// launched: std::invalid_argument for widths or counts that are not the form's, operands of different counts or
+// contexts, a constant of outWidth() bits or more, or an output past 2^31 words per element.  An empty batch gives empty
+// planes.
+//
 // RANGES, SETS AND STEP FUNCTIONS OF PUBLIC CONSTANTS.  Over F2 they are sums (operator+, concatenation) of the
 // comparisons above of ONE integer, plus at most one ONE: csgn_uint_plain_sum's words (include/csgn_hip.h).  With
 // P(cmp, k) the words of the comparison of a with the public k (lessThan(a, k) is P(LT, k), ...), top = 2^w - 1:
@@ -658,6 +685,69 @@ class LookupTable {
   private:
     std::shared_ptr<Impl> impl_;
 };
+
+// A public polynomial over F2 of several integers (the block "PUBLIC POLYNOMIAL MAPS OVER F2" above).  The operands
+// have the widths widths() (each 1..64, 256 bits in all); bit i of operand o is the VARIABLE (the sum of the widths
+// before o) + i.  outWidth() rows (1..64); row j is a set of monomials, a monomial a set of variables whose product
+// XORs into output bit j, plus the row's bit of constant().  Host only, no device work.  A row is kept canonical: the
+// variables of a monomial ascending with none twice (x x = x), the monomials ascending by (degree, then the variables),
+// none twice (duplicates cancel over F2 here, where they are public), a monomial of no variable folded into the
+// constant.  std::invalid_argument for widths outside these limits, a variable at or above variables(), a degree above
+// 8, operands of mismatched shapes, and a result past 262144 monomials.
+class F2Polynomial {
+  public:
+    typedef std::vector<unsigned> Monomial;                 // variables
+    typedef std::vector<std::vector<Monomial> > Rows;
+
+  private:
+    Rows rows_;
+    std::vector<unsigned> widths_;
+    uint64_t constant_;
+    F2Polynomial(const Rows &rows, const std::vector<unsigned> &widths, uint64_t constant)
+        : rows_(rows), widths_(widths), constant_(constant) {}
+
+  public:
+    // any order, repetitions allowed: a monomial named an even number of times is gone; an empty monomial is the constant
+    static F2Polynomial fromMonomials(const Rows &rows, const std::vector<unsigned> &widths);
+    static F2Polynomial linear(const F2Matrix &m);          // one operand; linearMap's words
+    static F2Polynomial bilinear(const F2Bilinear &f);      // two operands; bilinearMap's words
+    static F2Polynomial fromLookupTable(const LookupTable &f);   // one operand; the table's ANF, of degree <= 8
+    static F2Polynomial ch(unsigned w);                     // (e, f, g) -> (e & f) ^ (~e & g) = ef + eg + g
+    static F2Polynomial maj(unsigned w);                    // (a, b, c) -> ab + ac + bc
+    static F2Polynomial chi(unsigned w);                    // (x, y, z) -> x ^ (~y & z) = x + z + yz
+    static F2Polynomial andAll(unsigned w, unsigned k);     // the AND of k operands of w bits, 1 <= k <= 8
+    static F2Polynomial mux(unsigned w);                    // (s, x, y) -> s ? x : y, s of one bit
+
+    const std::vector<unsigned> &widths() const { return widths_; }
+    unsigned variables() const;                             // the sum of the widths
+    unsigned outWidth() const { return (unsigned)rows_.size(); }
+    const Rows &rows() const { return rows_; }
+    uint64_t constant() const { return constant_; }
+    uint64_t apply(const std::vector<uint64_t> &operands) const;   // the clear value, the constant included
+    F2Polynomial operator^(const F2Polynomial &rhs) const;  // one shape
+    // the pointwise product, bit j = (*this)_j & rhs_j: monomials multiply, variables merge, duplicates cancel
+    F2Polynomial operator&(const F2Polynomial &rhs) const;
+    // the form after a linear map of each operand: on[o].outWidth() == widths()[o]; the new widths are on[o].inWidth()
+    F2Polynomial compose(const std::vector<F2Matrix> &on) const;
+    bool operator==(const F2Polynomial &rhs) const
+    {
+        return widths_ == rhs.widths_ && rows_ == rhs.rows_ && constant_ == rhs.constant_;
+    }
+};
+// the linear map after the form: m.inWidth() == form.outWidth()
+F2Polynomial operator*(const F2Matrix &m, const F2Polynomial &form);
+
+// element i: f(operands[0][i], operands[1][i], ...) ^ constant, of width f.outWidth(); the operands' widths are
+// f.widths(), constant < 2^outWidth().  Operands may be the same integer.
+UIntBatch polyMap(const std::vector<UIntBatch> &operands, const F2Polynomial &f, uint64_t constant = 0);
+UIntBatch ch(const UIntBatch &e, const UIntBatch &f, const UIntBatch &g);     // one width
+UIntBatch maj(const UIntBatch &a, const UIntBatch &b, const UIntBatch &c);
+UIntBatch chi(const UIntBatch &a, const UIntBatch &b, const UIntBatch &c);    // a ^ (~b & c)
+UIntBatch andAll(const std::vector<UIntBatch> &operands);                     // 1 to 8 operands of one width
+// The route polyMap takes (a static string): "k_uint_poly" (one csgn_uint_poly for every row that is neither a single
+// input bit nor a constant), "loop" (the CiphertextBatch operators: a ragged plane) or "none" (an empty batch, or no row
+// left to compute: nothing is launched).  No class of shapes is routed elsewhere.  No device work.
+const char *polyRoute(const std::vector<UIntBatch> &operands, const F2Polynomial &f, uint64_t constant = 0);
 
 // f(a), a.width() == f.inWidth(); f.outWidth() planes
 UIntBatch lookup(const UIntBatch &a, const LookupTable &f);

@@ -1424,6 +1424,103 @@ void csgn_uint_bilinear_destroy(csgn_uint_bilinear_plan *plan);
 int csgn_uint_bilinear(const csgn_uint_bilinear_plan *plan, uint64_t n_bits, uint64_t batch,
                        const uint64_t *const *h_a, const uint64_t *const *h_b, uint64_t *const *h_out, void *stream);
 
+/* ------------------------------------- a public polynomial over F2 of encrypted planes ---- */
+
+/* csgn_uint_poly: a PUBLIC polynomial over F2 of ENCRYPTED planes, sparse, of mixed degree up to 8, every output plane
+ * in one launch: SHA-2's Ch(e,f,g) = ef + eg + g and Maj(a,b,c) = ab + ac + bc, Keccak's chi a + c + bc, a Simon
+ * round, Trivium and Grain updates, a full adder's carry, a k-way AND, an S-box ANF on wide words.  It covers what lies
+ * between csgn_uint_linear (degree 1), csgn_uint_bilinear (pure degree 2 of two integers) and csgn_uint_lut (dense, at
+ * most 16 input bits).  No carry exists: an output bit is a sum over F2 of products of input bits.
+ * Inputs:
+ *   - n_in uniform input planes (1..256), plane i of h_terms[i] = t_i >= 1 terms per element.  The caller concatenates
+ *     its integers' planes: the ABI knows nothing of operands;
+ *   - n_out output planes (1..64).  The monomials of plane x are h_first[x] .. h_first[x+1] - 1 (h_first[0] = 0,
+ *     h_first non-descending, n_out + 1 values);
+ *   - monomial m has the factors h_factor[h_mfirst[m] .. h_mfirst[m+1] - 1] (h_mfirst[0] = 0, h_first[n_out] + 1
+ *     values), each below n_in; its degree h_mfirst[m+1] - h_mfirst[m] is 1..8;
+ *   - `constant`, whose bit x adds ONE to plane x (a bit at or above n_out: CSGN_ERR_INVALID).
+ * Output plane x is the left-nested sum (the reference's operator+: concatenation) of its monomials in the order given,
+ * followed by + ONE where constant_x = 1; a monomial is the left-nested product (the reference's operator*: every pair
+ * of terms ANDed, the left term slow) of its factors in the order given:
+ *     plane x = ((M_1 + M_2) + ...) + M_m [+ ONE]
+ *     M       = ((p_f1 * p_f2) * ...) * p_fd         prod t_f terms, the first factor's term index slowest
+ *     T_x     = sum over the plane's monomials of prod t_f, + constant_x
+ * A plane with no monomial is the one-term constant: ZERO (zero words) for constant_x = 0, ONE for 1; T_x = 1
+ * (csgn_uint_linear's rule for an empty row).  Input pointers may alias in any way; no output overlaps an input or
+ * another output.  Nothing cancels on the device: a monomial named twice is written twice (and cancels over F2 only at
+ * decryption), and a factor named twice inside a monomial is multiplied with itself, t^2 terms. */
+/* T of ONE plane of n_monomials monomials (host only); monomial m has the factors h_factor[h_mfirst[m] ..
+ * h_mfirst[m+1] - 1], h_mfirst[0] being any offset into h_factor, so a plane of a plan's arrays is h_mfirst +
+ * h_first[x] with the plan's h_factor.  0 for n_in outside 1..256, a null array (h_mfirst and h_factor may be null when
+ * n_monomials = 0), an input plane of 0 terms or 2^62 or more, a degree outside 1..8, a factor at or above n_in, a
+ * constant_bit other than 0 or 1, or a count of 2^62 or more (computed without wrap-around). */
+uint64_t csgn_uint_poly_terms(uint64_t n_in, const uint64_t *h_terms, uint64_t n_monomials, const uint64_t *h_mfirst,
+                              const uint64_t *h_factor, int constant_bit);
+/* The decode by position (host only): term q < T of ONE plane is the AND, over the factors j < degree of monomial
+ * *h_monomial, of term h_factor_terms[j] of that factor's plane (8 values are written, 0 at and past the degree).
+ * *h_monomial = n_monomials means ONE and n_monomials + 1 means ZERO.  It runs the two functions the kernel runs
+ * (poly_monomial: one division where every input plane has one term count and every monomial one degree, else the
+ * search over the monomials' first terms; poly_split: the mixed-radix division; csgn_uint_poly.hip).  Returns 1, or 0
+ * (nothing written) for arguments csgn_uint_poly_terms refuses, more than 262144 monomials, a plane of 2^31 terms or
+ * more, q >= T or a null pointer. */
+int csgn_uint_poly_decode(uint64_t n_in, const uint64_t *h_terms, uint64_t n_monomials, const uint64_t *h_mfirst,
+                          const uint64_t *h_factor, int constant_bit, uint64_t q, uint64_t *h_monomial,
+                          uint64_t h_factor_terms[8]);
+/* How a call of this shape is cut under the calling thread's knob "launch_blocks" (host only, no device work).  The
+ * grid, the tiles, the chunks and the cut into launches are csgn_uint_bilinear_launches', figure for figure:
+ *     h_plan[0]   bytes of the unit one lane writes when every pointer is 16-byte aligned: 16 for an even number of
+ *                 words per term, else 8 (a call with a pointer off alignment takes 8-byte units)
+ *     h_plan[1]   units per element over all output planes
+ *     h_plan[2]   G, the elements per tile.  Staged: as many as h_plan[11] bytes hold the operand units of (h_plan[10]
+ *                 units an element); else (262144 / units per element); at least 1, at most `batch`, and no more than
+ *                 keep a tile within 2^31 units
+ *     h_plan[3]   tiles = ceil(batch / G) (0 for batch == 0)
+ *     h_plan[4]   S, the workgroups per tile: (G * units per element / least), at least 1, where a workgroup walks at
+ *                 `least` 2048 units and, staged, 4 times the units it stages (G * h_plan[10]); summed over the plane
+ *                 groups
+ *     h_plan[5]   launches (0 for batch == 0): max(1, launch_blocks / S) tiles each, cut at whole tiles only
+ *     h_plan[6]   workgroups of the first launch (0 for batch == 0)
+ *     h_plan[7]   plane groups: 1, unless ONE element of all planes passes 2^31 units; G is then 1 and the planes go in
+ *                 that many runs of consecutive planes, each a stream and a launch sequence of its own
+ *     h_plan[8]   1 when the shape is STAGED: one element's operand units fit h_plan[11] bytes and the form writes at
+ *                 least twice the units it reads; every workgroup then copies its tile's operand units to LDS once
+ *     h_plan[9]   chunk, the units a workgroup walks: G * units per element in S even parts, rounded up to a multiple
+ *                 of 256 (of the first plane group)
+ *     h_plan[10]  operand units per element: (sum of t_i) * units per term
+ *     h_plan[11]  the LDS budget for operand units, in bytes
+ *     h_plan[12]  1 when a lane finds its monomial by one division: every input plane has one term count t, every
+ *                 monomial of the plan one degree d, and t^d is below 2^31; else by the search
+ *     h_plan[13]  how a lane finds the factors' term indices: 0 nothing is divided (every t_i = 1), 1 one shared
+ *                 divisor (every t_i equal), 2 the planes' divisors from the plan
+ * The same checks as csgn_uint_poly_create, in its order, then h_plan, then the sizes of csgn_uint_poly. */
+int csgn_uint_poly_launches(uint64_t n_bits, uint64_t batch, uint64_t n_in, const uint64_t *h_terms, uint64_t n_out,
+                            const uint64_t *h_first, const uint64_t *h_mfirst, const uint64_t *h_factor,
+                            uint64_t constant, uint64_t h_plan[14]);
+/* The plan of one shape: the planes' term counts and divisors and one 16-byte record per monomial, uploaded once,
+ * synchronously.  Checks, in this order: `plan`; n_in; n_out and the constant; h_terms and h_first, h_first[0] = 0 and
+ * non-descending, h_mfirst and h_factor where there is a monomial (CSGN_ERR_INVALID); more than 262144 monomials
+ * (CSGN_ERR_UNSUPPORTED); the input planes' term counts, h_mfirst[0] = 0, every degree and every factor, the term
+ * counts of the output planes (CSGN_ERR_INVALID); an output plane of 2^31 terms per element or more
+ * (CSGN_ERR_UNSUPPORTED); the device (CSGN_ERR_NO_DEVICE, no CPU fallback).  Release with csgn_uint_poly_destroy (null
+ * is ignored).  A plan is immutable: any number of threads and streams may launch from it. */
+typedef struct csgn_uint_poly_plan csgn_uint_poly_plan;
+int csgn_uint_poly_create(uint64_t n_in, const uint64_t *h_terms, uint64_t n_out, const uint64_t *h_first,
+                          const uint64_t *h_mfirst, const uint64_t *h_factor, uint64_t constant,
+                          csgn_uint_poly_plan **plan);
+/* T_x of plane x of the plan; 0 for a null plan or x >= n_out */
+uint64_t csgn_uint_poly_plan_terms(const csgn_uint_poly_plan *plan, uint64_t x);
+void csgn_uint_poly_destroy(csgn_uint_poly_plan *plan);
+/* The operation over `batch` elements.  h_in and h_out are HOST arrays of n_in / n_out device pointers: input plane i
+ * takes batch * t_i * dL words and output x batch * T_x * dL words.  Checks, in this order: n_bits; the host arrays; the
+ * plan (a null plan is CSGN_ERR_NO_DEVICE where there is no device -- no plan exists there -- and CSGN_ERR_INVALID
+ * otherwise); every t_i * dL and T_x * dL below 2^31 words per element and batch times that below 2^60
+ * (CSGN_ERR_UNSUPPORTED); null device pointers, the inputs, then the outputs (CSGN_ERR_INVALID); the device
+ * (CSGN_ERR_NO_DEVICE, no CPU fallback).  batch == 0 succeeds.  On the caller's stream, asynchronous and
+ * graph-capturable: k_uint_poly, one launch for every shape csgn_uint_poly_launches gives one; no scratch,
+ * no allocation, no synchronisation. */
+int csgn_uint_poly(const csgn_uint_poly_plan *plan, uint64_t n_bits, uint64_t batch, const uint64_t *const *h_in,
+                   uint64_t *const *h_out, void *stream);
+
 /* ------------------------------------- one-bit batches decrypted into one word per element ---- */
 
 /* n_planes one-bit batches of `batch` elements decrypted in ONE pass into one 64-bit word per element: what
